@@ -4,6 +4,7 @@
 -> word collation -> pause split) on batches of 30 s synthetic 16 kHz clips.
 
     python bench.py --gpus 1 --steps K --warmup W          (N=1)
+    python bench.py ... --dump-outputs DIR                 (+ the last timed step's results as DIR/*.npy: dump_outputs)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 One "step" = one pass of the whole path over one batch of B x 30 s clips per GPU (weak scaling: every
@@ -29,7 +30,7 @@ import numpy as np  # noqa: E402
 PMC_FILE = "r06_pmc_traffic_B8.json"     # latest committed PMC pass (tools/ab/run_gpu_pmc.sh + profiles/summarize_pmc.py)
 
 
-def parse():
+def parse(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=3)
@@ -65,7 +66,55 @@ def parse():
                     help="independent engine contexts per GPU, each with its own batch of --batch chunks, driven by "
                          "host threads (the decode step is latency-bound, so a second batch fills idle CUs); "
                          "default 1 = the BASELINE configuration")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (rank 0; see dump_outputs)")
+    a = ap.parse_args(argv)
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
+    if a.warmup < 0:
+        ap.error("--warmup must not be negative")
+    return a
+
+
+DUMP_BYTES_MAX = 64 << 20
+
+
+def dump_outputs(path, records, local_outs, pad_token_id, max_bytes=DUMP_BYTES_MAX):
+    """Write the last timed step's results as float32 / float64 .npy files under `path`, one row per chunk, rows in chunk order:
+    chunk_index [N] (the chunk's seed), word_counts [N], word_timestamps [N, W, 2] (start, end in s, after the pause split; NaN
+    pad), word_text_utf8 [N, T] (the words' UTF-8 joined by 0x00; -1 pad), sequences [N, L] (generated token ids; pad_token_id
+    pad) and token_timestamps [N, L] (s; NaN pad).  `records` = the gathered word records of every rank; `local_outs` = chunk
+    index -> (token ids, token timestamps) of this rank's chunks (rows of other ranks' chunks stay NaN in the last two).
+    Over `max_bytes` in all, a fixed seeded sample of the rows is written."""
+    from crisperwhisper_amd import dist
+    recs = sorted((dist.unpack_words(r) for r in records), key=lambda r: r[0])
+    n = len(recs)
+    n_words = max((len(w) for _, w in recs), default=0)
+    blobs = [b"\x00".join(w_["text"].encode("utf-8") for w_ in w) for _, w in recs]
+    n_len = max((max(len(t), len(s)) for t, s in local_outs.values()), default=0)
+    arrays = {"chunk_index": np.array([i for i, _ in recs], dtype=np.float64),
+              "word_counts": np.array([len(w) for _, w in recs], dtype=np.float64),
+              "word_timestamps": np.full((n, n_words, 2), np.nan, dtype=np.float64),
+              "word_text_utf8": np.full((n, max((len(b) for b in blobs), default=0)), -1.0, dtype=np.float32),
+              "sequences": np.full((n, n_len), np.nan, dtype=np.float64),
+              "token_timestamps": np.full((n, n_len), np.nan, dtype=np.float32)}
+    for row, ((idx, words), blob) in enumerate(zip(recs, blobs)):
+        if words:
+            arrays["word_timestamps"][row, :len(words)] = [w_["timestamp"] for w_ in words]
+        arrays["word_text_utf8"][row, :len(blob)] = np.frombuffer(blob, dtype=np.uint8)
+        if idx in local_outs:
+            toks, ts = local_outs[idx]
+            arrays["sequences"][row] = pad_token_id
+            arrays["sequences"][row, :len(toks)] = toks
+            arrays["token_timestamps"][row, :len(ts)] = ts
+    total = sum(x.nbytes for x in arrays.values())
+    if total > max_bytes:
+        keep = np.sort(np.random.default_rng(0).choice(n, max(1, n * max_bytes // total), replace=False))
+        arrays = {k: x[keep] for k, x in arrays.items()}
+    os.makedirs(path, exist_ok=True)
+    for k, x in arrays.items():
+        np.save(os.path.join(path, f"{k}.npy"), x)
+    return arrays
 
 
 def cpu_baseline(g, v, spec, weights, n_tok_gpu, words_per_chunk, cpu_tokens):
@@ -453,12 +502,14 @@ def main():
     audio_s = 30.0 * B * C
 
     last_raw = {}                                     # rank-local words of the latest step (before the pause split)
+    last_out = {}                                     # the latest step's generate() result per context, and the gathered records
 
     def step_ctx(ci):
         eng, nf = engines[ci], nfs[ci]
         eng.mel_resident(B)
         out = generation.generate(eng, B, nf, language="<|en|>", task="transcribe", max_new_tokens=a.tokens,
                                   min_new_tokens=a.tokens, num_beams=a.num_beams)
+        last_out[ci] = out
         # every chunk is an independent clip here, so each rank collates + pause-splits its own chunks and the
         # ranks exchange the per-chunk *word lists* (one small all-gather); rank 0 ends up with all results
         recs = []
@@ -485,6 +536,7 @@ def main():
         recs = [r for p_ in parts for r in p_[0]]
         n_tokens = sum(p_[1] for p_ in parts)
         allr = shard.all_gather_records(np.stack(recs), B * C)
+        last_out["records"] = allr
         n_words = 0
         if rank == 0:
             for r in allr:
@@ -513,6 +565,11 @@ def main():
         tokens += t
     fence()
     dt = time.perf_counter() - t0
+    if a.dump_outputs and rank == 0:
+        local = {(rank * C + ci) * B + k: (last_out[ci]["sequences"][k], last_out[ci]["token_timestamps"][k])
+                 for ci in range(C) for k in range(B)}
+        dump_outputs(a.dump_outputs, last_out["records"], local, spec.pad_token_id)
+
     def max_over_ranks(x):
         if pg is None:
             return x

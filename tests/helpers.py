@@ -3,6 +3,10 @@ from __future__ import annotations
 
 import json
 import os
+import subprocess
+import sys
+import tempfile
+import xml.etree.ElementTree as ET
 
 import numpy as np
 
@@ -155,6 +159,81 @@ def has_experiments() -> bool:
     switches") and the differential tests that hold them correct are available."""
     from crisperwhisper_amd import _native
     return bool(_native.load().cw_has_experiments())
+
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+EXPERIMENTS_LIB = os.path.join(ROOT, "crisperwhisper_amd", "libcw_experiments.so")
+
+
+def experiments_env() -> dict:
+    """Environment of a process that loads the A/B build of the library (`make EXTRA=-DCW_EXPERIMENTS`, built next to the
+    product library by __graft_entry__.build(); built here when it is missing, like the product library in conftest.py)."""
+    if not os.path.exists(EXPERIMENTS_LIB):
+        subprocess.check_call(["make", "-s", "-j8", "-C", os.path.join(ROOT, "crisperwhisper_amd", "csrc"), "EXTRA=-DCW_EXPERIMENTS",
+                               "BUILD=build_experiments", f"OUT={EXPERIMENTS_LIB}"])
+    return {"CW_LIB_PATH": EXPERIMENTS_LIB}
+
+
+_CHILD_RESULTS = {}
+
+
+def run_in_child(request, env: dict, selects, timeout=900) -> None:
+    """Run the calling test case in a child pytest process whose environment differs by `env` (value None: variable removed):
+    what the case needs is fixed once per process -- the A/B build of the library (experiments_env) or a kernel choice read from
+    the environment at the first launch.  Every case of the same test function that `selects(params)` picks and this session
+    runs goes to the same child, started once and never again; the case fails with the child's report unless it passed there.
+    A child that hangs (time limit), dies by a signal (abort, segmentation fault) or is interrupted ends the whole session:
+    nothing more is started on a device that may be faulted."""
+    import pytest
+    if os.environ.get("CW_TEST_CHILD"):
+        pytest.fail(f"the child process for {request.node.name} does not provide what the case needs ({env})")
+    node = request.node
+    key = (node.module.__name__, node.originalname, tuple(sorted(env.items())))
+    if key not in _CHILD_RESULTS:
+        rootdir = str(request.config.rootpath)            # node ids are relative to it
+        ids = [it.nodeid for it in request.session.items
+               if getattr(it, "module", None) is node.module and getattr(it, "originalname", None) == node.originalname
+               and selects(it.callspec.params)]
+        child_env = dict(os.environ, CW_TEST_CHILD="1")
+        for k, v in env.items():
+            if v is None:
+                child_env.pop(k, None)
+            else:
+                child_env[k] = v
+        _CHILD_RESULTS[key] = ({}, "child started, no result")     # recorded first: whatever happens, it is not started again
+        fatal = None
+        with tempfile.TemporaryDirectory() as tmp:
+            xml = os.path.join(tmp, "child.xml")
+            cmd = [sys.executable] + (["-s"] if sys.flags.no_user_site else []) + [
+                "-m", "pytest", "-q", "-p", "no:cacheprovider", f"--rootdir={rootdir}", f"--junitxml={xml}", *ids]
+            try:
+                p = subprocess.run(cmd, cwd=rootdir, env=child_env, capture_output=True, text=True, timeout=timeout)
+            except subprocess.TimeoutExpired as e:
+                fatal = f"child pytest for {node.originalname} exceeded {timeout} s and was killed\n{(e.stdout or '')[-3000:]}"
+            except BaseException as e:                    # e.g. the parent's own per-test time limit: the child is killed with it
+                fatal = f"child pytest for {node.originalname} interrupted: {e!r}"
+            if fatal is None:
+                tail = f"child rc={p.returncode}\n{p.stdout[-3000:]}\n{p.stderr[-2000:]}"
+                if p.returncode < 0 or p.returncode > 5:  # not a pytest exit status: killed by a signal (abort, segfault, ...)
+                    fatal = f"child pytest for {node.originalname} died: {tail}"
+                else:
+                    results = {}
+                    if os.path.exists(xml):
+                        for tc in ET.parse(xml).iter("testcase"):
+                            outcome, msg = "passed", ""
+                            for tag in ("failure", "error", "skipped"):
+                                el = tc.find(tag)
+                                if el is not None and outcome == "passed":
+                                    outcome, msg = tag, f"{el.get('message') or ''}\n{el.text or ''}"
+                            results[tc.get("name")] = (outcome, msg)
+                    _CHILD_RESULTS[key] = (results, tail)
+        if fatal is not None:
+            _CHILD_RESULTS[key] = ({}, fatal)
+            pytest.exit(f"{node.name}: {fatal[-4000:]}\nstopping the session: nothing more runs on a device that may be faulted",
+                        returncode=1)
+    results, tail = _CHILD_RESULTS[key]
+    outcome, msg = results.get(node.name, ("not run", tail))
+    assert outcome == "passed", f"{node.name} in the child process ({env}): {outcome}\n{msg[-4000:]}"
 
 
 def e4m3_round(x):

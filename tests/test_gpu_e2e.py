@@ -329,15 +329,15 @@ def test_native_seek_loop_equals_host_loop(tiny, eng_f32, language, task, kw):
 
 
 @pytest.mark.parametrize("skinny_mode", [0, 1, 2])
-def test_large_batch_decode_matches_small_batch_path(skinny_mode):
+def test_large_batch_decode_matches_small_batch_path(request, skinny_mode):
     """Decode batches of 17..64 rows take the one-weight-pass GEMV (prep + multi-tile kernel, gemm.hip); batches of
     <= 16 rows the latency kernel.  Same engine, same 20 windows, large-v3 shapes (K-split atomics, combine, 51866
     logits): teacher-forced logits of the two paths agree to bf16 rounding and pick the same tokens.
     skinny_mode 0 (default): the round-3 path.  1: cross-attention query through K-split planes finished inside the one-block-per-(row, head)
     cross-attention, which writes the out-projection's rows; 2: every LayerNorm projection through
     csrc/skinny.hip planes + finish launch.  Modes 1 and 2 were measured slower in the step and live in -DCW_EXPERIMENTS builds."""
-    if skinny_mode and not Hh.has_experiments():
-        pytest.skip("A/B kernel variants: library built without -DCW_EXPERIMENTS")
+    if skinny_mode and not Hh.has_experiments():     # A/B kernel variants: -DCW_EXPERIMENTS builds
+        return Hh.run_in_child(request, Hh.experiments_env(), lambda p: p["skinny_mode"] != 0)
     g, v = syn.large_v3_geometry()
     g.enc_layers = g.dec_layers = 2
     spec = syn.model_spec(g, v, n_align=15)
@@ -1391,7 +1391,7 @@ def test_combining_out_projection_in_row_groups_is_bit_identical(dt, rows):
 @pytest.mark.parametrize("feature,rows,dt", [("qkv_self", 8, "bf16"), ("qkv_self", 8, "f16"), ("qkv_self", 5, "bf16"), ("qkv_self", 1, "bf16"),
                                              ("declayer", 8, "bf16"), ("declayer", 8, "f16"), ("declayer", 3, "bf16"),
                                              ("mlp_chain", 8, "bf16"), ("mlp_chain", 8, "f16"), ("mlp_chain", 5, "bf16"), ("mlp_chain", 1, "bf16")])
-def test_persistent_decoder_layer_is_bit_identical(feature, rows, dt):
+def test_persistent_decoder_layer_is_bit_identical(request, feature, rows, dt):
     """csrc/declayer.hip: decoder stages that hand their results across CUs INSIDE a launch as 8-byte {tag, value} granules.
     qkv_self: LayerNorm + q/k/v projection + self-attention in one launch (default) against CW_NO_QKV_SELF=1 (two launches);
     declayer: fused out-projection / cross-query stage + cross-attention in one persistent launch (CW_DECLAYER=1, one 1024-thread
@@ -1404,7 +1404,8 @@ def test_persistent_decoder_layer_is_bit_identical(feature, rows, dt):
     bits here, not words."""
     import os
     if feature in ("declayer", "mlp_chain") and not Hh.has_experiments():
-        pytest.skip("measured-slower persistent stage: compiled into -DCW_EXPERIMENTS builds only (profiles/r05_declayer_phases.txt, r05_mlp_chain_phases.txt)")
+        # measured-slower persistent stage: compiled into -DCW_EXPERIMENTS builds only (profiles/r05_declayer_phases.txt, r05_mlp_chain_phases.txt)
+        return Hh.run_in_child(request, Hh.experiments_env(), lambda p: p["feature"] in ("declayer", "mlp_chain"))
     g, v = syn.large_v3_geometry()
     g.enc_layers, g.dec_layers = 1, 4
     spec = syn.model_spec(g, v, n_align=15)
@@ -1668,13 +1669,13 @@ def test_fused_decoder_stage_on_rows_with_a_large_mean():
 
 
 @pytest.mark.parametrize("rows", [17, 40, 64])
-def test_rows_path_without_preparation_launches_tracks_prepared_path(rows):
+def test_rows_path_without_preparation_launches_tracks_prepared_path(request, rows):
     """csrc/decfuse.hip gemv_rows_kernel: 17..64 decoder rows (beam search, batch 64) with the LayerNorm applied through its
     linearity on the consumer's output and whole-column residual GEMVs (9 launches per layer) against the same engine with a
     preparation launch in front of every GEMV and K-split atomics (`rows_ln` = 0, 12 launches), large-v3 shapes on a 2+2-layer
     stack, teacher-forced: logits within bf16 rounding of each other, same tokens, alignment rows within 2e-2."""
-    if not Hh.has_experiments():
-        pytest.skip("A/B kernel variant (measured slower, DESIGN.md 6d): library built without -DCW_EXPERIMENTS")
+    if not Hh.has_experiments():                     # A/B kernel variant (measured slower, DESIGN.md 6d): -DCW_EXPERIMENTS builds
+        return Hh.run_in_child(request, Hh.experiments_env(), lambda p: True)
     g, v = syn.large_v3_geometry()
     g.enc_layers = g.dec_layers = 2
     spec = syn.model_spec(g, v, n_align=15)

@@ -122,14 +122,14 @@ def test_gemm_fp8_exact_on_representable_inputs_and_quantisation_model_otherwise
 @pytest.mark.parametrize("sched", ["pingpong", "8phase", "w128"])
 @pytest.mark.parametrize("M,N,K", [(256, 256, 64), (300, 256, 128), (513, 768, 192), (2000, 512, 5120), (3333, 1280, 1280), (1500, 3840, 1280),
                                    (777, 512, 256), (12000, 1280, 320)])
-def test_gemm_pingpong_schedule_is_bit_identical_to_lockstep(engines, M, N, K, sched):
+def test_gemm_pingpong_schedule_is_bit_identical_to_lockstep(request, engines, M, N, K, sched):
     """The staggered 256-tile GEMM schedules -- ping-pong (two wave groups half a K-tile apart, LDS-DMA two tiles ahead) and
     the quarter-tile "8-phase" one (half-tile DMA every phase, counted vmcnt, round 3) -- accumulate in exactly the order of the
     lockstep kernel: same bits, run after run (a half tile overwritten early or read late shows up here), for 1, 2, 3, 4, 5, 20
     and 80 K-tiles, with and without an M-edge tile, also with every CU holding a block (12000 rows).  "w128" (round 4): four
     waves of 128 x 128 per block, self-pipelined in half steps of 32 MFMAs (csrc/gemm_w128.hip)."""
-    if sched in ("w128", "pingpong") and not Hh.has_experiments():
-        pytest.skip("superseded / rejected GEMM schedules live in -DCW_EXPERIMENTS builds")
+    if sched in ("w128", "pingpong") and not Hh.has_experiments():   # superseded / rejected schedules: -DCW_EXPERIMENTS builds
+        return Hh.run_in_child(request, Hh.experiments_env(), lambda p: p["sched"] in ("w128", "pingpong"))
     eng = engines["bf16"]
     rng = np.random.default_rng(M + N + K)
     A = rng.standard_normal((M, K)).astype(np.float32)
@@ -185,13 +185,13 @@ def _ln_plain(x):
 @pytest.mark.parametrize("dt,tol", [("bf16", 2e-2), ("f16", 2.5e-3)])
 @pytest.mark.parametrize("Mb,N,K,nks", [(17, 384, 128, 0), (20, 128, 512, 4), (33, 256, 256, 2), (40, 1280, 1280, 0), (48, 3840, 1280, 10),
                                          (64, 5120, 1280, 0), (64, 1280, 5120, 16), (64, 1280, 1280, 5), (25, 80, 64, 1), (64, 176, 1280, 8)])
-def test_skinny_projections_17_to_64_rows(engines, dt, tol, Mb, N, K, nks):
+def test_skinny_projections_17_to_64_rows(request, engines, dt, tol, Mb, N, K, nks):
     """Decoder projections of the 17..64-row path (csrc/skinny.hip) against float64: LayerNorm by linearity through K-split
     planes + finish (plain and GELU epilogues) and the residual projection by grid atomics, every supported K split shape,
     ragged row counts, column counts that leave waves / lanes without a tile.  The rows carry a mean 40x their spread (a
     kernel that rounded x to 16 bits before removing the mean loses those 5 bits) and every other row an outlier channel."""
-    if not Hh.has_experiments():
-        pytest.skip("csrc/skinny.hip is an A/B build (measured slower in the step): library built without -DCW_EXPERIMENTS")
+    if not Hh.has_experiments():   # csrc/skinny.hip is an A/B build (measured slower in the step): -DCW_EXPERIMENTS builds
+        return Hh.run_in_child(request, Hh.experiments_env(), lambda p: True)
     rng = np.random.default_rng(Mb * 13 + N + K)
     x = (rng.standard_normal((Mb, K)) * 0.5 + rng.uniform(-20, 20, (Mb, 1))).astype(np.float32)
     x[1::2, 7] *= 30.0
@@ -246,11 +246,12 @@ def test_encoder_attention(engines, dt, tol, B, H, S):
 def test_cross_attention_decode_kernels(engines, dt, tol, B, H, S, kv_div, path):
     """Key-split cross-attention of the decode step: the matrix-core kernel the 16-bit engines use for 2..16 hypotheses per
     K/V and the 8-lane-group kernel (one row per K/V; f32 engine; CW_CROSS_VALU) against float64 softmax attention on the same
-    16-bit K/V.  The query stays f32: the matrix-core kernel carries it (and the probabilities) as three 16-bit halves, so
+    16-bit K/V.  The f32 engine has no matrix-core kernel: with either setting it runs the 8-lane-group kernel, kv_div rows per
+    block for 2..6 rows per K/V, one row per block above that (K/V of row b at b / kv_div) -- its "mfma" cases are checked
+    against float64 and must be bit-identical to a launch with the switch on.  The query stays f32: the
+    matrix-core kernel carries it (and the probabilities) as three 16-bit halves, so
     both kernels are held to an f32 tolerance (5e-6), not a 16-bit one.  S = 50: splits with 9 keys, seven of the eight waves of a block without a key."""
     from crisperwhisper_amd import _native
-    if dt == "f32" and (path == "mfma" or kv_div > 6):
-        pytest.skip("the f32 engine has the 8-lane-group kernel only")
     if path == "valu" and kv_div > 6:
         pytest.skip("8-lane-group kernel: up to 6 rows per K/V")
     rng = np.random.default_rng(B * 1000 + S + kv_div)
@@ -272,24 +273,31 @@ def test_cross_attention_decode_kernels(engines, dt, tol, B, H, S, kv_div, path)
         lib.cw_test_set_option(b"cross_valu", 0)
     assert rel_err(got, ref) < tol, (dt, path, rel_err(got, ref))
     assert np.abs(al - p[:, H - 1]).max() < tol, (dt, path, np.abs(al - p[:, H - 1]).max())
+    if dt == "f32" and path == "mfma":               # the f32 engine's kernel selection does not depend on the switch
+        assert lib.cw_test_set_option(b"cross_valu", 1) == 0
+        try:
+            got1, al1 = engines[dt].test_cross_attention(q, k, v, kv_div=kv_div, align_head=H - 1)
+        finally:
+            lib.cw_test_set_option(b"cross_valu", 0)
+        assert np.array_equal(got1, got) and np.array_equal(al1, al)
 
 
 @pytest.mark.parametrize("dt", ["bf16", "f16"])
 @pytest.mark.parametrize("path", ["mfma8", "valu"])
 @pytest.mark.parametrize("B,H,S,kv_div", [(4, 2, 1500, 1), (10, 3, 1500, 5), (3, 2, 750, 1), (2, 2, 50, 1), (6, 1, 1499, 2)])
-def test_cross_attention_over_the_e4m3_cache(engines, dt, path, B, H, S, kv_div):
+def test_cross_attention_over_the_e4m3_cache(request, engines, dt, path, B, H, S, kv_div):
     """Opt-in e4m3 cross-attention cache: quantiser (one scale per (item, head, K|V), amax / 448) + the cross-attention kernel
     over it, against float64 softmax attention on the DEQUANTISED cache -- i.e. the kernels add nothing beyond the quantisation
     they are specified to do.  mfma8: v_mfma_f32_16x16x32_fp8_fp8 with the query and the probabilities carried as three e4m3 terms
     (12 significant bits: tolerance 2e-4 on outputs and alignment probabilities), V read in the fragment-major order the
-    quantiser writes; valu (CW_CROSS8_VALU=1 in the process, else skipped): conversions + f32 FMAs, f32 tolerance.  Column-
+    quantiser writes; valu (CW_CROSS8_VALU=1 in the process): conversions + f32 FMAs, f32 tolerance.  Column-
     dependent V scale: a transposed or permuted V fragment cannot pass; S = 50: splits of 9 keys, seven waves without a key;
-    kv_div: beam rows sharing one cache."""
+    kv_div: beam rows sharing one cache.  The kernel is chosen once per process: cases of the other kernel run in a child process."""
     import os
     from crisperwhisper_amd import _native
     valu_proc = bool(os.environ.get("CW_CROSS8_VALU"))
-    if (path == "valu") != valu_proc:
-        pytest.skip("the e4m3 kernel / cache layout is chosen once per process (CW_CROSS8_VALU)")
+    if (path == "valu") != valu_proc:        # the e4m3 kernel / cache layout is chosen once per process (CW_CROSS8_VALU)
+        return Hh.run_in_child(request, {"CW_CROSS8_VALU": "1" if path == "valu" else None}, lambda p: p["path"] == path)
     rng = np.random.default_rng(B * 1000 + S + kv_div + 7)
     q = (rng.standard_normal((B, H, 64)) * 0.35).astype(np.float32)
     k = rng.standard_normal((B // kv_div, H, S, 64)).astype(np.float32)

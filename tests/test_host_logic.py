@@ -476,3 +476,45 @@ def test_bench_longform_parity_measure_and_goldens_describe_the_bench_workload()
     assert bench.load_beam_goldens(64, "aligned", 5) == {} and bench.load_beam_goldens(128, "aligned", 3) == {}
     greedy = bench.load_bench_goldens(128, "aligned")
     assert sorted(greedy) == list(range(64))
+
+
+def test_bench_steps_and_dump_outputs(tmp_path):
+    """bench.py: --steps / --warmup are taken as given (at least one timed step); --dump-outputs writes the last timed step's
+    results -- gathered word records of every rank, this rank's tokens -- as float32 / float64 arrays in chunk order, the same
+    bytes for the same results, and a fixed seeded sample of the rows when the arrays would exceed the size bound."""
+    import bench
+    a = bench.parse(["--gpus", "1", "--steps", "7", "--warmup", "2", "--dump-outputs", str(tmp_path / "d")])
+    assert (a.steps, a.warmup, a.dump_outputs) == (7, 2, str(tmp_path / "d"))
+    assert bench.parse([]).dump_outputs is None
+    for bad in (["--steps", "0"], ["--warmup", "-1"]):
+        with pytest.raises(SystemExit):
+            bench.parse(bad)
+    words = {3: [{"text": " héllo", "timestamp": (0.5, 1.25)}, {"text": " x", "timestamp": (1.25, 2.0)}], 1: [],
+             2: [{"text": " y", "timestamp": (0.0, 0.5)}]}
+    records = [dist.pack_words(i, words[i]) for i in (3, 1, 2)]          # gathered order need not be chunk order
+    local = {1: (np.array([50, 51, 7, 7]), np.array([0.0, 0.5], np.float32)),
+             3: (np.array([50, 52, 53, 7]), np.array([0.0, 0.5, 1.0, 1.5], np.float32))}   # chunk 2 was decoded on another rank
+    out = bench.dump_outputs(str(tmp_path / "d"), records, local, pad_token_id=7)
+    files = {f[:-4]: np.load(tmp_path / "d" / f) for f in os.listdir(tmp_path / "d")}
+    assert sorted(files) == sorted(out) == ["chunk_index", "sequences", "token_timestamps", "word_counts", "word_text_utf8",
+                                            "word_timestamps"]
+    assert all(x.dtype in (np.float32, np.float64) for x in files.values())
+    assert files["chunk_index"].tolist() == [1, 2, 3] and files["word_counts"].tolist() == [0, 1, 2]
+    assert files["word_timestamps"].shape == (3, 2, 2) and files["word_timestamps"][2].tolist() == [[0.5, 1.25], [1.25, 2.0]]
+    assert np.isnan(files["word_timestamps"][0]).all() and np.isnan(files["word_timestamps"][1, 1]).all()
+    t = files["word_text_utf8"][2]
+    assert bytes(t[t >= 0].astype(np.uint8)).decode("utf-8") == " héllo\x00 x" and (files["word_text_utf8"][0] == -1).all()
+    assert files["sequences"][0].tolist() == [50, 51, 7, 7] and files["sequences"][2].tolist() == [50, 52, 53, 7]
+    assert np.isnan(files["sequences"][1]).all() and np.isnan(files["token_timestamps"][1]).all()
+    assert files["token_timestamps"][0, :2].tolist() == [0.0, 0.5] and np.isnan(files["token_timestamps"][0, 2:]).all()
+    again = bench.dump_outputs(str(tmp_path / "e"), records, local, pad_token_id=7)
+    assert all((tmp_path / "d" / f"{k}.npy").read_bytes() == (tmp_path / "e" / f"{k}.npy").read_bytes() for k in again)
+    many = [dist.pack_words(i, [{"text": " w", "timestamp": (0.0, 1.0)}] * (i % 5)) for i in range(200)]
+    full = bench.dump_outputs(str(tmp_path / "f"), many, {}, pad_token_id=7)
+    total = sum(x.nbytes for x in full.values())
+    small = bench.dump_outputs(str(tmp_path / "g"), many, {}, pad_token_id=7, max_bytes=total // 4)
+    assert sum(x.nbytes for x in small.values()) <= total // 4 and 0 < len(small["chunk_index"]) < 200
+    assert small["chunk_index"].tolist() == sorted(small["chunk_index"].tolist())
+    assert np.array_equal(small["word_counts"], small["chunk_index"] % 5)
+    redo = bench.dump_outputs(str(tmp_path / "h"), many, {}, pad_token_id=7, max_bytes=total // 4)
+    assert np.array_equal(redo["chunk_index"], small["chunk_index"])
