@@ -198,6 +198,13 @@ struct cw_ctx {
     hipEvent_t ev_step[2] = {nullptr, nullptr};
     // cw_time_decode_stage: one launch (stage_sel) of one layer (layer_sel) of decode_step; -1 = everything (the step itself)
     int stage_sel = -1, layer_sel = -1, stage_count = 0;
+    // decoder prompt prefill (prefill.hip): on by default on the 16-bit engines; cw_set_option "prompt_prefill" = 0 forces the
+    // per-position loop (A/B).  Work buffers for rows x positions, grown on demand and freed by cw_destroy.
+    bool prompt_prefill = true;
+    int pf_prefix = 0;                 // prompt_ids in front of the init tokens of the coming decoder inputs ("prompt_prefix")
+    size_t pf_rows = 0;
+    float* pf_x = nullptr;
+    void *pf_a = nullptr, *pf_q = nullptr, *pf_o = nullptr, *pf_h = nullptr;
     int stage_kind[CW_MAX_DEC_STAGES] = {};
     int stage_launches[CW_MAX_DEC_STAGES] = {};   // kernel launches behind each stage (2 where gemv_prep_kernel precedes gemv_mt_kernel)
     float stage_ms[CW_N_STAGES] = {};
@@ -657,6 +664,7 @@ void cw_destroy(cw_ctx* c) {
     for (auto& f : c->folds) hipFree(f.stage);
     for (auto& o : c->out_stages) hipFree(o.stage);
     for (void* p : c->allocs) hipFree(p);
+    for (void* p : {(void*)c->pf_x, c->pf_a, c->pf_q, c->pf_o, c->pf_h}) if (p) hipFree(p);
     if (c->h_nunf) hipHostFree(c->h_nunf);
     if (c->ev0) hipEventDestroy(c->ev0);
     if (c->ev1) hipEventDestroy(c->ev1);
@@ -1579,6 +1587,67 @@ static int epoch_hygiene(cw_ctx* c, long long upcoming_forwards) {
     return CW_OK;
 }
 
+// ---- decoder prompt prefill: one multi-token forward over the n_prompt - 1 forward-only input positions of every row
+// (prefill.hip).  Engages only for a decoder input that carries prompt_ids (cw_set_option "prompt_prefix" = their count, which
+// cw_transcribe_prompted sets itself), on the 16-bit engines with the 16-bit cross cache and packed, LN-folded decoder weights;
+// every other call keeps the per-position loop.  It writes the self-attention K/V cache rows 0 .. n_prompt-2 of every layer --
+// the state the loop leaves; the prompt's logits and alignment rows are never read.
+static bool prefill_engages(const cw_ctx* c, int n_prompt) {
+    return c->pf_prefix > 0 && n_prompt > c->pf_prefix && c->prompt_prefill && c->bf16 && c->d.d_model == 64 * c->d.n_heads && !c->kv8 && c->wpacked && c->ln_folded && c->layer_sel < 0;
+}
+
+static int prefill_reserve(cw_ctx* c, size_t M) {
+    if (M <= c->pf_rows) return CW_OK;
+    const int D = c->d.d_model, F = c->d.ffn_dim;
+    HIPCHK(c, hipStreamSynchronize(c->st));
+    for (void** p : {(void**)&c->pf_x, &c->pf_a, &c->pf_q, &c->pf_o, &c->pf_h}) if (*p) { hipFree(*p); *p = nullptr; }
+    c->pf_rows = 0;
+    const size_t bytes[5] = {M * D * 4, M * D * 2, M * D * 2, M * D * 2, M * F * 2};
+    void** dst[5] = {(void**)&c->pf_x, &c->pf_a, &c->pf_q, &c->pf_o, &c->pf_h};
+    for (int i = 0; i < 5; ++i) {
+        hipError_t e = hipMalloc(dst[i], bytes[i]);
+        if (e != hipSuccess) return fail(c, CW_ERR_NOMEM, "prefill: hipMalloc(%zu) failed: %s", bytes[i], hipGetErrorString(e));
+    }
+    c->pf_rows = M;
+    return CW_OK;
+}
+
+// rows decoder rows (ids in d_ids [rows][TGT]), cross K/V row = row / kv_div.  Launches per layer: 3 LayerNorms, 6 GEMMs, 2
+// attentions (the last layer: LayerNorm + q/k/v only -- its output feeds nothing the loop keeps).
+static int run_prefill(cw_ctx* c, int rows, int n_prompt, int kv_div) {
+    const int D = c->d.d_model, F = c->d.ffn_dim, H = c->d.n_heads, TGT = c->d.max_target_positions;
+    const int n_pos = n_prompt - 1;
+    const int M = rows * n_pos;
+    CWCHK(c, prefill_reserve(c, (size_t)M));
+    CWCHK(c, KD(c, cw_launch_prefill_embed, c->d_ids, TGT, n_pos, c->embed, c->dec_pos, c->pf_x, M, D, c->st));
+    const int NL = c->d.dec_layers;
+    for (int l = 0; l < NL; ++l) {
+        LayerW& L = c->dec[l];
+        PrefillEpi ep;
+        memset(&ep, 0, sizeof(ep));
+        CWCHK(c, KD(c, cw_launch_prefill_ln, c->pf_x, c->pf_a, M, D, c->st));
+        ep.mode = PF_QKV; ep.bias = L.bqkv; ep.out = c->pf_q; ep.sk = L.sk; ep.sv = L.sv; ep.D = D; ep.H = H; ep.cap = TGT; ep.n_pos = n_pos;
+        CWCHK(c, KD(c, cw_launch_prefill_gemm, c->pf_a, L.wqkv, ep, M, 3 * D, D, c->st));
+        if (l + 1 == NL) break;
+        CWCHK(c, KD(c, cw_launch_prefill_attn, c->pf_q, L.sk, L.sv, c->pf_o, rows, n_pos, H, TGT, n_pos, 1, 1, c->st));
+        memset(&ep, 0, sizeof(ep));
+        ep.mode = PF_RESID; ep.bias = L.bo; ep.x = c->pf_x;
+        CWCHK(c, KD(c, cw_launch_prefill_gemm, c->pf_o, L.wo, ep, M, D, D, c->st));
+        CWCHK(c, KD(c, cw_launch_prefill_ln, c->pf_x, c->pf_a, M, D, c->st));
+        ep.mode = PF_STORE; ep.bias = L.bq_c; ep.out = c->pf_q; ep.x = nullptr;
+        CWCHK(c, KD(c, cw_launch_prefill_gemm, c->pf_a, L.wq_c, ep, M, D, D, c->st));
+        CWCHK(c, KD(c, cw_launch_prefill_attn, c->pf_q, L.ck, L.cv, c->pf_o, rows, n_pos, H, CW_N_CTX, CW_N_CTX, 0, kv_div, c->st));
+        ep.mode = PF_RESID; ep.bias = L.bo_c; ep.out = nullptr; ep.x = c->pf_x;
+        CWCHK(c, KD(c, cw_launch_prefill_gemm, c->pf_o, L.wo_c, ep, M, D, D, c->st));
+        CWCHK(c, KD(c, cw_launch_prefill_ln, c->pf_x, c->pf_a, M, D, c->st));
+        ep.mode = PF_GELU; ep.bias = L.b1; ep.out = c->pf_h; ep.x = nullptr;
+        CWCHK(c, KD(c, cw_launch_prefill_gemm, c->pf_a, L.w1, ep, M, F, D, c->st));
+        ep.mode = PF_RESID; ep.bias = L.b2; ep.out = nullptr; ep.x = c->pf_x;
+        CWCHK(c, KD(c, cw_launch_prefill_gemm, c->pf_h, L.w2, ep, M, D, F, c->st));
+    }
+    return CW_OK;
+}
+
 static int decode_once(cw_ctx* c, int32_t nb, const int32_t* prompt, int32_t n_prompt, int32_t max_length,
                        int32_t min_new_tokens, const int32_t* forced, int32_t* sequences, int32_t* lengths,
                        int32_t* argmax_out);
@@ -1622,8 +1691,10 @@ static int decode_once(cw_ctx* c, int32_t nb, const int32_t* prompt, int32_t n_p
     HIPCHK(c, hipStreamSynchronize(c->st));
     StageTimer tm(c, CW_STAGE_DECODE);
 
-    // prompt positions 0 .. n_prompt-2: forward only (their alignment rows are recorded, :254-256)
-    for (int pos = 0; pos + 1 < n_prompt; ++pos) {
+    // prompt positions 0 .. n_prompt-2: forward only (their alignment rows are recorded, :254-256) -- one prefill when the input
+    // carries prompt_ids
+    if (prefill_engages(c, n_prompt)) CWCHK(c, run_prefill(c, nb, n_prompt, 1));
+    else for (int pos = 0; pos + 1 < n_prompt; ++pos) {
         c->hist_short = pos + 1 <= 64;
         CWCHK(c, KD(c, cw_launch_set_pos, c->d_pos, pos, nb, c->st, c->d_epoch));
         CWCHK(c, KD(c, cw_launch_embed, c->d_ids, TGT, pos, c->embed, c->bf16 ? 1 : 0, c->dec_pos, c->dx, nb, D, c->st));
@@ -1864,7 +1935,8 @@ int32_t cw_beam_begin(cw_ctx* c, int32_t n_items, int32_t num_beams, const int32
     c->beam_K = num_beams; c->beam_items = n_items; c->beam_n_prompt = n_prompt;
     c->beam_pos = n_prompt - 1; c->beam_max_len = max_length;
     c->align_cur = c->d_align;
-    for (int pos = 0; pos + 1 < n_prompt; ++pos) {          // prompt positions: forward only
+    if (prefill_engages(c, n_prompt)) CWCHK(c, run_prefill(c, rows, n_prompt, num_beams));
+    else for (int pos = 0; pos + 1 < n_prompt; ++pos) {     // prompt positions: forward only
         CWCHK(c, KD(c, cw_launch_set_pos, c->d_pos, pos, rows, c->st));
         CWCHK(c, KD(c, cw_launch_embed, c->d_ids, TGT, pos, c->embed, c->bf16 ? 1 : 0, c->dec_pos, c->dx, rows, D, c->st));
         c->hist_short = pos + 1 <= 64;
@@ -2023,9 +2095,25 @@ int32_t cw_token_timestamps(cw_ctx* c, int32_t nb, int32_t L, int32_t n_prompt, 
 // ------------------------------------------------------------------------------------------------
 int32_t cw_transcribe(cw_ctx* c, int32_t B, const int32_t* num_frames, const cw_transcribe_cfg* cfg, int32_t* tokens,
                       float* token_ts, int32_t* lens, int32_t cap, int32_t* n_passes) {
+    return cw_transcribe_prompted(c, B, num_frames, cfg, nullptr, 0, tokens, token_ts, lens, cap, n_passes);
+}
+
+int32_t cw_transcribe_prompted(cw_ctx* c, int32_t B, const int32_t* num_frames, const cw_transcribe_cfg* cfg,
+                               const int32_t* prefix, int32_t n_prefix, int32_t* tokens, float* token_ts, int32_t* lens,
+                               int32_t cap, int32_t* n_passes) {
+    struct PrefixScope {                     // the decode calls of this seek loop carry n_prefix prompt_ids
+        cw_ctx* c; int saved;
+        ~PrefixScope() { c->pf_prefix = saved; }
+    } scope{c, c->pf_prefix};
+    c->pf_prefix = n_prefix > 0 ? n_prefix : 0;
     const int TGT = c->d.max_target_positions, V = c->d.vocab_size;
     if (B < 1 || B > c->Bm) return fail(c, CW_ERR_INVALID, "B=%d out of range (max_batch %d)", B, c->Bm);
     if (!c->gen_set) return fail(c, CW_ERR_STATE, "cw_set_generation not called");
+    if (n_prefix < 0 || (n_prefix > 0 && !prefix)) return fail(c, CW_ERR_INVALID, "prefix: n_prefix=%d", n_prefix);
+    for (int k = 0; k < n_prefix; ++k)
+        if (prefix[k] < 0 || prefix[k] >= V) return fail(c, CW_ERR_INVALID, "prefix token %d out of range", prefix[k]);
+    if (n_prefix > 0 && (!isnan(c->logprob_thr) || !isnan(c->no_speech_thr)))
+        return fail(c, CW_ERR_INVALID, "a decoder prompt prefix together with logprob / no-speech thresholds is not implemented");
     const int tb = c->gen.no_timestamps_token_id + 1;
     const int eos = c->gen.eos_token_id, pad = c->gen.pad_token_id;
     std::vector<std::vector<int>> prompts(B);
@@ -2056,10 +2144,23 @@ int32_t cw_transcribe(cw_ctx* c, int32_t B, const int32_t* num_frames, const cw_
         }
         pre_encoded = true;
     }
+    // prompt_ids (generation_whisper.py:1909-1913): the prefix goes in front of every window's init tokens, after detection
+    if (n_prefix > 0)
+        for (int i = 0; i < B; ++i) prompts[i].insert(prompts[i].begin(), prefix, prefix + n_prefix);
     const int n_prompt = (int)prompts[0].size();
     int max_new = cfg->max_new_tokens;
-    if (max_new >= 0 && max_new + n_prompt > TGT) max_new = TGT - n_prompt;            // :1937-1942
-    const int max_length = max_new >= 0 ? n_prompt + max_new : (cfg->max_length < TGT ? cfg->max_length : TGT);
+    int max_length;
+    if (n_prefix > 0) {                                                                // _set_max_new_tokens_and_length
+        if ((max_new > 0 ? max_new : 0) + n_prompt > TGT)                              // :1920-1930
+            return fail(c, CW_ERR_INVALID, "decoder input of %d tokens + max_new_tokens %d exceeds max_target_positions %d",
+                        n_prompt, max_new, TGT);
+        const int n_init = n_prompt < TGT / 2 - 1 ? n_prompt : TGT / 2 - 1;             // :1932-1946
+        max_length = max_new >= 0 ? n_prompt + max_new : (cfg->max_length + n_init < TGT ? cfg->max_length + n_init : TGT);
+    } else {
+        if (max_new >= 0 && max_new + n_prompt > TGT) max_new = TGT - n_prompt;        // :1937-1942
+        max_length = max_new >= 0 ? n_prompt + max_new : (cfg->max_length < TGT ? cfg->max_length : TGT);
+    }
+    if (max_length <= n_prompt) return fail(c, CW_ERR_INVALID, "max_length %d leaves no room after %d decoder input tokens", max_length, n_prompt);
     std::vector<long> seek(B, 0);
     std::vector<std::vector<int>> out_tok(B);
     std::vector<std::vector<float>> out_ts(B);
@@ -2321,6 +2422,15 @@ static int enc8_quantise(cw_ctx* c) {
 
 int32_t cw_set_option(cw_ctx* c, const char* name, int32_t value) {
     if (!name) return fail(c, CW_ERR_INVALID, "cw_set_option: null option name");
+    if (!strcmp(name, "prompt_prefix")) {    // the coming decoder inputs start with this many prompt_ids (0: none)
+        if (value < 0 || value >= c->d.max_target_positions) return fail(c, CW_ERR_INVALID, "prompt_prefix=%d out of range", value);
+        c->pf_prefix = value;
+        return CW_OK;
+    }
+    if (!strcmp(name, "prompt_prefill")) {   // 0: prompt positions through the per-position decoder step (A/B of the prefill)
+        c->prompt_prefill = value != 0;
+        return CW_OK;
+    }
     if (!strcmp(name, "cross_kv_fp8")) {
         if (!value) { c->kv8 = false; return CW_OK; }
         if (!c->bf16) return fail(c, CW_ERR_INVALID, "cross_kv_fp8 needs the bf16 engine (the f32 engine is the parity mode)");
@@ -2446,6 +2556,63 @@ int32_t cw_test_gemm(cw_ctx* c, int32_t M, int32_t N, int32_t K, const float* A,
     }
     if (r == CW_OK) r = download_T(c, dO, 0, out, (size_t)M * N);
     hipFree(dA); hipFree(dW); hipFree(dO); hipFree(dB);
+    return r;
+}
+
+// Prefill kernels against a host reference (prefill.hip).  cw_test_prefill_gemm: A [M][K] and W [N][K] are rounded to the engine's
+// 16-bit type, W is packed fragment-major (wfrag_pack_kernel) and prefill_gemm_kernel runs with epilogue `mode`: 0 = store,
+// 2 = f32 residual (out holds the residual on entry and resid + A W^T + bias on return), 3 = erf GELU; 16-bit outputs are returned
+// as f32.  16-bit engines; K % 32 == 0, N % 16 == 0.
+int32_t cw_test_prefill_gemm(cw_ctx* c, int32_t mode, int32_t M, int32_t N, int32_t K, const float* A, const float* W,
+                             const float* bias, float* out) {
+    if (!c->bf16) return fail(c, CW_ERR_INVALID, "test_prefill_gemm: 16-bit engines only");
+    if ((mode != PF_STORE && mode != PF_RESID && mode != PF_GELU) || M < 1 || N < 16 || N % 16 || K < 32 || K % 32)
+        return fail(c, CW_ERR_INVALID, "test_prefill_gemm: bad arguments");
+    void *dA = nullptr, *dW = nullptr, *dWp = nullptr, *dO = nullptr; float* dB = nullptr;
+    const size_t e = c->esz;
+    int r = CW_OK;
+    if (hipMalloc(&dA, (size_t)M * K * e) != hipSuccess || hipMalloc(&dW, (size_t)N * K * e) != hipSuccess ||
+        hipMalloc(&dWp, KD(c, cw_wfrag_elems, N, K) * e) != hipSuccess || hipMalloc(&dO, (size_t)M * N * 4) != hipSuccess ||
+        hipMalloc((void**)&dB, (size_t)N * 4) != hipSuccess) r = fail(c, CW_ERR_NOMEM, "test_prefill_gemm: hipMalloc failed");
+    if (r == CW_OK) r = upload_T(c, dA, 0, A, (size_t)M * K);
+    if (r == CW_OK) r = upload_T(c, dW, 0, W, (size_t)N * K);
+    if (r == CW_OK && bias && hipMemcpy(dB, bias, (size_t)N * 4, hipMemcpyHostToDevice) != hipSuccess) r = fail(c, CW_ERR_HIP, "test_prefill_gemm: copy");
+    if (r == CW_OK && mode == PF_RESID && hipMemcpy(dO, out, (size_t)M * N * 4, hipMemcpyHostToDevice) != hipSuccess) r = fail(c, CW_ERR_HIP, "test_prefill_gemm: copy");
+    if (r == CW_OK) r = KD(c, cw_launch_wfrag_pack, dW, N, K, dWp, c->st);
+    PrefillEpi ep;
+    memset(&ep, 0, sizeof(ep));
+    ep.mode = mode; ep.bias = bias ? dB : nullptr;
+    if (mode == PF_RESID) ep.x = (float*)dO; else ep.out = dO;
+    if (r == CW_OK) r = KD(c, cw_launch_prefill_gemm, dA, dWp, ep, M, N, K, c->st);
+    if (r == CW_OK) { hipError_t er = hipStreamSynchronize(c->st); if (er != hipSuccess) r = fail(c, CW_ERR_HIP, "test_prefill_gemm: %s", hipGetErrorString(er)); }
+    if (r == CW_OK) {
+        if (mode == PF_RESID) { if (hipMemcpy(out, dO, (size_t)M * N * 4, hipMemcpyDeviceToHost) != hipSuccess) r = fail(c, CW_ERR_HIP, "test_prefill_gemm: copy"); }
+        else r = download_T(c, dO, 0, out, (size_t)M * N);
+    }
+    hipFree(dA); hipFree(dW); hipFree(dWp); hipFree(dO); hipFree(dB);
+    return r;
+}
+
+// cw_test_prefill_attention: q [rows * n_q][H * 64], k / v [rows / kv_div][H][cap][64] (f32, rounded to the 16-bit type) ->
+// out [rows * n_q][H * 64]: softmax(q k^T) v over keys 0 .. n_keys-1 (causal: keys 0 .. i for query position i; n_keys >= n_q),
+// cross K/V row = row / kv_div.  No scale is applied (the engine folds 1/8 into the query projections).
+int32_t cw_test_prefill_attention(cw_ctx* c, int32_t rows, int32_t n_q, int32_t H, int32_t cap, int32_t n_keys, int32_t causal,
+                                  int32_t kv_div, const float* q, const float* k, const float* v, float* out) {
+    if (!c->bf16) return fail(c, CW_ERR_INVALID, "test_prefill_attention: 16-bit engines only");
+    if (rows < 1 || n_q < 1 || H < 1 || cap < 1 || n_keys < 1 || n_keys > cap || kv_div < 1 || rows % kv_div || (causal && n_keys < n_q))
+        return fail(c, CW_ERR_INVALID, "test_prefill_attention: bad arguments");
+    const size_t e = c->esz, nq = (size_t)rows * n_q * H * 64, nkv = (size_t)(rows / kv_div) * H * cap * 64;
+    void *dQ = nullptr, *dK = nullptr, *dV = nullptr, *dO = nullptr;
+    int r = CW_OK;
+    if (hipMalloc(&dQ, nq * e) != hipSuccess || hipMalloc(&dK, nkv * e) != hipSuccess || hipMalloc(&dV, nkv * e) != hipSuccess ||
+        hipMalloc(&dO, nq * e) != hipSuccess) r = fail(c, CW_ERR_NOMEM, "test_prefill_attention: hipMalloc failed");
+    if (r == CW_OK) r = upload_T(c, dQ, 0, q, nq);
+    if (r == CW_OK) r = upload_T(c, dK, 0, k, nkv);
+    if (r == CW_OK) r = upload_T(c, dV, 0, v, nkv);
+    if (r == CW_OK) r = KD(c, cw_launch_prefill_attn, dQ, dK, dV, dO, rows, n_q, H, cap, n_keys, causal ? 1 : 0, kv_div, c->st);
+    if (r == CW_OK) { hipError_t er = hipStreamSynchronize(c->st); if (er != hipSuccess) r = fail(c, CW_ERR_HIP, "test_prefill_attention: %s", hipGetErrorString(er)); }
+    if (r == CW_OK) r = download_T(c, dO, 0, out, nq);
+    hipFree(dQ); hipFree(dK); hipFree(dV); hipFree(dO);
     return r;
 }
 

@@ -317,6 +317,17 @@ struct MelTables {
 // ---- launchers of the dtype-dependent translation units (gemm / attention / elementwise / mel .hip), compiled twice:
 // namespace cw_bf16 (bfloat16 build) and cw_f16 (-DCW_F16, IEEE binary16); `bool bf16` = "16-bit engine" in both, false
 // selects the f32 parity kernels (identical in the two builds).
+// prefill.hip: decoder prompt prefill (16-bit engines)
+enum PrefillMode { PF_STORE = 0, PF_QKV = 1, PF_RESID = 2, PF_GELU = 3 };
+struct PrefillEpi {
+    int mode;              // PrefillMode
+    const float* bias;     // [N] or null
+    void* out;             // PF_STORE / PF_GELU: 16-bit [M][N]; PF_QKV: q as 16-bit [M][D]
+    float* x;              // PF_RESID: f32 residual [M][N], += acc + bias
+    void* sk; void* sv;    // PF_QKV: self cache [rows][H][cap][64]; row = m / n_pos, position = m % n_pos
+    int D, H, cap, n_pos;
+};
+
 #define CW_DTYPE_KERNEL_DECLS \
     int cw_launch_gemm(bool bf16, int epi, const AParams& ap, const void* W, int M, int N, int K, const EpiParams& ep, hipStream_t st); \
     void cw_gemm_set_256_min_tiles(int n); \
@@ -368,6 +379,10 @@ struct MelTables {
     int cw_launch_align_gather(const float* align, const int* row_of_pos, int n_items, int n_align, int align_rows, int L, int n_keys, float* out, hipStream_t st); \
     int cw_launch_set_pos(int* pos, int value, int B, hipStream_t st, unsigned int* epoch = nullptr); \
     int cw_launch_embed(const int* ids, int ids_stride, int t, const void* embed, int embed_bf16, const float* pos_embed, float* x_out, int B, int d, hipStream_t st); \
+    int cw_launch_prefill_embed(const int* ids, int ids_stride, int n_pos, const void* embed, const float* pos_embed, float* x, int M, int D, hipStream_t st); \
+    int cw_launch_prefill_ln(const float* x, void* out, int M, int D, hipStream_t st); \
+    int cw_launch_prefill_gemm(const void* A, const void* W, const PrefillEpi& ep, int M, int N, int K, hipStream_t st); \
+    int cw_launch_prefill_attn(const void* Q, const void* K, const void* V, void* out, int rows, int n_q, int H, int cap, int n_keys, int causal, int kv_div, hipStream_t st); \
     int cw_launch_attn_encoder(bool bf16, const void* Q, const void* K, const void* V, void* out, int B, int H, int S, int S_pad, hipStream_t st); \
     int cw_launch_attn_decode(bool bf16, const DecAttnParams& p, hipStream_t st); \
     int cw_launch_attn_cross_split(bool bf16, const CrossSplitParams& p, hipStream_t st); \

@@ -264,10 +264,13 @@ class Engine:
         return out
 
     def transcribe(self, nb: int, num_frames, *, sot: int, language_token: int = -1, task_token: int = -1,
-                   max_new_tokens: int = -1, min_new_tokens: int = 0, max_length: int = 448, lang_ids=None):
+                   max_new_tokens: int = -1, min_new_tokens: int = 0, max_length: int = 448, lang_ids=None, prefix=None):
         """Native seek loop (cw_transcribe) over the nb resident feature items: returns (tokens, timestamps, passes),
-        the per-item concatenated segment tokens (int64) and absolute token timestamps (float32)."""
+        the per-item concatenated segment tokens (int64) and absolute token timestamps (float32).  ``prefix``: decoder
+        prompt ids (``prompt_ids``, starting with <|startofprev|>) put in front of every window's init tokens
+        (cw_transcribe_prompted)."""
         nf = _i32(num_frames)
+        pre = _i32(prefix if prefix is not None else [])
         lids = _i32(lang_ids if lang_ids is not None else [])
         cfg = N.TranscribeCfg(sot, language_token, task_token, max_new_tokens, min_new_tokens, max_length,
                               lids.ctypes.data_as(C.POINTER(C.c_int32)), len(lids))
@@ -280,8 +283,12 @@ class Engine:
             ts = np.zeros((nb, cap), dtype=np.float32)
             lens = np.zeros(nb, dtype=np.int32)
             passes = C.c_int32(0)
-            rc = self.lib.cw_transcribe(self.ctx, nb, _ptr(nf), C.byref(cfg), _ptr(toks), _ptr(ts), _ptr(lens), cap,
-                                        C.byref(passes))
+            if len(pre):
+                rc = self.lib.cw_transcribe_prompted(self.ctx, nb, _ptr(nf), C.byref(cfg), _ptr(pre), len(pre), _ptr(toks),
+                                                     _ptr(ts), _ptr(lens), cap, C.byref(passes))
+            else:
+                rc = self.lib.cw_transcribe(self.ctx, nb, _ptr(nf), C.byref(cfg), _ptr(toks), _ptr(ts), _ptr(lens), cap,
+                                            C.byref(passes))
             if rc != 0 and b"capacity" in (self.lib.cw_last_error(self.ctx) or b"") and cap < (1 << 20):
                 cap *= 4
                 continue
@@ -385,6 +392,35 @@ class Engine:
         B, H, S, _ = q.shape
         out = np.zeros((B, S, H * 64), np.float32)
         self._chk(self.lib.cw_test_attention(self.ctx, B, H, S, _ptr(q), _ptr(k), _ptr(v), _ptr(out)))
+        return out
+
+    def set_prompt_prefix(self, n: int):
+        """cw_set_option "prompt_prefix": the coming decode / beam_begin inputs start with n prompt_ids (0: none) -- what lets
+        the prefill engage; cw_transcribe_prompted sets it itself."""
+        self._chk(self.lib.cw_set_option(self.ctx, b"prompt_prefix", int(n)))
+
+    def set_prompt_prefill(self, on: bool):
+        """cw_set_option "prompt_prefill": 0 runs the prompt positions of a prompt_ids call through the per-position step."""
+        self._chk(self.lib.cw_set_option(self.ctx, b"prompt_prefill", 1 if on else 0))
+
+    def test_prefill_gemm(self, mode, A, W, bias=None, resid=None):
+        """cw_test_prefill_gemm: mode 0 store / 2 residual (returns resid + A W^T + bias) / 3 GELU, W [N][K] packed on device."""
+        A, W = (np.ascontiguousarray(t, np.float32) for t in (A, W))
+        M, K = A.shape
+        N = W.shape[0]
+        out = (np.ascontiguousarray(resid, np.float32).copy() if resid is not None else np.zeros((M, N), np.float32))
+        b = None if bias is None else np.ascontiguousarray(bias, np.float32)
+        self._chk(self.lib.cw_test_prefill_gemm(self.ctx, int(mode), M, N, K, _ptr(A), _ptr(W), _ptr(b), _ptr(out)))
+        return out
+
+    def test_prefill_attention(self, q, k, v, n_keys, causal, kv_div=1):
+        """cw_test_prefill_attention: q [rows][n_q][H*64], k / v [rows / kv_div][H][cap][64] -> [rows][n_q][H*64]."""
+        q, k, v = (np.ascontiguousarray(t, np.float32) for t in (q, k, v))
+        rows, n_q, D = q.shape
+        H, cap = k.shape[1], k.shape[2]
+        out = np.zeros_like(q)
+        self._chk(self.lib.cw_test_prefill_attention(self.ctx, rows, n_q, H, cap, int(n_keys), 1 if causal else 0, int(kv_div),
+                                                     _ptr(q), _ptr(k), _ptr(v), _ptr(out)))
         return out
 
     def test_cross_attention(self, q, k, v, kv_div=1, align_head=0):

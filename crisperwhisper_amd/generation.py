@@ -116,15 +116,67 @@ def resolve_prompt(spec, language: Optional[str], task: Optional[str]):
     return head + rest, detect
 
 
-def init_tokens(spec, language: Optional[str], task: Optional[str], lang_id: Optional[int] = None) -> List[int]:
+def init_tokens(spec, language: Optional[str], task: Optional[str], lang_id: Optional[int] = None,
+                prompt_ids=None) -> List[int]:
     """<|startoftranscript|><|lang|><|task|> (no <|notimestamps|>: return_timestamps=True); ``lang_id`` fills the
-    language slot when it has to be detected."""
+    language slot when it has to be detected.  ``prompt_ids`` (``processor.get_prompt_ids(text)``: <|startofprev|> p1 .. pk)
+    go in front: the decoder input of generation_whisper.py:1909-1913."""
     toks, detect = resolve_prompt(spec, language, task)
     if detect:
         if lang_id is None:
             raise ValueError("language is None and no detected language id was supplied")
         toks = [toks[0], int(lang_id)] + toks[2:]
-    return [int(t) for t in toks]
+    pre = [] if prompt_ids is None else [int(t) for t in check_prompt_ids(spec, prompt_ids)]
+    return pre + [int(t) for t in toks]
+
+
+def check_prompt_ids(spec, prompt_ids) -> np.ndarray:
+    """``prompt_ids`` as generate accepts them -- a 1-D integer list, numpy array or torch tensor of token ids in [0, vocab)
+    -- as an int64 array; anything else raises."""
+    if hasattr(prompt_ids, "detach") and hasattr(prompt_ids, "cpu"):      # torch.Tensor
+        prompt_ids = prompt_ids.detach().cpu().numpy()
+    if not isinstance(prompt_ids, (list, tuple, np.ndarray)):
+        raise ValueError(f"prompt_ids must be a 1-D list, numpy array or torch tensor of token ids, got {type(prompt_ids).__name__}")
+    if isinstance(prompt_ids, (list, tuple)) and not all(isinstance(t, (int, np.integer)) and not isinstance(t, bool)
+                                                         for t in prompt_ids):
+        raise ValueError("prompt_ids must hold integer token ids")
+    a = np.asarray(prompt_ids)
+    if a.ndim != 1 or a.size == 0:
+        raise ValueError(f"prompt_ids must be a non-empty 1-D sequence of token ids (shape {a.shape})")
+    if not np.issubdtype(a.dtype, np.integer):
+        raise ValueError(f"prompt_ids must hold integer token ids (dtype {a.dtype})")
+    if int(a.min()) < 0 or int(a.max()) >= spec.vocab_size:
+        raise ValueError(f"prompt_ids must lie in [0, {spec.vocab_size}) (got {int(a.min())} .. {int(a.max())})")
+    return a.astype(np.int64)
+
+
+def check_prompt_length(spec, n_input: int, max_new_tokens: Optional[int]) -> None:
+    """The length check of ``_set_max_new_tokens_and_length`` (generation_whisper.py:1920-1930) for a decoder input of
+    ``n_input`` ids (prompt + init tokens)."""
+    m = max_new_tokens if max_new_tokens is not None else 0
+    tgt = spec.max_target_positions
+    if m + n_input > tgt:
+        raise ValueError(
+            f"The length of `decoder_input_ids`, including special start tokens, prompt tokens, and previous tokens, is {n_input}, "
+            f" and `max_new_tokens` is {m}. Thus, the combined length of "
+            f"`decoder_input_ids` and `max_new_tokens` is: {m + n_input}. This exceeds the "
+            f"`max_target_positions` of the Whisper model: {tgt}. "
+            "You should either reduce the length of your prompt, or reduce the value of `max_new_tokens`, "
+            f"so that their combined length is less than {tgt}.")
+
+
+def prompted_max_length(spec, n_input: int, max_new_tokens: Optional[int]) -> int:
+    """max_length of a generate call whose decoder input (``n_input`` ids) carries prompt_ids (:1932-1946)."""
+    check_prompt_length(spec, n_input, max_new_tokens)
+    tgt = spec.max_target_positions
+    if max_new_tokens is not None:
+        out = n_input + int(max_new_tokens)
+    else:
+        out = min(int(spec.max_length) + min(tgt // 2 - 1, n_input), tgt)
+    if out <= n_input:
+        raise ValueError(f"max_length {out} leaves no room to generate after the {n_input} decoder input ids (prompt + init "
+                         f"tokens): pass max_new_tokens or a shorter prompt")
+    return out
 
 
 def split_segments(seq: np.ndarray, token_ts: np.ndarray, time_offset: float, timestamp_begin: int,
@@ -316,7 +368,7 @@ def _beam_search_tail(engine, seq_out, bi_out, scores, n_prompt):
 def generate(engine: Engine, n_items: int, num_frames, *, language: Optional[str], task: Optional[str] = None,
              max_new_tokens: Optional[int] = None, min_new_tokens: Optional[int] = None,
              num_beams: Optional[int] = 1, stats: Optional[dict] = None, native: Optional[bool] = None,
-             logprob_threshold: Optional[float] = None, no_speech_threshold: Optional[float] = None):
+             logprob_threshold: Optional[float] = None, no_speech_threshold: Optional[float] = None, prompt_ids=None):
     """Transcribe the ``n_items`` 30 s feature windows resident in the engine (items 0..n-1).
 
     Returns {"sequences": [B, Lmax] int64 (pad-right), "token_timestamps": list of float32 arrays,
@@ -329,12 +381,23 @@ def generate(engine: Engine, n_items: int, num_frames, *, language: Optional[str
     ``logprob_threshold`` / ``no_speech_threshold``: the deterministic (temperature 0) half of HF's
     ``generate_with_fallback`` (generation_whisper.py:970-1116, ``_need_fallback`` :1243-1287): a window whose average token
     log-probability is below the first AND whose no-speech probability is above the second is skipped -- seek moves on by the
-    whole window, no segment (:879-881).  Re-decoding at higher temperatures is not implemented (pipeline.py refuses it)."""
+    whole window, no segment (:879-881).  Re-decoding at higher temperatures is not implemented (pipeline.py refuses it).
+
+    ``prompt_ids`` (``processor.get_prompt_ids(text)``): every window of every seek pass decodes from
+    ``prompt_ids ++ init_tokens`` (generation_whisper.py:1909-1913, condition_on_prev_tokens False); language detection still
+    runs on <|startoftranscript|> alone; the prompt is never part of the output."""
     spec = engine.spec
     if no_speech_threshold is not None and logprob_threshold is None:
         raise ValueError("no_speech_threshold needs logprob_threshold as well (generation_whisper.py:1275-1285 compares both)")
     # every argument is checked before any engine state changes (a refused call must not leave its thresholds behind)
     skip_on = logprob_threshold is not None and no_speech_threshold is not None
+    prefix = None
+    if prompt_ids is not None:
+        prefix = check_prompt_ids(spec, prompt_ids)
+        if logprob_threshold is not None or no_speech_threshold is not None:
+            raise ValueError("prompt_ids together with logprob_threshold / no_speech_threshold is not implemented on the native "
+                             "path (the no-speech position moves with the prompt)")
+        prompted_max_length(spec, len(prefix) + len(resolve_prompt(spec, language, task)[0]), max_new_tokens)
     if skip_on and num_beams is not None and int(num_beams) > 1:
         raise ValueError("logprob_threshold / no_speech_threshold are implemented for greedy decoding only: pass num_beams=1")
     num_beams = 1 if num_beams is None else int(num_beams)
@@ -364,7 +427,8 @@ def generate(engine: Engine, n_items: int, num_frames, *, language: Optional[str
         toks, tts, n_calls = engine.transcribe(
             n_items, num_frames, sot=spec.decoder_start_token_id, language_token=lang_tok, task_token=task_tok,
             max_new_tokens=-1 if max_new_tokens is None else int(max_new_tokens), min_new_tokens=min_new_tokens or 0,
-            max_length=spec.max_length, lang_ids=sorted(set(spec.lang_to_id.values())) if spec.lang_to_id else None)
+            max_length=spec.max_length, lang_ids=sorted(set(spec.lang_to_id.values())) if spec.lang_to_id else None,
+            prefix=prefix)
         if stats is not None:
             stats["generate_calls"] = stats.get("generate_calls", 0) + n_calls
         width = max((len(s) for s in toks), default=0)
@@ -378,17 +442,42 @@ def generate(engine: Engine, n_items: int, num_frames, *, language: Optional[str
         # language auto-detection (the reference does not pass `language`, REF/transcribe.py:33)
         engine.encode(list(range(n_items)), np.zeros(n_items, np.int64), np.full(n_items, N_FRAMES, np.int64))
         langs = detect_language(engine, n_items)
-        init = np.asarray([init_tokens(spec, language, task, lang_id=l) for l in langs], dtype=np.int32)
+        init = np.asarray([init_tokens(spec, language, task, lang_id=l, prompt_ids=prefix) for l in langs], dtype=np.int32)
         pre_encoded = True
     else:
-        init = np.tile(np.asarray(init_tokens(spec, language, task), dtype=np.int32), (n_items, 1))
+        init = np.tile(np.asarray(init_tokens(spec, language, task, prompt_ids=prefix), dtype=np.int32), (n_items, 1))
     n_prompt = init.shape[1]
-    if max_new_tokens is not None and max_new_tokens + n_prompt > spec.max_target_positions:
+    if prefix is not None:
+        prompted_len = prompted_max_length(spec, n_prompt, max_new_tokens)
+    elif max_new_tokens is not None and max_new_tokens + n_prompt > spec.max_target_positions:
         max_new_tokens = spec.max_target_positions - n_prompt     # :1937-1942
     tb = spec.timestamp_begin
     seek = np.zeros(n_items, dtype=np.int64)
     max_frames = np.full(n_items, N_FRAMES, dtype=np.int64)
     segments: List[List[Segment]] = [[] for _ in range(n_items)]
+    n_calls = 0
+    set_prefix = getattr(engine, "set_prompt_prefix", None)     # the device engine: lets the prompt prefill engage
+    if prefix is not None and set_prefix is not None:
+        set_prefix(len(prefix))
+    try:
+        _seek_loop(engine, spec, n_items, num_frames, init, n_prompt, max_new_tokens, min_new_tokens, num_beams, prefix,
+                   prompted_len if prefix is not None else None, skip_on, logprob_threshold, no_speech_threshold, pre_encoded,
+                   seek, max_frames, segments, tb, stats)
+    finally:
+        if prefix is not None and set_prefix is not None:
+            set_prefix(0)
+    seq_list = [np.concatenate([s.tokens for s in segs]) if segs else np.zeros(0, np.int64) for segs in segments]
+    width = max((len(s) for s in seq_list), default=0)
+    sequences = np.full((n_items, width), spec.pad_token_id, dtype=np.int64)
+    for i, s in enumerate(seq_list):
+        sequences[i, :len(s)] = s
+    tts = [np.concatenate([s.token_timestamps for s in segs]) if segs else np.zeros(0, np.float32) for segs in segments]
+    return {"sequences": sequences, "token_timestamps": tts, "segments": segments}
+
+
+def _seek_loop(engine, spec, n_items, num_frames, init, n_prompt, max_new_tokens, min_new_tokens, num_beams, prefix, prompted_len,
+               skip_on, logprob_threshold, no_speech_threshold, pre_encoded, seek, max_frames, segments, tb, stats):
+    """The seek loop of the host path of ``generate`` (fills ``segments`` in place)."""
     n_calls = 0
     while True:
         active = [i for i in range(n_items) if seek[i] < max_frames[i]]
@@ -397,7 +486,10 @@ def generate(engine: Engine, n_items: int, num_frames, *, language: Optional[str
         seek_num = np.minimum(max_frames - seek, N_FRAMES)
         if not (pre_encoded and n_calls == 0):            # first pass: windows already encoded for detection
             engine.encode(active, seek[active], seek_num[active])
-        max_length = (n_prompt + max_new_tokens) if max_new_tokens is not None else min(spec.max_length, spec.max_target_positions)
+        if prefix is not None:
+            max_length = prompted_len
+        else:
+            max_length = (n_prompt + max_new_tokens) if max_new_tokens is not None else min(spec.max_length, spec.max_target_positions)
         nsp = engine.no_speech_probs(len(active), spec.decoder_start_token_id) if skip_on else None
         if num_beams > 1:
             bs, _, L, alp = beam_search(engine, init[active], max_length, min_new_tokens or 0, num_beams)
@@ -430,10 +522,3 @@ def generate(engine: Engine, n_items: int, num_frames, *, language: Optional[str
             segments[i].extend(segs)
     if stats is not None:
         stats["generate_calls"] = stats.get("generate_calls", 0) + n_calls
-    seq_list = [np.concatenate([s.tokens for s in segs]) if segs else np.zeros(0, np.int64) for segs in segments]
-    width = max((len(s) for s in seq_list), default=0)
-    sequences = np.full((n_items, width), spec.pad_token_id, dtype=np.int64)
-    for i, s in enumerate(seq_list):
-        sequences[i, :len(s)] = s
-    tts = [np.concatenate([s.token_timestamps for s in segs]) if segs else np.zeros(0, np.float32) for segs in segments]
-    return {"sequences": sequences, "token_timestamps": tts, "segments": segments}

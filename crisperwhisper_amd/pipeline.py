@@ -213,9 +213,10 @@ _GENERATE_KWARGS = ("language", "task", "max_new_tokens", "min_new_tokens", "num
                     "logprob_threshold", "no_speech_threshold", "compression_ratio_threshold", "return_timestamps")
 
 
-def _check_generate_kwargs(gk: Dict[str, Any], default_num_beams: Optional[int] = None) -> None:
+def _check_generate_kwargs(gk: Dict[str, Any], default_num_beams: Optional[int] = None, spec=None) -> None:
     """``default_num_beams``: the width a call without ``num_beams`` decodes with (the pipeline default): the refusals that
-    depend on the beam width are then raised here, before any audio is loaded."""
+    depend on the beam width are then raised here, before any audio is loaded.  ``spec`` (the model's ModelSpec): the
+    ``prompt_ids`` checks that need the vocabulary and the length limit run here too."""
     unknown = sorted(k for k in gk if k not in _GENERATE_KWARGS)
     if unknown:
         raise ValueError(f"generate_kwargs {unknown} are not implemented on the native path (implemented: "
@@ -239,9 +240,18 @@ def _check_generate_kwargs(gk: Dict[str, Any], default_num_beams: Optional[int] 
                          "generator); pass temperature=0.0 or leave it out")
     if gk.get("num_return_sequences") not in (None, 1):
         raise ValueError("generate_kwargs['num_return_sequences'] > 1 is not supported on the native path")
-    for k in ("prompt_ids", "assistant_model"):
-        if gk.get(k) is not None:
-            raise ValueError(f"generate_kwargs[{k!r}] is not supported on the native path")
+    if gk.get("assistant_model") is not None:
+        raise ValueError("generate_kwargs['assistant_model'] is not supported on the native path")
+    if gk.get("prompt_ids") is not None:
+        if gk.get("logprob_threshold") is not None or gk.get("no_speech_threshold") is not None:
+            raise ValueError("generate_kwargs['prompt_ids'] together with logprob_threshold / no_speech_threshold is not "
+                             "supported on the native path: the no-speech position moves with the prompt and that combination "
+                             "is not reproduced")
+        if spec is None:                     # ids and length are only checkable against a model's vocabulary and limits
+            raise ValueError("generate_kwargs['prompt_ids'] can only be checked against a model: pass its ModelSpec")
+        pids = generation.check_prompt_ids(spec, gk["prompt_ids"])
+        n_init = len(generation.resolve_prompt(spec, gk.get("language"), gk.get("task"))[0])
+        generation.prompted_max_length(spec, len(pids) + n_init, gk.get("max_new_tokens"))
     if gk.get("return_timestamps") not in (None, True, "word"):
         raise ValueError("generate_kwargs['return_timestamps'] must be left to the pipeline argument of the same name")
     if gk.get("no_speech_threshold") is not None and gk.get("logprob_threshold") is None:
@@ -361,7 +371,7 @@ class CrisperWhisperPipeline:
         if return_language:
             raise ValueError("return_language is not supported on the native path")
         gk = dict(generate_kwargs or {})
-        _check_generate_kwargs(gk, self.default_num_beams)
+        _check_generate_kwargs(gk, self.default_num_beams, self.bundle.spec)
         if "num_beams" not in gk:
             _warn_once("beams", f"no num_beams given: decoding with {self.default_num_beams} beams like the installed transformers "
                                 "ASR pipeline default; pass generate_kwargs={'num_beams': 1} for the greedy decoding of the 2024 reference")
@@ -404,7 +414,7 @@ class CrisperWhisperPipeline:
                 eng, len(idxs), nf, language=gk.get("language"), task=gk.get("task"),
                 max_new_tokens=gk.get("max_new_tokens"), min_new_tokens=gk.get("min_new_tokens"),
                 num_beams=num_beams, stats=st, logprob_threshold=gk.get("logprob_threshold"),
-                no_speech_threshold=gk.get("no_speech_threshold"))
+                no_speech_threshold=gk.get("no_speech_threshold"), prompt_ids=gk.get("prompt_ids"))
             rs = []
             for k, i in enumerate(idxs):
                 n_tok = len(out["token_timestamps"][k])

@@ -76,7 +76,11 @@ int32_t cw_set_generation(cw_ctx* ctx, const cw_gen_cfg* cfg);
  * "encoder_gemm_fp8" = 1 (after the weights are loaded; 16-bit engines): e4m3 copies of the encoder's qkv / fc1 / fc2 and the
  * decoder's cross-K/V weights are made with one scale per output row, the LayerNorms in front of those GEMMs emit e4m3 rows with
  * one scale per row, and the GEMMs run on v_mfma_scale_f32_16x16x128_f8f6f4 -- the fp8 MFMA half of BASELINE configs[3];
- * accuracy-gated like the cache option, 0 switches back.                                                              */
+ * accuracy-gated like the cache option, 0 switches back.
+ * "prompt_prefix" = n (default 0): the coming cw_decode / cw_beam_begin inputs start with n prompt_ids in front of the init
+ * tokens (cw_transcribe_prompted sets it for its own calls).  With n > 0 and "prompt_prefill" (default 1) the forward-only
+ * positions run as ONE multi-token decoder forward on the matrix cores (csrc/prefill.hip) on 16-bit engines with the 16-bit cross
+ * cache; "prompt_prefill" = 0, n = 0 and every other engine run them through the per-position decoder step.                 */
 int32_t cw_set_option(cw_ctx* ctx, const char* name, int32_t value);
 
 /* ---- audio ingest (the step in front of seam 1) -------------------------------------------------
@@ -173,6 +177,16 @@ typedef struct {
 } cw_transcribe_cfg;
 int32_t cw_transcribe(cw_ctx* ctx, int32_t B, const int32_t* num_frames, const cw_transcribe_cfg* cfg,
                       int32_t* tokens, float* token_ts, int32_t* lens, int32_t cap, int32_t* n_passes);
+/* cw_transcribe_prompted: the same with generate(prompt_ids=...) (generation_whisper.py:1909-1913): prefix[n_prefix]
+ * (<|startofprev|> p1 .. pk) goes in front of every window's {sot, lang[, task]} after language detection, and every pass
+ * of the seek loop starts from that same decoder input (condition_on_prev_tokens = False).  With a prefix the length
+ * rules are transformers' _set_max_new_tokens_and_length (:1920-1946): n_prompt + max_new_tokens > max_target_positions
+ * fails; without max_new_tokens max_length = min(cfg->max_length + min(max_target / 2 - 1, n_prompt), max_target).
+ * The prefix is never part of the output.  A prefix fails while either threshold of cw_set_thresholds is set (not NaN).
+ * cw_transcribe(...) == cw_transcribe_prompted(..., NULL, 0, ...).                                                 */
+int32_t cw_transcribe_prompted(cw_ctx* ctx, int32_t B, const int32_t* num_frames, const cw_transcribe_cfg* cfg,
+                               const int32_t* prefix, int32_t n_prefix, int32_t* tokens, float* token_ts, int32_t* lens,
+                               int32_t cap, int32_t* n_passes);
 
 /* ---- beam search (the transformers 5.x ASR pipeline defaults to num_beams = 5,
  * TF/pipelines/automatic_speech_recognition.py:160-163): device half of GenerationMixin._beam_search
@@ -272,6 +286,14 @@ int32_t cw_test_attention(cw_ctx* ctx, int32_t B, int32_t H, int32_t S, const fl
  * part_o [6][B][H*64], part_ml [B][H][6][2] = (max, sum) per split; head `align_head` captured as the only alignment head:
  * align [B][S] = exp(s - max of its split), align_ml [B][6][2].                                                     */
 #define CW_ATT_SPLITS 6
+/* Decoder prompt prefill kernels (16-bit engines) against a host reference: cw_test_prefill_gemm runs the prefill GEMM over
+ * fragment-major packed W with epilogue mode 0 = 16-bit store, 2 = f32 residual add (out: residual in, result out), 3 = erf GELU
+ * (K % 32 == 0, N % 16 == 0); cw_test_prefill_attention the flash attention of the prefill (causal over n_keys >= n_q keys, or
+ * all n_keys keys of K/V row row / kv_div), no scale applied.                                                                 */
+int32_t cw_test_prefill_gemm(cw_ctx* ctx, int32_t mode, int32_t M, int32_t N, int32_t K, const float* A, const float* W,
+                             const float* bias, float* out);
+int32_t cw_test_prefill_attention(cw_ctx* ctx, int32_t rows, int32_t n_q, int32_t H, int32_t cap, int32_t n_keys, int32_t causal,
+                                  int32_t kv_div, const float* q, const float* k, const float* v, float* out);
 int32_t cw_test_cross_attention(cw_ctx* ctx, int32_t B, int32_t H, int32_t S, int32_t kv_div, const float* q, const float* k,
                                 const float* v, int32_t align_head, float* part_o, float* part_ml, float* align,
                                 float* align_ml);
