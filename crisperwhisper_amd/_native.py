@@ -102,6 +102,8 @@ _SIGS = {
     "cw_test_skinny": (_I, [_P, _I, _I, _I, _I, _P, _P, _P, _I, _I, _P, _P]),
     "cw_test_attention": (_I, [_P, _I, _I, _I, _P, _P, _P, _P]),
     "cw_test_cross_attention": (_I, [_P, _I, _I, _I, _I, _P, _P, _P, _I, _P, _P, _P, _P]),
+    "cw_test_self_attention": (_I, [_P, _I, _I, _I, _I, _P, _P, _P, _P, _I, _P, _I, _I, _I, _I, _P, _P, _P]),
+    "cw_test_beam_state": (_I, [_P, _I, _P, _P, _P]),
     "cw_test_prefill_gemm": (_I, [_P, _I, _I, _I, _I, _P, _P, _P, _P]),
     "cw_test_prefill_attention": (_I, [_P, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P]),
     "cw_test_sample": (_I, [_P, _I, _P, _P, _I, _I, _I, _I, _P]),

@@ -2878,6 +2878,105 @@ int32_t cw_test_cross_attention(cw_ctx* c, int32_t B, int32_t H, int32_t S, int3
     return r;
 }
 
+// One launch of the decode self-attention dispatcher (cw_launch_attn_decode) on caller-supplied rows, parameters filled the way
+// decode_step fills them: q [B][H*64] (already scaled), k / v [B / kv_div][H][cap][64]; per-row histories (n_keys = 0: pos[b] + 1
+// keys) or a fixed n_keys (the f32 engine's cross-attention; pos[b] = alignment row).  anc [B][cap]: beam-search ancestry.
+// out_frag: the kernel writes the 16-bit MFMA fragment-major buffer; it comes back un-permuted as [B][H*64] and *frag_tail_ok
+// says whether its rows B .. 16-padded were left untouched.  align_head >= 0: that head is the only alignment slot; align
+// [B][align_rows][n_keys] is uploaded as the initial contents and downloaded after the launch.  Every index the kernels can
+// derive from the inputs is checked here, before anything is launched.
+int32_t cw_test_self_attention(cw_ctx* c, int32_t B, int32_t H, int32_t cap, int32_t kv_div, const float* q, const float* k,
+                               const float* v, const int32_t* pos, int32_t n_keys, const int32_t* anc, int32_t short_hist,
+                               int32_t out_frag, int32_t align_head, int32_t align_rows, float* out, float* align,
+                               int32_t* frag_tail_ok) {
+    if (B < 1 || H < 1 || cap < 1 || cap > 8192 || kv_div < 1 || B % kv_div)
+        return fail(c, CW_ERR_INVALID, "test_self_attention: shape B=%d H=%d cap=%d kv_div=%d", B, H, cap, kv_div);
+    if (!q || !k || !v || !pos || !out || (out_frag && !frag_tail_ok)) return fail(c, CW_ERR_INVALID, "test_self_attention: null buffer");
+    if (n_keys < 0 || n_keys > cap) return fail(c, CW_ERR_INVALID, "test_self_attention: n_keys=%d outside [0, cap=%d]", n_keys, cap);
+    for (int b = 0; b < B; ++b)
+        if (pos[b] < 0 || pos[b] >= cap) return fail(c, CW_ERR_INVALID, "test_self_attention: pos[%d]=%d outside [0, cap=%d)", b, pos[b], cap);
+    if (anc) {
+        if (kv_div > 1 || n_keys > 0 || align_head >= 0)
+            return fail(c, CW_ERR_INVALID, "test_self_attention: anc with kv_div=%d / n_keys=%d / align_head=%d", kv_div, n_keys, align_head);
+        for (int b = 0; b < B; ++b)
+            for (int t = 0; t <= pos[b]; ++t)
+                if (anc[(size_t)b * cap + t] < 0 || anc[(size_t)b * cap + t] >= B)
+                    return fail(c, CW_ERR_INVALID, "test_self_attention: anc[%d][%d]=%d outside [0, B=%d)", b, t, anc[(size_t)b * cap + t], B);
+    }
+    if (align_head < -1 || align_head >= H) return fail(c, CW_ERR_INVALID, "test_self_attention: align_head=%d", align_head);
+    if (align_head >= 0) {   // the capture's row stride is n_keys: only defined for a fixed key count
+        if (n_keys < 1 || align_rows < 1 || !align)
+            return fail(c, CW_ERR_INVALID, "test_self_attention: alignment capture needs a fixed n_keys (%d) and align_rows (%d)", n_keys, align_rows);
+        for (int b = 0; b < B; ++b)
+            if (pos[b] >= align_rows) return fail(c, CW_ERR_INVALID, "test_self_attention: pos[%d]=%d >= align_rows=%d", b, pos[b], align_rows);
+    }
+    const int D = H * 64, Mpad = (B + 15) & ~15;
+    const size_t nkv = (size_t)(B / kv_div) * H * cap * 64, nal = align_head >= 0 ? (size_t)B * align_rows * n_keys : 0;
+    float *dq = nullptr, *dout = nullptr, *dal = nullptr;
+    void *dk = nullptr, *dv = nullptr;
+    int *dpos = nullptr, *danc = nullptr, *dslot = nullptr;
+    unsigned short* dfrag = nullptr;
+    DevScope mem;
+    HIPCHK(c, mem.get(&dq, (size_t)B * D * 4)); HIPCHK(c, mem.get(&dk, nkv * c->esz)); HIPCHK(c, mem.get(&dv, nkv * c->esz));
+    HIPCHK(c, mem.get(&dpos, (size_t)B * 4)); HIPCHK(c, mem.get(&dout, (size_t)B * D * 4));
+    HIPCHK(c, hipMemcpy(dq, q, (size_t)B * D * 4, hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemcpy(dpos, pos, (size_t)B * 4, hipMemcpyHostToDevice));
+    CWCHK(c, upload_T(c, dk, 0, k, nkv)); CWCHK(c, upload_T(c, dv, 0, v, nkv));
+    DecAttnParams p = dec_attn(dq, dk, dv, cap, n_keys, dpos, dout, B, H);
+    p.kv_div = kv_div; p.short_hist = short_hist ? 1 : 0;
+    if (anc) {
+        HIPCHK(c, mem.get(&danc, (size_t)B * cap * 4));
+        HIPCHK(c, hipMemcpy(danc, anc, (size_t)B * cap * 4, hipMemcpyHostToDevice));
+        p.anc = danc;
+    }
+    if (out_frag) {
+        HIPCHK(c, mem.get(&dfrag, (size_t)Mpad * D * 2));
+        HIPCHK(c, hipMemsetAsync(dfrag, 0xA5, (size_t)Mpad * D * 2, c->st));
+        p.out_frag = dfrag;
+    }
+    if (align_head >= 0) {
+        std::vector<int> slot(H, -1);
+        slot[align_head] = 0;
+        HIPCHK(c, mem.get(&dal, nal * 4)); HIPCHK(c, mem.get(&dslot, (size_t)H * 4));
+        HIPCHK(c, hipMemcpy(dal, align, nal * 4, hipMemcpyHostToDevice));
+        HIPCHK(c, hipMemcpy(dslot, slot.data(), (size_t)H * 4, hipMemcpyHostToDevice));
+        p.align_out = dal; p.align_slot = dslot; p.n_align = 1; p.align_rows = align_rows;
+    }
+    int r = KD(c, cw_launch_attn_decode, c->bf16, p, c->st);
+    if (r != CW_OK) return fail(c, r, "test_self_attention: launch rejected");
+    { hipError_t er = hipStreamSynchronize(c->st); if (er != hipSuccess) return fail(c, CW_ERR_HIP, "test_self_attention: %s", hipGetErrorString(er)); }
+    if (out_frag) {
+        std::vector<unsigned short> f((size_t)Mpad * D);
+        HIPCHK(c, hipMemcpy(f.data(), dfrag, f.size() * 2, hipMemcpyDeviceToHost));
+        for (int b = 0; b < B; ++b)
+            for (int j = 0; j < D; ++j) {
+                const unsigned short h = f[frag_index(b, j, D)];
+                out[(size_t)b * D + j] = c->f16 ? cw_host_f16_to_f32(h) : cw_host_bf16_to_f32(h);
+            }
+        int ok = 1;
+        for (int b = B; b < Mpad; ++b)
+            for (int j = 0; j < D; ++j) ok &= f[frag_index(b, j, D)] == 0xA5A5;
+        *frag_tail_ok = ok;
+    } else {
+        HIPCHK(c, hipMemcpy(out, dout, (size_t)B * D * 4, hipMemcpyDeviceToHost));
+    }
+    if (align_head >= 0) HIPCHK(c, hipMemcpy(align, dal, nal * 4, hipMemcpyDeviceToHost));
+    return CW_OK;
+}
+
+// The beam-search state of the first `rows` rows after cw_beam_begin / cw_beam_advance: token history ids [rows][TGT], cache
+// ancestry anc [rows][TGT] and decoder input position pos [rows], as the device holds them.
+int32_t cw_test_beam_state(cw_ctx* c, int32_t rows, int32_t* ids, int32_t* anc, int32_t* pos) {
+    const int TGT = c->d.max_target_positions;
+    if (c->beam_K <= 0 || !c->d_anc) return fail(c, CW_ERR_STATE, "cw_beam_begin not called");
+    if (rows < 1 || rows > c->Bm || rows > 64 || !ids || !anc || !pos) return fail(c, CW_ERR_INVALID, "test_beam_state: rows=%d", rows);
+    HIPCHK(c, hipStreamSynchronize(c->st));
+    HIPCHK(c, hipMemcpy(ids, c->d_ids, (size_t)rows * TGT * 4, hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(anc, c->d_anc, (size_t)rows * TGT * 4, hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(pos, c->d_pos, (size_t)rows * 4, hipMemcpyDeviceToHost));
+    return CW_OK;
+}
+
 // One call of the fused logits-processor + argmax kernel (sample_kernel) on caller-supplied rows: logits [nb][V],
 // ids [nb][t] = prompt + generated so far (the kernel's grammar state is rebuilt from it), choice_out [nb] = the
 // token the kernel picks for index t.  Differential test against TF/generation/logits_process.py:203-260, 1816-2047.

@@ -444,6 +444,40 @@ class Engine:
         scale = np.repeat(aw, per, axis=1)[:, :S] / (a_l * aw).sum(-1, keepdims=True)
         return o.reshape(B, H * 64), al.astype(np.float64) * scale
 
+    def test_self_attention(self, q, k, v, pos, n_keys=0, anc=None, kv_div=1, short_hist=False, out_frag=False,
+                            align_head=-1, align_rows=0, align_init=None):
+        """One launch of the decode self-attention dispatcher (cw_test_self_attention): q [B][H*64] pre-scaled, k / v
+        [B / kv_div][H][cap][64], pos [B]; n_keys = 0: pos[b] + 1 keys per row, else that many (pos[b] = alignment row);
+        anc [B][cap] or None.  Returns out [B][H*64]; with out_frag also whether the fragment buffer's padding rows stayed
+        untouched; with align_head >= 0 also align [B][align_rows][n_keys] (starting from align_init, default zeros)."""
+        q, k, v = (np.ascontiguousarray(t, np.float32) for t in (q, k, v))
+        B = q.shape[0]
+        H, cap = k.shape[1], k.shape[2]
+        pos = _i32(pos)
+        a = None if anc is None else _i32(anc)
+        out = np.zeros((B, H * 64), np.float32)
+        al = None
+        if align_head >= 0:
+            al = (np.zeros((B, align_rows, n_keys), np.float32) if align_init is None
+                  else np.ascontiguousarray(align_init, np.float32).copy())
+        tail = np.zeros(1, np.int32)
+        self._chk(self.lib.cw_test_self_attention(self.ctx, B, H, cap, int(kv_div), _ptr(q), _ptr(k), _ptr(v), _ptr(pos),
+                                                  int(n_keys), _ptr(a), 1 if short_hist else 0, 1 if out_frag else 0,
+                                                  int(align_head), int(align_rows), _ptr(out), _ptr(al), _ptr(tail)))
+        res = (out,)
+        if out_frag:
+            res += (bool(tail[0]),)
+        if align_head >= 0:
+            res += (al,)
+        return res[0] if len(res) == 1 else res
+
+    def test_beam_state(self, rows: int):
+        """(ids, anc, pos) of the first `rows` beam rows as the device holds them (cw_test_beam_state)."""
+        tgt = self.spec.max_target_positions
+        ids = np.zeros((rows, tgt), np.int32); anc = np.zeros((rows, tgt), np.int32); pos = np.zeros(rows, np.int32)
+        self._chk(self.lib.cw_test_beam_state(self.ctx, int(rows), _ptr(ids), _ptr(anc), _ptr(pos)))
+        return ids, anc, pos
+
     def test_sample(self, logits: np.ndarray, ids: np.ndarray, n_prompt: int, min_new_tokens: int = 0,
                     max_length: Optional[int] = None) -> np.ndarray:
         """One launch of the fused logits processors + greedy choice on caller rows (cw_test_sample)."""

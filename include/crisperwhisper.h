@@ -297,6 +297,21 @@ int32_t cw_test_prefill_attention(cw_ctx* ctx, int32_t rows, int32_t n_q, int32_
 int32_t cw_test_cross_attention(cw_ctx* ctx, int32_t B, int32_t H, int32_t S, int32_t kv_div, const float* q, const float* k,
                                 const float* v, int32_t align_head, float* part_o, float* part_ml, float* align,
                                 float* align_ml);
+/* One launch of the decode self-attention dispatcher (cw_launch_attn_decode: attn_decode_kernel / attn_decode_anc_kernel) with
+ * the parameters decode_step gives it: q [B][H*64] pre-scaled, k / v [B / kv_div][H][cap][64], pos [B] (n_keys = 0: row b
+ * attends over its pos[b] + 1 keys; n_keys > 0: over n_keys keys, pos[b] = alignment row), anc [B][cap] or NULL (key t of row
+ * b in cache row anc[b][t]), short_hist = the host's <= 64-key hint.  out_frag = 1: the 16-bit fragment-major output,
+ * returned un-permuted in out [B][H*64] (*frag_tail_ok = 1 when its padding rows B.. were left untouched).  align_head >= 0
+ * (fixed n_keys only): that head captured as the only alignment slot into align [B][align_rows][n_keys] (in / out).
+ * Rejected before any launch: n_keys > cap, pos[b] outside [0, cap), anc[b][t <= pos[b]] outside [0, B), anc with
+ * kv_div > 1, a fixed n_keys or alignment capture.                                                                  */
+int32_t cw_test_self_attention(cw_ctx* ctx, int32_t B, int32_t H, int32_t cap, int32_t kv_div, const float* q, const float* k,
+                               const float* v, const int32_t* pos, int32_t n_keys, const int32_t* anc, int32_t short_hist,
+                               int32_t out_frag, int32_t align_head, int32_t align_rows, float* out, float* align,
+                               int32_t* frag_tail_ok);
+/* Beam-search state of rows 0..rows-1 after cw_beam_begin / cw_beam_advance: ids [rows][max_target_positions], anc
+ * [rows][max_target_positions] (cache row of every key position), pos [rows].                                       */
+int32_t cw_test_beam_state(cw_ctx* ctx, int32_t rows, int32_t* ids, int32_t* anc, int32_t* pos);
 /* One launch of the fused logits processors + greedy choice (MinNewTokensLength, SuppressTokensAtBegin, SuppressTokens,
  * WhisperTimeStamp: TF/generation/logits_process.py:203-260, 1816-2047; argmax TF/generation/utils.py:2925) on
  * caller-supplied rows: logits [nb][vocab], ids [nb][t] = prompt + tokens generated so far; choice_out [nb] = token for
