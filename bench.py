@@ -5,12 +5,19 @@
 
     python bench.py --gpus 1 --steps K --warmup W          (N=1)
     python bench.py ... --dump-outputs DIR                 (+ the last timed step's results as DIR/*.npy: dump_outputs)
+    python bench.py ... --full                             (+ everything beyond the headline: see below)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 One "step" = one pass of the whole path over one batch of B x 30 s clips per GPU (weak scaling: every
 rank processes its own B clips; the only collective is the all-gather of per-chunk word records).
 PCM is resident in HBM before the timed region (PCIe-inclusive rate: see DESIGN.md).  Weights are
 seeded random tensors of the large-v3 geometry (no checkpoint is available offline): data="synthetic".
+
+A plain run does what the headline needs: set up, warm up, time the steps, dump the outputs if asked, print the line.
+--full adds what takes work of its own after the timed steps: the parity check of the timed output against the committed
+transformers goldens (and exit status 3 when it fails), the per-launch roofline (cw_time_decode_stage / cw_time_kernel runs),
+the BASELINE configs[2] long-form and configs[3] batch-64 legs and the CPU reference leg; --no-longform, --no-config3,
+--no-cpu-baseline, --cpu-* and --kernel-iters select within it.
 """
 from __future__ import annotations
 
@@ -43,6 +50,9 @@ def parse(argv=None):
                     help="seeded synthetic weights: 'aligned' = random tensors whose alignment heads are peaked and monotone like a "
                          "trained checkpoint's (crisperwhisper_amd/synthetic.py); the run is then checked word for word against the "
                          "committed transformers output for the same clips (tests/golden/e2e_bench_golden.json)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beyond the headline figure: parity against the committed transformers goldens, the "
+                         "per-launch roofline, the configs[2] long-form and configs[3] legs and the CPU reference leg")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-tokens", type=int, default=12)
     ap.add_argument("--cpu-threads", type=int, default=0, help="torch threads of the reference leg; 0 = calibrated per stage on "
@@ -476,7 +486,7 @@ def main():
     engines = [Engine(spec, dtype=a.dtype, max_batch=B * max(1, a.num_beams), device=dev, cross_kv_dtype=None if a.cross_kv == "bf16" else a.cross_kv)
                for _ in range(C)]
     eng = engines[0]
-    keep = (not a.no_cpu_baseline) and world == 1 and rank == 0
+    keep = a.full and (not a.no_cpu_baseline) and world == 1 and rank == 0
     keep_weights = keep and a.cpu_port
     weights = {}
     t0 = time.perf_counter()
@@ -599,7 +609,7 @@ def main():
     # ---- the timed output against the reference: the clips of rank 0 are the ones tests/golden/gen_golden_bench.py ran
     # through transformers (CPU, fp32) with the same aligned weights and token count
     parity = None
-    if rank == 0 and a.geometry == "large-v3" and a.dtype in ("bf16", "f16"):
+    if a.full and rank == 0 and a.geometry == "large-v3" and a.dtype in ("bf16", "f16"):
         gold = load_bench_goldens(a.tokens, a.weights) if a.num_beams == 1 else load_beam_goldens(a.tokens, a.weights, a.num_beams)
         ks = [k for k in range(B) if k in gold and k in last_raw]
         if ks:
@@ -628,18 +638,18 @@ def main():
     # (contiguous blocks, dist.shard_bounds), one all-gather of the per-chunk records, seam merge + pause split on every
     # rank.  Everything from the host PCM array to the final word list is inside the timed call (PCIe included).
     longform = None
-    if a.geometry == "large-v3" and not a.no_longform and C == 1 and a.num_beams == 1:
+    if a.full and a.geometry == "large-v3" and not a.no_longform and C == 1 and a.num_beams == 1:
         longform = longform_leg(a, dev, g, v, spec, vocab, shard, world, fence, max_over_ranks)
     # roofline of the decode step: EVERY launch of the decoder layer as the step issues it at this batch (cw_time_decode_stage runs
     # the step's own launch code one stage at a time) + the logits projection, HIP events on the engine's own stream
     roof = []
-    if a.num_beams == 1:
+    if a.full and a.num_beams == 1:
         for st in eng.time_decode_stages(B, a.kernel_iters):
             roof.append({"kernel": st["kernel"], "stage": st["stage"], "avg_ms": st["avg_ms"], "algo_bytes": st["algo_bytes"], "per_step": g.dec_layers,
                          "launches": st.get("launches", 1)})
         ms, by = eng.time_kernel(7, B, a.kernel_iters)
         roof.append({"kernel": "LayerNorm + logits projection (gemv_loop_kernel)", "stage": 100, "avg_ms": ms, "algo_bytes": by, "per_step": 1})
-    else:   # beam rows: the two kernels of the greedy layer that dominate it (the beam layer's own launches are in the rocprofv3 table)
+    elif a.full:   # beam rows: the two kernels of the greedy layer that dominate it (the beam layer's own launches are in the rocprofv3 table)
         for which, kname in ((0, "LayerNorm + fc1 + GELU"), (1, "cross-attention")):
             ms, by = eng.time_kernel(which, B, a.kernel_iters)
             roof.append({"kernel": kname, "stage": which, "avg_ms": ms, "algo_bytes": by, "per_step": g.dec_layers})
@@ -667,7 +677,7 @@ def main():
         dec_step_ms = (dec_ms / dec_calls / (1 if a.num_beams > 1 else a.tokens + 2)) if dec_calls else None
         for r_ in roof:
             r_["share_of_decode_step"] = (r_["avg_ms"] * r_["per_step"] / dec_step_ms) if dec_step_ms else None
-        r = max(singles, key=lambda r_: r_["avg_ms"] * r_["per_step"])
+        r = max(singles, key=lambda r_: r_["avg_ms"] * r_["per_step"]) if singles else None     # None: no roofline runs (no --full)
         PMC_NAMES = {"cross-attention": "attn_cross_mfma8" if a.cross_kv == "fp8" else "attn_cross_split_kernel", "qkv_self_kernel": "qkv_self_kernel",
                      "gemv_stack_kernel": "gemv_stack_kernel", "fc1": "gemv2_bf16_kernelILi1E", "fc2": "gemv2_bf16_kernelILi2ELi2ELb1ELb0",
                      "out-projection (combines": "gemv2_bf16_kernelILi2ELi1ELb1ELb1", "logits": "gemv_loop_kernel"}
@@ -700,7 +710,7 @@ def main():
                          "launches_per_decode_step": r["per_step"], "share_of_decode_step": r["share_of_decode_step"],
                          "dominant_by": "largest measured share of the decode step among all launches of the layer + logits (roofline_other lists the rest)",
                          # the step as a whole (filled in below from the stage timers): algorithmic bytes of one token step / its time
-                         "step_frac": None, "step_achieved": None},
+                         "step_frac": None, "step_achieved": None} if r is not None else None,
             "parity": parity,
             "collective": {"backend": ("rccl (torch.distributed nccl)" if pg == "nccl" else pg), "all_gathers_in_timed_region": n_gathers,
                            # true = not a hardware scaling measurement: the ranks meet over gloo (host TCP) and may share devices
@@ -720,7 +730,7 @@ def main():
                                 "avg_launch_ms": r_["avg_ms"], "algorithmic_bytes_per_launch": r_["algo_bytes"],
                                 "launches_per_decode_step": r_["per_step"], "share_of_decode_step": r_["share_of_decode_step"],
                                 "traffic": pmc_of(r_["kernel"])}
-                               for r_ in roof if r_ is not r],
+                               for r_ in roof if r_ is not r] if r is not None else None,
         }
         # per-stage achieved fraction of roofline (BASELINE.md section 3 work figures; times = HIP events per call)
         if a.geometry == "large-v3":
@@ -761,12 +771,15 @@ def main():
                 sr["decode_step"] = {"bound": "hbm", "algorithmic_bytes": by, "streamed_bytes": streamed, "ms_per_step": per_step_ms,
                                      "achieved_GBps": by / per_step_ms / 1e6, "frac_of_8TBps": by / per_step_ms / 1e6 / 8000.0,
                                      # kernel launches (a 17..64-row LayerNorm / combining GEMV is a preparation launch + the GEMV: counted as two)
-                                     "launches_per_layer": (sum(r_.get("launches", 1) for r_ in roof if 0 <= r_["stage"] < 100) if a.num_beams == 1 else (12 if B * a.num_beams > 16 else 8))}
+                                     # (greedy: counted by the roofline runs of --full, None without them)
+                                     "launches_per_layer": ((sum(r_.get("launches", 1) for r_ in roof if 0 <= r_["stage"] < 100) if roof else None)
+                                                            if a.num_beams == 1 else (12 if B * a.num_beams > 16 else 8))}
                 if a.num_beams > 1:
                     sr["decode_step"]["rows"] = B * a.num_beams
-                line["roofline"]["step_frac"] = sr["decode_step"]["frac_of_8TBps"]
-                line["roofline"]["step_achieved"] = sr["decode_step"]["achieved_GBps"]
-                line["roofline"]["sum_of_launch_shares"] = sum(r_["share_of_decode_step"] for r_ in roof if r_["stage"] >= 0 and r_["share_of_decode_step"] is not None)
+                if line["roofline"] is not None:
+                    line["roofline"]["step_frac"] = sr["decode_step"]["frac_of_8TBps"]
+                    line["roofline"]["step_achieved"] = sr["decode_step"]["achieved_GBps"]
+                    line["roofline"]["sum_of_launch_shares"] = sum(r_["share_of_decode_step"] for r_ in roof if r_["stage"] >= 0 and r_["share_of_decode_step"] is not None)
             t = per_call("timestamps")
             if t:
                 by = 4.0 * 15 * a.tokens * 1500 * B
@@ -775,7 +788,7 @@ def main():
                                           "dtw_us_per_antidiagonal": t * 1e3 / (a.tokens + 1500 - 1)}
             line["stage_roofline"] = sr
             line["passes_per_step"] = stages["encoder"][1] / max(a.steps, 1)
-        if a.geometry == "large-v3" and world == 1 and not a.no_config3 and a.dtype in ("bf16", "f16") and a.num_beams == 1:
+        if a.full and a.geometry == "large-v3" and world == 1 and not a.no_config3 and a.dtype in ("bf16", "f16") and a.num_beams == 1:
             for e_ in engines:
                 e_.close()
             engines = []

@@ -107,17 +107,17 @@ def test_bench_gpus2_spawns_two_ranks_and_reports_them():
 
 @pytest.mark.gpu
 def test_bench_gpus4_large_geometry_shards_the_long_recording_like_one_rank():
-    """The multi-rank driver run on the one device of the box: `bench.py --gpus 4` at the large-v3 geometry spawns four ranks
-    (sharing the GPU: 4 x 3.1 GB of weights; collectives over gloo because RCCL ranks cannot share a device).  Four ranks and the
-    test process are five processes on the device: eight ranks would oversubscribe a shared card, and the split of the 30 chunks
-    over eight ranks is tested on the host (test_host_logic.test_shard_bounds_and_records).  The line must report 4 ranks seen by
-    the communicator, the BASELINE configs[2] recording (600 s -> 30 chunks) sharded (8,8,7,7), and the merged word list -- every
+    """The multi-rank driver run on the one device of the box: `bench.py --gpus 4 --full` (the long-form leg runs under --full) at
+    the large-v3 geometry spawns four ranks (sharing the GPU: 4 x 3.1 GB of weights; collectives over gloo because RCCL ranks
+    cannot share a device).  Four ranks and the test process are five processes on the device: eight ranks would oversubscribe a
+    shared card, and the split of the 30 chunks over eight ranks is tested on the host (test_host_logic.test_shard_bounds_and_records).
+    The line must report 4 ranks seen by the communicator, the BASELINE configs[2] recording (600 s -> 30 chunks) sharded (8,8,7,7), and the merged word list -- every
     word and timestamp, by digest -- must be the one a single rank produces from the same recording (chunks are independent,
     SURVEY.md 8e)."""
     env = dict(os.environ, CW_DIST_BACKEND="gloo", PYTHONUNBUFFERED="1")
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
-    common = ["--geometry", "large-v3", "--batch", "4", "--tokens", "8", "--steps", "1", "--warmup", "1", "--no-cpu-baseline",
+    common = ["--geometry", "large-v3", "--batch", "4", "--tokens", "8", "--steps", "1", "--warmup", "1", "--full", "--no-cpu-baseline",
               "--no-config3", "--kernel-iters", "3"]
     recs = {}
     for n in (1, 4):

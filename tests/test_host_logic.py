@@ -478,6 +478,18 @@ def test_bench_longform_parity_measure_and_goldens_describe_the_bench_workload()
     assert sorted(greedy) == list(range(64))
 
 
+def test_bench_full_is_opt_in():
+    """bench.py: a plain run measures the headline only; the parity check, the roofline runs and the long-form, configs[3] and CPU
+    reference legs run under --full, which `--gpus N` passes on to the ranks it spawns."""
+    import argparse
+    import bench
+    assert bench.parse([]).full is False
+    a = bench.parse(["--gpus", "2", "--steps", "3", "--warmup", "1", "--full", "--no-config3"])
+    assert a.full and a.no_config3 and (a.steps, a.warmup) == (3, 1)
+    argv = ["--gpus", "2", "--full"]
+    assert bench.spawn_command(argparse.Namespace(gpus=2), argv, 29555)[-len(argv):] == argv
+
+
 def test_bench_steps_and_dump_outputs(tmp_path):
     """bench.py: --steps / --warmup are taken as given (at least one timed step); --dump-outputs writes the last timed step's
     results -- gathered word records of every rank, this rank's tokens -- as float32 / float64 arrays in chunk order, the same
