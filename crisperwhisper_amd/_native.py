@@ -78,6 +78,8 @@ _SIGS = {
     "cw_beam_finish": (_I, [_P, _I, _I, _P]),
     "cw_transcribe": (_I, [_P, _I, _P, C.POINTER(TranscribeCfg), _P, _P, _P, _I, _P]),
     "cw_transcribe_prompted": (_I, [_P, _I, _P, C.POINTER(TranscribeCfg), _P, _I, _P, _P, _P, _I, _P]),
+    "cw_align_tokens": (_I, [_P, _I, _P, _P, _I, _P, _I, _P]),
+    "cw_align_prefill_runs": (_I, [_P]),
     "cw_align_matrix": (_I, [_P, _P, _I, _I, _I, _I, _P, _I, _P]),
     "cw_dtw": (_I, [_P, _P, _I, _I, _P, _P, _P]),
     "cw_adjust_pauses": (_I, [_P, _P, _P, _I, C.c_double]),
@@ -106,6 +108,7 @@ _SIGS = {
     "cw_test_beam_state": (_I, [_P, _I, _P, _P, _P]),
     "cw_test_prefill_gemm": (_I, [_P, _I, _I, _I, _I, _P, _P, _P, _P]),
     "cw_test_prefill_attention": (_I, [_P, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P]),
+    "cw_test_prefill_align_attention": (_I, [_P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P]),
     "cw_test_sample": (_I, [_P, _I, _P, _P, _I, _I, _I, _I, _P]),
     "cw_stage_times": (_I, [_P, _P, _P, _I]),
     "cw_time_kernel": (_I, [_P, _I, _I, _I, _P, _P]),

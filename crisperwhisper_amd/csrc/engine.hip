@@ -9,6 +9,7 @@
 #include <string>
 #include <vector>
 #include <functional>
+#include <algorithm>
 
 #include "../../include/crisperwhisper.h"
 #include "kernels.h"
@@ -201,6 +202,8 @@ struct cw_ctx {
     // decoder prompt prefill (prefill.hip): on by default on the 16-bit engines; cw_set_option "prompt_prefill" = 0 forces the
     // per-position loop (A/B).  Work buffers for rows x positions, grown on demand and freed by cw_destroy.
     bool prompt_prefill = true;
+    bool align_prefill = true;         // cw_align_tokens: the teacher-forced forward as one prefill ("align_prefill" = 0: the loop)
+    int align_prefill_runs = 0;        // cw_align_tokens calls whose forward ran as the prefill (cw_align_prefill_runs)
     int pf_prefix = 0;                 // prompt_ids in front of the init tokens of the coming decoder inputs ("prompt_prefix")
     size_t pf_rows = 0;
     float* pf_x = nullptr;
@@ -1567,6 +1570,7 @@ static int handoffs_off(cw_ctx* c, const char* where) {
     return CW_OK;
 }
 int32_t cw_handoff_fallbacks(cw_ctx* c) { return c->handoff_fallbacks; }
+int32_t cw_align_prefill_runs(cw_ctx* c) { return c->align_prefill_runs; }
 int32_t cw_handoff_resumes(cw_ctx* c) { return c->handoff_resumes; }
 
 // The granule tag is (epoch << 6) | layer in 32 bits: 26 bits of the device's forward counter.  Granules are never cleared, so a
@@ -1592,8 +1596,11 @@ static int epoch_hygiene(cw_ctx* c, long long upcoming_forwards) {
 // cw_transcribe_prompted sets itself), on the 16-bit engines with the 16-bit cross cache and packed, LN-folded decoder weights;
 // every other call keeps the per-position loop.  It writes the self-attention K/V cache rows 0 .. n_prompt-2 of every layer --
 // the state the loop leaves; the prompt's logits and alignment rows are never read.
+static bool prefill_capable(const cw_ctx* c) {
+    return c->bf16 && c->d.d_model == 64 * c->d.n_heads && !c->kv8 && c->wpacked && c->ln_folded && c->layer_sel < 0;
+}
 static bool prefill_engages(const cw_ctx* c, int n_prompt) {
-    return c->pf_prefix > 0 && n_prompt > c->pf_prefix && c->prompt_prefill && c->bf16 && c->d.d_model == 64 * c->d.n_heads && !c->kv8 && c->wpacked && c->ln_folded && c->layer_sel < 0;
+    return c->pf_prefix > 0 && n_prompt > c->pf_prefix && c->prompt_prefill && prefill_capable(c);
 }
 
 static int prefill_reserve(cw_ctx* c, size_t M) {
@@ -1614,13 +1621,21 @@ static int prefill_reserve(cw_ctx* c, size_t M) {
 
 // rows decoder rows (ids in d_ids [rows][TGT]), cross K/V row = row / kv_div.  Launches per layer: 3 LayerNorms, 6 GEMMs, 2
 // attentions (the last layer: LayerNorm + q/k/v only -- its output feeds nothing the loop keeps).
-static int run_prefill(cw_ctx* c, int rows, int n_prompt, int kv_div) {
+// align (cw_align_tokens): the cross-attention of every layer that holds an alignment head records its rows for positions
+// 0 .. n_prompt-2 into d_align / d_align_ml, and the forward stops after the cross-attention of the last such layer: that
+// layer's cross out-projection and MLP, the layers above it, the final LayerNorm and the logits feed no alignment row.
+static int align_last_layer(const cw_ctx* c) {
+    int last = -1;
+    for (int a = 0; a < c->d.n_align; ++a) last = c->align_layers[a] > last ? c->align_layers[a] : last;
+    return last;
+}
+static int run_prefill(cw_ctx* c, int rows, int n_prompt, int kv_div, bool align = false) {
     const int D = c->d.d_model, F = c->d.ffn_dim, H = c->d.n_heads, TGT = c->d.max_target_positions;
     const int n_pos = n_prompt - 1;
     const int M = rows * n_pos;
     CWCHK(c, prefill_reserve(c, (size_t)M));
     CWCHK(c, KD(c, cw_launch_prefill_embed, c->d_ids, TGT, n_pos, c->embed, c->dec_pos, c->pf_x, M, D, c->st));
-    const int NL = c->d.dec_layers;
+    const int NL = align ? align_last_layer(c) + 1 : c->d.dec_layers;
     for (int l = 0; l < NL; ++l) {
         LayerW& L = c->dec[l];
         PrefillEpi ep;
@@ -1628,7 +1643,7 @@ static int run_prefill(cw_ctx* c, int rows, int n_prompt, int kv_div) {
         CWCHK(c, KD(c, cw_launch_prefill_ln, c->pf_x, c->pf_a, M, D, c->st));
         ep.mode = PF_QKV; ep.bias = L.bqkv; ep.out = c->pf_q; ep.sk = L.sk; ep.sv = L.sv; ep.D = D; ep.H = H; ep.cap = TGT; ep.n_pos = n_pos;
         CWCHK(c, KD(c, cw_launch_prefill_gemm, c->pf_a, L.wqkv, ep, M, 3 * D, D, c->st));
-        if (l + 1 == NL) break;
+        if (!align && l + 1 == NL) break;
         CWCHK(c, KD(c, cw_launch_prefill_attn, c->pf_q, L.sk, L.sv, c->pf_o, rows, n_pos, H, TGT, n_pos, 1, 1, c->st));
         memset(&ep, 0, sizeof(ep));
         ep.mode = PF_RESID; ep.bias = L.bo; ep.x = c->pf_x;
@@ -1636,7 +1651,13 @@ static int run_prefill(cw_ctx* c, int rows, int n_prompt, int kv_div) {
         CWCHK(c, KD(c, cw_launch_prefill_ln, c->pf_x, c->pf_a, M, D, c->st));
         ep.mode = PF_STORE; ep.bias = L.bq_c; ep.out = c->pf_q; ep.x = nullptr;
         CWCHK(c, KD(c, cw_launch_prefill_gemm, c->pf_a, L.wq_c, ep, M, D, D, c->st));
-        CWCHK(c, KD(c, cw_launch_prefill_attn, c->pf_q, L.ck, L.cv, c->pf_o, rows, n_pos, H, CW_N_CTX, CW_N_CTX, 0, kv_div, c->st));
+        PrefillAlign al;
+        memset(&al, 0, sizeof(al));
+        if (align && std::find(c->align_layers.begin(), c->align_layers.end(), l) != c->align_layers.end()) {
+            al.out = c->d_align; al.ml = c->d_align_ml; al.slot = c->d_align_slot + (size_t)l * H; al.n_align = c->d.n_align; al.rows = TGT;
+        }
+        CWCHK(c, KD(c, cw_launch_prefill_attn_align, c->pf_q, L.ck, L.cv, c->pf_o, rows, n_pos, H, CW_N_CTX, CW_N_CTX, 0, kv_div, al, c->st));
+        if (align && l + 1 == NL) break;
         ep.mode = PF_RESID; ep.bias = L.bo_c; ep.out = nullptr; ep.x = c->pf_x;
         CWCHK(c, KD(c, cw_launch_prefill_gemm, c->pf_o, L.wo_c, ep, M, D, D, c->st));
         CWCHK(c, KD(c, cw_launch_prefill_ln, c->pf_x, c->pf_a, M, D, c->st));
@@ -2029,10 +2050,17 @@ static int run_alignment(cw_ctx* c, const float* w, int B, int Ha, int rows_cap,
     return CW_OK;
 }
 
+static int token_timestamps(cw_ctx* c, const float* w, int32_t nb, int32_t L, int32_t n_prompt, const int32_t* num_frames, float* ts_out);
+
 int32_t cw_token_timestamps(cw_ctx* c, int32_t nb, int32_t L, int32_t n_prompt, const int32_t* num_frames, float* ts_out) {
-    const int Ha = c->d.n_align, TGT = c->d.max_target_positions, S = CW_N_CTX;
-    if (Ha <= 0) return fail(c, CW_ERR_STATE, "no alignment heads configured");
+    if (c->d.n_align <= 0) return fail(c, CW_ERR_STATE, "no alignment heads configured");
     if (nb < 1 || nb > c->last_nb || L != c->last_L) return fail(c, CW_ERR_STATE, "rows retained: %d x %d, asked %d x %d", c->last_nb, c->last_L, nb, L);
+    return token_timestamps(c, nullptr, nb, L, n_prompt, num_frames, ts_out);
+}
+
+// w: alignment rows of item 0 of the nb items in the [B][n_align][TGT][S] layout (null: the retained rows)
+static int token_timestamps(cw_ctx* c, const float* w, int32_t nb, int32_t L, int32_t n_prompt, const int32_t* num_frames, float* ts_out) {
+    const int Ha = c->d.n_align, TGT = c->d.max_target_positions, S = CW_N_CTX;
     for (size_t i = 0; i < (size_t)nb * (L + 1); ++i) ts_out[i] = 0.f;
     const int N = L - n_prompt;
     if (N <= 0) return CW_OK;                     // generation_whisper.py:336-338
@@ -2055,7 +2083,8 @@ int32_t cw_token_timestamps(cw_ctx* c, int32_t nb, int32_t L, int32_t n_prompt, 
     HIPCHK(c, hipStreamSynchronize(c->st));
     StageTimer tm(c, CW_STAGE_TIMESTAMPS);
     CWCHK(c, normalize_alignment(c));
-    CWCHK(c, run_alignment(c, c->align_cur ? c->align_cur : c->d_align, nb, Ha, TGT, S, n_prompt, N, c->d_ncols, c->d.median_filter_width, c->d_mean, c->d_std, c->d_mat));
+    if (!w) w = c->align_cur ? c->align_cur : c->d_align;
+    CWCHK(c, run_alignment(c, w, nb, Ha, TGT, S, n_prompt, N, c->d_ncols, c->d.median_filter_width, c->d_mean, c->d_std, c->d_mat));
     {   // workspace of the wave-local DTW, grown on demand (diagonal-major copy of the cost matrices)
         const size_t need = cw_dtw_skew_floats(nb, N, S);
         if (need > c->skew_cap) {
@@ -2229,6 +2258,87 @@ int32_t cw_transcribe_prompted(cw_ctx* c, int32_t B, const int32_t* num_frames, 
         memcpy(token_ts + (size_t)i * cap, out_ts[i].data(), (size_t)n * 4);
     }
     if (n_passes) *n_passes = passes;
+    return CW_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// forced alignment of known token sequences (include/crisperwhisper.h: cw_align_tokens)
+// ------------------------------------------------------------------------------------------------
+int32_t cw_align_tokens(cw_ctx* c, int32_t nb, const int32_t* num_frames, const int32_t* ids, int32_t ids_stride,
+                        const int32_t* n_ids, int32_t n_init, float* token_ts) {
+    const int TGT = c->d.max_target_positions, V = c->d.vocab_size, Ha = c->d.n_align;
+    // every argument is checked before anything is launched
+    if (Ha <= 0) return fail(c, CW_ERR_STATE, "align_tokens: no alignment heads configured");
+    if (!c->gen_set) return fail(c, CW_ERR_STATE, "cw_set_generation not called");
+    if (nb < 1 || nb > c->Bm) return fail(c, CW_ERR_INVALID, "align_tokens: nb=%d out of range (the context has %d rows)", nb, c->Bm);
+    if (!num_frames || !ids || !n_ids || !token_ts) return fail(c, CW_ERR_INVALID, "align_tokens: null argument");
+    if (n_init < 1 || n_init >= TGT) return fail(c, CW_ERR_INVALID, "align_tokens: n_init=%d out of range", n_init);
+    if (ids_stride < n_init + 1) return fail(c, CW_ERR_INVALID, "align_tokens: ids_stride=%d below n_init + 1", ids_stride);
+    int n_max = 0;
+    for (int b = 0; b < nb; ++b) {
+        const int n = n_ids[b];
+        if (n < n_init + 1 || n > TGT || n > ids_stride)
+            return fail(c, CW_ERR_INVALID, "align_tokens: row %d has %d ids; needs %d .. %d (init tokens + eos .. max_target_positions)",
+                        b, n, n_init + 1, TGT < ids_stride ? TGT : ids_stride);
+        if (num_frames[b] < 0 || num_frames[b] > CW_N_FRAMES)
+            return fail(c, CW_ERR_INVALID, "align_tokens: num_frames[%d]=%d out of range 0 .. %d", b, num_frames[b], CW_N_FRAMES);
+        for (int k = 0; k < n; ++k) {
+            const int tok = ids[(size_t)b * ids_stride + k];
+            if (tok < 0 || tok >= V) return fail(c, CW_ERR_INVALID, "align_tokens: row %d id %d at %d is outside the vocabulary (%d)", b, tok, k, V);
+            if (k >= n_init && k + 1 < n && tok == c->gen.eos_token_id)
+                return fail(c, CW_ERR_INVALID, "align_tokens: row %d has eos at %d before its last id", b, k);
+        }
+        n_max = n > n_max ? n : n_max;
+    }
+    struct PrefixScope {                     // no prompt_ids here: the prompt prefill must not engage in the loop's decode
+        cw_ctx* c; int saved;
+        ~PrefixScope() { c->pf_prefix = saved; }
+    } scope{c, c->pf_prefix};
+    c->pf_prefix = 0;
+    std::vector<int> all(nb), zeros(nb, 0), full(nb, CW_N_FRAMES);
+    for (int i = 0; i < nb; ++i) all[i] = i;
+    CWCHK(c, cw_encode(c, nb, all.data(), zeros.data(), full.data()));
+    const int Lmax = n_max - 1;                  // decoder input positions 0 .. Lmax-1 (the last id of a row is only predicted)
+    if (c->align_prefill && prefill_capable(c)) {
+        // one teacher-forced forward of every row over positions 0 .. Lmax-1 (prefill.hip); positions beyond a row's own
+        // length run on pad ids and are never read: causal self-attention keeps them out of the row's earlier positions
+        std::vector<int> dev((size_t)nb * TGT, c->gen.pad_token_id);
+        for (int b = 0; b < nb; ++b) memcpy(dev.data() + (size_t)b * TGT, ids + (size_t)b * ids_stride, (size_t)n_ids[b] * 4);
+        c->beam_K = 0;
+        c->align_cur = c->d_align;
+        HIPCHK(c, hipMemcpyAsync(c->d_ids, dev.data(), dev.size() * 4, hipMemcpyHostToDevice, c->st));
+        HIPCHK(c, hipStreamSynchronize(c->st));
+        StageTimer tm(c, CW_STAGE_DECODE);
+        CWCHK(c, run_prefill(c, nb, Lmax + 1, 1, true));
+        KCHK(c);
+        tm.stop();
+        ++c->align_prefill_runs;
+        c->last_L = Lmax;
+        c->last_nb = nb;
+        c->align_unnormalized = true;
+    } else {
+        // the per-position decoder step: a greedy decode whose every generated token is forced (cw_decode's `forced`)
+        std::vector<int> prompt((size_t)nb * n_init), forced((size_t)nb * TGT, -1), seq((size_t)nb * TGT), lens(nb);
+        for (int b = 0; b < nb; ++b) {
+            memcpy(prompt.data() + (size_t)b * n_init, ids + (size_t)b * ids_stride, (size_t)n_init * 4);
+            for (int k = n_init; k < n_ids[b]; ++k) forced[(size_t)b * TGT + k] = ids[(size_t)b * ids_stride + k];
+        }
+        CWCHK(c, cw_decode(c, nb, prompt.data(), n_init, n_max, 0, forced.data(), seq.data(), lens.data(), nullptr));
+        if (c->last_L < Lmax) return fail(c, CW_ERR_STATE, "align_tokens: the forced decode stopped at %d of %d positions", c->last_L, Lmax);
+    }
+    // timestamps over each row's own token count: a row's z-score statistics, filter and DTW see its own rows only, so its
+    // timestamps do not depend on the other rows of the batch.  Consecutive rows of one length share one pass of the stages
+    // (per-item work in every one of them; num_frames >= 0 makes the one- and two-fold slicing of the columns agree).
+    CWCHK(c, normalize_alignment(c));
+    const float* w0 = c->align_cur ? c->align_cur : c->d_align;
+    std::vector<float> ts;
+    for (int b0 = 0, b1; b0 < nb; b0 = b1) {
+        for (b1 = b0 + 1; b1 < nb && n_ids[b1] == n_ids[b0]; ++b1) {}
+        const int L = n_ids[b0] - 1, n = b1 - b0;
+        ts.resize((size_t)n * (L + 1));
+        CWCHK(c, token_timestamps(c, w0 + (size_t)b0 * Ha * TGT * CW_N_CTX, n, L, n_init, num_frames + b0, ts.data()));
+        for (int r = 0; r < n; ++r) memcpy(token_ts + (size_t)(b0 + r) * ids_stride, ts.data() + (size_t)r * (L + 1), (size_t)(L + 1) * 4);
+    }
     return CW_OK;
 }
 
@@ -2431,6 +2541,10 @@ int32_t cw_set_option(cw_ctx* c, const char* name, int32_t value) {
         c->prompt_prefill = value != 0;
         return CW_OK;
     }
+    if (!strcmp(name, "align_prefill")) {    // 0: cw_align_tokens runs its forward through the per-position decoder step (A/B)
+        c->align_prefill = value != 0;
+        return CW_OK;
+    }
     if (!strcmp(name, "cross_kv_fp8")) {
         if (!value) { c->kv8 = false; return CW_OK; }
         if (!c->bf16) return fail(c, CW_ERR_INVALID, "cross_kv_fp8 needs the bf16 engine (the f32 engine is the parity mode)");
@@ -2613,6 +2727,43 @@ int32_t cw_test_prefill_attention(cw_ctx* c, int32_t rows, int32_t n_q, int32_t 
     if (r == CW_OK) { hipError_t er = hipStreamSynchronize(c->st); if (er != hipSuccess) r = fail(c, CW_ERR_HIP, "test_prefill_attention: %s", hipGetErrorString(er)); }
     if (r == CW_OK) r = download_T(c, dO, 0, out, nq);
     hipFree(dQ); hipFree(dK); hipFree(dV); hipFree(dO);
+    return r;
+}
+
+// cw_test_prefill_align_attention: the cross mode of prefill_attn_kernel with head align_head as alignment slot 0.  q [rows * n_q]
+// [H * 64], k / v [rows / kv_div][H][n_keys][64] (f32, rounded to the 16-bit type) -> out [rows * n_q][H * 64] and align
+// [rows][n_q][n_keys]: the recorded rows after align_normalize_kernel (the softmax weights of head align_head).
+int32_t cw_test_prefill_align_attention(cw_ctx* c, int32_t rows, int32_t n_q, int32_t H, int32_t n_keys, int32_t kv_div,
+                                        int32_t align_head, const float* q, const float* k, const float* v, float* out, float* align) {
+    if (!c->bf16) return fail(c, CW_ERR_INVALID, "test_prefill_align_attention: 16-bit engines only");
+    if (rows < 1 || rows > 64 || n_q < 1 || n_q > 512 || H < 1 || H > 64 || n_keys < 1 || n_keys > 4096 || kv_div < 1 || rows % kv_div ||
+        align_head < 0 || align_head >= H || !q || !k || !v || !out || !align)
+        return fail(c, CW_ERR_INVALID, "test_prefill_align_attention: bad arguments");
+    const size_t e = c->esz, nq = (size_t)rows * n_q * H * 64, nkv = (size_t)(rows / kv_div) * H * n_keys * 64;
+    const size_t na = (size_t)rows * n_q * n_keys, nml = (size_t)rows * n_q * ATT_NS * 2;
+    std::vector<int> slot(H, -1);
+    slot[align_head] = 0;
+    void *dQ = nullptr, *dK = nullptr, *dV = nullptr, *dO = nullptr;
+    float *dA = nullptr, *dML = nullptr;
+    int* dS = nullptr;
+    int r = CW_OK;
+    if (hipMalloc(&dQ, nq * e) != hipSuccess || hipMalloc(&dK, nkv * e) != hipSuccess || hipMalloc(&dV, nkv * e) != hipSuccess ||
+        hipMalloc(&dO, nq * e) != hipSuccess || hipMalloc((void**)&dA, na * 4) != hipSuccess || hipMalloc((void**)&dML, nml * 4) != hipSuccess ||
+        hipMalloc((void**)&dS, (size_t)H * 4) != hipSuccess) r = fail(c, CW_ERR_NOMEM, "test_prefill_align_attention: hipMalloc failed");
+    if (r == CW_OK) r = upload_T(c, dQ, 0, q, nq);
+    if (r == CW_OK) r = upload_T(c, dK, 0, k, nkv);
+    if (r == CW_OK) r = upload_T(c, dV, 0, v, nkv);
+    if (r == CW_OK && (hipMemcpy(dS, slot.data(), (size_t)H * 4, hipMemcpyHostToDevice) != hipSuccess ||
+                       hipMemset(dA, 0xff, na * 4) != hipSuccess || hipMemset(dML, 0xff, nml * 4) != hipSuccess))
+        r = fail(c, CW_ERR_HIP, "test_prefill_align_attention: copy");
+    PrefillAlign al;
+    al.out = dA; al.ml = dML; al.slot = dS; al.n_align = 1; al.rows = n_q;
+    if (r == CW_OK) r = KD(c, cw_launch_prefill_attn_align, dQ, dK, dV, dO, rows, n_q, H, n_keys, n_keys, 0, kv_div, al, c->st);
+    if (r == CW_OK) r = KD(c, cw_launch_align_normalize, dA, dML, rows, 1, n_q, n_q, n_keys, c->st);
+    if (r == CW_OK) { hipError_t er = hipStreamSynchronize(c->st); if (er != hipSuccess) r = fail(c, CW_ERR_HIP, "test_prefill_align_attention: %s", hipGetErrorString(er)); }
+    if (r == CW_OK) r = download_T(c, dO, 0, out, nq);
+    if (r == CW_OK && hipMemcpy(align, dA, na * 4, hipMemcpyDeviceToHost) != hipSuccess) r = fail(c, CW_ERR_HIP, "test_prefill_align_attention: copy");
+    hipFree(dQ); hipFree(dK); hipFree(dV); hipFree(dO); hipFree(dA); hipFree(dML); hipFree(dS);
     return r;
 }
 

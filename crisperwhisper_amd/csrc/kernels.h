@@ -327,6 +327,14 @@ struct PrefillEpi {
     void* sk; void* sv;    // PF_QKV: self cache [rows][H][cap][64]; row = m / n_pos, position = m % n_pos
     int D, H, cap, n_pos;
 };
+// prefill_attn_kernel, cross mode: alignment rows of the heads with slot[h] >= 0, in the decode step's layout -- out
+// [rows][n_align][rows_cap][n_keys] un-normalised exp(s - m), ml [rows][n_align][rows_cap][ATT_NS][2]; out null: none
+struct PrefillAlign {
+    float* out;
+    float* ml;
+    const int* slot;       // [H] this layer's alignment slot per head, -1: not an alignment head
+    int n_align, rows;     // rows = alignment rows per (row, slot) (max_target_positions); query position p -> row p
+};
 
 #define CW_DTYPE_KERNEL_DECLS \
     int cw_launch_gemm(bool bf16, int epi, const AParams& ap, const void* W, int M, int N, int K, const EpiParams& ep, hipStream_t st); \
@@ -383,6 +391,7 @@ struct PrefillEpi {
     int cw_launch_prefill_ln(const float* x, void* out, int M, int D, hipStream_t st); \
     int cw_launch_prefill_gemm(const void* A, const void* W, const PrefillEpi& ep, int M, int N, int K, hipStream_t st); \
     int cw_launch_prefill_attn(const void* Q, const void* K, const void* V, void* out, int rows, int n_q, int H, int cap, int n_keys, int causal, int kv_div, hipStream_t st); \
+    int cw_launch_prefill_attn_align(const void* Q, const void* K, const void* V, void* out, int rows, int n_q, int H, int cap, int n_keys, int causal, int kv_div, const PrefillAlign& al, hipStream_t st); \
     int cw_launch_attn_encoder(bool bf16, const void* Q, const void* K, const void* V, void* out, int B, int H, int S, int S_pad, hipStream_t st); \
     int cw_launch_attn_decode(bool bf16, const DecAttnParams& p, hipStream_t st); \
     int cw_launch_attn_cross_split(bool bf16, const CrossSplitParams& p, hipStream_t st); \

@@ -7,8 +7,10 @@
 //   prefill_gemm_kernel    C = A W^T + bias, MFMA 16x16x32 over fragment-major packed W (gemm.hip: wfrag_pack_kernel), epilogues:
 //                          16-bit store | q store + self-cache scatter of k / v | f32 residual add | erf GELU to 16-bit
 //   prefill_attn_kernel    flash attention of 16 query positions of one (row, head): online softmax in f32, MFMA for Q K^T and
-//                          P V; causal over the row's own self cache, or every key of the row's cross K/V cache
+//                          P V; causal over the row's own self cache, or every key of the row's cross K/V cache; in cross mode
+//                          it can record the alignment heads' attention rows (forced alignment, engine.hip: cw_align_tokens)
 #include <hip/hip_runtime.h>
+#include <string.h>
 #include "kernels.h"
 
 namespace CW_NS {
@@ -108,7 +110,7 @@ __global__ __launch_bounds__(256) void prefill_gemm_kernel(const bf16_t* __restr
 // [kv rows][H][cap][64], kv row = row / kv_div; causal: query position i sees keys 0 .. i, else keys 0 .. n_keys - 1.
 __global__ __launch_bounds__(64) void prefill_attn_kernel(const bf16_t* __restrict__ Q, const bf16_t* __restrict__ Kc,
                                                           const bf16_t* __restrict__ Vc, bf16_t* __restrict__ out, int n_q, int H,
-                                                          int cap, int n_keys, int causal, int kv_div) {
+                                                          int cap, int n_keys, int causal, int kv_div, PrefillAlign al) {
     __shared__ bf16_t Ps[16][32 + 8];
     __shared__ bf16_t Vs[32][64 + 8];
     const int lane = threadIdx.x, l15 = lane & 15, g = lane >> 4;
@@ -202,6 +204,40 @@ __global__ __launch_bounds__(64) void prefill_attn_kernel(const bf16_t* __restri
         for (int dt = 0; dt < 4; ++dt)
             Act<bf16_t>::st(out + ((size_t)row * n_q + qi) * D + h * 64 + dt * 16 + l15, o[dt][r] * inv);
     }
+    // Alignment heads (cross mode only): a second pass over the keys, once the final (m, l) of every query is known, writes
+    // exp(s - m) for query position qi into alignment row qi of slot al.slot[h] -- the row the decode step at position qi
+    // writes -- and (m, l) into split 0 of its ATT_NS statistics (the other splits (m, 0)), i.e. what a one-split decode
+    // launch leaves for align_normalize_kernel.  S is recomputed with the same MFMA sequence, so it equals the first pass's.
+    // Every other head leaves here: the branch is uniform per block.
+    const int slot = (al.out && !causal) ? al.slot[h] : -1;
+    if (slot < 0) return;
+    size_t rowi[4];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) rowi[r] = ((size_t)row * al.n_align + slot) * al.rows + (i0 + g * 4 + r);
+    for (int j0 = 0; j0 < kend; j0 += 32) {
+#pragma unroll
+        for (int hh = 0; hh < 2; ++hh) {
+            const int j = j0 + hh * 16 + l15;
+            f32x4_t s = f32x4_t{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int c = 0; c < 2; ++c) {
+                const bf16x8_t kb = j < kend ? *(const bf16x8_t*)(Kc + kvo + (size_t)j * 64 + c * 32 + g * 8) : zero;
+                s = cw_mfma_16x16x32(qa[c], kb, s);
+            }
+            if (j >= kend) continue;
+#pragma unroll
+            for (int r = 0; r < 4; ++r)
+                if (i0 + g * 4 + r < n_q) al.out[rowi[r] * n_keys + j] = __expf(s[r] - mrow[r]);
+        }
+    }
+    if (l15 < ATT_NS) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r)
+            if (i0 + g * 4 + r < n_q) {
+                al.ml[(rowi[r] * ATT_NS + l15) * 2] = mrow[r];
+                al.ml[(rowi[r] * ATT_NS + l15) * 2 + 1] = l15 == 0 ? lrow[r] : 0.f;
+            }
+    }
 }
 
 int cw_launch_prefill_embed(const int* ids, int ids_stride, int n_pos, const void* embed, const float* pos_embed, float* x,
@@ -228,9 +264,18 @@ int cw_launch_prefill_gemm(const void* A, const void* W, const PrefillEpi& ep, i
 
 int cw_launch_prefill_attn(const void* Q, const void* K, const void* V, void* out, int rows, int n_q, int H, int cap, int n_keys,
                            int causal, int kv_div, hipStream_t st) {
+    PrefillAlign none;
+    memset(&none, 0, sizeof(none));
+    return cw_launch_prefill_attn_align(Q, K, V, out, rows, n_q, H, cap, n_keys, causal, kv_div, none, st);
+}
+
+// al.out null: no alignment rows (the prompt prefill).  Otherwise cross mode only, n_q <= al.rows (alignment rows per slot).
+int cw_launch_prefill_attn_align(const void* Q, const void* K, const void* V, void* out, int rows, int n_q, int H, int cap,
+                                 int n_keys, int causal, int kv_div, const PrefillAlign& al, hipStream_t st) {
     if (rows < 1 || n_q < 1 || H < 1 || n_keys < 1 || n_keys > cap || kv_div < 1 || (causal && n_keys < n_q)) return CW_ERR_INVALID;
+    if (al.out && (causal || !al.ml || !al.slot || al.n_align < 1 || n_q > al.rows)) return CW_ERR_INVALID;
     hipLaunchKernelGGL(prefill_attn_kernel, dim3((n_q + 15) / 16, H, rows), dim3(64), 0, st, (const bf16_t*)Q, (const bf16_t*)K,
-                       (const bf16_t*)V, (bf16_t*)out, n_q, H, cap, n_keys, causal, kv_div);
+                       (const bf16_t*)V, (bf16_t*)out, n_q, H, cap, n_keys, causal, kv_div, al);
     return CW_OK;
 }
 

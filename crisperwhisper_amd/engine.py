@@ -297,6 +297,32 @@ class Engine:
         return ([toks[i, :lens[i]].astype(np.int64) for i in range(nb)], [ts[i, :lens[i]].copy() for i in range(nb)],
                 int(passes.value))
 
+    def align_tokens(self, num_frames, ids, n_init: int) -> List[np.ndarray]:
+        """Forced alignment (cw_align_tokens) of the resident feature items 0 .. len(ids)-1: ``ids[b]`` is row b's whole
+        sequence, the ``n_init`` init tokens, the transcript and eos.  Returns one float32 array of len(ids[b]) token
+        timestamps per row (cw_token_timestamps' convention)."""
+        nb = len(ids)
+        n = _i32([len(r) for r in ids])
+        stride = max(1, int(n.max()) if nb else 1)
+        table = np.zeros((nb, stride), dtype=np.int32)
+        for b, r in enumerate(ids):
+            r = np.asarray(r, dtype=np.int64)
+            if r.size and (r.min() < 0 or r.max() >= self.spec.vocab_size):    # before the int32 table could wrap them
+                raise ValueError(f"row {b}: token id outside the vocabulary (0 .. {self.spec.vocab_size - 1})")
+            table[b, :len(r)] = r
+        nf = _i32(num_frames)
+        ts = np.zeros((nb, stride), dtype=np.float32)
+        self._chk(self.lib.cw_align_tokens(self.ctx, nb, _ptr(nf), _ptr(table), stride, _ptr(n), int(n_init), _ptr(ts)))
+        return [ts[b, :n[b]].copy() for b in range(nb)]
+
+    def align_prefill_runs(self) -> int:
+        """cw_align_prefill_runs: align_tokens calls of this engine whose forward ran as the batched prefill."""
+        return int(self.lib.cw_align_prefill_runs(self.ctx))
+
+    def set_align_prefill(self, on: bool):
+        """cw_set_option "align_prefill": 0 runs cw_align_tokens' forward through the per-position decoder step."""
+        self._chk(self.lib.cw_set_option(self.ctx, b"align_prefill", 1 if on else 0))
+
     # ------------------------------------------------------------------ beam search (device half; host half: generation.beam_search)
     def beam_begin(self, prompt: np.ndarray, num_beams: int, max_length: int, min_new_tokens: int = 0):
         prompt = _i32(prompt)
@@ -422,6 +448,18 @@ class Engine:
         self._chk(self.lib.cw_test_prefill_attention(self.ctx, rows, n_q, H, cap, int(n_keys), 1 if causal else 0, int(kv_div),
                                                      _ptr(q), _ptr(k), _ptr(v), _ptr(out)))
         return out
+
+    def test_prefill_align_attention(self, q, k, v, kv_div=1, align_head=0):
+        """cw_test_prefill_align_attention: q [rows][n_q][H*64], k / v [rows / kv_div][H][n_keys][64] -> (out [rows][n_q][H*64],
+        align [rows][n_q][n_keys]: head align_head's recorded rows, normalised)."""
+        q, k, v = (np.ascontiguousarray(t, np.float32) for t in (q, k, v))
+        rows, n_q, _ = q.shape
+        H, n_keys = k.shape[1], k.shape[2]
+        out = np.zeros_like(q)
+        align = np.zeros((rows, n_q, n_keys), np.float32)
+        self._chk(self.lib.cw_test_prefill_align_attention(self.ctx, rows, n_q, H, n_keys, int(kv_div), int(align_head),
+                                                           _ptr(q), _ptr(k), _ptr(v), _ptr(out), _ptr(align)))
+        return out, align
 
     def test_cross_attention(self, q, k, v, kv_div=1, align_head=0):
         """One launch of the key-split cross-attention decode kernel (cw_test_cross_attention): q [B][H][64] pre-scaled,

@@ -522,3 +522,59 @@ def _seek_loop(engine, spec, n_items, num_frames, init, n_prompt, max_new_tokens
             segments[i].extend(segs)
     if stats is not None:
         stats["generate_calls"] = stats.get("generate_calls", 0) + n_calls
+
+
+def check_transcript_ids(spec, ids) -> np.ndarray:
+    """A transcript for ``align``: a 1-D integer sequence (list, numpy array or torch tensor) of text token ids, without the
+    init tokens and eos; timestamp tokens, as a generation emits them, are kept.  Special tokens (eos and the tags up to
+    <|notimestamps|>) and ids outside the vocabulary raise."""
+    if hasattr(ids, "detach") and hasattr(ids, "cpu"):
+        ids = ids.detach().cpu().numpy()
+    if isinstance(ids, (str, bytes)):
+        raise TypeError("a transcript here is a sequence of token ids; encode text with the tokenizer first")
+    a = np.asarray(ids)
+    if a.ndim != 1 or (a.size and not np.issubdtype(a.dtype, np.integer)):
+        raise ValueError(f"a transcript must be a 1-D sequence of integer token ids, got shape {a.shape} dtype {a.dtype}")
+    a = a.astype(np.int64)
+    bad = a[(a < 0) | (a >= spec.vocab_size)]
+    if bad.size:
+        raise ValueError(f"token id {int(bad[0])} is outside the vocabulary (0 .. {spec.vocab_size - 1})")
+    special = a[(a >= spec.eos_token_id) & (a < spec.timestamp_begin)]
+    if special.size:
+        raise ValueError(f"token id {int(special[0])} is a special token; a transcript holds text (and timestamp) tokens only "
+                         "(the init tokens and eos are added here)")
+    return a
+
+
+def align(engine: Engine, n_items: int, num_frames, transcripts, *, language: Optional[str] = None,
+          task: Optional[str] = None):
+    """Forced alignment of known transcripts to the ``n_items`` 30 s feature windows resident in the engine.
+
+    Row b is the decoder input <|startoftranscript|><|lang|><|task|> ++ transcripts[b] ++ eos, with the init tokens resolved by
+    ``resolve_prompt`` exactly as for ``generate`` (``language=None``: detected per item).  The engine runs one teacher-forced
+    forward (cw_align_tokens) and the token-timestamp stages on it.  Returns {"sequences": list of int64 arrays (the
+    transcripts), "token_timestamps": list of float32 arrays, one timestamp per transcript token} -- the fields the pipeline
+    hands to ``collate.decode_asr``, as ``generate`` returns them for its own tokens."""
+    spec = engine.spec
+    texts = [check_transcript_ids(spec, t) for t in transcripts]
+    if len(texts) != n_items:
+        raise ValueError(f"{len(texts)} transcripts for {n_items} items")
+    if n_items > engine.max_batch:
+        raise ValueError(f"{n_items} items exceed the engine's {engine.max_batch} rows")
+    toks, detect = resolve_prompt(spec, language, task)
+    if detect and not spec.lang_to_id:
+        raise ValueError("Cannot detect language for an English-only checkpoint: the generation config has no `lang_to_id`.")
+    n_init = len(toks)
+    for b, t in enumerate(texts):
+        if n_init + len(t) + 1 > spec.max_target_positions:
+            raise ValueError(f"transcript {b}: {n_init} init tokens + {len(t)} tokens + eos exceed max_target_positions "
+                             f"({spec.max_target_positions})")
+    num_frames = np.asarray(num_frames, dtype=np.int64)
+    if detect:
+        engine.encode(list(range(n_items)), np.zeros(n_items, np.int64), np.full(n_items, N_FRAMES, np.int64))
+        inits = [init_tokens(spec, language, task, lang_id=l) for l in detect_language(engine, n_items)]
+    else:
+        inits = [init_tokens(spec, language, task)] * n_items
+    rows = [np.concatenate([np.asarray(i, np.int64), t, [spec.eos_token_id]]) for i, t in zip(inits, texts)]
+    ts = engine.align_tokens(num_frames, rows, n_init)
+    return {"sequences": texts, "token_timestamps": [s[n_init:n_init + len(t)] for s, t in zip(ts, texts)]}

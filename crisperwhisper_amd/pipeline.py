@@ -295,6 +295,7 @@ class CrisperWhisperPipeline:
         if isinstance(tokenizer, str):
             tokenizer = collate.Vocabulary.from_pretrained(tokenizer)
         self.vocab = tokenizer if isinstance(tokenizer, collate.Vocabulary) else collate.Vocabulary.from_hf_tokenizer(tokenizer)
+        self.tokenizer = tokenizer              # align(): a str transcript needs a tokenizer with `encode`
         self.sampling_rate = getattr(feature_extractor, "sampling_rate", audio.SAMPLING_RATE)
         if feature_extractor is not None and getattr(feature_extractor, "feature_size", self.bundle.spec.n_mels) != self.bundle.spec.n_mels:
             raise ValueError("feature_extractor.feature_size does not match model.config.num_mel_bins")
@@ -464,6 +465,62 @@ class CrisperWhisperPipeline:
         self.stats["last_call_phase_s"] = {"load": t_ph[1] - t_ph[0], "local_batches": t_ph[2] - t_ph[1], "gather": t_ph[3] - t_ph[2],
                                            "collate_all_chunks": t_ph[4] - t_ph[3], "local_chunks": len(mine), "all_chunks": len(windows)}
         return {"text": text, "chunks": words}
+
+
+    # -- forced alignment of known transcripts ------------------------------------------------------
+    def _transcript_ids(self, transcript) -> np.ndarray:
+        if isinstance(transcript, str):
+            enc = getattr(self.tokenizer, "encode", None)
+            if enc is None or isinstance(self.tokenizer, collate.Vocabulary):
+                raise ValueError("a text transcript needs a tokenizer with `encode` (a transformers WhisperTokenizer); this "
+                                 "pipeline's Vocabulary has no BPE merges: pass the transcript as token ids")
+            return generation.check_transcript_ids(self.bundle.spec, enc(transcript, add_special_tokens=False))
+        return generation.check_transcript_ids(self.bundle.spec, transcript)
+
+    def align(self, inputs, transcripts, language: Optional[str] = None, task: Optional[str] = None, **kwargs):
+        """Word timestamps for known transcripts: ``inputs`` in any form ``__call__`` takes (one, or a list), each at most
+        30 s; ``transcripts`` one per input, a ``str`` (needs a transformers tokenizer) or token ids without special
+        tokens.  ``language`` / ``task`` resolve like ``generate_kwargs`` in ``__call__`` (``language=None``: detected per
+        item).  Returns {"text", "chunks": [{"text", "timestamp": (start, end)}]} like ``__call__(..., return_timestamps=
+        "word")``, or a list of them for a list of inputs; lists run in batches of up to the pipeline's decoder rows."""
+        gk = dict(kwargs.pop("generate_kwargs", None) or {})
+        if "prompt_ids" in kwargs or "prompt_ids" in gk:
+            raise ValueError("prompt_ids is not accepted by align: the decoder input is the init tokens and the transcript")
+        if kwargs:
+            raise TypeError(f"align() got unexpected keyword arguments {sorted(kwargs)}")
+        unknown = set(gk) - {"language", "task"}
+        if unknown:
+            raise ValueError(f"align() takes only language / task generate_kwargs, got {sorted(unknown)}")
+        language = language if language is not None else gk.get("language")
+        task = task if task is not None else gk.get("task")
+        single = not isinstance(inputs, (list, tuple))
+        if single:
+            inputs, transcripts = [inputs], [transcripts]
+        elif not isinstance(transcripts, (list, tuple)) or len(transcripts) != len(inputs):
+            raise ValueError(f"{len(inputs)} inputs need a list of {len(inputs)} transcripts, got "
+                             f"{len(transcripts) if isinstance(transcripts, (list, tuple)) else type(transcripts).__name__}")
+        ids = [self._transcript_ids(t) for t in transcripts]
+        generation.resolve_prompt(self.bundle.spec, language, task)        # refuses a bad language / task before any audio work
+        pcms = []
+        for k, x in enumerate(inputs):
+            pcm = self._load(x)
+            if len(pcm) > N_SAMPLES:
+                raise ValueError(f"input {k} is {len(pcm) / self.sampling_rate:.2f} s long: align takes at most 30 s "
+                                 f"({N_SAMPLES} samples) per input; long-form alignment is not implemented")
+            pcms.append(pcm)
+        eng = self.engine
+        per = max(1, eng.max_batch)
+        results = []
+        for b0 in range(0, len(pcms), per):
+            idx = list(range(b0, min(len(pcms), b0 + per)))
+            _, nf = eng.mel([pcms[i] for i in idx])
+            out = generation.align(eng, len(idx), nf, [ids[i] for i in idx], language=language, task=task)
+            for k in range(len(idx)):
+                text, words = collate.decode_asr(self.vocab, [{"tokens": out["sequences"][k],
+                                                               "token_timestamps": out["token_timestamps"][k]}],
+                                                 time_precision=0.02, return_timestamps="word")
+                results.append({"text": text, "chunks": words})
+        return results[0] if single else results
 
 
 def pipeline(task: str = "automatic-speech-recognition", model=None, tokenizer=None, feature_extractor=None, **kwargs):

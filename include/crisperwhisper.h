@@ -226,6 +226,23 @@ void cw_beam_host_free(cw_beam_host* s);
 int32_t cw_token_timestamps(cw_ctx* ctx, int32_t nb, int32_t L, int32_t n_prompt, const int32_t* num_frames,
                             float* ts_out);
 
+/* cw_align_tokens: forced alignment of known token sequences.  Encodes the nb resident feature items (cw_mel /
+ * cw_set_features), runs one teacher-forced decoder forward of row b over ids[b][0 .. n_ids[b]-2] (the n_init init tokens
+ * <|startoftranscript|><|lang|>[<|task|>], then the transcript; the last id, eos, is only predicted), records the alignment
+ * heads' cross-attention at exactly the positions a finished greedy generation of the same sequence leaves them, and runs
+ * the cw_token_timestamps stages on every row over its own n_ids[b] - 1 rows, so a row's result does not depend on the other
+ * rows of the batch.  token_ts [nb][ids_stride]: entries 0 .. n_ids[b]-1 of row b in cw_token_timestamps' convention (the init
+ * tokens 0, the eos the time of the token before it); the rest is not written.
+ * On the 16-bit engines with the 16-bit cross cache the forward is one batched prefill (csrc/prefill.hip) that stops after the
+ * last layer holding an alignment head; the f32 engine, the e4m3 cross cache and cw_set_option "align_prefill" = 0 run it
+ * through the per-position decoder step (cw_decode with every generated token forced).
+ * CW_ERR_INVALID, before anything is launched: nb outside 1 .. max_batch, an id outside the vocabulary, eos before a row's
+ * last id, n_ids[b] outside n_init + 1 .. min(max_target_positions, ids_stride), num_frames[b] outside 0 .. 3000.        */
+int32_t cw_align_tokens(cw_ctx* ctx, int32_t nb, const int32_t* num_frames, const int32_t* ids, int32_t ids_stride,
+                        const int32_t* n_ids, int32_t n_init, float* token_ts);
+/* cw_align_prefill_runs: how many cw_align_tokens calls of this context ran their forward as the batched prefill.        */
+int32_t cw_align_prefill_runs(cw_ctx* ctx);
+
 /* ---- stand-alone differential-test entry points for the alignment kernels ---------------------------- */
 /* attn [B][Ha][N][M] -> mat [B][N][M] (z-score, median(width), head mean); n_cols[b] <= M columns used.  */
 int32_t cw_align_matrix(cw_ctx* ctx, const float* attn, int32_t B, int32_t Ha, int32_t N, int32_t M,
@@ -294,6 +311,12 @@ int32_t cw_test_prefill_gemm(cw_ctx* ctx, int32_t mode, int32_t M, int32_t N, in
                              const float* bias, float* out);
 int32_t cw_test_prefill_attention(cw_ctx* ctx, int32_t rows, int32_t n_q, int32_t H, int32_t cap, int32_t n_keys, int32_t causal,
                                   int32_t kv_div, const float* q, const float* k, const float* v, float* out);
+/* cw_test_prefill_align_attention: the cross mode of the prefill attention with head align_head recording alignment rows (slot
+ * 0): q [rows * n_q][H * 64], k / v [rows / kv_div][H][n_keys][64] -> out [rows * n_q][H * 64] and align [rows][n_q][n_keys],
+ * the recorded rows after the alignment normalisation (softmax weights of that head).  16-bit engines only.                */
+int32_t cw_test_prefill_align_attention(cw_ctx* ctx, int32_t rows, int32_t n_q, int32_t H, int32_t n_keys, int32_t kv_div,
+                                        int32_t align_head, const float* q, const float* k, const float* v, float* out,
+                                        float* align);
 int32_t cw_test_cross_attention(cw_ctx* ctx, int32_t B, int32_t H, int32_t S, int32_t kv_div, const float* q, const float* k,
                                 const float* v, int32_t align_head, float* part_o, float* part_ml, float* align,
                                 float* align_ml);
