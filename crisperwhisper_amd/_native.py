@@ -80,6 +80,9 @@ _SIGS = {
     "cw_transcribe_prompted": (_I, [_P, _I, _P, C.POINTER(TranscribeCfg), _P, _I, _P, _P, _P, _I, _P]),
     "cw_align_tokens": (_I, [_P, _I, _P, _P, _I, _P, _I, _P]),
     "cw_align_prefill_runs": (_I, [_P]),
+    "cw_score_tokens": (_I, [_P, _I, _I, _P, _I, _P, _I, _P, _P, _P]),
+    "cw_align_score_tokens": (_I, [_P, _I, _P, _P, _I, _P, _I, _P, _P, _P, _P]),
+    "cw_score_prefill_runs": (_I, [_P]),
     "cw_align_matrix": (_I, [_P, _P, _I, _I, _I, _I, _P, _I, _P]),
     "cw_dtw": (_I, [_P, _P, _I, _I, _P, _P, _P]),
     "cw_adjust_pauses": (_I, [_P, _P, _P, _I, C.c_double]),
@@ -94,6 +97,8 @@ _SIGS = {
     "cw_collate_feed": (_I, [_P, _P, _I, _P, _I, _I, C.c_double, C.c_double, C.c_double]),
     "cw_collate_finish": (_I, [_P, _P, _P, _P, _P]),
     "cw_collate_get": (_I, [_P, _P, _P, _P, _P, _P]),
+    "cw_collate_token_groups_total": (C.c_int64, [_P]),
+    "cw_collate_get_token_groups": (_I, [_P, _P, _P]),
     "cw_collate_free": (None, [_P]),
     "cw_set_option": (_I, [_P, C.c_char_p, _I]),
     "cw_test_set_option": (_I, [C.c_char_p, _I]),
@@ -109,6 +114,8 @@ _SIGS = {
     "cw_test_prefill_gemm": (_I, [_P, _I, _I, _I, _I, _P, _P, _P, _P]),
     "cw_test_prefill_attention": (_I, [_P, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P]),
     "cw_test_prefill_align_attention": (_I, [_P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P]),
+    "cw_test_score_head": (_I, [_P, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "cw_time_score_head": (_I, [_P, _I, _I, _I, _P]),
     "cw_test_sample": (_I, [_P, _I, _P, _P, _I, _I, _I, _I, _P]),
     "cw_stage_times": (_I, [_P, _P, _P, _I]),
     "cw_time_kernel": (_I, [_P, _I, _I, _I, _P, _P]),

@@ -171,11 +171,13 @@ def _native_vocab(vocab: "Vocabulary"):
 
 
 def decode_asr(vocab: Vocabulary, model_outputs: List[dict], time_precision: float = 0.02, warn=None,
-               return_timestamps="word"):
+               return_timestamps="word", return_token_groups: bool = False):
     """model_outputs: [{"tokens", "token_timestamps", optional "stride": (len_s, left_s, right_s)}] in audio
     order -> (text, [{"text", "timestamp": (start, end)}]).  Runs in libcrisperwhisper.so (csrc/collate.cpp).
     ``return_timestamps="word"``: word chunks; ``True``: one chunk per timestamp-delimited segment (token_timestamps
-    not needed; a missing boundary is None, as in the reference)."""
+    not needed; a missing boundary is None, as in the reference).
+    ``return_token_groups=True``: a third result, per chunk the list of its tokens' positions in the concatenation of all
+    ``model_outputs`` token arrays -- the collator's own grouping (cw_collate_get_token_groups)."""
     if return_timestamps not in ("word", True):
         raise ValueError("return_timestamps must be 'word' or True")
     seg = return_timestamps is True
@@ -215,6 +217,12 @@ def decode_asr(vocab: Vocabulary, model_outputs: List[dict], time_precision: flo
             return None if x != x else float(x)                  # NaN = no timestamp predicted (segment mode)
         words = [{"text": raw[offs[k]:offs[k + 1]].decode("utf-8"), "timestamp": (_t(starts[k]), _t(ends[k]))}
                  for k in range(n)]
+        if return_token_groups:
+            goffs = np.zeros(n + 1, dtype=np.int64)
+            gidx = np.zeros(max(int(lib.cw_collate_token_groups_total(col)), 1), dtype=np.int32)
+            lib.cw_collate_get_token_groups(col, goffs.ctypes.data_as(C.c_void_p), gidx.ctypes.data_as(C.c_void_p))
+            groups = [[int(i) for i in gidx[goffs[k]:goffs[k + 1]]] for k in range(n)]
+            return text.tobytes()[:tb.value].decode("utf-8"), words, groups
         return text.tobytes()[:tb.value].decode("utf-8"), words
     finally:
         lib.cw_collate_free(col)

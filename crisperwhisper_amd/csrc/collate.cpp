@@ -106,7 +106,7 @@ struct cw_vocab {
     }
 };
 
-struct Word { U32 text; double start, end; };
+struct Word { U32 text; double start, end; std::vector<int> src; };   // src: the word's tokens as indices into the fed tokens
 
 struct cw_collator {
     const cw_vocab* v;
@@ -118,19 +118,23 @@ struct cw_collator {
     double time_offset;
     std::vector<std::vector<int>> pending;
     std::vector<std::vector<Span>> pending_ts;
+    std::vector<std::vector<int>> pending_src;   // index of every pending token in the concatenation of all fed token arrays
+    long long fed = 0;                   // tokens fed so far (cw_collate_feed calls before the current one)
     bool has_open; double open_start;
     bool skip;
     bool warned;
     int mode;                            // 0: word chunks (return_timestamps="word"), 1: one chunk per timestamp-delimited segment (True)
     std::string err;
 
-    void merge_overlapping(std::vector<int>& toks, std::vector<Span>& ts) {
+    void merge_overlapping(std::vector<int>& toks, std::vector<Span>& ts, std::vector<int>& src) {
         std::vector<int> left = pending[0];
         std::vector<Span> left_ts = pending_ts[0];
-        toks.clear(); ts.clear();
+        std::vector<int> left_src = pending_src[0];
+        toks.clear(); ts.clear(); src.clear();
         for (size_t si = 1; si < pending.size(); ++si) {
             const std::vector<int>& right = pending[si];
             const std::vector<Span>& right_ts = pending_ts[si];
+            const std::vector<int>& right_src = pending_src[si];
             const int nl = (int)left.size(), nr = (int)right.size();
             double best = 0.0;
             int wl0 = nl, wl1 = nl, wr0 = 0, wr1 = 0;
@@ -146,24 +150,27 @@ struct cw_collator {
             const int lmid = (wl1 + wl0) / 2, rmid = (wr1 + wr0) / 2;
             toks.insert(toks.end(), left.begin(), left.begin() + lmid);
             ts.insert(ts.end(), left_ts.begin(), left_ts.begin() + lmid);
+            src.insert(src.end(), left_src.begin(), left_src.begin() + lmid);
             left.assign(right.begin() + rmid, right.end());
             left_ts.assign(right_ts.begin() + rmid, right_ts.end());
+            left_src.assign(right_src.begin() + rmid, right_src.end());
         }
         toks.insert(toks.end(), left.begin(), left.end());
         ts.insert(ts.end(), left_ts.begin(), left_ts.end());
+        src.insert(src.end(), left_src.begin(), left_src.end());
     }
 
     // end_time: the closing timestamp of the segment (NaN: Whisper predicted none), used by the segment mode only
     void flush(double end_time) {
-        std::vector<int> toks; std::vector<Span> ts;
-        merge_overlapping(toks, ts);
+        std::vector<int> toks; std::vector<Span> ts; std::vector<int> src;
+        merge_overlapping(toks, ts, src);
         U32 whole;
         v->text(toks, whole);
         full_text += whole;
         if (mode == 1) {                                         // :1060-1075 without the word collation
-            Word w; w.text = whole; w.start = has_open ? open_start : NAN; w.end = end_time;
+            Word w; w.text = whole; w.start = has_open ? open_start : NAN; w.end = end_time; w.src = src;
             words.push_back(w);
-            pending.clear(); pending_ts.clear();
+            pending.clear(); pending_ts.clear(); pending_src.clear();
             has_open = false;
             return;
         }
@@ -216,9 +223,10 @@ struct cw_collator {
         for (size_t k = 0; k < ws.size(); ++k) {
             if (ws[k].empty()) continue;
             Word w; w.text = ws[k]; w.start = ts[wi[k].front()].first; w.end = ts[wi[k].back()].second;
+            for (int t : wi[k]) w.src.push_back(src[t]);
             words.push_back(w);
         }
-        pending.clear(); pending_ts.clear();
+        pending.clear(); pending_ts.clear(); pending_src.clear();
         has_open = false;
     }
 };
@@ -260,10 +268,12 @@ int32_t cw_collate_feed(cw_collator* c, const int64_t* tokens, int32_t n_tokens,
     const cw_vocab* v = c->v;
     const int tb = v->tb; const double tp = c->tp;
     std::vector<int> ids(tokens, tokens + n_tokens);
+    long long src0 = c->fed;                                                     // fed index of ids[0]
+    c->fed += n_tokens;
     if (!ids.empty() && v->startofprev >= 0 && ids[0] == v->startofprev) {       // _strip_prompt (:725-743)
         size_t k = 0;
         while (k < ids.size() && ids[k] != v->sot) ++k;
-        if (k < ids.size()) ids.erase(ids.begin(), ids.begin() + k); else ids.clear();
+        if (k < ids.size()) { ids.erase(ids.begin(), ids.begin() + k); src0 += (long long)k; } else ids.clear();
     }
     bool has_deferred = false; int deferred_from = 0;
     double first_ts = (double)tb;
@@ -281,7 +291,7 @@ int32_t cw_collate_feed(cw_collator* c, const int64_t* tokens, int32_t n_tokens,
             }
         }
     }
-    std::vector<int> cur; std::vector<Span> cur_ts;
+    std::vector<int> cur; std::vector<Span> cur_ts; std::vector<int> cur_src;
     double cur_max = 0.0, prev_len = 0.0, penult = 0.0;
     for (int i = 0; i < (int)ids.size(); ++i) {
         const int t = ids[i];
@@ -302,12 +312,13 @@ int32_t cw_collate_feed(cw_collator* c, const int64_t* tokens, int32_t n_tokens,
             else if (c->skip || (!c->pending.empty() && (double)t < first_ts)) c->skip = false;
             else if (!c->has_open) { c->has_open = true; c->open_start = when; }
             else if (when != c->open_start) {
-                c->pending.push_back(cur); c->pending_ts.push_back(cur_ts);
+                c->pending.push_back(cur); c->pending_ts.push_back(cur_ts); c->pending_src.push_back(cur_src);
                 c->flush(when);
-                cur.clear(); cur_ts.clear();
+                cur.clear(); cur_ts.clear(); cur_src.clear();
             }
         } else {
             cur.push_back(t);
+            cur_src.push_back((int)(src0 + i));
             if (c->mode == 1) { cur_ts.push_back(Span(0.0, 0.0)); continue; }
             if (i >= n_ts) { c->err = "token_timestamps shorter than tokens"; return -22; }
             const double begin = (i == 0) ? py_round2(0.0 + c->time_offset) : py_round2((double)token_ts[i - 1] + c->time_offset);
@@ -315,11 +326,11 @@ int32_t cw_collate_feed(cw_collator* c, const int64_t* tokens, int32_t n_tokens,
         }
     }
     if (has_stride) c->time_offset += chunk_len - stride_right;
-    if (!cur.empty()) { c->pending.push_back(cur); c->pending_ts.push_back(cur_ts); }
+    if (!cur.empty()) { c->pending.push_back(cur); c->pending_ts.push_back(cur_ts); c->pending_src.push_back(cur_src); }
     else {
         bool any = false;
         for (auto& p : c->pending) if (!p.empty()) any = true;
-        if (!any) { c->pending.clear(); c->pending_ts.clear(); c->has_open = false; }
+        if (!any) { c->pending.clear(); c->pending_ts.clear(); c->pending_src.clear(); c->has_open = false; }
     }
     return 0;
 }
@@ -347,6 +358,24 @@ int32_t cw_collate_get(cw_collator* c, uint8_t* text, double* starts, double* en
         starts[k] = c->words[k].start; ends[k] = c->words[k].end;
     }
     word_offsets[c->words.size()] = off;
+    return 0;
+}
+
+// The tokens behind every word of cw_collate_get, after cw_collate_finish: token_index holds, word after word, the positions
+// of the word's tokens in the concatenation of all fed token arrays; word k owns token_index[group_offsets[k] ..
+// group_offsets[k + 1]).  cw_collate_token_groups_total: the length of token_index.
+int64_t cw_collate_token_groups_total(cw_collator* c) {
+    int64_t n = 0;
+    for (auto& w : c->words) n += (int64_t)w.src.size();
+    return n;
+}
+int32_t cw_collate_get_token_groups(cw_collator* c, int64_t* group_offsets, int32_t* token_index) {
+    int64_t off = 0;
+    for (size_t k = 0; k < c->words.size(); ++k) {
+        group_offsets[k] = off;
+        for (int t : c->words[k].src) token_index[off++] = t;
+    }
+    group_offsets[c->words.size()] = off;
     return 0;
 }
 

@@ -208,6 +208,19 @@ struct cw_ctx {
     size_t pf_rows = 0;
     float* pf_x = nullptr;
     void *pf_a = nullptr, *pf_q = nullptr, *pf_o = nullptr, *pf_h = nullptr;
+    // scoring (score.hip, cw_score_tokens): the teacher-forced forward as one prefill with the scoring head ("score_prefill" = 0:
+    // the per-position loop, the only path of the f32 engine and the e4m3 cross cache).  Buffers for the scored positions grow
+    // on demand; sc_step_*: [Bm][TGT] results of the loop, filled position by position while score_hook is set.
+    bool score_prefill = true;
+    int score_prefill_runs = 0;
+    size_t sc_rows = 0, sc_parts = 0;
+    int *sc_src = nullptr, *sc_tgt = nullptr, *sc_ti = nullptr;
+    void* sc_a = nullptr;
+    ScorePart* sc_part = nullptr;
+    float *sc_lp = nullptr, *sc_tl = nullptr;
+    bool score_hook = false;
+    float *sc_step_lp = nullptr, *sc_step_tl = nullptr;
+    int* sc_step_ti = nullptr;
     int stage_kind[CW_MAX_DEC_STAGES] = {};
     int stage_launches[CW_MAX_DEC_STAGES] = {};   // kernel launches behind each stage (2 where gemv_prep_kernel precedes gemv_mt_kernel)
     float stage_ms[CW_N_STAGES] = {};
@@ -668,6 +681,7 @@ void cw_destroy(cw_ctx* c) {
     for (auto& o : c->out_stages) hipFree(o.stage);
     for (void* p : c->allocs) hipFree(p);
     for (void* p : {(void*)c->pf_x, c->pf_a, c->pf_q, c->pf_o, c->pf_h}) if (p) hipFree(p);
+    for (void* p : {(void*)c->sc_src, (void*)c->sc_tgt, (void*)c->sc_ti, c->sc_a, (void*)c->sc_part, (void*)c->sc_lp, (void*)c->sc_tl}) if (p) hipFree(p);
     if (c->h_nunf) hipHostFree(c->h_nunf);
     if (c->ev0) hipEventDestroy(c->ev0);
     if (c->ev1) hipEventDestroy(c->ev1);
@@ -1571,6 +1585,7 @@ static int handoffs_off(cw_ctx* c, const char* where) {
 }
 int32_t cw_handoff_fallbacks(cw_ctx* c) { return c->handoff_fallbacks; }
 int32_t cw_align_prefill_runs(cw_ctx* c) { return c->align_prefill_runs; }
+int32_t cw_score_prefill_runs(cw_ctx* c) { return c->score_prefill_runs; }
 int32_t cw_handoff_resumes(cw_ctx* c) { return c->handoff_resumes; }
 
 // The granule tag is (epoch << 6) | layer in 32 bits: 26 bits of the device's forward counter.  Granules are never cleared, so a
@@ -1629,13 +1644,16 @@ static int align_last_layer(const cw_ctx* c) {
     for (int a = 0; a < c->d.n_align; ++a) last = c->align_layers[a] > last ? c->align_layers[a] : last;
     return last;
 }
-static int run_prefill(cw_ctx* c, int rows, int n_prompt, int kv_div, bool align = false) {
+// full (cw_score_tokens): every layer runs to its end, the last one included, and leaves the residual stream of every position in
+// pf_x for the scoring head; with align the alignment rows are recorded on the way, by the launches the early-stopping
+// alignment forward makes.
+static int run_prefill(cw_ctx* c, int rows, int n_prompt, int kv_div, bool align = false, bool full = false) {
     const int D = c->d.d_model, F = c->d.ffn_dim, H = c->d.n_heads, TGT = c->d.max_target_positions;
     const int n_pos = n_prompt - 1;
     const int M = rows * n_pos;
     CWCHK(c, prefill_reserve(c, (size_t)M));
     CWCHK(c, KD(c, cw_launch_prefill_embed, c->d_ids, TGT, n_pos, c->embed, c->dec_pos, c->pf_x, M, D, c->st));
-    const int NL = align ? align_last_layer(c) + 1 : c->d.dec_layers;
+    const int NL = (align && !full) ? align_last_layer(c) + 1 : c->d.dec_layers;
     for (int l = 0; l < NL; ++l) {
         LayerW& L = c->dec[l];
         PrefillEpi ep;
@@ -1643,7 +1661,7 @@ static int run_prefill(cw_ctx* c, int rows, int n_prompt, int kv_div, bool align
         CWCHK(c, KD(c, cw_launch_prefill_ln, c->pf_x, c->pf_a, M, D, c->st));
         ep.mode = PF_QKV; ep.bias = L.bqkv; ep.out = c->pf_q; ep.sk = L.sk; ep.sv = L.sv; ep.D = D; ep.H = H; ep.cap = TGT; ep.n_pos = n_pos;
         CWCHK(c, KD(c, cw_launch_prefill_gemm, c->pf_a, L.wqkv, ep, M, 3 * D, D, c->st));
-        if (!align && l + 1 == NL) break;
+        if (!align && !full && l + 1 == NL) break;
         CWCHK(c, KD(c, cw_launch_prefill_attn, c->pf_q, L.sk, L.sv, c->pf_o, rows, n_pos, H, TGT, n_pos, 1, 1, c->st));
         memset(&ep, 0, sizeof(ep));
         ep.mode = PF_RESID; ep.bias = L.bo; ep.x = c->pf_x;
@@ -1657,7 +1675,7 @@ static int run_prefill(cw_ctx* c, int rows, int n_prompt, int kv_div, bool align
             al.out = c->d_align; al.ml = c->d_align_ml; al.slot = c->d_align_slot + (size_t)l * H; al.n_align = c->d.n_align; al.rows = TGT;
         }
         CWCHK(c, KD(c, cw_launch_prefill_attn_align, c->pf_q, L.ck, L.cv, c->pf_o, rows, n_pos, H, CW_N_CTX, CW_N_CTX, 0, kv_div, al, c->st));
-        if (align && l + 1 == NL) break;
+        if (align && !full && l + 1 == NL) break;
         ep.mode = PF_RESID; ep.bias = L.bo_c; ep.out = nullptr; ep.x = c->pf_x;
         CWCHK(c, KD(c, cw_launch_prefill_gemm, c->pf_o, L.wo_c, ep, M, D, D, c->st));
         CWCHK(c, KD(c, cw_launch_prefill_ln, c->pf_x, c->pf_a, M, D, c->st));
@@ -1738,6 +1756,8 @@ static int decode_once(cw_ctx* c, int32_t nb, const int32_t* prompt, int32_t n_p
             // forward at position t-1, logits, fused processors + argmax -> ids[t], x for position t, pos := t
             c->hist_short = t <= 64;               // keys 0 .. t-1
             CWCHK(c, run_step(c, nb));
+            if (c->score_hook)    // cw_score_tokens' loop: log-softmax / target / arg-max of the raw logits that predict ids[t]
+                CWCHK(c, KD(c, cw_launch_score_rows, c->dlogits, c->Vpad, V, c->d_forced, TGT, t, nb, c->sc_step_lp, c->sc_step_ti, c->sc_step_tl, c->st));
             if (c->logits_capture && step < c->logits_capture_steps)
                 HIPCHK(c, hipMemcpy2DAsync(c->logits_capture + (size_t)step * nb * V, (size_t)V * 4, c->dlogits, (size_t)c->Vpad * 4, (size_t)V * 4, nb, hipMemcpyDeviceToHost, c->st));
             ++t;                               // sequence length is now t
@@ -1768,7 +1788,7 @@ static int decode_once(cw_ctx* c, int32_t nb, const int32_t* prompt, int32_t n_p
         // rows below P are good.  Resume there when the sampler's state can be rebuilt from the ids alone (no log-probability sums, no
         // logits capture, P inside the generated part); otherwise cw_decode repeats the whole call.
         const int P = gave_up_word - 1;
-        if (P < n_prompt || P + 1 >= max_length || c->score_tokens || c->logits_capture) { tm.stop(); return CW_HANDOFF_RETRY; }
+        if (P < n_prompt || P + 1 >= max_length || c->score_tokens || c->logits_capture || c->score_hook) { tm.stop(); return CW_HANDOFF_RETRY; }
         CWCHK(c, handoffs_off(c, "decode"));
         HIPCHK(c, hipMemcpy(ids.data(), c->d_ids, ids.size() * 4, hipMemcpyDeviceToHost));
         std::vector<int> fin(nb), lts(nb);
@@ -2264,36 +2284,67 @@ int32_t cw_transcribe_prompted(cw_ctx* c, int32_t B, const int32_t* num_frames, 
 // ------------------------------------------------------------------------------------------------
 // forced alignment of known token sequences (include/crisperwhisper.h: cw_align_tokens)
 // ------------------------------------------------------------------------------------------------
-int32_t cw_align_tokens(cw_ctx* c, int32_t nb, const int32_t* num_frames, const int32_t* ids, int32_t ids_stride,
-                        const int32_t* n_ids, int32_t n_init, float* token_ts) {
-    const int TGT = c->d.max_target_positions, V = c->d.vocab_size, Ha = c->d.n_align;
-    // every argument is checked before anything is launched
-    if (Ha <= 0) return fail(c, CW_ERR_STATE, "align_tokens: no alignment heads configured");
-    if (!c->gen_set) return fail(c, CW_ERR_STATE, "cw_set_generation not called");
-    if (nb < 1 || nb > c->Bm) return fail(c, CW_ERR_INVALID, "align_tokens: nb=%d out of range (the context has %d rows)", nb, c->Bm);
-    if (!num_frames || !ids || !n_ids || !token_ts) return fail(c, CW_ERR_INVALID, "align_tokens: null argument");
-    if (n_init < 1 || n_init >= TGT) return fail(c, CW_ERR_INVALID, "align_tokens: n_init=%d out of range", n_init);
-    if (ids_stride < n_init + 1) return fail(c, CW_ERR_INVALID, "align_tokens: ids_stride=%d below n_init + 1", ids_stride);
+// whole decoder inputs (init tokens + text + eos) of cw_align_tokens / cw_score_tokens: every argument is checked before anything
+// is launched.  num_frames null: not needed by the caller (scoring alone).  n_max: the longest row.
+static int check_token_rows(cw_ctx* c, const char* who, int nb, const int32_t* num_frames, const int32_t* ids, int ids_stride,
+                            const int32_t* n_ids, int n_init, int* n_max_out) {
+    const int TGT = c->d.max_target_positions, V = c->d.vocab_size;
+    if (n_init < 1 || n_init >= TGT) return fail(c, CW_ERR_INVALID, "%s: n_init=%d out of range", who, n_init);
+    if (ids_stride < n_init + 1) return fail(c, CW_ERR_INVALID, "%s: ids_stride=%d below n_init + 1", who, ids_stride);
     int n_max = 0;
     for (int b = 0; b < nb; ++b) {
         const int n = n_ids[b];
         if (n < n_init + 1 || n > TGT || n > ids_stride)
-            return fail(c, CW_ERR_INVALID, "align_tokens: row %d has %d ids; needs %d .. %d (init tokens + eos .. max_target_positions)",
-                        b, n, n_init + 1, TGT < ids_stride ? TGT : ids_stride);
-        if (num_frames[b] < 0 || num_frames[b] > CW_N_FRAMES)
-            return fail(c, CW_ERR_INVALID, "align_tokens: num_frames[%d]=%d out of range 0 .. %d", b, num_frames[b], CW_N_FRAMES);
+            return fail(c, CW_ERR_INVALID, "%s: row %d has %d ids; needs %d .. %d (init tokens + eos .. max_target_positions)",
+                        who, b, n, n_init + 1, TGT < ids_stride ? TGT : ids_stride);
+        if (num_frames && (num_frames[b] < 0 || num_frames[b] > CW_N_FRAMES))
+            return fail(c, CW_ERR_INVALID, "%s: num_frames[%d]=%d out of range 0 .. %d", who, b, num_frames[b], CW_N_FRAMES);
         for (int k = 0; k < n; ++k) {
             const int tok = ids[(size_t)b * ids_stride + k];
-            if (tok < 0 || tok >= V) return fail(c, CW_ERR_INVALID, "align_tokens: row %d id %d at %d is outside the vocabulary (%d)", b, tok, k, V);
+            if (tok < 0 || tok >= V) return fail(c, CW_ERR_INVALID, "%s: row %d id %d at %d is outside the vocabulary (%d)", who, b, tok, k, V);
             if (k >= n_init && k + 1 < n && tok == c->gen.eos_token_id)
-                return fail(c, CW_ERR_INVALID, "align_tokens: row %d has eos at %d before its last id", b, k);
+                return fail(c, CW_ERR_INVALID, "%s: row %d has eos at %d before its last id", who, b, k);
         }
         n_max = n > n_max ? n : n_max;
     }
-    struct PrefixScope {                     // no prompt_ids here: the prompt prefill must not engage in the loop's decode
-        cw_ctx* c; int saved;
-        ~PrefixScope() { c->pf_prefix = saved; }
-    } scope{c, c->pf_prefix};
+    *n_max_out = n_max;
+    return CW_OK;
+}
+
+// timestamps over each row's own token count: a row's z-score statistics, filter and DTW see its own rows only, so its
+// timestamps do not depend on the other rows of the batch.  Consecutive rows of one length share one pass of the stages
+// (per-item work in every one of them; num_frames >= 0 makes the one- and two-fold slicing of the columns agree).
+static int forced_rows_timestamps(cw_ctx* c, int nb, const int32_t* num_frames, int ids_stride, const int32_t* n_ids, int n_init,
+                                  float* token_ts) {
+    const int TGT = c->d.max_target_positions, Ha = c->d.n_align;
+    CWCHK(c, normalize_alignment(c));
+    const float* w0 = c->align_cur ? c->align_cur : c->d_align;
+    std::vector<float> ts;
+    for (int b0 = 0, b1; b0 < nb; b0 = b1) {
+        for (b1 = b0 + 1; b1 < nb && n_ids[b1] == n_ids[b0]; ++b1) {}
+        const int L = n_ids[b0] - 1, n = b1 - b0;
+        ts.resize((size_t)n * (L + 1));
+        CWCHK(c, token_timestamps(c, w0 + (size_t)b0 * Ha * TGT * CW_N_CTX, n, L, n_init, num_frames + b0, ts.data()));
+        for (int r = 0; r < n; ++r) memcpy(token_ts + (size_t)(b0 + r) * ids_stride, ts.data() + (size_t)r * (L + 1), (size_t)(L + 1) * 4);
+    }
+    return CW_OK;
+}
+
+struct PrefixScope {                         // no prompt_ids here: the prompt prefill must not engage in the loop's decode
+    cw_ctx* c; int saved;
+    ~PrefixScope() { c->pf_prefix = saved; }
+};
+
+int32_t cw_align_tokens(cw_ctx* c, int32_t nb, const int32_t* num_frames, const int32_t* ids, int32_t ids_stride,
+                        const int32_t* n_ids, int32_t n_init, float* token_ts) {
+    const int TGT = c->d.max_target_positions, Ha = c->d.n_align;
+    if (Ha <= 0) return fail(c, CW_ERR_STATE, "align_tokens: no alignment heads configured");
+    if (!c->gen_set) return fail(c, CW_ERR_STATE, "cw_set_generation not called");
+    if (nb < 1 || nb > c->Bm) return fail(c, CW_ERR_INVALID, "align_tokens: nb=%d out of range (the context has %d rows)", nb, c->Bm);
+    if (!num_frames || !ids || !n_ids || !token_ts) return fail(c, CW_ERR_INVALID, "align_tokens: null argument");
+    int n_max = 0;
+    CWCHK(c, check_token_rows(c, "align_tokens", nb, num_frames, ids, ids_stride, n_ids, n_init, &n_max));
+    PrefixScope scope{c, c->pf_prefix};
     c->pf_prefix = 0;
     std::vector<int> all(nb), zeros(nb, 0), full(nb, CW_N_FRAMES);
     for (int i = 0; i < nb; ++i) all[i] = i;
@@ -2326,20 +2377,169 @@ int32_t cw_align_tokens(cw_ctx* c, int32_t nb, const int32_t* num_frames, const 
         CWCHK(c, cw_decode(c, nb, prompt.data(), n_init, n_max, 0, forced.data(), seq.data(), lens.data(), nullptr));
         if (c->last_L < Lmax) return fail(c, CW_ERR_STATE, "align_tokens: the forced decode stopped at %d of %d positions", c->last_L, Lmax);
     }
-    // timestamps over each row's own token count: a row's z-score statistics, filter and DTW see its own rows only, so its
-    // timestamps do not depend on the other rows of the batch.  Consecutive rows of one length share one pass of the stages
-    // (per-item work in every one of them; num_frames >= 0 makes the one- and two-fold slicing of the columns agree).
-    CWCHK(c, normalize_alignment(c));
-    const float* w0 = c->align_cur ? c->align_cur : c->d_align;
-    std::vector<float> ts;
-    for (int b0 = 0, b1; b0 < nb; b0 = b1) {
-        for (b1 = b0 + 1; b1 < nb && n_ids[b1] == n_ids[b0]; ++b1) {}
-        const int L = n_ids[b0] - 1, n = b1 - b0;
-        ts.resize((size_t)n * (L + 1));
-        CWCHK(c, token_timestamps(c, w0 + (size_t)b0 * Ha * TGT * CW_N_CTX, n, L, n_init, num_frames + b0, ts.data()));
-        for (int r = 0; r < n; ++r) memcpy(token_ts + (size_t)(b0 + r) * ids_stride, ts.data() + (size_t)r * (L + 1), (size_t)(L + 1) * 4);
+    return forced_rows_timestamps(c, nb, num_frames, ids_stride, n_ids, n_init, token_ts);
+}
+
+// ------------------------------------------------------------------------------------------------
+// scoring of known token sequences (include/crisperwhisper.h: cw_score_tokens, cw_align_score_tokens)
+// ------------------------------------------------------------------------------------------------
+static int score_reserve(cw_ctx* c, size_t M, size_t parts) {
+    if (M > c->sc_rows) {
+        const int D = c->d.d_model;
+        HIPCHK(c, hipStreamSynchronize(c->st));
+        for (void** p : {(void**)&c->sc_src, (void**)&c->sc_tgt, (void**)&c->sc_ti, &c->sc_a, (void**)&c->sc_lp, (void**)&c->sc_tl})
+            if (*p) { hipFree(*p); *p = nullptr; }
+        c->sc_rows = 0;
+        const size_t bytes[6] = {M * 4, M * 4, M * 4, M * D * 2, M * 4, M * 4};
+        void** dst[6] = {(void**)&c->sc_src, (void**)&c->sc_tgt, (void**)&c->sc_ti, &c->sc_a, (void**)&c->sc_lp, (void**)&c->sc_tl};
+        for (int i = 0; i < 6; ++i) {
+            hipError_t e = hipMalloc(dst[i], bytes[i]);
+            if (e != hipSuccess) return fail(c, CW_ERR_NOMEM, "score: hipMalloc(%zu) failed: %s", bytes[i], hipGetErrorString(e));
+        }
+        c->sc_rows = M;
+    }
+    if (parts > c->sc_parts) {
+        HIPCHK(c, hipStreamSynchronize(c->st));
+        if (c->sc_part) { hipFree(c->sc_part); c->sc_part = nullptr; }
+        c->sc_parts = 0;
+        hipError_t e = hipMalloc((void**)&c->sc_part, parts * sizeof(ScorePart));
+        if (e != hipSuccess) return fail(c, CW_ERR_NOMEM, "score: hipMalloc(%zu) failed: %s", parts * sizeof(ScorePart), hipGetErrorString(e));
+        c->sc_parts = parts;
     }
     return CW_OK;
+}
+
+// The scoring head over the residual stream run_prefill (full) leaves in pf_x [rows][n_pos][D]: position p of a row predicts id
+// p + 1, and only positions n_init-1 .. n_ids[row]-2 are projected.  score_head_prepare uploads their list and targets (they
+// depend on the arguments alone, so before the forward), score_head_launch queues the kernels behind the forward,
+// score_head_fetch reads the results.
+static int score_head_prepare(cw_ctx* c, int rows, int n_pos, const int32_t* ids, int ids_stride, const int32_t* n_ids, int n_init,
+                              int* M_out) {
+    std::vector<int> src, tgt;
+    for (int r = 0; r < rows; ++r)
+        for (int k = n_init; k < n_ids[r]; ++k) { src.push_back(r * n_pos + k - 1); tgt.push_back(ids[(size_t)r * ids_stride + k]); }
+    const int M = (int)src.size(), V = c->d.vocab_size, D = c->d.d_model;
+    const int ns = KD(c, cw_score_head_splits, M, V, nullptr);
+    CWCHK(c, score_reserve(c, (size_t)M, (size_t)M * ns));
+    HIPCHK(c, hipMemcpyAsync(c->sc_src, src.data(), (size_t)M * 4, hipMemcpyHostToDevice, c->st));
+    HIPCHK(c, hipMemcpyAsync(c->sc_tgt, tgt.data(), (size_t)M * 4, hipMemcpyHostToDevice, c->st));
+    HIPCHK(c, hipStreamSynchronize(c->st));      // host vectors go out of scope
+    *M_out = M;
+    return CW_OK;
+}
+
+static int score_head_launch(cw_ctx* c, int M) {
+    const int V = c->d.vocab_size, D = c->d.d_model;
+    CWCHK(c, KD(c, cw_launch_score_ln, c->pf_x, c->sc_src, c->dec_ln_g, c->dec_ln_b, c->sc_a, M, D, c->st));
+    CWCHK(c, KD(c, cw_launch_score_head, c->sc_a, c->embed_pk, c->sc_tgt, c->sc_part, M, V, D, c->sc_lp, c->sc_ti, c->sc_tl, c->st));
+    return CW_OK;
+}
+
+static int score_head_fetch(cw_ctx* c, int rows, int M, int ids_stride, const int32_t* n_ids, int n_init, float* token_logprob,
+                            int32_t* top_id, float* top_logprob) {
+    std::vector<float> lp(M), tl(M);
+    std::vector<int> ti(M);
+    HIPCHK(c, hipStreamSynchronize(c->st));
+    HIPCHK(c, hipMemcpy(lp.data(), c->sc_lp, (size_t)M * 4, hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(ti.data(), c->sc_ti, (size_t)M * 4, hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(tl.data(), c->sc_tl, (size_t)M * 4, hipMemcpyDeviceToHost));
+    int m = 0;
+    for (int r = 0; r < rows; ++r)
+        for (int k = n_init; k < n_ids[r]; ++k, ++m) {
+            token_logprob[(size_t)r * ids_stride + k] = lp[m];
+            if (top_id) top_id[(size_t)r * ids_stride + k] = ti[m];
+            if (top_logprob) top_logprob[(size_t)r * ids_stride + k] = tl[m];
+        }
+    return CW_OK;
+}
+
+// num_frames / token_ts null: scores only (any rows_per_item); else rows_per_item == 1 and the timestamps of cw_align_tokens too
+static int score_rows(cw_ctx* c, const char* who, int n_items, int rpi, const int32_t* num_frames, const int32_t* ids, int ids_stride,
+                      const int32_t* n_ids, int n_init, float* token_ts, float* token_logprob, int32_t* top_id, float* top_logprob) {
+    const int TGT = c->d.max_target_positions;
+    const bool align = token_ts != nullptr;
+    if (align && c->d.n_align <= 0) return fail(c, CW_ERR_STATE, "%s: no alignment heads configured", who);
+    if (!c->gen_set) return fail(c, CW_ERR_STATE, "cw_set_generation not called");
+    if (rpi < 1) return fail(c, CW_ERR_INVALID, "%s: rows_per_item=%d below 1", who, rpi);
+    if (n_items < 1 || n_items > c->Bm || (long long)n_items * rpi > c->Bm)
+        return fail(c, CW_ERR_INVALID, "%s: %d items x %d rows out of range (the context has %d rows)", who, n_items, rpi, c->Bm);
+    if (!ids || !n_ids || !token_logprob || (align && !num_frames)) return fail(c, CW_ERR_INVALID, "%s: null argument", who);
+    const int rows = n_items * rpi;
+    int n_max = 0;
+    CWCHK(c, check_token_rows(c, who, rows, num_frames, ids, ids_stride, n_ids, n_init, &n_max));
+    PrefixScope scope{c, c->pf_prefix};
+    c->pf_prefix = 0;
+    const int Lmax = n_max - 1;
+    if (c->score_prefill && prefill_capable(c)) {
+        // one encoder pass per item; decoder row r reads the cross K/V cache of item r / rows_per_item
+        std::vector<int> all(n_items), zeros(n_items, 0), full(n_items, CW_N_FRAMES);
+        for (int i = 0; i < n_items; ++i) all[i] = i;
+        CWCHK(c, cw_encode(c, n_items, all.data(), zeros.data(), full.data()));
+        std::vector<int> dev((size_t)rows * TGT, c->gen.pad_token_id);
+        for (int b = 0; b < rows; ++b) memcpy(dev.data() + (size_t)b * TGT, ids + (size_t)b * ids_stride, (size_t)n_ids[b] * 4);
+        c->beam_K = 0;
+        c->align_cur = c->d_align;
+        HIPCHK(c, hipMemcpyAsync(c->d_ids, dev.data(), dev.size() * 4, hipMemcpyHostToDevice, c->st));
+        int M = 0;
+        CWCHK(c, score_head_prepare(c, rows, Lmax, ids, ids_stride, n_ids, n_init, &M));     // (synchronises the stream)
+        StageTimer tm(c, CW_STAGE_DECODE);
+        CWCHK(c, run_prefill(c, rows, Lmax + 1, rpi, align, true));
+        CWCHK(c, score_head_launch(c, M));
+        KCHK(c);
+        tm.stop();
+        ++c->score_prefill_runs;
+        c->last_L = align ? Lmax : 0;            // without align no alignment rows were recorded: nothing is retained
+        c->last_nb = align ? rows : 0;
+        c->align_unnormalized = align;
+        CWCHK(c, score_head_fetch(c, rows, M, ids_stride, n_ids, n_init, token_logprob, top_id, top_logprob));
+    } else {
+        // the per-position decoder step with every token forced; the item is encoded into each of its rows, and the raw logits
+        // of every step are reduced on the device (score_rows_kernel) before the next step overwrites them
+        std::vector<int> item(rows), zeros(rows, 0), full(rows, CW_N_FRAMES);
+        for (int r = 0; r < rows; ++r) item[r] = r / rpi;
+        CWCHK(c, cw_encode(c, rows, item.data(), zeros.data(), full.data()));
+        if (!c->sc_step_lp) {
+            const size_t n = (size_t)c->Bm * TGT * 4;
+            CWCHK(c, dmalloc(c, &c->sc_step_lp, n)); CWCHK(c, dmalloc(c, &c->sc_step_tl, n)); CWCHK(c, dmalloc(c, &c->sc_step_ti, n));
+        }
+        std::vector<int> prompt((size_t)rows * n_init), forced((size_t)rows * TGT, -1), seq((size_t)rows * TGT), lens(rows);
+        for (int b = 0; b < rows; ++b) {
+            memcpy(prompt.data() + (size_t)b * n_init, ids + (size_t)b * ids_stride, (size_t)n_init * 4);
+            for (int k = n_init; k < n_ids[b]; ++k) forced[(size_t)b * TGT + k] = ids[(size_t)b * ids_stride + k];
+        }
+        struct HookScope { cw_ctx* c; ~HookScope() { c->score_hook = false; } } hook{c};
+        c->score_hook = true;
+        CWCHK(c, cw_decode(c, rows, prompt.data(), n_init, n_max, 0, forced.data(), seq.data(), lens.data(), nullptr));
+        c->score_hook = false;
+        if (c->last_L < Lmax) return fail(c, CW_ERR_STATE, "%s: the forced decode stopped at %d of %d positions", who, c->last_L, Lmax);
+        std::vector<float> lp((size_t)rows * TGT), tl((size_t)rows * TGT);
+        std::vector<int> ti((size_t)rows * TGT);
+        HIPCHK(c, hipMemcpy(lp.data(), c->sc_step_lp, lp.size() * 4, hipMemcpyDeviceToHost));
+        HIPCHK(c, hipMemcpy(ti.data(), c->sc_step_ti, ti.size() * 4, hipMemcpyDeviceToHost));
+        HIPCHK(c, hipMemcpy(tl.data(), c->sc_step_tl, tl.size() * 4, hipMemcpyDeviceToHost));
+        for (int r = 0; r < rows; ++r)
+            for (int k = n_init; k < n_ids[r]; ++k) {
+                token_logprob[(size_t)r * ids_stride + k] = lp[(size_t)r * TGT + k];
+                if (top_id) top_id[(size_t)r * ids_stride + k] = ti[(size_t)r * TGT + k];
+                if (top_logprob) top_logprob[(size_t)r * ids_stride + k] = tl[(size_t)r * TGT + k];
+            }
+    }
+    if (align) return forced_rows_timestamps(c, rows, num_frames, ids_stride, n_ids, n_init, token_ts);
+    return CW_OK;
+}
+
+int32_t cw_score_tokens(cw_ctx* c, int32_t n_items, int32_t rows_per_item, const int32_t* ids, int32_t ids_stride,
+                        const int32_t* n_ids, int32_t n_init, float* token_logprob, int32_t* top_id, float* top_logprob) {
+    return score_rows(c, "score_tokens", n_items, rows_per_item, nullptr, ids, ids_stride, n_ids, n_init, nullptr, token_logprob,
+                      top_id, top_logprob);
+}
+
+int32_t cw_align_score_tokens(cw_ctx* c, int32_t nb, const int32_t* num_frames, const int32_t* ids, int32_t ids_stride,
+                              const int32_t* n_ids, int32_t n_init, float* token_ts, float* token_logprob, int32_t* top_id,
+                              float* top_logprob) {
+    if (!token_ts) return fail(c, CW_ERR_INVALID, "align_score_tokens: null argument");
+    return score_rows(c, "align_score_tokens", nb, 1, num_frames, ids, ids_stride, n_ids, n_init, token_ts, token_logprob, top_id,
+                      top_logprob);
 }
 
 int32_t cw_align_matrix(cw_ctx* c, const float* attn, int32_t B, int32_t Ha, int32_t N, int32_t M, const int32_t* n_cols,
@@ -2545,6 +2745,10 @@ int32_t cw_set_option(cw_ctx* c, const char* name, int32_t value) {
         c->align_prefill = value != 0;
         return CW_OK;
     }
+    if (!strcmp(name, "score_prefill")) {    // 0: cw_score_tokens runs its forward through the per-position decoder step (A/B)
+        c->score_prefill = value != 0;
+        return CW_OK;
+    }
     if (!strcmp(name, "cross_kv_fp8")) {
         if (!value) { c->kv8 = false; return CW_OK; }
         if (!c->bf16) return fail(c, CW_ERR_INVALID, "cross_kv_fp8 needs the bf16 engine (the f32 engine is the parity mode)");
@@ -2704,6 +2908,88 @@ int32_t cw_test_prefill_gemm(cw_ctx* c, int32_t mode, int32_t M, int32_t N, int3
         else r = download_T(c, dO, 0, out, (size_t)M * N);
     }
     hipFree(dA); hipFree(dW); hipFree(dWp); hipFree(dO); hipFree(dB);
+    return r;
+}
+
+// cw_test_score_head: the scoring head (score.hip) on its own.  x [M][D] f32 residual rows, ln_g / ln_b [D], embed [V][D] (rounded
+// to the engine's 16-bit type and packed fragment-major), targets [M] -> logprob / top_id / top_logprob [M].  16-bit engines;
+// D % 32 == 0.  Sizes are validated on the host before anything is allocated or launched.
+int32_t cw_test_score_head(cw_ctx* c, int32_t M, int32_t D, int32_t V, const float* x, const float* ln_g, const float* ln_b,
+                           const float* embed, const int32_t* targets, float* logprob, int32_t* top_id, float* top_logprob) {
+    if (!c->bf16) return fail(c, CW_ERR_INVALID, "test_score_head: 16-bit engines only");
+    if (M < 1 || M > (1 << 16) || D < 32 || D % 32 || D > 8192 || V < 1 || V > (1 << 20) || !x || !ln_g || !ln_b || !embed || !targets ||
+        !logprob || !top_id || !top_logprob) return fail(c, CW_ERR_INVALID, "test_score_head: bad arguments");
+    for (int m = 0; m < M; ++m)
+        if (targets[m] < 0 || targets[m] >= V) return fail(c, CW_ERR_INVALID, "test_score_head: target %d of row %d outside 0 .. %d", targets[m], m, V - 1);
+    const size_t e = c->esz;
+    const int ns = KD(c, cw_score_head_splits, M, V, nullptr);
+    float *dx = nullptr, *dg = nullptr, *db = nullptr, *dlp = nullptr, *dtl = nullptr;
+    int *dt = nullptr, *dti = nullptr;
+    void *dA = nullptr, *dW = nullptr, *dWp = nullptr;
+    ScorePart* dP = nullptr;
+    int r = CW_OK;
+    if (hipMalloc((void**)&dx, (size_t)M * D * 4) != hipSuccess || hipMalloc((void**)&dg, (size_t)D * 4) != hipSuccess ||
+        hipMalloc((void**)&db, (size_t)D * 4) != hipSuccess || hipMalloc((void**)&dlp, (size_t)M * 4) != hipSuccess ||
+        hipMalloc((void**)&dtl, (size_t)M * 4) != hipSuccess || hipMalloc((void**)&dt, (size_t)M * 4) != hipSuccess ||
+        hipMalloc((void**)&dti, (size_t)M * 4) != hipSuccess || hipMalloc(&dA, (size_t)M * D * e) != hipSuccess ||
+        hipMalloc(&dW, (size_t)V * D * e) != hipSuccess || hipMalloc(&dWp, KD(c, cw_wfrag_elems, V, D) * e) != hipSuccess ||
+        hipMalloc((void**)&dP, (size_t)M * ns * sizeof(ScorePart)) != hipSuccess) r = fail(c, CW_ERR_NOMEM, "test_score_head: hipMalloc failed");
+    if (r == CW_OK && (hipMemcpy(dx, x, (size_t)M * D * 4, hipMemcpyHostToDevice) != hipSuccess ||
+                       hipMemcpy(dg, ln_g, (size_t)D * 4, hipMemcpyHostToDevice) != hipSuccess ||
+                       hipMemcpy(db, ln_b, (size_t)D * 4, hipMemcpyHostToDevice) != hipSuccess ||
+                       hipMemcpy(dt, targets, (size_t)M * 4, hipMemcpyHostToDevice) != hipSuccess)) r = fail(c, CW_ERR_HIP, "test_score_head: copy");
+    if (r == CW_OK) r = upload_T(c, dW, 0, embed, (size_t)V * D);
+    if (r == CW_OK) r = KD(c, cw_launch_wfrag_pack, dW, V, D, dWp, c->st);
+    if (r == CW_OK) r = KD(c, cw_launch_score_ln, dx, nullptr, dg, db, dA, M, D, c->st);
+    if (r == CW_OK) r = KD(c, cw_launch_score_head, dA, dWp, dt, dP, M, V, D, dlp, dti, dtl, c->st);
+    if (r == CW_OK) { hipError_t er = hipStreamSynchronize(c->st); if (er != hipSuccess) r = fail(c, CW_ERR_HIP, "test_score_head: %s", hipGetErrorString(er)); }
+    if (r == CW_OK && (hipMemcpy(logprob, dlp, (size_t)M * 4, hipMemcpyDeviceToHost) != hipSuccess ||
+                       hipMemcpy(top_id, dti, (size_t)M * 4, hipMemcpyDeviceToHost) != hipSuccess ||
+                       hipMemcpy(top_logprob, dtl, (size_t)M * 4, hipMemcpyDeviceToHost) != hipSuccess)) r = fail(c, CW_ERR_HIP, "test_score_head: copy");
+    hipFree(dx); hipFree(dg); hipFree(db); hipFree(dlp); hipFree(dtl); hipFree(dt); hipFree(dti); hipFree(dA); hipFree(dW); hipFree(dWp); hipFree(dP);
+    return r;
+}
+
+// cw_time_score_head: the scoring head at the context's own geometry (d_model, vocabulary, its packed tied embedding) over M
+// pseudo-random residual rows: LayerNorm + fused head + combine (unfused = 0), or LayerNorm + the same GEMM storing f32 logits
+// [M][Vpad] + a row-wise log-softmax pass (unfused = 1).  avg_ms: HIP-event time per repetition after one warm-up.
+int32_t cw_time_score_head(cw_ctx* c, int32_t M, int32_t unfused, int32_t iters, float* avg_ms) {
+    if (!c->bf16 || !c->embed_pk) return fail(c, CW_ERR_INVALID, "time_score_head: 16-bit engines with packed weights only");
+    if (M < 1 || M > (1 << 15) || iters < 1 || !avg_ms) return fail(c, CW_ERR_INVALID, "time_score_head: bad arguments");
+    CWCHK(c, cw_check_weights(c));
+    const int D = c->d.d_model, V = c->d.vocab_size;
+    const int ns = KD(c, cw_score_head_splits, M, V, nullptr);
+    std::vector<float> x((size_t)M * D);
+    std::vector<int> tg(M);
+    unsigned int lcg = 12345u;
+    for (auto& v : x) { lcg = lcg * 1664525u + 1013904223u; v = ((int)(lcg >> 8) % 4001 - 2000) * 1e-3f; }
+    for (int m = 0; m < M; ++m) { lcg = lcg * 1664525u + 1013904223u; tg[m] = (int)((lcg >> 8) % (unsigned)V); }
+    float *dx = nullptr, *dlp = nullptr, *dtl = nullptr, *dlog = nullptr;
+    int *dt = nullptr, *dti = nullptr;
+    void* dA = nullptr;
+    ScorePart* dP = nullptr;
+    int r = CW_OK;
+    if (hipMalloc((void**)&dx, x.size() * 4) != hipSuccess || hipMalloc((void**)&dlp, (size_t)M * 4) != hipSuccess ||
+        hipMalloc((void**)&dtl, (size_t)M * 4) != hipSuccess || hipMalloc((void**)&dt, (size_t)M * 4) != hipSuccess ||
+        hipMalloc((void**)&dti, (size_t)M * 4) != hipSuccess || hipMalloc(&dA, (size_t)M * D * 2) != hipSuccess ||
+        hipMalloc((void**)&dP, (size_t)M * ns * sizeof(ScorePart)) != hipSuccess ||
+        (unfused && hipMalloc((void**)&dlog, (size_t)M * c->Vpad * 4) != hipSuccess)) r = fail(c, CW_ERR_NOMEM, "time_score_head: hipMalloc failed");
+    if (r == CW_OK && (hipMemcpy(dx, x.data(), x.size() * 4, hipMemcpyHostToDevice) != hipSuccess ||
+                       hipMemcpy(dt, tg.data(), (size_t)M * 4, hipMemcpyHostToDevice) != hipSuccess)) r = fail(c, CW_ERR_HIP, "time_score_head: copy");
+    for (int it = 0; it <= iters && r == CW_OK; ++it) {
+        if (it == 1 && hipEventRecord(c->ev0, c->st) != hipSuccess) r = fail(c, CW_ERR_HIP, "time_score_head: event");
+        if (r == CW_OK) r = KD(c, cw_launch_score_ln, dx, nullptr, c->dec_ln_g, c->dec_ln_b, dA, M, D, c->st);
+        if (r == CW_OK) r = unfused ? KD(c, cw_launch_score_head_unfused, dA, c->embed_pk, dt, dlog, c->Vpad, M, V, D, dlp, dti, dtl, c->st)
+                                    : KD(c, cw_launch_score_head, dA, c->embed_pk, dt, dP, M, V, D, dlp, dti, dtl, c->st);
+    }
+    if (r == CW_OK) {
+        float ms = 0.f;
+        if (hipEventRecord(c->ev1, c->st) != hipSuccess || hipEventSynchronize(c->ev1) != hipSuccess ||
+            hipEventElapsedTime(&ms, c->ev0, c->ev1) != hipSuccess) r = fail(c, CW_ERR_HIP, "time_score_head: event");
+        else *avg_ms = ms / (float)iters;
+    }
+    hipStreamSynchronize(c->st);
+    hipFree(dx); hipFree(dlp); hipFree(dtl); hipFree(dt); hipFree(dti); hipFree(dA); hipFree(dP); if (dlog) hipFree(dlog);
     return r;
 }
 

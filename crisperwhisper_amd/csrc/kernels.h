@@ -336,6 +336,13 @@ struct PrefillAlign {
     int n_align, rows;     // rows = alignment rows per (row, slot) (max_target_positions); query position p -> row p
 };
 
+// score.hip: one vocabulary split's statistics of one scored row (score_head_kernel -> score_combine_kernel)
+struct ScorePart {
+    float mx, sum;         // maximum logit of the split's columns, sum of exp(logit - mx)
+    float tl;              // the target's logit if its column is the split's, else -inf
+    float bv; int bi;      // best (logit, id), lowest id on an exact tie
+};
+
 #define CW_DTYPE_KERNEL_DECLS \
     int cw_launch_gemm(bool bf16, int epi, const AParams& ap, const void* W, int M, int N, int K, const EpiParams& ep, hipStream_t st); \
     void cw_gemm_set_256_min_tiles(int n); \
@@ -392,6 +399,11 @@ struct PrefillAlign {
     int cw_launch_prefill_gemm(const void* A, const void* W, const PrefillEpi& ep, int M, int N, int K, hipStream_t st); \
     int cw_launch_prefill_attn(const void* Q, const void* K, const void* V, void* out, int rows, int n_q, int H, int cap, int n_keys, int causal, int kv_div, hipStream_t st); \
     int cw_launch_prefill_attn_align(const void* Q, const void* K, const void* V, void* out, int rows, int n_q, int H, int cap, int n_keys, int causal, int kv_div, const PrefillAlign& al, hipStream_t st); \
+    int cw_launch_score_ln(const float* x, const int* src, const float* g, const float* b, void* out, int M, int D, hipStream_t st); \
+    int cw_score_head_splits(int M, int V, int* tiles_per_split); \
+    int cw_launch_score_head(const void* A, const void* W, const int* target, ScorePart* part, int M, int V, int K, float* logprob, int* top_id, float* top_logprob, hipStream_t st); \
+    int cw_launch_score_head_unfused(const void* A, const void* W, const int* target, float* logits, int ldv, int M, int V, int K, float* logprob, int* top_id, float* top_logprob, hipStream_t st); \
+    int cw_launch_score_rows(const float* logits, int ldv, int V, const int* target, int t_stride, int t, int rows, float* logprob, int* top_id, float* top_logprob, hipStream_t st); \
     int cw_launch_attn_encoder(bool bf16, const void* Q, const void* K, const void* V, void* out, int B, int H, int S, int S_pad, hipStream_t st); \
     int cw_launch_attn_decode(bool bf16, const DecAttnParams& p, hipStream_t st); \
     int cw_launch_attn_cross_split(bool bf16, const CrossSplitParams& p, hipStream_t st); \

@@ -1,0 +1,265 @@
+// Scoring head (16-bit engines): the end of a teacher-forced decoder forward for every scored position at once -- final LayerNorm,
+// projection onto the vocabulary, log-softmax and the pick of the target token -- without ever writing the [M][V] logits
+// (engine.hip: cw_score_tokens, score_head_launch / score_head_fetch).
+//
+//   score_ln_kernel        a[m] = ((x[src[m]] - mean) * rstd) * g + b as 16-bit    (the final LayerNorm keeps its affine: the
+//                          tied embedding is shared with the token lookup, so nothing is folded into it)
+//   score_head_kernel      logits tile = a W^T on MFMA 16x16x32 over the fragment-major tied embedding (gemm.hip:
+//                          wfrag_pack_kernel); block (m-tile of 128 rows, split of the vocabulary).  Per row, in f32 registers:
+//                          running maximum, running sum of exp(logit - max), the target's logit if its column is the block's,
+//                          the best (logit, id) -- lowest id on an exact tie, as sample_kernel.  Columns >= V take no part.
+//   score_combine_kernel   merges the [M][n_split] partials: logprob = logit[target] - logsumexp, top_id, top_logprob
+//   score_rows_kernel      the same three numbers from a row of f32 logits the decode step left (the per-position fallback)
+#include <hip/hip_runtime.h>
+#include "kernels.h"
+
+namespace CW_NS {
+
+// one wave per row, 4 rows per block; src null: row m of x
+__global__ __launch_bounds__(256) void score_ln_kernel(const float* __restrict__ x, const int* __restrict__ src,
+                                                       const float* __restrict__ gam, const float* __restrict__ bet,
+                                                       bf16_t* __restrict__ out, int M, int D) {
+    const int lane = threadIdx.x & 63;
+    const int m = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (m >= M) return;
+    const float* xr = x + (size_t)(src ? src[m] : m) * D;
+    float s = 0.f;
+    for (int k = lane; k < D; k += 64) s += xr[k];
+    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
+    const float mean = s / (float)D;
+    float q = 0.f;
+    for (int k = lane; k < D; k += 64) { const float d = xr[k] - mean; q += d * d; }
+    for (int o = 32; o > 0; o >>= 1) q += __shfl_xor(q, o, 64);
+    const float rstd = 1.0f / sqrtf(q / (float)D + 1e-5f);
+    for (int k = lane; k < D; k += 64) Act<bf16_t>::st(out + (size_t)m * D + k, (xr[k] - mean) * rstd * gam[k] + bet[k]);
+}
+
+__device__ static inline bool score_better(float v, int i, float bv, int bi) { return v > bv || (v == bv && i < bi); }
+
+// grid (m-tiles of 128 rows, n_split); 4 waves, wave w owns rows m0 + 32 w .. + 31 and walks the split's 16-column tiles four at
+// a time (2 x 4 MFMA tiles, 8 accumulators).  The four waves read the same W fragments (one fetch, three cache hits), so one
+// block streams its vocabulary slice once for 128 rows.  A: [M][K] 16-bit row-major; W: fragment-major, (V + 15) / 16 tiles.
+// C fragment element r of lane (l15, g) is row 16 i + 4 g + r, column 16 j + l15: a lane keeps the statistics of its 8 rows over
+// its own columns, and the 16 lanes of a row are merged once at the end.
+// STORE (the unfused form, kept for the A/B of cw_time_score_head only): the same tile loop writes the f32 logits [M][ldv]
+// instead of keeping statistics; score_rows_kernel then makes one pass per row.
+template <bool STORE>
+__global__ __launch_bounds__(256) void score_head_kernel(const bf16_t* __restrict__ A, const bf16_t* __restrict__ W,
+                                                         const int* __restrict__ target, ScorePart* __restrict__ part,
+                                                         int M, int V, int K, int tiles_per_split, int n_split,
+                                                         float* __restrict__ logits, int ldv) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int l15 = lane & 15, g = lane >> 4;
+    const int m0 = blockIdx.x * 128 + wave * 32;
+    const int split = blockIdx.y;
+    const int NT = (V + 15) >> 4, KS = K >> 5;
+    const int t_begin = split * tiles_per_split;
+    const int t_end = min(NT, t_begin + tiles_per_split);
+    const bool mv[2] = {m0 + l15 < M, m0 + 16 + l15 < M};
+    const bf16x8_t zero = bf16x8_t{0, 0, 0, 0, 0, 0, 0, 0};
+    float mx[8], sum[8], tl[8], bv[8];
+    int bi[8], tg[8];
+#pragma unroll
+    for (int q = 0; q < 8; ++q) {
+        const int m = m0 + (q >> 2) * 16 + g * 4 + (q & 3);
+        mx[q] = -INFINITY; sum[q] = 0.f; tl[q] = -INFINITY; bv[q] = -INFINITY; bi[q] = 0x7fffffff;
+        tg[q] = m < M ? target[m] : -1;
+    }
+    const bf16_t* a0 = A + (size_t)(m0 + l15) * K + g * 8;
+    const bf16_t* a1 = a0 + (size_t)16 * K;
+    for (int t0 = t_begin; t0 < t_end; t0 += 4) {
+        f32x4_t acc[2][4];
+#pragma unroll
+        for (int i = 0; i < 2; ++i)
+#pragma unroll
+            for (int j = 0; j < 4; ++j) acc[i][j] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+        bool tv[4];
+        const bf16_t* wp[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            tv[j] = t0 + j < t_end;
+            wp[j] = W + ((size_t)(tv[j] ? t0 + j : t0) * KS * 64 + lane) * 8;
+        }
+        for (int s = 0; s < KS; ++s) {
+            bf16x8_t a[2], b[4];
+            a[0] = mv[0] ? *(const bf16x8_t*)(a0 + s * 32) : zero;
+            a[1] = mv[1] ? *(const bf16x8_t*)(a1 + s * 32) : zero;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) b[j] = *(const bf16x8_t*)(wp[j] + (size_t)s * 512);
+#pragma unroll
+            for (int i = 0; i < 2; ++i)
+#pragma unroll
+                for (int j = 0; j < 4; ++j) acc[i][j] = cw_mfma_16x16x32(a[i], b[j], acc[i][j]);
+        }
+        if (STORE) {
+#pragma unroll
+            for (int q = 0; q < 8; ++q) {
+                const int m = m0 + (q >> 2) * 16 + g * 4 + (q & 3);
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    const int n = (t0 + j) * 16 + l15;
+                    if (tv[j] && n < V && m < M) logits[(size_t)m * ldv + n] = acc[q >> 2][j][q & 3];
+                }
+            }
+            continue;
+        }
+#pragma unroll
+        for (int q = 0; q < 8; ++q) {
+            const int i = q >> 2, r = q & 3;
+            float v[4];
+            float mnew = mx[q];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const int n = (t0 + j) * 16 + l15;
+                const bool ok = tv[j] && n < V;
+                v[j] = ok ? acc[i][j][r] : -INFINITY;
+                mnew = fmaxf(mnew, v[j]);
+                if (ok && n == tg[q]) tl[q] = v[j];
+                if (ok && v[j] > bv[q]) { bv[q] = v[j]; bi[q] = n; }          // columns ascend within a lane: strict > keeps the lowest id
+            }
+            if (mnew > -INFINITY) {
+                float add = 0.f;
+#pragma unroll
+                for (int j = 0; j < 4; ++j) add += v[j] > -INFINITY ? expf(v[j] - mnew) : 0.f;
+                sum[q] = (mx[q] > -INFINITY ? sum[q] * expf(mx[q] - mnew) : 0.f) + add;
+                mx[q] = mnew;
+            }
+        }
+    }
+    if (STORE) return;
+    // the 16 lanes (l15) of a row
+#pragma unroll
+    for (int q = 0; q < 8; ++q) {
+#pragma unroll
+        for (int off = 1; off < 16; off <<= 1) {
+            const float omx = __shfl_xor(mx[q], off, 64), osum = __shfl_xor(sum[q], off, 64), otl = __shfl_xor(tl[q], off, 64);
+            const float obv = __shfl_xor(bv[q], off, 64);
+            const int obi = __shfl_xor(bi[q], off, 64);
+            const float mnew = fmaxf(mx[q], omx);
+            if (mnew > -INFINITY)
+                sum[q] = (mx[q] > -INFINITY ? sum[q] * expf(mx[q] - mnew) : 0.f) + (omx > -INFINITY ? osum * expf(omx - mnew) : 0.f);
+            mx[q] = mnew;
+            tl[q] = fmaxf(tl[q], otl);                                        // at most one lane holds the target's column
+            if (score_better(obv, obi, bv[q], bi[q])) { bv[q] = obv; bi[q] = obi; }
+        }
+        const int m = m0 + (q >> 2) * 16 + g * 4 + (q & 3);
+        if (l15 == 0 && m < M) {
+            ScorePart p;
+            p.mx = mx[q]; p.sum = sum[q]; p.tl = tl[q]; p.bv = bv[q]; p.bi = bi[q];
+            part[(size_t)m * n_split + split] = p;
+        }
+    }
+}
+
+// one thread per row
+__global__ __launch_bounds__(256) void score_combine_kernel(const ScorePart* __restrict__ part, int M, int n_split,
+                                                            float* __restrict__ logprob, int* __restrict__ top_id,
+                                                            float* __restrict__ top_logprob) {
+    const int m = blockIdx.x * 256 + threadIdx.x;
+    if (m >= M) return;
+    const ScorePart* p = part + (size_t)m * n_split;
+    float mx = -INFINITY, tl = -INFINITY, bv = -INFINITY;
+    int bi = 0x7fffffff;
+    for (int s = 0; s < n_split; ++s) {
+        mx = fmaxf(mx, p[s].mx);
+        tl = fmaxf(tl, p[s].tl);
+        if (score_better(p[s].bv, p[s].bi, bv, bi)) { bv = p[s].bv; bi = p[s].bi; }
+    }
+    float sum = 0.f;
+    for (int s = 0; s < n_split; ++s)
+        if (p[s].mx > -INFINITY) sum += p[s].sum * expf(p[s].mx - mx);
+    const float lse = mx + logf(sum);
+    logprob[m] = tl - lse;
+    top_id[m] = bi;
+    top_logprob[m] = bv - lse;
+}
+
+// one block per row of f32 logits [rows][ldv]; target[row * t_stride + t] (negative: no target, the row's logprob is -inf);
+// results at out[row * t_stride + t]
+__global__ __launch_bounds__(256) void score_rows_kernel(const float* __restrict__ logits, int ldv, int V,
+                                                         const int* __restrict__ target, int t_stride, int t,
+                                                         float* __restrict__ logprob, int* __restrict__ top_id,
+                                                         float* __restrict__ top_logprob) {
+    __shared__ float s_v[4], s_s[4];
+    __shared__ int s_i[4];
+    const int row = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const float* lg = logits + (size_t)row * ldv;
+    float bv = -INFINITY;
+    int bi = 0x7fffffff;
+    for (int n = tid; n < V; n += 256)
+        if (lg[n] > bv) { bv = lg[n]; bi = n; }
+    for (int o = 32; o > 0; o >>= 1) {
+        const float ov = __shfl_xor(bv, o, 64);
+        const int oi = __shfl_xor(bi, o, 64);
+        if (score_better(ov, oi, bv, bi)) { bv = ov; bi = oi; }
+    }
+    if (lane == 0) { s_v[wave] = bv; s_i[wave] = bi; }
+    __syncthreads();
+    bv = s_v[0]; bi = s_i[0];
+    for (int w = 1; w < 4; ++w)
+        if (score_better(s_v[w], s_i[w], bv, bi)) { bv = s_v[w]; bi = s_i[w]; }
+    float sum = 0.f;
+    for (int n = tid; n < V; n += 256) sum += expf(lg[n] - bv);
+    for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o, 64);
+    if (lane == 0) s_s[wave] = sum;
+    __syncthreads();
+    if (tid == 0) {
+        const float lse = bv + logf((s_s[0] + s_s[1]) + (s_s[2] + s_s[3]));
+        const size_t o = (size_t)row * t_stride + t;
+        const int tg = target[o];
+        logprob[o] = (tg >= 0 && tg < V) ? lg[tg] - lse : -INFINITY;
+        top_id[o] = bi;
+        top_logprob[o] = bv - lse;
+    }
+}
+
+int cw_launch_score_ln(const float* x, const int* src, const float* g, const float* b, void* out, int M, int D, hipStream_t st) {
+    if (M < 1 || D < 1) return CW_ERR_INVALID;
+    hipLaunchKernelGGL(score_ln_kernel, dim3((M + 3) / 4), dim3(256), 0, st, x, src, g, b, (bf16_t*)out, M, D);
+    return CW_OK;
+}
+
+// Vocabulary splits for M rows: about two blocks per compute unit over all m-tiles, four 16-column tiles at least per split
+int cw_score_head_splits(int M, int V, int* tiles_per_split) {
+    const int NT = (V + 15) / 16, mt = (M + 127) / 128;
+    int ns = 512 / mt;
+    ns = ns < 1 ? 1 : (ns > 256 ? 256 : ns);
+    int tps = ((NT + ns - 1) / ns + 3) & ~3;
+    if (tiles_per_split) *tiles_per_split = tps;
+    return (NT + tps - 1) / tps;
+}
+
+// part: cw_score_head_splits(M, V) records per row
+int cw_launch_score_head(const void* A, const void* W, const int* target, ScorePart* part, int M, int V, int K, float* logprob,
+                         int* top_id, float* top_logprob, hipStream_t st) {
+    if (M < 1 || V < 1 || K < 32 || K % 32) return CW_ERR_INVALID;
+    int tps = 0;
+    const int ns = cw_score_head_splits(M, V, &tps);
+    hipLaunchKernelGGL(score_head_kernel<false>, dim3((M + 127) / 128, ns), dim3(256), 0, st, (const bf16_t*)A, (const bf16_t*)W,
+                       target, part, M, V, K, tps, ns, (float*)nullptr, 0);
+    hipLaunchKernelGGL(score_combine_kernel, dim3((M + 255) / 256), dim3(256), 0, st, part, M, ns, logprob, top_id, top_logprob);
+    return CW_OK;
+}
+
+// the unfused form of cw_launch_score_head: f32 logits [M][ldv] (ldv >= V) through the same GEMM, then a row-wise pass
+int cw_launch_score_head_unfused(const void* A, const void* W, const int* target, float* logits, int ldv, int M, int V, int K,
+                                 float* logprob, int* top_id, float* top_logprob, hipStream_t st) {
+    if (M < 1 || V < 1 || ldv < V || K < 32 || K % 32) return CW_ERR_INVALID;
+    int tps = 0;
+    const int ns = cw_score_head_splits(M, V, &tps);
+    hipLaunchKernelGGL(score_head_kernel<true>, dim3((M + 127) / 128, ns), dim3(256), 0, st, (const bf16_t*)A, (const bf16_t*)W,
+                       target, (ScorePart*)nullptr, M, V, K, tps, ns, logits, ldv);
+    hipLaunchKernelGGL(score_rows_kernel, dim3(M), dim3(256), 0, st, (const float*)logits, ldv, V, target, 1, 0, logprob, top_id,
+                       top_logprob);
+    return CW_OK;
+}
+
+int cw_launch_score_rows(const float* logits, int ldv, int V, const int* target, int t_stride, int t, int rows, float* logprob,
+                         int* top_id, float* top_logprob, hipStream_t st) {
+    if (rows < 1 || V < 1 || ldv < V || t < 0 || t >= t_stride) return CW_ERR_INVALID;
+    hipLaunchKernelGGL(score_rows_kernel, dim3(rows), dim3(256), 0, st, logits, ldv, V, target, t_stride, t, logprob, top_id,
+                       top_logprob);
+    return CW_OK;
+}
+
+}  // namespace CW_NS

@@ -323,6 +323,86 @@ class Engine:
         """cw_set_option "align_prefill": 0 runs cw_align_tokens' forward through the per-position decoder step."""
         self._chk(self.lib.cw_set_option(self.ctx, b"align_prefill", 1 if on else 0))
 
+    def _token_table(self, ids):
+        nb = len(ids)
+        n = _i32([len(r) for r in ids])
+        stride = max(1, int(n.max()) if nb else 1)
+        table = np.zeros((nb, stride), dtype=np.int32)
+        for b, r in enumerate(ids):
+            r = np.asarray(r, dtype=np.int64)
+            if r.size and (r.min() < 0 or r.max() >= self.spec.vocab_size):    # before the int32 table could wrap them
+                raise ValueError(f"row {b}: token id outside the vocabulary (0 .. {self.spec.vocab_size - 1})")
+            table[b, :len(r)] = r
+        return n, stride, table
+
+    def score_tokens(self, rows, n_init: int, rows_per_item: int = 1):
+        """Teacher-forced log-probabilities (cw_score_tokens): ``rows[r]`` is a whole decoder input (``n_init`` init tokens,
+        transcript, eos), scored against resident feature item r // rows_per_item.  Returns (logprob, top_id, top_logprob):
+        per row one array over its text tokens and the eos (len(rows[r]) - n_init entries) -- log p(token | audio, tokens
+        before it) over the raw logits, and the arg-max id of the same distribution with its log-probability."""
+        nr = len(rows)
+        rpi = int(rows_per_item)
+        if rpi >= 1 and nr % rpi:
+            raise ValueError(f"{nr} rows are not a multiple of rows_per_item={rpi}")
+        n, stride, table = self._token_table(rows)
+        lp = np.zeros((nr, stride), dtype=np.float32)
+        ti = np.zeros((nr, stride), dtype=np.int32)
+        tl = np.zeros((nr, stride), dtype=np.float32)
+        self._chk(self.lib.cw_score_tokens(self.ctx, nr // rpi if rpi >= 1 else nr, rpi, _ptr(table), stride, _ptr(n), int(n_init),
+                                           _ptr(lp), _ptr(ti), _ptr(tl)))
+        k = int(n_init)
+        return ([lp[b, k:n[b]].copy() for b in range(nr)], [ti[b, k:n[b]].astype(np.int64) for b in range(nr)],
+                [tl[b, k:n[b]].copy() for b in range(nr)])
+
+    def align_score_tokens(self, num_frames, ids, n_init: int):
+        """cw_align_score_tokens: ``align_tokens`` and ``score_tokens`` (one row per item) of the same rows in one forward.
+        Returns (timestamps as align_tokens, logprob, top_id, top_logprob as score_tokens)."""
+        nb = len(ids)
+        n, stride, table = self._token_table(ids)
+        nf = _i32(num_frames)
+        ts = np.zeros((nb, stride), dtype=np.float32)
+        lp = np.zeros((nb, stride), dtype=np.float32)
+        ti = np.zeros((nb, stride), dtype=np.int32)
+        tl = np.zeros((nb, stride), dtype=np.float32)
+        self._chk(self.lib.cw_align_score_tokens(self.ctx, nb, _ptr(nf), _ptr(table), stride, _ptr(n), int(n_init), _ptr(ts),
+                                                 _ptr(lp), _ptr(ti), _ptr(tl)))
+        k = int(n_init)
+        return ([ts[b, :n[b]].copy() for b in range(nb)], [lp[b, k:n[b]].copy() for b in range(nb)],
+                [ti[b, k:n[b]].astype(np.int64) for b in range(nb)], [tl[b, k:n[b]].copy() for b in range(nb)])
+
+    def score_prefill_runs(self) -> int:
+        """cw_score_prefill_runs: scoring calls of this engine whose forward ran as the batched prefill."""
+        return int(self.lib.cw_score_prefill_runs(self.ctx))
+
+    def set_score_prefill(self, on: bool):
+        """cw_set_option "score_prefill": 0 runs the scoring forward through the per-position decoder step."""
+        self._chk(self.lib.cw_set_option(self.ctx, b"score_prefill", 1 if on else 0))
+
+    def test_score_head(self, x, ln_g, ln_b, embed, targets):
+        """cw_test_score_head: x [M][D], ln_g / ln_b [D], embed [V][D], targets [M] -> (logprob, top_id, top_logprob) [M]."""
+        x = np.ascontiguousarray(x, np.float32)
+        embed = np.ascontiguousarray(embed, np.float32)
+        g = np.ascontiguousarray(ln_g, np.float32)
+        b = np.ascontiguousarray(ln_b, np.float32)
+        t = _i32(targets)
+        M, D = x.shape
+        V = embed.shape[0]
+        if embed.shape[1] != D or g.shape != (D,) or b.shape != (D,) or t.shape != (M,):
+            raise ValueError("test_score_head: shapes do not agree")
+        lp = np.zeros(M, np.float32)
+        ti = np.zeros(M, np.int32)
+        tl = np.zeros(M, np.float32)
+        self._chk(self.lib.cw_test_score_head(self.ctx, M, D, V, _ptr(x), _ptr(g), _ptr(b), _ptr(embed), _ptr(t), _ptr(lp),
+                                              _ptr(ti), _ptr(tl)))
+        return lp, ti, tl
+
+    def time_score_head(self, M: int, unfused: bool = False, iters: int = 10) -> float:
+        """cw_time_score_head: ms per run of the scoring head over M rows at this engine's geometry (fused, or the unfused form
+        that stores f32 logits and reduces them row by row)."""
+        ms = C.c_float(0.0)
+        self._chk(self.lib.cw_time_score_head(self.ctx, int(M), 1 if unfused else 0, int(iters), C.byref(ms)))
+        return float(ms.value)
+
     # ------------------------------------------------------------------ beam search (device half; host half: generation.beam_search)
     def beam_begin(self, prompt: np.ndarray, num_beams: int, max_length: int, min_new_tokens: int = 0):
         prompt = _i32(prompt)

@@ -11,7 +11,7 @@ the device through ``Engine``; this module only decides *what* to run next from 
 from __future__ import annotations
 
 import dataclasses
-from typing import List, Optional
+from typing import Callable, List, Optional, Sequence
 
 import numpy as np
 
@@ -547,14 +547,16 @@ def check_transcript_ids(spec, ids) -> np.ndarray:
 
 
 def align(engine: Engine, n_items: int, num_frames, transcripts, *, language: Optional[str] = None,
-          task: Optional[str] = None):
+          task: Optional[str] = None, return_scores: bool = False):
     """Forced alignment of known transcripts to the ``n_items`` 30 s feature windows resident in the engine.
 
     Row b is the decoder input <|startoftranscript|><|lang|><|task|> ++ transcripts[b] ++ eos, with the init tokens resolved by
     ``resolve_prompt`` exactly as for ``generate`` (``language=None``: detected per item).  The engine runs one teacher-forced
     forward (cw_align_tokens) and the token-timestamp stages on it.  Returns {"sequences": list of int64 arrays (the
     transcripts), "token_timestamps": list of float32 arrays, one timestamp per transcript token} -- the fields the pipeline
-    hands to ``collate.decode_asr``, as ``generate`` returns them for its own tokens."""
+    hands to ``collate.decode_asr``, as ``generate`` returns them for its own tokens.  ``return_scores=True`` runs the full
+    scoring forward instead of the early-stopping one (cw_align_score_tokens: same timestamps) and adds "token_logprobs",
+    "top_ids", "top_logprobs": per transcript one entry per token plus one for the eos."""
     spec = engine.spec
     texts = [check_transcript_ids(spec, t) for t in transcripts]
     if len(texts) != n_items:
@@ -576,5 +578,89 @@ def align(engine: Engine, n_items: int, num_frames, transcripts, *, language: Op
     else:
         inits = [init_tokens(spec, language, task)] * n_items
     rows = [np.concatenate([np.asarray(i, np.int64), t, [spec.eos_token_id]]) for i, t in zip(inits, texts)]
+    if return_scores:
+        ts, lp, ti, tl = engine.align_score_tokens(num_frames, rows, n_init)
+        return {"sequences": texts, "token_timestamps": [s[n_init:n_init + len(t)] for s, t in zip(ts, texts)],
+                "token_logprobs": lp, "top_ids": ti, "top_logprobs": tl}
     ts = engine.align_tokens(num_frames, rows, n_init)
     return {"sequences": texts, "token_timestamps": [s[n_init:n_init + len(t)] for s, t in zip(ts, texts)]}
+
+
+def plan_score_calls(n_candidates: Sequence[int], max_batch: int):
+    """Groups the candidate rows of ``score`` into engine calls of equal rows_per_item: items with the same candidate count K
+    share calls of up to max_batch // K items; an item with more candidates than ``max_batch`` rows is split into slices of at
+    most max_batch candidates (a slice is grouped like an item of that many candidates).  Returns a list of
+    (rows_per_item, [(item, first candidate), ...]) in a deterministic order; every (item, candidate) appears exactly once."""
+    if max_batch < 1:
+        raise ValueError("max_batch must be at least 1")
+    by_k = {}
+    for b, k in enumerate(n_candidates):
+        if k < 1:
+            raise ValueError(f"item {b} has no candidates")
+        for c0 in range(0, k, max_batch):
+            by_k.setdefault(min(max_batch, k - c0), []).append((b, c0))
+    calls = []
+    for k in sorted(by_k):
+        per = max(1, max_batch // k)
+        for i in range(0, len(by_k[k]), per):
+            calls.append((k, by_k[k][i:i + per]))
+    return calls
+
+
+def score(engine: Engine, n_items: int, candidates, *, language: Optional[str] = None, task: Optional[str] = None,
+          load_items: Optional[Callable[[List[int]], None]] = None):
+    """Teacher-forced log-probabilities of candidate transcripts of the ``n_items`` 30 s feature windows resident in the engine.
+
+    ``candidates[b]`` is a list of K_b transcripts (token ids, ``check_transcript_ids``).  Row (b, k) is the decoder input
+    <|startoftranscript|><|lang|><|task|> ++ candidates[b][k] ++ eos, the init tokens resolved exactly as ``align`` does
+    (``language=None``: detected per item).  Calls are planned by ``plan_score_calls``.  The engine scores row r against
+    resident item r // rows_per_item, so a call over a subset of the items needs them resident as items 0 .. n-1:
+    ``load_items(items)`` is called before such a call (and once more with all items at the end) to make them so -- the
+    pipeline passes a function that computes their features again; without it only plans whose every call covers the items
+    0 .. n-1 in order run (all items with one candidate count, fitting one call).  Returns per item a list over its candidates of
+    {"ids", "token_logprobs", "top_ids", "top_logprobs"}: one entry per token plus one for the eos."""
+    spec = engine.spec
+    if len(candidates) != n_items:
+        raise ValueError(f"{len(candidates)} candidate lists for {n_items} items")
+    if n_items > engine.max_batch:
+        raise ValueError(f"{n_items} items exceed the engine's {engine.max_batch} rows")
+    texts = []
+    for b, cands in enumerate(candidates):
+        if len(cands) == 0:
+            raise ValueError(f"item {b}: empty candidate list")
+        texts.append([check_transcript_ids(spec, t) for t in cands])
+    toks, detect = resolve_prompt(spec, language, task)
+    if detect and not spec.lang_to_id:
+        raise ValueError("Cannot detect language for an English-only checkpoint: the generation config has no `lang_to_id`.")
+    n_init = len(toks)
+    for b, cands in enumerate(texts):
+        for k, t in enumerate(cands):
+            if n_init + len(t) + 1 > spec.max_target_positions:
+                raise ValueError(f"transcript {b}.{k}: {n_init} init tokens + {len(t)} tokens + eos exceed max_target_positions "
+                                 f"({spec.max_target_positions})")
+    if detect:
+        engine.encode(list(range(n_items)), np.zeros(n_items, np.int64), np.full(n_items, N_FRAMES, np.int64))
+        inits = [init_tokens(spec, language, task, lang_id=l) for l in detect_language(engine, n_items)]
+    else:
+        inits = [init_tokens(spec, language, task)] * n_items
+    out = [[None] * len(c) for c in texts]
+    resident = list(range(n_items))
+    for rpi, members in plan_score_calls([len(c) for c in texts], engine.max_batch):
+        items = [b for b, _ in members]
+        if items != resident[:len(items)]:
+            if load_items is None:
+                raise ValueError("score: this call covers items %s but the resident items are %s and no load_items was given"
+                                 % (items, resident))
+            load_items(items)
+            resident = list(items)
+        rows = [np.concatenate([np.asarray(inits[b], np.int64), texts[b][c0 + j], [spec.eos_token_id]])
+                for b, c0 in members for j in range(rpi)]
+        lp, ti, tl = engine.score_tokens(rows, n_init, rows_per_item=rpi)
+        r = 0
+        for b, c0 in members:
+            for j in range(rpi):
+                out[b][c0 + j] = {"ids": texts[b][c0 + j], "token_logprobs": lp[r], "top_ids": ti[r], "top_logprobs": tl[r]}
+                r += 1
+    if resident != list(range(n_items)) and load_items is not None:
+        load_items(list(range(n_items)))
+    return out

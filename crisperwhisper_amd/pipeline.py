@@ -477,22 +477,116 @@ class CrisperWhisperPipeline:
             return generation.check_transcript_ids(self.bundle.spec, enc(transcript, add_special_tokens=False))
         return generation.check_transcript_ids(self.bundle.spec, transcript)
 
-    def align(self, inputs, transcripts, language: Optional[str] = None, task: Optional[str] = None, **kwargs):
+    def _forced_kwargs(self, who, language, task, kwargs):
+        gk = dict(kwargs.pop("generate_kwargs", None) or {})
+        if "prompt_ids" in kwargs or "prompt_ids" in gk:
+            raise ValueError(f"prompt_ids is not accepted by {who}: the decoder input is the init tokens and the transcript")
+        if kwargs:
+            raise TypeError(f"{who}() got unexpected keyword arguments {sorted(kwargs)}")
+        unknown = set(gk) - {"language", "task"}
+        if unknown:
+            raise ValueError(f"{who}() takes only language / task generate_kwargs, got {sorted(unknown)}")
+        return (language if language is not None else gk.get("language")), (task if task is not None else gk.get("task"))
+
+    def _load_clips(self, who, inputs):
+        pcms = []
+        for k, x in enumerate(inputs):
+            pcm = self._load(x)
+            if len(pcm) > N_SAMPLES:
+                raise ValueError(f"input {k} is {len(pcm) / self.sampling_rate:.2f} s long: {who} takes at most 30 s "
+                                 f"({N_SAMPLES} samples) per input; long-form {'alignment' if who == 'align' else 'scoring'} is not implemented")
+            pcms.append(pcm)
+        return pcms
+
+    def _scored_words(self, ids, token_logprobs, token_timestamps=None):
+        """Words of one transcript with the sum of their tokens' log-probabilities, grouped by the collator itself."""
+        ts = token_timestamps if token_timestamps is not None else np.zeros(len(ids), np.float32)
+        text, words, groups = collate.decode_asr(self.vocab, [{"tokens": ids, "token_timestamps": ts}], time_precision=0.02,
+                                                 return_timestamps="word", return_token_groups=True)
+        chunks = []
+        for w, g in zip(words, groups):
+            c = {"text": w["text"], "logprob": float(np.sum(np.asarray(token_logprobs, np.float64)[g]))}
+            if token_timestamps is not None:
+                c["timestamp"] = w["timestamp"]
+            chunks.append(c)
+        return text, chunks
+
+    @staticmethod
+    def _candidate_list(t):
+        """transcripts[b] of ``score``: (list of candidates, whether it was given as a list).  A str, or a sequence whose
+        elements are integers, is one transcript; a list / tuple of str or of id sequences is a list of candidates."""
+        if isinstance(t, str):
+            return [t], False
+        if hasattr(t, "detach") and hasattr(t, "cpu"):
+            t = t.detach().cpu().numpy()
+        if isinstance(t, np.ndarray):
+            if t.ndim == 1:
+                return [t], False
+            raise ValueError(f"a transcript must be a 1-D sequence of token ids; give candidates as a list, got shape {t.shape}")
+        if not isinstance(t, (list, tuple)):
+            raise TypeError(f"a transcript is a str, a sequence of token ids or a list of those, got {type(t).__name__}")
+        if len(t) == 0:
+            raise ValueError("empty candidate list (an empty transcript is given as one candidate: [[]])")
+        is_int = [isinstance(e, (int, np.integer)) and not isinstance(e, bool) for e in t]
+        if all(is_int):
+            return [t], False
+        if any(is_int):
+            raise ValueError("a transcript mixes token ids with other elements: give either one sequence of ids or a list of candidates")
+        return list(t), True
+
+    def score(self, inputs, transcripts, language: Optional[str] = None, task: Optional[str] = None, **kwargs):
+        """How well known transcripts fit the audio: teacher-forced log-probabilities under the model.  ``inputs`` as
+        ``align`` takes them (one, or a list; each at most 30 s); ``transcripts[b]`` one transcript (``str`` or token ids) or
+        a list of candidates for input b, which share one encoder pass.  Per input one dict, or a list of dicts in the order
+        of the candidates: {"text", "logprob": sum over the tokens and the eos, "avg_logprob": logprob / (n_tokens + 1),
+        "tokens": [{"id", "logprob", "top_id", "top_logprob"}] (the eos last), "chunks": [{"text", "logprob"}]} -- a word's
+        logprob is the sum over the tokens the collator groups into it.  Raw logits: no suppress lists, no timestamp rules."""
+        language, task = self._forced_kwargs("score", language, task, kwargs)
+        single = not isinstance(inputs, (list, tuple))
+        if single:
+            inputs, transcripts = [inputs], [transcripts]
+        elif not isinstance(transcripts, (list, tuple)) or len(transcripts) != len(inputs):
+            raise ValueError(f"{len(inputs)} inputs need a list of {len(inputs)} transcripts, got "
+                             f"{len(transcripts) if isinstance(transcripts, (list, tuple)) else type(transcripts).__name__}")
+        cands, listed = [], []
+        for t in transcripts:
+            c, l = self._candidate_list(t)
+            cands.append([self._transcript_ids(x) for x in c])
+            listed.append(l)
+        generation.resolve_prompt(self.bundle.spec, language, task)        # refuses a bad language / task before any audio work
+        pcms = self._load_clips("score", inputs)
+        eng = self.engine
+        per = max(1, eng.max_batch)
+        eos = self.bundle.spec.eos_token_id
+        results = []
+        for b0 in range(0, len(pcms), per):
+            idx = list(range(b0, min(len(pcms), b0 + per)))
+            eng.mel([pcms[i] for i in idx])
+            out = generation.score(eng, len(idx), [cands[i] for i in idx], language=language, task=task,
+                                   load_items=lambda items: eng.mel([pcms[idx[j]] for j in items]))
+            for k, i in enumerate(idx):
+                rs = []
+                for o in out[k]:
+                    lp = np.asarray(o["token_logprobs"], np.float64)
+                    text, chunks = self._scored_words(o["ids"], lp[:-1])
+                    toks = [{"id": int(t), "logprob": float(a), "top_id": int(ti), "top_logprob": float(tl)}
+                            for t, a, ti, tl in zip(list(o["ids"]) + [eos], lp, o["top_ids"], o["top_logprobs"])]
+                    total = float(lp.sum())
+                    rs.append({"text": text, "logprob": total, "avg_logprob": total / (len(o["ids"]) + 1), "tokens": toks,
+                               "chunks": chunks})
+                results.append(rs if listed[i] else rs[0])
+        return results[0] if single else results
+
+    def align(self, inputs, transcripts, language: Optional[str] = None, task: Optional[str] = None,
+              return_scores: bool = False, **kwargs):
         """Word timestamps for known transcripts: ``inputs`` in any form ``__call__`` takes (one, or a list), each at most
         30 s; ``transcripts`` one per input, a ``str`` (needs a transformers tokenizer) or token ids without special
         tokens.  ``language`` / ``task`` resolve like ``generate_kwargs`` in ``__call__`` (``language=None``: detected per
         item).  Returns {"text", "chunks": [{"text", "timestamp": (start, end)}]} like ``__call__(..., return_timestamps=
-        "word")``, or a list of them for a list of inputs; lists run in batches of up to the pipeline's decoder rows."""
-        gk = dict(kwargs.pop("generate_kwargs", None) or {})
-        if "prompt_ids" in kwargs or "prompt_ids" in gk:
-            raise ValueError("prompt_ids is not accepted by align: the decoder input is the init tokens and the transcript")
-        if kwargs:
-            raise TypeError(f"align() got unexpected keyword arguments {sorted(kwargs)}")
-        unknown = set(gk) - {"language", "task"}
-        if unknown:
-            raise ValueError(f"align() takes only language / task generate_kwargs, got {sorted(unknown)}")
-        language = language if language is not None else gk.get("language")
-        task = task if task is not None else gk.get("task")
+        "word")``, or a list of them for a list of inputs; lists run in batches of up to the pipeline's decoder rows.
+        ``return_scores=True`` adds what ``score`` computes, from the same forward: "logprob" on every chunk, and "logprob" /
+        "avg_logprob" of the whole transcript (eos included) at the top level."""
+        language, task = self._forced_kwargs("align", language, task, kwargs)
         single = not isinstance(inputs, (list, tuple))
         if single:
             inputs, transcripts = [inputs], [transcripts]
@@ -501,19 +595,23 @@ class CrisperWhisperPipeline:
                              f"{len(transcripts) if isinstance(transcripts, (list, tuple)) else type(transcripts).__name__}")
         ids = [self._transcript_ids(t) for t in transcripts]
         generation.resolve_prompt(self.bundle.spec, language, task)        # refuses a bad language / task before any audio work
-        pcms = []
-        for k, x in enumerate(inputs):
-            pcm = self._load(x)
-            if len(pcm) > N_SAMPLES:
-                raise ValueError(f"input {k} is {len(pcm) / self.sampling_rate:.2f} s long: align takes at most 30 s "
-                                 f"({N_SAMPLES} samples) per input; long-form alignment is not implemented")
-            pcms.append(pcm)
+        pcms = self._load_clips("align", inputs)
         eng = self.engine
         per = max(1, eng.max_batch)
         results = []
         for b0 in range(0, len(pcms), per):
             idx = list(range(b0, min(len(pcms), b0 + per)))
             _, nf = eng.mel([pcms[i] for i in idx])
+            if return_scores:
+                out = generation.align(eng, len(idx), nf, [ids[i] for i in idx], language=language, task=task, return_scores=True)
+                for k in range(len(idx)):
+                    lp = np.asarray(out["token_logprobs"][k], np.float64)
+                    text, chunks = self._scored_words(out["sequences"][k], lp[:-1], out["token_timestamps"][k])
+                    total = float(lp.sum())
+                    results.append({"text": text, "chunks": [{"text": c["text"], "timestamp": c["timestamp"], "logprob": c["logprob"]}
+                                                             for c in chunks],
+                                    "logprob": total, "avg_logprob": total / (len(out["sequences"][k]) + 1)})
+                continue
             out = generation.align(eng, len(idx), nf, [ids[i] for i in idx], language=language, task=task)
             for k in range(len(idx)):
                 text, words = collate.decode_asr(self.vocab, [{"tokens": out["sequences"][k],

@@ -243,6 +243,28 @@ int32_t cw_align_tokens(cw_ctx* ctx, int32_t nb, const int32_t* num_frames, cons
 /* cw_align_prefill_runs: how many cw_align_tokens calls of this context ran their forward as the batched prefill.        */
 int32_t cw_align_prefill_runs(cw_ctx* ctx);
 
+/* cw_score_tokens: teacher-forced log-probabilities of known token sequences.  rows = n_items * rows_per_item decoder rows,
+ * row r scored against resident feature item r / rows_per_item (several candidate texts of one clip share its encoder pass).
+ * ids rows are whole decoder inputs exactly as cw_align_tokens takes them (init tokens, text, eos).  Written at index k =
+ * n_init .. n_ids[r]-1 of row r (the text tokens and the eos; nothing else is written): token_logprob = log p(ids[k] | audio,
+ * ids[0 .. k-1]) over the raw logits -- no suppress lists, no timestamp rules, temperature 1 -- and top_id / top_logprob the
+ * arg-max of the same distribution (lowest id on an exact tie).  Each [rows][ids_stride]; top_id / top_logprob may be null.
+ * On the 16-bit engines with the 16-bit cross cache the forward is one batched prefill over every layer followed by the
+ * scoring head (csrc/score.hip: final LayerNorm, vocabulary projection, log-softmax and gather fused; the logits are never
+ * stored); the f32 engine, the e4m3 cross cache and cw_set_option "score_prefill" = 0 run the per-position decoder step with
+ * every token forced.  CW_ERR_INVALID, before anything is launched: what cw_align_tokens refuses, rows_per_item < 1, rows
+ * over max_batch, a null ids / n_ids / token_logprob.                                                                      */
+int32_t cw_score_tokens(cw_ctx* ctx, int32_t n_items, int32_t rows_per_item, const int32_t* ids, int32_t ids_stride,
+                        const int32_t* n_ids, int32_t n_init, float* token_logprob, int32_t* top_id, float* top_logprob);
+/* cw_align_score_tokens: cw_align_tokens and cw_score_tokens (rows_per_item 1) of the same rows in one forward.  token_ts is
+ * bit-identical to cw_align_tokens' (the alignment rows come from launches both forwards make alike), the scores to
+ * cw_score_tokens'.                                                                                                        */
+int32_t cw_align_score_tokens(cw_ctx* ctx, int32_t nb, const int32_t* num_frames, const int32_t* ids, int32_t ids_stride,
+                              const int32_t* n_ids, int32_t n_init, float* token_ts, float* token_logprob, int32_t* top_id,
+                              float* top_logprob);
+/* cw_score_prefill_runs: how many scoring calls of this context ran their forward as the batched prefill.                  */
+int32_t cw_score_prefill_runs(cw_ctx* ctx);
+
 /* ---- stand-alone differential-test entry points for the alignment kernels ---------------------------- */
 /* attn [B][Ha][N][M] -> mat [B][N][M] (z-score, median(width), head mean); n_cols[b] <= M columns used.  */
 int32_t cw_align_matrix(cw_ctx* ctx, const float* attn, int32_t B, int32_t Ha, int32_t N, int32_t M,
@@ -276,6 +298,11 @@ int32_t cw_collate_feed(cw_collator* c, const int64_t* tokens, int32_t n_tokens,
 int32_t cw_collate_finish(cw_collator* c, int32_t* n_words, int64_t* text_bytes, int64_t* words_bytes, int32_t* warned);
 int32_t cw_collate_get(cw_collator* c, uint8_t* text, double* starts, double* ends, int64_t* word_offsets /* [n+1] */,
                        uint8_t* words_blob);
+/* The tokens behind every word of cw_collate_get: token_index [cw_collate_token_groups_total] holds, word after word, the
+ * positions of the word's tokens in the concatenation of all fed token arrays; word k owns token_index[group_offsets[k] ..
+ * group_offsets[k + 1]).                                                                                                   */
+int64_t cw_collate_token_groups_total(cw_collator* c);
+int32_t cw_collate_get_token_groups(cw_collator* c, int64_t* group_offsets /* [n+1] */, int32_t* token_index);
 void cw_collate_free(cw_collator* c);
 
 /* ---- kernel-level hooks used by the parity tests (host f32 in/out, run in the context's dtype) -------- */
@@ -303,6 +330,13 @@ int32_t cw_test_attention(cw_ctx* ctx, int32_t B, int32_t H, int32_t S, const fl
  * part_o [6][B][H*64], part_ml [B][H][6][2] = (max, sum) per split; head `align_head` captured as the only alignment head:
  * align [B][S] = exp(s - max of its split), align_ml [B][6][2].                                                     */
 #define CW_ATT_SPLITS 6
+/* The scoring head (csrc/score.hip) on its own: x [M][D] f32, ln_g / ln_b [D], embed [V][D] (rounded to the engine's 16-bit
+ * type), targets [M] in 0 .. V-1 -> logprob / top_id / top_logprob [M].  16-bit engines; D % 32 == 0.                      */
+int32_t cw_test_score_head(cw_ctx* ctx, int32_t M, int32_t D, int32_t V, const float* x, const float* ln_g, const float* ln_b,
+                           const float* embed, const int32_t* targets, float* logprob, int32_t* top_id, float* top_logprob);
+/* Times the scoring head at the context's geometry over M pseudo-random rows: unfused = 0 the fused kernels, 1 the same GEMM
+ * writing f32 logits [M][V] plus a row-wise log-softmax pass.  avg_ms per repetition (HIP events, one warm-up).           */
+int32_t cw_time_score_head(cw_ctx* ctx, int32_t M, int32_t unfused, int32_t iters, float* avg_ms);
 /* Decoder prompt prefill kernels (16-bit engines) against a host reference: cw_test_prefill_gemm runs the prefill GEMM over
  * fragment-major packed W with epilogue mode 0 = 16-bit store, 2 = f32 residual add (out: residual in, result out), 3 = erf GELU
  * (K % 32 == 0, N % 16 == 0); cw_test_prefill_attention the flash attention of the prefill (causal over n_keys >= n_q keys, or
