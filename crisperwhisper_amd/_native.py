@@ -60,6 +60,8 @@ _SIGS = {
     "cw_get_encoder_output": (_I, [_P, _P, _I]),
     "cw_decode": (_I, [_P, _I, _P, _I, _I, _I, _P, _P, _P, _P]),
     "cw_set_thresholds": (_I, [_P, C.c_float, C.c_float]),
+    "cw_set_sampling": (_I, [_P, C.c_float, C.c_uint64, _P, _I]),
+    "cw_decode_rows": (_I, [_P, _I, _P, _I, _I, _I, _P, _P, _P, _P, _P]),
     "cw_no_speech_probs": (_I, [_P, _I, _I, _P]),
     "cw_get_avg_logprobs": (_I, [_P, _P, _I]),
     "cw_get_logits": (_I, [_P, _P, _I]),
@@ -117,6 +119,7 @@ _SIGS = {
     "cw_test_score_head": (_I, [_P, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P]),
     "cw_time_score_head": (_I, [_P, _I, _I, _I, _P]),
     "cw_test_sample": (_I, [_P, _I, _P, _P, _I, _I, _I, _I, _P]),
+    "cw_test_sample_seeded": (_I, [_P, _I, _P, _P, _I, _I, _I, _I, C.c_float, C.c_uint64, _P, _P]),
     "cw_stage_times": (_I, [_P, _P, _P, _I]),
     "cw_time_kernel": (_I, [_P, _I, _I, _I, _P, _P]),
     "cw_time_decode_stage": (_I, [_P, _I, _I, _I, _P, _P, _P, _P]),

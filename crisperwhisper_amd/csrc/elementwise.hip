@@ -213,6 +213,32 @@ __device__ inline ArgPair wave_argmax(ArgPair a) {   // same DPP scan as wave_su
 // merges the SAMPLE_NS records of its row.
 #define SAMPLE_NS 16
 struct SamplePart { float bt_v; int bt_i; float bs_v; int bs_i; float ts_sum; float pad[3]; };
+struct SamplePert { float pt_v; int pt_i; float ps_v; int ps_i; };   // sampling: best perturbed text / timestamp token of a slice
+
+// Seeded sampling (include/crisperwhisper.h, cw_set_sampling): Gumbel-max.  The token drawn at temperature T is
+// argmax_v(s_v / T + g_v) over the allowed tokens, g_v = -log(-log(u_v)), an exact draw from softmax(s / T); restricted to a
+// subset (the timestamps once the timestamp rule has fired) it is an exact draw from the renormalised subset.  u_v comes from
+// Philox4x32-10 with key (seed_lo, seed_hi) and counter (v >> 2, t, stream_lo, stream_hi): one block of four words serves the
+// four logits of one float4 load, and nothing depends on the row index or the batch size.
+__device__ inline void philox4x32_10(unsigned c0, unsigned c1, unsigned c2, unsigned c3, unsigned k0, unsigned k1, unsigned out[4]) {
+#pragma unroll
+    for (int r = 0; r < 10; ++r) {
+        const unsigned hi0 = __umulhi(0xD2511F53u, c0), lo0 = 0xD2511F53u * c0;
+        const unsigned hi1 = __umulhi(0xCD9E8D57u, c2), lo1 = 0xCD9E8D57u * c2;
+        c0 = hi1 ^ c1 ^ k0; c1 = lo1; c2 = hi0 ^ c3 ^ k1; c3 = lo0;
+        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
+    }
+    out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
+}
+// g = -log(-log(u)), u = ((x >> 8) + 0.5) * 2^-24 as a real number.  n + 0.5 has 25 significant bits once n >= 2^23, so the upper
+// half of the range goes through 1 - u = (2^24 - n - 0.5) * 2^-24, which is exact there, and log1p: u itself would round to 1.
+__device__ inline float gumbel_from_bits(unsigned x) {
+    const unsigned n = x >> 8;
+    float e;
+    if (n < (1u << 23)) e = -logf(((float)n + 0.5f) * 5.9604644775390625e-08f);
+    else e = -log1pf(-(((float)((1u << 24) - n) - 0.5f) * 5.9604644775390625e-08f));
+    return -logf(e);
+}
 __global__ __launch_bounds__(256) void sample_partial_kernel(SampleParams p, SamplePart* __restrict__ part) {
     __shared__ float s_f[64];
     __shared__ int s_i[64];
@@ -233,12 +259,19 @@ __global__ __launch_bounds__(256) void sample_partial_kernel(SampleParams p, Sam
     const float4* lg4 = (const float4*)lg;
     const uchar4* mk4 = (const uchar4*)p.mask;
     ArgPair bt = {-INFINITY, 0x7fffffff}, bs = {-INFINITY, 0x7fffffff};
+    ArgPair pt = {-INFINITY, 0x7fffffff}, ps = {-INFINITY, 0x7fffffff};    // sampling: the same over the perturbed scores
+    const float temp = p.samp ? __uint_as_float(p.samp[0]) : 0.f;          // block-uniform; 0 = greedy
+    const bool sampling = temp > 0.f;
+    unsigned seed_lo = 0, seed_hi = 0, stream_lo = 0, stream_hi = 0;
+    if (sampling) { seed_lo = p.samp[1]; seed_hi = p.samp[2]; stream_lo = p.samp[4 + 2 * b]; stream_hi = p.samp[5 + 2 * b]; }
     float sv[4][4]; int nmine = 0;                                         // this thread's allowed timestamp scores
     float tv[4][4];                                                        // ... and allowed text scores (p.lp_sum only)
     for (int i4 = lo4 + tid, it = 0; i4 < hi4; i4 += 256, ++it) {
         const float4 x = lg4[i4]; const uchar4 mk = mk4[i4];
         const float xs[4] = {x.x, x.y, x.z, x.w};
         const unsigned char ms[4] = {mk.x, mk.y, mk.z, mk.w};
+        unsigned rnd[4] = {0u, 0u, 0u, 0u};
+        if (sampling) philox4x32_10((unsigned)i4, (unsigned)t, stream_lo, stream_hi, seed_lo, seed_hi, rnd);
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             const int v = i4 * 4 + j;
@@ -252,6 +285,10 @@ __global__ __launch_bounds__(256) void sample_partial_kernel(SampleParams p, Sam
                 if (!dead) val = xs[j];
                 ArgPair c = {val, v};
                 if (v < tb) bt = arg_better(bt, c); else bs = arg_better(bs, c);
+                if (sampling && !dead) {
+                    ArgPair q = {__fadd_rn(__fdiv_rn(val, temp), gumbel_from_bits(rnd[j])), v};
+                    if (v < tb) pt = arg_better(pt, q); else ps = arg_better(ps, q);
+                }
             }
             if (it < 4) { sv[it][j] = (v >= tb && v < p.V) ? val : -INFINITY; tv[it][j] = (v < tb) ? val : -INFINITY; }
         }
@@ -288,6 +325,22 @@ __global__ __launch_bounds__(256) void sample_partial_kernel(SampleParams p, Sam
         *p.n_unfinished = 0;                                     // stage 2 (a later launch) counts the running rows into it
         if (p.epoch) *p.epoch += 1u;                             // the next decoder forward tags its granules with a fresh epoch (declayer.hip)
     }
+    if (sampling) {                                             // block-uniform: every thread takes the barriers
+        pt = wave_argmax(pt);
+        ps = wave_argmax(ps);
+        __syncthreads();
+        if (lane == 0) { s_f[wave] = pt.v; s_i[wave] = pt.i; s_f[32 + wave] = ps.v; s_i[32 + wave] = ps.i; }
+        __syncthreads();
+        if (tid == 0) {
+            pt = {-INFINITY, 0x7fffffff}; ps = {-INFINITY, 0x7fffffff};
+            for (int w = 0; w < 4; ++w) {
+                pt = arg_better(pt, ArgPair{s_f[w], s_i[w]});
+                ps = arg_better(ps, ArgPair{s_f[32 + w], s_i[32 + w]});
+            }
+            SamplePert o; o.pt_v = pt.v; o.pt_i = pt.i; o.ps_v = ps.v; o.ps_i = ps.i;
+            ((SamplePert*)p.pert)[(size_t)b * SAMPLE_NS + sl] = o;
+        }
+    }
     if (tid == 0) {
         SamplePart o; o.bt_v = bt.v; o.bt_i = bt.i; o.bs_v = bs.v; o.bs_i = bs.i; o.ts_sum = acc; o.pad[0] = acc_t; o.pad[1] = o.pad[2] = 0.f;
         part[(size_t)b * SAMPLE_NS + sl] = o;
@@ -306,7 +359,8 @@ __global__ __launch_bounds__(1024) void sample_kernel(SampleParams p) {
     const int t = p.pos[b] + 1, tb = p.timestamp_begin;
     const int n_gen = t - n_prompt;
 
-    const bool was_finished = p.finished[b] != 0;
+    const int fin_in = p.finished[b];                  // 2: a row the caller masked out (cw_decode_rows): its ids stay as they are
+    const bool was_finished = fin_in != 0;
     int forced = (p.forced && use_forced) ? p.forced[(size_t)b * p.ids_stride + t] : -1;
 
     // timestamp grammar state from the generated suffix
@@ -334,6 +388,16 @@ __global__ __launch_bounds__(1024) void sample_kernel(SampleParams p) {
         int choice;
         if (force_ts || !(bt.v > -INFINITY)) choice = bs.i;
         else choice = arg_better(bt, bs).i;
+        const float temp = p.samp ? __uint_as_float(p.samp[0]) : 0.f;
+        if (temp > 0.f) {                              // seeded sampling: the winners over the perturbed scores; the rule above stays
+            ArgPair pt = {-INFINITY, 0x7fffffff}, ps = {-INFINITY, 0x7fffffff};
+            const SamplePert* pp = (const SamplePert*)p.pert + (size_t)b * SAMPLE_NS;
+            for (int i = 0; i < SAMPLE_NS; ++i) {
+                pt = arg_better(pt, ArgPair{pp[i].pt_v, pp[i].pt_i});
+                ps = arg_better(ps, ArgPair{pp[i].ps_v, pp[i].ps_i});
+            }
+            choice = force_ts ? ps.i : arg_better(pt, ps).i;
+        }
         // no finite candidate at all (every token masked, or NaN logits): torch.argmax of an all -inf row is index 0;
         // never hand an out-of-range id to the next step's embedding gather
         if (!(M > -INFINITY) || choice < 0 || choice >= p.V) choice = 0;
@@ -352,9 +416,9 @@ __global__ __launch_bounds__(1024) void sample_kernel(SampleParams p) {
             }
         }
         if (was_finished) tok = p.pad;                                  // utils.py:2928-2929
-        ids[t] = tok;
+        if (fin_in != 2) ids[t] = tok;
         if (tok >= tb && n_gen >= 0) p.last_ts_tok[b] = tok;
-        int fin = was_finished || (n_gen >= 0 && tok == p.eos) || (t + 1 >= max_length);
+        int fin = was_finished ? fin_in : ((n_gen >= 0 && tok == p.eos) || (t + 1 >= max_length));
         p.finished[b] = fin;
         if (!fin) atomicAdd(p.n_unfinished, 1);
         s_tok = tok;

@@ -154,6 +154,9 @@ struct cw_ctx {
     bool score_tokens = false;
     float logprob_thr = NAN, no_speech_thr = NAN;             // cw_set_thresholds (NaN: unset)
     void* d_sample_part = nullptr;            // [Bm][16] 32-byte slice records of the two-stage sampler
+    void* d_sample_pert = nullptr;            // [Bm][16] 16-byte records of the perturbed winners (seeded sampling)
+    unsigned int* d_samp = nullptr;           // [4 + 2 * Bm] temperature bits, seed, per-row stream ids (cw_set_sampling); zero = greedy
+    std::vector<unsigned int> samp_host;      // what d_samp holds
     float* d_align = nullptr;
     float *d_part_o = nullptr, *d_part_ml = nullptr, *d_align_ml = nullptr;   // split cross-attention partials
     bool align_unnormalized = false;
@@ -623,6 +626,9 @@ static int create_impl(cw_ctx* c) {
     CWCHK(c, dmalloc(c, &c->d_pos, 64 * 4)); CWCHK(c, dmalloc(c, &c->d_cfg, 4 * 4));
     CWCHK(c, dmalloc(c, &c->d_mask, (size_t)V + 16));
     CWCHK(c, dmalloc(c, &c->d_sample_part, (size_t)Bm * 16 * 32));
+    CWCHK(c, dmalloc(c, &c->d_sample_pert, (size_t)Bm * 16 * 16));
+    CWCHK(c, dmalloc(c, &c->d_samp, (size_t)(4 + 2 * Bm) * 4));
+    c->samp_host.assign((size_t)4 + 2 * Bm, 0u);
     CWCHK(c, dmalloc(c, &c->d_lp_sum, (size_t)Bm * 4)); CWCHK(c, dmalloc(c, &c->d_lp_cnt, (size_t)Bm * 4));
     CWCHK(c, dmalloc(c, &c->d_align_slot, (size_t)d.dec_layers * H * 4));
     {
@@ -1526,6 +1532,7 @@ static int launch_sample(cw_ctx* c, int nb, bool forced) {
     sp.partials = c->d_sample_part;
     if (c->score_tokens) { sp.lp_sum = c->d_lp_sum; sp.lp_cnt = c->d_lp_cnt; }
     sp.epoch = c->d_epoch;
+    sp.samp = c->d_samp; sp.pert = c->d_sample_pert;
     (void)forced;
     return KD(c, cw_launch_sample, sp, c->st);
 }
@@ -1689,20 +1696,27 @@ static int run_prefill(cw_ctx* c, int rows, int n_prompt, int kv_div, bool align
 
 static int decode_once(cw_ctx* c, int32_t nb, const int32_t* prompt, int32_t n_prompt, int32_t max_length,
                        int32_t min_new_tokens, const int32_t* forced, int32_t* sequences, int32_t* lengths,
-                       int32_t* argmax_out);
+                       int32_t* argmax_out, const int32_t* row_active);
+int32_t cw_decode_rows(cw_ctx* c, int32_t nb, const int32_t* prompt, int32_t n_prompt, int32_t max_length,
+                       int32_t min_new_tokens, const int32_t* forced, const int32_t* row_active, int32_t* sequences,
+                       int32_t* lengths, int32_t* argmax_out) {
+    int r = decode_once(c, nb, prompt, n_prompt, max_length, min_new_tokens, forced, sequences, lengths, argmax_out, row_active);
+    if (r != CW_HANDOFF_RETRY) return r;
+    CWCHK(c, handoffs_off(c, "decode"));
+    r = decode_once(c, nb, prompt, n_prompt, max_length, min_new_tokens, forced, sequences, lengths, argmax_out, row_active);
+    return r == CW_HANDOFF_RETRY ? fail(c, CW_ERR_HIP, "decode: an in-kernel wait timed out on the launch-per-stage path") : r;
+}
 int32_t cw_decode(cw_ctx* c, int32_t nb, const int32_t* prompt, int32_t n_prompt, int32_t max_length,
                   int32_t min_new_tokens, const int32_t* forced, int32_t* sequences, int32_t* lengths,
                   int32_t* argmax_out) {
-    int r = decode_once(c, nb, prompt, n_prompt, max_length, min_new_tokens, forced, sequences, lengths, argmax_out);
-    if (r != CW_HANDOFF_RETRY) return r;
-    CWCHK(c, handoffs_off(c, "decode"));
-    r = decode_once(c, nb, prompt, n_prompt, max_length, min_new_tokens, forced, sequences, lengths, argmax_out);
-    return r == CW_HANDOFF_RETRY ? fail(c, CW_ERR_HIP, "decode: an in-kernel wait timed out on the launch-per-stage path") : r;
+    return cw_decode_rows(c, nb, prompt, n_prompt, max_length, min_new_tokens, forced, nullptr, sequences, lengths, argmax_out);
 }
 
+// row_active (cw_decode_rows): a row with row_active[b] == 0 starts finished (state 2 of d_finished: sample_kernel neither writes
+// its ids nor adds to its log-probability sums), so what the previous decode left in d_ids / d_lp_sum / d_lp_cnt for it stays.
 static int decode_once(cw_ctx* c, int32_t nb, const int32_t* prompt, int32_t n_prompt, int32_t max_length,
                        int32_t min_new_tokens, const int32_t* forced, int32_t* sequences, int32_t* lengths,
-                       int32_t* argmax_out) {
+                       int32_t* argmax_out, const int32_t* row_active) {
     const int D = c->d.d_model, V = c->d.vocab_size, TGT = c->d.max_target_positions;
     if (!c->gen_set) return fail(c, CW_ERR_STATE, "cw_set_generation not called");
     if (nb < 1 || nb > c->nb_encoded) return fail(c, CW_ERR_STATE, "nb=%d but %d windows encoded", nb, c->nb_encoded);
@@ -1712,17 +1726,39 @@ static int decode_once(cw_ctx* c, int32_t nb, const int32_t* prompt, int32_t n_p
     c->align_cur = c->d_align;
     CWCHK(c, epoch_hygiene(c, 2 * (long long)max_length + 4));   // (a resumed call runs some positions twice)
     std::vector<int> ids((size_t)nb * TGT, c->gen.pad_token_id);
-    for (int b = 0; b < nb; ++b)
+    std::vector<int> fin0(nb, 0);
+    int n_live = 0;
+    if (row_active) {
+        for (int b = 0; b < nb; ++b) { fin0[b] = row_active[b] ? 0 : 2; n_live += row_active[b] ? 1 : 0; }
+        if (n_live == 0) return fail(c, CW_ERR_INVALID, "decode_rows: no active row");
+        if (n_live < nb) {                     // masked rows keep the ids of the decode before
+            HIPCHK(c, hipStreamSynchronize(c->st));
+            HIPCHK(c, hipMemcpy(ids.data(), c->d_ids, ids.size() * 4, hipMemcpyDeviceToHost));
+        }
+    }
+    for (int b = 0; b < nb; ++b) {
+        if (fin0[b]) continue;
+        for (int t = 0; t < TGT; ++t) ids[(size_t)b * TGT + t] = c->gen.pad_token_id;
         for (int t = 0; t < n_prompt; ++t) {
             int tok = prompt[(size_t)b * n_prompt + t];
             if (tok < 0 || tok >= V) return fail(c, CW_ERR_INVALID, "prompt token %d out of range", tok);
             ids[(size_t)b * TGT + t] = tok;
         }
+    }
     HIPCHK(c, hipMemcpyAsync(c->d_ids, ids.data(), ids.size() * 4, hipMemcpyHostToDevice, c->st));
     if (forced) HIPCHK(c, hipMemcpyAsync(c->d_forced, forced, (size_t)nb * TGT * 4, hipMemcpyHostToDevice, c->st));
-    HIPCHK(c, hipMemsetAsync(c->d_finished, 0, nb * 4, c->st));
-    HIPCHK(c, hipMemsetAsync(c->d_lp_sum, 0, nb * 4, c->st));
-    HIPCHK(c, hipMemsetAsync(c->d_lp_cnt, 0, nb * 4, c->st));
+    if (!row_active || n_live == nb) {
+        HIPCHK(c, hipMemsetAsync(c->d_finished, 0, nb * 4, c->st));
+        HIPCHK(c, hipMemsetAsync(c->d_lp_sum, 0, nb * 4, c->st));
+        HIPCHK(c, hipMemsetAsync(c->d_lp_cnt, 0, nb * 4, c->st));
+    } else {
+        HIPCHK(c, hipMemcpyAsync(c->d_finished, fin0.data(), nb * 4, hipMemcpyHostToDevice, c->st));
+        for (int b = 0; b < nb; ++b)
+            if (!fin0[b]) {
+                HIPCHK(c, hipMemsetAsync(c->d_lp_sum + b, 0, 4, c->st));
+                HIPCHK(c, hipMemsetAsync(c->d_lp_cnt + b, 0, 4, c->st));
+            }
+    }
     HIPCHK(c, hipMemsetAsync(c->d_last_ts, 0xff, nb * 4, c->st));
     HIPCHK(c, hipMemsetAsync(c->d_argmax, 0xff, (size_t)nb * TGT * 4, c->st));
     const int cfg[4] = {n_prompt, min_new_tokens, max_length, forced ? 1 : 0};
@@ -1795,6 +1831,7 @@ static int decode_once(cw_ctx* c, int32_t nb, const int32_t* prompt, int32_t n_p
         const int tb = c->gen.no_timestamps_token_id + 1;
         for (int b = 0; b < nb; ++b) {                                  // sample_kernel's per-row state after it wrote ids[P]
             fin[b] = 0; lts[b] = -1;
+            if (fin0[b]) { fin[b] = 2; continue; }
             for (int k = n_prompt; k <= P; ++k) {
                 const int tok = ids[(size_t)b * TGT + k];
                 if (!fin[b] && tok >= tb) lts[b] = tok;
@@ -1820,7 +1857,7 @@ static int decode_once(cw_ctx* c, int32_t nb, const int32_t* prompt, int32_t n_p
         int len = t;
         for (int k = n_prompt; k < t; ++k)
             if (ids[(size_t)b * TGT + k] == c->gen.eos_token_id) { len = k + 1; break; }
-        lengths[b] = len;
+        lengths[b] = fin0[b] ? 0 : len;            // a masked row did not run
     }
     if (argmax_out) HIPCHK(c, hipMemcpy(argmax_out, c->d_argmax, (size_t)nb * TGT * 4, hipMemcpyDeviceToHost));
     c->last_L = t - 1;   // attention rows retained: one per decoder input position
@@ -1841,6 +1878,26 @@ int32_t cw_set_thresholds(cw_ctx* c, float logprob_threshold, float no_speech_th
     const bool want = !isnan(logprob_threshold);
     if (want != c->score_tokens) { c->score_tokens = want; drop_step_graphs(c); }
     return CW_OK;
+}
+
+// ---- stochastic half: seeded Gumbel-max sampling in the sampler kernels (include/crisperwhisper.h) ----------------------
+// The kernels read temperature, seed and stream ids from d_samp, so the captured step graphs stay as they are.
+static int write_sampling(cw_ctx* c, float temperature, uint64_t seed, const uint64_t* row_streams, int nb, const char* who) {
+    if (!(temperature >= 0.f) || std::isinf(temperature)) return fail(c, CW_ERR_INVALID, "%s: temperature must be finite and >= 0", who);
+    std::vector<unsigned int> w(c->samp_host.size(), 0u);
+    if (temperature > 0.f && row_streams) {
+        if (nb < 1 || nb > c->Bm) return fail(c, CW_ERR_INVALID, "%s: nb=%d outside 1 .. %d", who, nb, c->Bm);
+        memcpy(&w[0], &temperature, 4);
+        w[1] = (unsigned int)(seed & 0xffffffffu); w[2] = (unsigned int)(seed >> 32);
+        for (int b = 0; b < nb; ++b) { w[4 + 2 * b] = (unsigned int)(row_streams[b] & 0xffffffffu); w[5 + 2 * b] = (unsigned int)(row_streams[b] >> 32); }
+    }
+    HIPCHK(c, hipStreamSynchronize(c->st));
+    HIPCHK(c, hipMemcpy(c->d_samp, w.data(), w.size() * 4, hipMemcpyHostToDevice));
+    c->samp_host = w;
+    return CW_OK;
+}
+int32_t cw_set_sampling(cw_ctx* c, float temperature, uint64_t seed, const uint64_t* row_streams, int32_t nb) {
+    return write_sampling(c, temperature, seed, row_streams, nb, "set_sampling");
 }
 
 // average log_softmax(processed scores)[token] over the generated tokens of every row of the last cw_decode, the eos
@@ -3417,7 +3474,30 @@ int32_t cw_test_beam_state(cw_ctx* c, int32_t rows, int32_t* ids, int32_t* anc, 
 // One call of the fused logits-processor + argmax kernel (sample_kernel) on caller-supplied rows: logits [nb][V],
 // ids [nb][t] = prompt + generated so far (the kernel's grammar state is rebuilt from it), choice_out [nb] = the
 // token the kernel picks for index t.  Differential test against TF/generation/logits_process.py:203-260, 1816-2047.
+static int test_sample(cw_ctx* c, int32_t nb, const float* logits, const int32_t* ids, int32_t t, int32_t n_prompt,
+                       int32_t min_new_tokens, int32_t max_length, int32_t* choice_out);
 int32_t cw_test_sample(cw_ctx* c, int32_t nb, const float* logits, const int32_t* ids, int32_t t, int32_t n_prompt,
+                       int32_t min_new_tokens, int32_t max_length, int32_t* choice_out) {
+    return test_sample(c, nb, logits, ids, t, n_prompt, min_new_tokens, max_length, choice_out);
+}
+// The same two launches under a sampling setting of their own; the context's setting (cw_set_sampling) is put back afterwards.
+int32_t cw_test_sample_seeded(cw_ctx* c, int32_t nb, const float* logits, const int32_t* ids, int32_t t, int32_t n_prompt,
+                              int32_t min_new_tokens, int32_t max_length, float temperature, uint64_t seed,
+                              const uint64_t* row_streams, int32_t* choice_out) {
+    if (!logits || !ids || !choice_out) return fail(c, CW_ERR_INVALID, "test_sample_seeded: null argument");
+    if (nb < 1 || nb > c->Bm || nb > 64) return fail(c, CW_ERR_INVALID, "test_sample_seeded: nb=%d outside 1 .. %d", nb, c->Bm < 64 ? c->Bm : 64);
+    if (max_length <= n_prompt || max_length > c->d.max_target_positions || min_new_tokens < 0)
+        return fail(c, CW_ERR_INVALID, "test_sample_seeded: max_length=%d / min_new_tokens=%d out of range", max_length, min_new_tokens);
+    if (temperature > 0.f && !row_streams) return fail(c, CW_ERR_INVALID, "test_sample_seeded: a positive temperature needs row_streams");
+    const std::vector<unsigned int> keep = c->samp_host;
+    CWCHK(c, write_sampling(c, temperature, seed, row_streams, nb, "test_sample_seeded"));
+    const int r = test_sample(c, nb, logits, ids, t, n_prompt, min_new_tokens, max_length, choice_out);
+    HIPCHK(c, hipStreamSynchronize(c->st));
+    HIPCHK(c, hipMemcpy(c->d_samp, keep.data(), keep.size() * 4, hipMemcpyHostToDevice));
+    c->samp_host = keep;
+    return r;
+}
+static int test_sample(cw_ctx* c, int32_t nb, const float* logits, const int32_t* ids, int32_t t, int32_t n_prompt,
                        int32_t min_new_tokens, int32_t max_length, int32_t* choice_out) {
     const int V = c->d.vocab_size, TGT = c->d.max_target_positions;
     if (!c->gen_set) return fail(c, CW_ERR_STATE, "cw_set_generation not called");

@@ -44,6 +44,11 @@ struct SampleParams {
     float* lp_sum;             // [B]
     int* lp_cnt;               // [B]
     unsigned int* epoch;       // optional: device counter of decoder forwards, bumped by block 0 (declayer.hip tags its granules with it)
+    // optional (null: greedy): seeded Gumbel-max sampling (include/crisperwhisper.h: cw_set_sampling).  Device words, read by the
+    // kernels so that a captured step graph stays valid across calls: [0] temperature (f32 bits; 0 = greedy, today's path),
+    // [1] seed_lo, [2] seed_hi, [3] unused, [4 + 2b] / [5 + 2b] stream_lo / stream_hi of row b
+    const unsigned int* samp;
+    void* pert;                // [B][SAMPLE_NS] 16-byte records: best perturbed text / timestamp token of every slice (samp only)
 };
 // beam search (elementwise.hip): per row the n_cand best processed log-probabilities of the next token
 // (log_softmax of the raw logits, then the same processors as the greedy path) ...

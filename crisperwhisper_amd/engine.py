@@ -50,6 +50,9 @@ class ModelSpec:
     forced_decoder_ids: Optional[Sequence[Sequence[Optional[int]]]] = None
     language: Optional[str] = None
     task: Optional[str] = None
+    # top_k / top_p / min_p / typical_p / repetition_penalty of the checkpoint's generation_config where they are set to
+    # something that acts: a sampling call is refused then (temperature is the only warper the sampler implements)
+    sampling_warpers: Dict[str, float] = dataclasses.field(default_factory=dict)
 
     @property
     def timestamp_begin(self) -> int:
@@ -203,7 +206,11 @@ class Engine:
         return out
 
     def decode(self, prompt: np.ndarray, max_length: int, min_new_tokens: int = 0,
-               forced: Optional[np.ndarray] = None, want_argmax: bool = False):
+               forced: Optional[np.ndarray] = None, want_argmax: bool = False, row_active=None):
+        """``row_active`` (cw_decode_rows): rows with 0 start finished; their ids and log-probability sums on the device stay
+        what the previous decode left, their ``lens`` entry is 0 and their ``seqs`` row is what the device held."""
+        if row_active is not None:
+            return self._decode_rows(prompt, max_length, min_new_tokens, forced, want_argmax, row_active)
         prompt = _i32(prompt)
         nb, n_prompt = prompt.shape
         tgt = self.spec.max_target_positions
@@ -217,6 +224,35 @@ class Engine:
         self._chk(self.lib.cw_decode(self.ctx, nb, _ptr(prompt), n_prompt, int(max_length), int(min_new_tokens),
                                      _ptr(f), _ptr(seqs), _ptr(lens), _ptr(amax)))
         return seqs, lens, amax
+
+    def _decode_rows(self, prompt, max_length, min_new_tokens, forced, want_argmax, row_active):
+        prompt = _i32(prompt)
+        nb, n_prompt = prompt.shape
+        act = _i32(row_active)
+        if act.shape != (nb,):
+            raise ValueError(f"row_active must hold one entry per row ({nb}), got shape {act.shape}")
+        tgt = self.spec.max_target_positions
+        seqs = np.zeros((nb, tgt), dtype=np.int32)
+        lens = np.zeros(nb, dtype=np.int32)
+        amax = np.zeros((nb, tgt), dtype=np.int32) if want_argmax else None
+        f = None
+        if forced is not None:
+            f = np.full((nb, tgt), -1, dtype=np.int32)
+            f[:, :forced.shape[1]] = forced
+        self._chk(self.lib.cw_decode_rows(self.ctx, nb, _ptr(prompt), n_prompt, int(max_length), int(min_new_tokens),
+                                          _ptr(f), _ptr(act), _ptr(seqs), _ptr(lens), _ptr(amax)))
+        return seqs, lens, amax
+
+    def set_sampling(self, temperature: float = 0.0, seed: int = 0, row_streams=None):
+        """Seeded Gumbel-max sampling for the coming ``decode`` calls (``cw_set_sampling``): ``row_streams`` holds one 64-bit
+        stream id per row.  Temperature 0 or no streams: greedy."""
+        if row_streams is None or not float(temperature) > 0.0:
+            if not float(temperature) >= 0.0:
+                raise ValueError(f"temperature must be finite and >= 0, not {temperature!r}")
+            self._chk(self.lib.cw_set_sampling(self.ctx, 0.0, 0, None, 0))
+            return
+        rs = np.ascontiguousarray(row_streams, dtype=np.uint64)
+        self._chk(self.lib.cw_set_sampling(self.ctx, float(temperature), int(seed) & (2 ** 64 - 1), _ptr(rs), int(rs.shape[0])))
 
     def set_thresholds(self, logprob_threshold: Optional[float] = None, no_speech_threshold: Optional[float] = None):
         """Deterministic half of generate_with_fallback (``cw_set_thresholds``); None = unset."""
@@ -605,6 +641,23 @@ class Engine:
         out = np.zeros(nb, np.int32)
         self._chk(self.lib.cw_test_sample(self.ctx, nb, _ptr(lg), _ptr(ids), t, int(n_prompt), int(min_new_tokens),
                                           int(max_length or self.spec.max_target_positions), _ptr(out)))
+        return out
+
+    def test_sample_seeded(self, logits: np.ndarray, ids: np.ndarray, n_prompt: int, temperature: float, seed: int,
+                           row_streams, min_new_tokens: int = 0, max_length: Optional[int] = None) -> np.ndarray:
+        """The same two launches under a sampling setting of their own (cw_test_sample_seeded)."""
+        lg = np.ascontiguousarray(logits, np.float32)
+        ids = _i32(ids)
+        nb, t = ids.shape
+        if lg.shape != (nb, self.spec.vocab_size):
+            raise ValueError(f"logits must be [{nb}][{self.spec.vocab_size}], got {lg.shape}")
+        rs = None if row_streams is None else np.ascontiguousarray(row_streams, dtype=np.uint64)
+        if rs is not None and rs.shape != (nb,):
+            raise ValueError(f"row_streams must hold one id per row ({nb}), got shape {rs.shape}")
+        out = np.zeros(nb, np.int32)
+        self._chk(self.lib.cw_test_sample_seeded(self.ctx, nb, _ptr(lg), _ptr(ids), t, int(n_prompt), int(min_new_tokens),
+                                                 int(max_length or self.spec.max_target_positions), float(temperature),
+                                                 int(seed) & (2 ** 64 - 1), _ptr(rs), _ptr(out)))
         return out
 
     # ------------------------------------------------------------------ measurement

@@ -11,7 +11,9 @@ the device through ``Engine``; this module only decides *what* to run next from 
 from __future__ import annotations
 
 import dataclasses
-from typing import Callable, List, Optional, Sequence
+import math
+import zlib
+from typing import Callable, List, Optional, Sequence, Tuple
 
 import numpy as np
 
@@ -365,10 +367,69 @@ def _beam_search_tail(engine, seq_out, bi_out, scores, n_prompt):
     return seq_out, bi_out, unrolled.shape[1], np.asarray(scores, dtype=np.float32)
 
 
+MAX_FALLBACK_TEMPERATURES = 16          # the temperature index takes the low 4 bits of a row's stream id
+
+
+def normalise_temperatures(temperature) -> Tuple[float, ...]:
+    """``temperature`` of ``generate`` as a tuple of finite floats >= 0 (None: (0.0,)); at most 16 entries."""
+    if temperature is None:
+        return (0.0,)
+    temps = tuple(temperature) if isinstance(temperature, (tuple, list)) else (temperature,)
+    if len(temps) == 0:
+        raise ValueError("temperature: an empty tuple decodes nothing")
+    if len(temps) > MAX_FALLBACK_TEMPERATURES:
+        raise ValueError(f"temperature: at most {MAX_FALLBACK_TEMPERATURES} fallback temperatures are supported (the temperature "
+                         f"index is 4 bits of the sampler's stream id), got {len(temps)}")
+    out = []
+    for t in temps:
+        if isinstance(t, (bool, np.bool_)) or not isinstance(t, (int, float, np.integer, np.floating)):
+            raise ValueError(f"temperature must be a number or a tuple of numbers, got {t!r}")
+        t = float(t)
+        if not (t >= 0.0) or math.isinf(t):
+            raise ValueError(f"temperature must be finite and >= 0, got {t!r}")
+        out.append(t)
+    return tuple(out)
+
+
+def compression_ratio(tokens, vocab_size: int) -> float:
+    """``_retrieve_compression_ratio`` (generation_whisper.py:1949): raw bytes over zlib-compressed bytes of the tokens written
+    as fixed-width little-endian integers."""
+    length = int(math.log2(vocab_size) / 8) + 1
+    token_bytes = b"".join(int(t).to_bytes(length, "little") for t in np.asarray(tokens).tolist())
+    return len(token_bytes) / len(zlib.compress(token_bytes))
+
+
+def need_fallback(tokens, vocab_size, avg_logprob, no_speech_prob, compression_ratio_threshold, logprob_threshold,
+                  no_speech_threshold):
+    """``_need_fallback`` (generation_whisper.py:1243-1287) for one window: ``tokens`` are the generated tokens with the padding
+    stripped and the eos kept.  Returns (needs_fallback, should_skip, compression ratio or None)."""
+    needs, skip, cr = False, False, None
+    if compression_ratio_threshold is not None:
+        cr = compression_ratio(tokens, vocab_size)
+        if cr > compression_ratio_threshold:
+            needs = True
+    if logprob_threshold is not None and float(avg_logprob) < logprob_threshold:
+        needs = True
+    if no_speech_threshold is not None:
+        if float(avg_logprob) < logprob_threshold and float(no_speech_prob) > no_speech_threshold:
+            needs, skip = False, True
+    return needs, skip, cr
+
+
+def stream_id(item_id: int, seek_frame: int, temperature_index: int) -> int:
+    """The sampler's 64-bit stream of a window: stream_lo = the caller's item id (the pipeline passes the global window index),
+    stream_hi = (seek_frame << 4) | temperature_index."""
+    if not 0 <= temperature_index < MAX_FALLBACK_TEMPERATURES:
+        raise ValueError(f"temperature index {temperature_index} outside 0 .. {MAX_FALLBACK_TEMPERATURES - 1}")
+    hi = ((int(seek_frame) << 4) | int(temperature_index)) & 0xFFFFFFFF
+    return (hi << 32) | (int(item_id) & 0xFFFFFFFF)
+
+
 def generate(engine: Engine, n_items: int, num_frames, *, language: Optional[str], task: Optional[str] = None,
              max_new_tokens: Optional[int] = None, min_new_tokens: Optional[int] = None,
              num_beams: Optional[int] = 1, stats: Optional[dict] = None, native: Optional[bool] = None,
-             logprob_threshold: Optional[float] = None, no_speech_threshold: Optional[float] = None, prompt_ids=None):
+             logprob_threshold: Optional[float] = None, no_speech_threshold: Optional[float] = None, prompt_ids=None,
+             temperature=None, compression_ratio_threshold: Optional[float] = None, sampling_seed: int = 0, item_ids=None):
     """Transcribe the ``n_items`` 30 s feature windows resident in the engine (items 0..n-1).
 
     Returns {"sequences": [B, Lmax] int64 (pad-right), "token_timestamps": list of float32 arrays,
@@ -381,7 +442,15 @@ def generate(engine: Engine, n_items: int, num_frames, *, language: Optional[str
     ``logprob_threshold`` / ``no_speech_threshold``: the deterministic (temperature 0) half of HF's
     ``generate_with_fallback`` (generation_whisper.py:970-1116, ``_need_fallback`` :1243-1287): a window whose average token
     log-probability is below the first AND whose no-speech probability is above the second is skipped -- seek moves on by the
-    whole window, no segment (:879-881).  Re-decoding at higher temperatures is not implemented (pipeline.py refuses it).
+    whole window, no segment (:879-881).
+
+    ``temperature`` (a number or a tuple of up to 16) together with ``compression_ratio_threshold`` / ``logprob_threshold`` is the
+    stochastic half: the windows that fail a threshold at one temperature are decoded again at the next (only those rows are
+    live; the encoder does not run again), the last temperature's result is kept unconditionally.  Positive temperatures sample
+    with the engine's seeded Gumbel-max sampler (``cw_set_sampling``): key ``sampling_seed``, stream ``stream_id(item_ids[i],
+    seek, temperature index)`` (``item_ids`` defaults to 0 .. n_items-1), so a window's tokens do not depend on the batch it is
+    decoded in.  Without a threshold only the first temperature is used, as in transformers.  Greedy rows only; it runs on the
+    host seek loop.  ``stats["fallback"]`` receives one record per (window, temperature) decode that was judged.
 
     ``prompt_ids`` (``processor.get_prompt_ids(text)``): every window of every seek pass decodes from
     ``prompt_ids ++ init_tokens`` (generation_whisper.py:1909-1913, condition_on_prev_tokens False); language detection still
@@ -406,6 +475,23 @@ def generate(engine: Engine, n_items: int, num_frames, *, language: Optional[str
     if num_beams * n_items > engine.max_batch:
         raise ValueError(f"beam search decodes items x beams = {num_beams * n_items} rows; the engine was created with "
                          f"max_batch = {engine.max_batch}")
+    temps = normalise_temperatures(temperature)
+    if compression_ratio_threshold is None and logprob_threshold is None and no_speech_threshold is None:
+        temps = temps[:1]                               # no threshold, no fallback: the first temperature is kept (:1100-1104)
+    fb = None
+    if len(temps) > 1 or temps[0] > 0.0:
+        if num_beams > 1:
+            raise ValueError("a positive temperature samples, and sampling decodes greedy rows only (transformers forces "
+                             "num_beams = 1 there, generation_whisper.py:1004-1005): pass num_beams=1")
+        if prefix is not None and len(temps) > 1:
+            raise ValueError("temperature fallback together with prompt_ids is not implemented on the native path")
+        if not hasattr(engine, "set_sampling"):
+            raise ValueError("this engine does not implement sampling (cw_set_sampling)")
+        ids_ = list(range(n_items)) if item_ids is None else [int(i) for i in item_ids]
+        if len(ids_) != n_items:
+            raise ValueError(f"{len(ids_)} item_ids for {n_items} items")
+        fb = {"temps": temps, "seed": int(sampling_seed), "item_ids": ids_, "cr_thr": compression_ratio_threshold}
+        native = False                                  # the fallback loop runs here, like beam search
     if hasattr(engine, "set_thresholds"):
         engine.set_thresholds(logprob_threshold, no_speech_threshold)
     elif logprob_threshold is not None:
@@ -462,7 +548,7 @@ def generate(engine: Engine, n_items: int, num_frames, *, language: Optional[str
     try:
         _seek_loop(engine, spec, n_items, num_frames, init, n_prompt, max_new_tokens, min_new_tokens, num_beams, prefix,
                    prompted_len if prefix is not None else None, skip_on, logprob_threshold, no_speech_threshold, pre_encoded,
-                   seek, max_frames, segments, tb, stats)
+                   seek, max_frames, segments, tb, stats, fb)
     finally:
         if prefix is not None and set_prefix is not None:
             set_prefix(0)
@@ -476,8 +562,8 @@ def generate(engine: Engine, n_items: int, num_frames, *, language: Optional[str
 
 
 def _seek_loop(engine, spec, n_items, num_frames, init, n_prompt, max_new_tokens, min_new_tokens, num_beams, prefix, prompted_len,
-               skip_on, logprob_threshold, no_speech_threshold, pre_encoded, seek, max_frames, segments, tb, stats):
-    """The seek loop of the host path of ``generate`` (fills ``segments`` in place)."""
+               skip_on, logprob_threshold, no_speech_threshold, pre_encoded, seek, max_frames, segments, tb, stats, fb=None):
+    """The seek loop of the host path of ``generate`` (fills ``segments`` in place).  ``fb``: temperature fallback settings."""
     n_calls = 0
     while True:
         active = [i for i in range(n_items) if seek[i] < max_frames[i]]
@@ -491,6 +577,21 @@ def _seek_loop(engine, spec, n_items, num_frames, init, n_prompt, max_new_tokens
         else:
             max_length = (n_prompt + max_new_tokens) if max_new_tokens is not None else min(spec.max_length, spec.max_target_positions)
         nsp = engine.no_speech_probs(len(active), spec.decoder_start_token_id) if skip_on else None
+        if fb is not None:
+            kept = _decode_with_fallback(engine, spec, fb, active, init[active], n_prompt, max_length, min_new_tokens or 0,
+                                         (num_frames - seek)[active], seek[active], nsp, logprob_threshold, no_speech_threshold,
+                                         stats)
+            n_calls += 1
+            for row, i in enumerate(active):
+                s, ts_row, skip = kept[row]
+                if skip:
+                    seek[i] += seek_num[i]                        # should_skip (:879-881)
+                    continue
+                segs, advance = split_segments(s, ts_row, float(seek[i]) * TIME_PRECISION / INPUT_STRIDE, tb,
+                                               int(seek_num[i]), n_prompt)
+                seek[i] += advance
+                segments[i].extend(segs)
+            continue
         if num_beams > 1:
             bs, _, L, alp = beam_search(engine, init[active], max_length, min_new_tokens or 0, num_beams)
             total = bs.shape[1]
@@ -522,6 +623,67 @@ def _seek_loop(engine, spec, n_items, num_frames, init, n_prompt, max_new_tokens
             segments[i].extend(segs)
     if stats is not None:
         stats["generate_calls"] = stats.get("generate_calls", 0) + n_calls
+
+
+def _decode_with_fallback(engine, spec, fb, active, init_rows, n_prompt, max_length, min_new_tokens, frames, seeks, nsp,
+                          logprob_threshold, no_speech_threshold, stats):
+    """``generate_with_fallback`` (generation_whisper.py:970-1116) over the encoded windows ``active`` (engine rows 0 .. nb-1).
+
+    One decode per temperature; from the second on only the rows still in the fallback set are live (``row_active``), the others
+    idle through the step.  A row is settled by the first decode that needs no fallback, by a no-speech skip, or by the last
+    temperature; its token timestamps are taken right after that decode (a later decode overwrites the idle rows' attention
+    rows).  Decisions are indexed by the original row throughout -- transformers indexes ``needs_fallback[i]`` /
+    ``should_skip[i]`` by the row of the shrunken sub-batch (:1074 against :1088) and reads them back by the original one.
+    Returns per row (tokens without eos, token timestamps of the whole row, skip)."""
+    nb = len(active)
+    temps = fb["temps"]
+    kept = [None] * nb
+    pending = list(range(nb))
+    try:
+        for ti, temp in enumerate(temps):
+            if temp > 0.0:
+                streams = [stream_id(fb["item_ids"][active[r]], int(seeks[r]), ti) for r in range(nb)]
+                engine.set_sampling(temp, fb["seed"], streams)
+            else:
+                engine.set_sampling(0.0)
+            mask = None
+            if len(pending) < nb:
+                mask = np.zeros(nb, np.int32)
+                mask[pending] = 1
+            seqs, lens, _ = engine.decode(init_rows, max_length, min_new_tokens, row_active=mask)
+            total = int(lens.max())
+            alp = engine.avg_logprobs(nb) if logprob_threshold is not None else None
+            token_ts = engine.token_timestamps(nb, total - 1, n_prompt, frames)
+            again = []
+            for r in pending:
+                s = seqs[r, n_prompt:total].astype(np.int64)
+                if s[-1] == spec.pad_token_id:                    # strip right padding, keep one eos
+                    npad = int((s == spec.pad_token_id).sum())
+                    if spec.pad_token_id == spec.eos_token_id:
+                        npad -= 1
+                    if npad:
+                        s = s[:-npad]
+                needs, skip, cr = need_fallback(s, spec.vocab_size, None if alp is None else alp[r], None if nsp is None else nsp[r],
+                                                fb["cr_thr"], logprob_threshold, no_speech_threshold)
+                last = ti == len(temps) - 1
+                if stats is not None:
+                    stats.setdefault("fallback", []).append({
+                        "item": fb["item_ids"][active[r]], "seek": int(seeks[r]), "temperature_index": ti, "temperature": temp,
+                        "compression_ratio": cr, "avg_logprob": None if alp is None else float(alp[r]),
+                        "no_speech_prob": None if nsp is None else float(nsp[r]),
+                        "decision": "skip" if skip else ("fallback" if needs and not last else "keep"),
+                        "needs_fallback": bool(needs), "tokens": s.copy()})
+                if s[-1] == spec.eos_token_id:
+                    s = s[:-1]
+                kept[r] = (s, np.array(token_ts[r], copy=True), skip)
+                if needs and not last:
+                    again.append(r)
+            pending = again
+            if not pending:
+                break
+    finally:
+        engine.set_sampling(0.0)
+    return kept
 
 
 def check_transcript_ids(spec, ids) -> np.ndarray:

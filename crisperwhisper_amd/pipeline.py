@@ -32,6 +32,20 @@ def _warn_once(key: str, msg: str):
         logger.warning(msg)
 
 
+_WARPER_NEUTRAL = {"top_k": 0, "top_p": 1.0, "min_p": 0.0, "typical_p": 1.0, "repetition_penalty": 1.0}
+
+
+def _sampling_warpers(get) -> Dict[str, float]:
+    """The generation_config entries besides temperature that would change what a sampling call draws from (None and the
+    value that leaves the scores alone count as unset; transformers 5.15.0 defaults all of them to None)."""
+    out = {}
+    for k, neutral in _WARPER_NEUTRAL.items():
+        v = get(k)
+        if v is not None and float(v) != float(neutral):
+            out[k] = float(v)
+    return out
+
+
 class ModelBundle:
     """Geometry + generation settings + weights (HF state_dict names -> float32 numpy)."""
 
@@ -63,7 +77,8 @@ class ModelBundle:
             max_length=gc.max_length or cfg.max_target_positions,
             forced_decoder_ids=(getattr(gc, "forced_decoder_ids", None) if getattr(gc, "forced_decoder_ids", None) is not None
                                 else getattr(cfg, "forced_decoder_ids", None)),
-            language=getattr(gc, "language", None), task=getattr(gc, "task", None))
+            language=getattr(gc, "language", None), task=getattr(gc, "task", None),
+            sampling_warpers=_sampling_warpers(lambda k: getattr(gc, k, None)))
         weights = {k: v.detach().float().cpu().numpy() for k, v in model.state_dict().items() if k != "proj_out.weight"}
         return cls(spec, weights)
 
@@ -102,7 +117,7 @@ class ModelBundle:
             lang_to_id=dict(gc.get("lang_to_id") or {}), task_to_id=dict(gc.get("task_to_id") or {}),
             max_length=gc.get("max_length") or cfg.get("max_target_positions", 448),
             forced_decoder_ids=gc.get("forced_decoder_ids") if gc.get("forced_decoder_ids") is not None else cfg.get("forced_decoder_ids"),
-            language=gc.get("language"), task=gc.get("task"))
+            language=gc.get("language"), task=gc.get("task"), sampling_warpers=_sampling_warpers(gc.get))
         return cls(spec, _SafetensorsWeights(path))
 
 
@@ -213,31 +228,43 @@ _GENERATE_KWARGS = ("language", "task", "max_new_tokens", "min_new_tokens", "num
                     "logprob_threshold", "no_speech_threshold", "compression_ratio_threshold", "return_timestamps")
 
 
-def _check_generate_kwargs(gk: Dict[str, Any], default_num_beams: Optional[int] = None, spec=None) -> None:
+def _check_generate_kwargs(gk: Dict[str, Any], default_num_beams: Optional[int] = None, spec=None,
+                           sampling_seed: Optional[int] = None) -> None:
     """``default_num_beams``: the width a call without ``num_beams`` decodes with (the pipeline default): the refusals that
     depend on the beam width are then raised here, before any audio is loaded.  ``spec`` (the model's ModelSpec): the
-    ``prompt_ids`` checks that need the vocabulary and the length limit run here too."""
+    ``prompt_ids`` checks that need the vocabulary and the length limit run here too.  ``sampling_seed``: the seed a call that
+    samples would draw with (constructor or call argument of the pipeline); None = none was named, and such a call is refused."""
     unknown = sorted(k for k in gk if k not in _GENERATE_KWARGS)
     if unknown:
         raise ValueError(f"generate_kwargs {unknown} are not implemented on the native path (implemented: "
                          f"{', '.join(_GENERATE_KWARGS)}); they would be silently ignored otherwise")
     thresholds = [k for k in ("compression_ratio_threshold", "logprob_threshold", "no_speech_threshold") if gk.get(k) is not None]
     if gk.get("do_sample"):
-        raise ValueError("generate_kwargs['do_sample'] is not supported on the native path (deterministic greedy / beam search "
-                         "only: stochastic decoding cannot be made bit-comparable with torch's generator)")
-    temp = gk.get("temperature")
-    if isinstance(temp, (tuple, list)):
-        # temperature fallback (generation_whisper.py:970-1116) only fires when a threshold is set
-        if thresholds or len(temp) == 0:
-            raise ValueError("temperature fallback with sampling is not implemented on the native path "
-                             "(stochastic decoding cannot be made bit-comparable with torch's generator)")
-        temp = temp[0]
+        raise ValueError("generate_kwargs['do_sample'] is not supported on the native path: Whisper's generate derives it from the "
+                         "temperature (do_sample = temperature > 0, generation_whisper.py:1002); pass temperature=... instead")
     # do_sample = temperature > 0.0 (generation_whisper.py:1002): any positive temperature, 1.0 included, makes transformers
-    # SAMPLE (with num_beams forced to 1) -- only 0 is the deterministic decoding this path implements
-    if temp is not None and not (isinstance(temp, (int, float)) and not isinstance(temp, bool) and float(temp) == 0.0):
-        raise ValueError(f"generate_kwargs['temperature']={gk['temperature']!r} is not supported on the native path: transformers "
-                         "samples at every temperature > 0 (stochastic decoding cannot be made bit-comparable with torch's "
-                         "generator); pass temperature=0.0 or leave it out")
+    # sample, with num_beams forced to 1 (:1004-1005).  Here such a call runs the seeded sampler of the engine (greedy rows only);
+    # without a threshold the fallback never fires and only the first temperature of a tuple is used (:1100-1104)
+    temps = generation.normalise_temperatures(gk["temperature"]) if gk.get("temperature") is not None else (0.0,)
+    if not thresholds:
+        temps = temps[:1]
+    samples = any(t > 0.0 for t in temps)
+    beams = gk.get("num_beams") if gk.get("num_beams") is not None else default_num_beams
+    if samples and sampling_seed is None:
+        # there is no global generator here: what is drawn is a function of the seed, so a call that samples names one.  A call
+        # that only carries transformers' own arguments cannot, and is refused as before
+        raise ValueError(f"generate_kwargs['temperature']={gk['temperature']!r} samples (transformers samples at every temperature "
+                         "> 0, and re-decodes at the later temperatures of a tuple once a threshold is set), and the native "
+                         "sampler draws from a seeded stream, not from torch's generator: name the seed, "
+                         "pipeline(..., sampling_seed=0) or pipe(audio, sampling_seed=0, generate_kwargs=...)")
+    if samples and beams not in (None, 1):
+        raise ValueError(f"generate_kwargs['temperature']={gk['temperature']!r} samples, and sampling decodes greedy rows only "
+                         f"(transformers forces num_beams = 1 there); this call decodes with {beams} beams" +
+                         ("" if gk.get("num_beams") is not None else " (the pipeline default)") +
+                         ": pass generate_kwargs={'num_beams': 1, ...}")
+    if spec is not None and getattr(spec, "sampling_warpers", None) and samples:
+        raise ValueError(f"the checkpoint's generation_config sets {sorted(spec.sampling_warpers)}: temperature is the only "
+                         "sampling warper the native sampler implements")
     if gk.get("num_return_sequences") not in (None, 1):
         raise ValueError("generate_kwargs['num_return_sequences'] > 1 is not supported on the native path")
     if gk.get("assistant_model") is not None:
@@ -247,6 +274,9 @@ def _check_generate_kwargs(gk: Dict[str, Any], default_num_beams: Optional[int] 
             raise ValueError("generate_kwargs['prompt_ids'] together with logprob_threshold / no_speech_threshold is not "
                              "supported on the native path: the no-speech position moves with the prompt and that combination "
                              "is not reproduced")
+        if len(temps) > 1:
+            raise ValueError("generate_kwargs['prompt_ids'] together with temperature fallback (a temperature tuple with "
+                             "compression_ratio_threshold) is not supported on the native path")
         if spec is None:                     # ids and length are only checkable against a model's vocabulary and limits
             raise ValueError("generate_kwargs['prompt_ids'] can only be checked against a model: pass its ModelSpec")
         pids = generation.check_prompt_ids(spec, gk["prompt_ids"])
@@ -256,7 +286,6 @@ def _check_generate_kwargs(gk: Dict[str, Any], default_num_beams: Optional[int] 
         raise ValueError("generate_kwargs['return_timestamps'] must be left to the pipeline argument of the same name")
     if gk.get("no_speech_threshold") is not None and gk.get("logprob_threshold") is None:
         raise ValueError("no_speech_threshold needs logprob_threshold as well (generation_whisper.py:1275-1285 compares both)")
-    beams = gk.get("num_beams") if gk.get("num_beams") is not None else default_num_beams
     if thresholds and beams not in (None, 1) and any(k in thresholds for k in ("logprob_threshold", "no_speech_threshold")):
         raise ValueError(f"logprob_threshold / no_speech_threshold are implemented for greedy decoding only and this call decodes "
                          f"with {beams} beams" + ("" if gk.get("num_beams") is not None else " (the pipeline default)") +
@@ -265,9 +294,21 @@ def _check_generate_kwargs(gk: Dict[str, Any], default_num_beams: Optional[int] 
     if gk.get("logprob_threshold") is not None and gk.get("temperature") is None:
         raise ValueError("logprob_threshold needs an explicit temperature (pass temperature=0.0): transformers itself fails with "
                          "a TypeError in _retrieve_avg_logprobs otherwise (generation_whisper.py:1959)")
+    if len(temps) > 1 and beams not in (None, 1):
+        raise ValueError(f"temperature fallback is implemented for greedy decoding only and this call decodes with {beams} beams" +
+                         ("" if gk.get("num_beams") is not None else " (the pipeline default)") +
+                         ": pass generate_kwargs={'num_beams': 1, ...}")
     # with one temperature a failed compression-ratio / log-probability check has nowhere to fall back to and HF keeps the
-    # result (generation_whisper.py:1100-1104): the only observable effect of the thresholds at temperature 0 is the no-speech
-    # skip, which generation.generate implements; compression_ratio_threshold is therefore accepted and has no effect
+    # result (generation_whisper.py:1100-1104): the only observable effect of the thresholds is then the no-speech skip; with
+    # several, generation.generate decodes the windows that fail one again at the next temperature
+
+
+def _check_seed(seed) -> int:
+    """``sampling_seed``: the 64-bit key of the engine's counter-based sampler (transformers has no such argument: it draws
+    from torch's global generator)."""
+    if isinstance(seed, bool) or not isinstance(seed, (int, np.integer)) or not 0 <= int(seed) < 2 ** 64:
+        raise ValueError(f"sampling_seed must be an integer in 0 .. 2^64 - 1, not {seed!r}")
+    return int(seed)
 
 
 class CrisperWhisperPipeline:
@@ -275,7 +316,8 @@ class CrisperWhisperPipeline:
                  batch_size=1, return_timestamps=None, torch_dtype=None, dtype=None, device=None,
                  shard: Optional[dist.Shard] = None, contexts: int = 1, cross_kv_dtype: Optional[str] = None,
                  encoder_gemm_dtype: Optional[str] = None,
-                 engines: Optional[List[Engine]] = None, num_beams: Optional[int] = None, **kwargs):
+                 engines: Optional[List[Engine]] = None, num_beams: Optional[int] = None,
+                 sampling_seed: Optional[int] = None, **kwargs):
         """``num_beams`` (construction time): the widest beam the contexts are provisioned for -- decoder rows =
         batch_size x num_beams, at most 64.  Default 5 = ``AutomaticSpeechRecognitionPipeline._default_generation_config``
         of the installed transformers (TF/pipelines/automatic_speech_recognition.py:160-163), which is what a call
@@ -306,6 +348,9 @@ class CrisperWhisperPipeline:
         self.max_rows = min(64, self.batch_size * int(num_beams or DEFAULT_NUM_BEAMS))
         self.max_rows = max(self.max_rows, min(64, self.batch_size))
         self.return_timestamps = return_timestamps
+        # the key of the engine's sampler for calls with a positive temperature / temperature fallback; None: such calls must
+        # name one themselves (a call without any seed is refused, it does not draw from a hidden default)
+        self.sampling_seed = None if sampling_seed is None else _check_seed(sampling_seed)
         self.shard = shard or dist.Shard()
         # `contexts` > 1: independent engine contexts on the same GPU, each running its own batches from a host
         # thread -- the decode chain is latency-bound, so a second in-flight batch fills idle CUs.
@@ -363,7 +408,8 @@ class CrisperWhisperPipeline:
         return self._run_one(inputs, **kwargs)
 
     def _run_one(self, inputs, return_timestamps=None, generate_kwargs=None, chunk_length_s=None,
-                 stride_length_s=None, return_language=None, **unused):
+                 stride_length_s=None, return_language=None, sampling_seed=None, **unused):
+        seed = self.sampling_seed if sampling_seed is None else _check_seed(sampling_seed)
         rt = return_timestamps if return_timestamps is not None else self.return_timestamps
         if not (rt == "word" or rt is True):
             raise ValueError("crisperwhisper_amd implements the timestamped paths: pass return_timestamps='word' "
@@ -372,7 +418,7 @@ class CrisperWhisperPipeline:
         if return_language:
             raise ValueError("return_language is not supported on the native path")
         gk = dict(generate_kwargs or {})
-        _check_generate_kwargs(gk, self.default_num_beams, self.bundle.spec)
+        _check_generate_kwargs(gk, self.default_num_beams, self.bundle.spec, seed)
         if "num_beams" not in gk:
             _warn_once("beams", f"no num_beams given: decoding with {self.default_num_beams} beams like the installed transformers "
                                 "ASR pipeline default; pass generate_kwargs={'num_beams': 1} for the greedy decoding of the 2024 reference")
@@ -405,6 +451,7 @@ class CrisperWhisperPipeline:
 
         lo, hi = dist.shard_bounds(len(windows), self.shard.world)[self.shard.rank]
         mine = list(range(lo, hi))
+        fallback_trace = []                                 # one record per judged (window, temperature) decode
         def run_batch(args):
             slot, idxs = args
             eng = self.engines[slot % len(self.engines)]
@@ -415,7 +462,11 @@ class CrisperWhisperPipeline:
                 eng, len(idxs), nf, language=gk.get("language"), task=gk.get("task"),
                 max_new_tokens=gk.get("max_new_tokens"), min_new_tokens=gk.get("min_new_tokens"),
                 num_beams=num_beams, stats=st, logprob_threshold=gk.get("logprob_threshold"),
-                no_speech_threshold=gk.get("no_speech_threshold"), prompt_ids=gk.get("prompt_ids"))
+                no_speech_threshold=gk.get("no_speech_threshold"), prompt_ids=gk.get("prompt_ids"),
+                temperature=gk.get("temperature"), compression_ratio_threshold=gk.get("compression_ratio_threshold"),
+                sampling_seed=seed or 0, item_ids=idxs)
+            if "fallback" in st:
+                fallback_trace.extend(st["fallback"])
             rs = []
             for k, i in enumerate(idxs):
                 n_tok = len(out["token_timestamps"][k])
@@ -444,6 +495,7 @@ class CrisperWhisperPipeline:
         else:
             results = [run_batch(b) for b in batches]
         recs = [r for rs, _ in results for r in rs]
+        self.stats["fallback"] = sorted(fallback_trace, key=lambda d: (d["item"], d["seek"], d["temperature_index"]))
         self.stats["generate_calls"] = self.stats.get("generate_calls", 0) + sum(c for _, c in results)
         recs = np.stack(recs) if recs else np.zeros((0, dist.REC_WORDS), np.int32)
         max_per_rank = max(h - l for l, h in dist.shard_bounds(len(windows), self.shard.world))

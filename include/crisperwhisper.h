@@ -152,8 +152,32 @@ int32_t cw_decode(cw_ctx* ctx, int32_t nb, const int32_t* prompt, int32_t n_prom
  * no_timestamps_token_id - 1) is above no_speech_threshold is skipped: seek advances by the window, no segment (:879-881).
  * NaN = unset.  cw_transcribe applies them; stage-wise callers use cw_no_speech_probs before cw_decode and
  * cw_get_avg_logprobs after it (token scores are tracked while a logprob threshold is set).  The stochastic half --
- * re-decoding at higher temperatures -- is not implemented.                                                              */
+ * re-decoding the windows that fail a threshold at higher temperatures -- is built from cw_set_sampling and cw_decode_rows
+ * below by the host seek loop (crisperwhisper_amd/generation.py); cw_transcribe itself stays greedy, without fallback.      */
 int32_t cw_set_thresholds(cw_ctx* ctx, float logprob_threshold, float no_speech_threshold);
+/* Seeded sampling for the coming cw_decode / cw_decode_rows calls (greedy rows only; beam search is never sampled,
+ * generation_whisper.py:1004-1005).  The token written at sequence position t of a row is
+ *     argmax over the tokens v the logits processors allow of   fl(fl(s_v / T) + g_v),     lowest v on an exact tie,
+ * s the processed f32 score, T = temperature, g_v = -log(-log(u_v)) (Gumbel-max: an exact draw from softmax(s / T)).  Once
+ * the timestamp rule (logits_process.py:2040-2045) has fired -- it is evaluated on the unperturbed scores, as are the
+ * log-probability sums behind cw_get_avg_logprobs -- the argmax runs over the allowed timestamp tokens alone.
+ * The noise is counter-based: (x_0, x_1, x_2, x_3) = Philox4x32-10(key = (seed_lo, seed_hi), counter = (v >> 2, t, stream_lo,
+ * stream_hi)) (Salmon et al., "Parallel random numbers: as easy as 1, 2, 3", SC 2011; multipliers 0xD2511F53 / 0xCD9E8D57, key
+ * increments 0x9E3779B9 / 0xBB67AE85), word x_{v & 3} belongs to token v, and u = ((x >> 8) + 0.5) * 2^-24 as a real number in
+ * (0, 1) -- never 0 or 1.  u is exact in f32 for x >> 8 < 2^23; above that 1 - u is, and the kernel takes -log(u) as
+ * -log1p(-(1 - u)) there.  seed_lo / seed_hi and stream_lo / stream_hi are the low / high 32 bits of `seed` and of
+ * row_streams[b]: a token depends on (seed, stream of its row, t, logits) only, never on the row index or the batch.
+ * temperature 0 or row_streams == NULL: greedy again, bit for bit the path that never called this.  A negative, NaN or
+ * infinite temperature and nb outside 1 .. max_batch are refused.  The values live in device memory the sampler kernels read,
+ * so captured decode steps stay valid.                                                                                     */
+int32_t cw_set_sampling(cw_ctx* ctx, float temperature, uint64_t seed, const uint64_t* row_streams /* [nb] */, int32_t nb);
+/* cw_decode with only some rows live: row_active [nb] (NULL: all), a row with 0 starts finished -- the decoder still steps
+ * it (the step streams weights; an idle row costs nothing measurable), but its ids on device and its log-probability sum and
+ * count (cw_get_avg_logprobs) stay what the previous decode left, and its lengths entry is 0.  Its cache and alignment rows
+ * are overwritten: take cw_token_timestamps of a row after the decode that settled it.  No active row is refused.          */
+int32_t cw_decode_rows(cw_ctx* ctx, int32_t nb, const int32_t* prompt, int32_t n_prompt, int32_t max_length,
+                       int32_t min_new_tokens, const int32_t* forced, const int32_t* row_active, int32_t* sequences,
+                       int32_t* lengths, int32_t* argmax_out);
 int32_t cw_no_speech_probs(cw_ctx* ctx, int32_t nb, int32_t sot_token, float* out /* [nb] */);
 int32_t cw_get_avg_logprobs(cw_ctx* ctx, float* out /* [nb] */, int32_t nb);
 int32_t cw_get_logits(cw_ctx* ctx, float* out /* [nb][vocab] */, int32_t nb);       /* last sampled step */
@@ -375,6 +399,13 @@ int32_t cw_test_beam_state(cw_ctx* ctx, int32_t rows, int32_t* ids, int32_t* anc
  * sequence index t.  Uses the lists installed by cw_set_generation.                                               */
 int32_t cw_test_sample(cw_ctx* ctx, int32_t nb, const float* logits, const int32_t* ids, int32_t t, int32_t n_prompt,
                        int32_t min_new_tokens, int32_t max_length, int32_t* choice_out);
+/* The same two launches under cw_set_sampling(temperature, seed, row_streams, nb) for this call only (the context's own
+ * setting is put back).  Refused before any launch: a null pointer, nb outside 1 .. min(max_batch, 64), an id outside the
+ * vocabulary, t outside n_prompt .. max_target_positions - 1, max_length outside n_prompt + 1 .. max_target_positions, a
+ * negative min_new_tokens, a temperature cw_set_sampling refuses, a positive temperature without row_streams.            */
+int32_t cw_test_sample_seeded(cw_ctx* ctx, int32_t nb, const float* logits, const int32_t* ids, int32_t t, int32_t n_prompt,
+                              int32_t min_new_tokens, int32_t max_length, float temperature, uint64_t seed,
+                              const uint64_t* row_streams, int32_t* choice_out);
 
 /* ---- measurement -------------------------------------------------------------------------------------- */
 #define CW_STAGE_MEL 0
