@@ -43,6 +43,15 @@ class TranscribeCfg(C.Structure):
 
 _P = C.c_void_p
 _I = C.c_int32
+
+
+class GemmEpiArgs(C.Structure):
+    """cw_test_gemm_epi_args (include/crisperwhisper.h)"""
+    _fields_ = [(n, _I) for n in ("epi", "fp8", "M", "N", "K", "conv", "n_rows", "T_out", "C_in", "stride", "nb")] + [
+        (n, _P) for n in ("row_off", "row_valid", "A", "W", "bias", "resid", "pos")] + [
+        (n, _I) for n in ("ldo", "T", "S_pad", "H", "d_model")] + [(n, _P) for n in ("out", "out1", "out2")]
+
+
 _SIGS = {
     "cw_abi_version": (_I, []),
     "cw_create": (_P, [C.POINTER(ModelDesc), _I]),
@@ -106,6 +115,8 @@ _SIGS = {
     "cw_test_set_option": (_I, [C.c_char_p, _I]),
     "cw_test_gemm": (_I, [_P, _I, _I, _I, _P, _P, _P, _I, _P]),
     "cw_test_gemm_fp8": (_I, [_P, _I, _I, _I, _P, _P, _P, _I, _P]),
+    "cw_test_gemm_epi": (_I, [_P, C.POINTER(GemmEpiArgs)]),
+    "cw_test_rownorm": (_I, [_P, _I, _I, _I, _P, _P, _P, _P, _P, _P]),
     "cw_test_gemv": (_I, [_P, _I, _I, _I, _P, _P, _P, _P, _P, _I, _P]),
     "cw_has_experiments": (_I, []),
     "cw_test_skinny": (_I, [_P, _I, _I, _I, _I, _P, _P, _P, _I, _I, _P, _P]),

@@ -3148,6 +3148,160 @@ int32_t cw_test_gemm_fp8(cw_ctx* c, int32_t M, int32_t N, int32_t K, const float
     return r;
 }
 
+// One launch of cw_launch_gemm (fp8: cw_launch_quant_rows_fp8 twice + cw_launch_gemm_fp8) with any encoder epilogue and either
+// A-operand form, AParams / EpiParams filled the way cw_encode fills them (include/crisperwhisper.h).  Everything the kernels
+// derive an address from is checked here, before anything is launched; the outputs start from the caller's contents.
+int32_t cw_test_gemm_epi(cw_ctx* c, const cw_test_gemm_epi_args* a) {
+    if (!a) return fail(c, CW_ERR_INVALID, "test_gemm_epi: null arguments");
+    const int epi = a->epi, M = a->M, N = a->N, K = a->K, ldo = a->ldo;
+    const long long lim = 1ll << 26;                                  // elements per buffer: a test hook, not a workload
+    if (M < 1 || N < 1 || K < 1 || (long long)M * K > lim || (long long)N * K > lim)
+        return fail(c, CW_ERR_INVALID, "test_gemm_epi: shape M=%d N=%d K=%d", M, N, K);
+    if (K % 64) return fail(c, CW_ERR_INVALID, "test_gemm_epi: K=%d is not a multiple of 64", K);
+    if (!a->A || !a->W) return fail(c, CW_ERR_INVALID, "test_gemm_epi: null operand");
+    const bool heads = epi == EPI_HEADS, f32out = epi == EPI_RESID_F32 || epi == EPI_GELU_POS_F32 || epi == EPI_STORE_F32;
+    if (!(epi == EPI_STORE || epi == EPI_GELU || heads || f32out)) return fail(c, CW_ERR_INVALID, "test_gemm_epi: epilogue %d", epi);
+    if (!a->out) return fail(c, CW_ERR_INVALID, "test_gemm_epi: null output");
+    int n_which = 0;
+    size_t n_in = (size_t)M * K, n_out = 0;
+    if (heads) {
+        const int T = a->T, D = a->d_model;
+        if (T < 1 || M % T) return fail(c, CW_ERR_INVALID, "test_gemm_epi: M=%d is not a multiple of T=%d", M, T);
+        if (D < 64 || D % 64 || a->H != D / 64) return fail(c, CW_ERR_INVALID, "test_gemm_epi: d_model=%d H=%d", D, a->H);
+        if (N != 2 * D && N != 3 * D) return fail(c, CW_ERR_INVALID, "test_gemm_epi: N=%d is not 2 or 3 times d_model=%d", N, D);
+        if (a->S_pad < T) return fail(c, CW_ERR_INVALID, "test_gemm_epi: S_pad=%d < T=%d", a->S_pad, T);
+        n_which = N / D;
+        if (!a->out1 || (n_which == 3 && !a->out2)) return fail(c, CW_ERR_INVALID, "test_gemm_epi: null head-split output");
+        n_out = (size_t)(M / T) * a->H * a->S_pad * 64;
+    } else {
+        if (ldo < N) return fail(c, CW_ERR_INVALID, "test_gemm_epi: ldo=%d < N=%d", ldo, N);
+        n_out = (size_t)M * ldo;
+        if (epi == EPI_GELU_POS_F32 && (!a->pos || a->T < 1)) return fail(c, CW_ERR_INVALID, "test_gemm_epi: positions need pos and T >= 1");
+    }
+    if ((long long)n_out > lim) return fail(c, CW_ERR_INVALID, "test_gemm_epi: output of %zu elements", n_out);
+    if (a->conv) {
+        if (a->fp8) return fail(c, CW_ERR_INVALID, "test_gemm_epi: the e4m3 GEMM takes plain A only");
+        if (a->C_in < 64 || a->C_in % 64 || K != 3 * a->C_in) return fail(c, CW_ERR_INVALID, "test_gemm_epi: conv gather C_in=%d K=%d", a->C_in, K);
+        if (a->nb < 1 || a->T_out < 1 || (long long)a->nb * a->T_out != M || (a->stride != 1 && a->stride != 2))
+            return fail(c, CW_ERR_INVALID, "test_gemm_epi: conv gather nb=%d T_out=%d stride=%d M=%d", a->nb, a->T_out, a->stride, M);
+        if (a->n_rows < 1 || (long long)a->n_rows * a->C_in > lim || !a->row_off || !a->row_valid)
+            return fail(c, CW_ERR_INVALID, "test_gemm_epi: conv gather input of %d rows", a->n_rows);
+        for (int b = 0; b < a->nb; ++b)
+            if (a->row_off[b] < 0 || a->row_valid[b] < 0 || (long long)a->row_off[b] + a->row_valid[b] > a->n_rows)
+                return fail(c, CW_ERR_INVALID, "test_gemm_epi: window %d = rows [%d, %d + %d) outside the %d input rows", b, a->row_off[b],
+                            a->row_off[b], a->row_valid[b], a->n_rows);
+        n_in = (size_t)a->n_rows * a->C_in;
+    }
+    if (a->fp8) {
+        if (!c->bf16) return fail(c, CW_ERR_INVALID, "test_gemm_epi: the e4m3 GEMM belongs to the 16-bit engines");
+        if (!(epi == EPI_STORE || epi == EPI_GELU || epi == EPI_HEADS || epi == EPI_RESID_F32) || N % 256 || K % 128)
+            return fail(c, CW_ERR_INVALID, "test_gemm_epi: the e4m3 GEMM takes epilogues 0 / 1 / 2 / 4, N %% 256 == 0, K %% 128 == 0 (epi=%d N=%d K=%d)", epi, N, K);
+    }
+    const size_t e = c->esz;
+    void *dA = nullptr, *dW = nullptr, *dO[3] = {nullptr, nullptr, nullptr}, *dA8 = nullptr, *dW8 = nullptr;
+    float *dB = nullptr, *dR = nullptr, *dP = nullptr, *dsa = nullptr, *dsw = nullptr;
+    int *doff = nullptr, *dval = nullptr;
+    float* const host_out[3] = {a->out, a->out1, a->out2};
+    const int n_bufs = heads ? n_which : 1;
+    DevScope mem;
+    HIPCHK(c, mem.get(&dA, n_in * e)); HIPCHK(c, mem.get(&dW, (size_t)N * K * e));
+    CWCHK(c, upload_T(c, dA, 0, a->A, n_in)); CWCHK(c, upload_T(c, dW, 0, a->W, (size_t)N * K));
+    for (int i = 0; i < n_bufs; ++i) {
+        HIPCHK(c, mem.get(&dO[i], n_out * (f32out ? 4 : e)));
+        if (f32out) HIPCHK(c, hipMemcpy(dO[i], host_out[i], n_out * 4, hipMemcpyHostToDevice));
+        else CWCHK(c, upload_T(c, dO[i], 0, host_out[i], n_out));
+    }
+    if (a->bias) { HIPCHK(c, mem.get(&dB, (size_t)N * 4)); HIPCHK(c, hipMemcpy(dB, a->bias, (size_t)N * 4, hipMemcpyHostToDevice)); }
+    if (epi == EPI_RESID_F32 && a->resid) { HIPCHK(c, mem.get(&dR, n_out * 4)); HIPCHK(c, hipMemcpy(dR, a->resid, n_out * 4, hipMemcpyHostToDevice)); }
+    if (epi == EPI_GELU_POS_F32) {
+        HIPCHK(c, mem.get(&dP, (size_t)a->T * ldo * 4));
+        HIPCHK(c, hipMemcpy(dP, a->pos, (size_t)a->T * ldo * 4, hipMemcpyHostToDevice));
+    }
+    AParams ap{dA, K, 0, 0, 0, 0, nullptr, nullptr};
+    if (a->conv) {
+        HIPCHK(c, mem.get(&doff, (size_t)a->nb * 4)); HIPCHK(c, mem.get(&dval, (size_t)a->nb * 4));
+        HIPCHK(c, hipMemcpy(doff, a->row_off, (size_t)a->nb * 4, hipMemcpyHostToDevice));
+        HIPCHK(c, hipMemcpy(dval, a->row_valid, (size_t)a->nb * 4, hipMemcpyHostToDevice));
+        ap = AParams{dA, 0, 1, a->T_out, a->C_in, a->stride, doff, dval};
+    }
+    EpiParams ep = epi0();
+    ep.bias = dB;
+    if (heads) {
+        ep.out = dO[0]; ep.out1 = dO[1]; ep.out2 = dO[2];
+        ep.T = a->T; ep.S_pad = a->S_pad; ep.H = a->H; ep.d_model = a->d_model;
+    } else if (f32out) {
+        ep.outf = (float*)dO[0]; ep.ldo = ldo;
+        if (epi == EPI_RESID_F32) ep.resid = dR ? dR : (const float*)dO[0];
+        if (epi == EPI_GELU_POS_F32) { ep.pos = dP; ep.T = a->T; }
+    } else {
+        ep.out = dO[0]; ep.ldo = ldo;
+    }
+    int r;
+    if (a->fp8) {
+        HIPCHK(c, mem.get(&dA8, (size_t)M * K)); HIPCHK(c, mem.get(&dW8, (size_t)N * K));
+        HIPCHK(c, mem.get(&dsa, (size_t)M * 4)); HIPCHK(c, mem.get(&dsw, (size_t)N * 4));
+        r = KD(c, cw_launch_quant_rows_fp8, dA, M, K, dA8, dsa, c->st);
+        if (r == CW_OK) r = KD(c, cw_launch_quant_rows_fp8, dW, N, K, dW8, dsw, c->st);
+        if (r == CW_OK) r = KD(c, cw_launch_gemm_fp8, epi, dA8, K, dW8, M, N, K, dsa, dsw, ep, c->st);
+    } else {
+        r = KD(c, cw_launch_gemm, c->bf16, epi, ap, dW, M, N, K, ep, c->st);
+    }
+    if (r != CW_OK) return fail(c, r, "test_gemm_epi: launch rejected (epi=%d M=%d N=%d K=%d)", epi, M, N, K);
+    { hipError_t er = hipStreamSynchronize(c->st); if (er != hipSuccess) return fail(c, CW_ERR_HIP, "test_gemm_epi: %s", hipGetErrorString(er)); }
+    { hipError_t er = hipGetLastError(); if (er != hipSuccess) return fail(c, CW_ERR_HIP, "test_gemm_epi: %s", hipGetErrorString(er)); }
+    for (int i = 0; i < n_bufs; ++i) {
+        if (f32out) HIPCHK(c, hipMemcpy(host_out[i], dO[i], n_out * 4, hipMemcpyDeviceToHost));
+        else CWCHK(c, download_T(c, dO[i], 0, host_out[i], n_out));
+    }
+    return CW_OK;
+}
+
+// One launch of a row kernel of the encoder: 0 cw_launch_layernorm, 1 cw_launch_layernorm_fp8, 2 cw_launch_quant_rows_fp8 on the
+// rows rounded to the engine's 16-bit type (include/crisperwhisper.h).  The outputs start from the caller's contents.
+int32_t cw_test_rownorm(cw_ctx* c, int32_t mode, int32_t rows, int32_t d, const float* x, const float* gamma, const float* beta,
+                        float* out, uint8_t* out8, float* scale) {
+    if (mode < 0 || mode > 2) return fail(c, CW_ERR_INVALID, "test_rownorm: mode %d", mode);
+    if (rows < 1 || d < 1 || (long long)rows * d > (1ll << 26)) return fail(c, CW_ERR_INVALID, "test_rownorm: rows=%d d=%d", rows, d);
+    if (mode != 0 && !c->bf16) return fail(c, CW_ERR_INVALID, "test_rownorm: the e4m3 row kernels belong to the 16-bit engines");
+    if (!x || (mode != 2 && (!gamma || !beta)) || (mode == 0 ? !out : (!out8 || !scale))) return fail(c, CW_ERR_INVALID, "test_rownorm: null buffer");
+    if ((mode != 2 && d % 4) || (mode == 1 && d > 2048) || (mode == 2 && d % 8)) return fail(c, CW_ERR_INVALID, "test_rownorm: mode %d does not take d=%d", mode, d);
+    const size_t n = (size_t)rows * d;
+    float *dx = nullptr, *dg = nullptr, *db = nullptr, *dsc = nullptr;
+    void *dx16 = nullptr, *dout = nullptr;
+    DevScope mem;
+    int r;
+    if (mode == 2) {
+        HIPCHK(c, mem.get(&dx16, n * c->esz));
+        CWCHK(c, upload_T(c, dx16, 0, x, n));
+    } else {
+        HIPCHK(c, mem.get(&dx, n * 4)); HIPCHK(c, mem.get(&dg, (size_t)d * 4)); HIPCHK(c, mem.get(&db, (size_t)d * 4));
+        HIPCHK(c, hipMemcpy(dx, x, n * 4, hipMemcpyHostToDevice));
+        HIPCHK(c, hipMemcpy(dg, gamma, (size_t)d * 4, hipMemcpyHostToDevice));
+        HIPCHK(c, hipMemcpy(db, beta, (size_t)d * 4, hipMemcpyHostToDevice));
+    }
+    if (mode == 0) {
+        HIPCHK(c, mem.get(&dout, n * c->esz));
+        CWCHK(c, upload_T(c, dout, 0, out, n));
+        r = KD(c, cw_launch_layernorm, c->bf16, dx, dg, db, dout, rows, d, c->st);
+    } else {
+        HIPCHK(c, mem.get(&dout, n)); HIPCHK(c, mem.get(&dsc, (size_t)rows * 4));
+        HIPCHK(c, hipMemcpy(dout, out8, n, hipMemcpyHostToDevice));
+        HIPCHK(c, hipMemcpy(dsc, scale, (size_t)rows * 4, hipMemcpyHostToDevice));
+        if (mode == 1) r = KD(c, cw_launch_layernorm_fp8, dx, dg, db, dout, dsc, rows, d, c->st);
+        else r = KD(c, cw_launch_quant_rows_fp8, dx16, rows, d, dout, dsc, c->st);
+    }
+    if (r != CW_OK) return fail(c, r, "test_rownorm: launch rejected (mode=%d rows=%d d=%d)", mode, rows, d);
+    { hipError_t er = hipStreamSynchronize(c->st); if (er != hipSuccess) return fail(c, CW_ERR_HIP, "test_rownorm: %s", hipGetErrorString(er)); }
+    { hipError_t er = hipGetLastError(); if (er != hipSuccess) return fail(c, CW_ERR_HIP, "test_rownorm: %s", hipGetErrorString(er)); }
+    if (mode == 0) {
+        CWCHK(c, download_T(c, dout, 0, out, n));
+    } else {
+        HIPCHK(c, hipMemcpy(out8, dout, n, hipMemcpyDeviceToHost));
+        HIPCHK(c, hipMemcpy(scale, dsc, (size_t)rows * 4, hipMemcpyDeviceToHost));
+    }
+    return CW_OK;
+}
+
 int32_t cw_test_gemv(cw_ctx* c, int32_t Mb, int32_t N, int32_t K, const float* x, const float* W, const float* bias,
                      const float* ln_g, const float* ln_b, int32_t gelu, float* out) {
     float *dx = nullptr, *dB = nullptr, *dO = nullptr, *dg = nullptr, *db = nullptr, *dxn = nullptr; void* dW = nullptr;

@@ -507,6 +507,63 @@ class Engine:
         self._chk(self.lib.cw_test_gemm_fp8(self.ctx, A.shape[0], W.shape[0], A.shape[1], _ptr(A), _ptr(W), _ptr(b), int(gelu), _ptr(out)))
         return out
 
+    def test_gemm_epi(self, epi, A, W, bias=None, *, out, out1=None, out2=None, conv=None, resid=None, pos=None, ldo=0, T=0,
+                      S_pad=0, H=0, d_model=0, fp8=False, M=None, K=None):
+        """One launch of the encoder GEMM dispatcher with epilogue `epi` (cw_test_gemm_epi).  A [M][K], or with
+        conv = (T_out, stride, row_off, row_valid) the time-major input rows [n_rows][C_in] of the implicit conv1d gather;
+        W [N][K].  out (head split: out, out1, out2) are float32 arrays holding the caller's sentinel; they are overwritten in
+        place with what the device holds after the launch and `out` is returned.  M / K override the operand's own shape (the
+        refusal tests)."""
+        A = np.ascontiguousarray(A, np.float32); W = np.ascontiguousarray(W, np.float32)
+        keep = [A, W]
+        a = N.GemmEpiArgs()
+        a.epi, a.fp8, a.N = int(epi), int(bool(fp8)), W.shape[0]
+        if conv is None:
+            a.conv, a.M, a.K = 0, A.shape[0], A.shape[1]
+        else:
+            T_out, stride, row_off, row_valid = conv
+            ro, rv = _i32(row_off), _i32(row_valid)
+            keep += [ro, rv]
+            a.conv, a.n_rows, a.C_in, a.T_out, a.stride, a.nb = 1, A.shape[0], A.shape[1], int(T_out), int(stride), len(ro)
+            a.row_off, a.row_valid = _ptr(ro), _ptr(rv)
+            a.M, a.K = len(ro) * int(T_out), 3 * A.shape[1]
+        if M is not None:
+            a.M = int(M)
+        if K is not None:
+            a.K = int(K)
+        a.A, a.W = _ptr(A), _ptr(W)
+        for name, t in (("bias", bias), ("resid", resid), ("pos", pos)):
+            if t is not None:
+                t = np.ascontiguousarray(t, np.float32)
+                keep.append(t)
+                setattr(a, name, _ptr(t))
+        a.ldo, a.T, a.S_pad, a.H, a.d_model = int(ldo), int(T), int(S_pad), int(H), int(d_model)
+        for name, t in (("out", out), ("out1", out1), ("out2", out2)):
+            if t is not None:
+                assert t.dtype == np.float32 and t.flags["C_CONTIGUOUS"] and t.flags["WRITEABLE"]
+                setattr(a, name, _ptr(t))
+        self._chk(self.lib.cw_test_gemm_epi(self.ctx, C.byref(a)))
+        return out
+
+    def test_rownorm(self, mode, x, gamma=None, beta=None, *, out=None, out8=None, scale=None):
+        """One launch of a row kernel (cw_test_rownorm): mode 0 LayerNorm -> out [rows][d] float32; mode 1 LayerNorm -> e4m3
+        bytes out8 [rows][d] (uint8) + scale [rows]; mode 2 row-wise e4m3 quantisation of x rounded to the 16-bit type.  The
+        output arrays are in / out (sentinel in, device contents out); missing ones are created zero-filled.  Returns out, or
+        (out8, scale)."""
+        x = np.ascontiguousarray(x, np.float32)
+        rows, d = x.shape
+        g = None if gamma is None else np.ascontiguousarray(gamma, np.float32)
+        b = None if beta is None else np.ascontiguousarray(beta, np.float32)
+        if mode == 0:
+            out = np.zeros((rows, d), np.float32) if out is None else out
+            assert out.dtype == np.float32 and out.flags["C_CONTIGUOUS"]
+        else:
+            out8 = np.zeros((rows, d), np.uint8) if out8 is None else out8
+            scale = np.zeros(rows, np.float32) if scale is None else scale
+            assert out8.dtype == np.uint8 and scale.dtype == np.float32 and out8.flags["C_CONTIGUOUS"]
+        self._chk(self.lib.cw_test_rownorm(self.ctx, int(mode), rows, d, _ptr(x), _ptr(g), _ptr(b), _ptr(out), _ptr(out8), _ptr(scale)))
+        return out if mode == 0 else (out8, scale)
+
     def test_gemv(self, x, W, bias=None, ln=None, gelu=False):
         x = np.ascontiguousarray(x, np.float32); W = np.ascontiguousarray(W, np.float32)
         b = None if bias is None else np.ascontiguousarray(bias, np.float32)

@@ -339,6 +339,43 @@ int32_t cw_test_gemm(cw_ctx* ctx, int32_t M, int32_t N, int32_t K, const float* 
 /* e4m3 x e4m3 GEMM of the opt-in fp8 encoder mode (row-wise scales, v_mfma_scale_f32_16x16x128_f8f6f4): out = T(A W^T + bias) */
 int32_t cw_test_gemm_fp8(cw_ctx* ctx, int32_t M, int32_t N, int32_t K, const float* A, const float* W, const float* bias,
                          int32_t gelu, float* out);
+/* One launch of the encoder's tile-GEMM dispatcher with any of its epilogues and either A-operand form, parameters filled the
+ * way cw_encode fills them.  Host f32 in / out; A, W and the 16-bit outputs are rounded to / returned from the context's dtype.
+ *   epi     0 store, 1 GELU: out [M][ldo] (engine type);  2 f32 residual, 3 GELU + pos[m % T], 5 f32 store: out [M][ldo] f32;
+ *           4 head split: N = 2 or 3 times d_model column groups -> out, out1 (, out2), each [M / T][H][S_pad][64] (engine type)
+ *   conv    0: A [M][K] row-major.  1: implicit conv1d(k = 3, pad = 1) gather over time-major input rows A [n_rows][C_in]:
+ *           row m = b * T_out + t of the operand is the concatenation over tap = 0, 1, 2 of input row
+ *           row_off[b] + t * stride + tap - 1, or zeros unless 0 <= t * stride + tap - 1 < row_valid[b];  M = nb * T_out, K = 3 C_in
+ *   resid   epi 2: [M][ldo], or null for the in-place form the engine uses (out holds the residual on entry)
+ *   fp8     1: A and W are quantised row-wise (cw_test_rownorm mode 2's kernel) and multiplied by the e4m3 GEMM: 16-bit engines,
+ *           plain A, epi 0 / 1 / 2 / 4, N % 256 == 0, K % 128 == 0
+ * Every output buffer is in / out: its contents are uploaded before the launch and downloaded after it, so a sentinel the caller
+ * wrote marks every element the kernel left alone.  Refused (CW_ERR_INVALID) before anything is launched: a null buffer the
+ * epilogue needs, K % 64, ldo < N, a conv gather with C_in % 64, K != 3 C_in, M != nb * T_out, a stride other than 1 / 2 or a
+ * window outside [0, n_rows), a head split with M % T, d_model % 64, H != d_model / 64, N not 2 or 3 times d_model or S_pad < T,
+ * epi 3 without pos / T, and what the fp8 form does not take.                                                                */
+typedef struct cw_test_gemm_epi_args {
+    int32_t epi, fp8, M, N, K;
+    int32_t conv, n_rows, T_out, C_in, stride, nb;
+    const int32_t* row_off;   /* [nb] */
+    const int32_t* row_valid; /* [nb] */
+    const float* A;
+    const float* W;           /* [N][K] */
+    const float* bias;        /* [N] or null */
+    const float* resid;
+    const float* pos;         /* epi 3: [T][ldo] */
+    int32_t ldo, T, S_pad, H, d_model;
+    float* out;
+    float* out1;
+    float* out2;
+} cw_test_gemm_epi_args;
+int32_t cw_test_gemm_epi(cw_ctx* ctx, const cw_test_gemm_epi_args* args);
+/* One launch of a row kernel on x [rows][d] (f32), gamma / beta [d].  mode 0: LayerNorm -> out [rows][d] (engine type, f32 on the
+ * f32 engine; d % 4 == 0).  mode 1: LayerNorm -> e4m3 bytes out8 [rows][d] + scale [rows] (d % 4 == 0, d <= 2048).  mode 2: x
+ * rounded to the engine's 16-bit type -> row-wise e4m3 quantisation, out8 + scale (d % 8 == 0; gamma / beta unused).  Modes 1 and
+ * 2 belong to the 16-bit engines.  The outputs are in / out like those of cw_test_gemm_epi.                                    */
+int32_t cw_test_rownorm(cw_ctx* ctx, int32_t mode, int32_t rows, int32_t d, const float* x, const float* gamma, const float* beta,
+                        float* out, uint8_t* out8, float* scale);
 int32_t cw_test_gemv(cw_ctx* ctx, int32_t Mb, int32_t N, int32_t K, const float* x, const float* W,
                      const float* bias, const float* ln_g, const float* ln_b, int32_t gelu, float* out);
 /* One skinny-M decoder projection (17..64 rows; csrc/skinny.hip) on caller-supplied rows, 16-bit engines.  mode 0: LayerNorm
