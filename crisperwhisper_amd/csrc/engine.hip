@@ -2882,8 +2882,10 @@ int32_t cw_has_experiments(void) {
 }
 
 static int g_test_cross_fp8 = 0;   // cw_test_cross_attention through the e4m3 cache (option "cross_test_fp8")
+static int g_test_attn_poison_qpad = 0;   // cw_test_attention: Q rows S .. S_pad-1 hold NaN instead of zeros (option "attn_poison_qpad")
 int32_t cw_test_set_option(const char* name, int32_t value) {
     if (!strcmp(name, "cross_test_fp8")) { g_test_cross_fp8 = value; return CW_OK; }
+    if (!strcmp(name, "attn_poison_qpad")) { g_test_attn_poison_qpad = value; return CW_OK; }
     if (!strcmp(name, "gemm256_min_tiles")) { cw_bf16::cw_gemm_set_256_min_tiles(value); cw_f16::cw_gemm_set_256_min_tiles(value); return CW_OK; }
     if (!strcmp(name, "beam_topk_1block")) { cw_bf16::cw_beam_topk_set_1block(value); cw_f16::cw_beam_topk_set_1block(value); return CW_OK; }
     if (!strcmp(name, "gemm_pp")) { cw_bf16::cw_gemm_set_pp(value); cw_f16::cw_gemm_set_pp(value); return CW_OK; }
@@ -3435,19 +3437,28 @@ int32_t cw_test_skinny(cw_ctx* c, int32_t mode, int32_t Mb, int32_t N, int32_t K
     return r;
 }
 
+// One launch of the encoder self-attention on caller-supplied rows.  K and V rows S .. S_pad-1 are zero, the engine's contract
+// (dmalloc zeroes kb / vb and the head-split epilogue writes rows < T only); the Q pad rows are zero too, or NaN under the option
+// "attn_poison_qpad" (the kernels clamp query loads to row S-1: nothing may change).  `out` is in / out; ATTN_GUARD_ROWS rows of
+// 0xFF bytes lie behind it on the device and have to come back untouched.
+#define ATTN_GUARD_ROWS 64
 int32_t cw_test_attention(cw_ctx* c, int32_t B, int32_t H, int32_t S, const float* q, const float* k, const float* v, float* out) {
+    if (B < 1 || H < 1 || S < 1 || !q || !k || !v || !out) return fail(c, CW_ERR_INVALID, "test_attention: bad arguments (B=%d H=%d S=%d)", B, H, S);
     const int S_pad = (S + 63) & ~63;
-    const size_t e = c->esz, nh = (size_t)B * H * S_pad * 64;
+    const size_t e = c->esz, nh = (size_t)B * H * S_pad * 64, nout = (size_t)B * S * H * 64, nguard = (size_t)ATTN_GUARD_ROWS * H * 64 * e;
     DevScope mem;
     void *dq = nullptr, *dk = nullptr, *dv = nullptr, *dout = nullptr;
     HIPCHK(c, mem.get(&dq, nh * e)); HIPCHK(c, mem.get(&dk, nh * e)); HIPCHK(c, mem.get(&dv, nh * e));
-    HIPCHK(c, mem.get(&dout, (size_t)B * S * H * 64 * e));
-    HIPCHK(c, hipMemset(dq, 0, nh * e)); HIPCHK(c, hipMemset(dk, 0, nh * e)); HIPCHK(c, hipMemset(dv, 0, nh * e));
+    HIPCHK(c, mem.get(&dout, nout * e + nguard));
+    HIPCHK(c, hipMemset(dq, g_test_attn_poison_qpad ? 0xFF : 0, nh * e));   // all-ones is a NaN in bf16, f16 and f32
+    HIPCHK(c, hipMemset(dk, 0, nh * e)); HIPCHK(c, hipMemset(dv, 0, nh * e));
+    HIPCHK(c, hipMemset((char*)dout + nout * e, 0xFF, nguard));
     for (int bh = 0; bh < B * H; ++bh) {   // inputs are [B][H][S][64]
         CWCHK(c, upload_T(c, dq, (size_t)bh * S_pad * 64, q + (size_t)bh * S * 64, (size_t)S * 64));
         CWCHK(c, upload_T(c, dk, (size_t)bh * S_pad * 64, k + (size_t)bh * S * 64, (size_t)S * 64));
         CWCHK(c, upload_T(c, dv, (size_t)bh * S_pad * 64, v + (size_t)bh * S * 64, (size_t)S * 64));
     }
+    CWCHK(c, upload_T(c, dout, 0, out, nout));
     int r = KD(c, cw_launch_attn_encoder, c->bf16, dq, dk, dv, dout, B, H, S, S_pad, c->st);
     if (r == CW_OK) { hipError_t er = hipStreamSynchronize(c->st); if (er != hipSuccess) r = fail(c, CW_ERR_HIP, "test_attention: %s", hipGetErrorString(er)); }
     if (const int reps = cw_sw::cw_switches().test_attn_reps) {   // kernel A/B timing for the profiles (stderr only)
@@ -3464,7 +3475,13 @@ int32_t cw_test_attention(cw_ctx* c, int32_t B, int32_t H, int32_t S, const floa
             hipEventDestroy(e0); hipEventDestroy(e1);
         }
     }
-    if (r == CW_OK) r = download_T(c, dout, 0, out, (size_t)B * S * H * 64);
+    if (r == CW_OK) r = download_T(c, dout, 0, out, nout);
+    if (r == CW_OK) {
+        std::vector<unsigned char> guard(nguard);
+        HIPCHK(c, hipMemcpy(guard.data(), (const char*)dout + nout * e, nguard, hipMemcpyDeviceToHost));
+        for (size_t i = 0; i < nguard; ++i)
+            if (guard[i] != 0xFF) { return fail(c, CW_ERR_STATE, "test_attention: the kernel wrote behind the output (guard byte %zu)", i); }
+    }
     return r;
 }
 

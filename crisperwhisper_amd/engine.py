@@ -586,10 +586,13 @@ class Engine:
                                           int(nks), int(reps), _ptr(out), _ptr(us)))
         return out, (float(us[0]), float(us[1]))
 
-    def test_attention(self, q, k, v):
+    def test_attention(self, q, k, v, out0=None):
+        """cw_test_attention: q / k / v [B][H][S][64] -> [B][S][H*64].  out0: what the output buffer holds before the launch (a
+        sentinel shows every element the kernel did not write); zeros when omitted."""
         q, k, v = (np.ascontiguousarray(t, np.float32) for t in (q, k, v))
         B, H, S, _ = q.shape
-        out = np.zeros((B, S, H * 64), np.float32)
+        out = np.zeros((B, S, H * 64), np.float32) if out0 is None else np.ascontiguousarray(out0, np.float32).copy()
+        assert out.shape == (B, S, H * 64), out.shape
         self._chk(self.lib.cw_test_attention(self.ctx, B, H, S, _ptr(q), _ptr(k), _ptr(v), _ptr(out)))
         return out
 

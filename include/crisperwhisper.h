@@ -384,6 +384,10 @@ int32_t cw_test_gemv(cw_ctx* ctx, int32_t Mb, int32_t N, int32_t K, const float*
  * weights: us[0] GEMM, us[1] finish (microseconds per launch). */
 int32_t cw_test_skinny(cw_ctx* ctx, int32_t mode, int32_t Mb, int32_t N, int32_t K, const float* x, const float* W,
                        const float* bias, int32_t nks, int32_t reps, float* out, float* us);
+/* One launch of the encoder self-attention: q (pre-scaled) / k / v [B][H][S][64] -> out [B][S][H*64].  The rows S .. S_pad-1 of K
+ * and V are zero on the device, as in the engine; those of Q are zero, or NaN after cw_test_set_option("attn_poison_qpad", 1) (the
+ * kernels never use them).  out is in / out like the outputs of cw_test_gemm_epi, and rows behind it are guarded: a write there is
+ * CW_ERR_STATE.  Refused (CW_ERR_INVALID) before anything is launched: B, H or S < 1, a null buffer.                            */
 int32_t cw_test_attention(cw_ctx* ctx, int32_t B, int32_t H, int32_t S, const float* q, const float* k,
                           const float* v, float* out /* [B][S][H*64] */);
 /* One launch of the key-split cross-attention decode kernel (CW_ATT_SPLITS = 6 key splits): q [B][H*64] pre-scaled, k / v
