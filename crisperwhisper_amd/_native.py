@@ -52,6 +52,24 @@ class GemmEpiArgs(C.Structure):
         (n, _I) for n in ("ldo", "T", "S_pad", "H", "d_model")] + [(n, _P) for n in ("out", "out1", "out2")]
 
 
+class FoldArgs(C.Structure):
+    """cw_test_fold_args (include/crisperwhisper.h)"""
+    _fields_ = [(n, _I) for n in ("op", "N", "J", "K")] + [("scale", C.c_float)] + [
+        (n, _P) for n in ("a", "s", "v", "w16", "out16", "c_out", "w_out", "image")]
+
+
+class StackSegArgs(C.Structure):
+    """cw_test_stack_seg (include/crisperwhisper.h)"""
+    _fields_ = [(n, _P) for n in ("x", "bias", "wsum", "resid")] + [(n, _I) for n in ("n_tiles", "nt", "epi", "pstats_blocks")] + [
+        (n, _P) for n in ("out", "out2", "pstats")]
+
+
+class GemvStackArgs(C.Structure):
+    """cw_test_gemv_stack_args (include/crisperwhisper.h)"""
+    _fields_ = [(n, _I) for n in ("Mb", "K", "nt", "wpk", "nseg")] + [("W", _P), ("seg", StackSegArgs * 3), ("zero", _P),
+                                                                     ("zero_n4", _I)]
+
+
 _SIGS = {
     "cw_abi_version": (_I, []),
     "cw_create": (_P, [C.POINTER(ModelDesc), _I]),
@@ -122,6 +140,9 @@ _SIGS = {
     "cw_test_skinny": (_I, [_P, _I, _I, _I, _I, _P, _P, _P, _I, _I, _P, _P]),
     "cw_test_attention": (_I, [_P, _I, _I, _I, _P, _P, _P, _P]),
     "cw_test_cross_attention": (_I, [_P, _I, _I, _I, _I, _P, _P, _P, _I, _P, _P, _P, _P]),
+    "cw_test_cross_attention_fused": (_I, [_P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _I, _P, _P, _I, _P, _P, _P, _P]),
+    "cw_test_fold": (_I, [_P, C.POINTER(FoldArgs)]),
+    "cw_test_gemv_stack": (_I, [_P, C.POINTER(GemvStackArgs)]),
     "cw_test_self_attention": (_I, [_P, _I, _I, _I, _I, _P, _P, _P, _P, _I, _P, _I, _I, _I, _I, _P, _P, _P]),
     "cw_test_beam_state": (_I, [_P, _I, _P, _P, _P]),
     "cw_test_prefill_gemm": (_I, [_P, _I, _I, _I, _I, _P, _P, _P, _P]),

@@ -3543,6 +3543,243 @@ int32_t cw_test_cross_attention(cw_ctx* c, int32_t B, int32_t H, int32_t S, int3
     return r;
 }
 
+// cw_test_cross_attention with the query left to the kernel (the fused out-projection stage of decfuse.hip): qa, qb [B][H*64], qw,
+// qbias [H*64] and the producer's planes pstats [ceil(B / 16)][n_pstats][16][2] replace q.  CrossSplitParams as decode_step fills
+// them behind X1, and its dispatch: e4m3 cache -> cw_launch_attn_cross_split_fp8, else cw_launch_attn_cross_split.
+int32_t cw_test_cross_attention_fused(cw_ctx* c, int32_t B, int32_t H, int32_t S, int32_t kv_div, const float* qa, const float* qb,
+                                      const float* qw, const float* qbias, const float* pstats, int32_t n_pstats, const float* k,
+                                      const float* v, int32_t align_head, float* part_o, float* part_ml, float* align, float* align_ml) {
+    if (!c->bf16) return fail(c, CW_ERR_INVALID, "test_cross_attention_fused: 16-bit engines only");
+    if (B < 1 || B > 64 || H < 1 || H > 1024 || S < 1 || S > 8192 || kv_div < 1 || B % kv_div || align_head < 0 || align_head >= H || n_pstats < 1 || n_pstats > 128)
+        return fail(c, CW_ERR_INVALID, "test_cross_attention_fused: shape B=%d H=%d S=%d kv_div=%d n_pstats=%d", B, H, S, kv_div, n_pstats);
+    if (!qa || !qb || !qw || !qbias || !pstats || !k || !v || !part_o || !part_ml || !align || !align_ml)
+        return fail(c, CW_ERR_INVALID, "test_cross_attention_fused: null buffer");
+    const bool fp8 = c->kv8;
+    if (fp8 && (kv_div > 1 || !KD(c, cw_cross8_is_mfma, S)))   // refused by the launcher: here, in front of the quantiser's launch
+        return fail(c, CW_ERR_INVALID, "test_cross_attention_fused: the e4m3 cache finishes the query at kv_div == 1 in the matrix-core kernel only (kv_div=%d S=%d)", kv_div, S);
+    const int Bk = B / kv_div, D = H * 64, groups = (B + 15) / 16;
+    const size_t nkv = (size_t)Bk * H * S * 64, nps = (size_t)groups * n_pstats * 32;
+    float *dqa = nullptr, *dqb = nullptr, *dqw = nullptr, *dqc = nullptr, *dps = nullptr, *dpo = nullptr, *dml = nullptr, *dal = nullptr,
+          *daml = nullptr, *dkvs = nullptr;
+    void *dk = nullptr, *dv = nullptr, *dk8 = nullptr, *dv8 = nullptr;
+    int *dslot = nullptr, *dpos = nullptr;
+    DevScope mem;
+    HIPCHK(c, mem.get(&dqa, (size_t)B * D * 4)); HIPCHK(c, mem.get(&dqb, (size_t)B * D * 4));
+    HIPCHK(c, mem.get(&dqw, (size_t)D * 4)); HIPCHK(c, mem.get(&dqc, (size_t)D * 4));
+    HIPCHK(c, mem.get(&dps, (nps + 128 * 32) * 4));   // 128 further plane slots of NaN: what a read beyond n_pstats in the last group meets
+    HIPCHK(c, hipMemset(dps + nps, 0xFF, (size_t)128 * 32 * 4));
+    HIPCHK(c, mem.get(&dk, nkv * c->esz)); HIPCHK(c, mem.get(&dv, nkv * c->esz));
+    HIPCHK(c, mem.get(&dpo, (size_t)ATT_NS * B * D * 4)); HIPCHK(c, mem.get(&dml, (size_t)B * H * ATT_NS * 2 * 4));
+    HIPCHK(c, mem.get(&dal, (size_t)B * S * 4)); HIPCHK(c, mem.get(&daml, (size_t)B * ATT_NS * 2 * 4));
+    HIPCHK(c, mem.get(&dslot, (size_t)H * 4)); HIPCHK(c, mem.get(&dpos, (size_t)B * 4));
+    std::vector<int> slot(H, -1); slot[align_head] = 0;
+    HIPCHK(c, hipMemcpy(dslot, slot.data(), (size_t)H * 4, hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemset(dpos, 0, (size_t)B * 4)); HIPCHK(c, hipMemset(dal, 0, (size_t)B * S * 4));
+    HIPCHK(c, hipMemset(daml, 0, (size_t)B * ATT_NS * 2 * 4));
+    HIPCHK(c, hipMemcpy(dqa, qa, (size_t)B * D * 4, hipMemcpyHostToDevice)); HIPCHK(c, hipMemcpy(dqb, qb, (size_t)B * D * 4, hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemcpy(dqw, qw, (size_t)D * 4, hipMemcpyHostToDevice)); HIPCHK(c, hipMemcpy(dqc, qbias, (size_t)D * 4, hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemcpy(dps, pstats, nps * 4, hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemcpy(dpo, part_o, (size_t)ATT_NS * B * D * 4, hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemcpy(dml, part_ml, (size_t)B * H * ATT_NS * 2 * 4, hipMemcpyHostToDevice));
+    CWCHK(c, upload_T(c, dk, 0, k, nkv)); CWCHK(c, upload_T(c, dv, 0, v, nkv));
+    CrossSplitParams p{};
+    p.K = dk; p.V = dv; p.n_keys = S; p.part_o = dpo; p.part_ml = dml; p.align_out = dal; p.align_ml = daml;
+    p.align_slot = dslot; p.pos = dpos; p.n_align = 1; p.align_rows = 1; p.B = B; p.H = H; p.kv_div = kv_div;
+    p.qa = dqa; p.qb = dqb; p.qw = dqw; p.qbias = dqc; p.pstats = dps; p.n_pstats = n_pstats;
+    if (fp8) {
+        HIPCHK(c, mem.get(&dk8, nkv)); HIPCHK(c, mem.get(&dv8, (size_t)Bk * cw_bf16::cw_kv8_v_bytes(H, S)));
+        HIPCHK(c, mem.get(&dkvs, (size_t)Bk * H * 2 * 4));
+        int rq = KD(c, cw_launch_kv_quant_fp8, dk, dv, dk8, dv8, dkvs, Bk, H, S, c->st);
+        if (rq != CW_OK) { return fail(c, rq, "test_cross_attention_fused: quantiser rejected S=%d", S); }
+        p.K = dk8; p.V = dv8; p.kv_scale = dkvs;
+    }
+    int r = fp8 ? KD(c, cw_launch_attn_cross_split_fp8, p, c->st) : KD(c, cw_launch_attn_cross_split, true, p, c->st);
+    if (r != CW_OK) {
+        hipStreamSynchronize(c->st);
+        return fail(c, r, "test_cross_attention_fused: launch rejected (B=%d H=%d S=%d kv_div=%d n_pstats=%d)", B, H, S, kv_div, n_pstats);
+    }
+    { hipError_t er = hipStreamSynchronize(c->st); if (er != hipSuccess) return fail(c, CW_ERR_HIP, "test_cross_attention_fused: %s", hipGetErrorString(er)); }
+    { hipError_t er = hipGetLastError(); if (er != hipSuccess) return fail(c, CW_ERR_HIP, "test_cross_attention_fused: %s", hipGetErrorString(er)); }
+    HIPCHK(c, hipMemcpy(part_o, dpo, (size_t)ATT_NS * B * D * 4, hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(part_ml, dml, (size_t)B * H * ATT_NS * 2 * 4, hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(align, dal, (size_t)B * S * 4, hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(align_ml, daml, (size_t)B * ATT_NS * 2 * 4, hipMemcpyDeviceToHost));
+    return CW_OK;
+}
+
+// One launch of a load-time rewrite (include/crisperwhisper.h): the launchers apply_folds / pack_decoder_weights call, on
+// caller-supplied operands.  f32 operands stay f32 on the device, as the staged checkpoint tensors do; 16-bit outputs start from
+// the caller's contents.
+int32_t cw_test_fold(cw_ctx* c, const cw_test_fold_args* a) {
+    if (!a) return fail(c, CW_ERR_INVALID, "test_fold: null arguments");
+    if (!c->bf16) return fail(c, CW_ERR_INVALID, "test_fold: 16-bit engines only");
+    const int op = a->op, N = a->N, J = a->J, K = a->K;
+    const long long lim = 1ll << 26;
+    if (op < 0 || op > 3) return fail(c, CW_ERR_INVALID, "test_fold: op %d", op);
+    const bool useJ = op == 1 || op == 2, useK = op != 2;
+    if (N < 1 || (useJ && J < 1) || (useK && K < 1) || (useJ && (long long)N * J > lim) || (useK && (long long)N * K > lim) ||
+        (op == 1 && (long long)J * K > lim))
+        return fail(c, CW_ERR_INVALID, "test_fold: op %d shape N=%d J=%d K=%d", op, N, J, K);
+    const size_t e = c->esz;
+    DevScope mem;
+    auto up = [&](float** d, const float* h, size_t n) -> int {
+        HIPCHK(c, mem.get(d, n * 4));
+        HIPCHK(c, hipMemcpy(*d, h, n * 4, hipMemcpyHostToDevice));
+        return CW_OK;
+    };
+    float *dA = nullptr, *ds = nullptr, *dv = nullptr, *dc = nullptr, *dw = nullptr;
+    void *d16 = nullptr, *dimg = nullptr;
+    int r = CW_OK;
+    if (op == 0) {
+        if (!a->a || !a->s || !a->v || !a->out16 || !a->c_out) return fail(c, CW_ERR_INVALID, "test_fold: null buffer (fold_layernorm)");
+        if (K % 4) return fail(c, CW_ERR_INVALID, "test_fold: fold_layernorm takes K %% 4 == 0 (K=%d)", K);
+        CWCHK(c, up(&dA, a->a, (size_t)N * K)); CWCHK(c, up(&ds, a->s, K)); CWCHK(c, up(&dv, a->v, K)); CWCHK(c, up(&dc, a->c_out, N));
+        HIPCHK(c, mem.get(&d16, (size_t)N * K * e)); CWCHK(c, upload_T(c, d16, 0, a->out16, (size_t)N * K));
+        r = KD(c, cw_launch_fold_layernorm, dA, N, K, ds, dv, a->scale, d16, dc, c->st);
+    } else if (op == 1) {
+        if (!a->a || !a->v || !a->out16) return fail(c, CW_ERR_INVALID, "test_fold: null buffer (fold_product)");
+        if (N % 64 || K % 64 || J % 16) return fail(c, CW_ERR_INVALID, "test_fold: fold_product takes N %% 64 == 0, K %% 64 == 0, J %% 16 == 0 (N=%d J=%d K=%d)", N, J, K);
+        CWCHK(c, up(&dA, a->a, (size_t)N * J)); CWCHK(c, up(&dv, a->v, (size_t)J * K));
+        if (a->s) CWCHK(c, up(&ds, a->s, J));
+        HIPCHK(c, mem.get(&d16, (size_t)N * K * e)); CWCHK(c, upload_T(c, d16, 0, a->out16, (size_t)N * K));
+        r = KD(c, cw_launch_fold_product, dA, ds, a->scale, dv, N, J, K, d16, c->st);
+    } else if (op == 2) {
+        if ((!a->c_out && !a->w_out) || (a->c_out && (!a->a || !a->v)) || (a->w_out && !a->w16)) return fail(c, CW_ERR_INVALID, "test_fold: null buffer (fold_rowvec)");
+        if (a->c_out) {
+            CWCHK(c, up(&dA, a->a, (size_t)N * J)); CWCHK(c, up(&dv, a->v, J)); CWCHK(c, up(&dc, a->c_out, N));
+            if (a->s) CWCHK(c, up(&ds, a->s, J));
+        }
+        if (a->w_out) {
+            CWCHK(c, up(&dw, a->w_out, N));
+            HIPCHK(c, mem.get(&d16, (size_t)N * J * e)); CWCHK(c, upload_T(c, d16, 0, a->w16, (size_t)N * J));
+        }
+        r = KD(c, cw_launch_fold_rowvec, dA, ds, a->scale, dv, d16, N, J, dc, dw, c->st);
+    } else {
+        if (!a->a || !a->image) return fail(c, CW_ERR_INVALID, "test_fold: null buffer (wfrag_pack)");
+        if (K % 32) return fail(c, CW_ERR_INVALID, "test_fold: wfrag_pack takes K %% 32 == 0 (K=%d)", K);
+        const size_t ni = KD(c, cw_wfrag_elems, N, K);
+        HIPCHK(c, mem.get(&d16, (size_t)N * K * e)); CWCHK(c, upload_T(c, d16, 0, a->a, (size_t)N * K));
+        HIPCHK(c, mem.get(&dimg, ni * 2)); HIPCHK(c, hipMemcpy(dimg, a->image, ni * 2, hipMemcpyHostToDevice));
+        r = KD(c, cw_launch_wfrag_pack, d16, N, K, dimg, c->st);
+    }
+    if (r != CW_OK) return fail(c, r, "test_fold: launch rejected (op=%d N=%d J=%d K=%d)", op, N, J, K);
+    { hipError_t er = hipStreamSynchronize(c->st); if (er != hipSuccess) return fail(c, CW_ERR_HIP, "test_fold: %s", hipGetErrorString(er)); }
+    { hipError_t er = hipGetLastError(); if (er != hipSuccess) return fail(c, CW_ERR_HIP, "test_fold: %s", hipGetErrorString(er)); }
+    if (op == 0 || op == 1) CWCHK(c, download_T(c, d16, 0, a->out16, (size_t)N * K));
+    if (dc) HIPCHK(c, hipMemcpy(a->c_out, dc, (size_t)N * 4, hipMemcpyDeviceToHost));
+    if (dw) HIPCHK(c, hipMemcpy(a->w_out, dw, (size_t)N * 4, hipMemcpyDeviceToHost));
+    if (op == 3) HIPCHK(c, hipMemcpy(a->image, dimg, KD(c, cw_wfrag_elems, N, K) * 2, hipMemcpyDeviceToHost));
+    return CW_OK;
+}
+
+// One cw_launch_gemv_stack call on caller-supplied operands (include/crisperwhisper.h).  The block count of a segment follows
+// from the launcher's rule for nt (decfuse.hip: cw_launch_gemv_stack / launch_stack_nt), restated here so that every pstats
+// buffer can be sized, and the caller's idea of it checked, before the launch.
+#define STACK_GUARD_FLOATS 1024
+int32_t cw_test_gemv_stack(cw_ctx* c, const cw_test_gemv_stack_args* a) {
+    if (!a) return fail(c, CW_ERR_INVALID, "test_gemv_stack: null arguments");
+    if (!c->bf16) return fail(c, CW_ERR_INVALID, "test_gemv_stack: 16-bit engines only");
+    const int Mb = a->Mb, K = a->K, nseg = a->nseg;
+    if (Mb < 1 || Mb > 64 || K < 128 || K % 128 || K > 1280 || nseg < 1 || nseg > 3 || a->nt < 0 || a->nt > 3 || !a->W)
+        return fail(c, CW_ERR_INVALID, "test_gemv_stack: Mb=%d K=%d nseg=%d nt=%d", Mb, K, nseg, a->nt);
+    int tiles = 0;
+    for (int s = 0; s < nseg; ++s) {
+        const cw_test_stack_seg& g = a->seg[s];
+        if (g.n_tiles < 1 || g.n_tiles > 4096 || g.nt < 0 || g.nt > 3 || g.epi < 0 || g.epi > 2 || !g.x || !g.out)
+            return fail(c, CW_ERR_INVALID, "test_gemv_stack: segment %d n_tiles=%d nt=%d epi=%d", s, g.n_tiles, g.nt, g.epi);
+        if (g.epi == 1 ? (!g.resid || g.wsum) : (g.resid || g.out2 || g.pstats))
+            return fail(c, CW_ERR_INVALID, "test_gemv_stack: segment %d: a buffer its epilogue %d does not use, or no resid", s, g.epi);
+        for (int t = 0; t < s; ++t)
+            if (a->seg[t].out == g.out && (g.epi != 2 || a->seg[t].epi != 2 || a->seg[t].n_tiles != g.n_tiles))
+                return fail(c, CW_ERR_INVALID, "test_gemv_stack: segments %d and %d share `out`", t, s);
+        tiles += g.n_tiles;
+    }
+    // the launcher's nt: 0 = the smallest of 1 .. 3 that keeps the launch within 256 blocks; a segment's own nt where it is smaller
+    int nt = a->nt;
+    if (nt <= 0) {
+        for (nt = 1;; ++nt) {
+            int blocks = 0;
+            for (int s = 0; s < nseg; ++s) {
+                const int snt = a->seg[s].nt > 0 && a->seg[s].nt < nt ? a->seg[s].nt : nt;
+                blocks += (a->seg[s].n_tiles + snt - 1) / snt;
+            }
+            if (blocks <= 256 || nt == 3) break;
+        }
+    }
+    int seg_blocks[3] = {0, 0, 0}, blocks = 0;
+    for (int s = 0; s < nseg; ++s) {
+        const int snt = a->seg[s].nt > 0 && a->seg[s].nt < nt ? a->seg[s].nt : nt;
+        seg_blocks[s] = (a->seg[s].n_tiles + snt - 1) / snt;
+        blocks += seg_blocks[s];
+        if (a->seg[s].pstats && a->seg[s].pstats_blocks != seg_blocks[s])
+            return fail(c, CW_ERR_INVALID, "test_gemv_stack: segment %d has %d blocks, pstats_blocks=%d", s, seg_blocks[s], a->seg[s].pstats_blocks);
+    }
+    if (a->zero && (a->zero_n4 < 1 || (long long)blocks * 256 < a->zero_n4))
+        return fail(c, CW_ERR_INVALID, "test_gemv_stack: zero_n4=%d with %d blocks", a->zero_n4, blocks);
+    const int groups = (Mb + 15) / 16;
+    const size_t e = c->esz, nW = (size_t)tiles * 16 * K;
+    DevScope mem;
+    void *dW = nullptr, *dWp = nullptr;
+    HIPCHK(c, mem.get(&dW, nW * e));
+    CWCHK(c, upload_T(c, dW, 0, a->W, nW));
+    if (a->wpk) {
+        HIPCHK(c, mem.get(&dWp, KD(c, cw_wfrag_elems, tiles * 16, K) * e));
+        CWCHK(c, KD(c, cw_launch_wfrag_pack, dW, tiles * 16, K, dWp, c->st));
+    }
+    auto up = [&](float** d, const float* h, size_t n, size_t guard = 0) -> int {
+        HIPCHK(c, mem.get(d, (n + guard) * 4));
+        HIPCHK(c, hipMemcpy(*d, h, n * 4, hipMemcpyHostToDevice));
+        if (guard) HIPCHK(c, hipMemset(*d + n, 0xFF, guard * 4));
+        return CW_OK;
+    };
+    StackParams sp;
+    memset(&sp, 0, sizeof(sp));
+    sp.W = a->wpk ? dWp : dW; sp.wpk = a->wpk ? 1 : 0; sp.K = K; sp.Mb = Mb; sp.nseg = nseg;
+    float *dout[3] = {}, *dout2[3] = {}, *dps[3] = {}, *dzero = nullptr;
+    int tile0 = 0;
+    for (int s = 0; s < nseg; ++s) {
+        const cw_test_stack_seg& g = a->seg[s];
+        const size_t n = (size_t)g.n_tiles * 16, no = (size_t)Mb * n;
+        float *dx = nullptr, *db = nullptr, *dws = nullptr, *dr = nullptr;
+        CWCHK(c, up(&dx, g.x, (size_t)Mb * K));
+        if (g.bias) CWCHK(c, up(&db, g.bias, n));
+        if (g.wsum) CWCHK(c, up(&dws, g.wsum, n));
+        if (g.resid) CWCHK(c, up(&dr, g.resid, no));
+        for (int t = 0; t < s; ++t) if (a->seg[t].out == g.out) dout[s] = dout[t];   // the two accumulating halves of X2
+        if (!dout[s]) CWCHK(c, up(&dout[s], g.out, no));
+        if (g.out2) CWCHK(c, up(&dout2[s], g.out2, no));
+        if (g.pstats) CWCHK(c, up(&dps[s], g.pstats, (size_t)groups * seg_blocks[s] * 32, STACK_GUARD_FLOATS));
+        StackSeg& q = sp.seg[s];
+        q.x = dx; q.bias = db; q.wsum = dws; q.resid = dr; q.out = dout[s]; q.out2 = dout2[s]; q.pstats = dps[s];
+        q.tile0 = tile0; q.n_tiles = g.n_tiles; q.nt = g.nt; q.epi = g.epi;
+        tile0 += g.n_tiles;
+    }
+    if (a->zero) { CWCHK(c, up(&dzero, a->zero, (size_t)a->zero_n4 * 4)); sp.zero = dzero; sp.zero_n4 = a->zero_n4; }
+    int r = KD(c, cw_launch_gemv_stack, sp, a->nt, c->st);
+    if (r != CW_OK) {
+        hipStreamSynchronize(c->st);
+        return fail(c, r, "test_gemv_stack: launch rejected (Mb=%d K=%d nseg=%d nt=%d)", Mb, K, nseg, a->nt);
+    }
+    { hipError_t er = hipStreamSynchronize(c->st); if (er != hipSuccess) return fail(c, CW_ERR_HIP, "test_gemv_stack: %s", hipGetErrorString(er)); }
+    { hipError_t er = hipGetLastError(); if (er != hipSuccess) return fail(c, CW_ERR_HIP, "test_gemv_stack: %s", hipGetErrorString(er)); }
+    for (int s = 0; s < nseg; ++s) {
+        const cw_test_stack_seg& g = a->seg[s];
+        const size_t no = (size_t)Mb * g.n_tiles * 16;
+        HIPCHK(c, hipMemcpy(g.out, dout[s], no * 4, hipMemcpyDeviceToHost));
+        if (g.out2) HIPCHK(c, hipMemcpy(g.out2, dout2[s], no * 4, hipMemcpyDeviceToHost));
+        if (g.pstats) {
+            const size_t np = (size_t)groups * seg_blocks[s] * 32;
+            HIPCHK(c, hipMemcpy(g.pstats, dps[s], np * 4, hipMemcpyDeviceToHost));
+            std::vector<unsigned int> guard(STACK_GUARD_FLOATS);
+            HIPCHK(c, hipMemcpy(guard.data(), dps[s] + np, (size_t)STACK_GUARD_FLOATS * 4, hipMemcpyDeviceToHost));
+            for (size_t i = 0; i < guard.size(); ++i)
+                if (guard[i] != 0xFFFFFFFFu) { return fail(c, CW_ERR_STATE, "test_gemv_stack: segment %d wrote behind its pstats planes (guard element %zu)", s, i); }
+        }
+    }
+    if (a->zero) HIPCHK(c, hipMemcpy(a->zero, dzero, (size_t)a->zero_n4 * 16, hipMemcpyDeviceToHost));
+    return CW_OK;
+}
+
 // One launch of the decode self-attention dispatcher (cw_launch_attn_decode) on caller-supplied rows, parameters filled the way
 // decode_step fills them: q [B][H*64] (already scaled), k / v [B / kv_div][H][cap][64]; per-row histories (n_keys = 0: pos[b] + 1
 // keys) or a fixed n_keys (the f32 engine's cross-attention; pos[b] = alignment row).  anc [B][cap]: beam-search ancestry.

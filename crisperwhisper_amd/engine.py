@@ -658,6 +658,82 @@ class Engine:
         scale = np.repeat(aw, per, axis=1)[:, :S] / (a_l * aw).sum(-1, keepdims=True)
         return o.reshape(B, H * 64), al.astype(np.float64) * scale
 
+    def test_cross_attention_raw(self, q, k, v, kv_div=1, align_head=0):
+        """cw_test_cross_attention without the host combine: q [B][H*64] -> (part_o [6][B][H*64], part_ml [B][H][6][2])."""
+        q, k, v = (np.ascontiguousarray(t, np.float32) for t in (q, k, v))
+        B, H, S, NS = q.shape[0], k.shape[1], k.shape[2], 6
+        po = np.zeros((NS, B, H * 64), np.float32); ml = np.zeros((B, H, NS, 2), np.float32)
+        al = np.zeros((B, S), np.float32); aml = np.zeros((B, NS, 2), np.float32)
+        self._chk(self.lib.cw_test_cross_attention(self.ctx, B, H, S, int(kv_div), _ptr(q), _ptr(k), _ptr(v), int(align_head),
+                                                   _ptr(po), _ptr(ml), _ptr(al), _ptr(aml)))
+        return po, ml
+
+    def test_cross_attention_fused(self, qa, qb, qw, qbias, pstats, k, v, kv_div=1, align_head=0, n_pstats=None, fill=0.0):
+        """cw_test_cross_attention_fused: qa / qb [B][H*64], qw / qbias [H*64], pstats [ceil(B/16)][n_pstats][16][2], k / v
+        [B / kv_div][H][S][64] -> (part_o [6][B][H*64], part_ml [B][H][6][2]), which hold `fill` before the launch."""
+        qa, qb, qw, qbias, pstats, k, v = (np.ascontiguousarray(t, np.float32) for t in (qa, qb, qw, qbias, pstats, k, v))
+        B, H, S, NS = qa.shape[0], k.shape[1], k.shape[2], 6
+        n_pstats = pstats.shape[1] if n_pstats is None else int(n_pstats)
+        assert qa.shape == qb.shape == (B, H * 64) and qw.shape == qbias.shape == (H * 64,)
+        assert pstats.size == ((B + 15) // 16) * n_pstats * 32 or n_pstats < 1 or n_pstats > 128, pstats.shape
+        po = np.full((NS, B, H * 64), fill, np.float32); ml = np.full((B, H, NS, 2), fill, np.float32)
+        al = np.zeros((B, S), np.float32); aml = np.zeros((B, NS, 2), np.float32)
+        self._chk(self.lib.cw_test_cross_attention_fused(self.ctx, B, H, S, int(kv_div), _ptr(qa), _ptr(qb), _ptr(qw), _ptr(qbias),
+                                                         _ptr(pstats), n_pstats, _ptr(k), _ptr(v), int(align_head), _ptr(po),
+                                                         _ptr(ml), _ptr(al), _ptr(aml)))
+        return po, ml
+
+    def test_fold(self, op, *, n, j=0, k=0, scale=1.0, a=None, s=None, v=None, w16=None, out16=None, c_out=None, w_out=None,
+                  image=None):
+        """One load-time rewrite (cw_test_fold; op 0 fold_layernorm, 1 fold_product, 2 fold_rowvec, 3 wfrag_pack).  The inputs
+        a / s / v / w16 are float32 arrays (or None); out16 / c_out / w_out (float32) and image (uint16) are in / out: they are
+        overwritten in place with what the device holds after the launch."""
+        keep = []
+        args = N.FoldArgs()
+        args.op, args.N, args.J, args.K, args.scale = int(op), int(n), int(j), int(k), float(scale)
+        for name, t in (("a", a), ("s", s), ("v", v), ("w16", w16)):
+            if t is not None:
+                t = np.ascontiguousarray(t, np.float32)
+                keep.append(t)
+                setattr(args, name, _ptr(t))
+        for name, t, dt in (("out16", out16, np.float32), ("c_out", c_out, np.float32), ("w_out", w_out, np.float32),
+                            ("image", image, np.uint16)):
+            if t is not None:
+                assert t.dtype == dt and t.flags["C_CONTIGUOUS"] and t.flags["WRITEABLE"], name
+                setattr(args, name, _ptr(t))
+        self._chk(self.lib.cw_test_fold(self.ctx, C.byref(args)))
+
+    def test_gemv_stack(self, W, segs, *, Mb, K, nt=0, wpk=False, zero=None):
+        """One cw_launch_gemv_stack call (cw_test_gemv_stack).  W [sum n_tiles * 16][K]; segs: up to three dicts with x [Mb][K],
+        n_tiles, epi, optional bias / wsum / resid / nt, and the in / out float32 arrays out, out2, pstats ([groups][blocks][16][2];
+        its second dimension is passed on as the caller's block count), which are overwritten in place; `zero` likewise (a float32
+        array of a multiple of four elements)."""
+        W = np.ascontiguousarray(W, np.float32)
+        keep = [W]
+        a = N.GemvStackArgs()
+        a.Mb, a.K, a.nt, a.wpk, a.nseg, a.W = int(Mb), int(K), int(nt), int(bool(wpk)), len(segs), _ptr(W)
+        assert len(segs) <= 3
+        for i, sg in enumerate(segs):
+            q = a.seg[i]
+            for name in ("x", "bias", "wsum", "resid"):
+                t = sg.get(name)
+                if t is not None:
+                    t = np.ascontiguousarray(t, np.float32)
+                    keep.append(t)
+                    setattr(q, name, _ptr(t))
+            q.n_tiles, q.nt, q.epi = int(sg["n_tiles"]), int(sg.get("nt", 0)), int(sg["epi"])
+            for name in ("out", "out2", "pstats"):
+                t = sg.get(name)
+                if t is not None:
+                    assert t.dtype == np.float32 and t.flags["C_CONTIGUOUS"] and t.flags["WRITEABLE"], name
+                    setattr(q, name, _ptr(t))
+            if sg.get("pstats") is not None:
+                q.pstats_blocks = int(sg.get("pstats_blocks", sg["pstats"].shape[1]))
+        if zero is not None:
+            assert zero.dtype == np.float32 and zero.flags["C_CONTIGUOUS"] and zero.size % 4 == 0
+            a.zero, a.zero_n4 = _ptr(zero), zero.size // 4
+        self._chk(self.lib.cw_test_gemv_stack(self.ctx, C.byref(a)))
+
     def test_self_attention(self, q, k, v, pos, n_keys=0, anc=None, kv_div=1, short_hist=False, out_frag=False,
                             align_head=-1, align_rows=0, align_init=None):
         """One launch of the decode self-attention dispatcher (cw_test_self_attention): q [B][H*64] pre-scaled, k / v

@@ -419,6 +419,71 @@ int32_t cw_test_prefill_align_attention(cw_ctx* ctx, int32_t rows, int32_t n_q, 
 int32_t cw_test_cross_attention(cw_ctx* ctx, int32_t B, int32_t H, int32_t S, int32_t kv_div, const float* q, const float* k,
                                 const float* v, int32_t align_head, float* part_o, float* part_ml, float* align,
                                 float* align_ml);
+/* The same launch and outputs with the query left unfinished, as the fused out-projection stage hands it over (16-bit engines):
+ * qa, qb [B][H*64], qw, qbias [H*64] and pstats [ceil(B / 16)][n_pstats][16][2], the per-block (sum, sum of squares) planes of
+ * gemv_stack_kernel; the kernel finishes q = rstd (qa + qb - mean qw) + qbias itself.  Dispatched as decode_step does: the
+ * context's e4m3 cache (cw_set_option "cross_kv_fp8") -> cw_launch_attn_cross_split_fp8 on the quantised rows, else
+ * cw_launch_attn_cross_split, which takes kv_div == 1 to the split kernel and kv_div > 1 to the beam-search matrix-core kernel.
+ * part_o and part_ml are in / out.  Refused (CW_ERR_INVALID) before anything runs: the f32 engine, a null buffer, B outside
+ * 1 .. 64, H, S or kv_div < 1, B % kv_div, a key split without a key, and whatever the launchers refuse (n_pstats outside
+ * 1 .. 128, or 1 .. 96 under beam search; H > 20 or kv_div > 16; beam search on the e4m3 cache).                            */
+int32_t cw_test_cross_attention_fused(cw_ctx* ctx, int32_t B, int32_t H, int32_t S, int32_t kv_div, const float* qa,
+                                      const float* qb, const float* qw, const float* qbias, const float* pstats,
+                                      int32_t n_pstats, const float* k, const float* v, int32_t align_head, float* part_o,
+                                      float* part_ml, float* align, float* align_ml);
+/* One launch of a load-time rewrite of the 16-bit decode step (16-bit engines), parameters as load_state_dict gives them.
+ *   op 0  cw_launch_fold_layernorm: a = W [N][K], s = gamma [K], v = beta [K] -> out16 [N][K] = T(scale W diag(gamma)),
+ *         c_out [N] += scale W beta
+ *   op 1  cw_launch_fold_product:   a = A [N][J], s [J] or null, v = B [J][K]  -> out16 [N][K] = T((A diag(s) scale) B)
+ *   op 2  cw_launch_fold_rowvec:    c_out [N] = (A diag(s) scale) v from a = A [N][J], s [J] or null, v [J];  w_out [N] = row sums
+ *         of w16 [N][J] rounded to the engine's type.  Either output may be null, and a / s / v with c_out, w16 with w_out
+ *   op 3  cw_launch_wfrag_pack:     a = W [N][K] rounded to the engine's type -> image [ceil(N / 16) * 16 * K], the raw 16-bit
+ *         fragment-major image (pad rows included)
+ * out16, c_out, w_out and image are in / out.  Refused (CW_ERR_INVALID) before any launch: the f32 engine, an unknown op, a size
+ * < 1, a null buffer the op needs, and what the launcher refuses (op 0: K % 4; op 1: N % 64, K % 64, J % 16; op 3: K % 32).     */
+typedef struct cw_test_fold_args {
+    int32_t op, N, J, K;
+    float scale;
+    const float* a;
+    const float* s;
+    const float* v;
+    const float* w16;
+    float* out16;
+    float* c_out;
+    float* w_out;
+    uint16_t* image;
+} cw_test_fold_args;
+int32_t cw_test_fold(cw_ctx* ctx, const cw_test_fold_args* args);
+/* One cw_launch_gemv_stack call (csrc/decfuse.hip; 16-bit engines) with StackParams filled the way decode_step fills them: W
+ * [sum n_tiles * 16][K] rounded to the engine's type (wpk = 1: packed by cw_launch_wfrag_pack first), Mb rows, the launch's nt
+ * (0 = chosen by the launcher) and nseg <= 3 segments whose tile0 is the running sum of the earlier n_tiles.  Per segment: x
+ * [Mb][K], bias / wsum [n_tiles * 16] or null, resid [Mb][n_tiles * 16] (epi 1), n_tiles, nt (0 = the launch's), epi 0 store / 1
+ * residual grid / 2 accumulate, and the in / out buffers out, out2 (epi 1, optional) [Mb][n_tiles * 16] and pstats (epi 1,
+ * optional) [ceil(Mb / 16)][pstats_blocks][16][2], pstats_blocks = ceil(n_tiles / effective nt).  Segments that name the same
+ * `out` share one device buffer (the two accumulating halves of X2).  zero [zero_n4 * 4]: in / out, cleared by the launch.
+ * The device copy of every pstats buffer is followed by guard elements: a write there is CW_ERR_STATE.  Refused (CW_ERR_INVALID)
+ * before any launch: the f32 engine, a null buffer, Mb outside 1 .. 64, K % 128 or K > 1280, nseg outside 1 .. 3, nt outside
+ * 0 .. 3, n_tiles < 1, an unknown epi, epi 1 without resid, wsum / out2 / pstats with an epilogue that does not use them,
+ * shared `out` buffers of different sizes or epilogues other than 2, a pstats_blocks that is not the launch's block count of the
+ * segment, zero_n4 < 1 or beyond 256 elements per block of the launch.                                                        */
+typedef struct cw_test_stack_seg {
+    const float* x;
+    const float* bias;
+    const float* wsum;
+    const float* resid;
+    int32_t n_tiles, nt, epi, pstats_blocks;
+    float* out;
+    float* out2;
+    float* pstats;
+} cw_test_stack_seg;
+typedef struct cw_test_gemv_stack_args {
+    int32_t Mb, K, nt, wpk, nseg;
+    const float* W;
+    cw_test_stack_seg seg[3];
+    float* zero;
+    int32_t zero_n4;
+} cw_test_gemv_stack_args;
+int32_t cw_test_gemv_stack(cw_ctx* ctx, const cw_test_gemv_stack_args* args);
 /* One launch of the decode self-attention dispatcher (cw_launch_attn_decode: attn_decode_kernel / attn_decode_anc_kernel) with
  * the parameters decode_step gives it: q [B][H*64] pre-scaled, k / v [B / kv_div][H][cap][64], pos [B] (n_keys = 0: row b
  * attends over its pos[b] + 1 keys; n_keys > 0: over n_keys keys, pos[b] = alignment row), anc [B][cap] or NULL (key t of row
