@@ -70,6 +70,14 @@ class GemvStackArgs(C.Structure):
                                                                      ("zero_n4", _I)]
 
 
+class GemvEpiArgs(C.Structure):
+    """cw_test_gemv_epi_args (include/crisperwhisper.h)"""
+    _fields_ = [(n, _I) for n in ("op", "epi", "Mb", "N", "K", "ldo", "wpk", "x16", "inplace", "frag_in", "H", "cap", "d_model",
+                                  "n_pstats", "n_stats")] + [
+        (n, _P) for n in ("x", "W", "bias", "ln_g", "ln_b", "resid", "part_o", "part_ml", "pstats", "pos", "cvec_in", "stats_in",
+                          "wsum", "out", "sk", "sv", "y", "stats", "cvec", "nt", "frag_tail_ok")]
+
+
 _SIGS = {
     "cw_abi_version": (_I, []),
     "cw_create": (_P, [C.POINTER(ModelDesc), _I]),
@@ -143,6 +151,7 @@ _SIGS = {
     "cw_test_cross_attention_fused": (_I, [_P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _I, _P, _P, _I, _P, _P, _P, _P]),
     "cw_test_fold": (_I, [_P, C.POINTER(FoldArgs)]),
     "cw_test_gemv_stack": (_I, [_P, C.POINTER(GemvStackArgs)]),
+    "cw_test_gemv_epi": (_I, [_P, C.POINTER(GemvEpiArgs)]),
     "cw_test_self_attention": (_I, [_P, _I, _I, _I, _I, _P, _P, _P, _P, _I, _P, _I, _I, _I, _I, _P, _P, _P]),
     "cw_test_beam_state": (_I, [_P, _I, _P, _P, _P]),
     "cw_test_prefill_gemm": (_I, [_P, _I, _I, _I, _I, _P, _P, _P, _P]),

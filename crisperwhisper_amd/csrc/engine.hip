@@ -3780,6 +3780,238 @@ int32_t cw_test_gemv_stack(cw_ctx* c, const cw_test_gemv_stack_args* a) {
     return CW_OK;
 }
 
+// One call of a launcher of the decode GEMV dispatcher (include/crisperwhisper.h) with the arguments decode_step / gemv_ln give
+// it.  Every device output is followed by GEMV_EPI_GUARD bytes of 0xFF; fragment-major outputs are filled with 0xA5 bytes in their
+// pad rows.  The scratch and every fragment-major operand hold 64 rows: gemv_mt_kernel's row-group blocks request the row tiles of
+// both groups whatever Mb is (as decode_step's d_xfrag does).
+#define GEMV_EPI_GUARD 4096
+int32_t cw_test_gemv_epi(cw_ctx* c, const cw_test_gemv_epi_args* a) {
+    if (!a) return fail(c, CW_ERR_INVALID, "test_gemv_epi: null arguments");
+    const int op = a->op, epi = a->epi, Mb = a->Mb, N = a->N, K = a->K;
+    if (op < 0 || op > 3) return fail(c, CW_ERR_INVALID, "test_gemv_epi: op %d", op);
+    const bool comb = a->part_o || a->part_ml;
+    if (!c->bf16 && !(op == 0 && (epi == EPI_RESID_F32 || epi == EPI_STORE_F32 || epi == EPI_QKV_CACHE || epi == EPI_GELU_F32) && !a->ln_g &&
+                      !a->ln_b && !comb && !a->wpk && !a->x16 && !a->frag_in))
+        return fail(c, CW_ERR_INVALID, "test_gemv_epi: the f32 engine takes op 0 with epi 2 / 5 / 6 / 7 on plain rows and row-major weights only");
+    if (Mb < 1 || N < 1 || K < 1) return fail(c, CW_ERR_INVALID, "test_gemv_epi: size < 1 (Mb=%d N=%d K=%d)", Mb, N, K);
+    if (Mb > 64) return fail(c, CW_ERR_INVALID, "test_gemv_epi: Mb=%d > 64", Mb);
+    if (K % 128 || K > 5120) return fail(c, CW_ERR_INVALID, "test_gemv_epi: K=%d is not a multiple of 128 up to 5120", K);
+    if (N > 65536) return fail(c, CW_ERR_INVALID, "test_gemv_epi: N=%d > 65536", N);
+    if (op != 1 && !a->W) return fail(c, CW_ERR_INVALID, "test_gemv_epi: null buffer W");
+    const int H = a->H, cap = a->cap, dm = a->d_model;
+    int ldo = a->ldo;
+    if (comb || op == 1) {
+        if (!a->part_o || !a->part_ml) return fail(c, CW_ERR_INVALID, "test_gemv_epi: null buffer (a combine takes part_o and part_ml)");
+        if (H < 1 || H * 64 != K) return fail(c, CW_ERR_INVALID, "test_gemv_epi: combine with H=%d, H * 64 != K=%d", H, K);
+        if (a->ln_g) return fail(c, CW_ERR_INVALID, "test_gemv_epi: combine in front of a LayerNorm");
+    }
+    if (!a->out) return fail(c, CW_ERR_INVALID, "test_gemv_epi: null buffer out");
+    if (op == 0) {
+        if (epi != EPI_GELU && epi != EPI_RESID_F32 && epi != EPI_STORE_F32 && epi != EPI_QKV_CACHE && epi != EPI_GELU_F32 && epi != EPI_GELU_FRAG)
+            return fail(c, CW_ERR_INVALID, "test_gemv_epi: epi %d", epi);
+        if (!comb && !a->x) return fail(c, CW_ERR_INVALID, "test_gemv_epi: null buffer x");
+        if (a->ln_b && !a->ln_g) return fail(c, CW_ERR_INVALID, "test_gemv_epi: ln_b without ln_g");
+        if (epi != EPI_RESID_F32 && (a->inplace || a->resid)) return fail(c, CW_ERR_INVALID, "test_gemv_epi: inplace / resid with epi %d", epi);
+        if (epi == EPI_RESID_F32 && !a->inplace && !a->resid) return fail(c, CW_ERR_INVALID, "test_gemv_epi: null buffer resid");
+        if (epi == EPI_RESID_F32 && a->inplace && a->resid) return fail(c, CW_ERR_INVALID, "test_gemv_epi: inplace with a separate resid");
+        if (a->frag_in && comb) return fail(c, CW_ERR_INVALID, "test_gemv_epi: frag_in with a combine");
+        if (epi == EPI_QKV_CACHE) {
+            if (dm < 64 || dm % 64) return fail(c, CW_ERR_INVALID, "test_gemv_epi: d_model=%d %% 64", dm);
+            if (N != 3 * dm) return fail(c, CW_ERR_INVALID, "test_gemv_epi: N=%d != 3 d_model=%d", N, 3 * dm);
+            if (H * 64 != dm) return fail(c, CW_ERR_INVALID, "test_gemv_epi: H=%d, H * 64 != d_model=%d", H, dm);
+            if (cap < 1 || cap > 8192) return fail(c, CW_ERR_INVALID, "test_gemv_epi: cap=%d", cap);
+            if (!a->pos || !a->sk || !a->sv) return fail(c, CW_ERR_INVALID, "test_gemv_epi: null buffer (epi 6 takes pos, sk and sv)");
+            for (int b = 0; b < Mb; ++b)
+                if (a->pos[b] < 0 || a->pos[b] >= cap) return fail(c, CW_ERR_INVALID, "test_gemv_epi: pos[%d]=%d outside [0, cap=%d)", b, a->pos[b], cap);
+            ldo = dm;
+        } else if (epi == EPI_GELU_FRAG) {
+            if (ldo != N) return fail(c, CW_ERR_INVALID, "test_gemv_epi: epi 8 takes ldo == N (ldo=%d N=%d)", ldo, N);
+        } else if (ldo < N) return fail(c, CW_ERR_INVALID, "test_gemv_epi: ldo=%d < N=%d", ldo, N);
+    } else if (op == 1) {
+        if (a->pstats ? (!a->cvec || a->n_pstats < 1 || a->n_pstats > 256) : (a->cvec != nullptr))
+            return fail(c, CW_ERR_INVALID, "test_gemv_epi: op 1 takes pstats with n_pstats in 1 .. 256 (%d) and cvec, or neither", a->n_pstats);
+    } else if (op == 2) {
+        if (!a->x || !a->cvec_in || !a->y || !a->stats) return fail(c, CW_ERR_INVALID, "test_gemv_epi: null buffer (op 2 takes x, cvec_in, y and stats)");
+    } else {
+        if (!a->x || !a->stats_in || !a->wsum) return fail(c, CW_ERR_INVALID, "test_gemv_epi: null buffer (op 3 takes x, stats_in and wsum)");
+        if (a->n_stats < 1) return fail(c, CW_ERR_INVALID, "test_gemv_epi: n_stats=%d < 1", a->n_stats);
+    }
+    const size_t e = c->esz;
+    const int Mpad = (Mb + 15) & ~15;
+    DevScope mem;
+    struct Guarded { void* d; size_t bytes; const char* name; };
+    std::vector<Guarded> guards;
+    auto getg = [&](void** d, size_t bytes, const char* name) -> int {   // an output: guard bytes behind it
+        HIPCHK(c, mem.get(d, bytes + GEMV_EPI_GUARD));
+        HIPCHK(c, hipMemset((char*)*d + bytes, 0xFF, GEMV_EPI_GUARD));
+        guards.push_back({*d, bytes, name});
+        return CW_OK;
+    };
+    auto upf = [&](float** d, const float* h, size_t n) -> int {
+        HIPCHK(c, mem.get(d, n * 4));
+        HIPCHK(c, hipMemcpy(*d, h, n * 4, hipMemcpyHostToDevice));
+        return CW_OK;
+    };
+    auto to16 = [&](float v) -> bf16_t { return c->f16 ? cw_host_f32_to_f16(v) : cw_host_f32_to_bf16(v); };
+    auto from16 = [&](bf16_t v) -> float { return c->f16 ? cw_host_f16_to_f32(v) : cw_host_bf16_to_f32(v); };
+    // host rows [rows][cols] -> a fragment-major 16-bit image of `prows` rows, every other element `fill`
+    auto frag_up = [&](void* d, const float* h, int rows, int cols, int prows, unsigned short fill) -> int {
+        std::vector<bf16_t> img((size_t)prows * cols, (bf16_t)fill);
+        for (int m = 0; m < rows; ++m)
+            for (int k = 0; k < cols; ++k) img[frag_index(m, k, cols)] = to16(h[(size_t)m * cols + k]);
+        HIPCHK(c, hipMemcpy(d, img.data(), img.size() * 2, hipMemcpyHostToDevice));
+        return CW_OK;
+    };
+    bool tail_ok = true;
+    auto frag_down = [&](const void* d, float* h, int rows, int cols, int prows, unsigned short fill) -> int {
+        std::vector<bf16_t> img((size_t)prows * cols);
+        HIPCHK(c, hipMemcpy(img.data(), d, img.size() * 2, hipMemcpyDeviceToHost));
+        for (int m = 0; m < prows; ++m)
+            for (int k = 0; k < cols; ++k) {
+                const bf16_t v = img[frag_index(m, k, cols)];
+                if (m < rows) h[(size_t)m * cols + k] = from16(v);
+                else if (v != (bf16_t)fill) tail_ok = false;
+            }
+        return CW_OK;
+    };
+    // weights
+    void *dW = nullptr, *dWp = nullptr;
+    if (op != 1) {
+        HIPCHK(c, mem.get(&dW, (size_t)N * K * e));
+        CWCHK(c, upload_T(c, dW, 0, a->W, (size_t)N * K));
+        if (a->wpk) {
+            HIPCHK(c, mem.get(&dWp, KD(c, cw_wfrag_elems, N, K) * e));
+            CWCHK(c, KD(c, cw_launch_wfrag_pack, dW, N, K, dWp, c->st));
+        }
+    }
+    const void* Wd = a->wpk ? dWp : dW;
+    float *dbias = nullptr, *dg = nullptr, *dbeta = nullptr, *dpo = nullptr, *dml = nullptr;
+    if (a->bias && op != 1) CWCHK(c, upf(&dbias, a->bias, (size_t)N));
+    if (comb || op == 1) {
+        CWCHK(c, upf(&dpo, a->part_o, (size_t)ATT_NS * Mb * K));
+        CWCHK(c, upf(&dml, a->part_ml, (size_t)Mb * H * ATT_NS * 2));
+    }
+    void* dscr = nullptr;                                       // 64 fragment-major rows
+    HIPCHK(c, mem.get(&dscr, (size_t)64 * K * 2));
+    HIPCHK(c, hipMemset(dscr, 0, (size_t)64 * K * 2));
+    int r = CW_OK;
+    void *dout = nullptr, *dsk = nullptr, *dsv = nullptr, *dy = nullptr;
+    float *dstats = nullptr, *dcvec = nullptr;
+    int own_nt = 0, slots = 0;
+    size_t ncache = 0;
+    const unsigned short FILL = 0xA5A5;
+    if (op == 0) {
+        float* dx = nullptr; void* dx16 = nullptr;
+        if (!comb) {
+            if (a->frag_in) CWCHK(c, frag_up(dscr, a->x, Mb, K, 64, 0));
+            else if (a->x16) { HIPCHK(c, mem.get(&dx16, (size_t)Mb * K * 2)); CWCHK(c, upload_T(c, dx16, 0, a->x, (size_t)Mb * K)); }
+            else CWCHK(c, upf(&dx, a->x, (size_t)Mb * K));
+        }
+        if (a->ln_g) CWCHK(c, upf(&dg, a->ln_g, (size_t)K));
+        if (a->ln_b) CWCHK(c, upf(&dbeta, a->ln_b, (size_t)K));
+        EpiParams ep = epi0();
+        ep.bias = dbias; ep.ldo = a->ldo; ep.x16 = a->x16 ? 1 : 0;
+        if (epi == EPI_GELU) {
+            CWCHK(c, getg(&dout, (size_t)Mb * ldo * 2, "out"));
+            CWCHK(c, upload_T(c, dout, 0, a->out, (size_t)Mb * ldo));
+            ep.out = dout;
+        } else if (epi == EPI_GELU_FRAG) {
+            CWCHK(c, getg(&dout, (size_t)Mpad * N * 2, "out"));
+            CWCHK(c, frag_up(dout, a->out, Mb, N, Mpad, FILL));
+            ep.out = dout;
+        } else {
+            CWCHK(c, getg(&dout, (size_t)Mb * ldo * 4, "out"));
+            HIPCHK(c, hipMemcpy(dout, a->out, (size_t)Mb * ldo * 4, hipMemcpyHostToDevice));
+            ep.outf = (float*)dout;
+        }
+        if (epi == EPI_RESID_F32) {
+            if (a->inplace) ep.resid = (const float*)dout;
+            else { float* dr = nullptr; CWCHK(c, upf(&dr, a->resid, (size_t)Mb * ldo)); ep.resid = dr; }
+        }
+        if (epi == EPI_QKV_CACHE) {
+            int* dpos = nullptr;
+            ncache = (size_t)Mb * H * cap * 64;
+            HIPCHK(c, mem.get(&dpos, (size_t)Mb * 4));
+            HIPCHK(c, hipMemcpy(dpos, a->pos, (size_t)Mb * 4, hipMemcpyHostToDevice));
+            CWCHK(c, getg(&dsk, ncache * e, "sk")); CWCHK(c, getg(&dsv, ncache * e, "sv"));
+            CWCHK(c, upload_T(c, dsk, 0, a->sk, ncache)); CWCHK(c, upload_T(c, dsv, 0, a->sv, ncache));
+            ep.out1 = dsk; ep.out2 = dsv; ep.H = H; ep.S_pad = cap; ep.d_model = dm; ep.row_pos = dpos; ep.ldo = 0;
+        }
+        CombineParams cb{dml, H, Mb * K, nullptr, 0, nullptr};
+        const float* xin = comb ? dpo : a->frag_in ? nullptr : a->x16 ? (const float*)dx16 : dx;
+        const bool wpacked = c->bf16 && a->wpk;
+        r = KD(c, cw_launch_gemv, c->bf16, epi, xin, Mb, K, Wd, N, dg, dbeta, ep, c->st, comb ? &cb : nullptr,
+               (Mb <= 16 || wpacked) ? dscr : nullptr, wpacked);
+    } else if (op == 1) {
+        CWCHK(c, getg(&dout, (size_t)Mpad * K * 2, "out"));
+        CWCHK(c, frag_up(dout, a->out, Mb, K, Mpad, FILL));
+        CombineParams cb{dml, H, Mb * K, nullptr, 0, nullptr};
+        if (a->pstats) {
+            float* dps = nullptr;
+            CWCHK(c, upf(&dps, a->pstats, (size_t)(Mpad / 16) * a->n_pstats * 32));
+            CWCHK(c, getg((void**)&dcvec, (size_t)Mb * 4, "cvec"));
+            HIPCHK(c, hipMemcpy(dcvec, a->cvec, (size_t)Mb * 4, hipMemcpyHostToDevice));
+            cb.pstats = dps; cb.n_pstats = a->n_pstats; cb.cvec_out = dcvec;
+        }
+        r = KD(c, cw_launch_rows_combine, dpo, Mb, K, cb, dout, c->st);
+    } else if (op == 2) {
+        own_nt = KD(c, cw_gemv_own_nt, N);
+        slots = (N + 16 * own_nt - 1) / (16 * own_nt);
+        if (a->nt) *a->nt = own_nt;
+        float* dcin = nullptr;
+        CWCHK(c, frag_up(dscr, a->x, Mb, K, 64, 0));
+        CWCHK(c, upf(&dcin, a->cvec_in, (size_t)Mb));
+        CWCHK(c, getg(&dout, (size_t)Mb * N * 4, "out"));
+        HIPCHK(c, hipMemcpy(dout, a->out, (size_t)Mb * N * 4, hipMemcpyHostToDevice));
+        CWCHK(c, getg(&dy, (size_t)Mpad * N * 2, "y"));
+        CWCHK(c, frag_up(dy, a->y, Mb, N, Mpad, FILL));
+        CWCHK(c, getg((void**)&dstats, (size_t)slots * 128 * 4, "stats"));
+        HIPCHK(c, hipMemcpy(dstats, a->stats, (size_t)slots * 128 * 4, hipMemcpyHostToDevice));
+        EpiParams ep = epi0();
+        ep.outf = (float*)dout; ep.resid = (const float*)dout; ep.bias = dbias; ep.ldo = N;
+        r = KD(c, cw_launch_gemv_own, dscr, Mb, K, Wd, N, ep, dcin, dy, dstats, c->st, a->wpk != 0);
+    } else {
+        float *dsi = nullptr, *dws = nullptr;
+        CWCHK(c, frag_up(dscr, a->x, Mb, K, 64, 0));
+        CWCHK(c, upf(&dsi, a->stats_in, (size_t)a->n_stats * 128));
+        CWCHK(c, upf(&dws, a->wsum, (size_t)N));
+        CWCHK(c, getg(&dout, (size_t)Mpad * N * 2, "out"));
+        CWCHK(c, frag_up(dout, a->out, Mb, N, Mpad, FILL));
+        EpiParams ep = epi0();
+        ep.out = dout; ep.bias = dbias; ep.ldo = N;
+        r = KD(c, cw_launch_gemv_lna, dscr, Mb, K, Wd, N, ep, dsi, a->n_stats, dws, c->st, a->wpk != 0);
+    }
+    if (r != CW_OK) {
+        hipStreamSynchronize(c->st);
+        return fail(c, r, "test_gemv_epi: launch rejected (op=%d epi=%d Mb=%d N=%d K=%d wpk=%d)", op, epi, Mb, N, K, a->wpk);
+    }
+    { hipError_t er = hipStreamSynchronize(c->st); if (er != hipSuccess) return fail(c, CW_ERR_HIP, "test_gemv_epi: %s", hipGetErrorString(er)); }
+    { hipError_t er = hipGetLastError(); if (er != hipSuccess) return fail(c, CW_ERR_HIP, "test_gemv_epi: %s", hipGetErrorString(er)); }
+    if (op == 0) {
+        if (epi == EPI_GELU) CWCHK(c, download_T(c, dout, 0, a->out, (size_t)Mb * ldo));
+        else if (epi == EPI_GELU_FRAG) CWCHK(c, frag_down(dout, a->out, Mb, N, Mpad, FILL));
+        else HIPCHK(c, hipMemcpy(a->out, dout, (size_t)Mb * ldo * 4, hipMemcpyDeviceToHost));
+        if (epi == EPI_QKV_CACHE) { CWCHK(c, download_T(c, dsk, 0, a->sk, ncache)); CWCHK(c, download_T(c, dsv, 0, a->sv, ncache)); }
+    } else if (op == 1) {
+        CWCHK(c, frag_down(dout, a->out, Mb, K, Mpad, FILL));
+        if (dcvec) HIPCHK(c, hipMemcpy(a->cvec, dcvec, (size_t)Mb * 4, hipMemcpyDeviceToHost));
+    } else if (op == 2) {
+        HIPCHK(c, hipMemcpy(a->out, dout, (size_t)Mb * N * 4, hipMemcpyDeviceToHost));
+        CWCHK(c, frag_down(dy, a->y, Mb, N, Mpad, FILL));
+        HIPCHK(c, hipMemcpy(a->stats, dstats, (size_t)slots * 128 * 4, hipMemcpyDeviceToHost));
+    } else {
+        CWCHK(c, frag_down(dout, a->out, Mb, N, Mpad, FILL));
+    }
+    if (a->frag_tail_ok) *a->frag_tail_ok = tail_ok ? 1 : 0;
+    std::vector<unsigned char> gb(GEMV_EPI_GUARD);
+    for (const Guarded& g : guards) {
+        HIPCHK(c, hipMemcpy(gb.data(), (const char*)g.d + g.bytes, GEMV_EPI_GUARD, hipMemcpyDeviceToHost));
+        for (size_t i = 0; i < gb.size(); ++i)
+            if (gb[i] != 0xFF) return fail(c, CW_ERR_STATE, "test_gemv_epi: the launch wrote behind `%s` (guard byte %zu)", g.name, i);
+    }
+    return CW_OK;
+}
+
 // One launch of the decode self-attention dispatcher (cw_launch_attn_decode) on caller-supplied rows, parameters filled the way
 // decode_step fills them: q [B][H*64] (already scaled), k / v [B / kv_div][H][cap][64]; per-row histories (n_keys = 0: pos[b] + 1
 // keys) or a fixed n_keys (the f32 engine's cross-attention; pos[b] = alignment row).  anc [B][cap]: beam-search ancestry.

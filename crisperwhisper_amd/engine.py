@@ -14,6 +14,8 @@ import numpy as np
 
 from . import _native as N
 
+_GemvEpiArgs = N.GemvEpiArgs     # (test_gemv_epi has a parameter named N)
+
 
 def _ptr(a: Optional[np.ndarray]):
     return None if a is None else a.ctypes.data_as(C.c_void_p)
@@ -733,6 +735,36 @@ class Engine:
             assert zero.dtype == np.float32 and zero.flags["C_CONTIGUOUS"] and zero.size % 4 == 0
             a.zero, a.zero_n4 = _ptr(zero), zero.size // 4
         self._chk(self.lib.cw_test_gemv_stack(self.ctx, C.byref(a)))
+
+    def test_gemv_epi(self, *, op=0, epi=0, Mb, N, K, W=None, ldo=None, wpk=False, x16=False, inplace=False, frag_in=False, H=0, cap=0,
+                      d_model=0, x=None, bias=None, ln_g=None, ln_b=None, resid=None, part_o=None, part_ml=None, pstats=None,
+                      n_pstats=0, pos=None, cvec_in=None, stats_in=None, n_stats=0, wsum=None, out=None, sk=None, sv=None, y=None,
+                      stats=None, cvec=None):
+        """One call of a launcher of the decode GEMV dispatcher (cw_test_gemv_epi; include/crisperwhisper.h describes the forms).
+        The in / out float32 arrays out, sk, sv, y, stats and cvec are overwritten in place.  Returns {"nt", "frag_tail_ok"}."""
+        a = _GemvEpiArgs()
+        keep = []
+        a.op, a.epi, a.Mb, a.N, a.K = int(op), int(epi), int(Mb), int(N), int(K)
+        a.ldo = int(N if ldo is None else ldo)
+        a.wpk, a.x16, a.inplace, a.frag_in = int(bool(wpk)), int(bool(x16)), int(bool(inplace)), int(bool(frag_in))
+        a.H, a.cap, a.d_model, a.n_pstats, a.n_stats = int(H), int(cap), int(d_model), int(n_pstats), int(n_stats)
+        for name, t in (("x", x), ("W", W), ("bias", bias), ("ln_g", ln_g), ("ln_b", ln_b), ("resid", resid), ("part_o", part_o),
+                        ("part_ml", part_ml), ("pstats", pstats), ("cvec_in", cvec_in), ("stats_in", stats_in), ("wsum", wsum)):
+            if t is not None:
+                t = np.ascontiguousarray(t, np.float32)
+                keep.append(t)
+                setattr(a, name, _ptr(t))
+        if pos is not None:
+            pos = _i32(pos)
+            a.pos = _ptr(pos)
+        for name, t in (("out", out), ("sk", sk), ("sv", sv), ("y", y), ("stats", stats), ("cvec", cvec)):
+            if t is not None:
+                assert t.dtype == np.float32 and t.flags["C_CONTIGUOUS"] and t.flags["WRITEABLE"], name
+                setattr(a, name, _ptr(t))
+        nt, tail = np.zeros(1, np.int32), np.zeros(1, np.int32)
+        a.nt, a.frag_tail_ok = _ptr(nt), _ptr(tail)
+        self._chk(self.lib.cw_test_gemv_epi(self.ctx, C.byref(a)))
+        return {"nt": int(nt[0]), "frag_tail_ok": bool(tail[0])}
 
     def test_self_attention(self, q, k, v, pos, n_keys=0, anc=None, kv_div=1, short_hist=False, out_frag=False,
                             align_head=-1, align_rows=0, align_init=None):

@@ -484,6 +484,57 @@ typedef struct cw_test_gemv_stack_args {
     int32_t zero_n4;
 } cw_test_gemv_stack_args;
 int32_t cw_test_gemv_stack(cw_ctx* ctx, const cw_test_gemv_stack_args* args);
+/* One call of a launcher of the decode GEMV dispatcher (csrc/gemm.hip) with the arguments decode_step / gemv_ln give it.  Host f32
+ * in / out; W and every 16-bit operand are rounded to the context's type; wpk = 1: W is packed by cw_launch_wfrag_pack first.
+ *   op 0  cw_launch_gemv: x [Mb][K] (x16 = 1: uploaded as 16-bit rows), W [N][K], bias [N] or null, ln_g / ln_b [K] (both null: no
+ *         LayerNorm; ln_b null: the folded form).  epi 1: out [Mb][ldo] 16-bit GELU rows;  2: out [Mb][ldo] = resid + grid(acc +
+ *         bias), resid [Mb][ldo], or inplace = 1: out holds the residual on entry and resid == outf (the K-split form);  5 / 7: out
+ *         [Mb][ldo] f32 store / GELU;  6: N = 3 d_model, out = q [Mb][d_model], k / v appended to sk / sv [Mb][H][cap][64] at row
+ *         pos[b];  8: out [Mb][N] = the 16-bit fragment-major GELU rows (ldo = N), returned un-permuted.  part_o [6][Mb][K] + part_ml
+ *         [Mb][H][6][2]: the activations are the combination of the key-split partials (plane = Mb K; x unused).  frag_in = 1: the
+ *         producer form -- the hook writes the rounded rows of x fragment-major (frag_index) into the scratch and passes x = null.
+ *         The scratch (64 rows) is the hook's own and is passed exactly when gemv_ln passes one (Mb <= 16 or wpk).
+ *   op 1  cw_launch_rows_combine: part_o, part_ml -> out [Mb][K], the 16-bit fragment-major rows un-permuted; with pstats
+ *         [ceil(Mb / 16)][n_pstats][16][2] also cvec [Mb] = the row sums of the planes' first components over K.
+ *   op 2  cw_launch_gemv_own: x = the rounded activation rows a [Mb][K] (written fragment-major by the hook), W [N][K], bias, out
+ *         [Mb][N] the residual in place, cvec_in [Mb] -> out, y [Mb][N] (the 16-bit fragment-major rows x_new - c un-permuted) and
+ *         stats [N / (16 nt)][64][2] per-block (sum y, sum y^2); nt, the launcher's cw_gemv_own_nt, is reported in *nt.
+ *   op 3  cw_launch_gemv_lna: x = y [Mb][K] rounded (fragment-major by the hook), stats_in [n_stats][64][2], wsum [N], W [N][K], bias
+ *         -> out [Mb][N], the 16-bit fragment-major GELU rows un-permuted.
+ * Every output (out, sk, sv, y, stats, cvec) is in / out: uploaded before the launch and downloaded after it, so a sentinel marks
+ * what the kernel left alone.  *frag_tail_ok = 1 when the pad rows Mb .. of every fragment-major output kept their fill.  Every
+ * device output is followed by guard elements: a write there is CW_ERR_STATE.  Refused (CW_ERR_INVALID) before the launcher is
+ * called: the f32 engine for everything but op 0 with epi 2 / 5 / 6 / 7 and no LayerNorm / combine / wpk / x16 / frag_in, an unknown
+ * op or epi, a null buffer the form needs, a size < 1, Mb > 64, K % 128 or K > 5120, N > 65536, ldo < N (epi 8: ldo != N), a combine
+ * with H 64 != K or in front of a LayerNorm, inplace or resid with an epilogue other than 2, epi 6 with d_model % 64, N != 3
+ * d_model, H 64 != d_model, cap < 1 or a pos[b] outside [0, cap), n_pstats outside 1 .. 256, n_stats < 1; and whatever the launcher
+ * itself refuses, reported as its refusal.                                                                                       */
+typedef struct cw_test_gemv_epi_args {
+    int32_t op, epi, Mb, N, K, ldo, wpk, x16, inplace, frag_in;
+    int32_t H, cap, d_model, n_pstats, n_stats;
+    const float* x;
+    const float* W;
+    const float* bias;
+    const float* ln_g;
+    const float* ln_b;
+    const float* resid;
+    const float* part_o;
+    const float* part_ml;
+    const float* pstats;
+    const int32_t* pos;
+    const float* cvec_in;
+    const float* stats_in;
+    const float* wsum;
+    float* out;
+    float* sk;
+    float* sv;
+    float* y;
+    float* stats;
+    float* cvec;
+    int32_t* nt;           /* out (op 2), may be null */
+    int32_t* frag_tail_ok; /* out, may be null */
+} cw_test_gemv_epi_args;
+int32_t cw_test_gemv_epi(cw_ctx* ctx, const cw_test_gemv_epi_args* args);
 /* One launch of the decode self-attention dispatcher (cw_launch_attn_decode: attn_decode_kernel / attn_decode_anc_kernel) with
  * the parameters decode_step gives it: q [B][H*64] pre-scaled, k / v [B / kv_div][H][cap][64], pos [B] (n_keys = 0: row b
  * attends over its pos[b] + 1 keys; n_keys > 0: over n_keys keys, pos[b] = alignment row), anc [B][cap] or NULL (key t of row
