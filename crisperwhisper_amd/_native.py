@@ -99,6 +99,9 @@ _SIGS = {
     "cw_decode_rows": (_I, [_P, _I, _P, _I, _I, _I, _P, _P, _P, _P, _P]),
     "cw_no_speech_probs": (_I, [_P, _I, _I, _P]),
     "cw_get_avg_logprobs": (_I, [_P, _P, _I]),
+    "cw_set_token_logprobs": (_I, [_P, _I]),
+    "cw_get_token_logprobs": (_I, [_P, _P, _I]),
+    "cw_get_transcribe_token_logprobs": (_I, [_P, _P, _I, _I]),
     "cw_get_logits": (_I, [_P, _P, _I]),
     "cw_set_logits_capture": (_I, [_P, _P, _I]),
     "cw_get_alignment": (_I, [_P, _P, _I, _I]),
@@ -129,6 +132,7 @@ _SIGS = {
     "cw_beam_host_new": (_P, [_I, _I, _I, _I, _I, _I, _I, C.c_double, _I, _P]),
     "cw_beam_host_step": (_I, [_P, _P, _P, _P, _P]),
     "cw_beam_host_result": (_I, [_P, _P, _P, _P]),
+    "cw_beam_host_token_logprobs": (_I, [_P, _P]),
     "cw_beam_host_free": (None, [_P]),
     "cw_collate_set_mode": (_I, [_P, _I]),
     "cw_collate_feed": (_I, [_P, _P, _I, _P, _I, _I, C.c_double, C.c_double, C.c_double]),
@@ -161,6 +165,7 @@ _SIGS = {
     "cw_time_score_head": (_I, [_P, _I, _I, _I, _P]),
     "cw_test_sample": (_I, [_P, _I, _P, _P, _I, _I, _I, _I, _P]),
     "cw_test_sample_seeded": (_I, [_P, _I, _P, _P, _I, _I, _I, _I, C.c_float, C.c_uint64, _P, _P]),
+    "cw_test_sample_logprobs": (_I, [_P, _I, _P, _P, _I, _I, _I, _I, C.c_float, C.c_uint64, _P, _P, _P, _P]),
     "cw_stage_times": (_I, [_P, _P, _P, _I]),
     "cw_time_kernel": (_I, [_P, _I, _I, _I, _P, _P]),
     "cw_time_decode_stage": (_I, [_P, _I, _I, _I, _P, _P, _P, _P]),

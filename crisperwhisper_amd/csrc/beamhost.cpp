@@ -29,6 +29,7 @@ struct cw_beam_host {
     int gen_cap;                                   // max_length - n_prompt
     std::vector<int64_t> running_seq, sequences;  // [B][K][max_length]
     std::vector<int32_t> running_bi, beam_indices;  // [B][K][gen_cap]
+    std::vector<float> running_tl, token_lp;       // [B][K][gen_cap] candidate log-probability of every generated token (NaN behind the end)
     std::vector<float> running_scores, beam_scores;  // [B][K]
     std::vector<uint8_t> finished;                 // [B][K]
     std::vector<uint8_t> unsat;                    // [B]
@@ -55,6 +56,8 @@ cw_beam_host* cw_beam_host_new(int32_t n_items, int32_t num_beams, int32_t n_pro
     s->sequences = s->running_seq;
     s->running_bi.assign(BK * s->gen_cap, -1);
     s->beam_indices = s->running_bi;
+    s->running_tl.assign(BK * s->gen_cap, std::numeric_limits<float>::quiet_NaN());
+    s->token_lp = s->running_tl;
     s->running_scores.assign(BK, -1.0e9f);
     for (int b = 0; b < n_items; ++b) s->running_scores[(size_t)b * num_beams] = 0.0f;
     s->beam_scores.assign(BK, -1.0e9f);
@@ -89,6 +92,7 @@ int32_t cw_beam_host_step(cw_beam_host* s, const float* cand_logprob, const int3
     std::vector<float> acc(n), topk_lp(keep), run_lp(keep), lp2(keep), m_scores(K + keep);
     std::vector<int64_t> flat(n), topk_seq((size_t)keep * ML), new_seq((size_t)K * ML);
     std::vector<int32_t> topk_bi((size_t)keep * GC), new_bi((size_t)K * GC);
+    std::vector<float> topk_tl((size_t)keep * GC), new_tl((size_t)K * GC);
     std::vector<int> order(n), nxt(K), sel(K), tmp;
     std::vector<uint8_t> hits(keep), did_top(keep), new_fin(K);
     std::vector<float> new_scores(K);
@@ -102,6 +106,8 @@ int32_t cw_beam_host_step(cw_beam_host* s, const float* cand_logprob, const int3
         int64_t* fseq = &s->sequences[(size_t)b * K * ML];
         int32_t* rbi = &s->running_bi[(size_t)b * K * GC];
         int32_t* fbi = &s->beam_indices[(size_t)b * K * GC];
+        float* rtl = &s->running_tl[(size_t)b * K * GC];
+        float* ftl = &s->token_lp[(size_t)b * K * GC];
         // candidate union of the item's beams in (value desc, flattened vocabulary index asc) order: torch.topk over [K * V] (:3147)
         for (int k = 0; k < K; ++k)
             for (int j = 0; j < keep; ++j) {
@@ -128,6 +134,8 @@ int32_t cw_beam_host_step(cw_beam_host* s, const float* cand_logprob, const int3
             topk_seq[(size_t)j * ML + cur] = id;
             std::memcpy(&topk_bi[(size_t)j * GC], rbi + (size_t)beam * GC, sizeof(int32_t) * GC);
             topk_bi[(size_t)j * GC + gpos] = beam + b * K;
+            std::memcpy(&topk_tl[(size_t)j * GC], rtl + (size_t)beam * GC, sizeof(float) * GC);
+            topk_tl[(size_t)j * GC + gpos] = cand_logprob[(size_t)b * n + i];              // before the running score is added
             hits[j] = (id == s->eos) || (cur + 1 >= ML);                                              // :3456-3462
             all_hits = all_hits && hits[j];
             run_lp[j] = hits[j] ? topk_lp[j] + NEG : topk_lp[j];                                      // :3173-3190
@@ -146,6 +154,8 @@ int32_t cw_beam_host_step(cw_beam_host* s, const float* cand_logprob, const int3
             const int m = sel[k];
             const int64_t* src = m < K ? fseq + (size_t)m * ML : &topk_seq[(size_t)(m - K) * ML];
             const int32_t* sbi = m < K ? fbi + (size_t)m * GC : &topk_bi[(size_t)(m - K) * GC];
+            const float* stl = m < K ? ftl + (size_t)m * GC : &topk_tl[(size_t)(m - K) * GC];
+            std::memcpy(&new_tl[(size_t)k * GC], stl, sizeof(float) * GC);
             std::memcpy(&new_seq[(size_t)k * ML], src, sizeof(int64_t) * ML);
             std::memcpy(&new_bi[(size_t)k * GC], sbi, sizeof(int32_t) * GC);
             new_scores[k] = m_scores[m];
@@ -153,11 +163,13 @@ int32_t cw_beam_host_step(cw_beam_host* s, const float* cand_logprob, const int3
         }
         std::memcpy(fseq, new_seq.data(), sizeof(int64_t) * K * ML);
         std::memcpy(fbi, new_bi.data(), sizeof(int32_t) * K * GC);
+        std::memcpy(ftl, new_tl.data(), sizeof(float) * K * GC);
         for (int k = 0; k < K; ++k) { bs[k] = new_scores[k]; fin[k] = new_fin[k]; }
         topk_desc(run_lp.data(), keep, K, nxt.data(), tmp);
         for (int k = 0; k < K; ++k) {
             std::memcpy(rseq + (size_t)k * ML, &topk_seq[(size_t)nxt[k] * ML], sizeof(int64_t) * ML);
             std::memcpy(rbi + (size_t)k * GC, &topk_bi[(size_t)nxt[k] * GC], sizeof(int32_t) * GC);
+            std::memcpy(rtl + (size_t)k * GC, &topk_tl[(size_t)nxt[k] * GC], sizeof(float) * GC);
             new_scores[k] = run_lp[nxt[k]];
         }
         for (int k = 0; k < K; ++k) {
@@ -198,6 +210,15 @@ int32_t cw_beam_host_result(const cw_beam_host* s, int64_t* sequences, int32_t* 
         std::memcpy(beam_indices + (size_t)b * s->gen_cap, &s->beam_indices[(size_t)b * s->K * s->gen_cap], sizeof(int32_t) * s->gen_cap);
         score[b] = s->beam_scores[(size_t)b * s->K];
     }
+    return CW_OK;
+}
+
+// candidate log-probability (log_softmax of the raw logits; a masked candidate is never chosen, so it equals the processed value)
+// of every generated token of the best hypothesis: out [n_items][max_length - n_prompt], NaN behind the end
+int32_t cw_beam_host_token_logprobs(const cw_beam_host* s, float* out) {
+    if (!s || !out) return CW_ERR_INVALID;
+    for (int b = 0; b < s->B; ++b)
+        std::memcpy(out + (size_t)b * s->gen_cap, &s->token_lp[(size_t)b * s->K * s->gen_cap], sizeof(float) * s->gen_cap);
     return CW_OK;
 }
 

@@ -266,6 +266,7 @@ __global__ __launch_bounds__(256) void sample_partial_kernel(SampleParams p, Sam
     if (sampling) { seed_lo = p.samp[1]; seed_hi = p.samp[2]; stream_lo = p.samp[4 + 2 * b]; stream_hi = p.samp[5 + 2 * b]; }
     float sv[4][4]; int nmine = 0;                                         // this thread's allowed timestamp scores
     float tv[4][4];                                                        // ... and allowed text scores (p.lp_sum only)
+    float rm = -INFINITY, rs = 0.f;                                        // p.tok_lp: online raw max / sum exp(x - rm), v < V
     for (int i4 = lo4 + tid, it = 0; i4 < hi4; i4 += 256, ++it) {
         const float4 x = lg4[i4]; const uchar4 mk = mk4[i4];
         const float xs[4] = {x.x, x.y, x.z, x.w};
@@ -291,6 +292,16 @@ __global__ __launch_bounds__(256) void sample_partial_kernel(SampleParams p, Sam
                 }
             }
             if (it < 4) { sv[it][j] = (v >= tb && v < p.V) ? val : -INFINITY; tv[it][j] = (v < tb) ? val : -INFINITY; }
+        }
+        if (p.tok_lp) {                                         // block-uniform; masked tokens count, pad columns do not
+            float gm = -INFINITY;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) if (i4 * 4 + j < p.V) gm = fmaxf(gm, xs[j]);
+            if (gm > rm) { rs *= expf(rm - gm); rm = gm; }      // rs == 0 while rm == -inf
+            if (rm > -INFINITY) {
+#pragma unroll
+                for (int j = 0; j < 4; ++j) if (i4 * 4 + j < p.V) rs += expf(xs[j] - rm);
+            }
         }
         nmine = it + 1;
     }
@@ -321,6 +332,13 @@ __global__ __launch_bounds__(256) void sample_partial_kernel(SampleParams p, Sam
         __syncthreads();
         acc_t = block_sum(acc_t, s_f);
     }
+    float raw_m = -INFINITY, raw_s = 0.f;                      // slice-wide raw max and sum exp(x - raw_m), on request
+    if (p.tok_lp) {
+        __syncthreads();
+        raw_m = block_max(rm, s_f);
+        __syncthreads();
+        raw_s = block_sum(rm > -INFINITY ? rs * expf(rm - raw_m) : 0.f, s_f);
+    }
     if (tid == 0 && b == 0 && sl == 0) {
         *p.n_unfinished = 0;                                     // stage 2 (a later launch) counts the running rows into it
         if (p.epoch) *p.epoch += 1u;                             // the next decoder forward tags its granules with a fresh epoch (declayer.hip)
@@ -342,7 +360,7 @@ __global__ __launch_bounds__(256) void sample_partial_kernel(SampleParams p, Sam
         }
     }
     if (tid == 0) {
-        SamplePart o; o.bt_v = bt.v; o.bt_i = bt.i; o.bs_v = bs.v; o.bs_i = bs.i; o.ts_sum = acc; o.pad[0] = acc_t; o.pad[1] = o.pad[2] = 0.f;
+        SamplePart o; o.bt_v = bt.v; o.bt_i = bt.i; o.bs_v = bs.v; o.bs_i = bs.i; o.ts_sum = acc; o.pad[0] = acc_t; o.pad[1] = raw_m; o.pad[2] = raw_s;
         part[(size_t)b * SAMPLE_NS + sl] = o;
     }
 }
@@ -414,6 +432,15 @@ __global__ __launch_bounds__(1024) void sample_kernel(SampleParams p) {
                 p.lp_sum[b] += lg[tok] - (M + logf(tot));
                 p.lp_cnt[b] += 1;
             }
+        }
+        if (p.tok_lp && !was_finished && n_gen >= 0 && tok >= 0 && tok < p.V) {
+            // log_softmax of the RAW logits at the token written at t (arg-max, sampled or forced): no processors, no
+            // temperature, pad columns excluded -- the quantity cw_score_tokens reports
+            float Mr = -INFINITY, Sr = 0.f;
+            for (int i = 0; i < SAMPLE_NS; ++i) Mr = fmaxf(Mr, pr[i].pad[1]);
+            for (int i = 0; i < SAMPLE_NS; ++i)
+                if (pr[i].pad[1] > -INFINITY) Sr += pr[i].pad[2] * expf(pr[i].pad[1] - Mr);
+            p.tok_lp[(size_t)b * p.ids_stride + t] = lg[tok] - (Mr + logf(Sr));
         }
         if (was_finished) tok = p.pad;                                  // utils.py:2928-2929
         if (fin_in != 2) ids[t] = tok;

@@ -152,6 +152,9 @@ struct cw_ctx {
     unsigned char* d_mask = nullptr;
     float* d_lp_sum = nullptr; int* d_lp_cnt = nullptr;      // per-row sum / count of chosen-token log-probabilities (score_tokens)
     bool score_tokens = false;
+    float* d_tok_lp = nullptr;                                // [Bm][max_target] log_softmax(raw logits)[token] (cw_set_token_logprobs)
+    bool tok_lp_on = false;
+    std::vector<std::vector<float>> tr_lp;                    // ... of the last cw_transcribe, per item, aligned with its tokens
     float logprob_thr = NAN, no_speech_thr = NAN;             // cw_set_thresholds (NaN: unset)
     void* d_sample_part = nullptr;            // [Bm][16] 32-byte slice records of the two-stage sampler
     void* d_sample_pert = nullptr;            // [Bm][16] 16-byte records of the perturbed winners (seeded sampling)
@@ -1531,6 +1534,7 @@ static int launch_sample(cw_ctx* c, int nb, bool forced) {
     sp.embed = c->embed; sp.pos_embed = c->dec_pos; sp.x_out = c->dx; sp.d = c->d.d_model; sp.embed_bf16 = c->bf16 ? 1 : 0;
     sp.partials = c->d_sample_part;
     if (c->score_tokens) { sp.lp_sum = c->d_lp_sum; sp.lp_cnt = c->d_lp_cnt; }
+    if (c->tok_lp_on) sp.tok_lp = c->d_tok_lp;
     sp.epoch = c->d_epoch;
     sp.samp = c->d_samp; sp.pert = c->d_sample_pert;
     (void)forced;
@@ -1751,12 +1755,14 @@ static int decode_once(cw_ctx* c, int32_t nb, const int32_t* prompt, int32_t n_p
         HIPCHK(c, hipMemsetAsync(c->d_finished, 0, nb * 4, c->st));
         HIPCHK(c, hipMemsetAsync(c->d_lp_sum, 0, nb * 4, c->st));
         HIPCHK(c, hipMemsetAsync(c->d_lp_cnt, 0, nb * 4, c->st));
+        if (c->tok_lp_on) HIPCHK(c, hipMemsetAsync(c->d_tok_lp, 0xff, (size_t)nb * TGT * 4, c->st));   // all-ones = NaN
     } else {
         HIPCHK(c, hipMemcpyAsync(c->d_finished, fin0.data(), nb * 4, hipMemcpyHostToDevice, c->st));
         for (int b = 0; b < nb; ++b)
             if (!fin0[b]) {
                 HIPCHK(c, hipMemsetAsync(c->d_lp_sum + b, 0, 4, c->st));
                 HIPCHK(c, hipMemsetAsync(c->d_lp_cnt + b, 0, 4, c->st));
+                if (c->tok_lp_on) HIPCHK(c, hipMemsetAsync(c->d_tok_lp + (size_t)b * TGT, 0xff, (size_t)TGT * 4, c->st));
             }
     }
     HIPCHK(c, hipMemsetAsync(c->d_last_ts, 0xff, nb * 4, c->st));
@@ -1824,7 +1830,7 @@ static int decode_once(cw_ctx* c, int32_t nb, const int32_t* prompt, int32_t n_p
         // rows below P are good.  Resume there when the sampler's state can be rebuilt from the ids alone (no log-probability sums, no
         // logits capture, P inside the generated part); otherwise cw_decode repeats the whole call.
         const int P = gave_up_word - 1;
-        if (P < n_prompt || P + 1 >= max_length || c->score_tokens || c->logits_capture || c->score_hook) { tm.stop(); return CW_HANDOFF_RETRY; }
+        if (P < n_prompt || P + 1 >= max_length || c->score_tokens || c->tok_lp_on || c->logits_capture || c->score_hook) { tm.stop(); return CW_HANDOFF_RETRY; }
         CWCHK(c, handoffs_off(c, "decode"));
         HIPCHK(c, hipMemcpy(ids.data(), c->d_ids, ids.size() * 4, hipMemcpyDeviceToHost));
         std::vector<int> fin(nb), lts(nb);
@@ -1877,6 +1883,42 @@ int32_t cw_set_thresholds(cw_ctx* c, float logprob_threshold, float no_speech_th
     c->logprob_thr = logprob_threshold; c->no_speech_thr = no_speech_threshold;
     const bool want = !isnan(logprob_threshold);
     if (want != c->score_tokens) { c->score_tokens = want; drop_step_graphs(c); }
+    return CW_OK;
+}
+
+// ---- per-token log-probabilities of the free-running decode (include/crisperwhisper.h) -------------------------------------
+int32_t cw_set_token_logprobs(cw_ctx* c, int32_t on) {
+    const bool want = on != 0;
+    const size_t n = (size_t)c->Bm * c->d.max_target_positions;
+    if (want && !c->d_tok_lp) {
+        CWCHK(c, dmalloc(c, &c->d_tok_lp, n * 4, false));
+        HIPCHK(c, hipMemset(c->d_tok_lp, 0xff, n * 4));
+    }
+    if (want != c->tok_lp_on) {
+        HIPCHK(c, hipStreamSynchronize(c->st));
+        if (want) HIPCHK(c, hipMemset(c->d_tok_lp, 0xff, n * 4));   // nothing decoded under this switch yet
+        c->tok_lp_on = want;
+        c->tr_lp.clear();
+        drop_step_graphs(c);
+    }
+    return CW_OK;
+}
+int32_t cw_get_token_logprobs(cw_ctx* c, float* out, int32_t nb) {
+    if (!c->tok_lp_on) return fail(c, CW_ERR_STATE, "token log-probabilities are off (cw_set_token_logprobs)");
+    if (!out || nb < 1 || nb > c->Bm) return fail(c, CW_ERR_INVALID, "get_token_logprobs: nb=%d outside 1 .. %d", nb, c->Bm);
+    HIPCHK(c, hipStreamSynchronize(c->st));
+    HIPCHK(c, hipMemcpy(out, c->d_tok_lp, (size_t)nb * c->d.max_target_positions * 4, hipMemcpyDeviceToHost));
+    return CW_OK;
+}
+int32_t cw_get_transcribe_token_logprobs(cw_ctx* c, float* out, int32_t B, int32_t cap) {
+    if (!c->tok_lp_on) return fail(c, CW_ERR_STATE, "token log-probabilities are off (cw_set_token_logprobs)");
+    if (!out || B < 1 || (size_t)B != c->tr_lp.size()) return fail(c, CW_ERR_STATE, "get_transcribe_token_logprobs: B=%d but the last cw_transcribe had %d items", B, (int)c->tr_lp.size());
+    for (int i = 0; i < B; ++i) {
+        const int n = (int)c->tr_lp[i].size();
+        if (n > cap) return fail(c, CW_ERR_INVALID, "item %d holds %d tokens, capacity %d", i, n, cap);
+        memcpy(out + (size_t)i * cap, c->tr_lp[i].data(), (size_t)n * 4);
+        for (int k = n; k < cap; ++k) out[(size_t)i * cap + k] = NAN;
+    }
     return CW_OK;
 }
 
@@ -2269,7 +2311,8 @@ int32_t cw_transcribe_prompted(cw_ctx* c, int32_t B, const int32_t* num_frames, 
     if (max_length <= n_prompt) return fail(c, CW_ERR_INVALID, "max_length %d leaves no room after %d decoder input tokens", max_length, n_prompt);
     std::vector<long> seek(B, 0);
     std::vector<std::vector<int>> out_tok(B);
-    std::vector<std::vector<float>> out_ts(B);
+    std::vector<std::vector<float>> out_ts(B), out_lp(B);
+    c->tr_lp.clear();
     int passes = 0;
     for (;;) {
         std::vector<int> active, a_seek, a_n, a_nf;
@@ -2291,6 +2334,8 @@ int32_t cw_transcribe_prompted(cw_ctx* c, int32_t B, const int32_t* num_frames, 
         if (thr) CWCHK(c, cw_no_speech_probs(c, nb, cfg->sot_token, nsp.data()));
         CWCHK(c, cw_decode(c, nb, prm.data(), n_prompt, max_length, cfg->min_new_tokens, nullptr, seq.data(), ln.data(), nullptr));
         if (thr) CWCHK(c, cw_get_avg_logprobs(c, alp.data(), nb));
+        std::vector<float> tlp;
+        if (c->tok_lp_on) { tlp.resize((size_t)nb * TGT); CWCHK(c, cw_get_token_logprobs(c, tlp.data(), nb)); }
         int total = 0;
         for (int r = 0; r < nb; ++r) total = ln[r] > total ? ln[r] : total;
         const int L = total - 1;
@@ -2323,6 +2368,7 @@ int32_t cw_transcribe_prompted(cw_ctx* c, int32_t B, const int32_t* num_frames, 
             for (int k = 0; k < keep; ++k) {
                 out_tok[i].push_back(s[k]);
                 out_ts[i].push_back(ts[(size_t)r * (L + 1) + n_prompt + k] + off32);
+                if (c->tok_lp_on) out_lp[i].push_back(tlp[(size_t)r * TGT + n_prompt + k]);
             }
             seek[i] += advance;
         }
@@ -2334,6 +2380,7 @@ int32_t cw_transcribe_prompted(cw_ctx* c, int32_t B, const int32_t* num_frames, 
         memcpy(tokens + (size_t)i * cap, out_tok[i].data(), (size_t)n * 4);
         memcpy(token_ts + (size_t)i * cap, out_ts[i].data(), (size_t)n * 4);
     }
+    if (c->tok_lp_on) c->tr_lp = std::move(out_lp);
     if (n_passes) *n_passes = passes;
     return CW_OK;
 }
@@ -4115,7 +4162,8 @@ int32_t cw_test_beam_state(cw_ctx* c, int32_t rows, int32_t* ids, int32_t* anc, 
 // ids [nb][t] = prompt + generated so far (the kernel's grammar state is rebuilt from it), choice_out [nb] = the
 // token the kernel picks for index t.  Differential test against TF/generation/logits_process.py:203-260, 1816-2047.
 static int test_sample(cw_ctx* c, int32_t nb, const float* logits, const int32_t* ids, int32_t t, int32_t n_prompt,
-                       int32_t min_new_tokens, int32_t max_length, int32_t* choice_out);
+                       int32_t min_new_tokens, int32_t max_length, int32_t* choice_out, const int32_t* forced_tok = nullptr,
+                       float* lp_out = nullptr);
 int32_t cw_test_sample(cw_ctx* c, int32_t nb, const float* logits, const int32_t* ids, int32_t t, int32_t n_prompt,
                        int32_t min_new_tokens, int32_t max_length, int32_t* choice_out) {
     return test_sample(c, nb, logits, ids, t, n_prompt, min_new_tokens, max_length, choice_out);
@@ -4137,8 +4185,32 @@ int32_t cw_test_sample_seeded(cw_ctx* c, int32_t nb, const float* logits, const 
     c->samp_host = keep;
     return r;
 }
+// ... and with the per-token log-probability store switched on for this call only: lp_out [nb] = what the kernels stored at
+// [b][t]; forced_tok [nb] (or NULL; -1 = not forced) is written at t in place of the choice, choice_out stays the un-forced choice.
+int32_t cw_test_sample_logprobs(cw_ctx* c, int32_t nb, const float* logits, const int32_t* ids, int32_t t, int32_t n_prompt,
+                                int32_t min_new_tokens, int32_t max_length, float temperature, uint64_t seed,
+                                const uint64_t* row_streams, const int32_t* forced_tok, int32_t* choice_out, float* lp_out) {
+    if (!logits || !ids || !choice_out || !lp_out) return fail(c, CW_ERR_INVALID, "test_sample_logprobs: null argument");
+    if (nb < 1 || nb > c->Bm || nb > 64) return fail(c, CW_ERR_INVALID, "test_sample_logprobs: nb=%d outside 1 .. %d", nb, c->Bm < 64 ? c->Bm : 64);
+    if (max_length <= n_prompt || max_length > c->d.max_target_positions || min_new_tokens < 0)
+        return fail(c, CW_ERR_INVALID, "test_sample_logprobs: max_length=%d / min_new_tokens=%d out of range", max_length, min_new_tokens);
+    if (temperature > 0.f && !row_streams) return fail(c, CW_ERR_INVALID, "test_sample_logprobs: a positive temperature needs row_streams");
+    if (forced_tok)
+        for (int b = 0; b < nb; ++b)
+            if (forced_tok[b] >= c->d.vocab_size) return fail(c, CW_ERR_INVALID, "test_sample_logprobs: forced token %d out of range", forced_tok[b]);
+    const bool was_on = c->tok_lp_on;
+    CWCHK(c, cw_set_token_logprobs(c, 1));
+    const std::vector<unsigned int> keep = c->samp_host;
+    CWCHK(c, write_sampling(c, temperature, seed, row_streams, nb, "test_sample_logprobs"));
+    const int r = test_sample(c, nb, logits, ids, t, n_prompt, min_new_tokens, max_length, choice_out, forced_tok, lp_out);
+    HIPCHK(c, hipStreamSynchronize(c->st));
+    HIPCHK(c, hipMemcpy(c->d_samp, keep.data(), keep.size() * 4, hipMemcpyHostToDevice));
+    c->samp_host = keep;
+    if (!was_on) CWCHK(c, cw_set_token_logprobs(c, 0));
+    return r;
+}
 static int test_sample(cw_ctx* c, int32_t nb, const float* logits, const int32_t* ids, int32_t t, int32_t n_prompt,
-                       int32_t min_new_tokens, int32_t max_length, int32_t* choice_out) {
+                       int32_t min_new_tokens, int32_t max_length, int32_t* choice_out, const int32_t* forced_tok, float* lp_out) {
     const int V = c->d.vocab_size, TGT = c->d.max_target_positions;
     if (!c->gen_set) return fail(c, CW_ERR_STATE, "cw_set_generation not called");
     if (nb < 1 || nb > c->Bm || t < n_prompt || t < 1 || t >= TGT || n_prompt < 1) return fail(c, CW_ERR_INVALID, "test_sample: bad args");
@@ -4156,7 +4228,13 @@ static int test_sample(cw_ctx* c, int32_t nb, const float* logits, const int32_t
     HIPCHK(c, hipMemcpy(c->d_pos, posv.data(), 64 * 4, hipMemcpyHostToDevice));
     HIPCHK(c, hipMemset(c->d_finished, 0, nb * 4));
     HIPCHK(c, hipMemset(c->d_argmax, 0xff, (size_t)nb * TGT * 4));
-    const int cfg[4] = {n_prompt, min_new_tokens, max_length, 0};
+    if (forced_tok) {
+        std::vector<int> fr((size_t)nb * TGT, -1);
+        for (int b = 0; b < nb; ++b) fr[(size_t)b * TGT + t] = forced_tok[b];
+        HIPCHK(c, hipMemcpy(c->d_forced, fr.data(), fr.size() * 4, hipMemcpyHostToDevice));
+    }
+    if (lp_out) HIPCHK(c, hipMemset(c->d_tok_lp, 0xff, (size_t)nb * TGT * 4));
+    const int cfg[4] = {n_prompt, min_new_tokens, max_length, forced_tok ? 1 : 0};
     HIPCHK(c, hipMemcpy(c->d_cfg, cfg, sizeof(cfg), hipMemcpyHostToDevice));
     HIPCHK(c, hipMemcpy2D(c->dlogits, (size_t)c->Vpad * 4, logits, (size_t)V * 4, (size_t)V * 4, nb, hipMemcpyHostToDevice));
     CWCHK(c, launch_sample(c, nb, false));
@@ -4164,6 +4242,11 @@ static int test_sample(cw_ctx* c, int32_t nb, const float* logits, const int32_t
     std::vector<int> am((size_t)nb * TGT);
     HIPCHK(c, hipMemcpy(am.data(), c->d_argmax, am.size() * 4, hipMemcpyDeviceToHost));
     for (int b = 0; b < nb; ++b) choice_out[b] = am[(size_t)b * TGT + t];
+    if (lp_out) {
+        std::vector<float> lp((size_t)nb * TGT);
+        HIPCHK(c, hipMemcpy(lp.data(), c->d_tok_lp, lp.size() * 4, hipMemcpyDeviceToHost));
+        for (int b = 0; b < nb; ++b) lp_out[b] = lp[(size_t)b * TGT + t];
+    }
     return CW_OK;
 }
 

@@ -49,6 +49,9 @@ struct SampleParams {
     // [1] seed_lo, [2] seed_hi, [3] unused, [4 + 2b] / [5 + 2b] stream_lo / stream_hi of row b
     const unsigned int* samp;
     void* pert;                // [B][SAMPLE_NS] 16-byte records: best perturbed text / timestamp token of every slice (samp only)
+    // optional (null: off): log_softmax(raw logits)[token written at t] of every running row, stored at [b][t]
+    // (include/crisperwhisper.h: cw_set_token_logprobs)
+    float* tok_lp;             // [B][ids_stride]
 };
 // beam search (elementwise.hip): per row the n_cand best processed log-probabilities of the next token
 // (log_softmax of the raw logits, then the same processors as the greedy path) ...

@@ -23,9 +23,19 @@ def shard_bounds(n_chunks: int, world: int):
     return bounds
 
 
-def pack_record(idx: int, tokens: np.ndarray, ts: np.ndarray, stride) -> np.ndarray:
-    rec = np.zeros(REC_WORDS, dtype=np.int32)
+REC_WORDS_SCORED = REC_WORDS + REC_TOKENS   # ... followed by one f32 log-probability per token (only when scores are requested)
+
+
+def pack_record(idx: int, tokens: np.ndarray, ts: np.ndarray, stride, scores: Optional[np.ndarray] = None) -> np.ndarray:
+    """One chunk's record.  ``scores`` (one float32 per token) widens it to REC_WORDS_SCORED; without it the record is the
+    REC_WORDS one."""
+    rec = np.zeros(REC_WORDS if scores is None else REC_WORDS_SCORED, dtype=np.int32)
     nt, ns = len(tokens), len(ts)
+    if scores is not None:
+        if len(scores) != nt:
+            raise ValueError(f"{len(scores)} token scores for {nt} tokens")
+        if nt <= REC_TOKENS:
+            rec[REC_WORDS:REC_WORDS + nt] = np.asarray(scores, dtype=np.float32).view(np.int32)
     if nt > REC_TOKENS or ns > REC_TOKENS:
         raise ValueError(f"chunk output of {max(nt, ns)} tokens exceeds the record capacity ({REC_TOKENS})")
     rec[0], rec[1], rec[2] = idx, nt, ns
@@ -40,6 +50,8 @@ def unpack_record(rec: np.ndarray):
     stride = tuple(float(x) for x in rec[3:6].view(np.float32))
     tokens = rec[6:6 + nt].astype(np.int64)
     ts = rec[6 + REC_TOKENS:6 + REC_TOKENS + ns].view(np.float32).copy()
+    if len(rec) == REC_WORDS_SCORED:                 # a record packed with scores: a fifth value, one f32 per token
+        return idx, tokens, ts, stride, rec[REC_WORDS:REC_WORDS + nt].view(np.float32).copy()
     return idx, tokens, ts, stride
 
 

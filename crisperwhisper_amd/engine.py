@@ -272,6 +272,27 @@ class Engine:
         self._chk(self.lib.cw_get_avg_logprobs(self.ctx, _ptr(out), nb))
         return out
 
+    def set_token_logprobs(self, on: bool):
+        """Per-token log-probabilities of the free-running decode (``cw_set_token_logprobs``); off by default."""
+        self._chk(self.lib.cw_set_token_logprobs(self.ctx, 1 if on else 0))
+
+    def token_logprobs(self, nb: int) -> np.ndarray:
+        """[nb, max_target_positions] float32 aligned with the last ``decode``'s sequences: ``logits[tok] -
+        logsumexp(logits[:vocab])`` on the raw logits of the step that wrote each token; NaN at prompt positions, behind a
+        row's end and for rows never decoded (``cw_get_token_logprobs``)."""
+        out = np.empty((nb, self.spec.max_target_positions), np.float32)
+        self._chk(self.lib.cw_get_token_logprobs(self.ctx, _ptr(out), nb))
+        return out
+
+    def transcribe_token_logprobs(self, lens) -> List[np.ndarray]:
+        """The values of the last ``transcribe``, one float32 array per item aligned with its tokens (``lens`` = their
+        counts; ``cw_get_transcribe_token_logprobs``)."""
+        nb = len(lens)
+        cap = max(1, max((int(n) for n in lens), default=1))
+        out = np.empty((nb, cap), np.float32)
+        self._chk(self.lib.cw_get_transcribe_token_logprobs(self.ctx, _ptr(out), nb, cap))
+        return [out[i, :int(n)].copy() for i, n in enumerate(lens)]
+
     def last_logits(self, nb: int) -> np.ndarray:
         out = np.empty((nb, self.spec.vocab_size), dtype=np.float32)
         self._chk(self.lib.cw_get_logits(self.ctx, _ptr(out), nb))
@@ -827,6 +848,28 @@ class Engine:
                                                  int(max_length or self.spec.max_target_positions), float(temperature),
                                                  int(seed) & (2 ** 64 - 1), _ptr(rs), _ptr(out)))
         return out
+
+    def test_sample_logprobs(self, logits: np.ndarray, ids: np.ndarray, n_prompt: int, temperature: float = 0.0, seed: int = 0,
+                             row_streams=None, forced=None, min_new_tokens: int = 0, max_length: Optional[int] = None):
+        """``test_sample_seeded`` with the per-token log-probability store on (cw_test_sample_logprobs): returns (choice [nb],
+        logprob [nb] of the token written at index t).  ``forced`` [nb] (-1: not forced) is written instead of the choice."""
+        lg = np.ascontiguousarray(logits, np.float32)
+        ids = _i32(ids)
+        nb, t = ids.shape
+        if lg.shape != (nb, self.spec.vocab_size):
+            raise ValueError(f"logits must be [{nb}][{self.spec.vocab_size}], got {lg.shape}")
+        rs = None if row_streams is None else np.ascontiguousarray(row_streams, dtype=np.uint64)
+        if rs is not None and rs.shape != (nb,):
+            raise ValueError(f"row_streams must hold one id per row ({nb}), got shape {rs.shape}")
+        fr = None if forced is None else _i32(forced)
+        if fr is not None and fr.shape != (nb,):
+            raise ValueError(f"forced must hold one token per row ({nb}), got shape {fr.shape}")
+        out = np.zeros(nb, np.int32)
+        lp = np.zeros(nb, np.float32)
+        self._chk(self.lib.cw_test_sample_logprobs(self.ctx, nb, _ptr(lg), _ptr(ids), t, int(n_prompt), int(min_new_tokens),
+                                                   int(max_length or self.spec.max_target_positions), float(temperature),
+                                                   int(seed) & (2 ** 64 - 1), _ptr(rs), _ptr(fr), _ptr(out), _ptr(lp)))
+        return out, lp
 
     # ------------------------------------------------------------------ measurement
     def stage_times(self, reset: bool = False):

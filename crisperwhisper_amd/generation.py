@@ -29,6 +29,7 @@ class Segment:
     tokens: np.ndarray             # int64
     token_timestamps: np.ndarray   # float32, absolute seconds within the 30 s chunk
     idxs: tuple
+    token_logprobs: Optional[np.ndarray] = None   # float32, one per token (generate(return_token_logprobs=True))
 
 
 def detect_language(engine: Engine, n_items: int) -> np.ndarray:
@@ -182,8 +183,11 @@ def prompted_max_length(spec, n_input: int, max_new_tokens: Optional[int]) -> in
 
 
 def split_segments(seq: np.ndarray, token_ts: np.ndarray, time_offset: float, timestamp_begin: int,
-                   seek_num_frames: int, idx_offset: int):
-    """Slice one decoded window at paired timestamp tokens; returns (segments, frames to advance)."""
+                   seek_num_frames: int, idx_offset: int, token_lp: Optional[np.ndarray] = None):
+    """Slice one decoded window at paired timestamp tokens; returns (segments, frames to advance).  ``token_lp`` (per-token
+    log-probabilities of the row, indexed like ``token_ts``) is cut by the same index ranges."""
+    def lp(a, b):
+        return None if token_lp is None else np.asarray(token_lp[a:b], dtype=np.float32).copy()
     is_ts = seq >= timestamp_begin
     single_ending = len(seq) >= 2 and (not is_ts[-2]) and bool(is_ts[-1])
     if len(seq) == 1:
@@ -200,7 +204,7 @@ def split_segments(seq: np.ndarray, token_ts: np.ndarray, time_offset: float, ti
         prev = 0
         for cut in cuts:
             out.append(Segment(seq[prev:cut], (token_ts[idx_offset + prev: idx_offset + cut] + off32).astype(np.float32),
-                               (idx_offset + prev, idx_offset + cut)))
+                               (idx_offset + prev, idx_offset + cut), lp(idx_offset + prev, idx_offset + cut)))
             prev = cut
         if single_ending:
             advance = seek_num_frames
@@ -208,7 +212,7 @@ def split_segments(seq: np.ndarray, token_ts: np.ndarray, time_offset: float, ti
             advance = (int(seq[prev - 2]) - timestamp_begin) * INPUT_STRIDE
     else:
         out.append(Segment(seq, (token_ts[idx_offset: idx_offset + len(seq)] + off32).astype(np.float32),
-                           (idx_offset, idx_offset + len(seq))))
+                           (idx_offset, idx_offset + len(seq)), lp(idx_offset, idx_offset + len(seq))))
         advance = seek_num_frames
     return out, advance
 
@@ -252,13 +256,18 @@ def _beam_search_native_host(engine, prompt, max_length, min_new_tokens, K, leng
         rc = lib.cw_beam_host_result(st, seqs.ctypes.data_as(C.c_void_p), bi.ctypes.data_as(C.c_void_p), sc.ctypes.data_as(C.c_void_p))
         if rc != 0:
             raise RuntimeError(f"cw_beam_host_result failed ({rc})")
-        return seqs, bi, sc
+        tl = np.empty((B, max_length - n_prompt), np.float32)
+        rc = lib.cw_beam_host_token_logprobs(st, tl.ctypes.data_as(C.c_void_p))
+        if rc != 0:
+            raise RuntimeError(f"cw_beam_host_token_logprobs failed ({rc})")
+        return seqs, bi, sc, tl
     finally:
         lib.cw_beam_host_free(st)
 
 
 def beam_search(engine: Engine, prompt: np.ndarray, max_length: int, min_new_tokens: int, num_beams: int,
-                length_penalty: float = 1.0, early_stopping=False, native_host: Optional[bool] = None):
+                length_penalty: float = 1.0, early_stopping=False, native_host: Optional[bool] = None,
+                return_token_logprobs: bool = False):
     """Host half of ``GenerationMixin._beam_search`` (TF/generation/utils.py:3208-3520) -- running / finished
     hypotheses, length penalty, the early-stopping heuristic (:3009-3053), all in float32 like HF -- over the device half
     (``Engine.beam_begin / beam_step / beam_advance / beam_finish``: decoder forwards on items x beams rows, log-softmax +
@@ -270,7 +279,11 @@ def beam_search(engine: Engine, prompt: np.ndarray, max_length: int, min_new_tok
 
     ``native_host`` (default True): the bookkeeping of every step runs in ``csrc/beamhost.cpp`` (one C call per step instead
     of ~45 numpy calls, 0.23 ms per step at 8 items x 5 beams); ``False`` keeps the numpy statement below, which
-    ``tests/test_beam_host.py`` holds bit-equal to the native one on random candidate streams."""
+    ``tests/test_beam_host.py`` holds bit-equal to the native one on random candidate streams.
+
+    ``return_token_logprobs=True`` appends a fifth value: [B, max_generated] float32, for every generated token of the
+    returned hypothesis the candidate log-probability it was chosen with (``log_softmax`` of the raw logits of its step: a
+    masked candidate is never chosen, so processed and raw value coincide), followed along the ancestry; NaN behind the end."""
     if early_stopping is not True and early_stopping is not False:
         # transformers also knows "never" (a third stopping heuristic, generation/utils.py:3042-3053); it is not implemented
         # here and must not be mistaken for False
@@ -281,8 +294,8 @@ def beam_search(engine: Engine, prompt: np.ndarray, max_length: int, min_new_tok
     B, n_prompt = prompt.shape
     K, V = int(num_beams), spec.vocab_size
     if native_host is None or native_host:
-        seqs, bi, sc = _beam_search_native_host(engine, prompt, max_length, min_new_tokens, K, length_penalty, early_stopping)
-        return _beam_search_tail(engine, seqs, bi, sc, n_prompt)
+        seqs, bi, sc, tl = _beam_search_native_host(engine, prompt, max_length, min_new_tokens, K, length_penalty, early_stopping)
+        return _beam_search_tail(engine, seqs, bi, sc, n_prompt, tl if return_token_logprobs else None)
     eos, pad = spec.eos_token_id, spec.pad_token_id
     keep = max(2, 1 + 1) * K                                    # beams_to_keep (:3280-3281), one eos token id
     top_mask = np.arange(keep) < K
@@ -296,6 +309,8 @@ def beam_search(engine: Engine, prompt: np.ndarray, max_length: int, min_new_tok
     unsat = np.ones((B, 1), bool)
     running_bi = np.full((B, K, max_length - n_prompt), -1, dtype=np.int32)
     beam_indices = running_bi.copy()
+    running_tl = np.full((B, K, max_length - n_prompt), np.nan, dtype=f32)
+    token_lp = running_tl.copy()
     cur_len = n_prompt
     bidx = np.arange(B)[:, None]
     engine.beam_begin(prompt, K, max_length, min_new_tokens)
@@ -310,11 +325,14 @@ def beam_search(engine: Engine, prompt: np.ndarray, max_length: int, min_new_tok
         order = np.lexsort((flat, -acc), axis=-1)[:, :keep]
         topk_lp = np.take_along_axis(acc, order, axis=1)
         topk_flat = np.take_along_axis(flat, order, axis=1)
+        topk_cand = np.take_along_axis(vals.reshape(B, K * keep), order, axis=1)   # before the running score is added
         topk_beam, topk_ids = topk_flat // V, topk_flat % V
         topk_seq = running_seq[bidx, topk_beam]                   # [B, keep, max_length]
         topk_seq[:, :, cur_len] = topk_ids
         topk_bi = running_bi[bidx, topk_beam]
         topk_bi[:, :, cur_len - n_prompt] = (topk_beam + np.arange(B)[:, None] * K).astype(np.int32)
+        topk_tl = running_tl[bidx, topk_beam]
+        topk_tl[:, :, cur_len - n_prompt] = topk_cand
         # d. stopping criteria: eos token, max length (:3456-3462)
         hits = (topk_ids == eos) | (cur_len + 1 >= max_length)
         # e. running beams of the next iteration (:3173-3190)
@@ -323,6 +341,7 @@ def beam_search(engine: Engine, prompt: np.ndarray, max_length: int, min_new_tok
         running_seq = np.take_along_axis(topk_seq, nxt[:, :, None], axis=1)
         running_scores = np.take_along_axis(run_lp, nxt, axis=1)
         running_bi = np.take_along_axis(topk_bi, nxt[:, :, None], axis=1)
+        running_tl = np.take_along_axis(topk_tl, nxt[:, :, None], axis=1)
         # f. finished hypotheses (:3192-3245)
         did_top = hits & top_mask[None, :]
         lp2 = (topk_lp / f32((cur_len + 1 - n_prompt) ** length_penalty)).astype(f32)
@@ -338,6 +357,7 @@ def beam_search(engine: Engine, prompt: np.ndarray, max_length: int, min_new_tok
         sequences = np.take_along_axis(m_seq, sel[:, :, None], axis=1)
         beam_scores = np.take_along_axis(m_scores, sel, axis=1)
         beam_indices = np.take_along_axis(m_bi, sel[:, :, None], axis=1)
+        token_lp = np.take_along_axis(np.concatenate([token_lp, topk_tl], axis=1), sel[:, :, None], axis=1)
         is_sent_finished = np.take_along_axis(m_fin, sel, axis=1)
         # g. next iteration: cache re-ordering (device), stopping condition of the search as a whole
         parent = running_bi[:, :, cur_len - n_prompt].reshape(-1)
@@ -351,10 +371,11 @@ def beam_search(engine: Engine, prompt: np.ndarray, max_length: int, min_new_tok
         if not go_on:
             break
         engine.beam_advance(parent, token)
-    return _beam_search_tail(engine, sequences[:, 0, :], beam_indices[:, 0, :], beam_scores[:, 0], n_prompt)
+    return _beam_search_tail(engine, sequences[:, 0, :], beam_indices[:, 0, :], beam_scores[:, 0], n_prompt,
+                             token_lp[:, 0, :] if return_token_logprobs else None)
 
 
-def _beam_search_tail(engine, seq_out, bi_out, scores, n_prompt):
+def _beam_search_tail(engine, seq_out, bi_out, scores, n_prompt, tl_out=None):
     """Trim to the longest returned hypothesis and gather the alignment rows of the returned sequences."""
     max_gen = int((bi_out != -1).sum(axis=1).max())
     seq_out = seq_out[:, :n_prompt + max_gen]
@@ -364,6 +385,8 @@ def _beam_search_tail(engine, seq_out, bi_out, scores, n_prompt):
     unrolled = np.concatenate([np.repeat(bi_out[:, :1], n_prompt - 1, axis=1), bi_out], axis=1) if n_prompt > 1 else bi_out
     unrolled = np.where(unrolled == -1, 0, unrolled).astype(np.int32)
     engine.beam_finish(unrolled)
+    if tl_out is not None:
+        return seq_out, bi_out, unrolled.shape[1], np.asarray(scores, dtype=np.float32), np.asarray(tl_out[:, :max_gen], np.float32)
     return seq_out, bi_out, unrolled.shape[1], np.asarray(scores, dtype=np.float32)
 
 
@@ -429,7 +452,8 @@ def generate(engine: Engine, n_items: int, num_frames, *, language: Optional[str
              max_new_tokens: Optional[int] = None, min_new_tokens: Optional[int] = None,
              num_beams: Optional[int] = 1, stats: Optional[dict] = None, native: Optional[bool] = None,
              logprob_threshold: Optional[float] = None, no_speech_threshold: Optional[float] = None, prompt_ids=None,
-             temperature=None, compression_ratio_threshold: Optional[float] = None, sampling_seed: int = 0, item_ids=None):
+             temperature=None, compression_ratio_threshold: Optional[float] = None, sampling_seed: int = 0, item_ids=None,
+             return_token_logprobs: bool = False):
     """Transcribe the ``n_items`` 30 s feature windows resident in the engine (items 0..n-1).
 
     Returns {"sequences": [B, Lmax] int64 (pad-right), "token_timestamps": list of float32 arrays,
@@ -454,8 +478,16 @@ def generate(engine: Engine, n_items: int, num_frames, *, language: Optional[str
 
     ``prompt_ids`` (``processor.get_prompt_ids(text)``): every window of every seek pass decodes from
     ``prompt_ids ++ init_tokens`` (generation_whisper.py:1909-1913, condition_on_prev_tokens False); language detection still
-    runs on <|startoftranscript|> alone; the prompt is never part of the output."""
+    runs on <|startoftranscript|> alone; the prompt is never part of the output.
+
+    ``return_token_logprobs=True`` adds "token_logprobs": one float32 array per item aligned with ``token_timestamps``,
+    ``logits[tok] - logsumexp(logits[:vocab])`` on the raw logits of the step that produced each token (the quantity ``score``
+    reports).  Greedy, sampled and forced rows take it from the sampler kernels (``cw_set_token_logprobs``), beam search from
+    the candidate values along the winning hypothesis' ancestry; no extra forward runs."""
     spec = engine.spec
+    want_lp = bool(return_token_logprobs)
+    if want_lp and not hasattr(engine, "set_token_logprobs"):
+        raise ValueError("this engine does not implement per-token log-probabilities (cw_set_token_logprobs)")
     if no_speech_threshold is not None and logprob_threshold is None:
         raise ValueError("no_speech_threshold needs logprob_threshold as well (generation_whisper.py:1275-1285 compares both)")
     # every argument is checked before any engine state changes (a refused call must not leave its thresholds behind)
@@ -490,12 +522,15 @@ def generate(engine: Engine, n_items: int, num_frames, *, language: Optional[str
         ids_ = list(range(n_items)) if item_ids is None else [int(i) for i in item_ids]
         if len(ids_) != n_items:
             raise ValueError(f"{len(ids_)} item_ids for {n_items} items")
-        fb = {"temps": temps, "seed": int(sampling_seed), "item_ids": ids_, "cr_thr": compression_ratio_threshold}
+        fb = {"temps": temps, "seed": int(sampling_seed), "item_ids": ids_, "cr_thr": compression_ratio_threshold,
+              "token_logprobs": want_lp}
         native = False                                  # the fallback loop runs here, like beam search
     if hasattr(engine, "set_thresholds"):
         engine.set_thresholds(logprob_threshold, no_speech_threshold)
     elif logprob_threshold is not None:
         raise ValueError("this engine does not implement logprob_threshold / no_speech_threshold")
+    if hasattr(engine, "set_token_logprobs"):
+        engine.set_token_logprobs(want_lp)
     num_frames = np.asarray(num_frames, dtype=np.int64)
     if native is None:
         native = hasattr(engine, "transcribe") and num_beams == 1
@@ -521,7 +556,10 @@ def generate(engine: Engine, n_items: int, num_frames, *, language: Optional[str
         sequences = np.full((n_items, width), spec.pad_token_id, dtype=np.int64)
         for i, s in enumerate(toks):
             sequences[i, :len(s)] = s
-        return {"sequences": sequences, "token_timestamps": tts, "segments": None}
+        out = {"sequences": sequences, "token_timestamps": tts, "segments": None}
+        if want_lp:
+            out["token_logprobs"] = engine.transcribe_token_logprobs([len(s) for s in toks])
+        return out
     pre_encoded = False
     _, detect = resolve_prompt(spec, language, task)
     if detect:
@@ -548,7 +586,7 @@ def generate(engine: Engine, n_items: int, num_frames, *, language: Optional[str
     try:
         _seek_loop(engine, spec, n_items, num_frames, init, n_prompt, max_new_tokens, min_new_tokens, num_beams, prefix,
                    prompted_len if prefix is not None else None, skip_on, logprob_threshold, no_speech_threshold, pre_encoded,
-                   seek, max_frames, segments, tb, stats, fb)
+                   seek, max_frames, segments, tb, stats, fb, want_lp)
     finally:
         if prefix is not None and set_prefix is not None:
             set_prefix(0)
@@ -558,11 +596,15 @@ def generate(engine: Engine, n_items: int, num_frames, *, language: Optional[str
     for i, s in enumerate(seq_list):
         sequences[i, :len(s)] = s
     tts = [np.concatenate([s.token_timestamps for s in segs]) if segs else np.zeros(0, np.float32) for segs in segments]
-    return {"sequences": sequences, "token_timestamps": tts, "segments": segments}
+    out = {"sequences": sequences, "token_timestamps": tts, "segments": segments}
+    if want_lp:
+        out["token_logprobs"] = [np.concatenate([s.token_logprobs for s in segs]) if segs else np.zeros(0, np.float32)
+                                 for segs in segments]
+    return out
 
 
 def _seek_loop(engine, spec, n_items, num_frames, init, n_prompt, max_new_tokens, min_new_tokens, num_beams, prefix, prompted_len,
-               skip_on, logprob_threshold, no_speech_threshold, pre_encoded, seek, max_frames, segments, tb, stats, fb=None):
+               skip_on, logprob_threshold, no_speech_threshold, pre_encoded, seek, max_frames, segments, tb, stats, fb=None, want_lp=False):
     """The seek loop of the host path of ``generate`` (fills ``segments`` in place).  ``fb``: temperature fallback settings."""
     n_calls = 0
     while True:
@@ -583,18 +625,23 @@ def _seek_loop(engine, spec, n_items, num_frames, init, n_prompt, max_new_tokens
                                          stats)
             n_calls += 1
             for row, i in enumerate(active):
-                s, ts_row, skip = kept[row]
+                s, ts_row, skip = kept[row][:3]
+                lp_row = kept[row][3] if want_lp else None
                 if skip:
                     seek[i] += seek_num[i]                        # should_skip (:879-881)
                     continue
                 segs, advance = split_segments(s, ts_row, float(seek[i]) * TIME_PRECISION / INPUT_STRIDE, tb,
-                                               int(seek_num[i]), n_prompt)
+                                               int(seek_num[i]), n_prompt, lp_row)
                 seek[i] += advance
                 segments[i].extend(segs)
             continue
         if num_beams > 1:
-            bs, _, L, alp = beam_search(engine, init[active], max_length, min_new_tokens or 0, num_beams)
+            bs, _, L, alp, *btl = beam_search(engine, init[active], max_length, min_new_tokens or 0, num_beams,
+                                              return_token_logprobs=want_lp)
             total = bs.shape[1]
+            if want_lp:                                           # indexed by sequence position, like token_ts
+                tok_lp = np.full((len(active), total), np.nan, np.float32)
+                tok_lp[:, n_prompt:] = btl[0]
             seqs = np.full((len(active), spec.max_target_positions), spec.pad_token_id, dtype=np.int64)
             seqs[:, :total] = bs
         else:
@@ -602,6 +649,8 @@ def _seek_loop(engine, spec, n_items, num_frames, init, n_prompt, max_new_tokens
             total = int(lens.max())
             L = total - 1
             alp = engine.avg_logprobs(len(active)) if skip_on else None
+            if want_lp:
+                tok_lp = engine.token_logprobs(len(active))
         token_ts = engine.token_timestamps(len(active), L, n_prompt, (num_frames - seek)[active])
         n_calls += 1
         for row, i in enumerate(active):
@@ -618,7 +667,7 @@ def _seek_loop(engine, spec, n_items, num_frames, init, n_prompt, max_new_tokens
             if s[-1] == spec.eos_token_id:
                 s = s[:-1]
             segs, advance = split_segments(s, token_ts[row], float(seek[i]) * TIME_PRECISION / INPUT_STRIDE, tb,
-                                           int(seek_num[i]), n_prompt)
+                                           int(seek_num[i]), n_prompt, tok_lp[row] if want_lp else None)
             seek[i] += advance
             segments[i].extend(segs)
     if stats is not None:
@@ -634,7 +683,8 @@ def _decode_with_fallback(engine, spec, fb, active, init_rows, n_prompt, max_len
     temperature; its token timestamps are taken right after that decode (a later decode overwrites the idle rows' attention
     rows).  Decisions are indexed by the original row throughout -- transformers indexes ``needs_fallback[i]`` /
     ``should_skip[i]`` by the row of the shrunken sub-batch (:1074 against :1088) and reads them back by the original one.
-    Returns per row (tokens without eos, token timestamps of the whole row, skip)."""
+    Returns per row (tokens without eos, token timestamps of the whole row, skip[, token log-probabilities of the whole row when
+    ``fb["token_logprobs"]`` is set])."""
     nb = len(active)
     temps = fb["temps"]
     kept = [None] * nb
@@ -654,6 +704,7 @@ def _decode_with_fallback(engine, spec, fb, active, init_rows, n_prompt, max_len
             total = int(lens.max())
             alp = engine.avg_logprobs(nb) if logprob_threshold is not None else None
             token_ts = engine.token_timestamps(nb, total - 1, n_prompt, frames)
+            tok_lp = engine.token_logprobs(nb) if fb.get("token_logprobs") else None   # a masked row keeps its settled values
             again = []
             for r in pending:
                 s = seqs[r, n_prompt:total].astype(np.int64)
@@ -676,6 +727,8 @@ def _decode_with_fallback(engine, spec, fb, active, init_rows, n_prompt, max_len
                 if s[-1] == spec.eos_token_id:
                     s = s[:-1]
                 kept[r] = (s, np.array(token_ts[r], copy=True), skip)
+                if tok_lp is not None:
+                    kept[r] += (np.array(tok_lp[r], copy=True),)
                 if needs and not last:
                     again.append(r)
             pending = again

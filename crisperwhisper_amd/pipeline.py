@@ -311,14 +311,33 @@ def _check_seed(seed) -> int:
     return int(seed)
 
 
+def scored_words(vocab, outputs, token_logprobs, warn=None):
+    """``collate.decode_asr(outputs, return_timestamps="word")`` with "logprob" on every word: the float64 sum of
+    ``token_logprobs`` (one array per entry of ``outputs``, one value per token) over the collator's own token group of the word.
+    The groups address the concatenation of all windows' tokens, so a token the seam merge drops counts in no word."""
+    if len(token_logprobs) != len(outputs) or any(len(a) != len(o["tokens"]) for a, o in zip(token_logprobs, outputs)):
+        raise ValueError("scored_words: one log-probability per token of every window is required")
+    text, words, groups = collate.decode_asr(vocab, outputs, time_precision=0.02, warn=warn, return_timestamps="word",
+                                             return_token_groups=True)
+    flat = np.concatenate([np.asarray(a, np.float64) for a in token_logprobs]) if token_logprobs else np.zeros(0, np.float64)
+    for w, g in zip(words, groups):
+        w["logprob"] = float(np.sum(flat[g]))
+    return text, words
+
+
 class CrisperWhisperPipeline:
     def __init__(self, model, tokenizer=None, feature_extractor=None, chunk_length_s=0, stride_length_s=None,
                  batch_size=1, return_timestamps=None, torch_dtype=None, dtype=None, device=None,
                  shard: Optional[dist.Shard] = None, contexts: int = 1, cross_kv_dtype: Optional[str] = None,
                  encoder_gemm_dtype: Optional[str] = None,
                  engines: Optional[List[Engine]] = None, num_beams: Optional[int] = None,
-                 sampling_seed: Optional[int] = None, **kwargs):
-        """``num_beams`` (construction time): the widest beam the contexts are provisioned for -- decoder rows =
+                 sampling_seed: Optional[int] = None, return_scores: bool = False, **kwargs):
+        """``return_scores`` (here or per call, default False): with ``return_timestamps="word"`` every chunk gains
+        "logprob", the float64 sum over its tokens of ``logits[tok] - logsumexp(logits[:vocab])`` on the raw logits of the
+        decode step that chose each token -- grouped by the collator's own token groups, so tokens dropped in a seam
+        overlap count in no word.
+
+        ``num_beams`` (construction time): the widest beam the contexts are provisioned for -- decoder rows =
         batch_size x num_beams, at most 64.  Default 5 = ``AutomaticSpeechRecognitionPipeline._default_generation_config``
         of the installed transformers (TF/pipelines/automatic_speech_recognition.py:160-163), which is what a call
         without ``generate_kwargs`` runs (REF/transcribe.py:33); pass ``generate_kwargs={"num_beams": 1}`` per call for
@@ -348,6 +367,7 @@ class CrisperWhisperPipeline:
         self.max_rows = min(64, self.batch_size * int(num_beams or DEFAULT_NUM_BEAMS))
         self.max_rows = max(self.max_rows, min(64, self.batch_size))
         self.return_timestamps = return_timestamps
+        self.return_scores = bool(return_scores)
         # the key of the engine's sampler for calls with a positive temperature / temperature fallback; None: such calls must
         # name one themselves (a call without any seed is refused, it does not draw from a hidden default)
         self.sampling_seed = None if sampling_seed is None else _check_seed(sampling_seed)
@@ -408,9 +428,13 @@ class CrisperWhisperPipeline:
         return self._run_one(inputs, **kwargs)
 
     def _run_one(self, inputs, return_timestamps=None, generate_kwargs=None, chunk_length_s=None,
-                 stride_length_s=None, return_language=None, sampling_seed=None, **unused):
+                 stride_length_s=None, return_language=None, sampling_seed=None, return_scores=None, **unused):
         seed = self.sampling_seed if sampling_seed is None else _check_seed(sampling_seed)
         rt = return_timestamps if return_timestamps is not None else self.return_timestamps
+        scores = self.return_scores if return_scores is None else bool(return_scores)
+        if scores and rt != "word":
+            raise ValueError('return_scores=True gives every word its log-probability: it needs return_timestamps="word" '
+                             f"(got {rt!r}; segment-level scores are not implemented)")
         if not (rt == "word" or rt is True):
             raise ValueError("crisperwhisper_amd implements the timestamped paths: pass return_timestamps='word' "
                              "(CrisperWhisper's purpose, REF/transcribe.py:28) or True (segment-level chunks, the "
@@ -464,14 +488,15 @@ class CrisperWhisperPipeline:
                 num_beams=num_beams, stats=st, logprob_threshold=gk.get("logprob_threshold"),
                 no_speech_threshold=gk.get("no_speech_threshold"), prompt_ids=gk.get("prompt_ids"),
                 temperature=gk.get("temperature"), compression_ratio_threshold=gk.get("compression_ratio_threshold"),
-                sampling_seed=seed or 0, item_ids=idxs)
+                sampling_seed=seed or 0, item_ids=idxs, **({"return_token_logprobs": True} if scores else {}))
             if "fallback" in st:
                 fallback_trace.extend(st["fallback"])
             rs = []
             for k, i in enumerate(idxs):
                 n_tok = len(out["token_timestamps"][k])
                 stride = tuple(x / sr for x in windows[i][2])
-                rs.append(dist.pack_record(i, out["sequences"][k][:n_tok], out["token_timestamps"][k], stride))
+                rs.append(dist.pack_record(i, out["sequences"][k][:n_tok], out["token_timestamps"][k], stride,
+                                           out["token_logprobs"][k] if scores else None))
             return rs, st.get("generate_calls", 0)
 
         per = self.batch_size
@@ -497,20 +522,24 @@ class CrisperWhisperPipeline:
         recs = [r for rs, _ in results for r in rs]
         self.stats["fallback"] = sorted(fallback_trace, key=lambda d: (d["item"], d["seek"], d["temperature_index"]))
         self.stats["generate_calls"] = self.stats.get("generate_calls", 0) + sum(c for _, c in results)
-        recs = np.stack(recs) if recs else np.zeros((0, dist.REC_WORDS), np.int32)
+        recs = np.stack(recs) if recs else np.zeros((0, dist.REC_WORDS_SCORED if scores else dist.REC_WORDS), np.int32)
         max_per_rank = max(h - l for l, h in dist.shard_bounds(len(windows), self.shard.world))
         t_ph.append(_time.perf_counter())
         allr = self.shard.all_gather_records(recs, max_per_rank)
         t_ph.append(_time.perf_counter())
-        outputs = []
+        outputs, token_lp = [], []
         for r in allr:
-            _, toks, ts, stride = dist.unpack_record(r)
+            _, toks, ts, stride, *lp = dist.unpack_record(r)
             o = {"tokens": toks, "token_timestamps": ts}
             if with_stride:
                 o["stride"] = stride
             outputs.append(o)
-        text, words = collate.decode_asr(self.vocab, outputs, time_precision=0.02, warn=logger.warning,
-                                         return_timestamps="word" if rt == "word" else True)
+            token_lp.extend(lp)
+        if scores:
+            text, words = scored_words(self.vocab, outputs, token_lp, warn=logger.warning)
+        else:
+            text, words = collate.decode_asr(self.vocab, outputs, time_precision=0.02, warn=logger.warning,
+                                             return_timestamps="word" if rt == "word" else True)
         t_ph.append(_time.perf_counter())
         # where the wall time of the last call went on this rank (bench.py's long-form leg prints it: the scaling model of
         # DESIGN.md section 5 needs the rank-local part, which shrinks with the rank count, apart from the rest, which does not)

@@ -180,6 +180,22 @@ int32_t cw_decode_rows(cw_ctx* ctx, int32_t nb, const int32_t* prompt, int32_t n
                        int32_t* lengths, int32_t* argmax_out);
 int32_t cw_no_speech_probs(cw_ctx* ctx, int32_t nb, int32_t sot_token, float* out /* [nb] */);
 int32_t cw_get_avg_logprobs(cw_ctx* ctx, float* out /* [nb] */, int32_t nb);
+/* Per-token log-probabilities of the free-running decode (word confidence).  With the switch on (default off), the sampler
+ * kernels store for every row and sequence position t it writes
+ *     logprob[t] = logits[tok_t] - logsumexp(logits[0 .. vocab_size-1]),
+ * logits = the raw f32 logits of the step that produced tok_t (no suppress lists, no timestamp rule, no temperature; pad
+ * columns never count), tok_t = what was written at t: the arg-max, the sampled or the forced token.  It is the quantity
+ * cw_score_tokens reports, taken where the token is chosen: no extra launch, no extra forward.  expf / logf throughout.
+ * cw_set_token_logprobs allocates a [max_batch][max_target_positions] f32 buffer on first use and drops the captured decode
+ * steps when the value changes.  cw_get_token_logprobs is valid after cw_decode / cw_decode_rows and aligned with `sequences`:
+ * NaN marks prompt positions, positions behind a row's end and rows never decoded (0.0 is a legitimate value); a row that
+ * cw_decode_rows masks keeps the values of the decode before.  With the switch on a lost in-launch hand-off repeats the
+ * whole cw_decode call on the launch-per-stage kernels (as with a logprob threshold) instead of resuming mid-sequence.
+ * cw_transcribe / cw_transcribe_prompted carry the values through segment slicing exactly as they carry token timestamps;
+ * cw_get_transcribe_token_logprobs returns those of the last call, aligned with its `tokens` (NaN behind lens[i]).          */
+int32_t cw_set_token_logprobs(cw_ctx* ctx, int32_t on);
+int32_t cw_get_token_logprobs(cw_ctx* ctx, float* out /* [nb][max_target_positions] */, int32_t nb);
+int32_t cw_get_transcribe_token_logprobs(cw_ctx* ctx, float* out /* [B][cap] */, int32_t B, int32_t cap);
 int32_t cw_get_logits(cw_ctx* ctx, float* out /* [nb][vocab] */, int32_t nb);       /* last sampled step */
 int32_t cw_set_logits_capture(cw_ctx* ctx, float* host_buf, int32_t max_steps);    /* [steps][nb][vocab] */
 int32_t cw_get_alignment(cw_ctx* ctx, float* out /* [nb][n_align][L][1500] */, int32_t nb, int32_t L);
@@ -242,6 +258,9 @@ cw_beam_host* cw_beam_host_new(int32_t n_items, int32_t num_beams, int32_t n_pro
 int32_t cw_beam_host_step(cw_beam_host* s, const float* cand_logprob, const int32_t* cand_token /* [rows][2 * num_beams] */,
                           int32_t* parent, int32_t* token /* [rows] */);
 int32_t cw_beam_host_result(const cw_beam_host* s, int64_t* sequences, int32_t* beam_indices, float* score);
+/* The candidate log-probability (the value handed to cw_beam_host_step, before the running score is added) of every generated
+ * token of the best hypothesis, followed along its ancestry: out [n_items][max_length - n_prompt], NaN behind the end.       */
+int32_t cw_beam_host_token_logprobs(const cw_beam_host* s, float* out);
 void cw_beam_host_free(cw_beam_host* s);
 
 /* cw_token_timestamps: _extract_token_timestamps (generation_whisper.py:241-381) on the retained rows:
@@ -563,6 +582,12 @@ int32_t cw_test_sample(cw_ctx* ctx, int32_t nb, const float* logits, const int32
 int32_t cw_test_sample_seeded(cw_ctx* ctx, int32_t nb, const float* logits, const int32_t* ids, int32_t t, int32_t n_prompt,
                               int32_t min_new_tokens, int32_t max_length, float temperature, uint64_t seed,
                               const uint64_t* row_streams, int32_t* choice_out);
+/* cw_test_sample_seeded with the per-token log-probability store on for this call: lp_out [nb] = the value stored for sequence
+ * index t.  forced_tok [nb] (NULL: none; -1: row not forced) is written at t instead of the choice; choice_out stays the
+ * un-forced choice, as cw_decode's argmax_out.                                                                             */
+int32_t cw_test_sample_logprobs(cw_ctx* ctx, int32_t nb, const float* logits, const int32_t* ids, int32_t t, int32_t n_prompt,
+                                int32_t min_new_tokens, int32_t max_length, float temperature, uint64_t seed,
+                                const uint64_t* row_streams, const int32_t* forced_tok, int32_t* choice_out, float* lp_out);
 
 /* ---- measurement -------------------------------------------------------------------------------------- */
 #define CW_STAGE_MEL 0
@@ -596,7 +621,7 @@ int32_t cw_handoff_fallbacks(cw_ctx* ctx);
  * hand-off, the host sees it with the one-step lag of its "rows still running" read, rebuilds the sampler's per-row state from the
  * token ids (/root/reference has no counterpart; the state is that of transformers' WhisperTimeStampLogitsProcessor +
  * stopping criteria, generation_whisper.py / logits_process.py:1933-2048) and resumes at that position.  The whole call is
- * repeated instead while a logprob threshold is set (its running sums cannot be rebuilt from ids). */
+ * repeated instead while a logprob threshold is set (its running sums cannot be rebuilt from ids) or cw_set_token_logprobs is on. */
 int32_t cw_handoff_resumes(cw_ctx* ctx);
 
 #ifdef __cplusplus

@@ -7,8 +7,13 @@ geometry: large-v3 shape, aligned synthetic weights, --rows x 30 s clips residen
                     --temperature with --redo of the rows live (the others idle through the step) and its token timestamps;
                     the stage timers carry the number of encoder passes of either call
 
+  --token-logprobs  the step measurement once more with cw_set_token_logprobs on (the sampler also reduces the raw log-sum-exp
+                    of every row and stores log_softmax(raw)[token]): step_*_logprobs_ms, off and on in the same build
+  --no-fallback-round  leave the fallback round out
+
 Best of --reps after one warm-up, wall time around the call with the stream synchronised.
-usage: python tools/sample_step_bench.py [--dtype bf16] [--rows 8] [--tokens 128] [--temperature 0.6] [--redo 2] [--reps 5]"""
+usage: python tools/sample_step_bench.py [--dtype bf16] [--rows 8] [--tokens 128] [--temperature 0.6] [--redo 2] [--reps 5]
+                                         [--token-logprobs] [--no-fallback-round]"""
 import argparse, json, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
@@ -23,6 +28,7 @@ def main():
     ap.add_argument("--dtype", default="bf16"); ap.add_argument("--rows", type=int, default=8)
     ap.add_argument("--tokens", type=int, default=128); ap.add_argument("--temperature", type=float, default=0.6)
     ap.add_argument("--redo", type=int, default=2); ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--token-logprobs", action="store_true"); ap.add_argument("--no-fallback-round", action="store_true")
     a = ap.parse_args()
     g, v = syn.large_v3_geometry()
     spec = syn.model_spec(g, v, n_align=15)
@@ -39,12 +45,19 @@ def main():
 
     def steps():
         eng.decode(prompt, 3 + T, min_new_tokens=T)
-    for name, temp in (("greedy", 0.0), ("sampling", a.temperature)):
-        eng.set_sampling(temp, 1, streams)
-        ms, split = timed(eng, steps, a.reps)
-        out[f"step_{name}_ms"] = round(split["decode"] / T, 4)
-        out[f"decode_{name}_wall_ms"] = ms
+    for on in ((False, True) if a.token_logprobs else (False,)):
+        eng.set_token_logprobs(on)
+        for name, temp in (("greedy", 0.0), ("sampling", a.temperature)):
+            eng.set_sampling(temp, 1, streams)
+            ms, split = timed(eng, steps, a.reps)
+            out[f"step_{name}{'_logprobs' if on else ''}_ms"] = round(split["decode"] / T, 4)
+            out[f"decode_{name}{'_logprobs' if on else ''}_wall_ms"] = ms
     eng.set_sampling(0.0)
+    eng.set_token_logprobs(False)
+    if a.no_fallback_round:
+        print(json.dumps(out))
+        eng.close()
+        return
 
     def round_(redo):
         def fn():
