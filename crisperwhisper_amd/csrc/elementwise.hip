@@ -214,6 +214,12 @@ __device__ inline ArgPair wave_argmax(ArgPair a) {   // same DPP scan as wave_su
 #define SAMPLE_NS 16
 struct SamplePart { float bt_v; int bt_i; float bs_v; int bs_i; float ts_sum; float pad[3]; };
 struct SamplePert { float pt_v; int pt_i; float ps_v; int ps_i; };   // sampling: best perturbed text / timestamp token of a slice
+// top_logprobs (include/crisperwhisper.h, cw_set_top_logprobs): the p.top_k best raw logits of a slice, best first, in a record
+// of CW_TOP_LOGPROBS_MAX pairs per (row, slice); a slice with fewer candidates pads with the identity of arg_better
+struct TopPair { float v; int i; };
+__device__ inline bool arg_after(ArgPair c, ArgPair prev) {   // c comes strictly after prev in the order of arg_better
+    return c.v < prev.v || (c.v == prev.v && c.i > prev.i);
+}
 
 // Seeded sampling (include/crisperwhisper.h, cw_set_sampling): Gumbel-max.  The token drawn at temperature T is
 // argmax_v(s_v / T + g_v) over the allowed tokens, g_v = -log(-log(u_v)), an exact draw from softmax(s / T); restricted to a
@@ -239,6 +245,9 @@ __device__ inline float gumbel_from_bits(unsigned x) {
     else e = -log1pf(-(((float)((1u << 24) - n) - 0.5f) * 5.9604644775390625e-08f));
     return -logf(e);
 }
+// TOPK (block-uniform, a template parameter so that the instantiation without it keeps its registers): also emit the slice's
+// p.top_k best raw candidates (v < V, x > -inf: masked tokens count, pad columns and NaN do not) into p.top_part.
+template <bool TOPK>
 __global__ __launch_bounds__(256) void sample_partial_kernel(SampleParams p, SamplePart* __restrict__ part) {
     __shared__ float s_f[64];
     __shared__ int s_i[64];
@@ -267,6 +276,13 @@ __global__ __launch_bounds__(256) void sample_partial_kernel(SampleParams p, Sam
     float sv[4][4]; int nmine = 0;                                         // this thread's allowed timestamp scores
     float tv[4][4];                                                        // ... and allowed text scores (p.lp_sum only)
     float rm = -INFINITY, rs = 0.f;                                        // p.tok_lp: online raw max / sum exp(x - rm), v < V
+    float rv[4][4];                                                        // TOPK: this thread's raw candidates (-inf: none)
+    if (TOPK) {
+#pragma unroll
+        for (int it = 0; it < 4; ++it)
+#pragma unroll
+            for (int j = 0; j < 4; ++j) rv[it][j] = -INFINITY;
+    }
     for (int i4 = lo4 + tid, it = 0; i4 < hi4; i4 += 256, ++it) {
         const float4 x = lg4[i4]; const uchar4 mk = mk4[i4];
         const float xs[4] = {x.x, x.y, x.z, x.w};
@@ -292,6 +308,7 @@ __global__ __launch_bounds__(256) void sample_partial_kernel(SampleParams p, Sam
                 }
             }
             if (it < 4) { sv[it][j] = (v >= tb && v < p.V) ? val : -INFINITY; tv[it][j] = (v < tb) ? val : -INFINITY; }
+            if (TOPK && it < 4) rv[it][j] = (v < p.V && xs[j] > -INFINITY) ? xs[j] : -INFINITY;   // false for NaN
         }
         if (p.tok_lp) {                                         // block-uniform; masked tokens count, pad columns do not
             float gm = -INFINITY;
@@ -339,6 +356,32 @@ __global__ __launch_bounds__(256) void sample_partial_kernel(SampleParams p, Sam
         __syncthreads();
         raw_s = block_sum(rm > -INFINITY ? rs * expf(rm - raw_m) : 0.f, s_f);
     }
+    if (TOPK) {
+        // p.top_k rounds of "best candidate strictly after the previous winner"; the waves' winners alternate between two
+        // halves of s_tf / s_ti, so one barrier per round is enough
+        __shared__ float s_tf[8];
+        __shared__ int s_ti[8];
+        TopPair* rec = (TopPair*)p.top_part + ((size_t)b * SAMPLE_NS + sl) * CW_TOP_LOGPROBS_MAX;
+        ArgPair prev = {INFINITY, -1};
+        for (int r = 0; r < p.top_k; ++r) {
+            ArgPair c = {-INFINITY, 0x7fffffff};
+#pragma unroll
+            for (int it = 0; it < 4; ++it)
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    const ArgPair q = {rv[it][j], (lo4 + tid + it * 256) * 4 + j};
+                    if (q.v > -INFINITY && arg_after(q, prev)) c = arg_better(c, q);
+                }
+            c = wave_argmax(c);
+            const int h = (r & 1) * 4;
+            if (lane == 0) { s_tf[h + wave] = c.v; s_ti[h + wave] = c.i; }
+            __syncthreads();
+            c = {-INFINITY, 0x7fffffff};
+            for (int w = 0; w < 4; ++w) c = arg_better(c, ArgPair{s_tf[h + w], s_ti[h + w]});
+            if (tid == 0) { TopPair o; o.v = c.v; o.i = c.i; rec[r] = o; }
+            prev = c;                                           // (-inf, INT_MAX) once the slice is exhausted: nothing comes after it
+        }
+    }
     if (tid == 0 && b == 0 && sl == 0) {
         *p.n_unfinished = 0;                                     // stage 2 (a later launch) counts the running rows into it
         if (p.epoch) *p.epoch += 1u;                             // the next decoder forward tags its granules with a fresh epoch (declayer.hip)
@@ -365,7 +408,7 @@ __global__ __launch_bounds__(256) void sample_partial_kernel(SampleParams p, Sam
     }
 }
 
-template <typename T>
+template <typename T, bool TOPK>
 __global__ __launch_bounds__(1024) void sample_kernel(SampleParams p) {
     __shared__ float s_f[64];
     __shared__ int s_i[64];
@@ -401,6 +444,39 @@ __global__ __launch_bounds__(1024) void sample_kernel(SampleParams p) {
     for (int i = 0; i < SAMPLE_NS; ++i)
         if (pr[i].bs_v > -INFINITY) acc += pr[i].ts_sum * expf(pr[i].bs_v - M);
 
+    if (TOPK) {
+        // top_logprobs: wave 0 merges the SAMPLE_NS x p.top_k slice winners (two pairs per lane) into the row's p.top_k best and
+        // stores id and x - (Mr + logf(Sr)) at [b][t][0 .. top_k-1], under the conditions and with the normaliser of the
+        // tok_lp store below (a row masked by cw_decode_rows has fin_in == 2, so was_finished covers it)
+        if (wave == 0 && !was_finished && n_gen >= 0) {
+            float Mr = -INFINITY, Sr = 0.f;
+            for (int i = 0; i < SAMPLE_NS; ++i) Mr = fmaxf(Mr, pr[i].pad[1]);
+            for (int i = 0; i < SAMPLE_NS; ++i)
+                if (pr[i].pad[1] > -INFINITY) Sr += pr[i].pad[2] * expf(pr[i].pad[1] - Mr);
+            const float norm = Mr + logf(Sr);
+            const TopPair* tp = (const TopPair*)p.top_part + (size_t)b * SAMPLE_NS * CW_TOP_LOGPROBS_MAX;
+            const int k = p.top_k;
+            const ArgPair none = {-INFINITY, 0x7fffffff};
+            const bool have = (lane & (CW_TOP_LOGPROBS_MAX - 1)) < k;           // rank inside the slice record
+            const ArgPair c0 = have ? ArgPair{tp[lane].v, tp[lane].i} : none;
+            const ArgPair c1 = have ? ArgPair{tp[lane + 64].v, tp[lane + 64].i} : none;
+            ArgPair prev = {INFINITY, -1}, mine = none;
+            for (int r = 0; r < k; ++r) {
+                ArgPair c = none;
+                if (arg_after(c0, prev)) c = arg_better(c, c0);
+                if (arg_after(c1, prev)) c = arg_better(c, c1);
+                c = wave_argmax(c);
+                if (lane == r) mine = c;
+                prev = c;
+            }
+            if (lane < k) {
+                const size_t o = ((size_t)b * p.ids_stride + t) * CW_TOP_LOGPROBS_MAX + lane;
+                const bool ok = mine.v > -INFINITY;                           // fewer than lane + 1 candidates in the row
+                p.top_id[o] = ok ? mine.i : -1;
+                p.top_lp[o] = ok ? mine.v - norm : NAN;
+            }
+        }
+    }
     if (tid == 0) {
         bool force_ts = (acc > 0.f) && (logf(acc) > bt.v - M);
         int choice;
@@ -809,11 +885,20 @@ int cw_launch_align_gather(const float* align, const int* row_of_pos, int n_item
 
 int cw_launch_sample(const SampleParams& p, hipStream_t st) {
     if (!p.partials || (p.ldv >> 2) > SAMPLE_NS * 1024 || (p.ldv & 3)) return CW_ERR_INVALID;
-    hipLaunchKernelGGL(sample_partial_kernel, dim3(p.B, SAMPLE_NS), dim3(256), 0, st, p, (SamplePart*)p.partials);
+    if (p.top_k != 0) {                                         // top_logprobs: the instantiations that also select
+        if (p.top_k < 0 || p.top_k > CW_TOP_LOGPROBS_MAX || !p.top_part || !p.top_id || !p.top_lp || !p.tok_lp) return CW_ERR_INVALID;
+        hipLaunchKernelGGL(sample_partial_kernel<true>, dim3(p.B, SAMPLE_NS), dim3(256), 0, st, p, (SamplePart*)p.partials);
+        if (p.embed_bf16)
+            hipLaunchKernelGGL((sample_kernel<bf16_t, true>), dim3(p.B), dim3(256), 0, st, p);
+        else
+            hipLaunchKernelGGL((sample_kernel<float, true>), dim3(p.B), dim3(256), 0, st, p);
+        return CW_OK;
+    }
+    hipLaunchKernelGGL(sample_partial_kernel<false>, dim3(p.B, SAMPLE_NS), dim3(256), 0, st, p, (SamplePart*)p.partials);
     if (p.embed_bf16)
-        hipLaunchKernelGGL((sample_kernel<bf16_t>), dim3(p.B), dim3(256), 0, st, p);
+        hipLaunchKernelGGL((sample_kernel<bf16_t, false>), dim3(p.B), dim3(256), 0, st, p);
     else
-        hipLaunchKernelGGL((sample_kernel<float>), dim3(p.B), dim3(256), 0, st, p);
+        hipLaunchKernelGGL((sample_kernel<float, false>), dim3(p.B), dim3(256), 0, st, p);
     return CW_OK;
 }
 

@@ -155,6 +155,12 @@ struct cw_ctx {
     float* d_tok_lp = nullptr;                                // [Bm][max_target] log_softmax(raw logits)[token] (cw_set_token_logprobs)
     bool tok_lp_on = false;
     std::vector<std::vector<float>> tr_lp;                    // ... of the last cw_transcribe, per item, aligned with its tokens
+    // the top_k best raw logits of every step (cw_set_top_logprobs; needs tok_lp_on)
+    int top_k = 0;                                            // 0: off
+    int* d_top_id = nullptr; float* d_top_lp = nullptr;       // [Bm][max_target][CW_TOP_LOGPROBS_MAX]
+    void* d_top_part = nullptr;                               // [Bm][16][CW_TOP_LOGPROBS_MAX] (value, id) pairs of the sampler's stage 1
+    std::vector<std::vector<int>> tr_top_id;                  // ... of the last cw_transcribe: top_k entries per token of every item
+    std::vector<std::vector<float>> tr_top_lp;
     float logprob_thr = NAN, no_speech_thr = NAN;             // cw_set_thresholds (NaN: unset)
     void* d_sample_part = nullptr;            // [Bm][16] 32-byte slice records of the two-stage sampler
     void* d_sample_pert = nullptr;            // [Bm][16] 16-byte records of the perturbed winners (seeded sampling)
@@ -1535,6 +1541,7 @@ static int launch_sample(cw_ctx* c, int nb, bool forced) {
     sp.partials = c->d_sample_part;
     if (c->score_tokens) { sp.lp_sum = c->d_lp_sum; sp.lp_cnt = c->d_lp_cnt; }
     if (c->tok_lp_on) sp.tok_lp = c->d_tok_lp;
+    if (c->tok_lp_on && c->top_k > 0) { sp.top_k = c->top_k; sp.top_part = c->d_top_part; sp.top_id = c->d_top_id; sp.top_lp = c->d_top_lp; }
     sp.epoch = c->d_epoch;
     sp.samp = c->d_samp; sp.pert = c->d_sample_pert;
     (void)forced;
@@ -1756,6 +1763,10 @@ static int decode_once(cw_ctx* c, int32_t nb, const int32_t* prompt, int32_t n_p
         HIPCHK(c, hipMemsetAsync(c->d_lp_sum, 0, nb * 4, c->st));
         HIPCHK(c, hipMemsetAsync(c->d_lp_cnt, 0, nb * 4, c->st));
         if (c->tok_lp_on) HIPCHK(c, hipMemsetAsync(c->d_tok_lp, 0xff, (size_t)nb * TGT * 4, c->st));   // all-ones = NaN
+        if (c->top_k > 0) {                                                                             // ... and id -1
+            HIPCHK(c, hipMemsetAsync(c->d_top_id, 0xff, (size_t)nb * TGT * CW_TOP_LOGPROBS_MAX * 4, c->st));
+            HIPCHK(c, hipMemsetAsync(c->d_top_lp, 0xff, (size_t)nb * TGT * CW_TOP_LOGPROBS_MAX * 4, c->st));
+        }
     } else {
         HIPCHK(c, hipMemcpyAsync(c->d_finished, fin0.data(), nb * 4, hipMemcpyHostToDevice, c->st));
         for (int b = 0; b < nb; ++b)
@@ -1763,6 +1774,11 @@ static int decode_once(cw_ctx* c, int32_t nb, const int32_t* prompt, int32_t n_p
                 HIPCHK(c, hipMemsetAsync(c->d_lp_sum + b, 0, 4, c->st));
                 HIPCHK(c, hipMemsetAsync(c->d_lp_cnt + b, 0, 4, c->st));
                 if (c->tok_lp_on) HIPCHK(c, hipMemsetAsync(c->d_tok_lp + (size_t)b * TGT, 0xff, (size_t)TGT * 4, c->st));
+                if (c->top_k > 0) {
+                    const size_t row = (size_t)TGT * CW_TOP_LOGPROBS_MAX;
+                    HIPCHK(c, hipMemsetAsync(c->d_top_id + (size_t)b * row, 0xff, row * 4, c->st));
+                    HIPCHK(c, hipMemsetAsync(c->d_top_lp + (size_t)b * row, 0xff, row * 4, c->st));
+                }
             }
     }
     HIPCHK(c, hipMemsetAsync(c->d_last_ts, 0xff, nb * 4, c->st));
@@ -1889,6 +1905,7 @@ int32_t cw_set_thresholds(cw_ctx* c, float logprob_threshold, float no_speech_th
 // ---- per-token log-probabilities of the free-running decode (include/crisperwhisper.h) -------------------------------------
 int32_t cw_set_token_logprobs(cw_ctx* c, int32_t on) {
     const bool want = on != 0;
+    if (!want && c->top_k > 0) CWCHK(c, cw_set_top_logprobs(c, 0));   // the alternatives share this switch's normaliser
     const size_t n = (size_t)c->Bm * c->d.max_target_positions;
     if (want && !c->d_tok_lp) {
         CWCHK(c, dmalloc(c, &c->d_tok_lp, n * 4, false));
@@ -1918,6 +1935,57 @@ int32_t cw_get_transcribe_token_logprobs(cw_ctx* c, float* out, int32_t B, int32
         if (n > cap) return fail(c, CW_ERR_INVALID, "item %d holds %d tokens, capacity %d", i, n, cap);
         memcpy(out + (size_t)i * cap, c->tr_lp[i].data(), (size_t)n * 4);
         for (int k = n; k < cap; ++k) out[(size_t)i * cap + k] = NAN;
+    }
+    return CW_OK;
+}
+
+// ---- top_logprobs: the k best raw logits of every step of the free-running decode (include/crisperwhisper.h) ---------------
+int32_t cw_set_top_logprobs(cw_ctx* c, int32_t k) {
+    if (k < 0 || k > CW_TOP_LOGPROBS_MAX) return fail(c, CW_ERR_INVALID, "set_top_logprobs: k=%d outside 0 .. %d", k, CW_TOP_LOGPROBS_MAX);
+    if (k > 0 && !c->tok_lp_on) return fail(c, CW_ERR_STATE, "top_logprobs needs token log-probabilities (cw_set_token_logprobs)");
+    const size_t n = (size_t)c->Bm * c->d.max_target_positions * CW_TOP_LOGPROBS_MAX;
+    if (k > 0 && !c->d_top_id) {
+        CWCHK(c, dmalloc(c, &c->d_top_part, (size_t)c->Bm * 16 * CW_TOP_LOGPROBS_MAX * 8));
+        CWCHK(c, dmalloc(c, &c->d_top_lp, n * 4, false));
+        CWCHK(c, dmalloc(c, &c->d_top_id, n * 4, false));
+    }
+    if (k != c->top_k) {
+        HIPCHK(c, hipStreamSynchronize(c->st));
+        if (k > 0) {                                                  // nothing decoded under this value yet
+            HIPCHK(c, hipMemset(c->d_top_id, 0xff, n * 4));          // all-ones: id -1, value NaN
+            HIPCHK(c, hipMemset(c->d_top_lp, 0xff, n * 4));
+        }
+        c->top_k = k;
+        c->tr_top_id.clear(); c->tr_top_lp.clear();
+        drop_step_graphs(c);
+    }
+    return CW_OK;
+}
+int32_t cw_get_top_logprobs(cw_ctx* c, int32_t* ids_out, float* lp_out, int32_t nb) {
+    if (c->top_k < 1) return fail(c, CW_ERR_STATE, "top_logprobs is off (cw_set_top_logprobs)");
+    if (!ids_out || !lp_out || nb < 1 || nb > c->Bm) return fail(c, CW_ERR_INVALID, "get_top_logprobs: nb=%d outside 1 .. %d", nb, c->Bm);
+    const size_t n = (size_t)nb * c->d.max_target_positions, k = (size_t)c->top_k;
+    std::vector<int> hi(n * CW_TOP_LOGPROBS_MAX); std::vector<float> hl(n * CW_TOP_LOGPROBS_MAX);
+    HIPCHK(c, hipStreamSynchronize(c->st));
+    HIPCHK(c, hipMemcpy(hi.data(), c->d_top_id, hi.size() * 4, hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(hl.data(), c->d_top_lp, hl.size() * 4, hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < n; ++i) {                                  // device rows are CW_TOP_LOGPROBS_MAX wide, the caller's k
+        memcpy(ids_out + i * k, &hi[i * CW_TOP_LOGPROBS_MAX], k * 4);
+        memcpy(lp_out + i * k, &hl[i * CW_TOP_LOGPROBS_MAX], k * 4);
+    }
+    return CW_OK;
+}
+int32_t cw_get_transcribe_top_logprobs(cw_ctx* c, int32_t* ids_out, float* lp_out, int32_t B, int32_t cap) {
+    if (c->top_k < 1) return fail(c, CW_ERR_STATE, "top_logprobs is off (cw_set_top_logprobs)");
+    if (!ids_out || !lp_out || B < 1 || (size_t)B != c->tr_top_id.size())
+        return fail(c, CW_ERR_STATE, "get_transcribe_top_logprobs: B=%d but the last cw_transcribe had %d items", B, (int)c->tr_top_id.size());
+    const size_t k = (size_t)c->top_k;
+    for (int i = 0; i < B; ++i) {
+        const size_t n = c->tr_top_id[i].size() / k;
+        if (n > (size_t)cap) return fail(c, CW_ERR_INVALID, "item %d holds %d tokens, capacity %d", i, (int)n, cap);
+        memcpy(ids_out + (size_t)i * cap * k, c->tr_top_id[i].data(), n * k * 4);
+        memcpy(lp_out + (size_t)i * cap * k, c->tr_top_lp[i].data(), n * k * 4);
+        for (size_t j = n * k; j < (size_t)cap * k; ++j) { ids_out[(size_t)i * cap * k + j] = -1; lp_out[(size_t)i * cap * k + j] = NAN; }
     }
     return CW_OK;
 }
@@ -2311,8 +2379,11 @@ int32_t cw_transcribe_prompted(cw_ctx* c, int32_t B, const int32_t* num_frames, 
     if (max_length <= n_prompt) return fail(c, CW_ERR_INVALID, "max_length %d leaves no room after %d decoder input tokens", max_length, n_prompt);
     std::vector<long> seek(B, 0);
     std::vector<std::vector<int>> out_tok(B);
-    std::vector<std::vector<float>> out_ts(B), out_lp(B);
+    std::vector<std::vector<float>> out_ts(B), out_lp(B), out_tl(B);
+    std::vector<std::vector<int>> out_ti(B);
     c->tr_lp.clear();
+    c->tr_top_id.clear(); c->tr_top_lp.clear();
+    const int top_k = c->tok_lp_on ? c->top_k : 0;
     int passes = 0;
     for (;;) {
         std::vector<int> active, a_seek, a_n, a_nf;
@@ -2336,6 +2407,11 @@ int32_t cw_transcribe_prompted(cw_ctx* c, int32_t B, const int32_t* num_frames, 
         if (thr) CWCHK(c, cw_get_avg_logprobs(c, alp.data(), nb));
         std::vector<float> tlp;
         if (c->tok_lp_on) { tlp.resize((size_t)nb * TGT); CWCHK(c, cw_get_token_logprobs(c, tlp.data(), nb)); }
+        std::vector<int> tti; std::vector<float> ttl;
+        if (top_k > 0) {
+            tti.resize((size_t)nb * TGT * top_k); ttl.resize(tti.size());
+            CWCHK(c, cw_get_top_logprobs(c, tti.data(), ttl.data(), nb));
+        }
         int total = 0;
         for (int r = 0; r < nb; ++r) total = ln[r] > total ? ln[r] : total;
         const int L = total - 1;
@@ -2369,6 +2445,11 @@ int32_t cw_transcribe_prompted(cw_ctx* c, int32_t B, const int32_t* num_frames, 
                 out_tok[i].push_back(s[k]);
                 out_ts[i].push_back(ts[(size_t)r * (L + 1) + n_prompt + k] + off32);
                 if (c->tok_lp_on) out_lp[i].push_back(tlp[(size_t)r * TGT + n_prompt + k]);
+                if (top_k > 0) {
+                    const size_t o = ((size_t)r * TGT + n_prompt + k) * top_k;
+                    out_ti[i].insert(out_ti[i].end(), tti.begin() + o, tti.begin() + o + top_k);
+                    out_tl[i].insert(out_tl[i].end(), ttl.begin() + o, ttl.begin() + o + top_k);
+                }
             }
             seek[i] += advance;
         }
@@ -2381,6 +2462,7 @@ int32_t cw_transcribe_prompted(cw_ctx* c, int32_t B, const int32_t* num_frames, 
         memcpy(token_ts + (size_t)i * cap, out_ts[i].data(), (size_t)n * 4);
     }
     if (c->tok_lp_on) c->tr_lp = std::move(out_lp);
+    if (top_k > 0) { c->tr_top_id = std::move(out_ti); c->tr_top_lp = std::move(out_tl); }
     if (n_passes) *n_passes = passes;
     return CW_OK;
 }
@@ -4163,7 +4245,7 @@ int32_t cw_test_beam_state(cw_ctx* c, int32_t rows, int32_t* ids, int32_t* anc, 
 // token the kernel picks for index t.  Differential test against TF/generation/logits_process.py:203-260, 1816-2047.
 static int test_sample(cw_ctx* c, int32_t nb, const float* logits, const int32_t* ids, int32_t t, int32_t n_prompt,
                        int32_t min_new_tokens, int32_t max_length, int32_t* choice_out, const int32_t* forced_tok = nullptr,
-                       float* lp_out = nullptr);
+                       float* lp_out = nullptr, int32_t* top_id_out = nullptr, float* top_lp_out = nullptr);
 int32_t cw_test_sample(cw_ctx* c, int32_t nb, const float* logits, const int32_t* ids, int32_t t, int32_t n_prompt,
                        int32_t min_new_tokens, int32_t max_length, int32_t* choice_out) {
     return test_sample(c, nb, logits, ids, t, n_prompt, min_new_tokens, max_length, choice_out);
@@ -4209,8 +4291,38 @@ int32_t cw_test_sample_logprobs(cw_ctx* c, int32_t nb, const float* logits, cons
     if (!was_on) CWCHK(c, cw_set_token_logprobs(c, 0));
     return r;
 }
+// ... and with the alternatives on as well: k = 1 .. CW_TOP_LOGPROBS_MAX, top_id_out / top_lp_out [nb][k] = what the kernels stored
+// at [b][t][0 .. k-1].  The context's settings are restored afterwards.
+int32_t cw_test_sample_top_logprobs(cw_ctx* c, int32_t nb, const float* logits, const int32_t* ids, int32_t t, int32_t n_prompt,
+                                    int32_t min_new_tokens, int32_t max_length, float temperature, uint64_t seed,
+                                    const uint64_t* row_streams, const int32_t* forced_tok, int32_t k, int32_t* choice_out,
+                                    float* lp_out, int32_t* top_id_out, float* top_lp_out) {
+    if (!logits || !ids || !choice_out || !lp_out || !top_id_out || !top_lp_out) return fail(c, CW_ERR_INVALID, "test_sample_top_logprobs: null argument");
+    if (k < 1 || k > CW_TOP_LOGPROBS_MAX) return fail(c, CW_ERR_INVALID, "test_sample_top_logprobs: k=%d outside 1 .. %d", k, CW_TOP_LOGPROBS_MAX);
+    if (nb < 1 || nb > c->Bm || nb > 64) return fail(c, CW_ERR_INVALID, "test_sample_top_logprobs: nb=%d outside 1 .. %d", nb, c->Bm < 64 ? c->Bm : 64);
+    if (max_length <= n_prompt || max_length > c->d.max_target_positions || min_new_tokens < 0)
+        return fail(c, CW_ERR_INVALID, "test_sample_top_logprobs: max_length=%d / min_new_tokens=%d out of range", max_length, min_new_tokens);
+    if (temperature > 0.f && !row_streams) return fail(c, CW_ERR_INVALID, "test_sample_top_logprobs: a positive temperature needs row_streams");
+    if (forced_tok)
+        for (int b = 0; b < nb; ++b)
+            if (forced_tok[b] >= c->d.vocab_size) return fail(c, CW_ERR_INVALID, "test_sample_top_logprobs: forced token %d out of range", forced_tok[b]);
+    const bool was_on = c->tok_lp_on;
+    const int was_k = c->top_k;
+    CWCHK(c, cw_set_token_logprobs(c, 1));
+    CWCHK(c, cw_set_top_logprobs(c, k));
+    const std::vector<unsigned int> keep = c->samp_host;
+    CWCHK(c, write_sampling(c, temperature, seed, row_streams, nb, "test_sample_top_logprobs"));
+    const int r = test_sample(c, nb, logits, ids, t, n_prompt, min_new_tokens, max_length, choice_out, forced_tok, lp_out, top_id_out, top_lp_out);
+    HIPCHK(c, hipStreamSynchronize(c->st));
+    HIPCHK(c, hipMemcpy(c->d_samp, keep.data(), keep.size() * 4, hipMemcpyHostToDevice));
+    c->samp_host = keep;
+    CWCHK(c, cw_set_top_logprobs(c, was_on ? was_k : 0));
+    if (!was_on) CWCHK(c, cw_set_token_logprobs(c, 0));
+    return r;
+}
 static int test_sample(cw_ctx* c, int32_t nb, const float* logits, const int32_t* ids, int32_t t, int32_t n_prompt,
-                       int32_t min_new_tokens, int32_t max_length, int32_t* choice_out, const int32_t* forced_tok, float* lp_out) {
+                       int32_t min_new_tokens, int32_t max_length, int32_t* choice_out, const int32_t* forced_tok, float* lp_out,
+                       int32_t* top_id_out, float* top_lp_out) {
     const int V = c->d.vocab_size, TGT = c->d.max_target_positions;
     if (!c->gen_set) return fail(c, CW_ERR_STATE, "cw_set_generation not called");
     if (nb < 1 || nb > c->Bm || t < n_prompt || t < 1 || t >= TGT || n_prompt < 1) return fail(c, CW_ERR_INVALID, "test_sample: bad args");
@@ -4234,11 +4346,21 @@ static int test_sample(cw_ctx* c, int32_t nb, const float* logits, const int32_t
         HIPCHK(c, hipMemcpy(c->d_forced, fr.data(), fr.size() * 4, hipMemcpyHostToDevice));
     }
     if (lp_out) HIPCHK(c, hipMemset(c->d_tok_lp, 0xff, (size_t)nb * TGT * 4));
+    if (top_id_out) {
+        HIPCHK(c, hipMemset(c->d_top_id, 0xff, (size_t)nb * TGT * CW_TOP_LOGPROBS_MAX * 4));
+        HIPCHK(c, hipMemset(c->d_top_lp, 0xff, (size_t)nb * TGT * CW_TOP_LOGPROBS_MAX * 4));
+    }
     const int cfg[4] = {n_prompt, min_new_tokens, max_length, forced_tok ? 1 : 0};
     HIPCHK(c, hipMemcpy(c->d_cfg, cfg, sizeof(cfg), hipMemcpyHostToDevice));
     HIPCHK(c, hipMemcpy2D(c->dlogits, (size_t)c->Vpad * 4, logits, (size_t)V * 4, (size_t)V * 4, nb, hipMemcpyHostToDevice));
+    const int n_padcol = c->Vpad - V;
+    if (top_id_out && n_padcol > 0) {                 // the pad columns hold +75 for this call: they must never count
+        const std::vector<float> hot((size_t)nb * n_padcol, 75.0f);
+        HIPCHK(c, hipMemcpy2D(c->dlogits + V, (size_t)c->Vpad * 4, hot.data(), (size_t)n_padcol * 4, (size_t)n_padcol * 4, nb, hipMemcpyHostToDevice));
+    }
     CWCHK(c, launch_sample(c, nb, false));
     HIPCHK(c, hipStreamSynchronize(c->st));
+    if (top_id_out && n_padcol > 0) HIPCHK(c, hipMemset2D(c->dlogits + V, (size_t)c->Vpad * 4, 0, (size_t)n_padcol * 4, nb));
     std::vector<int> am((size_t)nb * TGT);
     HIPCHK(c, hipMemcpy(am.data(), c->d_argmax, am.size() * 4, hipMemcpyDeviceToHost));
     for (int b = 0; b < nb; ++b) choice_out[b] = am[(size_t)b * TGT + t];
@@ -4246,6 +4368,15 @@ static int test_sample(cw_ctx* c, int32_t nb, const float* logits, const int32_t
         std::vector<float> lp((size_t)nb * TGT);
         HIPCHK(c, hipMemcpy(lp.data(), c->d_tok_lp, lp.size() * 4, hipMemcpyDeviceToHost));
         for (int b = 0; b < nb; ++b) lp_out[b] = lp[(size_t)b * TGT + t];
+    }
+    if (top_id_out) {
+        const int k = c->top_k;
+        std::vector<int> ti((size_t)nb * TGT * k); std::vector<float> tl(ti.size());
+        CWCHK(c, cw_get_top_logprobs(c, ti.data(), tl.data(), nb));
+        for (int b = 0; b < nb; ++b) {
+            memcpy(top_id_out + (size_t)b * k, &ti[((size_t)b * TGT + t) * k], (size_t)k * 4);
+            memcpy(top_lp_out + (size_t)b * k, &tl[((size_t)b * TGT + t) * k], (size_t)k * 4);
+        }
     }
     return CW_OK;
 }

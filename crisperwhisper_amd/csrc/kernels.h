@@ -52,6 +52,12 @@ struct SampleParams {
     // optional (null: off): log_softmax(raw logits)[token written at t] of every running row, stored at [b][t]
     // (include/crisperwhisper.h: cw_set_token_logprobs)
     float* tok_lp;             // [B][ids_stride]
+    // optional (top_k == 0: off; needs tok_lp): the top_k best raw logits of every step as (token id, log_softmax value), best
+    // first, stored at [b][t][0 .. top_k-1] (include/crisperwhisper.h: cw_set_top_logprobs)
+    int top_k;                 // 0 .. CW_TOP_LOGPROBS_MAX
+    void* top_part;            // [B][SAMPLE_NS][CW_TOP_LOGPROBS_MAX] 8-byte (value, id) pairs: the slices' winners, written by stage 1
+    int* top_id;               // [B][ids_stride][CW_TOP_LOGPROBS_MAX]
+    float* top_lp;             // [B][ids_stride][CW_TOP_LOGPROBS_MAX]
 };
 // beam search (elementwise.hip): per row the n_cand best processed log-probabilities of the next token
 // (log_softmax of the raw logits, then the same processors as the greedy path) ...

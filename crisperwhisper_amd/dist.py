@@ -26,11 +26,30 @@ def shard_bounds(n_chunks: int, world: int):
 REC_WORDS_SCORED = REC_WORDS + REC_TOKENS   # ... followed by one f32 log-probability per token (only when scores are requested)
 
 
-def pack_record(idx: int, tokens: np.ndarray, ts: np.ndarray, stride, scores: Optional[np.ndarray] = None) -> np.ndarray:
-    """One chunk's record.  ``scores`` (one float32 per token) widens it to REC_WORDS_SCORED; without it the record is the
+def rec_words_top(k: int) -> int:
+    """Width of a record that also carries ``k`` alternatives per token: the scored record, then k int32 ids per token, then k
+    f32 log-probabilities per token (only when top_logprobs are requested)."""
+    return REC_WORDS_SCORED + 2 * int(k) * REC_TOKENS
+
+
+def pack_record(idx: int, tokens: np.ndarray, ts: np.ndarray, stride, scores: Optional[np.ndarray] = None, top=None) -> np.ndarray:
+    """One chunk's record.  ``scores`` (one float32 per token) widens it to REC_WORDS_SCORED; ``top`` = (ids [n_tok][k], log-
+    probabilities [n_tok][k]), with scores only, widens it further to ``rec_words_top(k)``; without either the record is the
     REC_WORDS one."""
-    rec = np.zeros(REC_WORDS if scores is None else REC_WORDS_SCORED, dtype=np.int32)
     nt, ns = len(tokens), len(ts)
+    if top is None:
+        rec = np.zeros(REC_WORDS if scores is None else REC_WORDS_SCORED, dtype=np.int32)
+    else:
+        if scores is None:
+            raise ValueError("alternatives travel with the token scores: pass scores as well")
+        tid, tlp = np.asarray(top[0], dtype=np.int32), np.asarray(top[1], dtype=np.float32)
+        if tid.ndim != 2 or tid.shape != tlp.shape or tid.shape[0] != nt or tid.shape[1] < 1:
+            raise ValueError(f"alternatives of shape {tid.shape} / {tlp.shape} for {nt} tokens")
+        k = tid.shape[1]
+        rec = np.zeros(rec_words_top(k), dtype=np.int32)
+        if nt <= REC_TOKENS:
+            rec[REC_WORDS_SCORED:REC_WORDS_SCORED + nt * k] = tid.reshape(-1)
+            rec[REC_WORDS_SCORED + k * REC_TOKENS:REC_WORDS_SCORED + k * REC_TOKENS + nt * k] = tlp.reshape(-1).view(np.int32)
     if scores is not None:
         if len(scores) != nt:
             raise ValueError(f"{len(scores)} token scores for {nt} tokens")
@@ -52,6 +71,14 @@ def unpack_record(rec: np.ndarray):
     ts = rec[6 + REC_TOKENS:6 + REC_TOKENS + ns].view(np.float32).copy()
     if len(rec) == REC_WORDS_SCORED:                 # a record packed with scores: a fifth value, one f32 per token
         return idx, tokens, ts, stride, rec[REC_WORDS:REC_WORDS + nt].view(np.float32).copy()
+    if len(rec) > REC_WORDS_SCORED:                  # ... and with alternatives: ids and log-probabilities [n_tok][k] as well
+        k, odd = divmod(len(rec) - REC_WORDS_SCORED, 2 * REC_TOKENS)
+        if odd or k < 1:
+            raise ValueError(f"a record of {len(rec)} words is none of the known widths")
+        o = REC_WORDS_SCORED
+        return (idx, tokens, ts, stride, rec[REC_WORDS:REC_WORDS + nt].view(np.float32).copy(),
+                rec[o:o + nt * k].reshape(nt, k).copy(),
+                rec[o + k * REC_TOKENS:o + k * REC_TOKENS + nt * k].view(np.float32).reshape(nt, k).copy())
     return idx, tokens, ts, stride
 
 

@@ -273,8 +273,11 @@ class Engine:
         return out
 
     def set_token_logprobs(self, on: bool):
-        """Per-token log-probabilities of the free-running decode (``cw_set_token_logprobs``); off by default."""
+        """Per-token log-probabilities of the free-running decode (``cw_set_token_logprobs``); off by default.  Switching them
+        off switches ``set_top_logprobs`` off as well."""
         self._chk(self.lib.cw_set_token_logprobs(self.ctx, 1 if on else 0))
+        if not on:
+            self._top_k = 0
 
     def token_logprobs(self, nb: int) -> np.ndarray:
         """[nb, max_target_positions] float32 aligned with the last ``decode``'s sequences: ``logits[tok] -
@@ -292,6 +295,33 @@ class Engine:
         out = np.empty((nb, cap), np.float32)
         self._chk(self.lib.cw_get_transcribe_token_logprobs(self.ctx, _ptr(out), nb, cap))
         return [out[i, :int(n)].copy() for i, n in enumerate(lens)]
+
+    def set_top_logprobs(self, k: int):
+        """The ``k`` (0 = off, at most 8) best raw logits of every decode step next to the token log-probabilities
+        (``cw_set_top_logprobs``); needs ``set_token_logprobs(True)``."""
+        self._chk(self.lib.cw_set_top_logprobs(self.ctx, int(k)))
+        self._top_k = int(k)
+
+    def top_logprobs(self, nb: int):
+        """(ids int32, logprobs float32), both [nb, max_target_positions, k], aligned with the last ``decode``'s sequences: the
+        k best raw logits of the step that wrote each position, best first, ties to the lower id; -1 / NaN beyond the number
+        of finite logits and wherever ``token_logprobs`` holds NaN (``cw_get_top_logprobs``)."""
+        k = max(1, getattr(self, "_top_k", 0))
+        ids = np.empty((nb, self.spec.max_target_positions, k), np.int32)
+        lp = np.empty((nb, self.spec.max_target_positions, k), np.float32)
+        self._chk(self.lib.cw_get_top_logprobs(self.ctx, _ptr(ids), _ptr(lp), nb))
+        return ids, lp
+
+    def transcribe_top_logprobs(self, lens):
+        """The alternatives of the last ``transcribe``: (ids, logprobs), each one [n_tok][k] array per item aligned with its
+        tokens (``lens`` = their counts; ``cw_get_transcribe_top_logprobs``)."""
+        nb = len(lens)
+        k = max(1, getattr(self, "_top_k", 0))
+        cap = max(1, max((int(n) for n in lens), default=1))
+        ids = np.empty((nb, cap, k), np.int32)
+        lp = np.empty((nb, cap, k), np.float32)
+        self._chk(self.lib.cw_get_transcribe_top_logprobs(self.ctx, _ptr(ids), _ptr(lp), nb, cap))
+        return ([ids[i, :int(n)].copy() for i, n in enumerate(lens)], [lp[i, :int(n)].copy() for i, n in enumerate(lens)])
 
     def last_logits(self, nb: int) -> np.ndarray:
         out = np.empty((nb, self.spec.vocab_size), dtype=np.float32)
@@ -870,6 +900,34 @@ class Engine:
                                                    int(max_length or self.spec.max_target_positions), float(temperature),
                                                    int(seed) & (2 ** 64 - 1), _ptr(rs), _ptr(fr), _ptr(out), _ptr(lp)))
         return out, lp
+
+    def test_sample_top_logprobs(self, logits: np.ndarray, ids: np.ndarray, n_prompt: int, k: int, temperature: float = 0.0,
+                                 seed: int = 0, row_streams=None, forced=None, min_new_tokens: int = 0,
+                                 max_length: Optional[int] = None):
+        """``test_sample_logprobs`` with ``set_top_logprobs(k)`` on for the call (cw_test_sample_top_logprobs): returns (choice
+        [nb], logprob [nb], top ids [nb][k], top logprobs [nb][k]) of index t."""
+        lg = np.ascontiguousarray(logits, np.float32)
+        ids = _i32(ids)
+        nb, t = ids.shape
+        if lg.shape != (nb, self.spec.vocab_size):
+            raise ValueError(f"logits must be [{nb}][{self.spec.vocab_size}], got {lg.shape}")
+        if not 1 <= int(k) <= 8:
+            raise ValueError(f"k must be in 1 .. 8, got {k}")
+        rs = None if row_streams is None else np.ascontiguousarray(row_streams, dtype=np.uint64)
+        if rs is not None and rs.shape != (nb,):
+            raise ValueError(f"row_streams must hold one id per row ({nb}), got shape {rs.shape}")
+        fr = None if forced is None else _i32(forced)
+        if fr is not None and fr.shape != (nb,):
+            raise ValueError(f"forced must hold one token per row ({nb}), got shape {fr.shape}")
+        out = np.zeros(nb, np.int32)
+        lp = np.zeros(nb, np.float32)
+        top_id = np.zeros((nb, int(k)), np.int32)
+        top_lp = np.zeros((nb, int(k)), np.float32)
+        self._chk(self.lib.cw_test_sample_top_logprobs(self.ctx, nb, _ptr(lg), _ptr(ids), t, int(n_prompt), int(min_new_tokens),
+                                                       int(max_length or self.spec.max_target_positions), float(temperature),
+                                                       int(seed) & (2 ** 64 - 1), _ptr(rs), _ptr(fr), int(k), _ptr(out), _ptr(lp),
+                                                       _ptr(top_id), _ptr(top_lp)))
+        return out, lp, top_id, top_lp
 
     # ------------------------------------------------------------------ measurement
     def stage_times(self, reset: bool = False):

@@ -22,6 +22,7 @@ from .engine import Engine
 
 TIME_PRECISION = 0.02          # seconds per encoder frame (30 / 1500)
 INPUT_STRIDE = 2               # conv1.stride * conv2.stride
+TOP_LOGPROBS_MAX = 8           # CW_TOP_LOGPROBS_MAX: alternatives per token (generate(top_logprobs=k))
 
 
 @dataclasses.dataclass
@@ -30,6 +31,8 @@ class Segment:
     token_timestamps: np.ndarray   # float32, absolute seconds within the 30 s chunk
     idxs: tuple
     token_logprobs: Optional[np.ndarray] = None   # float32, one per token (generate(return_token_logprobs=True))
+    top_ids: Optional[np.ndarray] = None          # int32 [n_tok][k]: the k best raw logits of each token's step (generate(top_logprobs=k))
+    top_logprobs: Optional[np.ndarray] = None     # float32 [n_tok][k]: their log-probabilities (-1 / NaN: fewer than k candidates)
 
 
 def detect_language(engine: Engine, n_items: int) -> np.ndarray:
@@ -183,11 +186,17 @@ def prompted_max_length(spec, n_input: int, max_new_tokens: Optional[int]) -> in
 
 
 def split_segments(seq: np.ndarray, token_ts: np.ndarray, time_offset: float, timestamp_begin: int,
-                   seek_num_frames: int, idx_offset: int, token_lp: Optional[np.ndarray] = None):
+                   seek_num_frames: int, idx_offset: int, token_lp: Optional[np.ndarray] = None, token_top=None):
     """Slice one decoded window at paired timestamp tokens; returns (segments, frames to advance).  ``token_lp`` (per-token
-    log-probabilities of the row, indexed like ``token_ts``) is cut by the same index ranges."""
+    log-probabilities of the row, indexed like ``token_ts``) and ``token_top`` (the row's (ids [T][k], log-probabilities [T][k])
+    alternatives, indexed alike) are cut by the same index ranges."""
     def lp(a, b):
         return None if token_lp is None else np.asarray(token_lp[a:b], dtype=np.float32).copy()
+
+    def top(a, b):
+        if token_top is None:
+            return None, None
+        return np.asarray(token_top[0][a:b], dtype=np.int32).copy(), np.asarray(token_top[1][a:b], dtype=np.float32).copy()
     is_ts = seq >= timestamp_begin
     single_ending = len(seq) >= 2 and (not is_ts[-2]) and bool(is_ts[-1])
     if len(seq) == 1:
@@ -204,7 +213,8 @@ def split_segments(seq: np.ndarray, token_ts: np.ndarray, time_offset: float, ti
         prev = 0
         for cut in cuts:
             out.append(Segment(seq[prev:cut], (token_ts[idx_offset + prev: idx_offset + cut] + off32).astype(np.float32),
-                               (idx_offset + prev, idx_offset + cut), lp(idx_offset + prev, idx_offset + cut)))
+                               (idx_offset + prev, idx_offset + cut), lp(idx_offset + prev, idx_offset + cut),
+                               *top(idx_offset + prev, idx_offset + cut)))
             prev = cut
         if single_ending:
             advance = seek_num_frames
@@ -212,7 +222,8 @@ def split_segments(seq: np.ndarray, token_ts: np.ndarray, time_offset: float, ti
             advance = (int(seq[prev - 2]) - timestamp_begin) * INPUT_STRIDE
     else:
         out.append(Segment(seq, (token_ts[idx_offset: idx_offset + len(seq)] + off32).astype(np.float32),
-                           (idx_offset, idx_offset + len(seq)), lp(idx_offset, idx_offset + len(seq))))
+                           (idx_offset, idx_offset + len(seq)), lp(idx_offset, idx_offset + len(seq)),
+                           *top(idx_offset, idx_offset + len(seq))))
         advance = seek_num_frames
     return out, advance
 
@@ -453,7 +464,7 @@ def generate(engine: Engine, n_items: int, num_frames, *, language: Optional[str
              num_beams: Optional[int] = 1, stats: Optional[dict] = None, native: Optional[bool] = None,
              logprob_threshold: Optional[float] = None, no_speech_threshold: Optional[float] = None, prompt_ids=None,
              temperature=None, compression_ratio_threshold: Optional[float] = None, sampling_seed: int = 0, item_ids=None,
-             return_token_logprobs: bool = False):
+             return_token_logprobs: bool = False, top_logprobs: int = 0):
     """Transcribe the ``n_items`` 30 s feature windows resident in the engine (items 0..n-1).
 
     Returns {"sequences": [B, Lmax] int64 (pad-right), "token_timestamps": list of float32 arrays,
@@ -483,11 +494,29 @@ def generate(engine: Engine, n_items: int, num_frames, *, language: Optional[str
     ``return_token_logprobs=True`` adds "token_logprobs": one float32 array per item aligned with ``token_timestamps``,
     ``logits[tok] - logsumexp(logits[:vocab])`` on the raw logits of the step that produced each token (the quantity ``score``
     reports).  Greedy, sampled and forced rows take it from the sampler kernels (``cw_set_token_logprobs``), beam search from
-    the candidate values along the winning hypothesis' ancestry; no extra forward runs."""
+    the candidate values along the winning hypothesis' ancestry; no extra forward runs.
+
+    ``top_logprobs=k`` (1 .. 8; needs ``return_token_logprobs=True`` and ``num_beams=1``) adds "top_ids" and "top_logprobs": one
+    [n_tok][k] array per item aligned with ``token_timestamps``, the ids (int32) and log-probabilities (float32) of the k best raw
+    logits of each token's step, best first, ties to the lower id (``cw_set_top_logprobs``): no suppress lists, no timestamp
+    rule, no temperature, so the written token need not be among them; where it is, its value equals ``token_logprobs`` bit for
+    bit.  A rank beyond the number of finite logits holds -1 / NaN."""
     spec = engine.spec
     want_lp = bool(return_token_logprobs)
     if want_lp and not hasattr(engine, "set_token_logprobs"):
         raise ValueError("this engine does not implement per-token log-probabilities (cw_set_token_logprobs)")
+    want_top = 0 if top_logprobs is None else top_logprobs
+    if isinstance(want_top, bool) or not isinstance(want_top, (int, np.integer)) or not 0 <= int(want_top) <= TOP_LOGPROBS_MAX:
+        raise ValueError(f"top_logprobs must be an integer in 0 .. {TOP_LOGPROBS_MAX}, got {top_logprobs!r}")
+    want_top = int(want_top)
+    if want_top:
+        if not want_lp:
+            raise ValueError("top_logprobs needs return_token_logprobs=True (the alternatives share its normaliser)")
+        if num_beams is not None and int(num_beams) > 1:
+            raise ValueError("top_logprobs is implemented for greedy and sampled decoding only (beam search re-parents its rows "
+                             "every step): pass num_beams=1")
+        if not hasattr(engine, "set_top_logprobs"):
+            raise ValueError("this engine does not implement top_logprobs (cw_set_top_logprobs)")
     if no_speech_threshold is not None and logprob_threshold is None:
         raise ValueError("no_speech_threshold needs logprob_threshold as well (generation_whisper.py:1275-1285 compares both)")
     # every argument is checked before any engine state changes (a refused call must not leave its thresholds behind)
@@ -523,7 +552,7 @@ def generate(engine: Engine, n_items: int, num_frames, *, language: Optional[str
         if len(ids_) != n_items:
             raise ValueError(f"{len(ids_)} item_ids for {n_items} items")
         fb = {"temps": temps, "seed": int(sampling_seed), "item_ids": ids_, "cr_thr": compression_ratio_threshold,
-              "token_logprobs": want_lp}
+              "token_logprobs": want_lp, "top_logprobs": want_top}
         native = False                                  # the fallback loop runs here, like beam search
     if hasattr(engine, "set_thresholds"):
         engine.set_thresholds(logprob_threshold, no_speech_threshold)
@@ -531,6 +560,8 @@ def generate(engine: Engine, n_items: int, num_frames, *, language: Optional[str
         raise ValueError("this engine does not implement logprob_threshold / no_speech_threshold")
     if hasattr(engine, "set_token_logprobs"):
         engine.set_token_logprobs(want_lp)
+    if hasattr(engine, "set_top_logprobs"):
+        engine.set_top_logprobs(want_top)
     num_frames = np.asarray(num_frames, dtype=np.int64)
     if native is None:
         native = hasattr(engine, "transcribe") and num_beams == 1
@@ -559,6 +590,8 @@ def generate(engine: Engine, n_items: int, num_frames, *, language: Optional[str
         out = {"sequences": sequences, "token_timestamps": tts, "segments": None}
         if want_lp:
             out["token_logprobs"] = engine.transcribe_token_logprobs([len(s) for s in toks])
+        if want_top:
+            out["top_ids"], out["top_logprobs"] = engine.transcribe_top_logprobs([len(s) for s in toks])
         return out
     pre_encoded = False
     _, detect = resolve_prompt(spec, language, task)
@@ -586,7 +619,7 @@ def generate(engine: Engine, n_items: int, num_frames, *, language: Optional[str
     try:
         _seek_loop(engine, spec, n_items, num_frames, init, n_prompt, max_new_tokens, min_new_tokens, num_beams, prefix,
                    prompted_len if prefix is not None else None, skip_on, logprob_threshold, no_speech_threshold, pre_encoded,
-                   seek, max_frames, segments, tb, stats, fb, want_lp)
+                   seek, max_frames, segments, tb, stats, fb, want_lp, want_top)
     finally:
         if prefix is not None and set_prefix is not None:
             set_prefix(0)
@@ -600,11 +633,17 @@ def generate(engine: Engine, n_items: int, num_frames, *, language: Optional[str
     if want_lp:
         out["token_logprobs"] = [np.concatenate([s.token_logprobs for s in segs]) if segs else np.zeros(0, np.float32)
                                  for segs in segments]
+    if want_top:
+        out["top_ids"] = [np.concatenate([s.top_ids for s in segs]) if segs else np.zeros((0, want_top), np.int32)
+                          for segs in segments]
+        out["top_logprobs"] = [np.concatenate([s.top_logprobs for s in segs]) if segs else np.zeros((0, want_top), np.float32)
+                               for segs in segments]
     return out
 
 
 def _seek_loop(engine, spec, n_items, num_frames, init, n_prompt, max_new_tokens, min_new_tokens, num_beams, prefix, prompted_len,
-               skip_on, logprob_threshold, no_speech_threshold, pre_encoded, seek, max_frames, segments, tb, stats, fb=None, want_lp=False):
+               skip_on, logprob_threshold, no_speech_threshold, pre_encoded, seek, max_frames, segments, tb, stats, fb=None, want_lp=False,
+               want_top=0):
     """The seek loop of the host path of ``generate`` (fills ``segments`` in place).  ``fb``: temperature fallback settings."""
     n_calls = 0
     while True:
@@ -627,11 +666,12 @@ def _seek_loop(engine, spec, n_items, num_frames, init, n_prompt, max_new_tokens
             for row, i in enumerate(active):
                 s, ts_row, skip = kept[row][:3]
                 lp_row = kept[row][3] if want_lp else None
+                top_row = kept[row][4:6] if want_top else None
                 if skip:
                     seek[i] += seek_num[i]                        # should_skip (:879-881)
                     continue
                 segs, advance = split_segments(s, ts_row, float(seek[i]) * TIME_PRECISION / INPUT_STRIDE, tb,
-                                               int(seek_num[i]), n_prompt, lp_row)
+                                               int(seek_num[i]), n_prompt, lp_row, top_row)
                 seek[i] += advance
                 segments[i].extend(segs)
             continue
@@ -651,6 +691,8 @@ def _seek_loop(engine, spec, n_items, num_frames, init, n_prompt, max_new_tokens
             alp = engine.avg_logprobs(len(active)) if skip_on else None
             if want_lp:
                 tok_lp = engine.token_logprobs(len(active))
+            if want_top:
+                tok_top = engine.top_logprobs(len(active))
         token_ts = engine.token_timestamps(len(active), L, n_prompt, (num_frames - seek)[active])
         n_calls += 1
         for row, i in enumerate(active):
@@ -667,7 +709,8 @@ def _seek_loop(engine, spec, n_items, num_frames, init, n_prompt, max_new_tokens
             if s[-1] == spec.eos_token_id:
                 s = s[:-1]
             segs, advance = split_segments(s, token_ts[row], float(seek[i]) * TIME_PRECISION / INPUT_STRIDE, tb,
-                                           int(seek_num[i]), n_prompt, tok_lp[row] if want_lp else None)
+                                           int(seek_num[i]), n_prompt, tok_lp[row] if want_lp else None,
+                                           (tok_top[0][row], tok_top[1][row]) if want_top else None)
             seek[i] += advance
             segments[i].extend(segs)
     if stats is not None:
@@ -684,7 +727,7 @@ def _decode_with_fallback(engine, spec, fb, active, init_rows, n_prompt, max_len
     rows).  Decisions are indexed by the original row throughout -- transformers indexes ``needs_fallback[i]`` /
     ``should_skip[i]`` by the row of the shrunken sub-batch (:1074 against :1088) and reads them back by the original one.
     Returns per row (tokens without eos, token timestamps of the whole row, skip[, token log-probabilities of the whole row when
-    ``fb["token_logprobs"]`` is set])."""
+    ``fb["token_logprobs"]`` is set[, alternative ids and log-probabilities of the whole row when ``fb["top_logprobs"]`` is]])."""
     nb = len(active)
     temps = fb["temps"]
     kept = [None] * nb
@@ -705,6 +748,7 @@ def _decode_with_fallback(engine, spec, fb, active, init_rows, n_prompt, max_len
             alp = engine.avg_logprobs(nb) if logprob_threshold is not None else None
             token_ts = engine.token_timestamps(nb, total - 1, n_prompt, frames)
             tok_lp = engine.token_logprobs(nb) if fb.get("token_logprobs") else None   # a masked row keeps its settled values
+            tok_top = engine.top_logprobs(nb) if tok_lp is not None and fb.get("top_logprobs") else None   # ... and entries
             again = []
             for r in pending:
                 s = seqs[r, n_prompt:total].astype(np.int64)
@@ -729,6 +773,8 @@ def _decode_with_fallback(engine, spec, fb, active, init_rows, n_prompt, max_len
                 kept[r] = (s, np.array(token_ts[r], copy=True), skip)
                 if tok_lp is not None:
                     kept[r] += (np.array(tok_lp[r], copy=True),)
+                if tok_top is not None:
+                    kept[r] += (np.array(tok_top[0][r], copy=True), np.array(tok_top[1][r], copy=True))
                 if needs and not last:
                     again.append(r)
             pending = again

@@ -311,18 +311,61 @@ def _check_seed(seed) -> int:
     return int(seed)
 
 
-def scored_words(vocab, outputs, token_logprobs, warn=None):
+def token_text(vocab, tok: int) -> str:
+    """One token as text: its bytes decoded as UTF-8 with replacement; a special token's ``<|name|>``; a timestamp token's
+    ``<|seconds|>``."""
+    tok = int(tok)
+    b = vocab.token_bytes[tok] if 0 <= tok < len(vocab.token_bytes) else None
+    if b is not None:
+        return bytes(b).decode("utf-8", errors="replace")
+    if tok in vocab.specials:
+        return vocab.specials[tok]
+    if tok >= vocab.timestamp_begin:
+        return f"<|{(tok - vocab.timestamp_begin) * 0.02:.2f}|>"
+    return ""
+
+
+def scored_words(vocab, outputs, token_logprobs, warn=None, token_top=None):
     """``collate.decode_asr(outputs, return_timestamps="word")`` with "logprob" on every word: the float64 sum of
     ``token_logprobs`` (one array per entry of ``outputs``, one value per token) over the collator's own token group of the word.
-    The groups address the concatenation of all windows' tokens, so a token the seam merge drops counts in no word."""
+    The groups address the concatenation of all windows' tokens, so a token the seam merge drops counts in no word.
+
+    ``token_top`` (one (ids [n_tok][k], log-probabilities [n_tok][k]) pair per entry of ``outputs``) adds "tokens" to every
+    word, over the same group: ``[{"id", "text", "logprob", "top_logprobs": [{"id", "text", "logprob"}, ...]}]``, alternatives
+    best first, entries with id -1 left out."""
     if len(token_logprobs) != len(outputs) or any(len(a) != len(o["tokens"]) for a, o in zip(token_logprobs, outputs)):
         raise ValueError("scored_words: one log-probability per token of every window is required")
+    if token_top is not None and (len(token_top) != len(outputs) or any(
+            len(t[0]) != len(o["tokens"]) or len(t[1]) != len(o["tokens"]) for t, o in zip(token_top, outputs))):
+        raise ValueError("scored_words: one row of alternatives per token of every window is required")
     text, words, groups = collate.decode_asr(vocab, outputs, time_precision=0.02, warn=warn, return_timestamps="word",
                                              return_token_groups=True)
     flat = np.concatenate([np.asarray(a, np.float64) for a in token_logprobs]) if token_logprobs else np.zeros(0, np.float64)
     for w, g in zip(words, groups):
         w["logprob"] = float(np.sum(flat[g]))
+    if token_top is not None and outputs:
+        k = max((np.asarray(t[0]).shape[1] for t in token_top if np.asarray(t[0]).ndim == 2), default=1)
+        ids = np.concatenate([np.asarray(o["tokens"], np.int64) for o in outputs])
+        tid = np.concatenate([np.asarray(t[0], np.int32).reshape(-1, k) for t in token_top])
+        tlp = np.concatenate([np.asarray(t[1], np.float32).reshape(-1, k) for t in token_top])
+        lp32 = np.concatenate([np.asarray(a, np.float32) for a in token_logprobs])
+        for w, g in zip(words, groups):
+            w["tokens"] = [{"id": int(ids[i]), "text": token_text(vocab, ids[i]), "logprob": float(lp32[i]),
+                            "top_logprobs": [{"id": int(v), "text": token_text(vocab, v), "logprob": float(x)}
+                                             for v, x in zip(tid[i], tlp[i]) if v >= 0]}
+                           for i in np.asarray(g, np.int64).reshape(-1)]
+    elif token_top is not None:
+        for w in words:
+            w["tokens"] = []
     return text, words
+
+
+def _check_top_logprobs(k) -> int:
+    if k is None:
+        return 0
+    if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 0 <= int(k) <= generation.TOP_LOGPROBS_MAX:
+        raise ValueError(f"top_logprobs must be an integer in 0 .. {generation.TOP_LOGPROBS_MAX}, got {k!r}")
+    return int(k)
 
 
 class CrisperWhisperPipeline:
@@ -331,11 +374,15 @@ class CrisperWhisperPipeline:
                  shard: Optional[dist.Shard] = None, contexts: int = 1, cross_kv_dtype: Optional[str] = None,
                  encoder_gemm_dtype: Optional[str] = None,
                  engines: Optional[List[Engine]] = None, num_beams: Optional[int] = None,
-                 sampling_seed: Optional[int] = None, return_scores: bool = False, **kwargs):
+                 sampling_seed: Optional[int] = None, return_scores: bool = False, top_logprobs: int = 0, **kwargs):
         """``return_scores`` (here or per call, default False): with ``return_timestamps="word"`` every chunk gains
         "logprob", the float64 sum over its tokens of ``logits[tok] - logsumexp(logits[:vocab])`` on the raw logits of the
         decode step that chose each token -- grouped by the collator's own token groups, so tokens dropped in a seam
         overlap count in no word.
+
+        ``top_logprobs`` (here or per call, 0 .. 8, default 0; needs ``return_scores=True``, ``return_timestamps="word"`` and
+        ``num_beams=1``): every word chunk also gains "tokens", one entry per token of the word with its id, text, log-probability
+        and the k most probable tokens of its decode step (``scored_words``).  Everything else in the result is unchanged.
 
         ``num_beams`` (construction time): the widest beam the contexts are provisioned for -- decoder rows =
         batch_size x num_beams, at most 64.  Default 5 = ``AutomaticSpeechRecognitionPipeline._default_generation_config``
@@ -368,6 +415,7 @@ class CrisperWhisperPipeline:
         self.max_rows = max(self.max_rows, min(64, self.batch_size))
         self.return_timestamps = return_timestamps
         self.return_scores = bool(return_scores)
+        self.top_logprobs = _check_top_logprobs(top_logprobs)
         # the key of the engine's sampler for calls with a positive temperature / temperature fallback; None: such calls must
         # name one themselves (a call without any seed is refused, it does not draw from a hidden default)
         self.sampling_seed = None if sampling_seed is None else _check_seed(sampling_seed)
@@ -428,13 +476,18 @@ class CrisperWhisperPipeline:
         return self._run_one(inputs, **kwargs)
 
     def _run_one(self, inputs, return_timestamps=None, generate_kwargs=None, chunk_length_s=None,
-                 stride_length_s=None, return_language=None, sampling_seed=None, return_scores=None, **unused):
+                 stride_length_s=None, return_language=None, sampling_seed=None, return_scores=None, top_logprobs=None,
+                 **unused):
         seed = self.sampling_seed if sampling_seed is None else _check_seed(sampling_seed)
         rt = return_timestamps if return_timestamps is not None else self.return_timestamps
         scores = self.return_scores if return_scores is None else bool(return_scores)
         if scores and rt != "word":
             raise ValueError('return_scores=True gives every word its log-probability: it needs return_timestamps="word" '
                              f"(got {rt!r}; segment-level scores are not implemented)")
+        top_k = getattr(self, "top_logprobs", 0) if top_logprobs is None else _check_top_logprobs(top_logprobs)
+        if top_k and not scores:
+            raise ValueError("top_logprobs lists the alternatives next to every token's log-probability: it needs "
+                             'return_scores=True and return_timestamps="word"')
         if not (rt == "word" or rt is True):
             raise ValueError("crisperwhisper_amd implements the timestamped paths: pass return_timestamps='word' "
                              "(CrisperWhisper's purpose, REF/transcribe.py:28) or True (segment-level chunks, the "
@@ -449,6 +502,9 @@ class CrisperWhisperPipeline:
         num_beams = int(gk.get("num_beams", self.default_num_beams))
         if gk.get("length_penalty") not in (None, 1.0) or gk.get("early_stopping") not in (None, False):
             raise ValueError("only the default length_penalty=1.0 / early_stopping=False beam search is implemented")
+        if top_k and num_beams > 1:
+            raise ValueError(f"top_logprobs is implemented for greedy and sampled decoding only, this call decodes with "
+                             f"{num_beams} beams: pass generate_kwargs={{'num_beams': 1}}")
         import time as _time
         t_ph = [_time.perf_counter()]                       # phase clock of this call: load | local batches | gather | collation
         pcm = self._load(inputs)
@@ -488,7 +544,8 @@ class CrisperWhisperPipeline:
                 num_beams=num_beams, stats=st, logprob_threshold=gk.get("logprob_threshold"),
                 no_speech_threshold=gk.get("no_speech_threshold"), prompt_ids=gk.get("prompt_ids"),
                 temperature=gk.get("temperature"), compression_ratio_threshold=gk.get("compression_ratio_threshold"),
-                sampling_seed=seed or 0, item_ids=idxs, **({"return_token_logprobs": True} if scores else {}))
+                sampling_seed=seed or 0, item_ids=idxs, **({"return_token_logprobs": True} if scores else {}),
+                **({"top_logprobs": top_k} if top_k else {}))
             if "fallback" in st:
                 fallback_trace.extend(st["fallback"])
             rs = []
@@ -496,7 +553,8 @@ class CrisperWhisperPipeline:
                 n_tok = len(out["token_timestamps"][k])
                 stride = tuple(x / sr for x in windows[i][2])
                 rs.append(dist.pack_record(i, out["sequences"][k][:n_tok], out["token_timestamps"][k], stride,
-                                           out["token_logprobs"][k] if scores else None))
+                                           out["token_logprobs"][k] if scores else None,
+                                           (out["top_ids"][k], out["top_logprobs"][k]) if top_k else None))
             return rs, st.get("generate_calls", 0)
 
         per = self.batch_size
@@ -522,21 +580,26 @@ class CrisperWhisperPipeline:
         recs = [r for rs, _ in results for r in rs]
         self.stats["fallback"] = sorted(fallback_trace, key=lambda d: (d["item"], d["seek"], d["temperature_index"]))
         self.stats["generate_calls"] = self.stats.get("generate_calls", 0) + sum(c for _, c in results)
-        recs = np.stack(recs) if recs else np.zeros((0, dist.REC_WORDS_SCORED if scores else dist.REC_WORDS), np.int32)
+        # an empty shard sends the width the other ranks send
+        width = dist.rec_words_top(top_k) if top_k else (dist.REC_WORDS_SCORED if scores else dist.REC_WORDS)
+        recs = np.stack(recs) if recs else np.zeros((0, width), np.int32)
         max_per_rank = max(h - l for l, h in dist.shard_bounds(len(windows), self.shard.world))
         t_ph.append(_time.perf_counter())
         allr = self.shard.all_gather_records(recs, max_per_rank)
         t_ph.append(_time.perf_counter())
-        outputs, token_lp = [], []
+        outputs, token_lp, token_top = [], [], []
         for r in allr:
             _, toks, ts, stride, *lp = dist.unpack_record(r)
+            if top_k:
+                token_top.append((lp[1], lp[2]))
+                lp = lp[:1]
             o = {"tokens": toks, "token_timestamps": ts}
             if with_stride:
                 o["stride"] = stride
             outputs.append(o)
             token_lp.extend(lp)
         if scores:
-            text, words = scored_words(self.vocab, outputs, token_lp, warn=logger.warning)
+            text, words = scored_words(self.vocab, outputs, token_lp, warn=logger.warning, token_top=token_top if top_k else None)
         else:
             text, words = collate.decode_asr(self.vocab, outputs, time_precision=0.02, warn=logger.warning,
                                              return_timestamps="word" if rt == "word" else True)

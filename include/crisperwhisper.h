@@ -196,6 +196,28 @@ int32_t cw_get_avg_logprobs(cw_ctx* ctx, float* out /* [nb] */, int32_t nb);
 int32_t cw_set_token_logprobs(cw_ctx* ctx, int32_t on);
 int32_t cw_get_token_logprobs(cw_ctx* ctx, float* out /* [nb][max_target_positions] */, int32_t nb);
 int32_t cw_get_transcribe_token_logprobs(cw_ctx* ctx, float* out /* [B][cap] */, int32_t B, int32_t cap);
+/* top_logprobs: what else the model considered.  With k = 1 .. CW_TOP_LOGPROBS_MAX (0 = off, the default) the sampler kernels
+ * also store, for every row and sequence position t they write, the k best raw logits of the step:
+ *   candidates  the columns v < vocab_size with logits[v] > -inf: the RAW f32 logits (no suppress lists, no timestamp rule, no
+ *               temperature, no Gumbel noise: masked tokens count; pad columns never count; a NaN logit is never a candidate)
+ *   order       value descending, token id ascending on an exact tie
+ *   top_id[t][j]       the id of the j-th candidate
+ *   top_logprob[t][j]  logits[id] - logsumexp(logits[0 .. vocab_size-1]) with the very normaliser of logprob[t] above, so where
+ *                      the written token is among the k its value is bit-identical to cw_get_token_logprobs at t
+ * A rank at or beyond the number of candidates holds id -1 / NaN, and so do all k entries wherever cw_get_token_logprobs holds
+ * NaN.  The written token (arg-max, sampled or forced) need not be among the alternatives.  A row masked by cw_decode_rows
+ * keeps its entries.  No launch and no forward is added: stage 1 of the sampler selects the k best of each of its 16 slices
+ * from the registers it already holds, stage 2 merges the 16 x k pairs in one wave.
+ * cw_set_top_logprobs: CW_ERR_INVALID outside 0 .. CW_TOP_LOGPROBS_MAX; CW_ERR_STATE for k > 0 while cw_set_token_logprobs is
+ * off (switching that off switches this off too).  Allocates [max_batch][max_target_positions][CW_TOP_LOGPROBS_MAX] int32 and
+ * f32 on first use; drops the captured decode steps when the value changes.  Greedy / sampled decoding only: beam search does
+ * not carry alternatives.
+ * cw_get_top_logprobs: [nb][max_target_positions][k], aligned with `sequences`.  cw_get_transcribe_top_logprobs: those of the
+ * last cw_transcribe / cw_transcribe_prompted, [B][cap][k] aligned with its `tokens` (-1 / NaN behind lens[i]).             */
+#define CW_TOP_LOGPROBS_MAX 8
+int32_t cw_set_top_logprobs(cw_ctx* ctx, int32_t k);
+int32_t cw_get_top_logprobs(cw_ctx* ctx, int32_t* ids_out, float* lp_out /* [nb][max_target_positions][k] */, int32_t nb);
+int32_t cw_get_transcribe_top_logprobs(cw_ctx* ctx, int32_t* ids_out, float* lp_out /* [B][cap][k] */, int32_t B, int32_t cap);
 int32_t cw_get_logits(cw_ctx* ctx, float* out /* [nb][vocab] */, int32_t nb);       /* last sampled step */
 int32_t cw_set_logits_capture(cw_ctx* ctx, float* host_buf, int32_t max_steps);    /* [steps][nb][vocab] */
 int32_t cw_get_alignment(cw_ctx* ctx, float* out /* [nb][n_align][L][1500] */, int32_t nb, int32_t L);
@@ -588,6 +610,13 @@ int32_t cw_test_sample_seeded(cw_ctx* ctx, int32_t nb, const float* logits, cons
 int32_t cw_test_sample_logprobs(cw_ctx* ctx, int32_t nb, const float* logits, const int32_t* ids, int32_t t, int32_t n_prompt,
                                 int32_t min_new_tokens, int32_t max_length, float temperature, uint64_t seed,
                                 const uint64_t* row_streams, const int32_t* forced_tok, int32_t* choice_out, float* lp_out);
+/* ... and with cw_set_top_logprobs(k) on for this call as well: top_id_out / top_lp_out [nb][k] = the alternatives stored for
+ * sequence index t.  The pad columns of the logits rows (vocab_size .. the padded width) hold +75 during the call, so a kernel
+ * that counted them would list them.  The context's own settings are restored afterwards.                                   */
+int32_t cw_test_sample_top_logprobs(cw_ctx* ctx, int32_t nb, const float* logits, const int32_t* ids, int32_t t, int32_t n_prompt,
+                                    int32_t min_new_tokens, int32_t max_length, float temperature, uint64_t seed,
+                                    const uint64_t* row_streams, const int32_t* forced_tok, int32_t k, int32_t* choice_out,
+                                    float* lp_out, int32_t* top_id_out, float* top_lp_out);
 
 /* ---- measurement -------------------------------------------------------------------------------------- */
 #define CW_STAGE_MEL 0

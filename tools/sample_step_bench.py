@@ -9,11 +9,13 @@ geometry: large-v3 shape, aligned synthetic weights, --rows x 30 s clips residen
 
   --token-logprobs  the step measurement once more with cw_set_token_logprobs on (the sampler also reduces the raw log-sum-exp
                     of every row and stores log_softmax(raw)[token]): step_*_logprobs_ms, off and on in the same build
+  --top-logprobs K [K ...]  (with --token-logprobs) ... and once more per K with cw_set_top_logprobs(K) on top (the sampler also
+                    selects the K best raw logits of every row): step_*_top<K>_ms, all in the same build and process
   --no-fallback-round  leave the fallback round out
 
 Best of --reps after one warm-up, wall time around the call with the stream synchronised.
 usage: python tools/sample_step_bench.py [--dtype bf16] [--rows 8] [--tokens 128] [--temperature 0.6] [--redo 2] [--reps 5]
-                                         [--token-logprobs] [--no-fallback-round]"""
+                                         [--token-logprobs [--top-logprobs 5 8]] [--no-fallback-round]"""
 import argparse, json, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
@@ -29,7 +31,10 @@ def main():
     ap.add_argument("--tokens", type=int, default=128); ap.add_argument("--temperature", type=float, default=0.6)
     ap.add_argument("--redo", type=int, default=2); ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--token-logprobs", action="store_true"); ap.add_argument("--no-fallback-round", action="store_true")
+    ap.add_argument("--top-logprobs", type=int, nargs="+", default=[], metavar="K")
     a = ap.parse_args()
+    if a.top_logprobs and not a.token_logprobs:
+        ap.error("--top-logprobs needs --token-logprobs (cw_set_top_logprobs shares its normaliser)")
     g, v = syn.large_v3_geometry()
     spec = syn.model_spec(g, v, n_align=15)
     B, T = a.rows, a.tokens
@@ -45,13 +50,16 @@ def main():
 
     def steps():
         eng.decode(prompt, 3 + T, min_new_tokens=T)
-    for on in ((False, True) if a.token_logprobs else (False,)):
+    variants = [("", False, 0)] + ([("_logprobs", True, 0)] if a.token_logprobs else []) + [(f"_top{k}", True, k) for k in a.top_logprobs]
+    for tag, on, k in variants:
         eng.set_token_logprobs(on)
+        if on:
+            eng.set_top_logprobs(k)
         for name, temp in (("greedy", 0.0), ("sampling", a.temperature)):
             eng.set_sampling(temp, 1, streams)
             ms, split = timed(eng, steps, a.reps)
-            out[f"step_{name}{'_logprobs' if on else ''}_ms"] = round(split["decode"] / T, 4)
-            out[f"decode_{name}{'_logprobs' if on else ''}_wall_ms"] = ms
+            out[f"step_{name}{tag}_ms"] = round(split["decode"] / T, 4)
+            out[f"decode_{name}{tag}_wall_ms"] = ms
     eng.set_sampling(0.0)
     eng.set_token_logprobs(False)
     if a.no_fallback_round:
