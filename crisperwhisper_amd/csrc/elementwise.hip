@@ -594,7 +594,7 @@ __global__ __launch_bounds__(1024) void beam_topk_kernel(SampleParams p, int n_c
     for (int v = tid; v < p.V; v += blockDim.x) {
         const float x = lg[v];
         rsum += expf(x - rmax);
-        if (v >= tb && !dead(v)) tsum += expf(x - M);
+        if (v >= tb && !dead(v) && x > -INFINITY) tsum += expf(x - M);    // a NaN is no candidate and carries no mass (as in the two-stage form)
     }
     rsum = block_sum(rsum, s_f); __syncthreads();
     tsum = block_sum(tsum, s_f); __syncthreads();
@@ -778,7 +778,7 @@ __global__ __launch_bounds__(64) void beam_topk_merge_kernel(const float* __rest
     const float M = fmaxf(gtext, gts);
     float rsum = 0.f, tsum = 0.f;
     if (lane < BT_NS) {
-        rsum = rec0[lane * BT_REC + 1] * expf(rmax - gmax);
+        if (rmax > -INFINITY) rsum = rec0[lane * BT_REC + 1] * expf(rmax - gmax);    // a slice of -inf logits holds a NaN sum (expf(-inf - -inf)): it adds nothing
         if (bts > -INFINITY) tsum = rec0[lane * BT_REC + 4] * expf(bts - M);
     }
     rsum = wave_sum(rsum); tsum = wave_sum(tsum);

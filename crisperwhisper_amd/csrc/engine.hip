@@ -2157,6 +2157,20 @@ int32_t cw_beam_begin(cw_ctx* c, int32_t n_items, int32_t num_beams, const int32
     return CW_OK;
 }
 
+// The candidate selection of one beam step on the first `rows` rows of the logits buffer (cw_beam_step, and cw_test_beam_topk on
+// caller-supplied rows): [rows][n_cand] best (log-probability, token) pairs into d_cand_val / d_cand_id.
+static int launch_beam_topk(cw_ctx* c, int rows, int n_cand) {
+    SampleParams sp;
+    memset(&sp, 0, sizeof(sp));
+    sp.logits = c->dlogits; sp.V = c->d.vocab_size; sp.ldv = c->Vpad; sp.B = rows; sp.mask = c->d_mask;
+    sp.eos = c->gen.eos_token_id; sp.pad = c->gen.pad_token_id;
+    sp.timestamp_begin = c->gen.no_timestamps_token_id + 1;
+    sp.max_initial_timestamp_index = c->gen.max_initial_timestamp_index;
+    sp.cfg = c->d_cfg; sp.pos = c->d_pos; sp.ids_stride = c->d.max_target_positions; sp.ids = c->d_ids;
+    sp.embed_bf16 = c->bf16 ? 1 : 0;
+    return KD(c, cw_launch_beam_topk, sp, n_cand, c->d_cand_val, c->d_cand_id, c->d_topk_scratch, c->st);
+}
+
 int32_t cw_beam_step(cw_ctx* c, int32_t n_cand, float* cand_logprob, int32_t* cand_token) {
     if (c->beam_K <= 0) return fail(c, CW_ERR_STATE, "cw_beam_begin not called");
     if (n_cand < 1 || n_cand > 64) return fail(c, CW_ERR_INVALID, "n_cand=%d out of range", n_cand);
@@ -2167,15 +2181,7 @@ int32_t cw_beam_step(cw_ctx* c, int32_t n_cand, float* cand_logprob, int32_t* ca
     StageTimer tm(c, CW_STAGE_DECODE);
     c->hist_short = c->beam_pos + 1 <= 64;   // keys 0 .. beam_pos
     CWCHK(c, decode_step(c, rows, true));
-    SampleParams sp;
-    memset(&sp, 0, sizeof(sp));
-    sp.logits = c->dlogits; sp.V = c->d.vocab_size; sp.ldv = c->Vpad; sp.B = rows; sp.mask = c->d_mask;
-    sp.eos = c->gen.eos_token_id; sp.pad = c->gen.pad_token_id;
-    sp.timestamp_begin = c->gen.no_timestamps_token_id + 1;
-    sp.max_initial_timestamp_index = c->gen.max_initial_timestamp_index;
-    sp.cfg = c->d_cfg; sp.pos = c->d_pos; sp.ids_stride = c->d.max_target_positions; sp.ids = c->d_ids;
-    sp.embed_bf16 = c->bf16 ? 1 : 0;
-    CWCHK(c, KD(c, cw_launch_beam_topk, sp, n_cand, c->d_cand_val, c->d_cand_id, c->d_topk_scratch, c->st));
+    CWCHK(c, launch_beam_topk(c, rows, n_cand));
     KCHK(c);
     tm.stop();
     HIPCHK(c, hipMemcpy(cand_logprob, c->d_cand_val, (size_t)rows * n_cand * 4, hipMemcpyDeviceToHost));
@@ -4237,6 +4243,65 @@ int32_t cw_test_beam_state(cw_ctx* c, int32_t rows, int32_t* ids, int32_t* anc, 
     HIPCHK(c, hipMemcpy(ids, c->d_ids, (size_t)rows * TGT * 4, hipMemcpyDeviceToHost));
     HIPCHK(c, hipMemcpy(anc, c->d_anc, (size_t)rows * TGT * 4, hipMemcpyDeviceToHost));
     HIPCHK(c, hipMemcpy(pos, c->d_pos, (size_t)rows * 4, hipMemcpyDeviceToHost));
+    return CW_OK;
+}
+
+// One launch of the beam-search candidate selection, exactly as cw_beam_step launches it (launch_beam_topk), on caller-supplied
+// rows: logits [nb][V] raw f32, ids [nb][t] = prompt + generated so far.  The pad columns V .. Vpad-1 hold +75 during the call, the
+// candidate buffers are filled with 0xff bytes and every float of the slice-record scratch with 1e30 beforehand: a pad column that
+// counted, a stale or unwritten list entry would win every selection.  cand_val / cand_id [max_batch * 64]: the WHOLE candidate
+// buffers as the device holds them afterwards ([nb][n_cand] written, 0xff behind).
+int32_t cw_test_beam_topk(cw_ctx* c, int32_t nb, const float* logits, const int32_t* ids, int32_t t, int32_t n_prompt,
+                          int32_t min_new_tokens, int32_t n_cand, float* cand_val, int32_t* cand_id) {
+    const int V = c->d.vocab_size, TGT = c->d.max_target_positions, Bm = c->Bm;
+    if (!logits || !ids || !cand_val || !cand_id) return fail(c, CW_ERR_INVALID, "test_beam_topk: null argument");
+    if (!c->gen_set) return fail(c, CW_ERR_STATE, "cw_set_generation not called");
+    if (c->beam_K > 0) return fail(c, CW_ERR_STATE, "test_beam_topk: a beam search is open (the hook overwrites its state)");
+    if (nb < 1 || nb > Bm || nb > 64) return fail(c, CW_ERR_INVALID, "test_beam_topk: nb=%d outside 1 .. %d", nb, Bm < 64 ? Bm : 64);
+    if (n_cand < 1 || n_cand > 64) return fail(c, CW_ERR_INVALID, "test_beam_topk: n_cand=%d outside 1 .. 64", n_cand);
+    if (n_prompt < 1 || t < n_prompt || t >= TGT) return fail(c, CW_ERR_INVALID, "test_beam_topk: t=%d / n_prompt=%d out of range", t, n_prompt);
+    if (min_new_tokens < 0) return fail(c, CW_ERR_INVALID, "test_beam_topk: min_new_tokens=%d is negative", min_new_tokens);
+    std::vector<int> hid((size_t)nb * TGT, c->gen.pad_token_id), posv(nb, t - 1);
+    for (int b = 0; b < nb; ++b)
+        for (int k = 0; k < t; ++k) {
+            const int tok = ids[(size_t)b * t + k];
+            if (tok < 0 || tok >= V) return fail(c, CW_ERR_INVALID, "test_beam_topk: token %d out of range", tok);
+            hid[(size_t)b * TGT + k] = tok;
+        }
+    CWCHK(c, beam_alloc(c));
+    HIPCHK(c, hipStreamSynchronize(c->st));
+    HIPCHK(c, hipMemcpy(c->d_ids, hid.data(), hid.size() * 4, hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemcpy(c->d_pos, posv.data(), (size_t)nb * 4, hipMemcpyHostToDevice));
+    const int cfg[4] = {n_prompt, min_new_tokens, TGT, 0};
+    HIPCHK(c, hipMemcpy(c->d_cfg, cfg, sizeof(cfg), hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemcpy2D(c->dlogits, (size_t)c->Vpad * 4, logits, (size_t)V * 4, (size_t)V * 4, nb, hipMemcpyHostToDevice));
+    const int n_padcol = c->Vpad - V;
+    if (n_padcol > 0) {                               // the pad columns hold +75 for this call: they must never count
+        const std::vector<float> hot((size_t)nb * n_padcol, 75.0f);
+        HIPCHK(c, hipMemcpy2D(c->dlogits + V, (size_t)c->Vpad * 4, hot.data(), (size_t)n_padcol * 4, (size_t)n_padcol * 4, nb, hipMemcpyHostToDevice));
+    }
+    HIPCHK(c, hipMemset(c->d_cand_val, 0xff, (size_t)Bm * 64 * 4));
+    HIPCHK(c, hipMemset(c->d_cand_id, 0xff, (size_t)Bm * 64 * 4));
+    const std::vector<float> poison(KD(c, cw_beam_topk_scratch_floats, Bm), 1e30f);
+    HIPCHK(c, hipMemcpy(c->d_topk_scratch, poison.data(), poison.size() * 4, hipMemcpyHostToDevice));
+    const int r = launch_beam_topk(c, nb, n_cand);
+    if (r != CW_OK) fail(c, r, "test_beam_topk: launch rejected");
+    hipError_t er = hipStreamSynchronize(c->st);
+    if (er == hipSuccess) er = hipGetLastError();
+    if (n_padcol > 0) HIPCHK(c, hipMemset2D(c->dlogits + V, (size_t)c->Vpad * 4, 0, (size_t)n_padcol * 4, nb));
+    if (r != CW_OK) return r;
+    if (er != hipSuccess) return fail(c, CW_ERR_HIP, "test_beam_topk: %s", hipGetErrorString(er));
+    HIPCHK(c, hipMemcpy(cand_val, c->d_cand_val, (size_t)Bm * 64 * 4, hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(cand_id, c->d_cand_id, (size_t)Bm * 64 * 4, hipMemcpyDeviceToHost));
+    return CW_OK;
+}
+
+// The decoder input rows of the next step as the device holds them: x [rows][d_model] (what cw_beam_advance / the sampler wrote).
+// Read-only.
+int32_t cw_test_beam_x(cw_ctx* c, int32_t rows, float* x) {
+    if (rows < 1 || rows > c->Bm || !x) return fail(c, CW_ERR_INVALID, "test_beam_x: rows=%d", rows);
+    HIPCHK(c, hipStreamSynchronize(c->st));
+    HIPCHK(c, hipMemcpy(x, c->dx, (size_t)rows * c->d.d_model * 4, hipMemcpyDeviceToHost));
     return CW_OK;
 }
 

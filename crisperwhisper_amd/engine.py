@@ -851,6 +851,29 @@ class Engine:
         self._chk(self.lib.cw_test_beam_state(self.ctx, int(rows), _ptr(ids), _ptr(anc), _ptr(pos)))
         return ids, anc, pos
 
+    def test_beam_topk(self, logits: np.ndarray, ids: np.ndarray, n_prompt: int, n_cand: int, min_new_tokens: int = 0):
+        """One launch of the beam-search candidate selection on caller rows (cw_test_beam_topk): returns (values [nb][n_cand] f32,
+        tokens [nb][n_cand] int32, untouched) where ``untouched`` says that everything behind the nb * n_cand written entries of
+        the device's candidate buffers still holds the 0xff bytes the hook put there."""
+        lg = np.ascontiguousarray(logits, np.float32)
+        ids = _i32(ids)
+        if ids.ndim != 2 or lg.shape != (ids.shape[0], self.spec.vocab_size):
+            raise ValueError(f"logits must be [nb][{self.spec.vocab_size}] and ids [nb][t], got {lg.shape} and {ids.shape}")
+        nb, t = ids.shape
+        val = np.zeros(self.max_batch * 64, np.float32)
+        tok = np.zeros(self.max_batch * 64, np.int32)
+        self._chk(self.lib.cw_test_beam_topk(self.ctx, nb, _ptr(lg), _ptr(ids), t, int(n_prompt), int(min_new_tokens), int(n_cand),
+                                             _ptr(val), _ptr(tok)))
+        n = nb * int(n_cand)
+        untouched = bool(np.all(val[n:].view(np.uint32) == 0xffffffff) and np.all(tok[n:] == -1))
+        return val[:n].reshape(nb, n_cand).copy(), tok[:n].reshape(nb, n_cand).copy(), untouched
+
+    def test_beam_x(self, rows: int) -> np.ndarray:
+        """The decoder input rows of the next step as the device holds them, [rows][d_model] (cw_test_beam_x)."""
+        x = np.zeros((int(rows), self.spec.d_model), np.float32)
+        self._chk(self.lib.cw_test_beam_x(self.ctx, int(rows), _ptr(x)))
+        return x
+
     def test_sample(self, logits: np.ndarray, ids: np.ndarray, n_prompt: int, min_new_tokens: int = 0,
                     max_length: Optional[int] = None) -> np.ndarray:
         """One launch of the fused logits processors + greedy choice on caller rows (cw_test_sample)."""

@@ -591,6 +591,18 @@ int32_t cw_test_self_attention(cw_ctx* ctx, int32_t B, int32_t H, int32_t cap, i
 /* Beam-search state of rows 0..rows-1 after cw_beam_begin / cw_beam_advance: ids [rows][max_target_positions], anc
  * [rows][max_target_positions] (cache row of every key position), pos [rows].                                       */
 int32_t cw_test_beam_state(cw_ctx* ctx, int32_t rows, int32_t* ids, int32_t* anc, int32_t* pos);
+/* One launch of the beam-search candidate selection as cw_beam_step launches it (log-softmax of the raw row, the logits
+ * processors on it, the n_cand best (value, token) pairs per row in (value desc, token asc) order) on caller-supplied rows: logits
+ * [nb][vocab], ids [nb][t].  The pad columns of the logits rows hold +75 during the call, the candidate buffers are filled with
+ * 0xff bytes and the slice records with 1e30 beforehand.  cand_val / cand_id [max_batch * 64]: the whole candidate buffers
+ * afterwards, [nb][n_cand] written.  The kernel form follows cw_test_set_option("beam_topk_1block").  Refused before any launch:
+ * a null pointer, nb outside 1 .. min(max_batch, 64), n_cand outside 1 .. 64, n_prompt < 1, t outside n_prompt ..
+ * max_target_positions - 1, a negative min_new_tokens, an id outside the vocabulary, an open beam search (its state would be
+ * overwritten).                                                                                                             */
+int32_t cw_test_beam_topk(cw_ctx* ctx, int32_t nb, const float* logits, const int32_t* ids, int32_t t, int32_t n_prompt,
+                          int32_t min_new_tokens, int32_t n_cand, float* cand_val, int32_t* cand_id);
+/* The decoder input rows of the next step as the device holds them, x [rows][d_model].  Read-only.                  */
+int32_t cw_test_beam_x(cw_ctx* ctx, int32_t rows, float* x);
 /* One launch of the fused logits processors + greedy choice (MinNewTokensLength, SuppressTokensAtBegin, SuppressTokens,
  * WhisperTimeStamp: TF/generation/logits_process.py:203-260, 1816-2047; argmax TF/generation/utils.py:2925) on
  * caller-supplied rows: logits [nb][vocab], ids [nb][t] = prompt + tokens generated so far; choice_out [nb] = token for

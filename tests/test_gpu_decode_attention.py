@@ -343,8 +343,16 @@ def test_beam_ancestry_end_to_end(dt):
         ids'[r] = ids[p][:t] ++ [token] ++ ids[r][t+1:],  anc'[r] = anc[p][:t-1] ++ [p] ++ [r]*,  pos' = pos + 1.
     At several steps the read-back table drives cw_test_self_attention over K/V in which cache row c at position k holds what
     the hypothesis in slot c wrote at step k, against float64 attention over a PHYSICALLY reordered host copy of the cache
-    (every step: rows copied from their parents, as HF's cache.reorder_cache does)."""
+    (every step: rows copied from their parents, as HF's cache.reorder_cache does).
+    The advances then go on to the end of the position table (446 in all, the same state checks after each).  At a handful of
+    steps, the first and the last among them, the next-step embedding rows beam_commit_kernel wrote (cw_test_beam_x) are held
+    bit for bit to embed[token[r]] + pos_embed[t] from the loaded weights: the f32 sum on the f32 engine; on the 16-bit engines
+    the embedding row rounded to the 16-bit type, the f32 sum, then the 2^-12 residual grid (tests/beam_refs.py: resid_grid,
+    shown exact on the CPU by tests/test_beam_refs.py).  The advance to t == max_target_positions leaves the rows untouched."""
+    from tests.beam_refs import resid_grid
     g, v, W, spec = Hh.tiny_setup()
+    embed = round16(dt, W["model.decoder.embed_tokens.weight"])
+    pos_embed = np.asarray(W["model.decoder.embed_positions.weight"], np.float32)
     items, K, H = 3, 5, 2
     R, TGT = items * K, spec.max_target_positions
     rng = np.random.default_rng(17)
@@ -364,8 +372,10 @@ def test_beam_ancestry_end_to_end(dt):
         kphys, vphys = kdev.copy(), vdev.copy()           # host caches, reordered by copying rows
         d_ids, d_anc, d_pos = eng.test_beam_state(R)
         assert np.array_equal(d_ids, ids) and np.array_equal(d_anc, anc) and (d_pos == pos).all()
-        checks = 0
-        for step in range(200):
+        checks = x_checks = 0
+        x_prev = None
+        n_steps = TGT - n_prompt + 1                      # the last advance has t == max_target_positions
+        for step in range(n_steps):
             par = _parents(rng, step, items, K)
             tok = rng.integers(0, v.size, R).astype(np.int32)
             kphys[:, :, pos] = kdev[:, :, pos]            # the decode step at `pos` writes every row's own slot
@@ -388,6 +398,21 @@ def test_beam_ancestry_end_to_end(dt):
             assert (d_pos == pos).all(), (step, d_pos.tolist(), pos)
             assert np.array_equal(d_anc, anc), (step, np.argwhere(d_anc != anc)[:5].tolist())
             assert np.array_equal(d_ids, ids), (step, np.argwhere(d_ids != ids)[:5].tolist())
+            if step in (0, 1, 40, 128, 199, n_steps - 3, n_steps - 2, n_steps - 1):
+                x_checks += 1
+                x = eng.test_beam_x(R)
+                if t < TGT:
+                    s64 = embed[tok].astype(np.float64) + pos_embed[t].astype(np.float64)
+                    want = embed[tok] + pos_embed[t]                      # the f32 sum is the float64 sum rounded once
+                    assert want.dtype == np.float32 and np.array_equal(want, s64.astype(np.float32))
+                    if dt != "f32":
+                        want = resid_grid(want)
+                    assert x.tobytes() == want.tobytes(), (dt, step, np.argwhere(x != want)[:5].tolist())
+                else:                                     # nothing to feed at a position the table does not have
+                    assert step == n_steps - 1 and x.tobytes() == x_prev.tobytes(), (dt, step)
+                x_prev = x
+            if step == 199:
+                assert checks == 5 and pos == n_prompt - 1 + 200
             if step in (40, 125, 126, 127, 128, 199):
                 checks += 1
                 kc, vc = kphys.copy(), vphys.copy()
@@ -408,7 +433,7 @@ def test_beam_ancestry_end_to_end(dt):
                 ref, tol = reference(q, keys_of, vals_of)
                 got = eng.test_self_attention(q.reshape(R, -1), kd, vd, n - 1, anc=d_anc)
                 check(got, ref, tol, f"{dt} step {step} histories {n.tolist()}")
-        assert checks == 6 and pos == n_prompt - 1 + 200
+        assert checks == 6 and x_checks == 8 and pos == TGT
     finally:
         eng.close()
 
