@@ -105,6 +105,7 @@ _SIGS = {
     "cw_set_top_logprobs": (_I, [_P, _I]),
     "cw_get_top_logprobs": (_I, [_P, _P, _P, _I]),
     "cw_get_transcribe_top_logprobs": (_I, [_P, _P, _P, _I, _I]),
+    "cw_set_sequence_bias": (_I, [_P, _I, _P, _P, _P]),
     "cw_get_logits": (_I, [_P, _P, _I]),
     "cw_set_logits_capture": (_I, [_P, _P, _I]),
     "cw_get_alignment": (_I, [_P, _P, _I, _I]),
@@ -172,6 +173,7 @@ _SIGS = {
     "cw_test_sample_seeded": (_I, [_P, _I, _P, _P, _I, _I, _I, _I, C.c_float, C.c_uint64, _P, _P]),
     "cw_test_sample_logprobs": (_I, [_P, _I, _P, _P, _I, _I, _I, _I, C.c_float, C.c_uint64, _P, _P, _P, _P]),
     "cw_test_sample_top_logprobs": (_I, [_P, _I, _P, _P, _I, _I, _I, _I, C.c_float, C.c_uint64, _P, _P, _I, _P, _P, _P, _P]),
+    "cw_test_sample_biased": (_I, [_P, _I, _P, _P, _I, _I, _I, _I, C.c_float, C.c_uint64, _P, _P, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P]),
     "cw_stage_times": (_I, [_P, _P, _P, _I]),
     "cw_time_kernel": (_I, [_P, _I, _I, _I, _P, _P]),
     "cw_time_decode_stage": (_I, [_P, _I, _I, _I, _P, _P, _P, _P]),

@@ -247,7 +247,33 @@ __device__ inline float gumbel_from_bits(unsigned x) {
 }
 // TOPK (block-uniform, a template parameter so that the instantiation without it keeps its registers): also emit the slice's
 // p.top_k best raw candidates (v < V, x > -inf: masked tokens count, pad columns and NaN do not) into p.top_part.
-template <bool TOPK>
+//
+// BIAS (block-uniform, a template parameter for the same reason): sequence_bias (include/crisperwhisper.h, cw_set_sequence_bias).
+// Every score this kernel consumes becomes fl32(x + bias_row[v]); the raw quantities (p.tok_lp's sums, TOPK's candidates) do not.
+// The block looks only at the table entries whose last token lies in its slice (at most SB_MAX_SEQ, one per thread): thread e
+// matches entry e's prefix against the row's id suffix; then the first thread of every run of entries with one last token adds
+// the run's applying biases in table order -- one thread, a fixed order, no atomics -- and stores the sum into the slice's dense
+// bias row in LDS (4 * per4 floats, zero elsewhere), which the load loop reads next to the logits.  The cost does not depend on
+// how many entries hit: 256 entries in one slice are 256 threads with one entry each.
+__device__ inline bool seq_bias_applies(const int* __restrict__ tab, int e, const int* __restrict__ ids, int t) {
+    const int o = tab[SB_OFF + e], L = tab[SB_OFF + e + 1] - o;
+    if (L == 1) return true;
+    if (L < 1 || L > SB_MAX_LEN || L > t) return false;     // L <= t, not L - 1 <= t: SequenceBiasLogitsProcessor skips those
+    bool ok = true;
+    for (int k = 0; k < L - 1; ++k) ok &= (ids[t - L + 1 + k] == tab[SB_TOK + o + k]);
+    return ok;
+}
+// the row's bias for one token (stage 2 needs it for the token it writes): binary search for the token's run, then the same sum
+__device__ inline float seq_bias_of(const int* __restrict__ tab, int tok, const int* __restrict__ ids, int t) {
+    const int n = min(tab[SB_SLICE + SAMPLE_NS], SB_MAX_SEQ);
+    int lo = 0, hi = n;
+    while (lo < hi) { const int mid = (lo + hi) >> 1; if (tab[SB_LAST + mid] < tok) lo = mid + 1; else hi = mid; }
+    float sum = 0.f;
+    for (int e = lo; e < n && tab[SB_LAST + e] == tok; ++e)
+        if (seq_bias_applies(tab, e, ids, t)) sum = __fadd_rn(sum, __int_as_float(tab[SB_VAL + e]));
+    return sum;
+}
+template <bool TOPK, bool BIAS>
 __global__ __launch_bounds__(256) void sample_partial_kernel(SampleParams p, SamplePart* __restrict__ part) {
     __shared__ float s_f[64];
     __shared__ int s_i[64];
@@ -283,9 +309,40 @@ __global__ __launch_bounds__(256) void sample_partial_kernel(SampleParams p, Sam
 #pragma unroll
             for (int j = 0; j < 4; ++j) rv[it][j] = -INFINITY;
     }
+    __shared__ float4 s_bias4[BIAS ? 1024 : 1];                            // BIAS: the slice's dense bias row (per4 <= 1024: cw_launch_sample)
+    if constexpr (BIAS) {
+        __shared__ int s_bl[SB_MAX_SEQ];                                   // last token of entry e0 + i (-1 past the slice's entries)
+        __shared__ float s_bv[SB_MAX_SEQ];                                 // its bias where it applies to this row, else NaN
+        float* s_bias = (float*)s_bias4;
+        for (int k = tid; k < per4; k += 256) s_bias4[k] = make_float4(0.f, 0.f, 0.f, 0.f);
+        const int* tab = p.seq_bias;
+        const int e0 = tab[SB_SLICE + sl], ne = min(tab[SB_SLICE + sl + 1] - e0, SB_MAX_SEQ);
+        const bool have = tid < ne && e0 >= 0 && e0 + ne <= SB_MAX_SEQ;
+        int mylast = -1;
+        float myval = NAN;
+        if (have) {
+            mylast = tab[SB_LAST + e0 + tid];
+            if (seq_bias_applies(tab, e0 + tid, ids, t)) myval = __int_as_float(tab[SB_VAL + e0 + tid]);
+        }
+        s_bl[tid] = mylast; s_bv[tid] = myval;
+        __syncthreads();
+        const int rel = mylast - lo4 * 4;
+        if (have && rel >= 0 && rel < per4 * 4 && (tid == 0 || s_bl[tid - 1] != mylast)) {   // the first entry of a token's run
+            float sum = 0.f;
+            for (int e = tid; e < SB_MAX_SEQ && s_bl[e] == mylast; ++e)
+                if (s_bv[e] == s_bv[e]) sum = __fadd_rn(sum, s_bv[e]);     // table biases are finite: NaN marks "does not apply"
+            s_bias[rel] = sum;
+        }
+        __syncthreads();
+    }
     for (int i4 = lo4 + tid, it = 0; i4 < hi4; i4 += 256, ++it) {
         const float4 x = lg4[i4]; const uchar4 mk = mk4[i4];
-        const float xs[4] = {x.x, x.y, x.z, x.w};
+        const float xs[4] = {x.x, x.y, x.z, x.w};                          // raw
+        float xe[4] = {x.x, x.y, x.z, x.w};                                // what the processors see
+        if constexpr (BIAS) {
+            const float4 bb = s_bias4[i4 - lo4];
+            xe[0] = __fadd_rn(x.x, bb.x); xe[1] = __fadd_rn(x.y, bb.y); xe[2] = __fadd_rn(x.z, bb.z); xe[3] = __fadd_rn(x.w, bb.w);
+        }
         const unsigned char ms[4] = {mk.x, mk.y, mk.z, mk.w};
         unsigned rnd[4] = {0u, 0u, 0u, 0u};
         if (sampling) philox4x32_10((unsigned)i4, (unsigned)t, stream_lo, stream_hi, seed_lo, seed_hi, rnd);
@@ -299,7 +356,7 @@ __global__ __launch_bounds__(256) void sample_partial_kernel(SampleParams p, Sam
                 if (last_ts) dead |= penult_ts ? (v >= tb) : (v < p.eos);
                 dead |= (v >= tb && v < ts_floor);
                 if (at_begin) dead |= (v < tb) || (v > ts_cap);
-                if (!dead) val = xs[j];
+                if (!dead) val = xe[j];
                 ArgPair c = {val, v};
                 if (v < tb) bt = arg_better(bt, c); else bs = arg_better(bs, c);
                 if (sampling && !dead) {
@@ -408,7 +465,7 @@ __global__ __launch_bounds__(256) void sample_partial_kernel(SampleParams p, Sam
     }
 }
 
-template <typename T, bool TOPK>
+template <typename T, bool TOPK, bool BIAS>
 __global__ __launch_bounds__(1024) void sample_kernel(SampleParams p) {
     __shared__ float s_f[64];
     __shared__ int s_i[64];
@@ -505,7 +562,9 @@ __global__ __launch_bounds__(1024) void sample_kernel(SampleParams p) {
                 if (pr[i].bt_v > -INFINITY) st += pr[i].pad[0] * expf(pr[i].bt_v - M);
             const float tot = acc + (force_ts ? 0.f : st);
             if (tot > 0.f && tok >= 0 && tok < p.V) {
-                p.lp_sum[b] += lg[tok] - (M + logf(tot));
+                float xt = lg[tok];
+                if constexpr (BIAS) xt = __fadd_rn(xt, seq_bias_of(p.seq_bias, tok, ids, t));    // the score stage 1 saw
+                p.lp_sum[b] += xt - (M + logf(tot));
                 p.lp_cnt[b] += 1;
             }
         }
@@ -883,22 +942,24 @@ int cw_launch_align_gather(const float* align, const int* row_of_pos, int n_item
     return CW_OK;
 }
 
+template <bool TOPK, bool BIAS>
+static void launch_sample_t(const SampleParams& p, hipStream_t st) {
+    hipLaunchKernelGGL((sample_partial_kernel<TOPK, BIAS>), dim3(p.B, SAMPLE_NS), dim3(256), 0, st, p, (SamplePart*)p.partials);
+    if (p.embed_bf16)
+        hipLaunchKernelGGL((sample_kernel<bf16_t, TOPK, BIAS>), dim3(p.B), dim3(256), 0, st, p);
+    else
+        hipLaunchKernelGGL((sample_kernel<float, TOPK, BIAS>), dim3(p.B), dim3(256), 0, st, p);
+}
 int cw_launch_sample(const SampleParams& p, hipStream_t st) {
+    static_assert(SAMPLE_NS == 16 && SB_OFF > SB_SLICE + SAMPLE_NS, "the sequence_bias table holds one range per sampler slice");
     if (!p.partials || (p.ldv >> 2) > SAMPLE_NS * 1024 || (p.ldv & 3)) return CW_ERR_INVALID;
+    const bool bias = p.seq_bias != nullptr;                    // sequence_bias: the instantiations that also add the table
     if (p.top_k != 0) {                                         // top_logprobs: the instantiations that also select
         if (p.top_k < 0 || p.top_k > CW_TOP_LOGPROBS_MAX || !p.top_part || !p.top_id || !p.top_lp || !p.tok_lp) return CW_ERR_INVALID;
-        hipLaunchKernelGGL(sample_partial_kernel<true>, dim3(p.B, SAMPLE_NS), dim3(256), 0, st, p, (SamplePart*)p.partials);
-        if (p.embed_bf16)
-            hipLaunchKernelGGL((sample_kernel<bf16_t, true>), dim3(p.B), dim3(256), 0, st, p);
-        else
-            hipLaunchKernelGGL((sample_kernel<float, true>), dim3(p.B), dim3(256), 0, st, p);
+        if (bias) launch_sample_t<true, true>(p, st); else launch_sample_t<true, false>(p, st);
         return CW_OK;
     }
-    hipLaunchKernelGGL(sample_partial_kernel<false>, dim3(p.B, SAMPLE_NS), dim3(256), 0, st, p, (SamplePart*)p.partials);
-    if (p.embed_bf16)
-        hipLaunchKernelGGL((sample_kernel<bf16_t, false>), dim3(p.B), dim3(256), 0, st, p);
-    else
-        hipLaunchKernelGGL((sample_kernel<float, false>), dim3(p.B), dim3(256), 0, st, p);
+    if (bias) launch_sample_t<false, true>(p, st); else launch_sample_t<false, false>(p, st);
     return CW_OK;
 }
 

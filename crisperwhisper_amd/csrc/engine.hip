@@ -161,6 +161,10 @@ struct cw_ctx {
     void* d_top_part = nullptr;                               // [Bm][16][CW_TOP_LOGPROBS_MAX] (value, id) pairs of the sampler's stage 1
     std::vector<std::vector<int>> tr_top_id;                  // ... of the last cw_transcribe: top_k entries per token of every item
     std::vector<std::vector<float>> tr_top_lp;
+    // sequence_bias (cw_set_sequence_bias): the device table in the layout of kernels.h, its host copy and entry count (0: off)
+    int* d_seq_bias = nullptr;
+    std::vector<int> sb_host;
+    int sb_n = 0;
     float logprob_thr = NAN, no_speech_thr = NAN;             // cw_set_thresholds (NaN: unset)
     void* d_sample_part = nullptr;            // [Bm][16] 32-byte slice records of the two-stage sampler
     void* d_sample_pert = nullptr;            // [Bm][16] 16-byte records of the perturbed winners (seeded sampling)
@@ -1542,6 +1546,7 @@ static int launch_sample(cw_ctx* c, int nb, bool forced) {
     if (c->score_tokens) { sp.lp_sum = c->d_lp_sum; sp.lp_cnt = c->d_lp_cnt; }
     if (c->tok_lp_on) sp.tok_lp = c->d_tok_lp;
     if (c->tok_lp_on && c->top_k > 0) { sp.top_k = c->top_k; sp.top_part = c->d_top_part; sp.top_id = c->d_top_id; sp.top_lp = c->d_top_lp; }
+    if (c->sb_n > 0) sp.seq_bias = c->d_seq_bias;
     sp.epoch = c->d_epoch;
     sp.samp = c->d_samp; sp.pert = c->d_sample_pert;
     (void)forced;
@@ -1990,6 +1995,68 @@ int32_t cw_get_transcribe_top_logprobs(cw_ctx* c, int32_t* ids_out, float* lp_ou
     return CW_OK;
 }
 
+// ---- sequence_bias: phrase boosting inside the sampler kernels (include/crisperwhisper.h) ------------------------------------
+// Checks the caller's table and lays it out as the kernels read it (kernels.h): entries ordered by last token, for one last token
+// the length-1 entry first and the longer ones in the caller's order, plus the entry range of each of the 16 vocabulary slices of
+// the sampler's stage 1.  Touches no state.
+static int seq_bias_table(cw_ctx* c, int n_seq, const int32_t* tokens, const int32_t* lengths, const float* bias, std::vector<int>* out,
+                          const char* who) {
+    out->assign(SB_WORDS, 0);
+    if (n_seq < 0 || n_seq > SB_MAX_SEQ) return fail(c, CW_ERR_INVALID, "%s: %d sequences outside 0 .. %d", who, n_seq, SB_MAX_SEQ);
+    if (n_seq == 0) return CW_OK;
+    if (!tokens || !lengths || !bias) return fail(c, CW_ERR_INVALID, "%s: null argument", who);
+    const int V = c->d.vocab_size;
+    std::vector<int> start(n_seq), order(n_seq);
+    int total = 0;
+    for (int i = 0; i < n_seq; ++i) {
+        if (lengths[i] < 1 || lengths[i] > SB_MAX_LEN) return fail(c, CW_ERR_INVALID, "%s: sequence %d has %d tokens, outside 1 .. %d", who, i, lengths[i], SB_MAX_LEN);
+        if (!std::isfinite(bias[i])) return fail(c, CW_ERR_INVALID, "%s: the bias of sequence %d is not finite", who, i);
+        start[i] = total; total += lengths[i]; order[i] = i;
+    }
+    for (int k = 0; k < total; ++k)
+        if (tokens[k] < 0 || tokens[k] >= V) return fail(c, CW_ERR_INVALID, "%s: token %d outside 0 .. %d", who, tokens[k], V - 1);
+    for (int i = 0; i < n_seq; ++i)
+        for (int j = 0; j < i; ++j)
+            if (lengths[i] == lengths[j] && !memcmp(tokens + start[i], tokens + start[j], (size_t)lengths[i] * 4))
+                return fail(c, CW_ERR_INVALID, "%s: sequences %d and %d are the same", who, j, i);
+    auto last = [&](int i) { return tokens[start[i] + lengths[i] - 1]; };
+    std::stable_sort(order.begin(), order.end(), [&](int a, int b) {
+        if (last(a) != last(b)) return last(a) < last(b);
+        return (lengths[a] == 1) > (lengths[b] == 1);
+    });
+    int* w = out->data();
+    const int per4 = ((c->Vpad >> 2) + 15) / 16;                 // float4 groups per slice, as sample_partial_kernel cuts them
+    int off = 0;
+    for (int e = 0; e < n_seq; ++e) w[SB_SLICE + std::min(15, (last(order[e]) >> 2) / per4) + 1] += 1;
+    for (int s = 0; s < 16; ++s) w[SB_SLICE + s + 1] += w[SB_SLICE + s];     // [s]: entries whose last token lies in a slice below s
+    for (int e = 0; e < n_seq; ++e) {
+        const int i = order[e];
+        w[SB_OFF + e] = off;
+        memcpy(&w[SB_VAL + e], &bias[i], 4);
+        w[SB_LAST + e] = last(i);
+        memcpy(&w[SB_TOK + off], tokens + start[i], (size_t)lengths[i] * 4);
+        off += lengths[i];
+    }
+    w[SB_OFF + n_seq] = off;
+    return CW_OK;
+}
+// installs a table laid out by seq_bias_table; only the off <-> on transition changes which kernels the step graphs hold
+static int seq_bias_install(cw_ctx* c, const std::vector<int>& tab, int n_seq) {
+    if (n_seq > 0 && !c->d_seq_bias) CWCHK(c, dmalloc(c, &c->d_seq_bias, (size_t)SB_WORDS * 4));
+    HIPCHK(c, hipStreamSynchronize(c->st));                    // no step in flight reads the old contents
+    if (n_seq > 0) HIPCHK(c, hipMemcpy(c->d_seq_bias, tab.data(), (size_t)SB_WORDS * 4, hipMemcpyHostToDevice));
+    if ((n_seq > 0) != (c->sb_n > 0)) drop_step_graphs(c);
+    c->sb_n = n_seq;
+    c->sb_host = tab;
+    return CW_OK;
+}
+int32_t cw_set_sequence_bias(cw_ctx* c, int32_t n_seq, const int32_t* tokens, const int32_t* lengths, const float* bias) {
+    std::vector<int> tab;
+    CWCHK(c, seq_bias_table(c, n_seq, tokens, lengths, bias, &tab, "set_sequence_bias"));
+    if (c->beam_K > 0) return fail(c, CW_ERR_STATE, "set_sequence_bias: a beam search is open");
+    return seq_bias_install(c, tab, n_seq);
+}
+
 // ---- stochastic half: seeded Gumbel-max sampling in the sampler kernels (include/crisperwhisper.h) ----------------------
 // The kernels read temperature, seed and stream ids from d_samp, so the captured step graphs stay as they are.
 static int write_sampling(cw_ctx* c, float temperature, uint64_t seed, const uint64_t* row_streams, int nb, const char* who) {
@@ -2119,6 +2186,7 @@ static int beam_alloc(cw_ctx* c) {
 int32_t cw_beam_begin(cw_ctx* c, int32_t n_items, int32_t num_beams, const int32_t* prompt, int32_t n_prompt,
                       int32_t max_length, int32_t min_new_tokens) {
     const int D = c->d.d_model, V = c->d.vocab_size, TGT = c->d.max_target_positions;
+    if (c->sb_n > 0) return fail(c, CW_ERR_STATE, "beam search does not carry sequence_bias (it would be added to log_softmax(raw)): clear the table (cw_set_sequence_bias with n_seq = 0) first");
     if (!c->gen_set) return fail(c, CW_ERR_STATE, "cw_set_generation not called");
     if (num_beams < 1 || n_items < 1 || n_items > c->nb_encoded) return fail(c, CW_ERR_STATE, "beam_begin: %d items but %d windows encoded", n_items, c->nb_encoded);
     const int rows = n_items * num_beams;
@@ -4384,6 +4452,35 @@ int32_t cw_test_sample_top_logprobs(cw_ctx* c, int32_t nb, const float* logits, 
     CWCHK(c, cw_set_top_logprobs(c, was_on ? was_k : 0));
     if (!was_on) CWCHK(c, cw_set_token_logprobs(c, 0));
     return r;
+}
+// ... and with a sequence_bias table for this call only; proc_lp_out [nb] = what the step added to the processed-score sum.
+int32_t cw_test_sample_biased(cw_ctx* c, int32_t nb, const float* logits, const int32_t* ids, int32_t t, int32_t n_prompt,
+                              int32_t min_new_tokens, int32_t max_length, float temperature, uint64_t seed,
+                              const uint64_t* row_streams, const int32_t* forced_tok, int32_t k, int32_t n_seq,
+                              const int32_t* seq_tokens, const int32_t* seq_lengths, const float* seq_bias, int32_t* choice_out,
+                              float* lp_out, int32_t* top_id_out, float* top_lp_out, float* proc_lp_out) {
+    if (!proc_lp_out) return fail(c, CW_ERR_INVALID, "test_sample_biased: null argument");
+    if (c->beam_K > 0) return fail(c, CW_ERR_STATE, "test_sample_biased: a beam search is open");
+    std::vector<int> tab;
+    CWCHK(c, seq_bias_table(c, n_seq, seq_tokens, seq_lengths, seq_bias, &tab, "test_sample_biased"));
+    const std::vector<int> keep = c->sb_host;
+    const int keep_n = c->sb_n;
+    const bool keep_score = c->score_tokens;
+    CWCHK(c, seq_bias_install(c, tab, n_seq));
+    c->score_tokens = true;
+    HIPCHK(c, hipMemset(c->d_lp_sum, 0, (size_t)c->Bm * 4));
+    HIPCHK(c, hipMemset(c->d_lp_cnt, 0, (size_t)c->Bm * 4));
+    const int r = cw_test_sample_top_logprobs(c, nb, logits, ids, t, n_prompt, min_new_tokens, max_length, temperature, seed, row_streams,
+                                              forced_tok, k, choice_out, lp_out, top_id_out, top_lp_out);
+    c->score_tokens = keep_score;
+    int r2 = CW_OK;
+    if (r == CW_OK) {
+        hipError_t e = hipMemcpy(proc_lp_out, c->d_lp_sum, (size_t)nb * 4, hipMemcpyDeviceToHost);
+        if (e != hipSuccess) r2 = fail(c, CW_ERR_HIP, "test_sample_biased: %s", hipGetErrorString(e));
+    }
+    drop_step_graphs(c);                                       // (cw_set_top_logprobs dropped them already)
+    CWCHK(c, seq_bias_install(c, keep, keep_n));
+    return r != CW_OK ? r : r2;
 }
 static int test_sample(cw_ctx* c, int32_t nb, const float* logits, const int32_t* ids, int32_t t, int32_t n_prompt,
                        int32_t min_new_tokens, int32_t max_length, int32_t* choice_out, const int32_t* forced_tok, float* lp_out,

@@ -58,7 +58,26 @@ struct SampleParams {
     void* top_part;            // [B][SAMPLE_NS][CW_TOP_LOGPROBS_MAX] 8-byte (value, id) pairs: the slices' winners, written by stage 1
     int* top_id;               // [B][ids_stride][CW_TOP_LOGPROBS_MAX]
     float* top_lp;             // [B][ids_stride][CW_TOP_LOGPROBS_MAX]
+    // optional (null: off): sequence_bias, the table of include/crisperwhisper.h: cw_set_sequence_bias in the layout below.  The
+    // kernels add the row's float32 bias to every logit they consume; tok_lp / top_lp stay raw.
+    const int* seq_bias;       // [SB_WORDS]
 };
+// Device table of cw_set_sequence_bias (32-bit words).  The host orders the entries by their LAST token (stable: for one last token
+// the length-1 entry first, then the longer ones in the caller's order -- the summation order of SequenceBiasLogitsProcessor), so
+// the entries of one token are adjacent and those of one vocabulary slice of the sampler's stage 1 are one range:
+//   [SB_SLICE + s], s = 0 .. 16   first entry whose last token lies in slice s (slice 16: the entry count)
+//   [SB_OFF + e],   e = 0 .. n    offset of entry e in the token words (its length = the difference to the next)
+//   [SB_VAL + e]                  its bias (f32 bits)
+//   [SB_LAST + e]                 its last token (ascending)
+//   [SB_TOK + k]                  the entries' tokens, concatenated
+#define SB_MAX_SEQ 256         /* CW_SEQUENCE_BIAS_MAX */
+#define SB_MAX_LEN 16          /* CW_SEQUENCE_BIAS_MAX_LEN */
+#define SB_SLICE 0
+#define SB_OFF 32
+#define SB_VAL (SB_OFF + SB_MAX_SEQ + 32)
+#define SB_LAST (SB_VAL + SB_MAX_SEQ)
+#define SB_TOK (SB_LAST + SB_MAX_SEQ)
+#define SB_WORDS (SB_TOK + SB_MAX_SEQ * SB_MAX_LEN)
 // beam search (elementwise.hip): per row the n_cand best processed log-probabilities of the next token
 // (log_softmax of the raw logits, then the same processors as the greedy path) ...
 // ... and the re-ordering of the per-row state after the host picked (parent row, token) for every row

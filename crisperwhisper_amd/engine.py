@@ -302,6 +302,22 @@ class Engine:
         self._chk(self.lib.cw_set_top_logprobs(self.ctx, int(k)))
         self._top_k = int(k)
 
+    def set_sequence_bias(self, table):
+        """Phrase boosting in the sampler kernels (``cw_set_sequence_bias``): ``table`` is a sequence of ``(token ids, bias)``
+        pairs -- at most 256 distinct sequences of 1 .. 16 ids, finite biases -- with the semantics of transformers'
+        SequenceBiasLogitsProcessor; None or an empty one switches it off.  Greedy and sampled decoding only."""
+        table = list(table) if table is not None else []
+        if not table:
+            self._chk(self.lib.cw_set_sequence_bias(self.ctx, 0, None, None, None))
+            return
+        toks = _i32([t for ids, _ in table for t in ids])
+        lens = _i32([len(ids) for ids, _ in table])
+        bias = np.ascontiguousarray([b for _, b in table], np.float32)
+        self._chk(self.lib.cw_set_sequence_bias(self.ctx, len(table), _ptr(toks), _ptr(lens), _ptr(bias)))
+
+    def clear_sequence_bias(self):
+        self.set_sequence_bias(None)
+
     def top_logprobs(self, nb: int):
         """(ids int32, logprobs float32), both [nb, max_target_positions, k], aligned with the last ``decode``'s sequences: the
         k best raw logits of the step that wrote each position, best first, ties to the lower id; -1 / NaN beyond the number
@@ -951,6 +967,41 @@ class Engine:
                                                        int(seed) & (2 ** 64 - 1), _ptr(rs), _ptr(fr), int(k), _ptr(out), _ptr(lp),
                                                        _ptr(top_id), _ptr(top_lp)))
         return out, lp, top_id, top_lp
+
+    def test_sample_biased(self, logits: np.ndarray, ids: np.ndarray, n_prompt: int, k: int, table=None, temperature: float = 0.0,
+                           seed: int = 0, row_streams=None, forced=None, min_new_tokens: int = 0,
+                           max_length: Optional[int] = None):
+        """``test_sample_top_logprobs`` under a ``set_sequence_bias`` table for this call only (cw_test_sample_biased; ``table``
+        None or empty: none): returns (choice [nb], logprob [nb], top ids [nb][k], top logprobs [nb][k], processed-score
+        log-probability term [nb]) of index t."""
+        lg = np.ascontiguousarray(logits, np.float32)
+        ids = _i32(ids)
+        nb, t = ids.shape
+        if lg.shape != (nb, self.spec.vocab_size):
+            raise ValueError(f"logits must be [{nb}][{self.spec.vocab_size}], got {lg.shape}")
+        if not 1 <= int(k) <= 8:
+            raise ValueError(f"k must be in 1 .. 8, got {k}")
+        rs = None if row_streams is None else np.ascontiguousarray(row_streams, dtype=np.uint64)
+        if rs is not None and rs.shape != (nb,):
+            raise ValueError(f"row_streams must hold one id per row ({nb}), got shape {rs.shape}")
+        fr = None if forced is None else _i32(forced)
+        if fr is not None and fr.shape != (nb,):
+            raise ValueError(f"forced must hold one token per row ({nb}), got shape {fr.shape}")
+        table = list(table) if table is not None else []
+        toks = _i32([t_ for s, _ in table for t_ in s]) if table else None
+        lens = _i32([len(s) for s, _ in table]) if table else None
+        bias = np.ascontiguousarray([b for _, b in table], np.float32) if table else None
+        out = np.zeros(nb, np.int32)
+        lp = np.zeros(nb, np.float32)
+        top_id = np.zeros((nb, int(k)), np.int32)
+        top_lp = np.zeros((nb, int(k)), np.float32)
+        proc = np.zeros(nb, np.float32)
+        self._chk(self.lib.cw_test_sample_biased(self.ctx, nb, _ptr(lg), _ptr(ids), t, int(n_prompt), int(min_new_tokens),
+                                                 int(max_length or self.spec.max_target_positions), float(temperature),
+                                                 int(seed) & (2 ** 64 - 1), _ptr(rs), _ptr(fr), int(k), len(table), _ptr(toks),
+                                                 _ptr(lens), _ptr(bias), _ptr(out), _ptr(lp), _ptr(top_id), _ptr(top_lp),
+                                                 _ptr(proc)))
+        return out, lp, top_id, top_lp, proc
 
     # ------------------------------------------------------------------ measurement
     def stage_times(self, reset: bool = False):

@@ -23,6 +23,8 @@ from .engine import Engine
 TIME_PRECISION = 0.02          # seconds per encoder frame (30 / 1500)
 INPUT_STRIDE = 2               # conv1.stride * conv2.stride
 TOP_LOGPROBS_MAX = 8           # CW_TOP_LOGPROBS_MAX: alternatives per token (generate(top_logprobs=k))
+SEQUENCE_BIAS_MAX = 256        # CW_SEQUENCE_BIAS_MAX: sequences per table (generate(sequence_bias=...))
+SEQUENCE_BIAS_MAX_LEN = 16     # CW_SEQUENCE_BIAS_MAX_LEN: tokens per sequence
 
 
 @dataclasses.dataclass
@@ -459,12 +461,57 @@ def stream_id(item_id: int, seek_frame: int, temperature_index: int) -> int:
     return (hi << 32) | (int(item_id) & 0xFFFFFFFF)
 
 
+def check_sequence_bias(sequence_bias, vocab_size: int):
+    """transformers' ``sequence_bias`` (the list form ``[[[ids...], bias], ...]`` or the dict form ``{(ids...): bias}``) as a list
+    of ``(ids tuple, float bias)`` in the order SequenceBiasLogitsProcessor sums them, or None for None.  Refuses with ValueError
+    what the processor's ``_validate_arguments`` refuses (an empty container, non-tuple keys, negative ids, ids <= 0 in the list
+    form, biases that are no floats) and what the engine cannot honour: empty sequences, ids >= ``vocab_size`` (transformers raises
+    at the first step), more than SEQUENCE_BIAS_MAX sequences or SEQUENCE_BIAS_MAX_LEN tokens, non-finite biases.  Duplicates in
+    the list form collapse as the processor's dict conversion does: the last bias wins, at the first one's place."""
+    if sequence_bias is None:
+        return None
+    sb = sequence_bias
+    if not isinstance(sb, (dict, list)) or len(sb) == 0:
+        raise ValueError(f"`sequence_bias` has to be a non-empty dictionary, or non-empty list of lists but is {sb!r}")
+
+    def is_id(t):
+        return isinstance(t, (int, np.integer)) and not isinstance(t, (bool, np.bool_))
+    if isinstance(sb, dict):
+        if any(not isinstance(k, tuple) for k in sb):
+            raise ValueError(f"`sequence_bias` has to be a dict with tuples as keys, but is {sb!r}")
+        if any(len(k) == 0 or any(not is_id(t) or t < 0 for t in k) for k in sb):
+            raise ValueError(f"each key in `sequence_bias` has to be a non-empty tuple of non-negative integers, but is {sb!r}")
+        table = dict(sb)
+    else:
+        for e in sb:
+            if (not isinstance(e, (list, tuple)) or len(e) != 2 or not isinstance(e[0], list) or len(e[0]) == 0
+                    or any(not is_id(t) or t <= 0 for t in e[0]) or not isinstance(e[1], float)):
+                raise ValueError("each element in `sequence_bias` has to be [non-empty list of positive integers, float], "
+                                 f"but one is {e!r}")
+        table = {tuple(int(t) for t in e[0]): e[1] for e in sb}
+    if any(not isinstance(b, float) for b in table.values()):
+        raise ValueError(f"`sequence_bias` has to hold floats as biases, but is {sb!r}")
+    if len(table) > SEQUENCE_BIAS_MAX:
+        raise ValueError(f"sequence_bias holds {len(table)} sequences; at most {SEQUENCE_BIAS_MAX} are implemented")
+    out = []
+    for k, b in table.items():
+        if len(k) > SEQUENCE_BIAS_MAX_LEN:
+            raise ValueError(f"sequence_bias: a sequence of {len(k)} tokens; at most {SEQUENCE_BIAS_MAX_LEN} are implemented")
+        bad = [int(t) for t in k if t >= vocab_size]
+        if bad:
+            raise ValueError(f"The model vocabulary size is {vocab_size}, but the following tokens were being biased: {bad}")
+        if not np.isfinite(b):
+            raise ValueError(f"sequence_bias: the bias of {k} is {b}; it has to be finite")
+        out.append((tuple(int(t) for t in k), float(b)))
+    return out
+
+
 def generate(engine: Engine, n_items: int, num_frames, *, language: Optional[str], task: Optional[str] = None,
              max_new_tokens: Optional[int] = None, min_new_tokens: Optional[int] = None,
              num_beams: Optional[int] = 1, stats: Optional[dict] = None, native: Optional[bool] = None,
              logprob_threshold: Optional[float] = None, no_speech_threshold: Optional[float] = None, prompt_ids=None,
              temperature=None, compression_ratio_threshold: Optional[float] = None, sampling_seed: int = 0, item_ids=None,
-             return_token_logprobs: bool = False, top_logprobs: int = 0):
+             return_token_logprobs: bool = False, top_logprobs: int = 0, sequence_bias=None):
     """Transcribe the ``n_items`` 30 s feature windows resident in the engine (items 0..n-1).
 
     Returns {"sequences": [B, Lmax] int64 (pad-right), "token_timestamps": list of float32 arrays,
@@ -500,7 +547,39 @@ def generate(engine: Engine, n_items: int, num_frames, *, language: Optional[str
     [n_tok][k] array per item aligned with ``token_timestamps``, the ids (int32) and log-probabilities (float32) of the k best raw
     logits of each token's step, best first, ties to the lower id (``cw_set_top_logprobs``): no suppress lists, no timestamp
     rule, no temperature, so the written token need not be among them; where it is, its value equals ``token_logprobs`` bit for
-    bit.  A rank beyond the number of finite logits holds -1 / NaN."""
+    bit.  A rank beyond the number of finite logits holds -1 / NaN.
+
+    ``sequence_bias`` (transformers' list or dict form, ``check_sequence_bias``; needs ``num_beams=1``): phrase boosting with the
+    semantics of SequenceBiasLogitsProcessor, applied inside the sampler kernels (``cw_set_sequence_bias``) in front of every other
+    logits processor, in every window and every fallback re-decode.  The prompt tokens take part in the prefix match.  The raw
+    outputs ("token_logprobs", "top_logprobs") are unchanged by it.  The table is cleared again when the call ends or raises."""
+    spec = engine.spec
+    table = check_sequence_bias(sequence_bias, spec.vocab_size)
+    if table is not None:
+        if num_beams is not None and int(num_beams) > 1:
+            raise ValueError("sequence_bias is implemented for greedy and sampled decoding only (beam search would add it to "
+                             "log_softmax(raw), which moves the normaliser): pass num_beams=1")
+        if not hasattr(engine, "set_sequence_bias"):
+            raise ValueError("this engine does not implement sequence_bias (cw_set_sequence_bias)")
+        # the call proper (_generate) checks its own arguments before it touches the engine; whatever happens there, the table
+        # does not outlive the call
+        engine.set_sequence_bias(table)
+    try:
+        return _generate(engine, n_items, num_frames, language=language, task=task, max_new_tokens=max_new_tokens,
+                         min_new_tokens=min_new_tokens, num_beams=num_beams, stats=stats, native=native,
+                         logprob_threshold=logprob_threshold, no_speech_threshold=no_speech_threshold, prompt_ids=prompt_ids,
+                         temperature=temperature, compression_ratio_threshold=compression_ratio_threshold,
+                         sampling_seed=sampling_seed, item_ids=item_ids, return_token_logprobs=return_token_logprobs,
+                         top_logprobs=top_logprobs)
+    finally:
+        if table is not None:
+            engine.set_sequence_bias(None)
+
+
+def _generate(engine: Engine, n_items: int, num_frames, *, language, task, max_new_tokens, min_new_tokens, num_beams, stats, native,
+              logprob_threshold, no_speech_threshold, prompt_ids, temperature, compression_ratio_threshold, sampling_seed, item_ids,
+              return_token_logprobs, top_logprobs):
+    """``generate`` proper: everything but the sequence_bias table, which ``generate`` sets around this call."""
     spec = engine.spec
     want_lp = bool(return_token_logprobs)
     if want_lp and not hasattr(engine, "set_token_logprobs"):

@@ -225,7 +225,8 @@ def _device_index(device) -> int:
 # dropped: a drop-in must either honour an argument or refuse it
 _GENERATE_KWARGS = ("language", "task", "max_new_tokens", "min_new_tokens", "num_beams", "length_penalty", "early_stopping",
                     "do_sample", "temperature", "num_return_sequences", "prompt_ids", "assistant_model",
-                    "logprob_threshold", "no_speech_threshold", "compression_ratio_threshold", "return_timestamps")
+                    "logprob_threshold", "no_speech_threshold", "compression_ratio_threshold", "return_timestamps",
+                    "sequence_bias")
 
 
 def _check_generate_kwargs(gk: Dict[str, Any], default_num_beams: Optional[int] = None, spec=None,
@@ -282,6 +283,15 @@ def _check_generate_kwargs(gk: Dict[str, Any], default_num_beams: Optional[int] 
         pids = generation.check_prompt_ids(spec, gk["prompt_ids"])
         n_init = len(generation.resolve_prompt(spec, gk.get("language"), gk.get("task"))[0])
         generation.prompted_max_length(spec, len(pids) + n_init, gk.get("max_new_tokens"))
+    if gk.get("sequence_bias") is not None:
+        if spec is None:
+            raise ValueError("generate_kwargs['sequence_bias'] can only be checked against a model: pass its ModelSpec")
+        generation.check_sequence_bias(gk["sequence_bias"], spec.vocab_size)
+        if beams not in (None, 1):
+            raise ValueError(f"sequence_bias is implemented for greedy and sampled decoding only and this call decodes with {beams} "
+                             "beams" + ("" if gk.get("num_beams") is not None else " (the pipeline default)") +
+                             ": pass generate_kwargs={'num_beams': 1, ...} -- beam search adds the bias to log_softmax(raw), "
+                             "and that path is not reproduced")
     if gk.get("return_timestamps") not in (None, True, "word"):
         raise ValueError("generate_kwargs['return_timestamps'] must be left to the pipeline argument of the same name")
     if gk.get("no_speech_threshold") is not None and gk.get("logprob_threshold") is None:
@@ -545,7 +555,8 @@ class CrisperWhisperPipeline:
                 no_speech_threshold=gk.get("no_speech_threshold"), prompt_ids=gk.get("prompt_ids"),
                 temperature=gk.get("temperature"), compression_ratio_threshold=gk.get("compression_ratio_threshold"),
                 sampling_seed=seed or 0, item_ids=idxs, **({"return_token_logprobs": True} if scores else {}),
-                **({"top_logprobs": top_k} if top_k else {}))
+                **({"top_logprobs": top_k} if top_k else {}),
+                **({"sequence_bias": gk["sequence_bias"]} if gk.get("sequence_bias") is not None else {}))
             if "fallback" in st:
                 fallback_trace.extend(st["fallback"])
             rs = []
@@ -611,6 +622,27 @@ class CrisperWhisperPipeline:
         return {"text": text, "chunks": words}
 
 
+    def phrase_bias(self, phrases) -> list:
+        """A ``sequence_bias`` list for ``generate_kwargs`` from ``{phrase: bias}``: for every phrase its token sequence as the
+        tokenizer encodes it with and without a leading space (a word inside a sentence and one at the start of a segment are
+        different tokens), each with the phrase's bias.  Needs a tokenizer with ``encode``, like a text transcript of ``align``.
+        Nothing is applied implicitly: pass the result as ``generate_kwargs={"num_beams": 1, "sequence_bias": ...}``."""
+        if not isinstance(phrases, dict) or not phrases:
+            raise ValueError("phrase_bias takes a non-empty dict {phrase: bias}")
+        table = {}
+        for phrase, bias in phrases.items():
+            if not isinstance(phrase, str) or not phrase.strip():
+                raise ValueError(f"phrase_bias: a phrase is a non-empty str, got {phrase!r}")
+            if isinstance(bias, bool) or not isinstance(bias, (int, float)) or not np.isfinite(bias):
+                raise ValueError(f"phrase_bias: the bias of {phrase!r} has to be a finite number, got {bias!r}")
+            for text in (phrase.strip(), " " + phrase.strip()):
+                ids = tuple(int(t) for t in self._transcript_ids(text))
+                if ids:
+                    table[ids] = float(bias)
+        out = [[list(ids), b] for ids, b in table.items()]
+        generation.check_sequence_bias(out, self.bundle.spec.vocab_size)
+        return out
+
     # -- forced alignment of known transcripts ------------------------------------------------------
     def _transcript_ids(self, transcript) -> np.ndarray:
         if isinstance(transcript, str):
@@ -623,6 +655,9 @@ class CrisperWhisperPipeline:
 
     def _forced_kwargs(self, who, language, task, kwargs):
         gk = dict(kwargs.pop("generate_kwargs", None) or {})
+        if "sequence_bias" in kwargs or "sequence_bias" in gk:
+            raise ValueError(f"sequence_bias is not accepted by {who}: it reports the model's raw scores of a given transcript, "
+                             "nothing is chosen that a bias could steer")
         if "prompt_ids" in kwargs or "prompt_ids" in gk:
             raise ValueError(f"prompt_ids is not accepted by {who}: the decoder input is the init tokens and the transcript")
         if kwargs:

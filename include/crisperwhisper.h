@@ -218,6 +218,28 @@ int32_t cw_get_transcribe_token_logprobs(cw_ctx* ctx, float* out /* [B][cap] */,
 int32_t cw_set_top_logprobs(cw_ctx* ctx, int32_t k);
 int32_t cw_get_top_logprobs(cw_ctx* ctx, int32_t* ids_out, float* lp_out /* [nb][max_target_positions][k] */, int32_t nb);
 int32_t cw_get_transcribe_top_logprobs(cw_ctx* ctx, int32_t* ids_out, float* lp_out /* [B][cap][k] */, int32_t B, int32_t cap);
+/* sequence_bias: steer the free-running decode towards (or away from) known token sequences -- the contract of transformers'
+ * SequenceBiasLogitsProcessor.  The table is a set of n_seq distinct token sequences (`tokens` = their concatenation, lengths[i]
+ * tokens each, 1 .. CW_SEQUENCE_BIAS_MAX_LEN) with one finite bias each.  At the step that writes sequence index t (ids[0 .. t-1]
+ * exist: decoder prompt, prompt_ids prefix and what was generated) a sequence of length L applies to a row iff L == 1, or L <= t
+ * and ids[t-L+1 .. t-1] equals its first L-1 tokens; a sequence with L == t + 1 is skipped although its prefix would fit, as
+ * transformers skips it.  The row's bias of token v is the float32 sum of: the length-1 entry of v, then the applying longer
+ * sequences ending in v in table order.  The sampler kernels consume fl32(logits[v] + bias[v]) wherever they consumed logits[v]:
+ * suppress lists and timestamp grammar (a suppressed or -inf token stays -inf), the log-sum-exp timestamp rule, the arg-max,
+ * score / T + Gumbel under sampling, and the processed-score log-probability behind cw_get_avg_logprobs.  What reports RAW scores
+ * does not move: cw_get_token_logprobs, cw_get_top_logprobs, language detection, the no-speech probability.  A forced token is
+ * still written; only the un-forced choice moves.  The match and the add run inside the two sampler kernels: no launch, no
+ * forward and no host round trip per step is added.
+ * n_seq == 0 switches it off (the pointers may then be NULL).  Refused before any state changes: CW_ERR_INVALID for a null
+ * pointer, n_seq outside 0 .. CW_SEQUENCE_BIAS_MAX, a length outside 1 .. CW_SEQUENCE_BIAS_MAX_LEN, an id outside
+ * 0 .. vocab_size-1, a non-finite bias, a duplicate sequence; CW_ERR_STATE while a beam search is open.  Beam search does not
+ * carry the bias (there it would be added to log_softmax(raw), which moves the normaliser): cw_beam_begin returns CW_ERR_STATE
+ * while a table is set.  Only switching between off and on drops the captured decode steps; new contents are one device copy.
+ * cw_decode, cw_decode_rows, cw_transcribe and cw_transcribe_prompted all honour it.                                        */
+#define CW_SEQUENCE_BIAS_MAX 256
+#define CW_SEQUENCE_BIAS_MAX_LEN 16
+int32_t cw_set_sequence_bias(cw_ctx* ctx, int32_t n_seq, const int32_t* tokens, const int32_t* lengths /* [n_seq] */,
+                             const float* bias /* [n_seq] */);
 int32_t cw_get_logits(cw_ctx* ctx, float* out /* [nb][vocab] */, int32_t nb);       /* last sampled step */
 int32_t cw_set_logits_capture(cw_ctx* ctx, float* host_buf, int32_t max_steps);    /* [steps][nb][vocab] */
 int32_t cw_get_alignment(cw_ctx* ctx, float* out /* [nb][n_align][L][1500] */, int32_t nb, int32_t L);
@@ -629,6 +651,14 @@ int32_t cw_test_sample_top_logprobs(cw_ctx* ctx, int32_t nb, const float* logits
                                     int32_t min_new_tokens, int32_t max_length, float temperature, uint64_t seed,
                                     const uint64_t* row_streams, const int32_t* forced_tok, int32_t k, int32_t* choice_out,
                                     float* lp_out, int32_t* top_id_out, float* top_lp_out);
+/* ... and with a cw_set_sequence_bias table for this call only (n_seq == 0: none), the context's own table put back
+ * afterwards.  proc_lp_out [nb] = the processed-score log-probability term of the token written at t, i.e. what the step adds to
+ * the sum behind cw_get_avg_logprobs (0 where it adds nothing).                                                              */
+int32_t cw_test_sample_biased(cw_ctx* ctx, int32_t nb, const float* logits, const int32_t* ids, int32_t t, int32_t n_prompt,
+                              int32_t min_new_tokens, int32_t max_length, float temperature, uint64_t seed,
+                              const uint64_t* row_streams, const int32_t* forced_tok, int32_t k, int32_t n_seq,
+                              const int32_t* seq_tokens, const int32_t* seq_lengths, const float* seq_bias, int32_t* choice_out,
+                              float* lp_out, int32_t* top_id_out, float* top_lp_out, float* proc_lp_out);
 
 /* ---- measurement -------------------------------------------------------------------------------------- */
 #define CW_STAGE_MEL 0

@@ -11,11 +11,15 @@ geometry: large-v3 shape, aligned synthetic weights, --rows x 30 s clips residen
                     of every row and stores log_softmax(raw)[token]): step_*_logprobs_ms, off and on in the same build
   --top-logprobs K [K ...]  (with --token-logprobs) ... and once more per K with cw_set_top_logprobs(K) on top (the sampler also
                     selects the K best raw logits of every row): step_*_top<K>_ms, all in the same build and process
+  --sequence-bias N [N ...]  ... and once more per N with a cw_set_sequence_bias table of N entries (half single tokens, half
+                    two-token sequences) whose last tokens are spread over the 16 vocabulary slices of the sampler, and once with
+                    all N in one slice: step_*_bias<N>_ms / step_*_bias<N>_one_slice_ms, against the table-free figure of the same
+                    process
   --no-fallback-round  leave the fallback round out
 
 Best of --reps after one warm-up, wall time around the call with the stream synchronised.
 usage: python tools/sample_step_bench.py [--dtype bf16] [--rows 8] [--tokens 128] [--temperature 0.6] [--redo 2] [--reps 5]
-                                         [--token-logprobs [--top-logprobs 5 8]] [--no-fallback-round]"""
+                                         [--token-logprobs [--top-logprobs 5 8]] [--sequence-bias 8 256] [--no-fallback-round]"""
 import argparse, json, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
@@ -32,6 +36,7 @@ def main():
     ap.add_argument("--redo", type=int, default=2); ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--token-logprobs", action="store_true"); ap.add_argument("--no-fallback-round", action="store_true")
     ap.add_argument("--top-logprobs", type=int, nargs="+", default=[], metavar="K")
+    ap.add_argument("--sequence-bias", type=int, nargs="+", default=[], metavar="N")
     a = ap.parse_args()
     if a.top_logprobs and not a.token_logprobs:
         ap.error("--top-logprobs needs --token-logprobs (cw_set_top_logprobs shares its normaliser)")
@@ -62,6 +67,19 @@ def main():
             out[f"decode_{name}{tag}_wall_ms"] = ms
     eng.set_sampling(0.0)
     eng.set_token_logprobs(False)
+    V = spec.vocab_size
+    per = ((((V + 3) // 4) + 15) // 16) * 4                          # columns per sampler slice
+    for n in a.sequence_bias:
+        for tag, last in ((f"_bias{n}", lambda i: (i * V) // n + 5), (f"_bias{n}_one_slice", lambda i: 3 * per + i)):
+            table = [((last(i),) if i % 2 == 0 else (int(v.transcribe), last(i)), 0.25 + (i % 5)) for i in range(n)]
+            eng.set_sequence_bias(table)
+            for name, temp in (("greedy", 0.0), ("sampling", a.temperature)):
+                eng.set_sampling(temp, 1, streams)
+                ms, split = timed(eng, steps, a.reps)
+                out[f"step_{name}{tag}_ms"] = round(split["decode"] / T, 4)
+                out[f"decode_{name}{tag}_wall_ms"] = ms
+    eng.set_sampling(0.0)
+    eng.set_sequence_bias(None)
     if a.no_fallback_round:
         print(json.dumps(out))
         eng.close()
