@@ -15,6 +15,7 @@ LIB_PATH = os.environ.get("CW_LIB_PATH") or os.path.join(_HERE, "libcrisperwhisp
 CW_DTYPE_F32, CW_DTYPE_BF16, CW_DTYPE_F16 = 0, 1, 2
 N_SAMPLES, N_FRAMES, N_CTX = 480000, 3000, 1500
 STAGES = ("mel", "encoder", "cross_kv", "decode", "timestamps")
+ALIGN_HEADS_MAX_BYTES = 8 << 30   # CW_ALIGN_HEADS_MAX_BYTES: attention rows one cw_align_heads call may capture
 
 
 class NativeLibraryError(RuntimeError):
@@ -124,6 +125,9 @@ _SIGS = {
     "cw_transcribe_prompted": (_I, [_P, _I, _P, C.POINTER(TranscribeCfg), _P, _I, _P, _P, _P, _I, _P]),
     "cw_align_tokens": (_I, [_P, _I, _P, _P, _I, _P, _I, _P]),
     "cw_align_prefill_runs": (_I, [_P]),
+    "cw_align_heads": (_I, [_P, _I, _P, _P, _I, _P, _I, _I, _P, _P, _P, _P, _P, _I, _P]),
+    "cw_align_heads_times": (_I, [_P, _P]),
+    "cw_test_align_similarity": (_I, [_P, _P, _I, _I, _I, _I, _P, _P, _P, _I, _P]),
     "cw_score_tokens": (_I, [_P, _I, _I, _P, _I, _P, _I, _P, _P, _P]),
     "cw_align_score_tokens": (_I, [_P, _I, _P, _P, _I, _P, _I, _P, _P, _P, _P]),
     "cw_score_prefill_runs": (_I, [_P]),

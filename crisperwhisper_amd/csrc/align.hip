@@ -9,6 +9,7 @@
 //                        (:89-115) that also emits, per token row, the first frame of its run (= jump
 //                        time / 0.02 s, :368-369)
 //   pauses_kernel        REF/utils.py:8-26: per-boundary pause redistribution (boundaries independent)
+#include <limits.h>
 #include <stdlib.h>
 #include "common.h"
 #include "kernels.h"
@@ -288,6 +289,63 @@ __global__ void pauses_kernel(const double* __restrict__ start_in, const double*
         if (pause > 0) s = s - (pause > thr ? thr / 2 : pause / 2);
     }
     start_out[i] = s; end_out[i] = e;
+}
+
+// Similarity of every recorded (normalised) attention row to its reference interval: the cosine between the row a and the
+// target g of the interval [s, e] seconds -- 1 on frames f0 = floor(s / 0.02) .. f1 - 1 (f1 = max(f0 + 1, ceil(e / 0.02))), a
+// linear ramp 1 - k / 5 on the k-th frame outside either end (k = 1 .. 4), 0 elsewhere -- over frames 0 .. n_cols[b] - 1, with
+// a counted as 0 outside [f0 - clip, f1 + clip) when clip >= 0.  NaN when the interval is not finite or either norm is 0.
+// One wave per row (4 rows per block).  Lane l owns the float4 chunks l, l + 64, ...: the three sums of a chunk are formed as
+// (p0 + p1) + (p2 + p3) and added to the lane's running sums in chunk order, then wave_sum's six fixed steps; nothing depends
+// on timing.  The frame indices are computed in double (one division per row), so they equal the float64 definition's.
+// w [B][Ha][rows_cap][S] (S % 4 == 0, 16-byte aligned rows), token rows row0 .. row0 + N - 1; ref_* [B][N]; out [Ha][B][N].
+#define SIM_WAVES 4
+__global__ __launch_bounds__(64 * SIM_WAVES) void align_similarity_kernel(
+    const float* __restrict__ w, int B, int Ha, int rows_cap, int S, int row0, int N, const int* __restrict__ n_cols,
+    const float* __restrict__ ref_begin, const float* __restrict__ ref_end, int clip, float* __restrict__ out) {
+    const int lane = threadIdx.x & 63;
+    const long long r = (long long)blockIdx.x * SIM_WAVES + (threadIdx.x >> 6);
+    if (r >= (long long)B * Ha * N) return;                       // uniform per wave
+    const int t = (int)(r % N), a = (int)((r / N) % Ha), b = (int)(r / ((long long)N * Ha));
+    float* dst = out + ((size_t)a * B + b) * N + t;
+    const float s = ref_begin[(size_t)b * N + t], e = ref_end[(size_t)b * N + t];
+    const int M = min(n_cols[b], S);
+    // |s|, |e| < 2^31 frames keeps the conversions below defined; anything beyond is no interval of a 30 s window
+    if (!(fabsf(s) < 1e7f) || !(fabsf(e) < 1e7f) || M <= 0) { if (lane == 0) *dst = NAN; return; }
+    const int f0 = (int)floor((double)s / 0.02);
+    const int f1 = max(f0 + 1, (int)ceil((double)e / 0.02));
+    const int cl = min(clip, 1 << 20);                            // (keeps f0 - clip / f1 + clip inside int)
+    const int c0 = clip >= 0 ? f0 - cl : INT_MIN, c1 = clip >= 0 ? f1 + cl : INT_MAX;
+    const float4* row = (const float4*)(w + (((size_t)b * Ha + a) * rows_cap + row0 + t) * S);
+    float ag = 0.f, aa = 0.f, gg = 0.f;
+    for (int c = lane; 4 * c < M; c += 64) {
+        const float4 v4 = row[c];
+        const float v[4] = {v4.x, v4.y, v4.z, v4.w};
+        float pag[4], paa[4], pgg[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const int j = 4 * c + k;
+            const int d = j < f0 ? f0 - j : (j >= f1 ? j - f1 + 1 : 0);      // frames outside the interval
+            const float g = (j < M && d < 5) ? (float)(5 - d) / 5.f : 0.f;   // one rounding
+            const float x = (j < M && j >= c0 && j < c1) ? v[k] : 0.f;
+            pag[k] = x * g; paa[k] = x * x; pgg[k] = g * g;
+        }
+        ag += (pag[0] + pag[1]) + (pag[2] + pag[3]);
+        aa += (paa[0] + paa[1]) + (paa[2] + paa[3]);
+        gg += (pgg[0] + pgg[1]) + (pgg[2] + pgg[3]);
+    }
+    ag = wave_sum(ag); aa = wave_sum(aa); gg = wave_sum(gg);
+    if (lane == 0) *dst = (aa > 0.f && gg > 0.f) ? ag / (sqrtf(aa) * sqrtf(gg)) : NAN;
+}
+
+int cw_launch_align_similarity(const float* w, int B, int Ha, int rows_cap, int S, int row0, int N, const int* n_cols,
+                               const float* ref_begin, const float* ref_end, int clip, float* out, hipStream_t st) {
+    if (B < 1 || Ha < 1 || N < 1 || S < 4 || S % 4 || row0 < 0 || row0 + N > rows_cap) return CW_ERR_INVALID;
+    const long long rows = (long long)B * Ha * N;
+    if ((rows + SIM_WAVES - 1) / SIM_WAVES > 0x7fffffffLL) return CW_ERR_INVALID;
+    hipLaunchKernelGGL(align_similarity_kernel, dim3((unsigned)((rows + SIM_WAVES - 1) / SIM_WAVES)), dim3(64 * SIM_WAVES), 0, st,
+                       w, B, Ha, rows_cap, S, row0, N, n_cols, ref_begin, ref_end, clip, out);
+    return CW_OK;
 }
 
 int cw_launch_align_stats(const float* w, int B, int Ha, int rows_cap, int S, int row0, int N, const int* n_cols,

@@ -1,6 +1,7 @@
 // Engine + C ABI (include/crisperwhisper.h): owns device memory, the HIP stream, the weights and the
 // per-stage orchestration of the CrisperWhisper hot path on one MI355X.  No CPU fallbacks: every entry
 // point either runs the HIP kernels or returns an error.
+#include <chrono>
 #include <hip/hip_runtime.h>
 #include <stdarg.h>
 #include <stdlib.h>
@@ -171,6 +172,7 @@ struct cw_ctx {
     unsigned int* d_samp = nullptr;           // [4 + 2 * Bm] temperature bits, seed, per-row stream ids (cw_set_sampling); zero = greedy
     std::vector<unsigned int> samp_host;      // what d_samp holds
     float* d_align = nullptr;
+    int align_rows = 0;                   // rows per (item, slot) of d_align / d_align_ml: max_target_positions (cw_align_heads: its capture's)
     float *d_part_o = nullptr, *d_part_ml = nullptr, *d_align_ml = nullptr;   // split cross-attention partials
     bool align_unnormalized = false;
     int* h_nunf = nullptr;  // pinned
@@ -219,6 +221,7 @@ struct cw_ctx {
     // per-position loop (A/B).  Work buffers for rows x positions, grown on demand and freed by cw_destroy.
     bool prompt_prefill = true;
     bool align_prefill = true;         // cw_align_tokens: the teacher-forced forward as one prefill ("align_prefill" = 0: the loop)
+    float align_heads_ms[5] = {0.f, 0.f, 0.f, 0.f, 0.f};   // last cw_align_heads: forward, normalise, similarity, timestamps, similarity kernel alone (cw_align_heads_times)
     int align_prefill_runs = 0;        // cw_align_tokens calls whose forward ran as the prefill (cw_align_prefill_runs)
     int pf_prefix = 0;                 // prompt_ids in front of the init tokens of the coming decoder inputs ("prompt_prefix")
     size_t pf_rows = 0;
@@ -654,6 +657,7 @@ static int create_impl(cw_ctx* c) {
         HIPCHK(c, hipMemcpy(c->d_align_slot, slot.data(), slot.size() * 4, hipMemcpyHostToDevice));
     }
     const int Ha = d.n_align > 0 ? d.n_align : 1;
+    c->align_rows = TGT;
     CWCHK(c, dmalloc(c, &c->d_align, (size_t)Bm * Ha * TGT * CW_N_CTX * 4));
     CWCHK(c, dmalloc(c, &c->d_part_o, (size_t)ATT_NS * Bm * D * 4));
     CWCHK(c, dmalloc(c, &c->d_part_ml, (size_t)Bm * H * ATT_NS * 2 * 4));
@@ -1178,7 +1182,7 @@ static DecLayerParams dec_layer_params(cw_ctx* c, int l, int nb, const float* xi
     dp.bo = L.bo; dp.x1 = xalt;
     dp.K = L.ck; dp.V = L.cv; dp.n_keys = CW_N_CTX; dp.part_o = c->d_part_o; dp.part_ml = c->d_part_ml;
     dp.align_out = c->d.n_align > 0 ? c->d_align : nullptr; dp.align_ml = c->d_align_ml;
-    dp.align_slot = c->d_align_slot + (size_t)l * H; dp.pos = c->d_pos; dp.n_align = c->d.n_align; dp.align_rows = TGT;
+    dp.align_slot = c->d_align_slot + (size_t)l * H; dp.pos = c->d_pos; dp.n_align = c->d.n_align; dp.align_rows = c->align_rows;
     dp.qw = L.q_wsum; dp.qbias = L.bq_c;
     dp.gq = c->d_gq; dp.gps = c->d_gps; dp.epoch = c->d_epoch; dp.layer = l; dp.err = c->d_err;
     dp.Mb = nb; dp.D = D; dp.H = H;
@@ -1349,7 +1353,7 @@ static int decode_step(cw_ctx* c, int nb, bool want_logits) {
             // cross-attention; the kernel finishes q_c = rstd(x1) (qa + qb - mean(x1) W'q_c 1) + b'q_c
             CrossSplitParams p{nullptr, L.ck, L.cv, CW_N_CTX, c->d_part_o, c->d_part_ml,
                                c->d.n_align > 0 ? c->d_align : nullptr, c->d_align_ml, c->d_align_slot + (size_t)l * H,
-                               c->d_pos, c->d.n_align, TGT, nb, H};
+                               c->d_pos, c->d.n_align, c->align_rows, nb, H};
             p.kv_div = c->beam_K > 0 ? c->beam_K : 1;
             p.qa = c->d_qa; p.qb = c->d_qb; p.qw = L.q_wsum; p.qbias = L.bq_c;
             p.pstats = c->d_pstats; p.n_pstats = (TD + nt3 - 1) / nt3;
@@ -1454,7 +1458,7 @@ static int decode_step(cw_ctx* c, int nb, bool want_logits) {
         if (xfull) {
             CrossSplitParams p{c->dq, L.ck, L.cv, CW_N_CTX, c->d_part_o, c->d_part_ml,
                                c->d.n_align > 0 ? c->d_align : nullptr, c->d_align_ml, c->d_align_slot + (size_t)l * H,
-                               c->d_pos, c->d.n_align, TGT, nb, H};
+                               c->d_pos, c->d.n_align, c->align_rows, nb, H};
             p.kv_div = 1; p.a_frag = c->d_xfrag;
             if (sk_ok) {   // W'q_c (x - c) over K slices -> planes; the attention blocks apply rstd (sum - mean W'q_c 1) + b'q_c
                 SkinnyParams sp;
@@ -1483,7 +1487,7 @@ static int decode_step(cw_ctx* c, int nb, bool want_logits) {
             // keys split over ATT_NS blocks per (row, head); the out-projection GEMV combines the partials
             CrossSplitParams p{c->dq, L.ck, L.cv, CW_N_CTX, c->d_part_o, c->d_part_ml,
                                c->d.n_align > 0 ? c->d_align : nullptr, c->d_align_ml, c->d_align_slot + (size_t)l * H,
-                               c->d_pos, c->d.n_align, TGT, nb, H};
+                               c->d_pos, c->d.n_align, c->align_rows, nb, H};
             p.kv_div = c->beam_K > 0 ? c->beam_K : 1;
             if (c->kv8) {
                 p.K = L.ck8; p.V = L.cv8; p.kv_scale = L.kvs;
@@ -1498,7 +1502,7 @@ static int decode_step(cw_ctx* c, int nb, bool want_logits) {
         } else {
             DecAttnParams p = dec_attn(c->dq, L.ck, L.cv, CW_N_CTX, CW_N_CTX, c->d_pos, c->dattn, nb, H);
             p.align_out = c->d.n_align > 0 ? c->d_align : nullptr; p.align_slot = c->d_align_slot + (size_t)l * H;
-            p.n_align = c->d.n_align; p.align_rows = TGT;
+            p.n_align = c->d.n_align; p.align_rows = c->align_rows;
             p.kv_div = c->beam_K > 0 ? c->beam_K : 1;
             STG(DST_CROSS_ATTN, KD(c, cw_launch_attn_decode, c->bf16, p, c->st));
             EpiParams ep = epi0(); ep.outf = c->dx; ep.resid = c->dx; ep.bias = L.bo_c; ep.ldo = D;
@@ -1695,7 +1699,7 @@ static int run_prefill(cw_ctx* c, int rows, int n_prompt, int kv_div, bool align
         PrefillAlign al;
         memset(&al, 0, sizeof(al));
         if (align && std::find(c->align_layers.begin(), c->align_layers.end(), l) != c->align_layers.end()) {
-            al.out = c->d_align; al.ml = c->d_align_ml; al.slot = c->d_align_slot + (size_t)l * H; al.n_align = c->d.n_align; al.rows = TGT;
+            al.out = c->d_align; al.ml = c->d_align_ml; al.slot = c->d_align_slot + (size_t)l * H; al.n_align = c->d.n_align; al.rows = c->align_rows;
         }
         CWCHK(c, KD(c, cw_launch_prefill_attn_align, c->pf_q, L.ck, L.cv, c->pf_o, rows, n_pos, H, CW_N_CTX, CW_N_CTX, 0, kv_div, al, c->st));
         if (align && !full && l + 1 == NL) break;
@@ -2145,7 +2149,7 @@ int32_t cw_set_logits_capture(cw_ctx* c, float* host_buf, int32_t max_steps) {
 
 static int normalize_alignment(cw_ctx* c) {
     if (!c->align_unnormalized) return CW_OK;
-    CWCHK(c, KD(c, cw_launch_align_normalize, c->d_align, c->d_align_ml, c->last_nb, c->d.n_align, c->d.max_target_positions,
+    CWCHK(c, KD(c, cw_launch_align_normalize, c->d_align, c->d_align_ml, c->last_nb, c->d.n_align, c->align_rows,
                                        c->last_L, CW_N_CTX, c->st));
     c->align_unnormalized = false;
     return CW_OK;
@@ -2319,39 +2323,40 @@ int32_t cw_token_timestamps(cw_ctx* c, int32_t nb, int32_t L, int32_t n_prompt, 
     return token_timestamps(c, nullptr, nb, L, n_prompt, num_frames, ts_out);
 }
 
-// w: alignment rows of item 0 of the nb items in the [B][n_align][TGT][S] layout (null: the retained rows)
-static int token_timestamps(cw_ctx* c, const float* w, int32_t nb, int32_t L, int32_t n_prompt, const int32_t* num_frames, float* ts_out) {
-    const int Ha = c->d.n_align, TGT = c->d.max_target_positions, S = CW_N_CTX;
-    for (size_t i = 0; i < (size_t)nb * (L + 1); ++i) ts_out[i] = 0.f;
-    const int N = L - n_prompt;
-    if (N <= 0) return CW_OK;                     // generation_whisper.py:336-338
-    // Columns reaching the DTW, with HF's exact slicing semantics (:318-323 + :354): python-style
-    // `[..., : nf // 2]`, applied twice when every item has the same num_frames, once otherwise.
-    // nf <= 0 happens when the seek loop ran past the valid audio; it may leave zero columns.
-    std::vector<int> ncols(nb);
+// Columns reaching the DTW, with HF's exact slicing semantics (:318-323 + :354): python-style
+// `[..., : nf // 2]`, applied twice when every item has the same num_frames, once otherwise.
+// nf <= 0 happens when the seek loop ran past the valid audio; it may leave zero columns.
+static void timestamp_ncols(int nb, const int32_t* num_frames, std::vector<int>& ncols) {
+    const int S = CW_N_CTX;
+    ncols.resize(nb);
     bool uniform = true;
     for (int b = 1; b < nb; ++b) uniform = uniform && (num_frames[b] == num_frames[0]);
     auto floordiv2 = [](int v) { return (v >= 0) ? v / 2 : -((-v + 1) / 2); };
     auto slice_len = [](int n, int h) { return h >= 0 ? (h < n ? h : n) : (n + h > 0 ? n + h : 0); };
-    bool any_cols = false;
     for (int b = 0; b < nb; ++b) {
         int h = floordiv2(num_frames[b]);
         int n1 = slice_len(S, h);
         ncols[b] = uniform ? slice_len(n1, h) : n1;
-        any_cols = any_cols || ncols[b] > 0;
     }
-    HIPCHK(c, hipMemcpyAsync(c->d_ncols, ncols.data(), nb * 4, hipMemcpyHostToDevice, c->st));
+}
+
+// stats -> filter -> DTW of nseq sequences (nseq <= max_batch) of N token rows each: w [nseq][Ha][rows_cap][S], token rows
+// row0 .. row0 + N - 1, ncols[q] frames.  w null: the retained rows.  fc [nseq][N]: first frame of every token's run.
+static int timestamp_first_cols(cw_ctx* c, const float* w, int nseq, int Ha, int rows_cap, int row0, int N, const int* ncols,
+                                std::vector<int>& fc) {
+    const int S = CW_N_CTX;
+    HIPCHK(c, hipMemcpyAsync(c->d_ncols, ncols, nseq * 4, hipMemcpyHostToDevice, c->st));
     HIPCHK(c, hipStreamSynchronize(c->st));
     StageTimer tm(c, CW_STAGE_TIMESTAMPS);
     CWCHK(c, normalize_alignment(c));
     if (!w) w = c->align_cur ? c->align_cur : c->d_align;
-    CWCHK(c, run_alignment(c, w, nb, Ha, TGT, S, n_prompt, N, c->d_ncols, c->d.median_filter_width, c->d_mean, c->d_std, c->d_mat));
+    CWCHK(c, run_alignment(c, w, nseq, Ha, rows_cap, S, row0, N, c->d_ncols, c->d.median_filter_width, c->d_mean, c->d_std, c->d_mat));
     {   // workspace of the wave-local DTW, grown on demand (diagonal-major copy of the cost matrices)
-        const size_t need = cw_dtw_skew_floats(nb, N, S);
+        const size_t need = cw_dtw_skew_floats(nseq, N, S);
         if (need > c->skew_cap) {
             // grown at most a few times: sized for the worst case of this batch size (N = max_target_positions) and the
             // previous buffer is released, so a token count that creeps upwards cannot pile up dead workspaces
-            const size_t want = cw_dtw_skew_floats(nb, c->d.max_target_positions, S) > need ? cw_dtw_skew_floats(nb, c->d.max_target_positions, S) : need;
+            const size_t want = cw_dtw_skew_floats(nseq, c->d.max_target_positions, S) > need ? cw_dtw_skew_floats(nseq, c->d.max_target_positions, S) : need;
             if (c->d_skew) {
                 HIPCHK(c, hipStreamSynchronize(c->st));
                 for (auto it = c->allocs.begin(); it != c->allocs.end(); ++it)
@@ -2363,11 +2368,23 @@ static int token_timestamps(cw_ctx* c, const float* w, int32_t nb, int32_t L, in
             c->skew_cap = want;
         }
     }
-    CWCHK(c, cw_launch_dtw(c->d_mat, nb, N, S, c->d_ncols, c->d_trace, c->d_first_col, c->dtw_block ? c->d_path_text : nullptr, c->dtw_block ? c->d_path_time : nullptr, c->d_path_len, c->st, c->dtw_block ? nullptr : c->d_skew));
+    CWCHK(c, cw_launch_dtw(c->d_mat, nseq, N, S, c->d_ncols, c->d_trace, c->d_first_col, c->dtw_block ? c->d_path_text : nullptr, c->dtw_block ? c->d_path_time : nullptr, c->d_path_len, c->st, c->dtw_block ? nullptr : c->d_skew));
     KCHK(c);
     tm.stop();
-    std::vector<int> fc((size_t)nb * N);
+    fc.resize((size_t)nseq * N);
     HIPCHK(c, hipMemcpy(fc.data(), c->d_first_col, fc.size() * 4, hipMemcpyDeviceToHost));
+    return CW_OK;
+}
+
+// w: alignment rows of item 0 of the nb items in the [B][n_align][TGT][S] layout (null: the retained rows)
+static int token_timestamps(cw_ctx* c, const float* w, int32_t nb, int32_t L, int32_t n_prompt, const int32_t* num_frames, float* ts_out) {
+    const int Ha = c->d.n_align, TGT = c->d.max_target_positions;
+    for (size_t i = 0; i < (size_t)nb * (L + 1); ++i) ts_out[i] = 0.f;
+    const int N = L - n_prompt;
+    if (N <= 0) return CW_OK;                     // generation_whisper.py:336-338
+    std::vector<int> ncols, fc;
+    timestamp_ncols(nb, num_frames, ncols);
+    CWCHK(c, timestamp_first_cols(c, w, nb, Ha, TGT, n_prompt, N, ncols.data(), fc));
     for (int b = 0; b < nb; ++b) {
         float* ts = ts_out + (size_t)b * (L + 1);
         for (int i = 0; i < N; ++i) {
@@ -2638,6 +2655,216 @@ int32_t cw_align_tokens(cw_ctx* c, int32_t nb, const int32_t* num_frames, const 
         if (c->last_L < Lmax) return fail(c, CW_ERR_STATE, "align_tokens: the forced decode stopped at %d of %d positions", c->last_L, Lmax);
     }
     return forced_rows_timestamps(c, nb, num_frames, ids_stride, n_ids, n_init, token_ts);
+}
+
+// ------------------------------------------------------------------------------------------------
+// per-head forced alignment (include/crisperwhisper.h: cw_align_heads)
+// ------------------------------------------------------------------------------------------------
+namespace {
+struct DevBuf {                              // call-local device memory, released on every exit
+    void* p = nullptr;
+    ~DevBuf() { if (p) hipFree(p); }
+    hipError_t alloc(size_t bytes) { return hipMalloc(&p, bytes ? bytes : 16); }
+};
+// For the duration of cw_align_heads the context's alignment outputs are the call's capture buffer, its statistics and a slot
+// table built from the requested heads.  Restores the context's own on every exit and leaves no retained rows behind, so a
+// cw_token_timestamps / cw_get_alignment after the call is refused instead of answered from a buffer that no longer exists.
+struct AlignSwapScope {
+    cw_ctx* c;
+    float *align, *ml; int* slot; int n_align, rows; std::vector<int> layers, heads;
+    bool graphs;                             // the decode loop ran: its captured steps hold the call's pointers
+    AlignSwapScope(cw_ctx* c_, float* cap, float* cap_ml, int* cap_slot, int n, int rows_, std::vector<int> l, std::vector<int> h)
+        : c(c_), align(c_->d_align), ml(c_->d_align_ml), slot(c_->d_align_slot), n_align(c_->d.n_align), rows(c_->align_rows),
+          layers(std::move(l)), heads(std::move(h)), graphs(false) {
+        c->d_align = cap; c->d_align_ml = cap_ml; c->d_align_slot = cap_slot; c->d.n_align = n; c->align_rows = rows_;
+        c->align_layers.swap(layers); c->align_heads.swap(heads);
+        c->align_cur = cap;
+    }
+    void loop() { drop_step_graphs(c); graphs = true; }
+    ~AlignSwapScope() {
+        hipStreamSynchronize(c->st);
+        if (graphs) drop_step_graphs(c);
+        c->d_align = align; c->d_align_ml = ml; c->d_align_slot = slot; c->d.n_align = n_align; c->align_rows = rows;
+        c->align_layers.swap(layers); c->align_heads.swap(heads);
+        c->align_cur = c->d_align;
+        c->last_nb = 0; c->last_L = 0; c->align_unnormalized = false;
+    }
+};
+}  // namespace
+
+static size_t cw_align_heads_bytes(int32_t nb, int32_t n_heads, int32_t rows) {
+    return (size_t)nb * (size_t)n_heads * (size_t)rows * CW_N_CTX * 4;
+}
+
+int32_t cw_align_heads(cw_ctx* c, int32_t nb, const int32_t* num_frames, const int32_t* ids, int32_t ids_stride,
+                       const int32_t* n_ids, int32_t n_init, int32_t n_heads, const int32_t* layers, const int32_t* heads,
+                       float* token_ts, const float* ref_begin, const float* ref_end, int32_t clip_frames, float* similarity) {
+    const int TGT = c->d.max_target_positions, H = c->d.n_heads, NL = c->d.dec_layers, S = CW_N_CTX;
+    if (!c->gen_set) return fail(c, CW_ERR_STATE, "cw_set_generation not called");
+    if (nb < 1 || nb > c->Bm) return fail(c, CW_ERR_INVALID, "align_heads: nb=%d out of range (the context has %d rows)", nb, c->Bm);
+    if (!num_frames || !ids || !n_ids || !token_ts || !layers || !heads) return fail(c, CW_ERR_INVALID, "align_heads: null argument");
+    if (n_heads < 1 || n_heads > NL * H) return fail(c, CW_ERR_INVALID, "align_heads: n_heads=%d outside 1 .. %d", n_heads, NL * H);
+    std::vector<int> slot((size_t)NL * H, -1);
+    for (int k = 0; k < n_heads; ++k) {
+        const int l = layers[k], h = heads[k];
+        if (l < 0 || l >= NL || h < 0 || h >= H) return fail(c, CW_ERR_INVALID, "align_heads: head %d is (%d, %d), outside %d layers x %d heads", k, l, h, NL, H);
+        if (slot[(size_t)l * H + h] >= 0) return fail(c, CW_ERR_INVALID, "align_heads: head (%d, %d) requested twice", l, h);
+        slot[(size_t)l * H + h] = k;
+    }
+    if ((ref_begin == nullptr) != (ref_end == nullptr)) return fail(c, CW_ERR_INVALID, "align_heads: ref_begin and ref_end go together");
+    const bool sim = ref_begin && similarity;
+    int n_max = 0;
+    CWCHK(c, check_token_rows(c, "align_heads", nb, num_frames, ids, ids_stride, n_ids, n_init, &n_max));
+    const int Lmax = n_max - 1;                  // decoder input positions 0 .. Lmax-1 = capture rows per (item, head)
+    const size_t cap_bytes = cw_align_heads_bytes(nb, n_heads, Lmax);
+    if (cap_bytes > (size_t)CW_ALIGN_HEADS_MAX_BYTES)
+        return fail(c, CW_ERR_INVALID, "align_heads: %d items x %d heads x %d positions need %zu bytes of attention rows, above the cap of %llu; pass fewer items or heads per call",
+                    nb, n_heads, Lmax, cap_bytes, (unsigned long long)CW_ALIGN_HEADS_MAX_BYTES);
+
+    DevBuf cap, cap_ml, cap_slot, d_rb, d_re, d_sim;
+    const size_t n_rows = (size_t)nb * n_heads * Lmax;
+    if (cap.alloc(cap_bytes + (size_t)S * 4) != hipSuccess || cap_ml.alloc(n_rows * ATT_NS * 2 * 4) != hipSuccess ||
+        cap_slot.alloc(slot.size() * 4) != hipSuccess)
+        return fail(c, CW_ERR_NOMEM, "align_heads: hipMalloc of the %zu-byte capture failed", cap_bytes);
+    HIPCHK(c, hipMemcpy(cap_slot.p, slot.data(), slot.size() * 4, hipMemcpyHostToDevice));
+    // rows a shorter item never writes are read by nothing, but the similarity launch covers them: keep them defined
+    HIPCHK(c, hipMemsetAsync(cap.p, 0, cap_bytes + (size_t)S * 4, c->st));
+    HIPCHK(c, hipMemsetAsync(cap_ml.p, 0, n_rows * ATT_NS * 2 * 4, c->st));
+
+    PrefixScope scope{c, c->pf_prefix};
+    c->pf_prefix = 0;
+    AlignSwapScope swap(c, (float*)cap.p, (float*)cap_ml.p, (int*)cap_slot.p, n_heads, Lmax,
+                        std::vector<int>(layers, layers + n_heads), std::vector<int>(heads, heads + n_heads));
+    std::vector<int> all(nb), zeros(nb, 0), full(nb, CW_N_FRAMES);
+    for (int i = 0; i < nb; ++i) all[i] = i;
+    CWCHK(c, cw_encode(c, nb, all.data(), zeros.data(), full.data()));
+    // wall time of the call's four parts with the stream drained between them (cw_align_heads_times)
+    auto lap = [c](std::chrono::steady_clock::time_point& t0) {
+        hipStreamSynchronize(c->st);
+        const auto t1 = std::chrono::steady_clock::now();
+        const float ms = std::chrono::duration<float, std::milli>(t1 - t0).count();
+        t0 = t1;
+        return ms;
+    };
+    auto t0 = std::chrono::steady_clock::now();
+    lap(t0);
+    if (c->align_prefill && prefill_capable(c)) {
+        std::vector<int> dev((size_t)nb * TGT, c->gen.pad_token_id);
+        for (int b = 0; b < nb; ++b) memcpy(dev.data() + (size_t)b * TGT, ids + (size_t)b * ids_stride, (size_t)n_ids[b] * 4);
+        c->beam_K = 0;
+        HIPCHK(c, hipMemcpyAsync(c->d_ids, dev.data(), dev.size() * 4, hipMemcpyHostToDevice, c->st));
+        HIPCHK(c, hipStreamSynchronize(c->st));
+        StageTimer tm(c, CW_STAGE_DECODE);
+        CWCHK(c, run_prefill(c, nb, Lmax + 1, 1, true));
+        KCHK(c);
+        tm.stop();
+        ++c->align_prefill_runs;
+        c->last_L = Lmax;
+        c->last_nb = nb;
+        c->align_unnormalized = true;
+    } else {
+        swap.loop();
+        std::vector<int> prompt((size_t)nb * n_init), forced((size_t)nb * TGT, -1), seq((size_t)nb * TGT), lens(nb);
+        for (int b = 0; b < nb; ++b) {
+            memcpy(prompt.data() + (size_t)b * n_init, ids + (size_t)b * ids_stride, (size_t)n_init * 4);
+            for (int k = n_init; k < n_ids[b]; ++k) forced[(size_t)b * TGT + k] = ids[(size_t)b * ids_stride + k];
+        }
+        CWCHK(c, cw_decode(c, nb, prompt.data(), n_init, n_max, 0, forced.data(), seq.data(), lens.data(), nullptr));
+        c->align_cur = (float*)cap.p;            // (cw_decode points it at the context's d_align, which is the capture here)
+        if (c->last_L < Lmax) return fail(c, CW_ERR_STATE, "align_heads: the forced decode stopped at %d of %d positions", c->last_L, Lmax);
+        c->last_L = Lmax;                        // rows beyond Lmax - 1 do not exist in the capture
+    }
+    c->align_heads_ms[0] = lap(t0);
+    CWCHK(c, normalize_alignment(c));
+    c->align_heads_ms[1] = lap(t0);
+
+    std::vector<int> ncols;
+    timestamp_ncols(nb, num_frames, ncols);
+    c->align_heads_ms[2] = c->align_heads_ms[4] = 0.f;
+    if (sim) {   // the rows as normalised, before the timestamp stage reads them
+        std::vector<float> rb((size_t)nb * Lmax, NAN), re((size_t)nb * Lmax, NAN), out((size_t)n_heads * nb * Lmax);
+        for (int b = 0; b < nb; ++b)
+            for (int k = n_init; k < n_ids[b] - 1; ++k) {
+                rb[(size_t)b * Lmax + k] = ref_begin[(size_t)b * ids_stride + k];
+                re[(size_t)b * Lmax + k] = ref_end[(size_t)b * ids_stride + k];
+            }
+        if (d_rb.alloc(rb.size() * 4) != hipSuccess || d_re.alloc(re.size() * 4) != hipSuccess || d_sim.alloc(out.size() * 4) != hipSuccess)
+            return fail(c, CW_ERR_NOMEM, "align_heads: hipMalloc of the similarity buffers failed");
+        HIPCHK(c, hipMemcpyAsync(c->d_ncols, ncols.data(), nb * 4, hipMemcpyHostToDevice, c->st));
+        HIPCHK(c, hipMemcpyAsync(d_rb.p, rb.data(), rb.size() * 4, hipMemcpyHostToDevice, c->st));
+        HIPCHK(c, hipMemcpyAsync(d_re.p, re.data(), re.size() * 4, hipMemcpyHostToDevice, c->st));
+        HIPCHK(c, hipStreamSynchronize(c->st));
+        StageTimer tm(c, CW_STAGE_TIMESTAMPS);
+        CWCHK(c, cw_launch_align_similarity((const float*)cap.p, nb, n_heads, Lmax, S, 0, Lmax, c->d_ncols, (const float*)d_rb.p,
+                                            (const float*)d_re.p, clip_frames, (float*)d_sim.p, c->st));
+        KCHK(c);
+        tm.stop();
+        hipEventElapsedTime(&c->align_heads_ms[4], c->ev0, c->ev1);     // the events tm just recorded around the launch
+        HIPCHK(c, hipMemcpy(out.data(), d_sim.p, out.size() * 4, hipMemcpyDeviceToHost));
+        for (int k = 0; k < n_heads; ++k)
+            for (int b = 0; b < nb; ++b) {
+                float* dst = similarity + ((size_t)k * nb + b) * ids_stride;
+                for (int t = 0; t < ids_stride; ++t) dst[t] = t < Lmax ? out[((size_t)k * nb + b) * Lmax + t] : NAN;
+            }
+        c->align_heads_ms[2] = lap(t0);
+    } else if (similarity) {
+        for (size_t i = 0; i < (size_t)n_heads * nb * ids_stride; ++i) similarity[i] = NAN;
+    }
+
+    // timestamps: the (item, head) sequences are [nb * n_heads][1][Lmax][S]; consecutive sequences of one token count share
+    // a pass of the stages, at most max_batch of them (the workspaces' size)
+    for (size_t i = 0; i < (size_t)n_heads * nb * ids_stride; ++i) token_ts[i] = 0.f;
+    const int n_seq = nb * n_heads;
+    std::vector<int> nc, fc;
+    for (int q0 = 0, q1; q0 < n_seq; q0 = q1) {
+        const int L = n_ids[q0 / n_heads] - 1, N = L - n_init;
+        for (q1 = q0 + 1; q1 < n_seq && q1 - q0 < c->Bm && n_ids[q1 / n_heads] - 1 == L; ++q1) {}
+        if (N <= 0) continue;
+        nc.resize(q1 - q0);
+        for (int q = q0; q < q1; ++q) nc[q - q0] = ncols[q / n_heads];
+        CWCHK(c, timestamp_first_cols(c, (const float*)cap.p + (size_t)q0 * Lmax * S, q1 - q0, 1, Lmax, n_init, N, nc.data(), fc));
+        for (int q = q0; q < q1; ++q) {
+            const int b = q / n_heads, k = q % n_heads;
+            float* ts = token_ts + ((size_t)k * nb + b) * ids_stride;
+            for (int i = 0; i < N; ++i) {
+                const int col = ncols[b] > 0 ? fc[(size_t)(q - q0) * N + i] : -1;
+                ts[n_init + i] = (float)((double)col * 0.02);
+            }
+            ts[L] = ts[L - 1];
+        }
+    }
+    c->align_heads_ms[3] = lap(t0);
+    return CW_OK;
+}
+
+int32_t cw_align_heads_times(cw_ctx* c, float* ms) {
+    memcpy(ms, c->align_heads_ms, sizeof(c->align_heads_ms));
+    return CW_OK;
+}
+
+// cw_test_align_similarity: the similarity kernel, through cw_align_heads' launcher, on caller-supplied normalised rows.
+int32_t cw_test_align_similarity(cw_ctx* c, const float* attn, int32_t B, int32_t Ha, int32_t N, int32_t S, const int32_t* n_cols,
+                                 const float* ref_begin, const float* ref_end, int32_t clip_frames, float* out) {
+    if (!attn || !n_cols || !ref_begin || !ref_end || !out) return fail(c, CW_ERR_INVALID, "test_align_similarity: null argument");
+    if (B < 1 || Ha < 1 || N < 1 || S < 4 || S % 4 || (size_t)B * Ha * N * S > ((size_t)1 << 28))
+        return fail(c, CW_ERR_INVALID, "test_align_similarity: B=%d Ha=%d N=%d S=%d unsupported (S a multiple of 4, at most 2^28 elements)", B, Ha, N, S);
+    for (int b = 0; b < B; ++b)
+        if (n_cols[b] < 0 || n_cols[b] > S) return fail(c, CW_ERR_INVALID, "test_align_similarity: n_cols[%d]=%d outside 0 .. %d", b, n_cols[b], S);
+    DevBuf dw, dn, db, de, dout;
+    const size_t nw = (size_t)B * Ha * N * S, nr = (size_t)B * N, no = (size_t)Ha * B * N;
+    if (dw.alloc(nw * 4) != hipSuccess || dn.alloc((size_t)B * 4) != hipSuccess || db.alloc(nr * 4) != hipSuccess ||
+        de.alloc(nr * 4) != hipSuccess || dout.alloc(no * 4) != hipSuccess)
+        return fail(c, CW_ERR_NOMEM, "test_align_similarity: hipMalloc failed");
+    HIPCHK(c, hipMemcpy(dw.p, attn, nw * 4, hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemcpy(dn.p, n_cols, (size_t)B * 4, hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemcpy(db.p, ref_begin, nr * 4, hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemcpy(de.p, ref_end, nr * 4, hipMemcpyHostToDevice));
+    CWCHK(c, cw_launch_align_similarity((const float*)dw.p, B, Ha, N, S, 0, N, (const int*)dn.p, (const float*)db.p,
+                                        (const float*)de.p, clip_frames, (float*)dout.p, c->st));
+    KCHK(c);
+    HIPCHK(c, hipStreamSynchronize(c->st));
+    HIPCHK(c, hipMemcpy(out, dout.p, no * 4, hipMemcpyDeviceToHost));
+    return CW_OK;
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -78,6 +78,9 @@ struct SampleParams {
 #define SB_LAST (SB_VAL + SB_MAX_SEQ)
 #define SB_TOK (SB_LAST + SB_MAX_SEQ)
 #define SB_WORDS (SB_TOK + SB_MAX_SEQ * SB_MAX_LEN)
+// cw_align_heads: most bytes of attention rows ([items][heads][positions][1500] f32) one call may capture (as in
+// include/crisperwhisper.h); 8 items x 640 heads x 129 positions are 3.96 GB
+#define CW_ALIGN_HEADS_MAX_BYTES (8ull << 30)
 // beam search (elementwise.hip): per row the n_cand best processed log-probabilities of the next token
 // (log_softmax of the raw logits, then the same processors as the greedy path) ...
 // ... and the re-ordering of the per-row state after the host picked (parent row, token) for every row
@@ -461,6 +464,10 @@ int cw_launch_align_stats(const float* w, int B, int Ha, int rows_cap, int S, in
                           float* mean, float* stdv, hipStream_t st);
 int cw_launch_align_filter(const float* w, int B, int Ha, int rows_cap, int S, int row0, int N, const int* n_cols,
                            const float* mean, const float* stdv, int width, float* mat, hipStream_t st);
+// w [B][Ha][rows_cap][S] normalised rows (S % 4 == 0) -> out [Ha][B][N]: cosine of token row row0 + t to the target of its
+// reference interval ref_begin / ref_end [B][N] (seconds, NaN = none); clip < 0: no clipping
+int cw_launch_align_similarity(const float* w, int B, int Ha, int rows_cap, int S, int row0, int N, const int* n_cols,
+                               const float* ref_begin, const float* ref_end, int clip, float* out, hipStream_t st);
 // skew: workspace of cw_dtw_skew_floats(B, N, S) floats (null: round-1 block kernel)
 size_t cw_dtw_skew_floats(int B, int N, int S);
 int cw_launch_dtw(const float* mat, int B, int N, int S, const int* n_cols, unsigned char* trace, int* first_col,

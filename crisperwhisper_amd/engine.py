@@ -420,6 +420,68 @@ class Engine:
         self._chk(self.lib.cw_align_tokens(self.ctx, nb, _ptr(nf), _ptr(table), stride, _ptr(n), int(n_init), _ptr(ts)))
         return [ts[b, :n[b]].copy() for b in range(nb)]
 
+    def align_heads(self, num_frames, ids, n_init: int, heads, ref=None, clip_frames: int = 200):
+        """Per-head forced alignment (cw_align_heads) of the resident feature items 0 .. len(ids)-1.  ``ids`` as
+        ``align_tokens`` takes them; ``heads`` a list of distinct (layer, head) pairs of the decoder.  Returns per head, in the
+        order given, what ``align_tokens`` would return with that head as the only alignment head: a list over the heads of
+        lists over the rows of float32 arrays of len(ids[b]).  ``ref=(begin, end)``, per row one array of len(ids[b]) seconds
+        (NaN: no reference): also returns the similarity of every token's attention row to its interval, in the same shape
+        (NaN where undefined), with the row counted as 0 further than ``clip_frames`` frames from the interval (< 0: no
+        clipping)."""
+        nb = len(ids)
+        hd = np.asarray(heads, dtype=np.int64)
+        if hd.ndim != 2 or hd.shape[1] != 2 or hd.shape[0] < 1:
+            raise ValueError("heads must be a non-empty list of (layer, head) pairs")
+        n, stride, table = self._token_table(ids)
+        nf = _i32(num_frames)
+        nh = hd.shape[0]
+        layers, hh = _i32(hd[:, 0]), _i32(hd[:, 1])
+        ts = np.zeros((nh, nb, stride), dtype=np.float32)
+        rb = re = sim = None
+        if ref is not None:
+            begin, end = ref
+            if len(begin) != nb or len(end) != nb:
+                raise ValueError(f"ref holds {len(begin)} / {len(end)} rows for {nb} rows of ids")
+            rb = np.full((nb, stride), np.nan, dtype=np.float32)
+            re = np.full((nb, stride), np.nan, dtype=np.float32)
+            for b in range(nb):
+                if len(begin[b]) != n[b] or len(end[b]) != n[b]:
+                    raise ValueError(f"ref row {b} holds {len(begin[b])} / {len(end[b])} entries for {n[b]} ids")
+                rb[b, :n[b]] = begin[b]
+                re[b, :n[b]] = end[b]
+            sim = np.zeros((nh, nb, stride), dtype=np.float32)
+        self._chk(self.lib.cw_align_heads(self.ctx, nb, _ptr(nf), _ptr(table), stride, _ptr(n), int(n_init), nh, _ptr(layers),
+                                          _ptr(hh), _ptr(ts), _ptr(rb), _ptr(re), int(clip_frames), _ptr(sim)))
+        out = [[ts[k, b, :n[b]].copy() for b in range(nb)] for k in range(nh)]
+        if sim is None:
+            return out
+        return out, [[sim[k, b, :n[b]].copy() for b in range(nb)] for k in range(nh)]
+
+    def align_heads_times(self):
+        """cw_align_heads_times: milliseconds of the last ``align_heads`` call's forward, normalisation, similarity and
+        per-head timestamps, and of the similarity kernel alone."""
+        ms = np.zeros(5, dtype=np.float32)
+        self._chk(self.lib.cw_align_heads_times(self.ctx, _ptr(ms)))
+        return {"forward": float(ms[0]), "normalize": float(ms[1]), "similarity": float(ms[2]), "timestamps": float(ms[3]),
+                "similarity_kernel": float(ms[4])}
+
+    def test_align_similarity(self, attn, n_cols, ref_begin, ref_end, clip_frames: int) -> np.ndarray:
+        """cw_test_align_similarity: the similarity kernel of ``align_heads`` on normalised rows attn [B][Ha][N][S] (S a multiple
+        of 4), n_cols [B], ref_begin / ref_end [B][N] seconds -> [Ha][B][N]."""
+        a = np.ascontiguousarray(attn, dtype=np.float32)
+        if a.ndim != 4:
+            raise ValueError("test_align_similarity: attn must be [B][Ha][N][S]")
+        B, Ha, Nn, S = a.shape
+        nc = _i32(n_cols)
+        rb = np.ascontiguousarray(ref_begin, dtype=np.float32)
+        re = np.ascontiguousarray(ref_end, dtype=np.float32)
+        if nc.shape != (B,) or rb.shape != (B, Nn) or re.shape != (B, Nn):
+            raise ValueError("test_align_similarity: shapes do not agree")
+        out = np.zeros((Ha, B, Nn), dtype=np.float32)
+        self._chk(self.lib.cw_test_align_similarity(self.ctx, _ptr(a), B, Ha, Nn, S, _ptr(nc), _ptr(rb), _ptr(re), int(clip_frames),
+                                                    _ptr(out)))
+        return out
+
     def align_prefill_runs(self) -> int:
         """cw_align_prefill_runs: align_tokens calls of this engine whose forward ran as the batched prefill."""
         return int(self.lib.cw_align_prefill_runs(self.ctx))

@@ -17,6 +17,7 @@ from typing import Callable, List, Optional, Sequence, Tuple
 
 import numpy as np
 
+from . import _native as N
 from ._native import N_FRAMES
 from .engine import Engine
 
@@ -924,6 +925,133 @@ def align(engine: Engine, n_items: int, num_frames, transcripts, *, language: Op
                 "token_logprobs": lp, "top_ids": ti, "top_logprobs": tl}
     ts = engine.align_tokens(num_frames, rows, n_init)
     return {"sequences": texts, "token_timestamps": [s[n_init:n_init + len(t)] for s, t in zip(ts, texts)]}
+
+
+ALIGN_HEADS_ROW_BYTES = 1500 * 4          # one recorded attention row (f32 over the encoder frames)
+
+
+def check_heads(spec, heads):
+    """(layer, head) pairs of ``align_heads``: None = every head of the decoder, layer-major; else distinct integer pairs inside
+    the decoder's layers x heads.  Returns a list of [layer, head]."""
+    if heads is None:
+        return [[l, h] for l in range(spec.dec_layers) for h in range(spec.n_heads)]
+    if isinstance(heads, (str, bytes)) or not hasattr(heads, "__len__") or len(heads) == 0:
+        raise ValueError("heads must be None or a non-empty list of (layer, head) pairs")
+    out, seen = [], set()
+    for p in heads:
+        if isinstance(p, (str, bytes)) or not hasattr(p, "__len__") or len(p) != 2 or any(
+                isinstance(x, bool) or not isinstance(x, (int, np.integer)) for x in p):
+            raise ValueError(f"heads holds {p!r}: every entry is a (layer, head) pair of integers")
+        l, h = int(p[0]), int(p[1])
+        if not (0 <= l < spec.dec_layers and 0 <= h < spec.n_heads):
+            raise ValueError(f"head ({l}, {h}) is outside the decoder's {spec.dec_layers} layers x {spec.n_heads} heads")
+        if (l, h) in seen:
+            raise ValueError(f"head ({l}, {h}) is listed twice")
+        seen.add((l, h))
+        out.append([l, h])
+    return out
+
+
+def plan_align_heads_calls(n_ids: Sequence[int], n_heads: int, max_batch: int, max_bytes: Optional[int] = None):
+    """Splits the items of ``align_heads`` into engine calls of consecutive items whose capture -- items x heads x (longest
+    row's ids - 1) recorded rows of 6000 bytes -- stays within ``max_bytes`` (CW_ALIGN_HEADS_MAX_BYTES) and whose item count
+    within ``max_batch``.  Returns a list of lists of item indices."""
+    if max_batch < 1:
+        raise ValueError("max_batch must be at least 1")
+    if max_bytes is None:
+        max_bytes = N.ALIGN_HEADS_MAX_BYTES
+    calls, cur, longest = [], [], 0
+    for b, n in enumerate(n_ids):
+        rows = int(n) - 1
+        if n_heads * rows * ALIGN_HEADS_ROW_BYTES > max_bytes:
+            raise ValueError(f"item {b}: {n_heads} heads x {rows} positions need {n_heads * rows * ALIGN_HEADS_ROW_BYTES} bytes of "
+                             f"attention rows, above the cap of {max_bytes}; pass fewer heads per call")
+        new_longest = max(longest, rows)
+        if cur and (len(cur) + 1 > max_batch or (len(cur) + 1) * n_heads * new_longest * ALIGN_HEADS_ROW_BYTES > max_bytes):
+            calls.append(cur)
+            cur, new_longest = [], rows
+        cur.append(b)
+        longest = new_longest
+    if cur:
+        calls.append(cur)
+    return calls
+
+
+def align_heads(engine: Engine, n_items: int, num_frames, transcripts, heads=None, *, language: Optional[str] = None,
+                task: Optional[str] = None, ref=None, clip_frames: int = 200,
+                load_items: Optional[Callable[[List[int]], None]] = None):
+    """``align`` for every requested decoder cross-attention head on its own (cw_align_heads): what alignment-head selection
+    and an audit of the configured heads need.  ``heads``: list of (layer, head) pairs, None = every head in layer-major order.
+    Init tokens and language detection as in ``align``.  ``ref``: per item a pair (begin, end) of arrays with one entry per
+    transcript token, seconds (NaN: no reference) -- adds "similarity".  Items are split into calls whose capture stays under
+    the engine's cap (``plan_align_heads_calls``); a call over items other than 0 .. n-1 needs ``load_items(items)`` to make them
+    resident, as in ``score``.  Every argument is checked before the engine is touched.  Returns {"heads", "sequences",
+    "token_timestamps": [n_heads][n_items] float32 arrays over the transcript's tokens, "similarity": likewise, with ref}."""
+    spec = engine.spec
+    texts = [check_transcript_ids(spec, t) for t in transcripts]
+    if len(texts) != n_items:
+        raise ValueError(f"{len(texts)} transcripts for {n_items} items")
+    if n_items > engine.max_batch:
+        raise ValueError(f"{n_items} items exceed the engine's {engine.max_batch} rows")
+    hd = check_heads(spec, heads)
+    toks, detect = resolve_prompt(spec, language, task)
+    if detect and not spec.lang_to_id:
+        raise ValueError("Cannot detect language for an English-only checkpoint: the generation config has no `lang_to_id`.")
+    n_init = len(toks)
+    for b, t in enumerate(texts):
+        if n_init + len(t) + 1 > spec.max_target_positions:
+            raise ValueError(f"transcript {b}: {n_init} init tokens + {len(t)} tokens + eos exceed max_target_positions "
+                             f"({spec.max_target_positions})")
+    num_frames = np.asarray(num_frames, dtype=np.int64)
+    if num_frames.shape != (n_items,):
+        raise ValueError(f"num_frames holds {num_frames.shape} entries for {n_items} items")
+    refs = None
+    if ref is not None:
+        if len(ref) != n_items:
+            raise ValueError(f"ref holds {len(ref)} entries for {n_items} items")
+        refs = []
+        for b, r in enumerate(ref):
+            if len(r) != 2:
+                raise ValueError(f"ref[{b}] must be a pair (begin, end)")
+            rb, re = (np.asarray(x, dtype=np.float32).reshape(-1) for x in r)
+            if len(rb) != len(texts[b]) or len(re) != len(texts[b]):
+                raise ValueError(f"ref[{b}] holds {len(rb)} / {len(re)} times for {len(texts[b])} transcript tokens")
+            refs.append((rb, re))
+    calls = plan_align_heads_calls([n_init + len(t) + 1 for t in texts], len(hd), engine.max_batch)
+    if load_items is None and calls != [list(range(n_items))]:
+        raise ValueError(f"align_heads: {n_items} items x {len(hd)} heads do not fit one call (the capture is capped at "
+                         f"{N.ALIGN_HEADS_MAX_BYTES} bytes) and no load_items was given")
+    if detect:
+        engine.encode(list(range(n_items)), np.zeros(n_items, np.int64), np.full(n_items, N_FRAMES, np.int64))
+        inits = [init_tokens(spec, language, task, lang_id=l) for l in detect_language(engine, n_items)]
+    else:
+        inits = [init_tokens(spec, language, task)] * n_items
+    rows = [np.concatenate([np.asarray(i, np.int64), t, [spec.eos_token_id]]) for i, t in zip(inits, texts)]
+    ts_out = [[None] * n_items for _ in hd]
+    sim_out = [[None] * n_items for _ in hd] if refs is not None else None
+    nan = np.float32("nan")
+    resident = list(range(n_items))
+    for items in calls:
+        if items != resident[:len(items)]:
+            load_items(items)
+            resident = list(items)
+        r = None
+        if refs is not None:
+            pad = lambda x: np.concatenate([np.full(n_init, nan, np.float32), x, [nan]])
+            r = ([pad(refs[b][0]) for b in items], [pad(refs[b][1]) for b in items])
+        res = engine.align_heads(num_frames[items], [rows[b] for b in items], n_init, hd, ref=r, clip_frames=clip_frames)
+        ts, sim = res if refs is not None else (res, None)
+        for k in range(len(hd)):
+            for j, b in enumerate(items):
+                ts_out[k][b] = ts[k][j][n_init:n_init + len(texts[b])]
+                if sim is not None:
+                    sim_out[k][b] = sim[k][j][n_init:n_init + len(texts[b])]
+    if resident != list(range(n_items)) and load_items is not None:
+        load_items(list(range(n_items)))
+    out = {"heads": hd, "sequences": texts, "token_timestamps": ts_out}
+    if sim_out is not None:
+        out["similarity"] = sim_out
+    return out
 
 
 def plan_score_calls(n_candidates: Sequence[int], max_batch: int):

@@ -53,10 +53,34 @@ class ModelBundle:
         self.spec = spec
         self.weights = weights
 
+    @staticmethod
+    def check_alignment_heads(alignment_heads, dec_layers: int, n_heads: int):
+        """An ``alignment_heads`` override of the loaders, validated against the geometry: a non-empty list of distinct
+        (layer, head) pairs inside the decoder's layers x heads."""
+        if isinstance(alignment_heads, (str, bytes)) or not hasattr(alignment_heads, "__len__") or len(alignment_heads) == 0:
+            raise ValueError("alignment_heads must be a non-empty list of (layer, head) pairs")
+        out = []
+        for p in alignment_heads:
+            if isinstance(p, (str, bytes)) or not hasattr(p, "__len__") or len(p) != 2 or any(
+                    isinstance(x, bool) or not isinstance(x, (int, np.integer)) for x in p):
+                raise ValueError(f"alignment_heads holds {p!r}: every entry is a (layer, head) pair of integers")
+            l, h = int(p[0]), int(p[1])
+            if not (0 <= l < dec_layers and 0 <= h < n_heads):
+                raise ValueError(f"alignment head ({l}, {h}) is outside the decoder's {dec_layers} layers x {n_heads} heads")
+            if [l, h] in out:
+                raise ValueError(f"alignment head ({l}, {h}) is listed twice")
+            out.append([l, h])
+        return out
+
     @classmethod
-    def from_hf(cls, model) -> "ModelBundle":
+    def from_hf(cls, model, alignment_heads=None) -> "ModelBundle":
+        """``alignment_heads``: a list of (layer, head) pairs that replaces the generation config's (validated against the
+        geometry) -- how a checkpoint without heads, or with heads to be re-selected, is loaded
+        (``CrisperWhisperPipeline.rank_alignment_heads``).  None: the checkpoint's own, which must exist."""
         cfg, gc = model.config, model.generation_config
-        if not hasattr(gc, "alignment_heads"):
+        if alignment_heads is not None:
+            alignment_heads = cls.check_alignment_heads(alignment_heads, cfg.decoder_layers, cfg.decoder_attention_heads)
+        elif not hasattr(gc, "alignment_heads"):
             raise ValueError("Model generation config has no `alignment_heads`, token-level timestamps not available. "
                              "See https://gist.github.com/hollance/42e32852f24243b748ae6bc1f985b13a on how to add this "
                              "property to the generation config.")
@@ -67,7 +91,7 @@ class ModelBundle:
             enc_layers=cfg.encoder_layers, dec_layers=cfg.decoder_layers, n_mels=cfg.num_mel_bins,
             vocab_size=cfg.vocab_size, max_target_positions=cfg.max_target_positions,
             median_filter_width=cfg.median_filter_width,
-            alignment_heads=[list(h) for h in gc.alignment_heads],
+            alignment_heads=alignment_heads if alignment_heads is not None else [list(h) for h in gc.alignment_heads],
             eos_token_id=gc.eos_token_id if isinstance(gc.eos_token_id, int) else gc.eos_token_id[0],
             pad_token_id=gc.pad_token_id, decoder_start_token_id=gc.decoder_start_token_id,
             no_timestamps_token_id=gc.no_timestamps_token_id,
@@ -83,11 +107,12 @@ class ModelBundle:
         return cls(spec, weights)
 
     @classmethod
-    def from_pretrained(cls, path: str) -> "ModelBundle":
+    def from_pretrained(cls, path: str, alignment_heads=None) -> "ModelBundle":
         """Load a Whisper checkpoint directory without ``transformers``: ``config.json`` + ``generation_config.json``
         -> ModelSpec, ``model.safetensors`` (or the sharded ``model.safetensors.index.json``) -> weights, streamed tensor
         by tensor as float32.  Replaces ``AutoModelForSpeechSeq2Seq.from_pretrained(model_id)`` (REF/transcribe.py:14-17)
-        for a local snapshot; error texts follow the reference's (``generation_whisper.py:1399-1405, 1689-1693``)."""
+        for a local snapshot; error texts follow the reference's (``generation_whisper.py:1399-1405, 1689-1693``).
+        ``alignment_heads``: as in ``from_hf``."""
         import json
         import os
         cfg = json.load(open(os.path.join(path, "config.json")))
@@ -95,7 +120,10 @@ class ModelBundle:
         gc = json.load(open(gpath)) if os.path.exists(gpath) else {}
         if cfg.get("model_type", "whisper") != "whisper":
             raise ValueError(f"not a Whisper checkpoint: model_type={cfg.get('model_type')!r}")
-        if "alignment_heads" not in gc:
+        if alignment_heads is not None:
+            alignment_heads = cls.check_alignment_heads(alignment_heads, cfg["decoder_layers"],
+                                                        cfg.get("decoder_attention_heads", cfg["encoder_attention_heads"]))
+        elif "alignment_heads" not in gc:
             raise ValueError("Model generation config has no `alignment_heads`, token-level timestamps not available. "
                              "See https://gist.github.com/hollance/42e32852f24243b748ae6bc1f985b13a on how to add this "
                              "property to the generation config.")
@@ -107,7 +135,7 @@ class ModelBundle:
             enc_layers=cfg["encoder_layers"], dec_layers=cfg["decoder_layers"], n_mels=cfg["num_mel_bins"],
             vocab_size=cfg["vocab_size"], max_target_positions=cfg.get("max_target_positions", 448),
             median_filter_width=cfg.get("median_filter_width", 7),
-            alignment_heads=[list(h) for h in gc["alignment_heads"]],
+            alignment_heads=alignment_heads if alignment_heads is not None else [list(h) for h in gc["alignment_heads"]],
             eos_token_id=eos if isinstance(eos, int) else eos[0],
             pad_token_id=gc.get("pad_token_id", cfg.get("pad_token_id")),
             decoder_start_token_id=gc.get("decoder_start_token_id", cfg.get("decoder_start_token_id")),
@@ -673,7 +701,7 @@ class CrisperWhisperPipeline:
             pcm = self._load(x)
             if len(pcm) > N_SAMPLES:
                 raise ValueError(f"input {k} is {len(pcm) / self.sampling_rate:.2f} s long: {who} takes at most 30 s "
-                                 f"({N_SAMPLES} samples) per input; long-form {'alignment' if who == 'align' else 'scoring'} is not implemented")
+                                 f"({N_SAMPLES} samples) per input; long-form {'scoring' if who == 'score' else 'alignment'} is not implemented")
             pcms.append(pcm)
         return pcms
 
@@ -798,6 +826,103 @@ class CrisperWhisperPipeline:
                                                  time_precision=0.02, return_timestamps="word")
                 results.append({"text": text, "chunks": words})
         return results[0] if single else results
+
+    # -- per-head forced alignment, alignment-head selection -----------------------------------------
+    def _align_heads(self, who, inputs, transcripts, heads, language, task, word_refs=None):
+        """Shared by ``align_heads`` and ``rank_alignment_heads``: per input (heads, token timestamps [n_heads][n_tokens], word
+        chunks per head, similarity [n_heads][n_tokens] or None).  ``word_refs``: per input [W][2] reference word intervals."""
+        if not isinstance(transcripts, (list, tuple)) or len(transcripts) != len(inputs):
+            raise ValueError(f"{len(inputs)} inputs need a list of {len(inputs)} transcripts, got "
+                             f"{len(transcripts) if isinstance(transcripts, (list, tuple)) else type(transcripts).__name__}")
+        ids = [self._transcript_ids(t) for t in transcripts]
+        hd = generation.check_heads(self.bundle.spec, heads)
+        generation.resolve_prompt(self.bundle.spec, language, task)        # refuses a bad language / task before any audio work
+        tok_refs = None
+        if word_refs is not None:
+            tok_refs = []
+            for k, (t, wr) in enumerate(zip(ids, word_refs)):
+                _, words, groups = collate.decode_asr(self.vocab, [{"tokens": t, "token_timestamps": np.zeros(len(t), np.float32)}],
+                                                      time_precision=0.02, return_timestamps="word", return_token_groups=True)
+                if len(words) != len(wr):
+                    raise ValueError(f"input {k}: the transcript splits into {len(words)} words ({[w['text'] for w in words]}) "
+                                     f"but {len(wr)} references were given")
+                rb = np.full(len(t), np.nan, np.float32)
+                re = np.full(len(t), np.nan, np.float32)
+                for g, (s, e) in zip(groups, wr):
+                    rb[list(g)] = s
+                    re[list(g)] = e
+                tok_refs.append((rb, re))
+        pcms = self._load_clips(who, inputs)
+        eng = self.engine
+        per = max(1, eng.max_batch)
+        results = []
+        for b0 in range(0, len(pcms), per):
+            idx = list(range(b0, min(len(pcms), b0 + per)))
+            _, nf = eng.mel([pcms[i] for i in idx])
+            out = generation.align_heads(eng, len(idx), nf, [ids[i] for i in idx], hd, language=language, task=task,
+                                         ref=[tok_refs[i] for i in idx] if tok_refs is not None else None,
+                                         load_items=lambda items: eng.mel([pcms[idx[j]] for j in items]))
+            for k in range(len(idx)):
+                chunks = []
+                for h in range(len(hd)):
+                    _, words = collate.decode_asr(self.vocab, [{"tokens": out["sequences"][k],
+                                                                "token_timestamps": out["token_timestamps"][h][k]}],
+                                                  time_precision=0.02, return_timestamps="word")
+                    chunks.append(words)
+                results.append((hd, [out["token_timestamps"][h][k] for h in range(len(hd))], chunks,
+                                [out["similarity"][h][k] for h in range(len(hd))] if "similarity" in out else None))
+        return results
+
+    def align_heads(self, inputs, transcripts, heads=None, language: Optional[str] = None, task: Optional[str] = None, **kwargs):
+        """``align`` for every requested decoder cross-attention head on its own: which heads of this checkpoint align, and do
+        the configured ones still.  ``inputs`` / ``transcripts`` as ``align`` takes them (audio at most 30 s); ``heads`` a list
+        of (layer, head) pairs, None = every head of the decoder in layer-major order.  Returns per input {"heads": [[l, h],
+        ...], "token_timestamps": [n_heads][n_tokens], "chunks": per head the word chunks ``align`` would return with that head
+        as the only alignment head}, or a list of them for a list of inputs."""
+        language, task = self._forced_kwargs("align_heads", language, task, kwargs)
+        single = not isinstance(inputs, (list, tuple))
+        if single:
+            inputs, transcripts = [inputs], [transcripts]
+        res = self._align_heads("align_heads", inputs, transcripts, heads, language, task)
+        out = [{"heads": [list(h) for h in hd], "token_timestamps": [np.asarray(t) for t in ts], "chunks": chunks}
+               for hd, ts, chunks, _ in res]
+        return out[0] if single else out
+
+    def rank_alignment_heads(self, inputs, transcripts, references, top: int = 15, collar: float = 0.05, heads=None,
+                             language: Optional[str] = None, task: Optional[str] = None, **kwargs):
+        """Alignment-head selection: every head's own forced alignment of ``transcripts`` against reference word times.
+        ``references``: per input ``[{"text", "timestamp": (start, end)}, ...]``, one entry per word of the transcript as the
+        collation splits it (a different word count is an error that names the input).  Returns {"ranking": per head, best
+        first, {"head": [l, h], "mean_abs_error" (s, over word boundaries), "within_collar" (share of boundaries within
+        ``collar`` s), "mean_iou" (word intervals), "mean_similarity" (attention rows against the words' intervals), "n_within",
+        "n_boundaries"}, "alignment_heads": the ``top`` heads by share within the collar, ties by mean IoU, then similarity,
+        then (layer, head) -- the list for ``generation_config.json``}.  Arithmetic: ``crisperwhisper_amd.metrics``."""
+        from . import metrics
+        language, task = self._forced_kwargs("rank_alignment_heads", language, task, kwargs)
+        if not isinstance(inputs, (list, tuple)):
+            inputs, transcripts, references = [inputs], [transcripts], [references]
+        if not isinstance(references, (list, tuple)) or len(references) != len(inputs):
+            raise ValueError(f"{len(inputs)} inputs need a list of {len(inputs)} reference lists")
+        if isinstance(top, bool) or not isinstance(top, (int, np.integer)) or top < 1:
+            raise ValueError(f"top must be a positive integer, got {top!r}")
+        if not (isinstance(collar, (int, float)) and np.isfinite(collar) and collar >= 0):
+            raise ValueError(f"collar must be a non-negative number of seconds, got {collar!r}")
+        word_refs = []
+        for k, ref in enumerate(references):
+            rows = []
+            for w in ref:
+                ts = w.get("timestamp") if isinstance(w, dict) else None
+                if ts is None or len(ts) != 2 or not all(isinstance(x, (int, float, np.floating, np.integer)) and np.isfinite(x) for x in ts):
+                    raise ValueError(f"input {k}: every reference is {{'text', 'timestamp': (start, end)}} with finite times, got {w!r}")
+                rows.append((float(ts[0]), float(ts[1])))
+            word_refs.append(np.asarray(rows, np.float64).reshape(-1, 2))
+        res = self._align_heads("rank_alignment_heads", inputs, transcripts, heads, language, task, word_refs=word_refs)
+        hd = res[0][0] if res else generation.check_heads(self.bundle.spec, heads)
+        rows = []
+        for h in range(len(hd)):
+            pred = [np.asarray([c["timestamp"] for c in chunks[h]], np.float64).reshape(-1, 2) for _, _, chunks, _ in res]
+            rows.append(metrics.head_metrics(pred, word_refs, [sim[h] for _, _, _, sim in res], collar=float(collar)))
+        return metrics.rank_heads(hd, rows, top=int(top))
 
 
 def pipeline(task: str = "automatic-speech-recognition", model=None, tokenizer=None, feature_extractor=None, **kwargs):

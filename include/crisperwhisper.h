@@ -330,6 +330,38 @@ int32_t cw_align_tokens(cw_ctx* ctx, int32_t nb, const int32_t* num_frames, cons
 /* cw_align_prefill_runs: how many cw_align_tokens calls of this context ran their forward as the batched prefill.        */
 int32_t cw_align_prefill_runs(cw_ctx* ctx);
 
+/* cw_align_heads: cw_align_tokens for any set of decoder cross-attention heads at once -- what alignment-head selection needs.
+ * Same inputs, checks, encoder pass and forward path as cw_align_tokens (the batched prefill on the 16-bit engines with the
+ * 16-bit cross cache, else the forced per-position loop), but the n_heads heads (layers[k], heads[k]) are recorded instead of the
+ * context's own: for the duration of the call the alignment outputs are a call-local buffer [nb][n_heads][rows][1500] f32 (rows =
+ * the longest row's positions), and the prefill stops after the cross-attention of the highest requested layer.  The timestamp
+ * stages then run on every (item, head) pair on its own (one head, no head mean), with the frame count of item b computed as
+ * cw_align_tokens computes it.  token_ts [n_heads][nb][ids_stride] in request order: row (k, b) is bit-identical to what
+ * cw_align_tokens writes for item b in a context whose only alignment head is (layers[k], heads[k]).
+ * ref_begin / ref_end [nb][ids_stride] (seconds, NaN = no reference; both null: no similarity): reference interval of the
+ * token at the same index.  similarity [n_heads][nb][ids_stride] (null allowed) then receives, for every text token with a
+ * finite interval, the cosine between its normalised attention row a and the interval's target g over the item's frames:
+ * g = 1 on frames f0 = floor(begin / 0.02) .. f1 - 1, f1 = max(f0 + 1, ceil(end / 0.02)), 1 - k / 5 on the k-th frame outside
+ * either end (k = 1 .. 4), 0 elsewhere; with clip_frames >= 0, a counts as 0 outside [f0 - clip_frames, f1 + clip_frames).
+ * NaN where undefined (init tokens, eos, no reference, a zero norm).  Computed on the device: the rows are never copied out.
+ * On return, success or not, the context's own alignment heads are back in place and no alignment rows are retained
+ * (cw_token_timestamps / cw_get_alignment are refused until the next decode).
+ * CW_ERR_INVALID, before any device work: what cw_align_tokens refuses, n_heads < 1, a pair outside the decoder's layers x
+ * heads, a pair given twice, exactly one of ref_begin / ref_end null, a capture above CW_ALIGN_HEADS_MAX_BYTES.            */
+#define CW_ALIGN_HEADS_MAX_BYTES (8ull << 30)
+int32_t cw_align_heads(cw_ctx* ctx, int32_t nb, const int32_t* num_frames, const int32_t* ids, int32_t ids_stride,
+                       const int32_t* n_ids, int32_t n_init, int32_t n_heads, const int32_t* layers, const int32_t* heads,
+                       float* token_ts, const float* ref_begin, const float* ref_end, int32_t clip_frames, float* similarity);
+/* cw_align_heads_times: wall milliseconds of the last cw_align_heads' parts, the stream drained between them: ms[0] forward,
+ * [1] normalisation of the rows, [2] similarity (upload, kernel, download; 0 without references), [3] per-head timestamps,
+ * [4] the similarity kernel alone (device events).  ms holds 5 floats.                                                       */
+int32_t cw_align_heads_times(cw_ctx* ctx, float* ms);
+/* cw_test_align_similarity: cw_align_heads' similarity kernel, through the same launcher, on caller-supplied normalised rows
+ * attn [B][Ha][N][S] (S a multiple of 4), n_cols [B] <= S, ref_begin / ref_end [B][N] -> out [Ha][B][N].                   */
+int32_t cw_test_align_similarity(cw_ctx* ctx, const float* attn, int32_t B, int32_t Ha, int32_t N, int32_t S,
+                                 const int32_t* n_cols, const float* ref_begin, const float* ref_end, int32_t clip_frames,
+                                 float* out);
+
 /* cw_score_tokens: teacher-forced log-probabilities of known token sequences.  rows = n_items * rows_per_item decoder rows,
  * row r scored against resident feature item r / rows_per_item (several candidate texts of one clip share its encoder pass).
  * ids rows are whole decoder inputs exactly as cw_align_tokens takes them (init tokens, text, eos).  Written at index k =

@@ -5,9 +5,12 @@ after one mel, transcripts of --tokens text ids each (decoder input = 3 init tok
                     last alignment layer, timestamps row by row; the split comes from the engine's stage timers
   align (loop)      the same call with cw_set_option "align_prefill" = 0: the forward through the per-position decoder step
   transcribe        cw_transcribe of the same clips, greedy, --tokens forced-length tokens (bench.py's decode)
+  --heads all       cw_align_heads over every (layer, head) of the decoder with reference intervals, after the rows above: the
+                    call's own split (forward, normalise, similarity, per-head timestamps; cw_align_heads_times), the similarity
+                    kernel's bytes/s, and one cw_align_tokens call per head extrapolated from the measured row above
 
 Best of --reps after one warm-up, wall time around the call with the stream synchronised.
-usage: python tools/align_bench.py [--dtype bf16] [--tokens 128] [--reps 5] [--only-forward]"""
+usage: python tools/align_bench.py [--dtype bf16] [--tokens 128] [--reps 5] [--only-forward] [--heads all]"""
 import argparse, json, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
@@ -35,6 +38,7 @@ def main():
     ap.add_argument("--dtype", default="bf16"); ap.add_argument("--tokens", type=int, default=128)
     ap.add_argument("--items", type=int, default=8); ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--only-forward", action="store_true", help="one prefill align call only (for a kernel trace)")
+    ap.add_argument("--heads", choices=["all"], default=None, help="also time cw_align_heads over every decoder head")
     a = ap.parse_args()
     g, v = syn.large_v3_geometry()
     spec = syn.model_spec(g, v, n_align=15)
@@ -59,6 +63,30 @@ def main():
     out["transcribe_ms"], out["transcribe_split_ms"] = timed(
         eng, lambda: eng.transcribe(B, nf, sot=v.sot, language_token=v.lang_id("en"), task_token=v.transcribe,
                                     max_new_tokens=a.tokens, min_new_tokens=a.tokens), max(1, a.reps // 2))
+    if a.heads == "all":
+        heads = [[l, h] for l in range(g.dec_layers) for h in range(g.heads)]
+        n_tok = [len(r) for r in ids]
+        # reference intervals along the synthetic ridge (token t spoken at frame 11 t), 0.2 s long
+        begin = [np.where(np.arange(n) >= 3, np.arange(n) * syn.ALIGNED_FRAMES_PER_TOKEN * 0.02, np.nan).astype(np.float32) for n in n_tok]
+        end = [(b + 0.2).astype(np.float32) for b in begin]
+        best = None
+        for r in range(max(1, a.reps // 2) + 1):
+            eng.sync()
+            t0 = time.perf_counter()
+            eng.align_heads(nf, ids, 3, heads, ref=(begin, end), clip_frames=200)
+            eng.sync()
+            dt = (time.perf_counter() - t0) * 1e3
+            if r > 0 and (best is None or dt < best[0]):
+                best = (dt, eng.align_heads_times())
+        rows = B * len(heads) * (max(n_tok) - 1)
+        out["align_heads"] = {"heads": len(heads), "total_ms": round(best[0], 3), "split_ms": {k: round(v, 3) for k, v in best[1].items()},
+                              "capture_bytes": rows * 6000, "similarity_rows": rows,
+                              # rows with a reference (every text token) read their n_cols = 1500 frames once
+                              "similarity_kernel_TBps": round(len(heads) * sum(n - 4 for n in n_tok) * 6000 / (best[1]["similarity_kernel"] * 1e-3) / 1e12, 3),
+                              # what one cw_align_tokens call per head would cost: an extrapolation from the measured
+                              # 15-head call above (a single-head call runs the same encoder and, for a head in the last
+                              # alignment layer, the same forward)
+                              "extrapolated_single_head_calls_ms": round(out["align_prefill_ms"] * len(heads), 1)}
     print(json.dumps(out))
     eng.close()
 
