@@ -128,6 +128,10 @@ _SIGS = {
     "cw_align_heads": (_I, [_P, _I, _P, _P, _I, _P, _I, _I, _P, _P, _P, _P, _P, _I, _P]),
     "cw_align_heads_times": (_I, [_P, _P]),
     "cw_test_align_similarity": (_I, [_P, _P, _I, _I, _I, _I, _P, _P, _P, _I, _P]),
+    "cw_set_alignment_scores": (_I, [_P, _I, _I]),
+    "cw_get_alignment_scores": (_I, [_P, _P, _P, _I, _I]),
+    "cw_get_transcribe_alignment_scores": (_I, [_P, _P, _P, _I, _I]),
+    "cw_test_align_path_scores": (_I, [_P, _P, _I, _I, _I, _I, _P, _P, _I, _P, _P]),
     "cw_score_tokens": (_I, [_P, _I, _I, _P, _I, _P, _I, _P, _P, _P]),
     "cw_align_score_tokens": (_I, [_P, _I, _P, _P, _I, _P, _I, _P, _P, _P, _P]),
     "cw_score_prefill_runs": (_I, [_P]),

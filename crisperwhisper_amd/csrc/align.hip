@@ -9,6 +9,8 @@
 //                        (:89-115) that also emits, per token row, the first frame of its run (= jump
 //                        time / 0.02 s, :368-369)
 //   pauses_kernel        REF/utils.py:8-26: per-boundary pause redistribution (boundaries independent)
+//   align_path_score_kernel  (cw_set_alignment_scores) per token row, the share of the heads' attention inside the frames the
+//                        path gave the token, and the attention's spread in seconds
 #include <limits.h>
 #include <stdlib.h>
 #include "common.h"
@@ -345,6 +347,112 @@ int cw_launch_align_similarity(const float* w, int B, int Ha, int rows_cap, int 
     if ((rows + SIM_WAVES - 1) / SIM_WAVES > 0x7fffffffLL) return CW_ERR_INVALID;
     hipLaunchKernelGGL(align_similarity_kernel, dim3((unsigned)((rows + SIM_WAVES - 1) / SIM_WAVES)), dim3(64 * SIM_WAVES), 0, st,
                        w, B, Ha, rows_cap, S, row0, N, n_cols, ref_begin, ref_end, clip, out);
+    return CW_OK;
+}
+
+// Alignment scores: how much of the alignment heads' attention lies where the DTW path put a token, and how diffuse it is.
+// For token row t of sequence b, with M = n_cols[b] frames, lo = first_col[b][t], hi = max(lo + 1, first_col[b][t + 1])
+// (M behind the last row) and the window [max(0, lo - collar), min(M, hi + collar)):
+//     T_h = sum_j w_h[j]      mass = mean_h(sum_{j in window} w_h[j] / T_h)      mu = mean_h(sum_j w_h[j] j / T_h)
+//     spread = 0.02 s * sqrt(mean_h(sum_j w_h[j] (j - mu)^2 / T_h))
+// over frames j < M only (the rows hold stale data behind M: selected away, never multiplied); NaN for M <= 0, lo < 0 or a
+// T_h of 0.  One wave per (sequence, token row), APS_WAVES rows per block, two passes over the Ha rows (6 KB each, L2-resident
+// after the first): pass one forms T_h, the windowed sum and the first moment, pass two T_h again (same order, same bits) and
+// the second moment about mu.  Lane l owns the float4 chunks l, l + 64, ...: a chunk's terms are added as (p0 + p1) + (p2 + p3)
+// and to the lane's running sum in chunk order, then the six fixed DPP steps of wave_sum_f64, then the heads in index order --
+// no atomics, nothing shared between waves, so a row's result is bit-identical run to run and whatever else is in the batch.
+// The sums are float64: with at most 1500 non-negative terms their error is ~1e-13 relative, far inside the f32 result's
+// last place, and a one-hot row gives mass 1 / spread 0 exactly.  No arrays indexed at run time: no scratch.
+// w [B][Ha][rows_cap][S] (S % 4 == 0, 16-byte aligned rows), token rows row0 .. row0 + N - 1; first_col, mass, spread [B][N].
+template <int CTRL, int ROW_MASK>
+__device__ inline double dpp_mov_f64(double v) {                 // lanes without a source (and rows outside the mask) read 0.0
+    const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(v), CTRL, ROW_MASK, 0xf, false);
+    const int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(v), CTRL, ROW_MASK, 0xf, false);
+    return __hiloint2double(hi, lo);
+}
+__device__ inline double wave_sum_f64(double v) {                // wave_sum (common.h) on two dwords per step
+    v += dpp_mov_f64<0x111, 0xf>(v);
+    v += dpp_mov_f64<0x112, 0xf>(v);
+    v += dpp_mov_f64<0x114, 0xf>(v);
+    v += dpp_mov_f64<0x118, 0xf>(v);
+    v += dpp_mov_f64<0x142, 0xa>(v);
+    v += dpp_mov_f64<0x143, 0xc>(v);
+    return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), 63), __builtin_amdgcn_readlane(__double2loint(v), 63));
+}
+
+#define APS_WAVES 4
+__global__ __launch_bounds__(64 * APS_WAVES) void align_path_score_kernel(
+    const float* __restrict__ w, int B, int Ha, int rows_cap, int S, int row0, int N, const int* __restrict__ n_cols,
+    const int* __restrict__ first_col, int collar, float* __restrict__ mass, float* __restrict__ spread) {
+    const int lane = threadIdx.x & 63;
+    const long long r = (long long)blockIdx.x * APS_WAVES + (threadIdx.x >> 6);
+    if (r >= (long long)B * N) return;                            // uniform per wave
+    const int t = (int)(r % N), b = (int)(r / N);
+    const size_t o = (size_t)b * N + t;
+    const int M = min(n_cols[b], S);
+    const int lo = first_col[o];
+    if (M <= 0 || lo < 0) { if (lane == 0) { mass[o] = NAN; spread[o] = NAN; } return; }
+    const int nxt = t + 1 < N ? first_col[o + 1] : M;
+    const int hi = max(min(lo, S) + 1, min(nxt, S));              // (a path frame is below M <= S; the clamps keep the sums in int)
+    const int cl = min(collar, 1 << 20);
+    const int w0 = max(0, lo - cl), w1 = min(M, hi + cl);
+    double mass_acc = 0.0, mu_acc = 0.0;
+    bool dead = false;                                            // a head with T_h == 0 (uniform: every lane holds the wave's sums)
+    for (int a = 0; a < Ha; ++a) {
+        const float4* row = (const float4*)(w + (((size_t)b * Ha + a) * rows_cap + row0 + t) * S);
+        double T = 0.0, W = 0.0, M1 = 0.0;
+        for (int c = lane; 4 * c < M; c += 64) {
+            const float4 v4 = row[c];
+            const float v[4] = {v4.x, v4.y, v4.z, v4.w};
+            double pt[4], pw[4], pm[4];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const int j = 4 * c + k;
+                const double x = j < M ? (double)v[k] : 0.0;
+                pt[k] = x; pw[k] = (j >= w0 && j < w1) ? x : 0.0; pm[k] = x * (double)j;
+            }
+            T += (pt[0] + pt[1]) + (pt[2] + pt[3]);
+            W += (pw[0] + pw[1]) + (pw[2] + pw[3]);
+            M1 += (pm[0] + pm[1]) + (pm[2] + pm[3]);
+        }
+        T = wave_sum_f64(T); W = wave_sum_f64(W); M1 = wave_sum_f64(M1);
+        dead = dead || T == 0.0;
+        mass_acc += W / T; mu_acc += M1 / T;
+    }
+    const double mu = mu_acc / (double)Ha;
+    double var_acc = 0.0;
+    for (int a = 0; a < Ha; ++a) {
+        const float4* row = (const float4*)(w + (((size_t)b * Ha + a) * rows_cap + row0 + t) * S);
+        double T = 0.0, V = 0.0;
+        for (int c = lane; 4 * c < M; c += 64) {
+            const float4 v4 = row[c];
+            const float v[4] = {v4.x, v4.y, v4.z, v4.w};
+            double pt[4], pv[4];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const int j = 4 * c + k;
+                const double x = j < M ? (double)v[k] : 0.0, d = (double)j - mu;
+                pt[k] = x; pv[k] = x * (d * d);
+            }
+            T += (pt[0] + pt[1]) + (pt[2] + pt[3]);
+            V += (pv[0] + pv[1]) + (pv[2] + pv[3]);
+        }
+        T = wave_sum_f64(T); V = wave_sum_f64(V);
+        var_acc += V / T;
+    }
+    if (lane == 0) {
+        mass[o] = dead ? NAN : (float)(mass_acc / (double)Ha);
+        spread[o] = dead ? NAN : (float)(0.02 * sqrt(var_acc / (double)Ha));
+    }
+}
+
+int cw_launch_align_path_score(const float* w, int B, int Ha, int rows_cap, int S, int row0, int N, const int* n_cols,
+                               const int* first_col, int collar, float* mass, float* spread, hipStream_t st) {
+    if (B < 1 || Ha < 1 || N < 1 || S < 4 || S % 4 || row0 < 0 || row0 + N > rows_cap || collar < 0) return CW_ERR_INVALID;
+    const long long rows = (long long)B * N;
+    if ((rows + APS_WAVES - 1) / APS_WAVES > 0x7fffffffLL) return CW_ERR_INVALID;
+    hipLaunchKernelGGL(align_path_score_kernel, dim3((unsigned)((rows + APS_WAVES - 1) / APS_WAVES)), dim3(64 * APS_WAVES), 0, st,
+                       w, B, Ha, rows_cap, S, row0, N, n_cols, first_col, collar, mass, spread);
     return CW_OK;
 }
 

@@ -208,6 +208,12 @@ struct cw_ctx {
     unsigned char* d_trace = nullptr;
     int *d_first_col = nullptr, *d_path_text = nullptr, *d_path_time = nullptr, *d_path_len = nullptr,
         *d_ncols = nullptr;
+    // alignment scores (cw_set_alignment_scores): the path-score kernel behind every DTW of the timestamp stage
+    bool as_on = false;
+    int as_collar = 0;
+    float *d_as_mass = nullptr, *d_as_spread = nullptr;       // [Bm][max_target] per (sequence, token row) of the last DTW launch
+    std::vector<std::vector<float>> as_mass, as_spread;       // rows of the last timestamp stage, each [L + 1] in cw_token_timestamps' indexing
+    std::vector<std::vector<float>> tr_as_mass, tr_as_spread; // ... of the last cw_transcribe, per item, aligned with its tokens
 
     double* d_pause = nullptr;   // persistent scratch for cw_adjust_pauses: [4][pause_cap]
     int pause_cap = 0;
@@ -1999,6 +2005,56 @@ int32_t cw_get_transcribe_top_logprobs(cw_ctx* c, int32_t* ids_out, float* lp_ou
     return CW_OK;
 }
 
+// ---- alignment scores: attention mass on the DTW path and attention spread per token (include/crisperwhisper.h) ------------
+int32_t cw_set_alignment_scores(cw_ctx* c, int32_t on, int32_t collar_frames) {
+    if (collar_frames < 0) return fail(c, CW_ERR_INVALID, "set_alignment_scores: collar_frames=%d is negative", collar_frames);
+    const bool want = on != 0;
+    // switching off, or repeating the setting in force, changes nothing and is always accepted: a caller that sets the switch
+    // before every decode must not trip over a search that an interrupted caller left open (the next decode closes it)
+    if (!want && !c->as_on) return CW_OK;
+    if (want && c->as_on && collar_frames == c->as_collar) return CW_OK;
+    if (want && c->beam_K > 0) return fail(c, CW_ERR_STATE, "set_alignment_scores: a beam search is open");
+    if (want && !c->d_as_mass) {
+        const size_t n = (size_t)c->Bm * c->d.max_target_positions;
+        CWCHK(c, dmalloc(c, &c->d_as_mass, n * 4, false));
+        CWCHK(c, dmalloc(c, &c->d_as_spread, n * 4, false));
+    }
+    if (want != c->as_on || (want && collar_frames != c->as_collar)) {   // nothing aligned under this setting yet
+        c->as_mass.clear(); c->as_spread.clear();
+        c->tr_as_mass.clear(); c->tr_as_spread.clear();
+    }
+    c->as_on = want;
+    if (want) c->as_collar = collar_frames;
+    return CW_OK;
+}
+int32_t cw_get_alignment_scores(cw_ctx* c, float* mass, float* spread, int32_t nb, int32_t L) {
+    if (!c->as_on) return fail(c, CW_ERR_STATE, "alignment scores are off (cw_set_alignment_scores)");
+    if (!mass || !spread) return fail(c, CW_ERR_INVALID, "get_alignment_scores: null argument");
+    if (nb < 1 || (size_t)nb > c->as_mass.size() || L < 0)
+        return fail(c, CW_ERR_STATE, "get_alignment_scores: asked %d x %d, the last timestamp stage scored %d rows", nb, L, (int)c->as_mass.size());
+    for (int b = 0; b < nb; ++b) {
+        const size_t n = c->as_mass[b].size();
+        if (n > (size_t)L + 1) return fail(c, CW_ERR_STATE, "get_alignment_scores: row %d holds %d positions, asked L=%d", b, (int)n - 1, L);
+        memcpy(mass + (size_t)b * (L + 1), c->as_mass[b].data(), n * 4);
+        memcpy(spread + (size_t)b * (L + 1), c->as_spread[b].data(), n * 4);
+        for (size_t k = n; k <= (size_t)L; ++k) { mass[(size_t)b * (L + 1) + k] = NAN; spread[(size_t)b * (L + 1) + k] = NAN; }
+    }
+    return CW_OK;
+}
+int32_t cw_get_transcribe_alignment_scores(cw_ctx* c, float* mass, float* spread, int32_t B, int32_t cap) {
+    if (!c->as_on) return fail(c, CW_ERR_STATE, "alignment scores are off (cw_set_alignment_scores)");
+    if (!mass || !spread || B < 1 || (size_t)B != c->tr_as_mass.size())
+        return fail(c, CW_ERR_STATE, "get_transcribe_alignment_scores: B=%d but the last cw_transcribe had %d items", B, (int)c->tr_as_mass.size());
+    for (int i = 0; i < B; ++i) {
+        const int n = (int)c->tr_as_mass[i].size();
+        if (n > cap) return fail(c, CW_ERR_INVALID, "item %d holds %d tokens, capacity %d", i, n, cap);
+        memcpy(mass + (size_t)i * cap, c->tr_as_mass[i].data(), (size_t)n * 4);
+        memcpy(spread + (size_t)i * cap, c->tr_as_spread[i].data(), (size_t)n * 4);
+        for (int k = n; k < cap; ++k) { mass[(size_t)i * cap + k] = NAN; spread[(size_t)i * cap + k] = NAN; }
+    }
+    return CW_OK;
+}
+
 // ---- sequence_bias: phrase boosting inside the sampler kernels (include/crisperwhisper.h) ------------------------------------
 // Checks the caller's table and lays it out as the kernels read it (kernels.h): entries ordered by last token, for one last token
 // the length-1 entry first and the longer ones in the caller's order, plus the entry range of each of the 16 vocabulary slices of
@@ -2320,6 +2376,7 @@ static int token_timestamps(cw_ctx* c, const float* w, int32_t nb, int32_t L, in
 int32_t cw_token_timestamps(cw_ctx* c, int32_t nb, int32_t L, int32_t n_prompt, const int32_t* num_frames, float* ts_out) {
     if (c->d.n_align <= 0) return fail(c, CW_ERR_STATE, "no alignment heads configured");
     if (nb < 1 || nb > c->last_nb || L != c->last_L) return fail(c, CW_ERR_STATE, "rows retained: %d x %d, asked %d x %d", c->last_nb, c->last_L, nb, L);
+    c->as_mass.clear(); c->as_spread.clear();
     return token_timestamps(c, nullptr, nb, L, n_prompt, num_frames, ts_out);
 }
 
@@ -2342,8 +2399,10 @@ static void timestamp_ncols(int nb, const int32_t* num_frames, std::vector<int>&
 
 // stats -> filter -> DTW of nseq sequences (nseq <= max_batch) of N token rows each: w [nseq][Ha][rows_cap][S], token rows
 // row0 .. row0 + N - 1, ncols[q] frames.  w null: the retained rows.  fc [nseq][N]: first frame of every token's run.
+// sc non-null with cw_set_alignment_scores on: the path-score kernel runs behind the DTW on the rows and first columns it just
+// produced (both stay on the device), and sc receives mass [nseq][N] followed by spread [nseq][N].
 static int timestamp_first_cols(cw_ctx* c, const float* w, int nseq, int Ha, int rows_cap, int row0, int N, const int* ncols,
-                                std::vector<int>& fc) {
+                                std::vector<int>& fc, std::vector<float>* sc = nullptr) {
     const int S = CW_N_CTX;
     HIPCHK(c, hipMemcpyAsync(c->d_ncols, ncols, nseq * 4, hipMemcpyHostToDevice, c->st));
     HIPCHK(c, hipStreamSynchronize(c->st));
@@ -2369,10 +2428,19 @@ static int timestamp_first_cols(cw_ctx* c, const float* w, int nseq, int Ha, int
         }
     }
     CWCHK(c, cw_launch_dtw(c->d_mat, nseq, N, S, c->d_ncols, c->d_trace, c->d_first_col, c->dtw_block ? c->d_path_text : nullptr, c->dtw_block ? c->d_path_time : nullptr, c->d_path_len, c->st, c->dtw_block ? nullptr : c->d_skew));
+    const bool scores = sc && c->as_on;
+    if (scores)
+        CWCHK(c, cw_launch_align_path_score(w, nseq, Ha, rows_cap, S, row0, N, c->d_ncols, c->d_first_col, c->as_collar, c->d_as_mass,
+                                            c->d_as_spread, c->st));
     KCHK(c);
     tm.stop();
     fc.resize((size_t)nseq * N);
     HIPCHK(c, hipMemcpy(fc.data(), c->d_first_col, fc.size() * 4, hipMemcpyDeviceToHost));
+    if (scores) {
+        sc->resize((size_t)2 * nseq * N);
+        HIPCHK(c, hipMemcpy(sc->data(), c->d_as_mass, (size_t)nseq * N * 4, hipMemcpyDeviceToHost));
+        HIPCHK(c, hipMemcpy(sc->data() + (size_t)nseq * N, c->d_as_spread, (size_t)nseq * N * 4, hipMemcpyDeviceToHost));
+    }
     return CW_OK;
 }
 
@@ -2381,10 +2449,23 @@ static int token_timestamps(cw_ctx* c, const float* w, int32_t nb, int32_t L, in
     const int Ha = c->d.n_align, TGT = c->d.max_target_positions;
     for (size_t i = 0; i < (size_t)nb * (L + 1); ++i) ts_out[i] = 0.f;
     const int N = L - n_prompt;
+    // alignment scores: one row of L + 1 per sequence, appended to the rows of this timestamp stage (its caller cleared them);
+    // NaN wherever no token row was scored (prompt positions, the eos slot, N <= 0)
+    const size_t as0 = c->as_mass.size();
+    if (c->as_on) {
+        c->as_mass.resize(as0 + nb, std::vector<float>((size_t)L + 1, NAN));
+        c->as_spread.resize(as0 + nb, std::vector<float>((size_t)L + 1, NAN));
+    }
     if (N <= 0) return CW_OK;                     // generation_whisper.py:336-338
     std::vector<int> ncols, fc;
+    std::vector<float> sc;
     timestamp_ncols(nb, num_frames, ncols);
-    CWCHK(c, timestamp_first_cols(c, w, nb, Ha, TGT, n_prompt, N, ncols.data(), fc));
+    CWCHK(c, timestamp_first_cols(c, w, nb, Ha, TGT, n_prompt, N, ncols.data(), fc, &sc));
+    if (c->as_on)
+        for (int b = 0; b < nb; ++b) {
+            memcpy(c->as_mass[as0 + b].data() + n_prompt, sc.data() + (size_t)b * N, (size_t)N * 4);
+            memcpy(c->as_spread[as0 + b].data() + n_prompt, sc.data() + ((size_t)nb + b) * N, (size_t)N * 4);
+        }
     for (int b = 0; b < nb; ++b) {
         float* ts = ts_out + (size_t)b * (L + 1);
         for (int i = 0; i < N; ++i) {
@@ -2470,10 +2551,11 @@ int32_t cw_transcribe_prompted(cw_ctx* c, int32_t B, const int32_t* num_frames, 
     if (max_length <= n_prompt) return fail(c, CW_ERR_INVALID, "max_length %d leaves no room after %d decoder input tokens", max_length, n_prompt);
     std::vector<long> seek(B, 0);
     std::vector<std::vector<int>> out_tok(B);
-    std::vector<std::vector<float>> out_ts(B), out_lp(B), out_tl(B);
+    std::vector<std::vector<float>> out_ts(B), out_lp(B), out_tl(B), out_am(B), out_as(B);
     std::vector<std::vector<int>> out_ti(B);
     c->tr_lp.clear();
     c->tr_top_id.clear(); c->tr_top_lp.clear();
+    c->tr_as_mass.clear(); c->tr_as_spread.clear();
     const int top_k = c->tok_lp_on ? c->top_k : 0;
     int passes = 0;
     for (;;) {
@@ -2536,6 +2618,10 @@ int32_t cw_transcribe_prompted(cw_ctx* c, int32_t B, const int32_t* num_frames, 
                 out_tok[i].push_back(s[k]);
                 out_ts[i].push_back(ts[(size_t)r * (L + 1) + n_prompt + k] + off32);
                 if (c->tok_lp_on) out_lp[i].push_back(tlp[(size_t)r * TGT + n_prompt + k]);
+                if (c->as_on) {                                                        // (rows of the cw_token_timestamps above)
+                    out_am[i].push_back(c->as_mass[r][n_prompt + k]);
+                    out_as[i].push_back(c->as_spread[r][n_prompt + k]);
+                }
                 if (top_k > 0) {
                     const size_t o = ((size_t)r * TGT + n_prompt + k) * top_k;
                     out_ti[i].insert(out_ti[i].end(), tti.begin() + o, tti.begin() + o + top_k);
@@ -2554,6 +2640,7 @@ int32_t cw_transcribe_prompted(cw_ctx* c, int32_t B, const int32_t* num_frames, 
     }
     if (c->tok_lp_on) c->tr_lp = std::move(out_lp);
     if (top_k > 0) { c->tr_top_id = std::move(out_ti); c->tr_top_lp = std::move(out_tl); }
+    if (c->as_on) { c->tr_as_mass = std::move(out_am); c->tr_as_spread = std::move(out_as); }
     if (n_passes) *n_passes = passes;
     return CW_OK;
 }
@@ -2597,6 +2684,7 @@ static int forced_rows_timestamps(cw_ctx* c, int nb, const int32_t* num_frames, 
     CWCHK(c, normalize_alignment(c));
     const float* w0 = c->align_cur ? c->align_cur : c->d_align;
     std::vector<float> ts;
+    c->as_mass.clear(); c->as_spread.clear();     // (every group below appends its rows: row b ends up at index b)
     for (int b0 = 0, b1; b0 < nb; b0 = b1) {
         for (b1 = b0 + 1; b1 < nb && n_ids[b1] == n_ids[b0]; ++b1) {}
         const int L = n_ids[b0] - 1, n = b1 - b0;
@@ -2864,6 +2952,35 @@ int32_t cw_test_align_similarity(cw_ctx* c, const float* attn, int32_t B, int32_
     KCHK(c);
     HIPCHK(c, hipStreamSynchronize(c->st));
     HIPCHK(c, hipMemcpy(out, dout.p, no * 4, hipMemcpyDeviceToHost));
+    return CW_OK;
+}
+
+// cw_test_align_path_scores: the path-score kernel, through the timestamp stage's launcher, on caller-supplied rows.
+int32_t cw_test_align_path_scores(cw_ctx* c, const float* attn, int32_t B, int32_t Ha, int32_t N, int32_t S, const int32_t* n_cols,
+                                  const int32_t* first_col, int32_t collar_frames, float* mass, float* spread) {
+    if (!attn || !n_cols || !first_col || !mass || !spread) return fail(c, CW_ERR_INVALID, "test_align_path_scores: null argument");
+    if (B < 1 || Ha < 1 || N < 1 || S < 4 || S % 4 || (size_t)B * Ha * N * S > ((size_t)1 << 28))
+        return fail(c, CW_ERR_INVALID, "test_align_path_scores: B=%d Ha=%d N=%d S=%d unsupported (S a multiple of 4, at most 2^28 elements)", B, Ha, N, S);
+    if (collar_frames < 0) return fail(c, CW_ERR_INVALID, "test_align_path_scores: collar_frames=%d is negative", collar_frames);
+    for (int b = 0; b < B; ++b) {
+        if (n_cols[b] < 0 || n_cols[b] > S) return fail(c, CW_ERR_INVALID, "test_align_path_scores: n_cols[%d]=%d outside 0 .. %d", b, n_cols[b], S);
+        for (int i = 0; i < N; ++i)
+            if (first_col[(size_t)b * N + i] > S) return fail(c, CW_ERR_INVALID, "test_align_path_scores: first_col[%d][%d]=%d above %d", b, i, first_col[(size_t)b * N + i], S);
+    }
+    DevBuf dw, dn, df, dm, ds;
+    const size_t nw = (size_t)B * Ha * N * S, nr = (size_t)B * N;
+    if (dw.alloc(nw * 4) != hipSuccess || dn.alloc((size_t)B * 4) != hipSuccess || df.alloc(nr * 4) != hipSuccess ||
+        dm.alloc(nr * 4) != hipSuccess || ds.alloc(nr * 4) != hipSuccess)
+        return fail(c, CW_ERR_NOMEM, "test_align_path_scores: hipMalloc failed");
+    HIPCHK(c, hipMemcpy(dw.p, attn, nw * 4, hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemcpy(dn.p, n_cols, (size_t)B * 4, hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemcpy(df.p, first_col, nr * 4, hipMemcpyHostToDevice));
+    CWCHK(c, cw_launch_align_path_score((const float*)dw.p, B, Ha, N, S, 0, N, (const int*)dn.p, (const int*)df.p, collar_frames,
+                                        (float*)dm.p, (float*)ds.p, c->st));
+    KCHK(c);
+    HIPCHK(c, hipStreamSynchronize(c->st));
+    HIPCHK(c, hipMemcpy(mass, dm.p, nr * 4, hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(spread, ds.p, nr * 4, hipMemcpyDeviceToHost));
     return CW_OK;
 }
 

@@ -468,6 +468,9 @@ int cw_launch_align_filter(const float* w, int B, int Ha, int rows_cap, int S, i
 // reference interval ref_begin / ref_end [B][N] (seconds, NaN = none); clip < 0: no clipping
 int cw_launch_align_similarity(const float* w, int B, int Ha, int rows_cap, int S, int row0, int N, const int* n_cols,
                                const float* ref_begin, const float* ref_end, int clip, float* out, hipStream_t st);
+// alignment scores of the rows the DTW just walked (align.hip: align_path_score_kernel): mass / spread [B][N]
+int cw_launch_align_path_score(const float* w, int B, int Ha, int rows_cap, int S, int row0, int N, const int* n_cols,
+                               const int* first_col, int collar, float* mass, float* spread, hipStream_t st);
 // skew: workspace of cw_dtw_skew_floats(B, N, S) floats (null: round-1 block kernel)
 size_t cw_dtw_skew_floats(int B, int N, int S);
 int cw_launch_dtw(const float* mat, int B, int N, int S, const int* n_cols, unsigned char* trace, int* first_col,

@@ -82,6 +82,30 @@ def unpack_record(rec: np.ndarray):
     return idx, tokens, ts, stride
 
 
+REC_ALIGN_WORDS = 2 * REC_TOKENS             # alignment scores behind a record of any width: one f32 mass, then one f32 spread per token
+
+
+def append_alignment(rec: np.ndarray, mass, spread) -> np.ndarray:
+    """``rec`` (a ``pack_record`` of any width) followed by the chunk's per-token alignment scores.  The record itself is
+    unchanged; both ends of the gather know from the call's arguments that the tail is there."""
+    nt = int(rec[1])
+    mass, spread = np.asarray(mass, dtype=np.float32), np.asarray(spread, dtype=np.float32)
+    if mass.shape != (nt,) or spread.shape != (nt,):
+        raise ValueError(f"alignment scores of shape {mass.shape} / {spread.shape} for {nt} tokens")
+    tail = np.zeros(REC_ALIGN_WORDS, dtype=np.int32)
+    tail[:nt] = mass.view(np.int32)
+    tail[REC_TOKENS:REC_TOKENS + nt] = spread.view(np.int32)
+    return np.concatenate([rec, tail])
+
+
+def split_alignment(rec: np.ndarray):
+    """(the record ``append_alignment`` was given, mass [n_tok] f32, spread [n_tok] f32)."""
+    if len(rec) < REC_WORDS + REC_ALIGN_WORDS:
+        raise ValueError(f"a record of {len(rec)} words carries no alignment scores")
+    nt, o = int(rec[1]), len(rec) - REC_ALIGN_WORDS
+    return rec[:o], rec[o:o + nt].view(np.float32).copy(), rec[o + REC_TOKENS:o + REC_TOKENS + nt].view(np.float32).copy()
+
+
 WORD_MAX = 448
 WORD_TEXT_BYTES = 4096
 WORD_REC = 3 + 4 * WORD_MAX + WORD_TEXT_BYTES // 4   # chunk_idx, n_words, n_text_bytes, (start,end) f64 bits, utf-8 text

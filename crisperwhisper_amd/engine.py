@@ -103,6 +103,7 @@ class Engine:
             begin_suppress_tokens=bsup.ctypes.data_as(C.POINTER(C.c_int32)), n_begin_suppress=len(bsup))
         self._chk(self.lib.cw_set_generation(self.ctx, C.byref(cfg)))
         self._capture = None
+        self.alignment_scores_on = False                # what set_alignment_scores last set (generation.set_alignment_scores reads it)
         if cross_kv_dtype not in (None, "bf16", "f32", "fp8"):
             raise ValueError(f"cross_kv_dtype must be None or 'fp8', got {cross_kv_dtype!r}")
         if cross_kv_dtype == "fp8":
@@ -338,6 +339,48 @@ class Engine:
         lp = np.empty((nb, cap, k), np.float32)
         self._chk(self.lib.cw_get_transcribe_top_logprobs(self.ctx, _ptr(ids), _ptr(lp), nb, cap))
         return ([ids[i, :int(n)].copy() for i, n in enumerate(lens)], [lp[i, :int(n)].copy() for i, n in enumerate(lens)])
+
+    def set_alignment_scores(self, on: bool, collar_frames: int = 0):
+        """Alignment scores of every timestamp stage (``cw_set_alignment_scores``); off by default.  ``collar_frames`` >= 0
+        widens every token's window of path frames by that many 20 ms frames on either side.  Switching it on (or changing the
+        collar) is refused while a beam search is open; switching it off never is."""
+        self._chk(self.lib.cw_set_alignment_scores(self.ctx, 1 if on else 0, int(collar_frames)))
+        self.alignment_scores_on = bool(on)
+
+    def alignment_scores(self, nb: int, L: int):
+        """(mass, spread), both [nb, L + 1] float32 in ``token_timestamps``' indexing, of the last timestamp stage: the share of
+        the alignment heads' attention inside the frames the DTW path gave each token, and the attention's spread in seconds; NaN
+        at prompt positions, in the eos slot and behind a row's end (``cw_get_alignment_scores``)."""
+        mass = np.empty((nb, L + 1), np.float32)
+        spread = np.empty((nb, L + 1), np.float32)
+        self._chk(self.lib.cw_get_alignment_scores(self.ctx, _ptr(mass), _ptr(spread), nb, L))
+        return mass, spread
+
+    def transcribe_alignment_scores(self, lens):
+        """The alignment scores of the last ``transcribe``: (mass, spread), each one float32 array per item aligned with its
+        tokens (``lens`` = their counts; ``cw_get_transcribe_alignment_scores``)."""
+        nb = len(lens)
+        cap = max(1, max((int(n) for n in lens), default=1))
+        mass = np.empty((nb, cap), np.float32)
+        spread = np.empty((nb, cap), np.float32)
+        self._chk(self.lib.cw_get_transcribe_alignment_scores(self.ctx, _ptr(mass), _ptr(spread), nb, cap))
+        return ([mass[i, :int(n)].copy() for i, n in enumerate(lens)], [spread[i, :int(n)].copy() for i, n in enumerate(lens)])
+
+    def test_align_path_scores(self, attn, n_cols, first_col, collar_frames: int):
+        """cw_test_align_path_scores: the alignment-score kernel on rows attn [B][Ha][N][S] (S a multiple of 4), n_cols [B],
+        first_col [B][N] -> (mass, spread), both [B][N]."""
+        a = np.ascontiguousarray(attn, dtype=np.float32)
+        if a.ndim != 4:
+            raise ValueError("test_align_path_scores: attn must be [B][Ha][N][S]")
+        B, Ha, Nn, S = a.shape
+        nc, fc = _i32(n_cols), _i32(first_col)
+        if nc.shape != (B,) or fc.shape != (B, Nn):
+            raise ValueError("test_align_path_scores: shapes do not agree")
+        mass = np.zeros((B, Nn), dtype=np.float32)
+        spread = np.zeros((B, Nn), dtype=np.float32)
+        self._chk(self.lib.cw_test_align_path_scores(self.ctx, _ptr(a), B, Ha, Nn, S, _ptr(nc), _ptr(fc), int(collar_frames),
+                                                     _ptr(mass), _ptr(spread)))
+        return mass, spread
 
     def last_logits(self, nb: int) -> np.ndarray:
         out = np.empty((nb, self.spec.vocab_size), dtype=np.float32)

@@ -36,6 +36,8 @@ class Segment:
     token_logprobs: Optional[np.ndarray] = None   # float32, one per token (generate(return_token_logprobs=True))
     top_ids: Optional[np.ndarray] = None          # int32 [n_tok][k]: the k best raw logits of each token's step (generate(top_logprobs=k))
     top_logprobs: Optional[np.ndarray] = None     # float32 [n_tok][k]: their log-probabilities (-1 / NaN: fewer than k candidates)
+    alignment_scores: Optional[np.ndarray] = None   # float32, one per token: attention mass on the DTW path (generate(return_alignment_scores=True))
+    alignment_spreads: Optional[np.ndarray] = None  # float32, one per token: spread of the attention in seconds
 
 
 def detect_language(engine: Engine, n_items: int) -> np.ndarray:
@@ -189,10 +191,16 @@ def prompted_max_length(spec, n_input: int, max_new_tokens: Optional[int]) -> in
 
 
 def split_segments(seq: np.ndarray, token_ts: np.ndarray, time_offset: float, timestamp_begin: int,
-                   seek_num_frames: int, idx_offset: int, token_lp: Optional[np.ndarray] = None, token_top=None):
+                   seek_num_frames: int, idx_offset: int, token_lp: Optional[np.ndarray] = None, token_top=None, token_align=None):
     """Slice one decoded window at paired timestamp tokens; returns (segments, frames to advance).  ``token_lp`` (per-token
-    log-probabilities of the row, indexed like ``token_ts``) and ``token_top`` (the row's (ids [T][k], log-probabilities [T][k])
-    alternatives, indexed alike) are cut by the same index ranges."""
+    log-probabilities of the row, indexed like ``token_ts``), ``token_top`` (the row's (ids [T][k], log-probabilities [T][k])
+    alternatives, indexed alike) and ``token_align`` (the row's (mass, spread) alignment scores, indexed alike) are cut by the
+    same index ranges."""
+    def al(a, b):
+        if token_align is None:
+            return None, None
+        return np.asarray(token_align[0][a:b], dtype=np.float32).copy(), np.asarray(token_align[1][a:b], dtype=np.float32).copy()
+
     def lp(a, b):
         return None if token_lp is None else np.asarray(token_lp[a:b], dtype=np.float32).copy()
 
@@ -217,7 +225,7 @@ def split_segments(seq: np.ndarray, token_ts: np.ndarray, time_offset: float, ti
         for cut in cuts:
             out.append(Segment(seq[prev:cut], (token_ts[idx_offset + prev: idx_offset + cut] + off32).astype(np.float32),
                                (idx_offset + prev, idx_offset + cut), lp(idx_offset + prev, idx_offset + cut),
-                               *top(idx_offset + prev, idx_offset + cut)))
+                               *top(idx_offset + prev, idx_offset + cut), *al(idx_offset + prev, idx_offset + cut)))
             prev = cut
         if single_ending:
             advance = seek_num_frames
@@ -226,7 +234,7 @@ def split_segments(seq: np.ndarray, token_ts: np.ndarray, time_offset: float, ti
     else:
         out.append(Segment(seq, (token_ts[idx_offset: idx_offset + len(seq)] + off32).astype(np.float32),
                            (idx_offset, idx_offset + len(seq)), lp(idx_offset, idx_offset + len(seq)),
-                           *top(idx_offset, idx_offset + len(seq))))
+                           *top(idx_offset, idx_offset + len(seq)), *al(idx_offset, idx_offset + len(seq))))
         advance = seek_num_frames
     return out, advance
 
@@ -507,12 +515,31 @@ def check_sequence_bias(sequence_bias, vocab_size: int):
     return out
 
 
+def check_alignment_collar(spec, collar) -> int:
+    """``alignment_collar_frames``: None = ``median_filter_width // 2`` (the most the median filter can move an edge), else a
+    non-negative integer number of 20 ms frames."""
+    if collar is None:
+        return int(spec.median_filter_width) // 2
+    if isinstance(collar, (bool, np.bool_)) or not isinstance(collar, (int, np.integer)) or int(collar) < 0:
+        raise ValueError(f"alignment_collar_frames must be a non-negative integer number of frames, got {collar!r}")
+    return int(collar)
+
+
+def set_alignment_scores(engine, want: bool, collar: int):
+    """The engine's alignment-score switch as a call wants it.  A call without the flag touches the engine only to switch off
+    what an earlier call switched on (``engine.alignment_scores_on``): on an engine that never had it on, such a call is what it
+    was before the switch existed, whatever state the engine is in."""
+    if hasattr(engine, "set_alignment_scores") and (want or getattr(engine, "alignment_scores_on", False)):
+        engine.set_alignment_scores(want, collar)
+
+
 def generate(engine: Engine, n_items: int, num_frames, *, language: Optional[str], task: Optional[str] = None,
              max_new_tokens: Optional[int] = None, min_new_tokens: Optional[int] = None,
              num_beams: Optional[int] = 1, stats: Optional[dict] = None, native: Optional[bool] = None,
              logprob_threshold: Optional[float] = None, no_speech_threshold: Optional[float] = None, prompt_ids=None,
              temperature=None, compression_ratio_threshold: Optional[float] = None, sampling_seed: int = 0, item_ids=None,
-             return_token_logprobs: bool = False, top_logprobs: int = 0, sequence_bias=None):
+             return_token_logprobs: bool = False, top_logprobs: int = 0, sequence_bias=None,
+             return_alignment_scores: bool = False, alignment_collar_frames: Optional[int] = None):
     """Transcribe the ``n_items`` 30 s feature windows resident in the engine (items 0..n-1).
 
     Returns {"sequences": [B, Lmax] int64 (pad-right), "token_timestamps": list of float32 arrays,
@@ -553,7 +580,14 @@ def generate(engine: Engine, n_items: int, num_frames, *, language: Optional[str
     ``sequence_bias`` (transformers' list or dict form, ``check_sequence_bias``; needs ``num_beams=1``): phrase boosting with the
     semantics of SequenceBiasLogitsProcessor, applied inside the sampler kernels (``cw_set_sequence_bias``) in front of every other
     logits processor, in every window and every fallback re-decode.  The prompt tokens take part in the prefix match.  The raw
-    outputs ("token_logprobs", "top_logprobs") are unchanged by it.  The table is cleared again when the call ends or raises."""
+    outputs ("token_logprobs", "top_logprobs") are unchanged by it.  The table is cleared again when the call ends or raises.
+
+    ``return_alignment_scores=True`` adds "alignment_scores" and "alignment_spreads": one float32 array each per item aligned
+    with ``token_timestamps``.  The first is the share of the alignment heads' attention that lies inside the frames the DTW path
+    gave the token, widened by ``alignment_collar_frames`` 20 ms frames on either side (None: ``median_filter_width // 2``, the
+    most the median filter can move an edge); the second the standard deviation of that attention over the frames, in seconds
+    (``cw_set_alignment_scores``; NaN where undefined).  One reduction kernel behind every DTW, in every decoding mode; nothing
+    else in the result changes."""
     spec = engine.spec
     table = check_sequence_bias(sequence_bias, spec.vocab_size)
     if table is not None:
@@ -571,7 +605,8 @@ def generate(engine: Engine, n_items: int, num_frames, *, language: Optional[str
                          logprob_threshold=logprob_threshold, no_speech_threshold=no_speech_threshold, prompt_ids=prompt_ids,
                          temperature=temperature, compression_ratio_threshold=compression_ratio_threshold,
                          sampling_seed=sampling_seed, item_ids=item_ids, return_token_logprobs=return_token_logprobs,
-                         top_logprobs=top_logprobs)
+                         top_logprobs=top_logprobs, return_alignment_scores=return_alignment_scores,
+                         alignment_collar_frames=alignment_collar_frames)
     finally:
         if table is not None:
             engine.set_sequence_bias(None)
@@ -579,9 +614,13 @@ def generate(engine: Engine, n_items: int, num_frames, *, language: Optional[str
 
 def _generate(engine: Engine, n_items: int, num_frames, *, language, task, max_new_tokens, min_new_tokens, num_beams, stats, native,
               logprob_threshold, no_speech_threshold, prompt_ids, temperature, compression_ratio_threshold, sampling_seed, item_ids,
-              return_token_logprobs, top_logprobs):
+              return_token_logprobs, top_logprobs, return_alignment_scores=False, alignment_collar_frames=None):
     """``generate`` proper: everything but the sequence_bias table, which ``generate`` sets around this call."""
     spec = engine.spec
+    want_as = bool(return_alignment_scores)
+    collar = check_alignment_collar(spec, alignment_collar_frames)
+    if want_as and not hasattr(engine, "set_alignment_scores"):
+        raise ValueError("this engine does not implement alignment scores (cw_set_alignment_scores)")
     want_lp = bool(return_token_logprobs)
     if want_lp and not hasattr(engine, "set_token_logprobs"):
         raise ValueError("this engine does not implement per-token log-probabilities (cw_set_token_logprobs)")
@@ -632,7 +671,7 @@ def _generate(engine: Engine, n_items: int, num_frames, *, language, task, max_n
         if len(ids_) != n_items:
             raise ValueError(f"{len(ids_)} item_ids for {n_items} items")
         fb = {"temps": temps, "seed": int(sampling_seed), "item_ids": ids_, "cr_thr": compression_ratio_threshold,
-              "token_logprobs": want_lp, "top_logprobs": want_top}
+              "token_logprobs": want_lp, "top_logprobs": want_top, "alignment_scores": want_as}
         native = False                                  # the fallback loop runs here, like beam search
     if hasattr(engine, "set_thresholds"):
         engine.set_thresholds(logprob_threshold, no_speech_threshold)
@@ -642,6 +681,7 @@ def _generate(engine: Engine, n_items: int, num_frames, *, language, task, max_n
         engine.set_token_logprobs(want_lp)
     if hasattr(engine, "set_top_logprobs"):
         engine.set_top_logprobs(want_top)
+    set_alignment_scores(engine, want_as, collar)
     num_frames = np.asarray(num_frames, dtype=np.int64)
     if native is None:
         native = hasattr(engine, "transcribe") and num_beams == 1
@@ -672,6 +712,8 @@ def _generate(engine: Engine, n_items: int, num_frames, *, language, task, max_n
             out["token_logprobs"] = engine.transcribe_token_logprobs([len(s) for s in toks])
         if want_top:
             out["top_ids"], out["top_logprobs"] = engine.transcribe_top_logprobs([len(s) for s in toks])
+        if want_as:
+            out["alignment_scores"], out["alignment_spreads"] = engine.transcribe_alignment_scores([len(s) for s in toks])
         return out
     pre_encoded = False
     _, detect = resolve_prompt(spec, language, task)
@@ -699,7 +741,7 @@ def _generate(engine: Engine, n_items: int, num_frames, *, language, task, max_n
     try:
         _seek_loop(engine, spec, n_items, num_frames, init, n_prompt, max_new_tokens, min_new_tokens, num_beams, prefix,
                    prompted_len if prefix is not None else None, skip_on, logprob_threshold, no_speech_threshold, pre_encoded,
-                   seek, max_frames, segments, tb, stats, fb, want_lp, want_top)
+                   seek, max_frames, segments, tb, stats, fb, want_lp, want_top, want_as)
     finally:
         if prefix is not None and set_prefix is not None:
             set_prefix(0)
@@ -718,12 +760,17 @@ def _generate(engine: Engine, n_items: int, num_frames, *, language, task, max_n
                           for segs in segments]
         out["top_logprobs"] = [np.concatenate([s.top_logprobs for s in segs]) if segs else np.zeros((0, want_top), np.float32)
                                for segs in segments]
+    if want_as:
+        out["alignment_scores"] = [np.concatenate([s.alignment_scores for s in segs]) if segs else np.zeros(0, np.float32)
+                                   for segs in segments]
+        out["alignment_spreads"] = [np.concatenate([s.alignment_spreads for s in segs]) if segs else np.zeros(0, np.float32)
+                                    for segs in segments]
     return out
 
 
 def _seek_loop(engine, spec, n_items, num_frames, init, n_prompt, max_new_tokens, min_new_tokens, num_beams, prefix, prompted_len,
                skip_on, logprob_threshold, no_speech_threshold, pre_encoded, seek, max_frames, segments, tb, stats, fb=None, want_lp=False,
-               want_top=0):
+               want_top=0, want_as=False):
     """The seek loop of the host path of ``generate`` (fills ``segments`` in place).  ``fb``: temperature fallback settings."""
     n_calls = 0
     while True:
@@ -747,11 +794,12 @@ def _seek_loop(engine, spec, n_items, num_frames, init, n_prompt, max_new_tokens
                 s, ts_row, skip = kept[row][:3]
                 lp_row = kept[row][3] if want_lp else None
                 top_row = kept[row][4:6] if want_top else None
+                as_row = kept[row][-2:] if want_as else None
                 if skip:
                     seek[i] += seek_num[i]                        # should_skip (:879-881)
                     continue
                 segs, advance = split_segments(s, ts_row, float(seek[i]) * TIME_PRECISION / INPUT_STRIDE, tb,
-                                               int(seek_num[i]), n_prompt, lp_row, top_row)
+                                               int(seek_num[i]), n_prompt, lp_row, top_row, as_row)
                 seek[i] += advance
                 segments[i].extend(segs)
             continue
@@ -774,6 +822,8 @@ def _seek_loop(engine, spec, n_items, num_frames, init, n_prompt, max_new_tokens
             if want_top:
                 tok_top = engine.top_logprobs(len(active))
         token_ts = engine.token_timestamps(len(active), L, n_prompt, (num_frames - seek)[active])
+        if want_as:
+            tok_as = engine.alignment_scores(len(active), L)
         n_calls += 1
         for row, i in enumerate(active):
             if skip_on and float(alp[row]) < logprob_threshold and float(nsp[row]) > no_speech_threshold:
@@ -790,7 +840,8 @@ def _seek_loop(engine, spec, n_items, num_frames, init, n_prompt, max_new_tokens
                 s = s[:-1]
             segs, advance = split_segments(s, token_ts[row], float(seek[i]) * TIME_PRECISION / INPUT_STRIDE, tb,
                                            int(seek_num[i]), n_prompt, tok_lp[row] if want_lp else None,
-                                           (tok_top[0][row], tok_top[1][row]) if want_top else None)
+                                           (tok_top[0][row], tok_top[1][row]) if want_top else None,
+                                           (tok_as[0][row], tok_as[1][row]) if want_as else None)
             seek[i] += advance
             segments[i].extend(segs)
     if stats is not None:
@@ -807,7 +858,8 @@ def _decode_with_fallback(engine, spec, fb, active, init_rows, n_prompt, max_len
     rows).  Decisions are indexed by the original row throughout -- transformers indexes ``needs_fallback[i]`` /
     ``should_skip[i]`` by the row of the shrunken sub-batch (:1074 against :1088) and reads them back by the original one.
     Returns per row (tokens without eos, token timestamps of the whole row, skip[, token log-probabilities of the whole row when
-    ``fb["token_logprobs"]`` is set[, alternative ids and log-probabilities of the whole row when ``fb["top_logprobs"]`` is]])."""
+    ``fb["token_logprobs"]`` is set[, alternative ids and log-probabilities of the whole row when ``fb["top_logprobs"]`` is]][,
+    last of all, the row's alignment scores and spreads when ``fb["alignment_scores"]`` is set])."""
     nb = len(active)
     temps = fb["temps"]
     kept = [None] * nb
@@ -827,6 +879,7 @@ def _decode_with_fallback(engine, spec, fb, active, init_rows, n_prompt, max_len
             total = int(lens.max())
             alp = engine.avg_logprobs(nb) if logprob_threshold is not None else None
             token_ts = engine.token_timestamps(nb, total - 1, n_prompt, frames)
+            tok_as = engine.alignment_scores(nb, total - 1) if fb.get("alignment_scores") else None
             tok_lp = engine.token_logprobs(nb) if fb.get("token_logprobs") else None   # a masked row keeps its settled values
             tok_top = engine.top_logprobs(nb) if tok_lp is not None and fb.get("top_logprobs") else None   # ... and entries
             again = []
@@ -855,6 +908,8 @@ def _decode_with_fallback(engine, spec, fb, active, init_rows, n_prompt, max_len
                     kept[r] += (np.array(tok_lp[r], copy=True),)
                 if tok_top is not None:
                     kept[r] += (np.array(tok_top[0][r], copy=True), np.array(tok_top[1][r], copy=True))
+                if tok_as is not None:
+                    kept[r] += (np.array(tok_as[0][r], copy=True), np.array(tok_as[1][r], copy=True))
                 if needs and not last:
                     again.append(r)
             pending = again
@@ -888,7 +943,8 @@ def check_transcript_ids(spec, ids) -> np.ndarray:
 
 
 def align(engine: Engine, n_items: int, num_frames, transcripts, *, language: Optional[str] = None,
-          task: Optional[str] = None, return_scores: bool = False):
+          task: Optional[str] = None, return_scores: bool = False, return_alignment_scores: bool = False,
+          alignment_collar_frames: Optional[int] = None):
     """Forced alignment of known transcripts to the ``n_items`` 30 s feature windows resident in the engine.
 
     Row b is the decoder input <|startoftranscript|><|lang|><|task|> ++ transcripts[b] ++ eos, with the init tokens resolved by
@@ -897,8 +953,13 @@ def align(engine: Engine, n_items: int, num_frames, transcripts, *, language: Op
     transcripts), "token_timestamps": list of float32 arrays, one timestamp per transcript token} -- the fields the pipeline
     hands to ``collate.decode_asr``, as ``generate`` returns them for its own tokens.  ``return_scores=True`` runs the full
     scoring forward instead of the early-stopping one (cw_align_score_tokens: same timestamps) and adds "token_logprobs",
-    "top_ids", "top_logprobs": per transcript one entry per token plus one for the eos."""
+    "top_ids", "top_logprobs": per transcript one entry per token plus one for the eos.  ``return_alignment_scores=True`` adds
+    "alignment_scores" and "alignment_spreads", one value per transcript token, as ``generate`` defines them."""
     spec = engine.spec
+    want_as = bool(return_alignment_scores)
+    collar = check_alignment_collar(spec, alignment_collar_frames)
+    if want_as and not hasattr(engine, "set_alignment_scores"):
+        raise ValueError("this engine does not implement alignment scores (cw_set_alignment_scores)")
     texts = [check_transcript_ids(spec, t) for t in transcripts]
     if len(texts) != n_items:
         raise ValueError(f"{len(texts)} transcripts for {n_items} items")
@@ -919,12 +980,19 @@ def align(engine: Engine, n_items: int, num_frames, transcripts, *, language: Op
     else:
         inits = [init_tokens(spec, language, task)] * n_items
     rows = [np.concatenate([np.asarray(i, np.int64), t, [spec.eos_token_id]]) for i, t in zip(inits, texts)]
+    set_alignment_scores(engine, want_as, collar)
     if return_scores:
         ts, lp, ti, tl = engine.align_score_tokens(num_frames, rows, n_init)
-        return {"sequences": texts, "token_timestamps": [s[n_init:n_init + len(t)] for s, t in zip(ts, texts)],
-                "token_logprobs": lp, "top_ids": ti, "top_logprobs": tl}
-    ts = engine.align_tokens(num_frames, rows, n_init)
-    return {"sequences": texts, "token_timestamps": [s[n_init:n_init + len(t)] for s, t in zip(ts, texts)]}
+        out = {"sequences": texts, "token_timestamps": [s[n_init:n_init + len(t)] for s, t in zip(ts, texts)],
+               "token_logprobs": lp, "top_ids": ti, "top_logprobs": tl}
+    else:
+        ts = engine.align_tokens(num_frames, rows, n_init)
+        out = {"sequences": texts, "token_timestamps": [s[n_init:n_init + len(t)] for s, t in zip(ts, texts)]}
+    if want_as:
+        mass, spread = engine.alignment_scores(n_items, max(len(r) for r in rows) - 1)
+        out["alignment_scores"] = [mass[b, n_init:n_init + len(t)].copy() for b, t in enumerate(texts)]
+        out["alignment_spreads"] = [spread[b, n_init:n_init + len(t)].copy() for b, t in enumerate(texts)]
+    return out
 
 
 ALIGN_HEADS_ROW_BYTES = 1500 * 4          # one recorded attention row (f32 over the encoder frames)

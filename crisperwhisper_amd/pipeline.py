@@ -363,14 +363,28 @@ def token_text(vocab, tok: int) -> str:
     return ""
 
 
-def scored_words(vocab, outputs, token_logprobs, warn=None, token_top=None):
+def add_alignment_scores(words, groups, token_mass, token_spread):
+    """"alignment_score" and "alignment_spread" on every word of ``collate.decode_asr(..., return_token_groups=True)``: the
+    float64 mean of the tokens' values (``token_mass`` / ``token_spread``: one array per window, one value per token) over the
+    collator's own token group of the word -- the grouping ``scored_words`` uses, so a token the seam merge drops counts in no
+    word.  NaN if any member is NaN."""
+    mass = np.concatenate([np.asarray(a, np.float64) for a in token_mass]) if len(token_mass) else np.zeros(0, np.float64)
+    spread = np.concatenate([np.asarray(a, np.float64) for a in token_spread]) if len(token_spread) else np.zeros(0, np.float64)
+    for w, g in zip(words, groups):
+        g = np.asarray(g, np.int64).reshape(-1)
+        w["alignment_score"] = float(np.mean(mass[g])) if g.size else float("nan")
+        w["alignment_spread"] = float(np.mean(spread[g])) if g.size else float("nan")
+    return words
+
+
+def scored_words(vocab, outputs, token_logprobs, warn=None, token_top=None, return_groups=False):
     """``collate.decode_asr(outputs, return_timestamps="word")`` with "logprob" on every word: the float64 sum of
     ``token_logprobs`` (one array per entry of ``outputs``, one value per token) over the collator's own token group of the word.
     The groups address the concatenation of all windows' tokens, so a token the seam merge drops counts in no word.
 
     ``token_top`` (one (ids [n_tok][k], log-probabilities [n_tok][k]) pair per entry of ``outputs``) adds "tokens" to every
     word, over the same group: ``[{"id", "text", "logprob", "top_logprobs": [{"id", "text", "logprob"}, ...]}]``, alternatives
-    best first, entries with id -1 left out."""
+    best first, entries with id -1 left out.  ``return_groups=True`` returns the collator's token groups as a third value."""
     if len(token_logprobs) != len(outputs) or any(len(a) != len(o["tokens"]) for a, o in zip(token_logprobs, outputs)):
         raise ValueError("scored_words: one log-probability per token of every window is required")
     if token_top is not None and (len(token_top) != len(outputs) or any(
@@ -395,6 +409,8 @@ def scored_words(vocab, outputs, token_logprobs, warn=None, token_top=None):
     elif token_top is not None:
         for w in words:
             w["tokens"] = []
+    if return_groups:
+        return text, words, groups
     return text, words
 
 
@@ -412,8 +428,17 @@ class CrisperWhisperPipeline:
                  shard: Optional[dist.Shard] = None, contexts: int = 1, cross_kv_dtype: Optional[str] = None,
                  encoder_gemm_dtype: Optional[str] = None,
                  engines: Optional[List[Engine]] = None, num_beams: Optional[int] = None,
-                 sampling_seed: Optional[int] = None, return_scores: bool = False, top_logprobs: int = 0, **kwargs):
-        """``return_scores`` (here or per call, default False): with ``return_timestamps="word"`` every chunk gains
+                 sampling_seed: Optional[int] = None, return_scores: bool = False, top_logprobs: int = 0,
+                 return_alignment_scores: bool = False, alignment_collar_frames: Optional[int] = None, **kwargs):
+        """``return_alignment_scores`` (here or per call, default False; needs ``return_timestamps="word"``): every word chunk
+        gains "alignment_score", the share of the alignment heads' attention that lies inside the frames the DTW path gave the
+        word's tokens (1: every head looks exactly there; near 0: the path had to invent the boundary), and "alignment_spread",
+        the standard deviation of that attention over the frames in seconds -- float64 means over the collator's own token groups,
+        NaN where undefined.  ``alignment_collar_frames`` (here or per call): the window is widened by that many 20 ms frames on
+        either side; None = ``median_filter_width // 2``, the most the median filter can move an edge.  Independent of
+        ``return_scores`` / ``top_logprobs``; everything else in the result is unchanged.
+
+        ``return_scores`` (here or per call, default False): with ``return_timestamps="word"`` every chunk gains
         "logprob", the float64 sum over its tokens of ``logits[tok] - logsumexp(logits[:vocab])`` on the raw logits of the
         decode step that chose each token -- grouped by the collator's own token groups, so tokens dropped in a seam
         overlap count in no word.
@@ -454,6 +479,10 @@ class CrisperWhisperPipeline:
         self.return_timestamps = return_timestamps
         self.return_scores = bool(return_scores)
         self.top_logprobs = _check_top_logprobs(top_logprobs)
+        self.return_alignment_scores = bool(return_alignment_scores)
+        if alignment_collar_frames is not None:
+            generation.check_alignment_collar(self.bundle.spec, alignment_collar_frames)
+        self.alignment_collar_frames = alignment_collar_frames
         # the key of the engine's sampler for calls with a positive temperature / temperature fallback; None: such calls must
         # name one themselves (a call without any seed is refused, it does not draw from a hidden default)
         self.sampling_seed = None if sampling_seed is None else _check_seed(sampling_seed)
@@ -515,13 +544,20 @@ class CrisperWhisperPipeline:
 
     def _run_one(self, inputs, return_timestamps=None, generate_kwargs=None, chunk_length_s=None,
                  stride_length_s=None, return_language=None, sampling_seed=None, return_scores=None, top_logprobs=None,
-                 **unused):
+                 return_alignment_scores=None, alignment_collar_frames=None, **unused):
         seed = self.sampling_seed if sampling_seed is None else _check_seed(sampling_seed)
         rt = return_timestamps if return_timestamps is not None else self.return_timestamps
         scores = self.return_scores if return_scores is None else bool(return_scores)
         if scores and rt != "word":
             raise ValueError('return_scores=True gives every word its log-probability: it needs return_timestamps="word" '
                              f"(got {rt!r}; segment-level scores are not implemented)")
+        align_on = getattr(self, "return_alignment_scores", False) if return_alignment_scores is None else bool(return_alignment_scores)
+        if align_on and rt != "word":
+            raise ValueError('return_alignment_scores=True gives every word its alignment score: it needs return_timestamps="word" '
+                             f"(got {rt!r})")
+        collar = getattr(self, "alignment_collar_frames", None) if alignment_collar_frames is None else alignment_collar_frames
+        if collar is not None:
+            collar = generation.check_alignment_collar(None, collar)
         top_k = getattr(self, "top_logprobs", 0) if top_logprobs is None else _check_top_logprobs(top_logprobs)
         if top_k and not scores:
             raise ValueError("top_logprobs lists the alternatives next to every token's log-probability: it needs "
@@ -584,6 +620,7 @@ class CrisperWhisperPipeline:
                 temperature=gk.get("temperature"), compression_ratio_threshold=gk.get("compression_ratio_threshold"),
                 sampling_seed=seed or 0, item_ids=idxs, **({"return_token_logprobs": True} if scores else {}),
                 **({"top_logprobs": top_k} if top_k else {}),
+                **({"return_alignment_scores": True, "alignment_collar_frames": collar} if align_on else {}),
                 **({"sequence_bias": gk["sequence_bias"]} if gk.get("sequence_bias") is not None else {}))
             if "fallback" in st:
                 fallback_trace.extend(st["fallback"])
@@ -594,6 +631,8 @@ class CrisperWhisperPipeline:
                 rs.append(dist.pack_record(i, out["sequences"][k][:n_tok], out["token_timestamps"][k], stride,
                                            out["token_logprobs"][k] if scores else None,
                                            (out["top_ids"][k], out["top_logprobs"][k]) if top_k else None))
+                if align_on:                               # the alignment scores travel behind the record, whatever its width
+                    rs[-1] = dist.append_alignment(rs[-1], out["alignment_scores"][k], out["alignment_spreads"][k])
             return rs, st.get("generate_calls", 0)
 
         per = self.batch_size
@@ -621,13 +660,19 @@ class CrisperWhisperPipeline:
         self.stats["generate_calls"] = self.stats.get("generate_calls", 0) + sum(c for _, c in results)
         # an empty shard sends the width the other ranks send
         width = dist.rec_words_top(top_k) if top_k else (dist.REC_WORDS_SCORED if scores else dist.REC_WORDS)
+        if align_on:
+            width += dist.REC_ALIGN_WORDS
         recs = np.stack(recs) if recs else np.zeros((0, width), np.int32)
         max_per_rank = max(h - l for l, h in dist.shard_bounds(len(windows), self.shard.world))
         t_ph.append(_time.perf_counter())
         allr = self.shard.all_gather_records(recs, max_per_rank)
         t_ph.append(_time.perf_counter())
-        outputs, token_lp, token_top = [], [], []
+        outputs, token_lp, token_top, token_mass, token_spread = [], [], [], [], []
         for r in allr:
+            if align_on:
+                r, mass, spread = dist.split_alignment(r)
+                token_mass.append(mass)
+                token_spread.append(spread)
             _, toks, ts, stride, *lp = dist.unpack_record(r)
             if top_k:
                 token_top.append((lp[1], lp[2]))
@@ -638,10 +683,16 @@ class CrisperWhisperPipeline:
             outputs.append(o)
             token_lp.extend(lp)
         if scores:
-            text, words = scored_words(self.vocab, outputs, token_lp, warn=logger.warning, token_top=token_top if top_k else None)
+            text, words, groups = scored_words(self.vocab, outputs, token_lp, warn=logger.warning,
+                                               token_top=token_top if top_k else None, return_groups=True)
+        elif align_on:
+            text, words, groups = collate.decode_asr(self.vocab, outputs, time_precision=0.02, warn=logger.warning,
+                                                     return_timestamps="word", return_token_groups=True)
         else:
             text, words = collate.decode_asr(self.vocab, outputs, time_precision=0.02, warn=logger.warning,
                                              return_timestamps="word" if rt == "word" else True)
+        if align_on:
+            add_alignment_scores(words, groups, token_mass, token_spread)
         t_ph.append(_time.perf_counter())
         # where the wall time of the last call went on this rank (bench.py's long-form leg prints it: the scaling model of
         # DESIGN.md section 5 needs the rank-local part, which shrinks with the rank count, apart from the rest, which does not)
@@ -705,8 +756,9 @@ class CrisperWhisperPipeline:
             pcms.append(pcm)
         return pcms
 
-    def _scored_words(self, ids, token_logprobs, token_timestamps=None):
-        """Words of one transcript with the sum of their tokens' log-probabilities, grouped by the collator itself."""
+    def _scored_words(self, ids, token_logprobs, token_timestamps=None, return_groups=False):
+        """Words of one transcript with the sum of their tokens' log-probabilities, grouped by the collator itself
+        (``return_groups=True``: its token groups as a third value)."""
         ts = token_timestamps if token_timestamps is not None else np.zeros(len(ids), np.float32)
         text, words, groups = collate.decode_asr(self.vocab, [{"tokens": ids, "token_timestamps": ts}], time_precision=0.02,
                                                  return_timestamps="word", return_token_groups=True)
@@ -716,6 +768,8 @@ class CrisperWhisperPipeline:
             if token_timestamps is not None:
                 c["timestamp"] = w["timestamp"]
             chunks.append(c)
+        if return_groups:
+            return text, chunks, groups
         return text, chunks
 
     @staticmethod
@@ -785,15 +839,27 @@ class CrisperWhisperPipeline:
         return results[0] if single else results
 
     def align(self, inputs, transcripts, language: Optional[str] = None, task: Optional[str] = None,
-              return_scores: bool = False, **kwargs):
+              return_scores: bool = False, return_alignment_scores: bool = False,
+              alignment_collar_frames: Optional[int] = None, **kwargs):
         """Word timestamps for known transcripts: ``inputs`` in any form ``__call__`` takes (one, or a list), each at most
         30 s; ``transcripts`` one per input, a ``str`` (needs a transformers tokenizer) or token ids without special
         tokens.  ``language`` / ``task`` resolve like ``generate_kwargs`` in ``__call__`` (``language=None``: detected per
         item).  Returns {"text", "chunks": [{"text", "timestamp": (start, end)}]} like ``__call__(..., return_timestamps=
         "word")``, or a list of them for a list of inputs; lists run in batches of up to the pipeline's decoder rows.
         ``return_scores=True`` adds what ``score`` computes, from the same forward: "logprob" on every chunk, and "logprob" /
-        "avg_logprob" of the whole transcript (eos included) at the top level."""
+        "avg_logprob" of the whole transcript (eos included) at the top level.  ``return_alignment_scores=True`` adds
+        "alignment_score" / "alignment_spread" to every chunk, as ``__call__`` defines them (``alignment_collar_frames`` likewise;
+        None: the pipeline's own setting)."""
         language, task = self._forced_kwargs("align", language, task, kwargs)
+        collar = getattr(self, "alignment_collar_frames", None) if alignment_collar_frames is None else alignment_collar_frames
+        if collar is not None:
+            collar = generation.check_alignment_collar(None, collar)
+        akw = {"return_alignment_scores": True, "alignment_collar_frames": collar} if return_alignment_scores else {}
+
+        def with_alignment(out, k, chunks, groups):          # groups: the collator's, from the one collation of item k
+            if akw:
+                add_alignment_scores(chunks, groups, [out["alignment_scores"][k]], [out["alignment_spreads"][k]])
+            return chunks
         single = not isinstance(inputs, (list, tuple))
         if single:
             inputs, transcripts = [inputs], [transcripts]
@@ -810,21 +876,24 @@ class CrisperWhisperPipeline:
             idx = list(range(b0, min(len(pcms), b0 + per)))
             _, nf = eng.mel([pcms[i] for i in idx])
             if return_scores:
-                out = generation.align(eng, len(idx), nf, [ids[i] for i in idx], language=language, task=task, return_scores=True)
+                out = generation.align(eng, len(idx), nf, [ids[i] for i in idx], language=language, task=task, return_scores=True,
+                                       **akw)
                 for k in range(len(idx)):
                     lp = np.asarray(out["token_logprobs"][k], np.float64)
-                    text, chunks = self._scored_words(out["sequences"][k], lp[:-1], out["token_timestamps"][k])
+                    text, chunks, groups = self._scored_words(out["sequences"][k], lp[:-1], out["token_timestamps"][k],
+                                                              return_groups=True)
                     total = float(lp.sum())
-                    results.append({"text": text, "chunks": [{"text": c["text"], "timestamp": c["timestamp"], "logprob": c["logprob"]}
-                                                             for c in chunks],
+                    results.append({"text": text, "chunks": with_alignment(out, k, [
+                        {"text": c["text"], "timestamp": c["timestamp"], "logprob": c["logprob"]} for c in chunks], groups),
                                     "logprob": total, "avg_logprob": total / (len(out["sequences"][k]) + 1)})
                 continue
-            out = generation.align(eng, len(idx), nf, [ids[i] for i in idx], language=language, task=task)
+            out = generation.align(eng, len(idx), nf, [ids[i] for i in idx], language=language, task=task, **akw)
             for k in range(len(idx)):
-                text, words = collate.decode_asr(self.vocab, [{"tokens": out["sequences"][k],
-                                                               "token_timestamps": out["token_timestamps"][k]}],
-                                                 time_precision=0.02, return_timestamps="word")
-                results.append({"text": text, "chunks": words})
+                text, words, *groups = collate.decode_asr(self.vocab, [{"tokens": out["sequences"][k],
+                                                                        "token_timestamps": out["token_timestamps"][k]}],
+                                                          time_precision=0.02, return_timestamps="word",
+                                                          **({"return_token_groups": True} if akw else {}))
+                results.append({"text": text, "chunks": with_alignment(out, k, words, groups[0] if akw else None)})
         return results[0] if single else results
 
     # -- per-head forced alignment, alignment-head selection -----------------------------------------

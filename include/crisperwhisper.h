@@ -312,6 +312,31 @@ void cw_beam_host_free(cw_beam_host* s);
  * filter, head mean, DTW, jump times.  L = rows retained = max(lengths) - 1.  ts_out [nb][L+1] seconds. */
 int32_t cw_token_timestamps(cw_ctx* ctx, int32_t nb, int32_t L, int32_t n_prompt, const int32_t* num_frames,
                             float* ts_out);
+/* Alignment scores: how sure the model is of WHEN a token was said.  With the switch on (default off) every run of the timestamp
+ * stage -- cw_token_timestamps after a greedy, sampled or beam decode, cw_align_tokens, cw_align_score_tokens, every pass of
+ * cw_transcribe / cw_transcribe_prompted; not cw_align_heads -- launches one more kernel behind its DTW, inside the
+ * CW_STAGE_TIMESTAMPS timer, on the normalised alignment rows and the first frames the DTW just left on the device.  For token
+ * row i of a sequence with n frames (the columns that reached the DTW), rows w[h][i][0 .. n-1] of the Ha alignment heads and
+ * first frames fc[0 .. N-1] (fc[N] := n):
+ *   lo = fc[i], hi = max(lo + 1, fc[i+1]), window = [max(0, lo - collar_frames), min(n, hi + collar_frames))
+ *   T_h = sum_j w[h][i][j],  p_h[j] = w[h][i][j] / T_h,  pbar[j] = mean_h p_h[j]
+ *   mass   = sum of pbar[j] over the window: the share of the heads' attention that lies where the path put the token
+ *   spread = 0.02 * sqrt(sum_j pbar[j] (j - mu)^2) seconds, mu = sum_j pbar[j] j: how diffuse the attention is, path or no path
+ * both NaN when n == 0, when a T_h is 0 or when fc[i] < 0.  Float64 sums in a fixed order (csrc/align.hip), rounded to f32 once:
+ * a row's values are bit-identical from run to run and whatever else is in the batch.
+ * cw_set_alignment_scores: CW_ERR_INVALID for a negative collar_frames; CW_ERR_STATE for switching it on, or changing the collar,
+ * while a beam search is open (cw_beam_begin without cw_beam_finish; the next decode closes it).  Switching it off, and repeating
+ * the setting in force, change nothing and are accepted in any state.  Allocates two
+ * [max_batch][max_target_positions] f32 buffers on first use.  While off nothing is launched, allocated or copied, and every
+ * other output is bit-identical either way.
+ * cw_get_alignment_scores: those of the last timestamp stage, mass / spread [nb][L+1] in cw_token_timestamps' indexing (after
+ * cw_align_tokens / cw_align_score_tokens: L = the longest row's n_ids - 1); NaN at prompt positions, in the eos slot and
+ * behind a row's end.  CW_ERR_STATE while off, for more rows than were scored, or for an L below a row's own.
+ * cw_get_transcribe_alignment_scores: those of the last cw_transcribe / cw_transcribe_prompted, carried through segment slicing
+ * and eos stripping exactly as the token timestamps are: [B][cap] aligned with its `tokens` (NaN behind lens[i]).          */
+int32_t cw_set_alignment_scores(cw_ctx* ctx, int32_t on, int32_t collar_frames);
+int32_t cw_get_alignment_scores(cw_ctx* ctx, float* mass, float* spread /* [nb][L+1] */, int32_t nb, int32_t L);
+int32_t cw_get_transcribe_alignment_scores(cw_ctx* ctx, float* mass, float* spread /* [B][cap] */, int32_t B, int32_t cap);
 
 /* cw_align_tokens: forced alignment of known token sequences.  Encodes the nb resident feature items (cw_mel /
  * cw_set_features), runs one teacher-forced decoder forward of row b over ids[b][0 .. n_ids[b]-2] (the n_init init tokens
@@ -361,6 +386,11 @@ int32_t cw_align_heads_times(cw_ctx* ctx, float* ms);
 int32_t cw_test_align_similarity(cw_ctx* ctx, const float* attn, int32_t B, int32_t Ha, int32_t N, int32_t S,
                                  const int32_t* n_cols, const float* ref_begin, const float* ref_end, int32_t clip_frames,
                                  float* out);
+/* cw_test_align_path_scores: the alignment-score kernel, through the timestamp stage's launcher, on caller-supplied rows
+ * attn [B][Ha][N][S] (S a multiple of 4), n_cols [B] <= S, first_col [B][N] (<= S) -> mass / spread [B][N].                 */
+int32_t cw_test_align_path_scores(cw_ctx* ctx, const float* attn, int32_t B, int32_t Ha, int32_t N, int32_t S,
+                                  const int32_t* n_cols, const int32_t* first_col, int32_t collar_frames, float* mass,
+                                  float* spread);
 
 /* cw_score_tokens: teacher-forced log-probabilities of known token sequences.  rows = n_items * rows_per_item decoder rows,
  * row r scored against resident feature item r / rows_per_item (several candidate texts of one clip share its encoder pass).
