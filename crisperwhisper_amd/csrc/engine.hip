@@ -1037,7 +1037,8 @@ int32_t cw_set_features(cw_ctx* c, const float* feats, int32_t B) {
 // ------------------------------------------------------------------------------------------------
 // encoder
 // ------------------------------------------------------------------------------------------------
-static EpiParams epi0() { EpiParams p; memset(&p, 0, sizeof(p)); return p; }
+extern "C++" { template <class T> static T zeroed() { T p; memset(&p, 0, sizeof(p)); return p; } }   // launch parameters start from all-zero bytes
+static EpiParams epi0() { return zeroed<EpiParams>(); }
 static DecAttnParams dec_attn(const float* q, const void* K, const void* V, int cap, int n_keys, const int* pos, float* out,
                               int B, int H) {
     DecAttnParams p;
@@ -1149,17 +1150,253 @@ static int gemv_ln(cw_ctx* c, int epi, const float* x, int Mb, int K, const void
     return KD(c, cw_launch_gemv, false, epi, c->dxn, Mb, K, W, N, nullptr, nullptr, ep, c->st);
 }
 
+static int launch_logits(cw_ctx* c, int nb, const float* x) {   // final LN + tied proj_out (:790, :1080), logits in f32 (utils.py:2894)
+    EpiParams ep = epi0(); ep.outf = c->dlogits; ep.ldo = c->Vpad;
+    return gemv_ln(c, EPI_STORE_F32, x, nb, c->d.d_model, (c->bf16 && c->wpacked) ? c->embed_pk : c->embed, c->d.vocab_size, c->dec_ln_g, c->dec_ln_b, ep);
+}
+
+// ---- the decode step: plan, layers, logits.  Which launches a decoder layer has is constant over the layers of one forward: plan_step settles it
+// once per (context, nb), every predicate in one place; decode_step, run_step (graph slot) and the stage bookkeeping of cw_time_decode_stage read it.
+struct StepPlan {
+    bool frag, fuse, own, qs, short_hist, mid16; int nt3;
+#ifdef CW_EXPERIMENTS
+    bool fuse_mlp, mlp_pair, mlp_chain, dl, sk_ok, skinny, xfull, rows, pf; int lo_off;
+#else   // the measured-and-rejected variants are not in this build: create_impl and cw_set_option refuse their switches
+    static constexpr bool fuse_mlp = false, mlp_pair = false, mlp_chain = false, dl = false, sk_ok = false, skinny = false, xfull = false, rows = false, pf = false;
+    static constexpr int lo_off = 0;
+#endif
+};
+static StepPlan plan_step(const cw_ctx* c, int nb) {
+    const int D = c->d.d_model, H = c->d.n_heads, F = c->d.ffn_dim, TGT = c->d.max_target_positions;
+    StepPlan P{};
+    // 17..64 rows (bf16): producers hand activations to the next GEMV already in MFMA fragment order (no prep launch)
+    P.frag = c->bf16 && nb > 16 && c->wpacked;      // (row-major weights: groups of 16 rows on the <= 16-row kernels, see gemv_ln)
+    // fused out-projection / cross-query stage (decfuse.hip): greedy rows of one MFMA half tile, 16-bit caches.  The residual
+    // stream then alternates between two buffers: a layer reads x from `xin` and leaves x1, x2, x3 in `xalt`.
+    // (e4m3 cache: the fp8 matrix-core kernel finishes the fused query too; its VALU fallback does not)
+    // 17..64 greedy rows (round 5): the same stage in groups of 16 rows (gemv_stack_kernel's grid y) replaces out-projection,
+    // LayerNorm preparation and query projection -- three of the layer's twelve launches -- by one; the rest of the layer keeps its
+    // preparation + gemv_mt launches, on the alternating buffers.  CW_NO_FUSE_ROWS=1: the twelve launches (A/B).  Batch 64: decode
+    // 4.43 -> 4.28 ms per token step, 64 / 64 clips; over the e4m3 cache 3.47 -> 3.41 once the cross-attention kernel lets wave 0 alone
+    // finish the query (attn_cross_mfma8_kernel<1, 2>; every wave doing it, as at <= 16 rows, measured flat).  CW_NO_FUSE_ROWS8=1: A/B
+    // (the rejected 17..64-row A/B variants of -DCW_EXPERIMENTS builds -- rows path, skinny GEMMs, full-key cross-attention -- keep their
+    // own twelve / nine launches: they read c->dx and d_xfrag, which the fused stage's alternating buffers would leave stale)
+    const bool ab17 = nb > 16 && (c->rows_ln_enabled || c->skinny_mode != 0);
+    P.fuse = c->bf16 && c->fuse6_ready && c->fuse6_enabled && c->ln_folded && !ab17 && (nb <= 16 || P.frag) && (nb <= 16 || (c->fuse_rows && nb <= 64 && (!c->kv8 || c->fuse_rows8))) &&
+             // beam search (round 6): the hypotheses of an item share a cross-attention block that finishes their queries
+             // (attn_cross_mfma_kernel<.., FUSED>, 16-bit cache); CW_NO_FUSE_BEAM=1: the twelve launches
+             (c->beam_K == 0 || (c->fuse_beam && !c->kv8 && c->beam_K <= 16 && !c->fuse_mlp)) &&
+             (!c->kv8 || (KD(c, cw_cross8_is_mfma, CW_N_CTX) && !c->fuse_mlp)) && !((c->fuse_mlp || c->mlp_pair) && nb > 8);
+    // 33..64 rows behind the fused stage (round 6): the cross-attention out-projection owns whole columns (no K split, no atomics) and
+    // leaves fc1 its 16-bit rows and LayerNorm partial sums -- one preparation launch less per layer (gemm.hip: gemv_mt_kernel OWN / LNA)
+    P.own = c->own_cols && P.fuse && P.frag && nb > 32 && !c->fuse_mlp && !c->mlp_pair && c->rows_ln_ready && D % 32 == 0 && D / 16 <= 96 && D <= 1536 &&
+            D % 128 == 0 && F % 32 == 0;
+    // column tiles per X1 block (3 * TD blocks at 1: 240 at large-v3).  17..64 rows: two -- a block's 16 f32 rows are twice the bytes
+    // of a weight tile, and a pair of tiles shares them (64 rows, 4 groups: 11.2 us at one tile, 10.5 at two, 15.5 at three)
+    P.nt3 = c->stack_nt3 > 0 ? c->stack_nt3 : (nb > 16 ? 2 : 1);
+    // rows <= 8, 16-bit engines: LN + q/k/v projection + self-attention as ONE launch (declayer.hip: qkv_self_kernel; the tiles
+    // reach the attention blocks as granules, the history rows of the cache are requested at kernel entry); bit-identical
+    // (its 3 D / 16 blocks wait for each other: only where the whole grid is resident at once on this part; layer < 64: granule tag)
+    P.qs = c->qkv_self && c->bf16 && c->ln_folded && c->wpacked && nb <= 8 && c->beam_K == 0 && D <= 1280 && nb * H <= 3 * (D / 16) && TGT <= 512 &&
+           c->d.dec_layers <= 64 && 3 * (D / 16) <= c->n_cu * KD(c, cw_qkv_self_blocks_per_cu, D, TGT);
+    P.short_hist = c->hist_short && c->short_hist_enabled && nb > 8;   // bytes matter from 9 rows up (<= 8: latency-bound, qkv_self)
+    // <= 16 rows behind the fused stage: fc1 writes gelu(.) in the 16-bit type fc2 would round it to anyway (bit-identical): fc2's activation load halves
+    P.mid16 = P.fuse && !P.frag && F > 1280 && c->mid16;
+#ifdef CW_EXPERIMENTS
+    P.fuse_mlp = c->fuse_mlp;
+    P.mlp_pair = c->mlp_pair && F % D == 0 && D % 32 == 0 && F / 32 <= 256 && F / D <= 32;
+    P.mlp_chain = c->mlp_chain && c->wpacked && c->mid16 && nb <= 8 && KD(c, cw_mlp_chain_ok, nb, D, F);
+    // rows <= 8: X1 and the cross-attention as ONE persistent launch (declayer.hip): the K/V rows are requested at kernel
+    // entry and stream under the GEMV tile; qa / qb / the partial sums cross CUs as granules.  Bit-identical to the two launches.
+    P.dl = P.fuse && c->declayer && !c->kv8 && !c->fuse_mlp && P.nt3 == 1 && c->wpacked && nb <= 8 && 3 * (D / 16) <= c->n_cu &&
+           nb * H * ATT_NS <= 4 * c->n_cu && D / 16 <= 128 && KD(c, cw_dec_layer_lds, D) <= (size_t)160 * 1024;
+    // 17..64 rows without preparation launches (decfuse.hip: gemv_rows_kernel): the residual GEMVs own whole columns and leave
+    // the stream in f32, its 16-bit fragment-major copy in d_xfrag and LayerNorm partial sums in d_rstats; the LayerNorm
+    // GEMVs read that copy and normalise their outputs.  d_xfrag2 carries attention outputs and the GELU'd MLP rows.
+    // 17..64 rows, DEFAULT (skinny_mode 0): the round-3 path -- gemv_prep_kernel (LayerNorm / combine -> fragment-major rows) +
+    // gemv_mt_kernel per projection.  A/B only (-DCW_EXPERIMENTS builds, CW_SKINNY=1|2; measured slower in the step,
+    // profiles/r04_b64_skinny_planes_rejected_*): the LayerNorm projections as skinny-M GEMMs (skinny.hip): f32 rows -> K-split
+    // partial planes, finished (statistics, bias, cache / GELU epilogue) by one light launch.  The residual projections stay on
+    // the 16-column K-split GEMV either way: their cost is the f32 atomics (7 ps each), which a wider tile with more K slices multiplies.
+    P.sk_ok = P.frag && c->wpacked && c->ln_folded && c->rows_ln_ready && c->d_planes;
+    P.skinny = P.sk_ok && c->skinny_mode >= 2;
+    // greedy rows over the 16-bit cache: one cross-attention block per (row, head) over all keys writes the out-projection's
+    // 16-bit rows itself (1280 blocks at 64 rows: the chip is full without key splits)
+    P.xfull = P.frag && c->skinny_mode >= 1 && c->beam_K == 0 && !c->kv8 && !c->rows_ln_enabled && H <= 20 && CW_N_CTX <= 24 * 64;
+    P.rows = !P.skinny && P.frag && c->rows_ln_ready && c->rows_ln_enabled && c->ln_folded && D <= 1280;
+    // bf16 only: the 16-bit copy of the residual rows keeps 8 mantissa bits of values that are NOT normalised yet; carried as
+    // hi + lo halves (two MFMAs per fragment) the LayerNorm GEMVs see 16 bits, more than the rounded LN(x) of the prepared path
+    P.lo_off = (c->rows_hilo && !c->f16) ? 64 * (D / 8) : 0;
+    P.pf = c->prefetch > 0 && c->bf16 && c->beam_K == 0 && !c->kv8;
+#endif
+    return P;
+}
+// kernel launches behind a stage.  17..64 rows: a LayerNorm / combining GEMV is gemv_prep_kernel + gemv_mt_kernel
+static int stage_launches(const StepPlan& P, int kind) {
+    const bool prepared = kind == DST_QKV || kind == DST_CROSS_Q || kind == DST_FC1 || kind == DST_CROSS_O, owned = P.own && (kind == DST_FC1 || kind == DST_CROSS_O);
+    return (P.frag && !P.skinny && !P.rows && !P.xfull && prepared && !owned) ? 2 : 1;
+}
+// Books the next launch of the layer and tells whether to issue it.  cw_time_decode_stage runs ONE launch (stage_sel) of ONE layer (layer_sel)
+// through this very code: the kernels it times are the ones the step launches, with the step's arguments; `call` is evaluated for no other launch.
+static bool stage(cw_ctx* c, const StepPlan& P, int kind) {
+    const int s = c->stage_count++;
+    if (s < CW_MAX_DEC_STAGES) { c->stage_kind[s] = kind; c->stage_launches[s] = stage_launches(P, kind); }
+    return c->stage_sel < 0 || c->stage_sel == s;
+}
+#define STG(kind, call) do { if (stage(c, P, (kind))) CWCHK(c, call); } while (0)
+static EpiParams resid_epi(float* x, const float* bias, int D) { EpiParams ep = epi0(); ep.outf = x; ep.resid = x; ep.bias = bias; ep.ldo = D; return ep; }   // x += W a + bias
+static EpiParams qkv_epi(cw_ctx* c, LayerW& L) {   // q -> c->dq; k, v appended to the self-attention cache at pos[b]
+    EpiParams ep = epi0(); ep.outf = c->dq; ep.out1 = L.sk; ep.out2 = L.sv; ep.bias = L.bqkv;
+    ep.H = c->d.n_heads; ep.S_pad = c->d.max_target_positions; ep.d_model = c->d.d_model; ep.row_pos = c->d_pos;
+    return ep;
+}
+static EpiParams cross_q_epi(cw_ctx* c, LayerW& L) { EpiParams ep = epi0(); ep.outf = c->dq; ep.bias = L.bq_c; ep.ldo = c->d.d_model; return ep; }
+static EpiParams fc1_epi(cw_ctx* c, LayerW& L) { EpiParams ep = epi0(); ep.outf = c->dmid; ep.out = c->d_xfrag2; ep.bias = L.b1; ep.ldo = c->d.ffn_dim; return ep; }
+// x += W a + bias.  frag: a = the 16-bit fragment-major rows a producer left in xf; otherwise the f32 (x16: 16-bit) rows `a`
+static int gemv_resid(cw_ctx* c, bool frag, const float* a, void* xf, int nb, int K, const void* W, const float* bias, float* x, int x16 = 0) {
+    const int D = c->d.d_model;
+    EpiParams ep = resid_epi(x, bias, D); ep.x16 = x16;
+    if (frag) return KD(c, cw_launch_gemv, true, EPI_RESID_F32, nullptr, nb, K, W, D, nullptr, nullptr, ep, c->st, nullptr, xf, c->wpacked);
+    return gemv_ln(c, EPI_RESID_F32, a, nb, K, W, D, nullptr, nullptr, ep);
+}
+// keys split over ATT_NS blocks per (row, head).  q null (fused layer): the kernel finishes q_c = rstd(x1) (qa + qb - mean(x1) W'q_c 1) + b'q_c
+static CrossSplitParams cross_params(cw_ctx* c, const StepPlan& P, LayerW& L, int l, int nb, const float* q) {
+    const int H = c->d.n_heads;
+    CrossSplitParams p{q, L.ck, L.cv, CW_N_CTX, c->d_part_o, c->d_part_ml, c->d.n_align > 0 ? c->d_align : nullptr, c->d_align_ml,
+                       c->d_align_slot + (size_t)l * H, c->d_pos, c->d.n_align, c->align_rows, nb, H};
+    p.kv_div = c->beam_K > 0 ? c->beam_K : 1;
+    if (!q) { p.qa = c->d_qa; p.qb = c->d_qb; p.qw = L.q_wsum; p.qbias = L.bq_c; p.pstats = c->d_pstats; p.n_pstats = (c->d.d_model / 16 + P.nt3 - 1) / P.nt3; }
+    return p;
+}
+static int cross_attn(cw_ctx* c, LayerW& L, CrossSplitParams p) {   // over the 16-bit cache or its e4m3 copy
+    if (c->kv8) { p.K = L.ck8; p.V = L.cv8; p.kv_scale = L.kvs; return KD(c, cw_launch_attn_cross_split_fp8, p, c->st); }
+    return KD(c, cw_launch_attn_cross_split, true, p, c->st);
+}
+// the out-projection GEMV combines the key-split partials; x += Wo_c a_c + bo_c in place
+static int cross_out(cw_ctx* c, const StepPlan& P, LayerW& L, int nb, float* x) {
+    const int D = c->d.d_model;
+    const CombineParams cb{c->d_part_ml, c->d.n_heads, nb * D};
+    return KD(c, cw_launch_gemv, true, EPI_RESID_F32, c->d_part_o, nb, D, L.wo_c, D, nullptr, nullptr, resid_epi(x, L.bo_c, D), c->st, &cb, (nb <= 16 || P.frag) ? c->d_xfrag : nullptr, c->wpacked);
+}
+// LN + fc1 + GELU, fc2 + residual on the stream in x.  17..64 rows: LayerNorm preparation + gemv_mt launches, GELU rows fragment-major
+static int launch_mlp(cw_ctx* c, const StepPlan& P, LayerW& L, int nb, float* x) {
+    const int D = c->d.d_model, F = c->d.ffn_dim;
+    STG(DST_FC1, gemv_ln(c, P.frag ? EPI_GELU_FRAG : P.mid16 ? EPI_GELU : EPI_GELU_F32, x, nb, D, L.w1, F, L.ln2_g, c->ln_folded ? nullptr : L.ln2_b, fc1_epi(c, L)));
+    STG(DST_FC2, gemv_resid(c, P.frag, P.mid16 ? (const float*)c->d_xfrag2 : c->dmid, c->d_xfrag2, nb, F, L.w2, L.b2, x, P.mid16 ? 1 : 0));
+    return CW_OK;
+}
+// self-attention over the cache rows the q/k/v projection just appended to: c->dq -> c->dattn
+static int self_attn(cw_ctx* c, const StepPlan& P, LayerW& L, int nb) {
+    DecAttnParams p = dec_attn(c->dq, L.sk, L.sv, c->d.max_target_positions, 0, c->d_pos, c->dattn, nb, c->d.n_heads);
+    if (P.frag && !P.fuse) p.out_frag = (unsigned short*)c->d_xfrag2;   // the fused stage reads the f32 rows
+    if (c->beam_K > 0) p.anc = c->d_anc;
+    p.short_hist = P.short_hist ? 1 : 0;
+    return KD(c, cw_launch_attn_decode, c->bf16, p, c->st);
+}
+// Self-attention front of layer l on the stream in x: qkv_self in one launch, or LN + fused q/k/v projection and attn_decode
+static int layer_self_attention(cw_ctx* c, const StepPlan& P, int l, int nb, const float* x) {
+    const int D = c->d.d_model, H = c->d.n_heads, TGT = c->d.max_target_positions;
+    LayerW& L = c->dec[l];
+    if (!P.qs) {
+        STG(DST_QKV, gemv_ln(c, EPI_QKV_CACHE, x, nb, D, L.wqkv, 3 * D, L.ln1_g, c->ln_folded ? nullptr : L.ln1_b, qkv_epi(c, L)));
+        STG(DST_SELF_ATTN, self_attn(c, P, L, nb));
+        return CW_OK;
+    }
+    QkvSelfParams qp = zeroed<QkvSelfParams>();
+    qp.x = x; qp.W = L.wqkv; qp.bias = L.bqkv; qp.sk = L.sk; qp.sv = L.sv; qp.cap = TGT; qp.pos = c->d_pos; qp.out = c->dattn;
+    qp.gq = c->d_gq2; qp.gkv = c->d_gkv; qp.epoch = c->d_epoch; qp.layer = l; qp.err = c->d_err; qp.Mb = nb; qp.D = D; qp.H = H; qp.fail_pos = c->fail_pos;
+    const int dbg = cw_sw::cw_switches().qkv_self_dbg;   // 1: tiles fused, attention by attn_decode_kernel behind it (bisecting aid)
+    if (dbg) { qp.q_plain = c->dq; qp.no_attn = 1; }
+    STG(DST_QKV_SELF, KD(c, cw_launch_qkv_self, qp, c->st));
+    if (dbg) STG(DST_SELF_ATTN, self_attn(c, P, L, nb));
+    return CW_OK;
+}
+// X1 over [W'q_c ; W'q_c Wo ; Wo]:  qa = W'q_c x + W'q_c bo,  qb = (W'q_c Wo) a,  x1 = x + Wo a + bo
+static StackParams stack_params(cw_ctx* c, LayerW& L, int nb, const float* xin, float* xalt) {
+    const int D = c->d.d_model, TD = D / 16;
+    StackParams sp = zeroed<StackParams>();
+    sp.W = L.ws3; sp.wpk = c->wpacked ? 1 : 0; sp.K = D; sp.Mb = nb; sp.nseg = 3;
+    sp.seg[0].x = xin;      sp.seg[0].bias = L.qa_bias; sp.seg[0].out = c->d_qa; sp.seg[0].tile0 = 0;      sp.seg[0].n_tiles = TD; sp.seg[0].epi = 0;
+    sp.seg[0].wsum = c->stack_center ? L.q_wsum : nullptr;   // x is rounded as x - mean(x): the operand the cross-attention LayerNorm is sensitive to
+    sp.seg[1].x = c->dattn; sp.seg[1].bias = nullptr;   sp.seg[1].out = c->d_qb; sp.seg[1].tile0 = TD;     sp.seg[1].n_tiles = TD; sp.seg[1].epi = 0;
+    sp.seg[2].x = c->dattn; sp.seg[2].bias = L.bo;      sp.seg[2].out = xalt;    sp.seg[2].tile0 = 2 * TD; sp.seg[2].n_tiles = TD; sp.seg[2].epi = 1;
+    sp.seg[2].resid = xin; sp.seg[2].pstats = c->d_pstats;   // LayerNorm partial sums of x1 for the cross-attention
+    return sp;
+}
+// The fused layer behind the self-attention front (<= 16 rows; 17..64 rows in row groups): stack stage, cross-attention, then the column-owning
+// tail (33..64 rows) or the combining out-projection + fc1 / fc2.  Reads the stream from xin, leaves x1, x2, x3 in xalt and exchanges the two.
+static int layer_fused(cw_ctx* c, const StepPlan& P, int l, int nb, float*& xin, float*& xalt) {
+    const int D = c->d.d_model, H = c->d.n_heads, F = c->d.ffn_dim;
+    LayerW& L = c->dec[l];
+    STG(DST_STACK, KD(c, cw_launch_gemv_stack, stack_params(c, L, nb, xin, xalt), P.nt3, c->st));
+    const CrossSplitParams p = cross_params(c, P, L, l, nb, nullptr);
+    STG(DST_CROSS_ATTN, cross_attn(c, L, p));
+    if (P.own) {
+        // combine (+ the rows' centres) -> d_xfrag;  x2 = x1 + Wo_c a_c + bo_c in place, y = x2 - c -> d_xfrag2, partial sums;
+        // fc1 normalises on its accumulator, GELU rows -> d_xfrag;  fc2 as before
+        const CombineParams cb{c->d_part_ml, H, nb * D, c->d_pstats, p.n_pstats, c->d_cvec};
+        STG(DST_OTHER, KD(c, cw_launch_rows_combine, c->d_part_o, nb, D, cb, c->d_xfrag, c->st));
+        STG(DST_CROSS_O, KD(c, cw_launch_gemv_own, c->d_xfrag, nb, D, L.wo_c, D, resid_epi(xalt, L.bo_c, D), c->d_cvec, c->d_xfrag2, c->d_ostats, c->st, c->wpacked));
+        EpiParams ep = epi0(); ep.out = c->d_xfrag; ep.bias = L.b1; ep.ldo = F;
+        STG(DST_FC1, KD(c, cw_launch_gemv_lna, c->d_xfrag2, nb, D, L.w1, F, ep, c->d_ostats, D / (16 * KD(c, cw_gemv_own_nt, D)), L.u1_wsum, c->st, c->wpacked));
+        STG(DST_FC2, gemv_resid(c, true, nullptr, c->d_xfrag, nb, F, L.w2, L.b2, xalt));
+    } else {
+        STG(DST_CROSS_O, cross_out(c, P, L, nb, xalt));
+        CWCHK(c, launch_mlp(c, P, L, nb, xalt));
+    }
+    std::swap(xin, xalt);
+    return CW_OK;
+}
+// The unfused layer behind the self-attention front (f32 parity engine, CW_NO_FUSE6, row-major weights above 16 rows, beam search over
+// the e4m3 cache, ...): gemv_ln everywhere; the f32 engine's cross-attention is attn_decode.  The stream stays in c->dx.
+static int layer_unfused(cw_ctx* c, const StepPlan& P, int l, int nb) {
+    const int D = c->d.d_model, H = c->d.n_heads;
+    LayerW& L = c->dec[l];
+    STG(DST_O_PROJ, gemv_resid(c, P.frag, c->dattn, c->d_xfrag2, nb, D, L.wo, L.bo, c->dx));
+    // cross-attention: LN + q projection, attention over the cached encoder K/V
+    STG(DST_CROSS_Q, gemv_ln(c, EPI_STORE_F32, c->dx, nb, D, L.wq_c, D, L.lnc_g, c->ln_folded ? nullptr : L.lnc_b, cross_q_epi(c, L)));
+    if (c->bf16) {
+        STG(DST_CROSS_ATTN, cross_attn(c, L, cross_params(c, P, L, l, nb, c->dq)));
+        STG(DST_CROSS_O, cross_out(c, P, L, nb, c->dx));
+    } else {
+        DecAttnParams p = dec_attn(c->dq, L.ck, L.cv, CW_N_CTX, CW_N_CTX, c->d_pos, c->dattn, nb, H);
+        p.align_out = c->d.n_align > 0 ? c->d_align : nullptr; p.align_slot = c->d_align_slot + (size_t)l * H;
+        p.n_align = c->d.n_align; p.align_rows = c->align_rows; p.kv_div = c->beam_K > 0 ? c->beam_K : 1;
+        STG(DST_CROSS_ATTN, KD(c, cw_launch_attn_decode, c->bf16, p, c->st));
+        STG(DST_CROSS_O, gemv_resid(c, false, c->dattn, nullptr, nb, D, L.wo_c, L.bo_c, c->dx));
+    }
+    return launch_mlp(c, P, L, nb, c->dx);
+}
+// persistent decoder-layer launch of layer l (declayer.hip): fused out-projection / cross-query stage + cross-attention
+static DecLayerParams dec_layer_params(cw_ctx* c, int l, int nb, const float* xin, float* xalt) {
+    const int D = c->d.d_model, H = c->d.n_heads, TGT = c->d.max_target_positions;
+    LayerW& L = c->dec[l];
+    DecLayerParams dp = zeroed<DecLayerParams>();
+    dp.Ws = L.ws3; dp.x = xin; dp.a = c->dattn; dp.qa_bias = L.qa_bias; dp.q_wsum = c->stack_center ? L.q_wsum : nullptr;
+    dp.bo = L.bo; dp.x1 = xalt;
+    dp.K = L.ck; dp.V = L.cv; dp.n_keys = CW_N_CTX; dp.part_o = c->d_part_o; dp.part_ml = c->d_part_ml;
+    dp.align_out = c->d.n_align > 0 ? c->d_align : nullptr; dp.align_ml = c->d_align_ml;
+    dp.align_slot = c->d_align_slot + (size_t)l * H; dp.pos = c->d_pos; dp.n_align = c->d.n_align; dp.align_rows = c->align_rows;
+    dp.qw = L.q_wsum; dp.qbias = L.bq_c;
+    dp.gq = c->d_gq; dp.gps = c->d_gps; dp.epoch = c->d_epoch; dp.layer = l; dp.err = c->d_err;
+    dp.Mb = nb; dp.D = D; dp.H = H;
+    dp.kv_wait = cw_sw::cw_switches().dl_kvwait;
+    return dp;
+}
 
 #ifdef CW_EXPERIMENTS
-static int launch_prefetch_layer(cw_ctx* c, int l, int nb) {
+// ---- the measured-and-rejected variants (A/B and differential tests only; DESIGN.md "A/B switches") ----------------------------------
+// layer l's streams are touched while layer l - 1 runs (side stream: a parallel graph branch)
+static int launch_prefetch_layer(cw_ctx* c, const StepPlan& P, int l, int nb) {
+    HIPCHK(c, hipEventRecord(c->ev_pf[0], c->st));
+    HIPCHK(c, hipStreamWaitEvent(c->st2, c->ev_pf[0], 0));
     const int D = c->d.d_model, F = c->d.ffn_dim, H = c->d.n_heads;
     const size_t e = c->esz;
     LayerW& L = c->dec[l];
-    PrefetchRanges r;
-    memset(&r, 0, sizeof(r));
+    PrefetchRanges r = zeroed<PrefetchRanges>();
     auto add = [&](const void* p, size_t bytes) { if (p && bytes && r.count < 8) { r.p[r.count] = (const char*)p; r.n[r.count] = bytes; ++r.count; } };
     add(L.wqkv, (size_t)3 * D * D * e);
-    if (c->fuse6_ready && c->fuse6_enabled && nb <= 16 && c->beam_K == 0) add(L.ws3, (size_t)3 * D * D * e);
+    if (P.fuse) add(L.ws3, (size_t)3 * D * D * e);
     else { add(L.wo, (size_t)D * D * e); add(L.wq_c, (size_t)D * D * e); }
     add(L.ck, (size_t)nb * H * CW_N_CTX * 64 * e);
     add(L.cv, (size_t)nb * H * CW_N_CTX * 64 * e);
@@ -1174,375 +1411,165 @@ static int launch_prefetch_layer(cw_ctx* c, int l, int nb) {
     else hipLaunchKernelGGL(prefetch_kernel<0>, dim3(c->prefetch), dim3(256), 0, c->st2, r, c->d_pf_sink);
     return CW_OK;
 }
-#else
-static int launch_prefetch_layer(cw_ctx*, int, int) { return CW_ERR_INVALID; }
-#endif
 
-// persistent decoder-layer launch of layer l (declayer.hip): fused out-projection / cross-query stage + cross-attention
-static DecLayerParams dec_layer_params(cw_ctx* c, int l, int nb, const float* xin, float* xalt) {
-    const int D = c->d.d_model, H = c->d.n_heads, TGT = c->d.max_target_positions;
+// 17..64 rows, unfused, with the rows path (CW_ROWS_LN), the skinny GEMMs (CW_SKINNY=2) and / or the full-key cross-attention (CW_SKINNY=1|2):
+// the whole layer, self-attention front included; the stream stays in c->dx.  ln_nblk: statistics planes the rows path's last producer left.
+static int layer_unfused_ab(cw_ctx* c, const StepPlan& P, int l, int nb, int& ln_nblk) {
+    const int D = c->d.d_model, H = c->d.n_heads, F = c->d.ffn_dim;
     LayerW& L = c->dec[l];
-    DecLayerParams dp;
-    memset(&dp, 0, sizeof(dp));
-    dp.Ws = L.ws3; dp.x = xin; dp.a = c->dattn; dp.qa_bias = L.qa_bias; dp.q_wsum = c->stack_center ? L.q_wsum : nullptr;
-    dp.bo = L.bo; dp.x1 = xalt;
-    dp.K = L.ck; dp.V = L.cv; dp.n_keys = CW_N_CTX; dp.part_o = c->d_part_o; dp.part_ml = c->d_part_ml;
-    dp.align_out = c->d.n_align > 0 ? c->d_align : nullptr; dp.align_ml = c->d_align_ml;
-    dp.align_slot = c->d_align_slot + (size_t)l * H; dp.pos = c->d_pos; dp.n_align = c->d.n_align; dp.align_rows = c->align_rows;
-    dp.qw = L.q_wsum; dp.qbias = L.bq_c;
-    dp.gq = c->d_gq; dp.gps = c->d_gps; dp.epoch = c->d_epoch; dp.layer = l; dp.err = c->d_err;
-    dp.Mb = nb; dp.D = D; dp.H = H;
-    dp.kv_wait = cw_sw::cw_switches().dl_kvwait;
-    return dp;
-}
-
-// One decoder forward for the nb rows at the positions held in c->d_pos (device): 8 launches per layer.
-static int decode_step(cw_ctx* c, int nb, bool want_logits) {
-    const int D = c->d.d_model, H = c->d.n_heads, F = c->d.ffn_dim, V = c->d.vocab_size;
-    const int TGT = c->d.max_target_positions;
-    // 17..64 rows (bf16): producers hand activations to the next GEMV already in MFMA fragment order (no prep launch)
-    const bool frag = c->bf16 && nb > 16 && c->wpacked;      // (row-major weights: groups of 16 rows on the <= 16-row kernels, see gemv_ln)
-    // fused out-projection / cross-query stage (decfuse.hip): greedy rows of one MFMA half tile, 16-bit caches.  The residual
-    // stream then alternates between two buffers: a layer reads x from `xin` and leaves x1, x2, x3 in `xalt`.
-    // (e4m3 cache: the fp8 matrix-core kernel finishes the fused query too; its VALU fallback does not)
-    // 17..64 greedy rows (round 5): the same stage in groups of 16 rows (gemv_stack_kernel's grid y) replaces out-projection,
-    // LayerNorm preparation and query projection -- three of the layer's twelve launches -- by one; the rest of the layer keeps its
-    // preparation + gemv_mt launches, on the alternating buffers.  CW_NO_FUSE_ROWS=1: the twelve launches (A/B).  Batch 64: decode
-    // 4.43 -> 4.28 ms per token step, 64 / 64 clips; over the e4m3 cache 3.47 -> 3.41 once the cross-attention kernel lets wave 0 alone
-    // finish the query (attn_cross_mfma8_kernel<1, 2>; every wave doing it, as at <= 16 rows, measured flat).  CW_NO_FUSE_ROWS8=1: A/B
-    // (the rejected 17..64-row A/B variants of -DCW_EXPERIMENTS builds -- rows path, skinny GEMMs, full-key cross-attention -- keep their
-    // own twelve / nine launches: they read c->dx and d_xfrag, which the fused stage's alternating buffers would leave stale)
-    const bool ab17 = nb > 16 && (c->rows_ln_enabled || c->skinny_mode != 0);
-    const bool fuse = c->bf16 && c->fuse6_ready && c->fuse6_enabled && c->ln_folded && !ab17 && (nb <= 16 || frag) && (nb <= 16 || (c->fuse_rows && nb <= 64 && (!c->kv8 || c->fuse_rows8))) &&
-                      // beam search (round 6): the hypotheses of an item share a cross-attention block that finishes their queries
-                      // (attn_cross_mfma_kernel<.., FUSED>, 16-bit cache); CW_NO_FUSE_BEAM=1: the twelve launches
-                      (c->beam_K == 0 || (c->fuse_beam && !c->kv8 && c->beam_K <= 16 && !c->fuse_mlp)) &&
-                      (!c->kv8 || (KD(c, cw_cross8_is_mfma, CW_N_CTX) && !c->fuse_mlp)) && !((c->fuse_mlp || c->mlp_pair) && nb > 8);
-    float *xin = c->dx, *xalt = c->dx1;
-    // 17..64 rows without preparation launches (decfuse.hip: gemv_rows_kernel): the residual GEMVs own whole columns and leave
-    // the stream in f32, its 16-bit fragment-major copy in d_xfrag and LayerNorm partial sums in d_rstats; the LayerNorm
-    // GEMVs read that copy and normalise their outputs.  d_xfrag2 carries attention outputs and the GELU'd MLP rows.
-    // 17..64 rows, DEFAULT (skinny_mode 0): the round-3 path -- gemv_prep_kernel (LayerNorm / combine -> fragment-major rows) +
-    // gemv_mt_kernel per projection.  A/B only (-DCW_EXPERIMENTS builds, CW_SKINNY=1|2; measured slower in the step,
-    // profiles/r04_b64_skinny_planes_rejected_*): the LayerNorm projections as skinny-M GEMMs (skinny.hip): f32 rows -> K-split
-    // partial planes, finished (statistics, bias, cache / GELU epilogue) by one light launch.  The residual projections stay on
-    // the 16-column K-split GEMV either way: their cost is the f32 atomics (7 ps each), which a wider tile with more K slices multiplies.
-    const bool sk_ok = frag && c->wpacked && c->ln_folded && c->rows_ln_ready && c->d_planes;
-    const bool skinny = sk_ok && c->skinny_mode >= 2;
-    // greedy rows over the 16-bit cache: one cross-attention block per (row, head) over all keys writes the out-projection's
-    // 16-bit rows itself (1280 blocks at 64 rows: the chip is full without key splits)
-    const bool xfull = frag && c->skinny_mode >= 1 && c->beam_K == 0 && !c->kv8 && !c->rows_ln_enabled && H <= 20 && CW_N_CTX <= 24 * 64;
     auto sk_ln = [&](int epi, const void* W, int N, const float* wsum, const EpiParams& ep) -> int {
-        SkinnyParams sp;
-        memset(&sp, 0, sizeof(sp));
-        sp.x = c->dx; sp.W = W; sp.Mb = nb; sp.K = D; sp.N = N; sp.planes = c->d_planes;
+        SkinnyParams sp = zeroed<SkinnyParams>();
+        sp.x = c->dx; sp.W = W; sp.Mb = nb; sp.K = D; sp.N = N; sp.planes = c->d_planes; sp.stats = c->d_sk_stats;
         int smax = (int)(c->planes_cap / ((size_t)nb * N));
         if (smax > 16) smax = 16;
         const int nks = KD(c, cw_skinny_pick_nks, N, D, smax);
         if (nks < 1) return CW_ERR_INVALID;
-        sp.stats = c->d_sk_stats;
         int r = KD(c, cw_launch_skinny, 0, sp, nks, c->st);
         if (r != CW_OK) return r;
-        SkinnyFinishParams fp;
-        memset(&fp, 0, sizeof(fp));
-        fp.planes = c->d_planes; fp.S = (D / 32) / nks; fp.Mb = nb; fp.N = N; fp.x = c->dx; fp.K = D; fp.wsum = wsum; fp.ep = ep;
-        fp.stats = c->d_sk_stats;
+        SkinnyFinishParams fp = zeroed<SkinnyFinishParams>();
+        fp.planes = c->d_planes; fp.S = (D / 32) / nks; fp.Mb = nb; fp.N = N; fp.x = c->dx; fp.K = D; fp.wsum = wsum; fp.ep = ep; fp.stats = c->d_sk_stats;
         return KD(c, cw_launch_skinny_finish, epi, fp, c->st);
     };
-    const bool rows = !skinny && frag && c->rows_ln_ready && c->rows_ln_enabled && c->ln_folded && D <= 1280;
-    int ln_nblk = 1;
-    // bf16 only: the 16-bit copy of the residual rows keeps 8 mantissa bits of values that are NOT normalised yet; carried as
-    // hi + lo halves (two MFMAs per fragment) the LayerNorm GEMVs see 16 bits, more than the rounded LN(x) of the prepared path
-    const int lo_off = (c->rows_hilo && !c->f16) ? 64 * (D / 8) : 0;
+    auto rows_params = [&](const void* xf, const void* W, int K, int N, const EpiParams& ep) {
+        RowsParams rp = zeroed<RowsParams>();
+        rp.xf = xf; rp.W = W; rp.Mb = nb; rp.K = K; rp.N = N; rp.wpk = c->wpacked ? 1 : 0; rp.ep = ep; rp.lo_off = P.lo_off;
+        return rp;
+    };
     auto rows_consume = [&](int epi, const void* W, int N, const EpiParams& ep, const float* wsum) -> int {
-        RowsParams rp;
-        memset(&rp, 0, sizeof(rp));
-        rp.xf = c->d_xfrag; rp.W = W; rp.Mb = nb; rp.K = D; rp.N = N; rp.wpk = c->wpacked ? 1 : 0; rp.ep = ep;
-        rp.ln_pstats = c->d_rstats; rp.ln_nblk = ln_nblk; rp.ln_wsum = wsum; rp.lo_off = lo_off;
+        RowsParams rp = rows_params(c->d_xfrag, W, D, N, ep);
+        rp.ln_pstats = c->d_rstats; rp.ln_nblk = ln_nblk; rp.ln_wsum = wsum;
         return KD(c, cw_launch_gemv_rows, epi, false, rp, c->st);
     };
     auto rows_produce = [&](const void* W, int K, const float* bias) -> int {   // x += W a + b over the rows in d_xfrag2
-        RowsParams rp;
-        memset(&rp, 0, sizeof(rp));
-        rp.xf = c->d_xfrag2; rp.W = W; rp.Mb = nb; rp.K = K; rp.N = D; rp.wpk = c->wpacked ? 1 : 0;
-        rp.ep = epi0(); rp.ep.outf = c->dx; rp.ep.resid = c->dx; rp.ep.bias = bias; rp.ep.ldo = D;
-        rp.xf_out = c->d_xfrag; rp.pstats_out = c->d_rstats; rp.lo_off = lo_off;
+        RowsParams rp = rows_params(c->d_xfrag2, W, K, D, resid_epi(c->dx, bias, D));
+        rp.xf_out = c->d_xfrag; rp.pstats_out = c->d_rstats;
         ln_nblk = D / 16;
         return KD(c, cw_launch_gemv_rows, (int)EPI_RESID_F32, true, rp, c->st);
     };
-    if (rows) CWCHK(c, KD(c, cw_launch_rows_prep, c->dx, nb, D, c->d_xfrag, c->d_rstats, lo_off, c->st));
-    // 33..64 rows behind the fused stage (round 6): the cross-attention out-projection owns whole columns (no K split, no atomics) and
-    // leaves fc1 its 16-bit rows and LayerNorm partial sums -- one preparation launch less per layer (gemm.hip: gemv_mt_kernel OWN / LNA)
-    const bool own = c->own_cols && fuse && frag && nb > 32 && !c->fuse_mlp && !c->mlp_pair && c->rows_ln_ready && D % 32 == 0 && D / 16 <= 96 && D <= 1536 &&
-                     D % 128 == 0 && F % 32 == 0;
-    const bool pf = c->prefetch > 0 && c->bf16 && c->beam_K == 0 && !c->kv8;
-    // cw_time_decode_stage runs ONE launch (stage_sel) of ONE layer (layer_sel) through this very code: the kernels it times are
-    // the ones the step launches, with the step's arguments
-#define STG(kind, call)                                                                             \
-    do {                                                                                            \
-        if (c->stage_sel < 0 || c->stage_sel == stage_no) CWCHK(c, call);                           \
-        if (stage_no < CW_MAX_DEC_STAGES) {                                                         \
-            c->stage_kind[stage_no] = (kind);                                                       \
-            /* 17..64 rows: a LayerNorm / combining GEMV is gemv_prep_kernel + gemv_mt_kernel */    \
-            c->stage_launches[stage_no] = 1 + ((frag && !skinny && !rows && !xfull && ((kind) == DST_QKV || (kind) == DST_CROSS_Q || (kind) == DST_FC1 || (kind) == DST_CROSS_O) && \
-                                                !(own && ((kind) == DST_FC1 || (kind) == DST_CROSS_O))) ? 1 : 0); \
-        }                                                                                           \
-        c->stage_count = ++stage_no;                                                                \
-    } while (0)
-    const int l_lo = c->layer_sel >= 0 ? c->layer_sel : 0, l_hi = c->layer_sel >= 0 ? c->layer_sel + 1 : c->d.dec_layers;
-    for (int l = l_lo; l < l_hi; ++l) {
-        LayerW& L = c->dec[l];
-        int stage_no = 0;
-        if (pf && l + 1 < c->d.dec_layers) {   // layer l + 1's streams are touched while layer l runs (side stream: a parallel graph branch)
-            HIPCHK(c, hipEventRecord(c->ev_pf[0], c->st));
-            HIPCHK(c, hipStreamWaitEvent(c->st2, c->ev_pf[0], 0));
-            CWCHK(c, launch_prefetch_layer(c, l + 1, nb));
-        }
-        // rows <= 8, 16-bit engines: LN + q/k/v projection + self-attention as ONE launch (declayer.hip: qkv_self_kernel; the tiles
-        // reach the attention blocks as granules, the history rows of the cache are requested at kernel entry); bit-identical
-        // (its 3 D / 16 blocks wait for each other: only where the whole grid is resident at once on this part; layer < 64: granule tag)
-        const bool qs = c->qkv_self && c->bf16 && c->ln_folded && c->wpacked && nb <= 8 && c->beam_K == 0 && D <= 1280 && nb * H <= 3 * (D / 16) && TGT <= 512 &&
-                        c->d.dec_layers <= 64 && 3 * (D / 16) <= c->n_cu * KD(c, cw_qkv_self_blocks_per_cu, D, TGT);
-        if (qs) {
-            QkvSelfParams qp;
-            memset(&qp, 0, sizeof(qp));
-            qp.x = xin; qp.W = L.wqkv; qp.bias = L.bqkv; qp.sk = L.sk; qp.sv = L.sv; qp.cap = TGT; qp.pos = c->d_pos; qp.out = c->dattn;
-            qp.gq = c->d_gq2; qp.gkv = c->d_gkv; qp.epoch = c->d_epoch; qp.layer = l; qp.err = c->d_err; qp.Mb = nb; qp.D = D; qp.H = H; qp.fail_pos = c->fail_pos;
-            const int dbg = cw_sw::cw_switches().qkv_self_dbg;   // 1: tiles fused, attention by attn_decode_kernel behind it (bisecting aid)
-            if (dbg) { qp.q_plain = c->dq; qp.no_attn = 1; }
-            STG(DST_QKV_SELF, KD(c, cw_launch_qkv_self, qp, c->st));
-            if (dbg) {
-                DecAttnParams p = dec_attn(c->dq, L.sk, L.sv, TGT, 0, c->d_pos, c->dattn, nb, H);
-                STG(DST_SELF_ATTN, KD(c, cw_launch_attn_decode, c->bf16, p, c->st));
-            }
-        } else {
-        {   // LN + fused q/k/v projection; k,v appended to the self-attention cache at pos[b]
-            EpiParams ep = epi0(); ep.outf = c->dq; ep.out1 = L.sk; ep.out2 = L.sv; ep.bias = L.bqkv;
-            ep.H = H; ep.S_pad = TGT; ep.d_model = D; ep.row_pos = c->d_pos;
-            if (skinny) STG(DST_QKV, sk_ln(EPI_QKV_CACHE, L.wqkv, 3 * D, L.qkv_wsum, ep));
-            else if (rows) STG(DST_QKV, rows_consume(EPI_QKV_CACHE, L.wqkv, 3 * D, ep, L.qkv_wsum));
-            else STG(DST_QKV, gemv_ln(c, EPI_QKV_CACHE, xin, nb, D, L.wqkv, 3 * D, L.ln1_g, c->ln_folded ? nullptr : L.ln1_b, ep));
-        }
-        {
-            DecAttnParams p = dec_attn(c->dq, L.sk, L.sv, TGT, 0, c->d_pos, c->dattn, nb, H);
-            if (frag && !fuse) p.out_frag = (unsigned short*)c->d_xfrag2;   // the fused stage reads the f32 rows
-            if (c->beam_K > 0) p.anc = c->d_anc;
-            p.short_hist = (c->hist_short && c->short_hist_enabled && nb > 8) ? 1 : 0;   // bytes matter from 9 rows up (<= 8: latency-bound, qkv_self)
-            STG(DST_SELF_ATTN, KD(c, cw_launch_attn_decode, c->bf16, p, c->st));
-        }
-        }
-        if (fuse) {
-            const int TD = D / 16, TF = F / 16;
-            // column tiles per X1 block (3 * TD blocks at 1: 240 at large-v3).  17..64 rows: two -- a block's 16 f32 rows are twice the bytes
-            // of a weight tile, and a pair of tiles shares them (64 rows, 4 groups: 11.2 us at one tile, 10.5 at two, 15.5 at three)
-            const int nt3 = c->stack_nt3 > 0 ? c->stack_nt3 : (nb > 16 ? 2 : 1);
-            // rows <= 8: X1 and the cross-attention as ONE persistent launch (declayer.hip): the K/V rows are requested at kernel
-            // entry and stream under the GEMV tile; qa / qb / the partial sums cross CUs as granules.  Bit-identical to the two launches.
-            const bool dl = c->declayer && !c->kv8 && !c->fuse_mlp && nt3 == 1 && c->wpacked && nb <= 8 && 3 * TD <= c->n_cu &&
-                            nb * H * ATT_NS <= 4 * c->n_cu && TD <= 128 && KD(c, cw_dec_layer_lds, D) <= (size_t)160 * 1024;
-            if (dl) {
-                const DecLayerParams dp = dec_layer_params(c, l, nb, xin, xalt);
-                STG(DST_STACK_CROSS, KD(c, cw_launch_dec_layer, dp, c->n_cu, c->st));
-            } else
-            {   // X1 over [W'q_c ; W'q_c Wo ; Wo]:  qa = W'q_c x + W'q_c bo,  qb = (W'q_c Wo) a,  x1 = x + Wo a + bo
-                StackParams sp;
-                memset(&sp, 0, sizeof(sp));
-                sp.W = L.ws3; sp.wpk = c->wpacked ? 1 : 0; sp.K = D; sp.Mb = nb; sp.nseg = 3;
-                sp.seg[0].x = xin;      sp.seg[0].bias = L.qa_bias; sp.seg[0].out = c->d_qa; sp.seg[0].tile0 = 0;      sp.seg[0].n_tiles = TD; sp.seg[0].epi = 0;
-                sp.seg[0].wsum = c->stack_center ? L.q_wsum : nullptr;   // x is rounded as x - mean(x): the operand the cross-attention LayerNorm is sensitive to
-                sp.seg[1].x = c->dattn; sp.seg[1].bias = nullptr;   sp.seg[1].out = c->d_qb; sp.seg[1].tile0 = TD;     sp.seg[1].n_tiles = TD; sp.seg[1].epi = 0;
-                sp.seg[2].x = c->dattn; sp.seg[2].bias = L.bo;      sp.seg[2].out = xalt;    sp.seg[2].tile0 = 2 * TD; sp.seg[2].n_tiles = TD; sp.seg[2].epi = 1;
-                sp.seg[2].resid = xin; sp.seg[2].pstats = c->d_pstats;   // LayerNorm partial sums of x1 for the cross-attention
-                if (c->fuse_mlp) { sp.zero = c->d_u1; sp.zero_n4 = nb * F / 4; }   // X2 below accumulates its two halves into u1
-                STG(DST_STACK, KD(c, cw_launch_gemv_stack, sp, nt3, c->st));
-            }
-            // cross-attention; the kernel finishes q_c = rstd(x1) (qa + qb - mean(x1) W'q_c 1) + b'q_c
-            CrossSplitParams p{nullptr, L.ck, L.cv, CW_N_CTX, c->d_part_o, c->d_part_ml,
-                               c->d.n_align > 0 ? c->d_align : nullptr, c->d_align_ml, c->d_align_slot + (size_t)l * H,
-                               c->d_pos, c->d.n_align, c->align_rows, nb, H};
-            p.kv_div = c->beam_K > 0 ? c->beam_K : 1;
-            p.qa = c->d_qa; p.qb = c->d_qb; p.qw = L.q_wsum; p.qbias = L.bq_c;
-            p.pstats = c->d_pstats; p.n_pstats = (TD + nt3 - 1) / nt3;
-            if (!c->fuse_mlp) {
-                if (c->kv8) {
-                    p.K = L.ck8; p.V = L.cv8; p.kv_scale = L.kvs;
-                    STG(DST_CROSS_ATTN, KD(c, cw_launch_attn_cross_split_fp8, p, c->st));
-                } else
-                if (!dl) STG(DST_CROSS_ATTN, KD(c, cw_launch_attn_cross_split, true, p, c->st));
-                if (own) {
-                    // combine (+ the rows' centres) -> d_xfrag;  x2 = x1 + Wo_c a_c + bo_c in place, y = x2 - c -> d_xfrag2, partial sums;
-                    // fc1 normalises on its accumulator, GELU rows -> d_xfrag;  fc2 as before
-                    CombineParams cb{c->d_part_ml, H, nb * D, c->d_pstats, p.n_pstats, c->d_cvec};
-                    STG(DST_OTHER, KD(c, cw_launch_rows_combine, c->d_part_o, nb, D, cb, c->d_xfrag, c->st));
-                    {
-                        EpiParams ep = epi0(); ep.outf = xalt; ep.resid = xalt; ep.bias = L.bo_c; ep.ldo = D;
-                        STG(DST_CROSS_O, KD(c, cw_launch_gemv_own, c->d_xfrag, nb, D, L.wo_c, D, ep, c->d_cvec, c->d_xfrag2, c->d_ostats, c->st, c->wpacked));
-                    }
-                    {
-                        EpiParams ep = epi0(); ep.out = c->d_xfrag; ep.bias = L.b1; ep.ldo = F;
-                        STG(DST_FC1, KD(c, cw_launch_gemv_lna, c->d_xfrag2, nb, D, L.w1, F, ep, c->d_ostats, D / (16 * KD(c, cw_gemv_own_nt, D)), L.u1_wsum, c->st, c->wpacked));
-                    }
-                    {
-                        EpiParams ep = epi0(); ep.outf = xalt; ep.resid = xalt; ep.bias = L.b2; ep.ldo = D;
-                        STG(DST_FC2, KD(c, cw_launch_gemv, true, EPI_RESID_F32, nullptr, nb, F, L.w2, D, nullptr, nullptr, ep, c->st, nullptr, c->d_xfrag, c->wpacked));
-                    }
-                    float* t = xin; xin = xalt; xalt = t;
-                    continue;
-                }
-                {   // out-projection combines the key-split partials; x2 = x1 + Wo_c a_c + bo_c in place
-                    EpiParams ep = epi0(); ep.outf = xalt; ep.resid = xalt; ep.bias = L.bo_c; ep.ldo = D;
-                    CombineParams cb{c->d_part_ml, H, nb * D};
-                    STG(DST_CROSS_O, KD(c, cw_launch_gemv, true, EPI_RESID_F32, c->d_part_o, nb, D, L.wo_c, D, nullptr, nullptr, ep, c->st, &cb, c->d_xfrag, c->wpacked));
-                }
-                if (c->mlp_pair && F % D == 0 && D % 32 == 0 && F / 32 <= 256 && F / D <= 32) {
-                    // LN + fc1 + GELU, group barrier, fc2 + residual in one launch (decfuse.hip: mlp_pair_kernel)
-                    MlpPairParams mp{xalt, L.w1, L.b1, L.w2, L.b2, c->d_xfrag2, c->d_bar, c->d_err, nb, D, F, c->wpacked ? 1 : 0, c->mlp_pair_fence ? 1 : 0};
-                    STG(DST_MLP_PAIR, KD(c, cw_launch_mlp_pair, mp, c->st));
-                } else if (c->mlp_chain && c->wpacked && c->mid16 && nb <= 8 && KD(c, cw_mlp_chain_ok, nb, D, F)) {
-                    // LN + fc1 + GELU and fc2 + residual in ONE launch: fc2's blocks request their weights at kernel entry and wait for
-                    // the fc1 blocks' flags instead of a kernel boundary (declayer.hip: mlp_chain_kernel); bit-identical
-                    MlpChainParams mp;
-                    memset(&mp, 0, sizeof(mp));
-                    mp.x = xalt; mp.W1 = L.w1; mp.b1 = L.b1; mp.W2 = L.w2; mp.b2 = L.b2; mp.xio = xalt; mp.mid = c->d_xfrag2;
-                    mp.flags = c->d_gflag; mp.epoch = c->d_epoch; mp.layer = l; mp.err = c->d_err; mp.Mb = nb; mp.D = D; mp.F = F;
-                    STG(DST_MLP_CHAIN, KD(c, cw_launch_mlp_chain, mp, c->st));
-                } else if (frag) {
-                    // 17..64 rows: LayerNorm preparation + gemv_mt launches of the twelve-launch layer, on the alternating buffer
-                    {
-                        EpiParams ep = epi0(); ep.outf = c->dmid; ep.out = c->d_xfrag2; ep.bias = L.b1; ep.ldo = F;
-                        STG(DST_FC1, gemv_ln(c, EPI_GELU_FRAG, xalt, nb, D, L.w1, F, L.ln2_g, c->ln_folded ? nullptr : L.ln2_b, ep));
-                    }
-                    {
-                        EpiParams ep = epi0(); ep.outf = xalt; ep.resid = xalt; ep.bias = L.b2; ep.ldo = D;
-                        STG(DST_FC2, KD(c, cw_launch_gemv, true, EPI_RESID_F32, nullptr, nb, F, L.w2, D, nullptr, nullptr, ep, c->st, nullptr, c->d_xfrag2, c->wpacked));
-                    }
-                } else {
-                    // fc1 writes gelu(.) in the 16-bit type fc2 would round it to anyway (bit-identical): fc2's activation load halves
-                    const bool mid16 = F > 1280 && c->mid16;
-                    {
-                        EpiParams ep = epi0(); ep.outf = c->dmid; ep.out = c->d_xfrag2; ep.bias = L.b1; ep.ldo = F;
-                        STG(DST_FC1, gemv_ln(c, mid16 ? EPI_GELU : EPI_GELU_F32, xalt, nb, D, L.w1, F, L.ln2_g, nullptr, ep));
-                    }
-                    {
-                        EpiParams ep = epi0(); ep.outf = xalt; ep.resid = xalt; ep.bias = L.b2; ep.ldo = D; ep.x16 = mid16 ? 1 : 0;
-                        STG(DST_FC2, gemv_ln(c, EPI_RESID_F32, mid16 ? (const float*)c->d_xfrag2 : c->dmid, nb, F, L.w2, D, nullptr, nullptr, ep));
-                    }
-                }
-                float* t = xin; xin = xalt; xalt = t;
-                continue;
-            }
-            // A/B (CW_FUSE_MLP=1), measured slower: cross out-projection + fc1 fused the same way.  Needs the
-            // finished attention output in one plane (one block per (row, head): 17 us against 12) and makes every fc2 block
-            // redo the statistics and the GELU of its K slice.
-            p.a_out = c->dattn; p.xstat = xalt;
-            STG(DST_CROSS_ATTN, KD(c, cw_launch_attn_cross_split, true, p, c->st));
-            {   // X2 over [W'1 ; W'1 Wo_c ; Wo_c]:  u1 = W'1 x1 + W'1 bo_c + (W'1 Wo_c) a_c (two halves, atomics into the zeros X1
-                // left: two commutative additions, so the order does not matter),  x2 = x1 + Wo_c a_c + bo_c (+ a copy that
-                // fc2 takes the LayerNorm statistics of while its atomics are already modifying the stream)
-                StackParams sp;
-                memset(&sp, 0, sizeof(sp));
-                sp.W = L.ws5; sp.wpk = c->wpacked ? 1 : 0; sp.K = D; sp.Mb = nb; sp.nseg = 3;
-                sp.seg[0].x = xalt;     sp.seg[0].bias = L.u1_bias; sp.seg[0].out = c->d_u1; sp.seg[0].tile0 = 0;      sp.seg[0].n_tiles = TF; sp.seg[0].epi = 2;
-                sp.seg[0].wsum = c->stack_center ? L.u1_wsum : nullptr;
-                sp.seg[1].x = c->dattn; sp.seg[1].bias = nullptr;   sp.seg[1].out = c->d_u1; sp.seg[1].tile0 = TF;     sp.seg[1].n_tiles = TF; sp.seg[1].epi = 2;
-                sp.seg[2].x = c->dattn; sp.seg[2].bias = L.bo_c;    sp.seg[2].out = xin;     sp.seg[2].tile0 = 2 * TF; sp.seg[2].n_tiles = TD; sp.seg[2].epi = 1;
-                sp.seg[2].resid = xalt; sp.seg[2].out2 = c->dx2c;
-                STG(DST_STACK, KD(c, cw_launch_gemv_stack, sp, c->stack_nt5, c->st));
-            }
-            {   // fc2: mid = gelu(rstd(x2) (u1 - mean(x2) W'1 1) + b'1) on load; x3 = x2 + W2 mid + b2 in place
-                Fc2xParams fp{c->dx2c, c->d_u1, L.u1_wsum, L.b1, L.w2, L.b2, xin, nb, D, F, c->wpacked ? 1 : 0};
-                STG(DST_FC2, KD(c, cw_launch_gemv_fc2x, fp, c->st));
-            }
-            continue;
-        }
-        {
-            EpiParams ep = epi0(); ep.outf = c->dx; ep.resid = c->dx; ep.bias = L.bo; ep.ldo = D;
-            if (rows) STG(DST_O_PROJ, rows_produce(L.wo, D, L.bo));
-            else if (frag) STG(DST_O_PROJ, KD(c, cw_launch_gemv, true, EPI_RESID_F32, nullptr, nb, D, L.wo, D, nullptr, nullptr, ep, c->st, nullptr, c->d_xfrag2, c->wpacked));
-            else STG(DST_O_PROJ, gemv_ln(c, EPI_RESID_F32, c->dattn, nb, D, L.wo, D, nullptr, nullptr, ep));
-        }
-        if (xfull) {
-            CrossSplitParams p{c->dq, L.ck, L.cv, CW_N_CTX, c->d_part_o, c->d_part_ml,
-                               c->d.n_align > 0 ? c->d_align : nullptr, c->d_align_ml, c->d_align_slot + (size_t)l * H,
-                               c->d_pos, c->d.n_align, c->align_rows, nb, H};
-            p.kv_div = 1; p.a_frag = c->d_xfrag;
-            if (sk_ok) {   // W'q_c (x - c) over K slices -> planes; the attention blocks apply rstd (sum - mean W'q_c 1) + b'q_c
-                SkinnyParams sp;
-                memset(&sp, 0, sizeof(sp));
-                sp.x = c->dx; sp.W = L.wq_c; sp.Mb = nb; sp.K = D; sp.N = D; sp.planes = c->d_planes;
-                const int nks = KD(c, cw_skinny_pick_nks, D, D, (int)(c->planes_cap / ((size_t)nb * D)));
-                if (nks < 1) return fail(c, CW_ERR_INVALID, "no K split for the cross-attention query GEMM");
-                STG(DST_OTHER, KD(c, cw_launch_skinny, 0, sp, nks, c->st));
-                p.q = nullptr; p.xstat = c->dx; p.qa = c->d_planes; p.q_planes = (D / 32) / nks; p.q_plane_stride = nb * D;
-                p.qw = L.q_wsum; p.qbias = L.bq_c;
-            } else {
-                EpiParams ep = epi0(); ep.outf = c->dq; ep.bias = L.bq_c; ep.ldo = D;
-                STG(DST_CROSS_Q, gemv_ln(c, EPI_STORE_F32, c->dx, nb, D, L.wq_c, D, L.lnc_g, c->ln_folded ? nullptr : L.lnc_b, ep));
-            }
-            STG(DST_CROSS_ATTN, KD(c, cw_launch_attn_cross_split, true, p, c->st));
-            EpiParams ep = epi0(); ep.outf = c->dx; ep.resid = c->dx; ep.bias = L.bo_c; ep.ldo = D;
-            STG(DST_CROSS_O, KD(c, cw_launch_gemv, true, EPI_RESID_F32, nullptr, nb, D, L.wo_c, D, nullptr, nullptr, ep, c->st, nullptr, c->d_xfrag, c->wpacked));
-        } else {
-        {   // cross-attention: LN + q projection, attention over the cached encoder K/V
-            EpiParams ep = epi0(); ep.outf = c->dq; ep.bias = L.bq_c; ep.ldo = D;
-            if (skinny) STG(DST_CROSS_Q, sk_ln(EPI_STORE_F32, L.wq_c, D, L.q_wsum, ep));
-            else if (rows) STG(DST_CROSS_Q, rows_consume(EPI_STORE_F32, L.wq_c, D, ep, L.q_wsum));
-            else STG(DST_CROSS_Q, gemv_ln(c, EPI_STORE_F32, c->dx, nb, D, L.wq_c, D, L.lnc_g, c->ln_folded ? nullptr : L.lnc_b, ep));
-        }
-        if (c->bf16) {
-            // keys split over ATT_NS blocks per (row, head); the out-projection GEMV combines the partials
-            CrossSplitParams p{c->dq, L.ck, L.cv, CW_N_CTX, c->d_part_o, c->d_part_ml,
-                               c->d.n_align > 0 ? c->d_align : nullptr, c->d_align_ml, c->d_align_slot + (size_t)l * H,
-                               c->d_pos, c->d.n_align, c->align_rows, nb, H};
-            p.kv_div = c->beam_K > 0 ? c->beam_K : 1;
-            if (c->kv8) {
-                p.K = L.ck8; p.V = L.cv8; p.kv_scale = L.kvs;
-                STG(DST_CROSS_ATTN, KD(c, cw_launch_attn_cross_split_fp8, p, c->st));
-            } else STG(DST_CROSS_ATTN, KD(c, cw_launch_attn_cross_split, true, p, c->st));
-            EpiParams ep = epi0(); ep.outf = c->dx; ep.resid = c->dx; ep.bias = L.bo_c; ep.ldo = D;
-            CombineParams cb{c->d_part_ml, H, nb * D};
-            if (rows) {
-                STG(DST_OTHER, KD(c, cw_launch_rows_combine, c->d_part_o, nb, D, cb, c->d_xfrag2, c->st));
-                STG(DST_CROSS_O, rows_produce(L.wo_c, D, L.bo_c));
-            } else STG(DST_CROSS_O, KD(c, cw_launch_gemv, true, EPI_RESID_F32, c->d_part_o, nb, D, L.wo_c, D, nullptr, nullptr, ep, c->st, &cb, (nb <= 16 || frag) ? c->d_xfrag : nullptr, c->wpacked));
-        } else {
-            DecAttnParams p = dec_attn(c->dq, L.ck, L.cv, CW_N_CTX, CW_N_CTX, c->d_pos, c->dattn, nb, H);
-            p.align_out = c->d.n_align > 0 ? c->d_align : nullptr; p.align_slot = c->d_align_slot + (size_t)l * H;
-            p.n_align = c->d.n_align; p.align_rows = c->align_rows;
-            p.kv_div = c->beam_K > 0 ? c->beam_K : 1;
-            STG(DST_CROSS_ATTN, KD(c, cw_launch_attn_decode, c->bf16, p, c->st));
-            EpiParams ep = epi0(); ep.outf = c->dx; ep.resid = c->dx; ep.bias = L.bo_c; ep.ldo = D;
-            STG(DST_CROSS_O, gemv_ln(c, EPI_RESID_F32, c->dattn, nb, D, L.wo_c, D, nullptr, nullptr, ep));
-        }
-        }
-        {
-            EpiParams ep = epi0(); ep.outf = c->dmid; ep.out = c->d_xfrag2; ep.bias = L.b1; ep.ldo = F;
-            if (skinny) STG(DST_FC1, sk_ln(EPI_GELU_FRAG, L.w1, F, L.u1_wsum, ep));
-            else if (rows) STG(DST_FC1, rows_consume(EPI_GELU_FRAG, L.w1, F, ep, L.u1_wsum));
-            else STG(DST_FC1, gemv_ln(c, frag ? EPI_GELU_FRAG : EPI_GELU_F32, c->dx, nb, D, L.w1, F, L.ln2_g, c->ln_folded ? nullptr : L.ln2_b, ep));
-        }
-        {
-            EpiParams ep = epi0(); ep.outf = c->dx; ep.resid = c->dx; ep.bias = L.b2; ep.ldo = D;
-            if (rows) STG(DST_FC2, rows_produce(L.w2, F, L.b2));
-            else if (frag) STG(DST_FC2, KD(c, cw_launch_gemv, true, EPI_RESID_F32, nullptr, nb, F, L.w2, D, nullptr, nullptr, ep, c->st, nullptr, c->d_xfrag2, c->wpacked));
-            else STG(DST_FC2, gemv_ln(c, EPI_RESID_F32, c->dmid, nb, F, L.w2, D, nullptr, nullptr, ep));
-        }
+    auto ln_gemv = [&](int epi, const void* W, int N, const float* wsum, const float* g, const float* b, const EpiParams& ep) -> int {   // W LN(x)
+        if (P.skinny) return sk_ln(epi, W, N, wsum, ep);
+        if (P.rows) return rows_consume(epi, W, N, ep, wsum);
+        return gemv_ln(c, epi, c->dx, nb, D, W, N, g, c->ln_folded ? nullptr : b, ep);
+    };
+    auto resid_gemv = [&](const void* W, int K, const float* bias) -> int { return P.rows ? rows_produce(W, K, bias) : gemv_resid(c, true, nullptr, c->d_xfrag2, nb, K, W, bias, c->dx); };
+    STG(DST_QKV, ln_gemv(EPI_QKV_CACHE, L.wqkv, 3 * D, L.qkv_wsum, L.ln1_g, L.ln1_b, qkv_epi(c, L)));
+    STG(DST_SELF_ATTN, self_attn(c, P, L, nb));
+    STG(DST_O_PROJ, resid_gemv(L.wo, D, L.bo));
+    CrossSplitParams p = cross_params(c, P, L, l, nb, c->dq);
+    if (P.xfull && P.sk_ok) {   // W'q_c (x - c) over K slices -> planes; the attention blocks apply rstd (sum - mean W'q_c 1) + b'q_c
+        SkinnyParams sp = zeroed<SkinnyParams>();
+        sp.x = c->dx; sp.W = L.wq_c; sp.Mb = nb; sp.K = D; sp.N = D; sp.planes = c->d_planes;
+        const int nks = KD(c, cw_skinny_pick_nks, D, D, (int)(c->planes_cap / ((size_t)nb * D)));
+        if (nks < 1) return fail(c, CW_ERR_INVALID, "no K split for the cross-attention query GEMM");
+        STG(DST_OTHER, KD(c, cw_launch_skinny, 0, sp, nks, c->st));
+        p.q = nullptr; p.xstat = c->dx; p.qa = c->d_planes; p.q_planes = (D / 32) / nks; p.q_plane_stride = nb * D;
+        p.qw = L.q_wsum; p.qbias = L.bq_c;
+    } else STG(DST_CROSS_Q, ln_gemv(EPI_STORE_F32, L.wq_c, D, L.q_wsum, L.lnc_g, L.lnc_b, cross_q_epi(c, L)));   // (xfull excludes the rows path)
+    if (P.xfull) {   // one block per (row, head) over all keys, 16-bit cache; writes the out-projection's fragment-major rows itself
+        p.a_frag = c->d_xfrag;
+        STG(DST_CROSS_ATTN, KD(c, cw_launch_attn_cross_split, true, p, c->st));
+        STG(DST_CROSS_O, gemv_resid(c, true, nullptr, c->d_xfrag, nb, D, L.wo_c, L.bo_c, c->dx));
+    } else {
+        STG(DST_CROSS_ATTN, cross_attn(c, L, p));
+        if (P.rows) {
+            const CombineParams cb{c->d_part_ml, H, nb * D};
+            STG(DST_OTHER, KD(c, cw_launch_rows_combine, c->d_part_o, nb, D, cb, c->d_xfrag2, c->st));
+            STG(DST_CROSS_O, rows_produce(L.wo_c, D, L.bo_c));
+        } else STG(DST_CROSS_O, cross_out(c, P, L, nb, c->dx));
     }
-#undef STG
-    if (pf && c->d.dec_layers > 1) {           // join the side stream (required before the capture ends; the last prefetch is long done)
-        HIPCHK(c, hipEventRecord(c->ev_pf[1], c->st2));
-        HIPCHK(c, hipStreamWaitEvent(c->st, c->ev_pf[1], 0));
-    }
-    if (want_logits) {   // final LN + tied proj_out (:790, :1080), logits in f32 (utils.py:2894)
-        EpiParams ep = epi0(); ep.outf = c->dlogits; ep.ldo = c->Vpad;
-        CWCHK(c, gemv_ln(c, EPI_STORE_F32, xin, nb, D, (c->bf16 && c->wpacked) ? c->embed_pk : c->embed, V, c->dec_ln_g, c->dec_ln_b, ep));
-    }
+    STG(DST_FC1, ln_gemv(EPI_GELU_FRAG, L.w1, F, L.u1_wsum, L.ln2_g, L.ln2_b, fc1_epi(c, L)));
+    STG(DST_FC2, resid_gemv(L.w2, F, L.b2));
     return CW_OK;
 }
 
-static int launch_sample(cw_ctx* c, int nb, bool forced) {
-    SampleParams sp;
-    memset(&sp, 0, sizeof(sp));
+// The fused layer behind the self-attention front with stage A of declayer.hip (CW_DECLAYER), the X2 tail (CW_FUSE_MLP), mlp_pair or
+// mlp_chain in it (rows <= 8).  Stream buffers as in layer_fused, except that X2 writes the stream back to xin (no exchange).
+static int layer_fused_ab(cw_ctx* c, const StepPlan& P, int l, int nb, float*& xin, float*& xalt) {
+    const int D = c->d.d_model, F = c->d.ffn_dim, TD = D / 16, TF = F / 16;
+    LayerW& L = c->dec[l];
+    if (P.dl) STG(DST_STACK_CROSS, KD(c, cw_launch_dec_layer, dec_layer_params(c, l, nb, xin, xalt), c->n_cu, c->st));
+    else {
+        StackParams sp = stack_params(c, L, nb, xin, xalt);
+        if (P.fuse_mlp) { sp.zero = c->d_u1; sp.zero_n4 = nb * F / 4; }   // X2 below accumulates its two halves into u1
+        STG(DST_STACK, KD(c, cw_launch_gemv_stack, sp, P.nt3, c->st));
+    }
+    CrossSplitParams p = cross_params(c, P, L, l, nb, nullptr);
+    if (P.fuse_mlp) {
+        // A/B (CW_FUSE_MLP=1), measured slower: cross out-projection + fc1 fused the same way.  Needs the
+        // finished attention output in one plane (one block per (row, head): 17 us against 12) and makes every fc2 block
+        // redo the statistics and the GELU of its K slice.
+        p.a_out = c->dattn; p.xstat = xalt;
+        STG(DST_CROSS_ATTN, KD(c, cw_launch_attn_cross_split, true, p, c->st));
+        // X2 over [W'1 ; W'1 Wo_c ; Wo_c]:  u1 = W'1 x1 + W'1 bo_c + (W'1 Wo_c) a_c (two halves, atomics into the zeros X1
+        // left: two commutative additions, so the order does not matter),  x2 = x1 + Wo_c a_c + bo_c (+ a copy that
+        // fc2 takes the LayerNorm statistics of while its atomics are already modifying the stream)
+        StackParams sp = zeroed<StackParams>();
+        sp.W = L.ws5; sp.wpk = c->wpacked ? 1 : 0; sp.K = D; sp.Mb = nb; sp.nseg = 3;
+        sp.seg[0].x = xalt;     sp.seg[0].bias = L.u1_bias; sp.seg[0].out = c->d_u1; sp.seg[0].tile0 = 0;      sp.seg[0].n_tiles = TF; sp.seg[0].epi = 2;
+        sp.seg[0].wsum = c->stack_center ? L.u1_wsum : nullptr;
+        sp.seg[1].x = c->dattn; sp.seg[1].bias = nullptr;   sp.seg[1].out = c->d_u1; sp.seg[1].tile0 = TF;     sp.seg[1].n_tiles = TF; sp.seg[1].epi = 2;
+        sp.seg[2].x = c->dattn; sp.seg[2].bias = L.bo_c;    sp.seg[2].out = xin;     sp.seg[2].tile0 = 2 * TF; sp.seg[2].n_tiles = TD; sp.seg[2].epi = 1;
+        sp.seg[2].resid = xalt; sp.seg[2].out2 = c->dx2c;
+        STG(DST_STACK, KD(c, cw_launch_gemv_stack, sp, c->stack_nt5, c->st));
+        // fc2: mid = gelu(rstd(x2) (u1 - mean(x2) W'1 1) + b'1) on load; x3 = x2 + W2 mid + b2 in place
+        Fc2xParams fp{c->dx2c, c->d_u1, L.u1_wsum, L.b1, L.w2, L.b2, xin, nb, D, F, c->wpacked ? 1 : 0};
+        STG(DST_FC2, KD(c, cw_launch_gemv_fc2x, fp, c->st));
+        return CW_OK;
+    }
+    if (!P.dl) STG(DST_CROSS_ATTN, cross_attn(c, L, p));
+    STG(DST_CROSS_O, cross_out(c, P, L, nb, xalt));
+    if (P.mlp_pair) {
+        // LN + fc1 + GELU, group barrier, fc2 + residual in one launch (decfuse.hip: mlp_pair_kernel)
+        MlpPairParams mp{xalt, L.w1, L.b1, L.w2, L.b2, c->d_xfrag2, c->d_bar, c->d_err, nb, D, F, c->wpacked ? 1 : 0, c->mlp_pair_fence ? 1 : 0};
+        STG(DST_MLP_PAIR, KD(c, cw_launch_mlp_pair, mp, c->st));
+    } else if (P.mlp_chain) {
+        // LN + fc1 + GELU and fc2 + residual in ONE launch: fc2's blocks request their weights at kernel entry and wait for
+        // the fc1 blocks' flags instead of a kernel boundary (declayer.hip: mlp_chain_kernel); bit-identical
+        MlpChainParams mp = zeroed<MlpChainParams>();
+        mp.x = xalt; mp.W1 = L.w1; mp.b1 = L.b1; mp.W2 = L.w2; mp.b2 = L.b2; mp.xio = xalt; mp.mid = c->d_xfrag2;
+        mp.flags = c->d_gflag; mp.epoch = c->d_epoch; mp.layer = l; mp.err = c->d_err; mp.Mb = nb; mp.D = D; mp.F = F;
+        STG(DST_MLP_CHAIN, KD(c, cw_launch_mlp_chain, mp, c->st));
+    } else CWCHK(c, launch_mlp(c, P, L, nb, xalt));
+    std::swap(xin, xalt);
+    return CW_OK;
+}
+#endif   // CW_EXPERIMENTS
+
+// One decoder forward for the nb rows at the positions held in c->d_pos (device): plan, layers, logits.  Which launches a layer
+// has at nb rows: plan_step and the three layer functions above (tests/golden/decode_stage_tables.json lists them per configuration).
+static int decode_step(cw_ctx* c, int nb, bool want_logits) {
+    const StepPlan P = plan_step(c, nb);
+    float *xin = c->dx, *xalt = c->dx1;   // xin holds the residual stream whenever a layer function returns
+#ifdef CW_EXPERIMENTS
+    int ln_nblk = 1;
+    if (P.rows) CWCHK(c, KD(c, cw_launch_rows_prep, c->dx, nb, c->d.d_model, c->d_xfrag, c->d_rstats, P.lo_off, c->st));
+#endif
+    const int l_lo = c->layer_sel >= 0 ? c->layer_sel : 0, l_hi = c->layer_sel >= 0 ? c->layer_sel + 1 : c->d.dec_layers;
+    for (int l = l_lo; l < l_hi; ++l) {
+        c->stage_count = 0;
+#ifdef CW_EXPERIMENTS
+        if (P.pf && l + 1 < c->d.dec_layers) CWCHK(c, launch_prefetch_layer(c, P, l + 1, nb));
+        if (P.rows || P.skinny || P.xfull) { CWCHK(c, layer_unfused_ab(c, P, l, nb, ln_nblk)); continue; }
+#endif
+        CWCHK(c, layer_self_attention(c, P, l, nb, xin));
+#ifdef CW_EXPERIMENTS
+        if (P.fuse && (P.dl || P.fuse_mlp || P.mlp_pair || P.mlp_chain)) { CWCHK(c, layer_fused_ab(c, P, l, nb, xin, xalt)); continue; }
+#endif
+        CWCHK(c, P.fuse ? layer_fused(c, P, l, nb, xin, xalt) : layer_unfused(c, P, l, nb));
+    }
+#ifdef CW_EXPERIMENTS
+    if (P.pf && c->d.dec_layers > 1) {           // join the side stream (required before the capture ends; the last prefetch is long done)
+        HIPCHK(c, hipEventRecord(c->ev_pf[1], c->st2));
+        HIPCHK(c, hipStreamWaitEvent(c->st, c->ev_pf[1], 0));
+    }
+#endif
+    if (want_logits) CWCHK(c, launch_logits(c, nb, xin));
+    return CW_OK;
+}
+#undef STG
+
+static int launch_sample(cw_ctx* c, int nb) {
+    SampleParams sp = zeroed<SampleParams>();
     sp.logits = c->dlogits; sp.V = c->d.vocab_size; sp.ldv = c->Vpad; sp.B = nb; sp.mask = c->d_mask;
     sp.eos = c->gen.eos_token_id; sp.pad = c->gen.pad_token_id;
     sp.timestamp_begin = c->gen.no_timestamps_token_id + 1;
@@ -1559,7 +1586,6 @@ static int launch_sample(cw_ctx* c, int nb, bool forced) {
     if (c->sb_n > 0) sp.seq_bias = c->d_seq_bias;
     sp.epoch = c->d_epoch;
     sp.samp = c->d_samp; sp.pert = c->d_sample_pert;
-    (void)forced;
     return KD(c, cw_launch_sample, sp, c->st);
 }
 
@@ -1569,14 +1595,14 @@ static int run_step(cw_ctx* c, int nb) {
     const bool graph_ok = c->use_graph && !c->logits_capture;
     if (!graph_ok) {
         CWCHK(c, decode_step(c, nb, true));
-        return launch_sample(c, nb, false);
+        return launch_sample(c, nb);
     }
-    const int gi = nb + ((c->hist_short && c->short_hist_enabled && nb > 8) ? 65 : 0);
+    const int gi = nb + (plan_step(c, nb).short_hist ? 65 : 0);
     if (!c->step_graph[gi]) {
         hipGraph_t g = nullptr;
         HIPCHK(c, hipStreamBeginCapture(c->st, hipStreamCaptureModeThreadLocal));
         int r = decode_step(c, nb, true);
-        if (r == CW_OK) r = launch_sample(c, nb, false);
+        if (r == CW_OK) r = launch_sample(c, nb);
         hipError_t e = hipStreamEndCapture(c->st, &g);
         if (r != CW_OK) { if (g) hipGraphDestroy(g); return r; }
         if (e != hipSuccess) return fail(c, CW_ERR_HIP, "hipStreamEndCapture: %s", hipGetErrorString(e));
@@ -1596,7 +1622,7 @@ static int run_step(cw_ctx* c, int nb) {
 // and, if it is set, switch every such kernel off for this context (for good) and run the call again: the launch-per-stage
 // kernels are bit-identical, so the caller sees the result it would have had, late.
 #define CW_HANDOFF_RETRY 0x7e57
-static void drop_step_graphs(cw_ctx* c);
+static void drop_step_graphs(cw_ctx* c) { for (auto& ge : c->step_graph) if (ge) { hipGraphExecDestroy(ge); ge = nullptr; } }   // kernel arguments are baked into the graphs
 static bool handoffs_on(const cw_ctx* c) { return c->qkv_self || c->mlp_chain || c->declayer || c->mlp_pair; }
 static int handoff_gave_up(cw_ctx* c, bool* gave_up, int* word = nullptr) {
     int e = 0;
@@ -1904,10 +1930,6 @@ static int decode_once(cw_ctx* c, int32_t nb, const int32_t* prompt, int32_t n_p
 }
 
 // ---- deterministic half of generate_with_fallback (generation_whisper.py:970-1116, 1243-1287)
-static void drop_step_graphs(cw_ctx* c) {   // (declared above cw_decode)
-    for (auto& ge : c->step_graph) if (ge) { hipGraphExecDestroy(ge); ge = nullptr; }   // kernel arguments are baked into the graphs
-}
-
 int32_t cw_set_thresholds(cw_ctx* c, float logprob_threshold, float no_speech_threshold) {
     if (!isnan(no_speech_threshold) && isnan(logprob_threshold))
         return fail(c, CW_ERR_INVALID, "no_speech_threshold needs logprob_threshold (generation_whisper.py:1275-1285 compares both)");
@@ -2288,8 +2310,7 @@ int32_t cw_beam_begin(cw_ctx* c, int32_t n_items, int32_t num_beams, const int32
 // The candidate selection of one beam step on the first `rows` rows of the logits buffer (cw_beam_step, and cw_test_beam_topk on
 // caller-supplied rows): [rows][n_cand] best (log-probability, token) pairs into d_cand_val / d_cand_id.
 static int launch_beam_topk(cw_ctx* c, int rows, int n_cand) {
-    SampleParams sp;
-    memset(&sp, 0, sizeof(sp));
+    SampleParams sp = zeroed<SampleParams>();
     sp.logits = c->dlogits; sp.V = c->d.vocab_size; sp.ldv = c->Vpad; sp.B = rows; sp.mask = c->d_mask;
     sp.eos = c->gen.eos_token_id; sp.pad = c->gen.pad_token_id;
     sp.timestamp_begin = c->gen.no_timestamps_token_id + 1;
@@ -3366,7 +3387,7 @@ int32_t cw_set_option(cw_ctx* c, const char* name, int32_t value) {
         }
         c->kv8 = true;
         c->nb_encoded = 0;                                   // windows must be re-encoded to fill the fp8 cache
-        for (auto& ge : c->step_graph) if (ge) { hipGraphExecDestroy(ge); ge = nullptr; }   // graphs hold the kernel choice
+        drop_step_graphs(c);   // graphs hold the kernel choice
         return CW_OK;
     }
     if (!strcmp(name, "encoder_gemm_fp8")) {
@@ -3402,17 +3423,17 @@ int32_t cw_set_option(cw_ctx* c, const char* name, int32_t value) {
     }
     if (!strcmp(name, "handoff_fail_pos")) {   // test hook: the in-launch hand-off of qkv_self_kernel gives up at this decoder position (-1: never)
         c->fail_pos = value;
-        for (auto& ge : c->step_graph) if (ge) { hipGraphExecDestroy(ge); ge = nullptr; }   // kernel arguments are baked into the graphs
+        drop_step_graphs(c);   // kernel arguments are baked into the graphs
         return CW_OK;
     }
     if (!strcmp(name, "rows_ln")) {   // 17..64-row decode: 0 = preparation launch in front of every GEMV (A/B, differential tests)
         c->rows_ln_enabled = value != 0;
-        for (auto& ge : c->step_graph) if (ge) { hipGraphExecDestroy(ge); ge = nullptr; }   // graphs hold the kernel choice
+        drop_step_graphs(c);   // graphs hold the kernel choice
         return CW_OK;
     }
     if (!strcmp(name, "skinny")) {    // 17..64-row decode: cw_ctx::skinny_mode (0 = round-3 path, for A/B and differential tests)
         c->skinny_mode = value;
-        for (auto& ge : c->step_graph) if (ge) { hipGraphExecDestroy(ge); ge = nullptr; }
+        drop_step_graphs(c);
         return CW_OK;
     }
     return fail(c, CW_ERR_INVALID, "unknown option %s", name);
@@ -4864,7 +4885,7 @@ static int test_sample(cw_ctx* c, int32_t nb, const float* logits, const int32_t
         const std::vector<float> hot((size_t)nb * n_padcol, 75.0f);
         HIPCHK(c, hipMemcpy2D(c->dlogits + V, (size_t)c->Vpad * 4, hot.data(), (size_t)n_padcol * 4, (size_t)n_padcol * 4, nb, hipMemcpyHostToDevice));
     }
-    CWCHK(c, launch_sample(c, nb, false));
+    CWCHK(c, launch_sample(c, nb));
     HIPCHK(c, hipStreamSynchronize(c->st));
     if (top_id_out && n_padcol > 0) HIPCHK(c, hipMemset2D(c->dlogits + V, (size_t)c->Vpad * 4, 0, (size_t)n_padcol * 4, nb));
     std::vector<int> am((size_t)nb * TGT);
@@ -4949,40 +4970,18 @@ int32_t cw_time_kernel(cw_ctx* c, int32_t which, int32_t nb, int32_t iters, floa
                     if (c->fuse6_ready && c->fuse6_enabled && c->ln_folded && nb <= 16 && (!c->kv8 || KD(c, cw_cross8_is_mfma, CW_N_CTX))) {
                         p.kv_div = 1; p.qa = c->d_qa; p.qb = c->d_qb; p.qw = L.q_wsum; p.qbias = L.bq_c;
                         p.pstats = c->d_pstats; p.n_pstats = D / 16;
-                        if (c->kv8) { p.K = L.ck8; p.V = L.cv8; p.kv_scale = L.kvs; return KD(c, cw_launch_attn_cross_split_fp8, p, c->st); }
-                        return KD(c, cw_launch_attn_cross_split, true, p, c->st);
                     }
-                    if (c->kv8) { p.K = L.ck8; p.V = L.cv8; p.kv_scale = L.kvs; return KD(c, cw_launch_attn_cross_split_fp8, p, c->st); }
-                    return KD(c, cw_launch_attn_cross_split, true, p, c->st);
+                    return cross_attn(c, L, p);
                 }
                 DecAttnParams p = dec_attn(c->dq, L.ck, L.cv, CW_N_CTX, CW_N_CTX, nullptr, c->dattn, nb, H);
                 return KD(c, cw_launch_attn_decode, c->bf16, p, c->st);
             }
-            case 2: {   // self-attention out projection (in-place residual, K split)
-                EpiParams ep = epi0(); ep.outf = c->dx; ep.resid = c->dx; ep.bias = L.bo; ep.ldo = D;
-                return gemv_ln(c, EPI_RESID_F32, c->dattn, nb, D, L.wo, D, nullptr, nullptr, ep);
-            }
-            case 3: {   // LN + qkv + cache append
-                EpiParams ep = epi0(); ep.outf = c->dq; ep.out1 = L.sk; ep.out2 = L.sv; ep.bias = L.bqkv;
-                ep.H = H; ep.S_pad = TGT; ep.d_model = D; ep.row_pos = c->d_pos;
-                return gemv_ln(c, EPI_QKV_CACHE, c->dx, nb, D, L.wqkv, 3 * D, L.ln1_g, c->ln_folded ? nullptr : L.ln1_b, ep);
-            }
-            case 4: {   // LN + cross q
-                EpiParams ep = epi0(); ep.outf = c->dq; ep.bias = L.bq_c; ep.ldo = D;
-                return gemv_ln(c, EPI_STORE_F32, c->dx, nb, D, L.wq_c, D, L.lnc_g, c->ln_folded ? nullptr : L.lnc_b, ep);
-            }
-            case 5: {   // fc2
-                EpiParams ep = epi0(); ep.outf = c->dx; ep.resid = c->dx; ep.bias = L.b2; ep.ldo = D;
-                return gemv_ln(c, EPI_RESID_F32, c->dmid, nb, F, L.w2, D, nullptr, nullptr, ep);
-            }
-            case 6: {   // self-attention at the positions in d_pos
-                DecAttnParams p = dec_attn(c->dq, L.sk, L.sv, TGT, 0, c->d_pos, c->dattn, nb, H);
-                return KD(c, cw_launch_attn_decode, c->bf16, p, c->st);
-            }
-            case 7: {   // logits
-                EpiParams ep = epi0(); ep.outf = c->dlogits; ep.ldo = c->Vpad;
-                return gemv_ln(c, EPI_STORE_F32, c->dx, nb, D, (c->bf16 && c->wpacked) ? c->embed_pk : c->embed, V, c->dec_ln_g, c->dec_ln_b, ep);
-            }
+            case 2: return gemv_resid(c, false, c->dattn, nullptr, nb, D, L.wo, L.bo, c->dx);   // self-attention out projection (in-place residual, K split)
+            case 3: return gemv_ln(c, EPI_QKV_CACHE, c->dx, nb, D, L.wqkv, 3 * D, L.ln1_g, c->ln_folded ? nullptr : L.ln1_b, qkv_epi(c, L));   // LN + qkv + cache append
+            case 4: return gemv_ln(c, EPI_STORE_F32, c->dx, nb, D, L.wq_c, D, L.lnc_g, c->ln_folded ? nullptr : L.lnc_b, cross_q_epi(c, L));   // LN + cross q
+            case 5: return gemv_resid(c, false, c->dmid, nullptr, nb, F, L.w2, L.b2, c->dx);   // fc2
+            case 6: return KD(c, cw_launch_attn_decode, c->bf16, dec_attn(c->dq, L.sk, L.sv, TGT, 0, c->d_pos, c->dattn, nb, H), c->st);   // self-attention at the positions in d_pos
+            case 7: return launch_logits(c, nb, c->dx);
             case 8:     // near-empty kernel: launch/boundary floor
                 return KD(c, cw_launch_set_pos, c->d_pos, 64, nb, c->st);
             case 9: {   // persistent stage A (declayer.hip) behind a near-empty launch that bumps the granule epoch (as the step's sampler does):
