@@ -99,6 +99,9 @@ _SIGS = {
     "cw_set_sampling": (_I, [_P, C.c_float, C.c_uint64, _P, _I]),
     "cw_decode_rows": (_I, [_P, _I, _P, _I, _I, _I, _P, _P, _P, _P, _P]),
     "cw_no_speech_probs": (_I, [_P, _I, _I, _P]),
+    "cw_detect_language": (_I, [_P, _I, _I, _P, _I, _P, _P, _P]),
+    "cw_test_language_probs": (_I, [_P, _P, _I, _P, _I, _I, _P, _P, _P]),
+    "cw_get_transcribe_languages": (_I, [_P, _P, _P, _I]),
     "cw_get_avg_logprobs": (_I, [_P, _P, _I]),
     "cw_set_token_logprobs": (_I, [_P, _I]),
     "cw_get_token_logprobs": (_I, [_P, _P, _I]),
@@ -152,6 +155,7 @@ _SIGS = {
     "cw_collate_get": (_I, [_P, _P, _P, _P, _P, _P]),
     "cw_collate_token_groups_total": (C.c_int64, [_P]),
     "cw_collate_get_token_groups": (_I, [_P, _P, _P]),
+    "cw_collate_get_languages": (_I, [_P, _P]),
     "cw_collate_free": (None, [_P]),
     "cw_set_option": (_I, [_P, C.c_char_p, _I]),
     "cw_test_set_option": (_I, [C.c_char_p, _I]),

@@ -171,13 +171,16 @@ def _native_vocab(vocab: "Vocabulary"):
 
 
 def decode_asr(vocab: Vocabulary, model_outputs: List[dict], time_precision: float = 0.02, warn=None,
-               return_timestamps="word", return_token_groups: bool = False):
+               return_timestamps="word", return_token_groups: bool = False, return_language: bool = False):
     """model_outputs: [{"tokens", "token_timestamps", optional "stride": (len_s, left_s, right_s)}] in audio
     order -> (text, [{"text", "timestamp": (start, end)}]).  Runs in libcrisperwhisper.so (csrc/collate.cpp).
     ``return_timestamps="word"``: word chunks; ``True``: one chunk per timestamp-delimited segment (token_timestamps
     not needed; a missing boundary is None, as in the reference).
     ``return_token_groups=True``: a third result, per chunk the list of its tokens' positions in the concatenation of all
-    ``model_outputs`` token arrays -- the collator's own grouping (cw_collate_get_token_groups)."""
+    ``model_outputs`` token arrays -- the collator's own grouping (cw_collate_get_token_groups).
+    ``return_language=True``: every chunk gains ``"language"``, the full lowercase name of the language token in force for
+    it (cw_collate_get_languages; None when the stream carried none), as ``_decode_asr(..., return_language=True)`` gives
+    it.  The language tokens have to be in ``tokens`` for that (with a 0.0 in front of ``token_timestamps`` each)."""
     if return_timestamps not in ("word", True):
         raise ValueError("return_timestamps must be 'word' or True")
     seg = return_timestamps is True
@@ -217,6 +220,12 @@ def decode_asr(vocab: Vocabulary, model_outputs: List[dict], time_precision: flo
             return None if x != x else float(x)                  # NaN = no timestamp predicted (segment mode)
         words = [{"text": raw[offs[k]:offs[k + 1]].decode("utf-8"), "timestamp": (_t(starts[k]), _t(ends[k]))}
                  for k in range(n)]
+        if return_language:
+            ltok = np.full(max(n, 1), -1, dtype=np.int32)
+            lib.cw_collate_get_languages(col, ltok.ctypes.data_as(C.c_void_p))
+            for k in range(n):
+                name = vocab.specials.get(int(ltok[k]))
+                words[k]["language"] = vocab.languages.get(name[2:-2]) if name else None
         if return_token_groups:
             goffs = np.zeros(n + 1, dtype=np.int64)
             gidx = np.zeros(max(int(lib.cw_collate_token_groups_total(col)), 1), dtype=np.int32)

@@ -106,7 +106,7 @@ struct cw_vocab {
     }
 };
 
-struct Word { U32 text; double start, end; std::vector<int> src; };   // src: the word's tokens as indices into the fed tokens
+struct Word { U32 text; double start, end; std::vector<int> src; int lang; };   // src: the word's tokens as indices into the fed tokens; lang: language token in force (-1 none)
 
 struct cw_collator {
     const cw_vocab* v;
@@ -115,6 +115,7 @@ struct cw_collator {
     std::vector<Word> words;
     U32 full_text;
     int lang_class;                      // -1 unknown
+    int last_lang = -1, chunk_lang = -1; // language token seen last (`last_language`) / of the chunk being built (chunk["language"], :20-25)
     double time_offset;
     std::vector<std::vector<int>> pending;
     std::vector<std::vector<Span>> pending_ts;
@@ -168,10 +169,11 @@ struct cw_collator {
         v->text(toks, whole);
         full_text += whole;
         if (mode == 1) {                                         // :1060-1075 without the word collation
-            Word w; w.text = whole; w.start = has_open ? open_start : NAN; w.end = end_time; w.src = src;
+            Word w; w.text = whole; w.start = has_open ? open_start : NAN; w.end = end_time; w.src = src; w.lang = chunk_lang;
             words.push_back(w);
             pending.clear(); pending_ts.clear(); pending_src.clear();
             has_open = false;
+            chunk_lang = last_lang;                              // new_chunk()
             return;
         }
         // unicode pieces (:1315-1344)
@@ -224,10 +226,12 @@ struct cw_collator {
             if (ws[k].empty()) continue;
             Word w; w.text = ws[k]; w.start = ts[wi[k].front()].first; w.end = ts[wi[k].back()].second;
             for (int t : wi[k]) w.src.push_back(src[t]);
+            w.lang = last_lang;                                  // _collate_word_timestamps(..., last_language, ...)
             words.push_back(w);
         }
         pending.clear(); pending_ts.clear(); pending_src.clear();
         has_open = false;
+        chunk_lang = last_lang;
     }
 };
 
@@ -297,7 +301,7 @@ int32_t cw_collate_feed(cw_collator* c, const int64_t* tokens, int32_t n_tokens,
         const int t = ids[i];
         const int kind = (t >= 0 && t < (int)v->kind.size()) ? v->kind[t] : 2;
         if (kind == 1) {
-            if (v->lang_class[t] >= 0) c->lang_class = v->lang_class[t];
+            if (v->lang_class[t] >= 0) { c->lang_class = v->lang_class[t]; c->last_lang = c->chunk_lang = t; }
         } else if (t >= tb) {
             const double stamp = (double)(t - tb) * tp;
             if (stamp < cur_max) {
@@ -330,7 +334,7 @@ int32_t cw_collate_feed(cw_collator* c, const int64_t* tokens, int32_t n_tokens,
     else {
         bool any = false;
         for (auto& p : c->pending) if (!p.empty()) any = true;
-        if (!any) { c->pending.clear(); c->pending_ts.clear(); c->pending_src.clear(); c->has_open = false; }
+        if (!any) { c->pending.clear(); c->pending_ts.clear(); c->pending_src.clear(); c->has_open = false; c->chunk_lang = c->last_lang; }
     }
     return 0;
 }
@@ -376,6 +380,16 @@ int32_t cw_collate_get_token_groups(cw_collator* c, int64_t* group_offsets, int3
         for (int t : c->words[k].src) token_index[off++] = t;
     }
     group_offsets[c->words.size()] = off;
+    return 0;
+}
+
+// The language token in force for every chunk of cw_collate_get (-1: none), after cw_collate_finish, by the rules of
+// _decode_asr(..., return_language=True): a word carries the language seen last when its segment is flushed (a segment merged
+// across a chunk seam takes the later window's); a segment chunk starts from the language seen last and takes a language
+// token met while it is current.
+int32_t cw_collate_get_languages(cw_collator* c, int32_t* lang_token) {
+    if (!c || !lang_token) return -22;
+    for (size_t k = 0; k < c->words.size(); ++k) lang_token[k] = c->words[k].lang;
     return 0;
 }
 

@@ -425,3 +425,4 @@ __device__ inline void epi_tile_interior(const EpiParams& p, const int (&rows)[4
 #define CW_ERR_HIP (-5)
 #define CW_ERR_STATE (-1)
 #define CW_TOP_LOGPROBS_MAX 8   /* as in include/crisperwhisper.h: alternatives per position (cw_set_top_logprobs) */
+#define CW_LANG_IDS_MAX 128     /* as in include/crisperwhisper.h: language candidates (cw_detect_language) */

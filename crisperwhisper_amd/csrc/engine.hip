@@ -214,6 +214,11 @@ struct cw_ctx {
     float *d_as_mass = nullptr, *d_as_spread = nullptr;       // [Bm][max_target] per (sequence, token row) of the last DTW launch
     std::vector<std::vector<float>> as_mass, as_spread;       // rows of the last timestamp stage, each [L + 1] in cw_token_timestamps' indexing
     std::vector<std::vector<float>> tr_as_mass, tr_as_spread; // ... of the last cw_transcribe, per item, aligned with its tokens
+    // language identification (langid.hip, cw_detect_language): candidate table and the per-row records, allocated on first use
+    int* d_lang_ids = nullptr;                                // [CW_LANG_IDS_MAX]
+    float* d_lang_out = nullptr;                              // [Bm][CW_LANG_IDS_MAX + 2]
+    std::vector<int> tr_lang;                                 // language token every item of the last cw_transcribe was decoded with
+    std::vector<float> tr_lang_prob;                          // ... its detection probability (NaN: forced)
 
     double* d_pause = nullptr;   // persistent scratch for cw_adjust_pauses: [4][pause_cap]
     int pause_cap = 0;
@@ -2175,12 +2180,12 @@ int32_t cw_get_avg_logprobs(cw_ctx* c, float* out, int32_t nb) {
 // WhisperNoSpeechDetection (logits_process.py:2050-2112): softmax of the raw decoder logits at the <|startoftranscript|>
 // position of every encoded window, at token no_timestamps_token_id - 1 (generation_whisper.py:1801-1806).  One decoder
 // forward at position 0; call it before cw_decode (which decodes position 0 again).
-int32_t cw_no_speech_probs(cw_ctx* c, int32_t nb, int32_t sot_token, float* out) {
-    const int D = c->d.d_model, V = c->d.vocab_size, TGT = c->d.max_target_positions;
-    if (!c->gen_set) return fail(c, CW_ERR_STATE, "cw_set_generation not called");
-    if (nb < 1 || nb > c->nb_encoded) return fail(c, CW_ERR_STATE, "nb=%d but %d windows encoded", nb, c->nb_encoded);
-    const int tok = c->gen.no_timestamps_token_id - 1;
-    if (sot_token < 0 || sot_token >= V || tok < 0) return fail(c, CW_ERR_INVALID, "no_speech_probs: token out of range");
+// The forward shared by cw_no_speech_probs and cw_detect_language: <|startoftranscript|> at position 0 of the nb encoded windows,
+// logits left in c->dlogits; a lost in-launch hand-off repeats it once on the launch-per-stage kernels.  short_hist: what
+// c->hist_short holds during the forward -- false as cw_no_speech_probs has always run it, true as cw_decode runs its position 0
+// (one key: the short-history attention at 9 rows and more), which is what language detection has to reproduce bit for bit.
+static int forward_sot(cw_ctx* c, int nb, int sot_token, bool short_hist, const char* who) {
+    const int D = c->d.d_model, TGT = c->d.max_target_positions;
     CWCHK(c, epoch_hygiene(c, 4));
     c->beam_K = 0;
     c->align_cur = c->d_align;
@@ -2191,15 +2196,25 @@ int32_t cw_no_speech_probs(cw_ctx* c, int32_t nb, int32_t sot_token, float* out)
     for (int attempt = 0;; ++attempt) {
         CWCHK(c, KD(c, cw_launch_set_pos, c->d_pos, 0, nb, c->st, c->d_epoch));
         CWCHK(c, KD(c, cw_launch_embed, c->d_ids, TGT, 0, c->embed, c->bf16 ? 1 : 0, c->dec_pos, c->dx, nb, D, c->st));
-        c->hist_short = false;
+        c->hist_short = short_hist;
         CWCHK(c, decode_step(c, nb, true));
         KCHK(c);
         bool gave_up = false;
         CWCHK(c, handoff_gave_up(c, &gave_up));
         if (!gave_up) break;
-        if (attempt) return fail(c, CW_ERR_HIP, "no_speech_probs: an in-kernel wait timed out on the launch-per-stage path");
-        CWCHK(c, handoffs_off(c, "no_speech_probs"));
+        if (attempt) return fail(c, CW_ERR_HIP, "%s: an in-kernel wait timed out on the launch-per-stage path", who);
+        CWCHK(c, handoffs_off(c, who));
     }
+    return CW_OK;
+}
+
+int32_t cw_no_speech_probs(cw_ctx* c, int32_t nb, int32_t sot_token, float* out) {
+    const int V = c->d.vocab_size;
+    if (!c->gen_set) return fail(c, CW_ERR_STATE, "cw_set_generation not called");
+    if (nb < 1 || nb > c->nb_encoded) return fail(c, CW_ERR_STATE, "nb=%d but %d windows encoded", nb, c->nb_encoded);
+    const int tok = c->gen.no_timestamps_token_id - 1;
+    if (sot_token < 0 || sot_token >= V || tok < 0) return fail(c, CW_ERR_INVALID, "no_speech_probs: token out of range");
+    CWCHK(c, forward_sot(c, nb, sot_token, false, "no_speech_probs"));
     std::vector<float> lg((size_t)nb * V);
     CWCHK(c, cw_get_logits(c, lg.data(), nb));
     for (int b = 0; b < nb; ++b) {
@@ -2209,6 +2224,85 @@ int32_t cw_no_speech_probs(cw_ctx* c, int32_t nb, int32_t sot_token, float* out)
         double z = 0.0;
         for (int v = 0; v < V; ++v) z += exp((double)(r[v] - m));
         out[b] = (float)(exp((double)(r[tok] - m)) / z);
+    }
+    return CW_OK;
+}
+
+// ---- language identification (include/crisperwhisper.h: cw_detect_language; kernel in langid.hip) ---------------------------
+static int check_lang_ids(cw_ctx* c, const char* who, const int32_t* lang_ids, int n_lang) {
+    if (!lang_ids) return fail(c, CW_ERR_INVALID, "%s: lang_ids is null", who);
+    if (n_lang < 1 || n_lang > CW_LANG_IDS_MAX) return fail(c, CW_ERR_INVALID, "%s: n_lang=%d outside 1 .. %d", who, n_lang, CW_LANG_IDS_MAX);
+    for (int k = 0; k < n_lang; ++k) {
+        if (lang_ids[k] < 0 || lang_ids[k] >= c->d.vocab_size)
+            return fail(c, CW_ERR_INVALID, "%s: language id %d at %d is outside the vocabulary (%d)", who, lang_ids[k], k, c->d.vocab_size);
+        for (int j = 0; j < k; ++j)
+            if (lang_ids[j] == lang_ids[k]) return fail(c, CW_ERR_INVALID, "%s: language id %d is listed twice", who, lang_ids[k]);
+    }
+    return CW_OK;
+}
+// the kernel over rows 0 .. nb-1 of c->dlogits and the one copy of its records; ns_tok < 0: no no-speech part
+static int language_probs(cw_ctx* c, int nb, const int32_t* lang_ids, int n_lang, int ns_tok, int32_t* best, float* prob,
+                          float* no_speech) {
+    if (!c->d_lang_ids) {
+        CWCHK(c, dmalloc(c, &c->d_lang_ids, (size_t)CW_LANG_IDS_MAX * 4));
+        CWCHK(c, dmalloc(c, &c->d_lang_out, (size_t)c->Bm * (CW_LANG_IDS_MAX + 2) * 4));
+    }
+    const int rec = n_lang + 2;
+    HIPCHK(c, hipMemcpyAsync(c->d_lang_ids, lang_ids, (size_t)n_lang * 4, hipMemcpyHostToDevice, c->st));
+    const int r = cw_launch_language_probs(c->dlogits, c->Vpad, c->d.vocab_size, c->d_lang_ids, n_lang, ns_tok, nb, c->d_lang_out, c->st);
+    if (r != CW_OK) return fail(c, r, "language_probs: launch rejected");
+    KCHK(c);
+    std::vector<float> h((size_t)nb * rec);
+    HIPCHK(c, hipStreamSynchronize(c->st));
+    HIPCHK(c, hipMemcpy(h.data(), c->d_lang_out, h.size() * 4, hipMemcpyDeviceToHost));
+    for (int b = 0; b < nb; ++b) {
+        const float* p = h.data() + (size_t)b * rec;
+        memcpy(&best[b], p, 4);
+        if (no_speech) no_speech[b] = p[1];
+        if (prob) memcpy(prob + (size_t)b * n_lang, p + 2, (size_t)n_lang * 4);
+    }
+    return CW_OK;
+}
+
+int32_t cw_detect_language(cw_ctx* c, int32_t nb, int32_t sot_token, const int32_t* lang_ids, int32_t n_lang, int32_t* best,
+                           float* prob, float* no_speech) {
+    if (!best) return fail(c, CW_ERR_INVALID, "detect_language: best is null");
+    CWCHK(c, check_lang_ids(c, "detect_language", lang_ids, n_lang));
+    if (sot_token < 0 || sot_token >= c->d.vocab_size) return fail(c, CW_ERR_INVALID, "detect_language: sot_token %d out of range", sot_token);
+    if (!c->gen_set) return fail(c, CW_ERR_STATE, "cw_set_generation not called");
+    if (nb < 1 || nb > c->nb_encoded) return fail(c, CW_ERR_STATE, "nb=%d but %d windows encoded", nb, c->nb_encoded);
+    const int ns_tok = no_speech ? c->gen.no_timestamps_token_id - 1 : -1;
+    if (no_speech && (ns_tok < 0 || ns_tok >= c->d.vocab_size)) return fail(c, CW_ERR_INVALID, "detect_language: no-speech token out of range");
+    CWCHK(c, forward_sot(c, nb, sot_token, true, "detect_language"));
+    return language_probs(c, nb, lang_ids, n_lang, ns_tok, best, prob, no_speech);
+}
+
+int32_t cw_test_language_probs(cw_ctx* c, const float* logits, int32_t nb, const int32_t* lang_ids, int32_t n_lang,
+                               int32_t nospeech_token, int32_t* best, float* prob, float* no_speech) {
+    const int V = c->d.vocab_size;
+    if (!logits || !best) return fail(c, CW_ERR_INVALID, "test_language_probs: null argument");
+    if (nb < 1 || nb > c->Bm) return fail(c, CW_ERR_INVALID, "test_language_probs: nb=%d outside 1 .. %d", nb, c->Bm);
+    if (nospeech_token < -1 || nospeech_token >= V) return fail(c, CW_ERR_INVALID, "test_language_probs: nospeech_token %d out of range", nospeech_token);
+    if (c->beam_K > 0) return fail(c, CW_ERR_STATE, "test_language_probs: a beam search is open (the hook overwrites its logits)");
+    CWCHK(c, check_lang_ids(c, "test_language_probs", lang_ids, n_lang));
+    HIPCHK(c, hipStreamSynchronize(c->st));
+    HIPCHK(c, hipMemcpy2D(c->dlogits, (size_t)c->Vpad * 4, logits, (size_t)V * 4, (size_t)V * 4, nb, hipMemcpyHostToDevice));
+    const int n_padcol = c->Vpad - V;
+    if (n_padcol > 0) {                               // the pad columns hold +75 for this call: they must never count
+        const std::vector<float> hot((size_t)nb * n_padcol, 75.0f);
+        HIPCHK(c, hipMemcpy2D(c->dlogits + V, (size_t)c->Vpad * 4, hot.data(), (size_t)n_padcol * 4, (size_t)n_padcol * 4, nb, hipMemcpyHostToDevice));
+    }
+    const int r = language_probs(c, nb, lang_ids, n_lang, nospeech_token, best, prob, no_speech);
+    if (n_padcol > 0) HIPCHK(c, hipMemset2D(c->dlogits + V, (size_t)c->Vpad * 4, 0, (size_t)n_padcol * 4, nb));
+    return r;
+}
+
+int32_t cw_get_transcribe_languages(cw_ctx* c, int32_t* lang_token, float* prob, int32_t B) {
+    if (!lang_token || B < 1 || (size_t)B != c->tr_lang.size())
+        return fail(c, CW_ERR_STATE, "get_transcribe_languages: B=%d but the last cw_transcribe had %d items", B, (int)c->tr_lang.size());
+    for (int i = 0; i < B; ++i) {
+        lang_token[i] = c->tr_lang[i];
+        if (prob) prob[i] = c->tr_lang_prob[i];
     }
     return CW_OK;
 }
@@ -2529,6 +2623,7 @@ int32_t cw_transcribe_prompted(cw_ctx* c, int32_t B, const int32_t* num_frames, 
     std::vector<int> all(B), zeros(B, 0), full(B, CW_N_FRAMES);
     for (int i = 0; i < B; ++i) all[i] = i;
     bool pre_encoded = false;
+    std::vector<float> lang_prob(B, NAN);            // NaN: the language was forced
     if (cfg->language_token >= 0) {
         for (int i = 0; i < B; ++i) {
             prompts[i] = {cfg->sot_token, cfg->language_token};
@@ -2537,21 +2632,29 @@ int32_t cw_transcribe_prompted(cw_ctx* c, int32_t B, const int32_t* num_frames, 
     } else {   // detect_language (:1610-1673): one decoder step on <|startoftranscript|>, argmax over the language ids
         if (!cfg->lang_ids || cfg->n_lang_ids <= 0) return fail(c, CW_ERR_INVALID, "language detection needs lang_ids");
         CWCHK(c, cw_encode(c, B, all.data(), zeros.data(), full.data()));
-        std::vector<int> sotp(B, cfg->sot_token), seq((size_t)B * TGT), ln(B);
-        CWCHK(c, cw_decode(c, B, sotp.data(), 1, 2, 0, nullptr, seq.data(), ln.data(), nullptr));
-        std::vector<float> lg((size_t)B * V);
-        CWCHK(c, cw_get_logits(c, lg.data(), B));
+        // (the logits stay on the device: langid.hip picks the arg-max, lowest id on a tie, and the candidates' softmax)
+        std::vector<int> cand;                        // an id listed twice counts once, as in the host loop this replaces
+        for (int k = 0; k < cfg->n_lang_ids; ++k)
+            if (std::find(cand.begin(), cand.end(), cfg->lang_ids[k]) == cand.end()) cand.push_back(cfg->lang_ids[k]);
+        const int n_cand = (int)cand.size();
+        std::vector<int> best(B);
+        std::vector<float> pr((size_t)B * n_cand);
+        CWCHK(c, cw_detect_language(c, B, cfg->sot_token, cand.data(), n_cand, best.data(), pr.data(), nullptr));
         for (int i = 0; i < B; ++i) {
-            int best = cfg->lang_ids[0];
-            for (int k = 1; k < cfg->n_lang_ids; ++k) {
-                const int id = cfg->lang_ids[k];
-                const float a = lg[(size_t)i * V + id], bv = lg[(size_t)i * V + best];
-                if (a > bv || (a == bv && id < best)) best = id;
-            }
-            prompts[i] = {cfg->sot_token, best};
+            prompts[i] = {cfg->sot_token, best[i]};
             if (cfg->task_token >= 0) prompts[i].push_back(cfg->task_token);
+            for (int k = 0; k < n_cand; ++k)
+                if (cand[k] == best[i]) lang_prob[i] = pr[(size_t)i * n_cand + k];
         }
         pre_encoded = true;
+    }
+    // what cw_get_transcribe_languages reports: slot 1 of the prompt where it is a language (one of cfg->lang_ids when given)
+    c->tr_lang.assign(B, -1); c->tr_lang_prob = lang_prob;
+    for (int i = 0; i < B; ++i) {
+        const int tok = prompts[i][1];
+        bool is_lang = !cfg->lang_ids || cfg->n_lang_ids <= 0;
+        for (int k = 0; k < cfg->n_lang_ids && !is_lang; ++k) is_lang = cfg->lang_ids[k] == tok;
+        if (is_lang) c->tr_lang[i] = tok;
     }
     // prompt_ids (generation_whisper.py:1909-1913): the prefix goes in front of every window's init tokens, after detection
     if (n_prefix > 0)

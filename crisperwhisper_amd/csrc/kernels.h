@@ -459,6 +459,10 @@ int cw_launch_normalise(float* x, long long n, double* acc2, hipStream_t st);
 int cw_launch_resample(const float* x, long long n_in, const float* taps_t, int orig, int nw, int width,
                        long long n_out, float* out, hipStream_t st);
 
+// langid.hip: per row of f32 logits [rows][ldv] the record {best id, no-speech probability (ns_tok < 0: NaN), prob[n_lang]}
+int cw_launch_language_probs(const float* logits, int ldv, int V, const int* lang_ids, int n_lang, int ns_tok, int rows,
+                             float* out, hipStream_t st);
+
 // align.hip
 int cw_launch_align_stats(const float* w, int B, int Ha, int rows_cap, int S, int row0, int N, const int* n_cols,
                           float* mean, float* stdv, hipStream_t st);

@@ -268,6 +268,43 @@ class Engine:
         self._chk(self.lib.cw_no_speech_probs(self.ctx, nb, int(sot), _ptr(out)))
         return out
 
+    def detect_language(self, nb: int, lang_ids=None, no_speech: bool = True, sot: Optional[int] = None):
+        """Language identification over the ``nb`` encoded windows (``cw_detect_language``): one decoder step on
+        <|startoftranscript|>, then one kernel on the logits where they lie.  ``lang_ids``: the candidate language tokens
+        (default: every value of ``spec.lang_to_id``, ascending).  Returns ``(ids [nb] int32, probs [nb][n_lang] float32 in
+        the order of lang_ids, no_speech [nb] float32 or None)``: the softmax over the candidates alone, and the probability
+        of the no-speech token over the whole vocabulary."""
+        lids = _i32(sorted(set(self.spec.lang_to_id.values())) if lang_ids is None else lang_ids).reshape(-1)
+        best = np.zeros(nb, np.int32)
+        prob = np.zeros((nb, max(len(lids), 1)), np.float32)
+        ns = np.zeros(nb, np.float32) if no_speech else None
+        sot = self.spec.decoder_start_token_id if sot is None else sot
+        self._chk(self.lib.cw_detect_language(self.ctx, int(nb), int(sot), _ptr(lids), len(lids), _ptr(best), _ptr(prob), _ptr(ns)))
+        return best, prob[:, :len(lids)], ns
+
+    def test_language_probs(self, logits: np.ndarray, lang_ids, nospeech_token: int = -1):
+        """cw_test_language_probs: the kernel of ``detect_language`` on caller-supplied rows logits [nb][vocab] ->
+        (ids, probs, no_speech); the pad columns of the device buffer hold +75 during the call."""
+        lg = np.ascontiguousarray(logits, dtype=np.float32)
+        if lg.ndim != 2 or lg.shape[1] != self.spec.vocab_size:
+            raise ValueError("test_language_probs: logits must be [nb][vocab_size]")
+        nb = lg.shape[0]
+        lids = _i32(lang_ids).reshape(-1)
+        best = np.zeros(nb, np.int32)
+        prob = np.zeros((nb, max(len(lids), 1)), np.float32)
+        ns = np.zeros(nb, np.float32)
+        self._chk(self.lib.cw_test_language_probs(self.ctx, _ptr(lg), nb, _ptr(lids), len(lids), int(nospeech_token),
+                                                  _ptr(best), _ptr(prob), _ptr(ns)))
+        return best, prob[:, :len(lids)], ns
+
+    def transcribe_languages(self, B: int):
+        """(language token int32 [B], detection probability float32 [B], NaN where forced) of the last ``transcribe``
+        (``cw_get_transcribe_languages``)."""
+        tok = np.zeros(B, np.int32)
+        prob = np.zeros(B, np.float32)
+        self._chk(self.lib.cw_get_transcribe_languages(self.ctx, _ptr(tok), _ptr(prob), int(B)))
+        return tok, prob
+
     def avg_logprobs(self, nb: int) -> np.ndarray:
         out = np.zeros(nb, np.float32)
         self._chk(self.lib.cw_get_avg_logprobs(self.ctx, _ptr(out), nb))

@@ -26,6 +26,7 @@ INPUT_STRIDE = 2               # conv1.stride * conv2.stride
 TOP_LOGPROBS_MAX = 8           # CW_TOP_LOGPROBS_MAX: alternatives per token (generate(top_logprobs=k))
 SEQUENCE_BIAS_MAX = 256        # CW_SEQUENCE_BIAS_MAX: sequences per table (generate(sequence_bias=...))
 SEQUENCE_BIAS_MAX_LEN = 16     # CW_SEQUENCE_BIAS_MAX_LEN: tokens per sequence
+LANG_IDS_MAX = 128             # CW_LANG_IDS_MAX: candidate languages of one detection (Engine.detect_language)
 
 
 @dataclasses.dataclass
@@ -45,14 +46,53 @@ def detect_language(engine: Engine, n_items: int) -> np.ndarray:
     over the already-encoded windows, argmax restricted to the language tokens.  Returns [n_items] ids.
     (HF runs a second encoder pass for this; the native path reuses the encoder output of the first
     seek iteration, which covers the same 3000-frame window.)"""
+    return detect_language_probs(engine, n_items)[0]
+
+
+def detect_language_probs(engine: Engine, n_items: int, lang_ids=None):
+    """``detect_language`` with the probability of the winner: ([n_items] int64 ids, [n_items] float32 probabilities -- the
+    softmax over the candidate language tokens alone, as Whisper's own detect_language computes it).  ``lang_ids``: the
+    candidates (default: every language of the generation config).  The device engine does this in one kernel on the logits
+    where they lie (``Engine.detect_language``); an engine double without it goes through ``decode`` + ``last_logits``."""
     spec = engine.spec
     if not spec.lang_to_id:
         raise ValueError("Cannot detect language for an English-only checkpoint: the generation config has no `lang_to_id`.")
+    lang_ids = np.array(sorted(set(spec.lang_to_id.values()) if lang_ids is None else set(int(t) for t in lang_ids)), dtype=np.int64)
+    if hasattr(engine, "detect_language"):
+        best, prob, _ = engine.detect_language(n_items, lang_ids, no_speech=False)
+        best = np.asarray(best, np.int64)
+        col = np.searchsorted(lang_ids, best)
+        return best, np.asarray(prob, np.float32)[np.arange(n_items), col]
     prompt = np.full((n_items, 1), spec.decoder_start_token_id, dtype=np.int32)
     engine.decode(prompt, max_length=2)
     logits = engine.last_logits(n_items)
-    lang_ids = np.array(sorted(set(spec.lang_to_id.values())), dtype=np.int64)
-    return lang_ids[np.argmax(logits[:, lang_ids], axis=-1)]
+    cand = np.asarray(logits)[:, lang_ids]
+    win = np.argmax(cand, axis=-1)
+    c64 = cand.astype(np.float64)
+    e = np.exp(c64 - c64.max(axis=-1, keepdims=True))
+    return lang_ids[win], (e[np.arange(n_items), win] / e.sum(axis=-1)).astype(np.float32)
+
+
+def check_language_candidates(spec, candidates):
+    """``language_candidates``: the languages auto-detection may answer with, in any form ``language_to_id`` accepts ('<|en|>',
+    'en', 'english'); at least one, no language twice.  Returns their token ids, ascending; None for None."""
+    if candidates is None:
+        return None
+    if isinstance(candidates, (str, bytes)) or not hasattr(candidates, "__len__"):
+        raise ValueError(f"language_candidates is a list of languages, got {candidates!r}")
+    if len(candidates) == 0:
+        raise ValueError("language_candidates needs at least one language")
+    if not spec.lang_to_id:
+        raise ValueError("Cannot detect language for an English-only checkpoint: the generation config has no `lang_to_id`.")
+    ids = []
+    for c in candidates:
+        if not isinstance(c, str):
+            raise ValueError(f"language_candidates holds {c!r}: every entry is a language name, code or <|tag|>")
+        t = language_to_id(spec, c)
+        if t in ids:
+            raise ValueError(f"language_candidates lists {c!r} twice")
+        ids.append(t)
+    return sorted(ids)
 
 
 def language_to_id(spec, language: str) -> int:
@@ -539,11 +579,17 @@ def generate(engine: Engine, n_items: int, num_frames, *, language: Optional[str
              logprob_threshold: Optional[float] = None, no_speech_threshold: Optional[float] = None, prompt_ids=None,
              temperature=None, compression_ratio_threshold: Optional[float] = None, sampling_seed: int = 0, item_ids=None,
              return_token_logprobs: bool = False, top_logprobs: int = 0, sequence_bias=None,
-             return_alignment_scores: bool = False, alignment_collar_frames: Optional[int] = None):
+             return_alignment_scores: bool = False, alignment_collar_frames: Optional[int] = None, language_candidates=None):
     """Transcribe the ``n_items`` 30 s feature windows resident in the engine (items 0..n-1).
 
     Returns {"sequences": [B, Lmax] int64 (pad-right), "token_timestamps": list of float32 arrays,
-    "segments": list of list of Segment (host loop only)} -- the fields the pipeline consumes.
+    "segments": list of list of Segment (host loop only)} -- the fields the pipeline consumes -- and, in every decoding mode,
+    "languages": [B] int64, the language token each item was decoded with (forced or detected; -1 when the decoder prompt
+    carries none, as for an English-only checkpoint) and "language_probs": [B] float32, the detection probability (the softmax
+    over the candidate language tokens alone; NaN where the language was forced).
+
+    ``language_candidates`` (only with ``language=None``): the languages auto-detection may answer with, in any form
+    ``language_to_id`` accepts; at least one, none twice (``check_language_candidates``).
 
     ``native`` (default: whenever the engine exports it) runs the seek loop inside the library
     (``cw_transcribe``, one C call per batch); ``native=False`` runs the same control flow here, stage by stage
@@ -606,7 +652,7 @@ def generate(engine: Engine, n_items: int, num_frames, *, language: Optional[str
                          temperature=temperature, compression_ratio_threshold=compression_ratio_threshold,
                          sampling_seed=sampling_seed, item_ids=item_ids, return_token_logprobs=return_token_logprobs,
                          top_logprobs=top_logprobs, return_alignment_scores=return_alignment_scores,
-                         alignment_collar_frames=alignment_collar_frames)
+                         alignment_collar_frames=alignment_collar_frames, language_candidates=language_candidates)
     finally:
         if table is not None:
             engine.set_sequence_bias(None)
@@ -614,9 +660,14 @@ def generate(engine: Engine, n_items: int, num_frames, *, language: Optional[str
 
 def _generate(engine: Engine, n_items: int, num_frames, *, language, task, max_new_tokens, min_new_tokens, num_beams, stats, native,
               logprob_threshold, no_speech_threshold, prompt_ids, temperature, compression_ratio_threshold, sampling_seed, item_ids,
-              return_token_logprobs, top_logprobs, return_alignment_scores=False, alignment_collar_frames=None):
+              return_token_logprobs, top_logprobs, return_alignment_scores=False, alignment_collar_frames=None,
+              language_candidates=None):
     """``generate`` proper: everything but the sequence_bias table, which ``generate`` sets around this call."""
     spec = engine.spec
+    cand_ids = check_language_candidates(spec, language_candidates)
+    if cand_ids is not None and (language is not None or not resolve_prompt(spec, language, task)[1]):
+        raise ValueError("language_candidates restricts language auto-detection: it cannot be combined with a language that is "
+                         "given (generate_kwargs['language'] or the generation config's own)")
     want_as = bool(return_alignment_scores)
     collar = check_alignment_collar(spec, alignment_collar_frames)
     if want_as and not hasattr(engine, "set_alignment_scores"):
@@ -699,7 +750,8 @@ def _generate(engine: Engine, n_items: int, num_frames, *, language, task, max_n
         toks, tts, n_calls = engine.transcribe(
             n_items, num_frames, sot=spec.decoder_start_token_id, language_token=lang_tok, task_token=task_tok,
             max_new_tokens=-1 if max_new_tokens is None else int(max_new_tokens), min_new_tokens=min_new_tokens or 0,
-            max_length=spec.max_length, lang_ids=sorted(set(spec.lang_to_id.values())) if spec.lang_to_id else None,
+            max_length=spec.max_length,
+            lang_ids=cand_ids if cand_ids is not None else (sorted(set(spec.lang_to_id.values())) if spec.lang_to_id else None),
             prefix=prefix)
         if stats is not None:
             stats["generate_calls"] = stats.get("generate_calls", 0) + n_calls
@@ -708,6 +760,11 @@ def _generate(engine: Engine, n_items: int, num_frames, *, language, task, max_n
         for i, s in enumerate(toks):
             sequences[i, :len(s)] = s
         out = {"sequences": sequences, "token_timestamps": tts, "segments": None}
+        if hasattr(engine, "transcribe_languages"):
+            ltok, lprob = engine.transcribe_languages(n_items)
+        else:                                   # an engine double without the getter: only a forced language is known here
+            ltok, lprob = np.full(n_items, lang_tok), np.full(n_items, np.nan)
+        out["languages"], out["language_probs"] = np.asarray(ltok, np.int64), np.asarray(lprob, np.float32)
         if want_lp:
             out["token_logprobs"] = engine.transcribe_token_logprobs([len(s) for s in toks])
         if want_top:
@@ -720,10 +777,13 @@ def _generate(engine: Engine, n_items: int, num_frames, *, language, task, max_n
     if detect:
         # language auto-detection (the reference does not pass `language`, REF/transcribe.py:33)
         engine.encode(list(range(n_items)), np.zeros(n_items, np.int64), np.full(n_items, N_FRAMES, np.int64))
-        langs = detect_language(engine, n_items)
+        langs, lang_probs = detect_language_probs(engine, n_items, cand_ids)
         init = np.asarray([init_tokens(spec, language, task, lang_id=l, prompt_ids=prefix) for l in langs], dtype=np.int32)
         pre_encoded = True
     else:
+        toks = resolve_prompt(spec, language, task)[0]
+        forced_lang = int(toks[1]) if len(toks) > 1 and toks[1] in set(spec.lang_to_id.values()) else -1
+        langs, lang_probs = np.full(n_items, forced_lang, np.int64), np.full(n_items, np.nan, np.float32)
         init = np.tile(np.asarray(init_tokens(spec, language, task, prompt_ids=prefix), dtype=np.int32), (n_items, 1))
     n_prompt = init.shape[1]
     if prefix is not None:
@@ -751,7 +811,8 @@ def _generate(engine: Engine, n_items: int, num_frames, *, language, task, max_n
     for i, s in enumerate(seq_list):
         sequences[i, :len(s)] = s
     tts = [np.concatenate([s.token_timestamps for s in segs]) if segs else np.zeros(0, np.float32) for segs in segments]
-    out = {"sequences": sequences, "token_timestamps": tts, "segments": segments}
+    out = {"sequences": sequences, "token_timestamps": tts, "segments": segments,
+           "languages": np.asarray(langs, np.int64), "language_probs": np.asarray(lang_probs, np.float32)}
     if want_lp:
         out["token_logprobs"] = [np.concatenate([s.token_logprobs for s in segs]) if segs else np.zeros(0, np.float32)
                                  for segs in segments]

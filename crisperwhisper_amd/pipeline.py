@@ -377,21 +377,22 @@ def add_alignment_scores(words, groups, token_mass, token_spread):
     return words
 
 
-def scored_words(vocab, outputs, token_logprobs, warn=None, token_top=None, return_groups=False):
+def scored_words(vocab, outputs, token_logprobs, warn=None, token_top=None, return_groups=False, return_language=False):
     """``collate.decode_asr(outputs, return_timestamps="word")`` with "logprob" on every word: the float64 sum of
     ``token_logprobs`` (one array per entry of ``outputs``, one value per token) over the collator's own token group of the word.
     The groups address the concatenation of all windows' tokens, so a token the seam merge drops counts in no word.
 
     ``token_top`` (one (ids [n_tok][k], log-probabilities [n_tok][k]) pair per entry of ``outputs``) adds "tokens" to every
     word, over the same group: ``[{"id", "text", "logprob", "top_logprobs": [{"id", "text", "logprob"}, ...]}]``, alternatives
-    best first, entries with id -1 left out.  ``return_groups=True`` returns the collator's token groups as a third value."""
+    best first, entries with id -1 left out.  ``return_groups=True`` returns the collator's token groups as a third value;
+    ``return_language=True`` adds "language" to every word (``collate.decode_asr``)."""
     if len(token_logprobs) != len(outputs) or any(len(a) != len(o["tokens"]) for a, o in zip(token_logprobs, outputs)):
         raise ValueError("scored_words: one log-probability per token of every window is required")
     if token_top is not None and (len(token_top) != len(outputs) or any(
             len(t[0]) != len(o["tokens"]) or len(t[1]) != len(o["tokens"]) for t, o in zip(token_top, outputs))):
         raise ValueError("scored_words: one row of alternatives per token of every window is required")
     text, words, groups = collate.decode_asr(vocab, outputs, time_precision=0.02, warn=warn, return_timestamps="word",
-                                             return_token_groups=True)
+                                             return_token_groups=True, return_language=return_language)
     flat = np.concatenate([np.asarray(a, np.float64) for a in token_logprobs]) if token_logprobs else np.zeros(0, np.float64)
     for w, g in zip(words, groups):
         w["logprob"] = float(np.sum(flat[g]))
@@ -544,7 +545,17 @@ class CrisperWhisperPipeline:
 
     def _run_one(self, inputs, return_timestamps=None, generate_kwargs=None, chunk_length_s=None,
                  stride_length_s=None, return_language=None, sampling_seed=None, return_scores=None, top_logprobs=None,
-                 return_alignment_scores=None, alignment_collar_frames=None, **unused):
+                 return_alignment_scores=None, alignment_collar_frames=None, language_candidates=None, **unused):
+        """``return_language=True``: every chunk gains "language", the full lowercase name of the language its window was
+        decoded with (``LANGUAGES[code]``, as transformers gives it; None when the decoder prompt carries no language), in word
+        and in segment mode and in every decoding mode.  Each window's language token -- forced or detected -- is put in front
+        of the window's tokens for the collation, as the transformers pipeline does, with a placeholder in front of every
+        per-token array so that they stay aligned.  Knowing the language changes word splitting for the six languages written
+        without spaces (chinese, japanese, thai, lao, myanmar, cantonese), exactly as it does in transformers: their words are
+        split per character.  For every other language ``text`` and every ``timestamp`` equal the call without it.
+
+        ``language_candidates`` (a call argument, not a ``generate_kwargs`` key; only with ``language`` unset): the languages
+        auto-detection may answer with during this call, e.g. ``["de", "es"]``."""
         seed = self.sampling_seed if sampling_seed is None else _check_seed(sampling_seed)
         rt = return_timestamps if return_timestamps is not None else self.return_timestamps
         scores = self.return_scores if return_scores is None else bool(return_scores)
@@ -566,10 +577,14 @@ class CrisperWhisperPipeline:
             raise ValueError("crisperwhisper_amd implements the timestamped paths: pass return_timestamps='word' "
                              "(CrisperWhisper's purpose, REF/transcribe.py:28) or True (segment-level chunks, the "
                              "setting REF/app.py:51-61 constructs its pipeline with)")
-        if return_language:
-            raise ValueError("return_language is not supported on the native path")
+        want_lang = bool(return_language)
         gk = dict(generate_kwargs or {})
         _check_generate_kwargs(gk, self.default_num_beams, self.bundle.spec, seed)
+        if language_candidates is not None:                 # refused before any audio is loaded
+            generation.check_language_candidates(self.bundle.spec, language_candidates)
+            if gk.get("language") is not None or not generation.resolve_prompt(self.bundle.spec, None, gk.get("task"))[1]:
+                raise ValueError("language_candidates restricts language auto-detection: it cannot be combined with a language "
+                                 "that is given (generate_kwargs['language'] or the generation config's own)")
         if "num_beams" not in gk:
             _warn_once("beams", f"no num_beams given: decoding with {self.default_num_beams} beams like the installed transformers "
                                 "ASR pipeline default; pass generate_kwargs={'num_beams': 1} for the greedy decoding of the 2024 reference")
@@ -621,18 +636,34 @@ class CrisperWhisperPipeline:
                 sampling_seed=seed or 0, item_ids=idxs, **({"return_token_logprobs": True} if scores else {}),
                 **({"top_logprobs": top_k} if top_k else {}),
                 **({"return_alignment_scores": True, "alignment_collar_frames": collar} if align_on else {}),
-                **({"sequence_bias": gk["sequence_bias"]} if gk.get("sequence_bias") is not None else {}))
+                **({"sequence_bias": gk["sequence_bias"]} if gk.get("sequence_bias") is not None else {}),
+                **({"language_candidates": language_candidates} if language_candidates is not None else {}))
             if "fallback" in st:
                 fallback_trace.extend(st["fallback"])
             rs = []
             for k, i in enumerate(idxs):
                 n_tok = len(out["token_timestamps"][k])
                 stride = tuple(x / sr for x in windows[i][2])
-                rs.append(dist.pack_record(i, out["sequences"][k][:n_tok], out["token_timestamps"][k], stride,
-                                           out["token_logprobs"][k] if scores else None,
-                                           (out["top_ids"][k], out["top_logprobs"][k]) if top_k else None))
+                r_tok, r_ts = out["sequences"][k][:n_tok], out["token_timestamps"][k]
+                r_lp = out["token_logprobs"][k] if scores else None
+                r_top = (out["top_ids"][k], out["top_logprobs"][k]) if top_k else None
+                r_as = (out["alignment_scores"][k], out["alignment_spreads"][k]) if align_on else None
+                if want_lang and int(out["languages"][k]) >= 0:
+                    # the window's language token leads its tokens (TF/pipelines/automatic_speech_recognition.py:640-650); it
+                    # belongs to no word, so the placeholder in front of every per-token array belongs to no group
+                    nan1 = np.full(1, np.nan, np.float32)
+                    r_tok = np.concatenate([np.asarray([out["languages"][k]], np.int64), np.asarray(r_tok, np.int64)])
+                    r_ts = np.concatenate([np.zeros(1, np.float32), np.asarray(r_ts, np.float32)])
+                    if scores:
+                        r_lp = np.concatenate([nan1, np.asarray(r_lp, np.float32)])
+                    if top_k:
+                        r_top = (np.concatenate([np.full((1, top_k), -1, np.int32), np.asarray(r_top[0], np.int32).reshape(-1, top_k)]),
+                                 np.concatenate([np.full((1, top_k), np.nan, np.float32), np.asarray(r_top[1], np.float32).reshape(-1, top_k)]))
+                    if align_on:
+                        r_as = (np.concatenate([nan1, np.asarray(r_as[0], np.float32)]), np.concatenate([nan1, np.asarray(r_as[1], np.float32)]))
+                rs.append(dist.pack_record(i, r_tok, r_ts, stride, r_lp, r_top))
                 if align_on:                               # the alignment scores travel behind the record, whatever its width
-                    rs[-1] = dist.append_alignment(rs[-1], out["alignment_scores"][k], out["alignment_spreads"][k])
+                    rs[-1] = dist.append_alignment(rs[-1], r_as[0], r_as[1])
             return rs, st.get("generate_calls", 0)
 
         per = self.batch_size
@@ -684,13 +715,14 @@ class CrisperWhisperPipeline:
             token_lp.extend(lp)
         if scores:
             text, words, groups = scored_words(self.vocab, outputs, token_lp, warn=logger.warning,
-                                               token_top=token_top if top_k else None, return_groups=True)
+                                               token_top=token_top if top_k else None, return_groups=True,
+                                               return_language=want_lang)
         elif align_on:
             text, words, groups = collate.decode_asr(self.vocab, outputs, time_precision=0.02, warn=logger.warning,
-                                                     return_timestamps="word", return_token_groups=True)
+                                                     return_timestamps="word", return_token_groups=True, return_language=want_lang)
         else:
             text, words = collate.decode_asr(self.vocab, outputs, time_precision=0.02, warn=logger.warning,
-                                             return_timestamps="word" if rt == "word" else True)
+                                             return_timestamps="word" if rt == "word" else True, return_language=want_lang)
         if align_on:
             add_alignment_scores(words, groups, token_mass, token_spread)
         t_ph.append(_time.perf_counter())
@@ -700,6 +732,64 @@ class CrisperWhisperPipeline:
                                            "collate_all_chunks": t_ph[4] - t_ph[3], "local_chunks": len(mine), "all_chunks": len(windows)}
         return {"text": text, "chunks": words}
 
+
+    def detect_language(self, inputs, candidates=None):
+        """Which language is this, how sure is the model, and is there speech at all -- without transcribing.  ``inputs`` in
+        any form ``__call__`` takes (one, or a list); ``candidates``: the languages to choose among, in any form
+        ``generate_kwargs["language"]`` accepts (None: every language of the generation config).  The audio is cut into
+        consecutive non-overlapping 30 s windows, batched by ``batch_size``; a batch is one encoder pass, one decoder step on
+        <|startoftranscript|> and one kernel on the logits where they lie (``Engine.detect_language``).  Per input
+        {"language": "german", "code": "de", "token_id", "probability", "no_speech_prob", "probabilities": {code: p},
+        "windows": [{"timestamp": (t0, t1), the same fields}]}: ``probabilities`` is the softmax over the candidates alone
+        (Whisper's own detect_language), ``no_speech_prob`` the probability of <|nospeech|> over the whole vocabulary.  With
+        more than one window the top-level vector is the float64 mean of the windows' vectors (the language its arg-max, the
+        lower token id on a tie) and ``no_speech_prob`` their mean; with one window the top level is that window.  Runs on this
+        rank's engine; it is not sharded."""
+        from ._native import N_FRAMES
+        from .languages import LANGUAGES
+        spec = self.bundle.spec
+        ids = generation.check_language_candidates(spec, candidates)
+        if ids is None:
+            if not spec.lang_to_id:
+                raise ValueError("Cannot detect language for an English-only checkpoint: the generation config has no `lang_to_id`.")
+            ids = sorted(set(spec.lang_to_id.values()))
+        if len(ids) > generation.LANG_IDS_MAX:
+            raise ValueError(f"{len(ids)} candidate languages; the kernel takes at most {generation.LANG_IDS_MAX}")
+        code_of = {int(t): tag[2:-2] for tag, t in spec.lang_to_id.items()}
+        codes = [code_of[t] for t in ids]
+        single = not isinstance(inputs, (list, tuple))
+        pcms = [self._load(x) for x in ([inputs] if single else inputs)]
+        sr = self.sampling_rate
+        wins = [(k, s0) for k, pcm in enumerate(pcms) for s0 in range(0, max(len(pcm), 1), N_SAMPLES)]
+        eng = self.engine
+        per = max(1, min(self.batch_size, eng.max_batch))
+        rows = []                                           # per window (best id, float64 probabilities, no-speech probability)
+        for b0 in range(0, len(wins), per):
+            batch = wins[b0:b0 + per]
+            n = len(batch)
+            eng.mel([pcms[k][s0:s0 + N_SAMPLES] for k, s0 in batch])
+            eng.encode(list(range(n)), [0] * n, [N_FRAMES] * n)
+            best, prob, ns = eng.detect_language(n, ids, no_speech=True)
+            rows.extend((int(best[r]), prob[r].astype(np.float64), float(ns[r])) for r in range(n))
+
+        def record(best, p, ns):
+            j = ids.index(best)
+            return {"language": LANGUAGES.get(codes[j], codes[j]), "code": codes[j], "token_id": int(best),
+                    "probability": float(p[j]), "no_speech_prob": float(ns),
+                    "probabilities": {c: float(x) for c, x in zip(codes, p)}}
+        results = []
+        for k, pcm in enumerate(pcms):
+            mine = [(s0, rows[w]) for w, (kk, s0) in enumerate(wins) if kk == k]
+            windows = [dict(timestamp=(s0 / sr, min(len(pcm), s0 + N_SAMPLES) / sr), **record(*r)) for s0, r in mine]
+            if len(mine) == 1:
+                top = record(*mine[0][1])
+            else:
+                p = np.mean(np.stack([r[1] for _, r in mine]), axis=0)
+                j = int(np.argmax(np.where(np.isnan(p), -np.inf, p)))
+                top = record(ids[j], p, float(np.mean([r[2] for _, r in mine])))
+            top["windows"] = windows
+            results.append(top)
+        return results[0] if single else results
 
     def phrase_bias(self, phrases) -> list:
         """A ``sequence_bias`` list for ``generate_kwargs`` from ``{phrase: bias}``: for every phrase its token sequence as the

@@ -272,6 +272,39 @@ int32_t cw_transcribe_prompted(cw_ctx* ctx, int32_t B, const int32_t* num_frames
                                const int32_t* prefix, int32_t n_prefix, int32_t* tokens, float* token_ts, int32_t* lens,
                                int32_t cap, int32_t* n_passes);
 
+/* Language identification (Whisper's detect_language, generation_whisper.py:1610-1673) over the nb windows already encoded:
+ * one decoder forward on <|startoftranscript|> at position 0, made as cw_decode makes its position 0 (the same kernels at
+ * every row count, so the logits are those of cw_decode(prompt = sot, max_length 2) bit for bit), then one kernel
+ * (csrc/langid.hip) on the logits where the forward left them -- they never leave the device; the results are one copy of
+ * nb * (n_lang + 2) * 4 bytes.  lang_ids [n_lang]: the candidate language tokens, 1 .. CW_LANG_IDS_MAX distinct ids inside
+ * the vocabulary (all of generation_config.lang_to_id, or the languages a deployment expects).
+ *   best [nb]             the candidate with the largest logit, lowest token id on an exact tie; a NaN logit is never a candidate
+ *   prob [nb][n_lang]     (nullable) expf(l_k - m) / S in table order, m the maximum over the candidates and S the f32 sum of
+ *                         expf(l_j - m) over the candidates: softmax with every other column masked, not a softmax over the
+ *                         vocabulary.  A candidate at -inf gets exactly 0.  No candidate above -inf: best is the lowest
+ *                         candidate id and every prob is NaN.
+ *   no_speech [nb]        (nullable) softmax of the same logits over the whole vocabulary at token no_timestamps_token_id - 1
+ *                         (the quantity of cw_no_speech_probs, in f32 on the device).
+ * cw_get_logits afterwards returns the logits the kernel consumed.  Refused before anything is launched: CW_ERR_INVALID for a
+ * null lang_ids / best, n_lang outside 1 .. CW_LANG_IDS_MAX, an id outside the vocabulary, a duplicate id; CW_ERR_STATE for nb
+ * above the encoded windows or before cw_set_generation.
+ * cw_transcribe / cw_transcribe_prompted with language_token < 0 detect through it over cfg->lang_ids: an id listed more than
+ * once there counts once, as it always has; more than CW_LANG_IDS_MAX distinct ids are refused with CW_ERR_INVALID (the host
+ * loop this replaces took any number; Whisper has at most 100 languages).
+ * cw_get_transcribe_languages: the language token every item of the last cw_transcribe / cw_transcribe_prompted was decoded
+ * with, and its detection probability (NaN where the language was forced).  A forced cfg->language_token that is not among
+ * cfg->lang_ids (when those are given) is no language: -1 is reported for it.                                              */
+#define CW_LANG_IDS_MAX 128
+int32_t cw_detect_language(cw_ctx* ctx, int32_t nb, int32_t sot_token, const int32_t* lang_ids, int32_t n_lang,
+                           int32_t* best /* [nb] */, float* prob /* [nb][n_lang], nullable */,
+                           float* no_speech /* [nb], nullable */);
+int32_t cw_get_transcribe_languages(cw_ctx* ctx, int32_t* lang_token /* [B] */, float* prob /* [B] */, int32_t B);
+/* cw_test_language_probs: the kernel of cw_detect_language, through the same launcher, on caller-supplied rows: logits [nb][V]
+ * go into the context's logits buffer with its real row stride, the pad columns hold +75 during the call (they must never
+ * count).  nospeech_token -1: no no-speech part (no_speech, if given, is NaN).                                              */
+int32_t cw_test_language_probs(cw_ctx* ctx, const float* logits /* [nb][V] */, int32_t nb, const int32_t* lang_ids,
+                               int32_t n_lang, int32_t nospeech_token, int32_t* best, float* prob, float* no_speech);
+
 /* ---- beam search (the transformers 5.x ASR pipeline defaults to num_beams = 5,
  * TF/pipelines/automatic_speech_recognition.py:160-163): device half of GenerationMixin._beam_search
  * (TF/generation/utils.py:3208-3520) over the encoded windows 0..n_items-1, items x beams decoder rows (row = item *
@@ -452,6 +485,10 @@ int32_t cw_collate_get(cw_collator* c, uint8_t* text, double* starts, double* en
  * group_offsets[k + 1]).                                                                                                   */
 int64_t cw_collate_token_groups_total(cw_collator* c);
 int32_t cw_collate_get_token_groups(cw_collator* c, int64_t* group_offsets /* [n+1] */, int32_t* token_index);
+/* The language token in force for every chunk of cw_collate_get (-1: none), by the rules of _decode_asr(return_language=True):
+ * a word carries the language token seen last when its segment is flushed (a segment merged across a chunk seam takes the later
+ * window's); a segment chunk starts from the language seen last and takes a language token met while it is current.          */
+int32_t cw_collate_get_languages(cw_collator* c, int32_t* lang_token /* [n_chunks] */);
 void cw_collate_free(cw_collator* c);
 
 /* ---- kernel-level hooks used by the parity tests (host f32 in/out, run in the context's dtype) -------- */
