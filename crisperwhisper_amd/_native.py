@@ -137,6 +137,9 @@ _SIGS = {
     "cw_test_align_path_scores": (_I, [_P, _P, _I, _I, _I, _I, _P, _P, _I, _P, _P]),
     "cw_score_tokens": (_I, [_P, _I, _I, _P, _I, _P, _I, _P, _P, _P]),
     "cw_align_score_tokens": (_I, [_P, _I, _P, _P, _I, _P, _I, _P, _P, _P, _P]),
+    "cw_align_cut_tokens": (_I, [_P, _I, _P, _P, _I, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "cw_test_score_head_stop": (_I, [_P, _I, _I, _I, _P, _P, _P, _P, _P, _I, _I, _P, _P, _P, _P]),
+    "cw_test_align_cut": (_I, [_P, _I, _I, _P, _P, _P, _P, _P, _P, _P]),
     "cw_score_prefill_runs": (_I, [_P]),
     "cw_align_matrix": (_I, [_P, _P, _I, _I, _I, _I, _P, _I, _P]),
     "cw_dtw": (_I, [_P, _P, _I, _I, _P, _P, _P]),

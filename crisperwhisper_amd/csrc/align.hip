@@ -11,6 +11,7 @@
 //   pauses_kernel        REF/utils.py:8-26: per-boundary pause redistribution (boundaries independent)
 //   align_path_score_kernel  (cw_set_alignment_scores) per token row, the share of the heads' attention inside the frames the
 //                        path gave the token, and the attention's spread in seconds
+//   align_cut_kernel     (cw_align_cut_tokens) per row, the most probable count of offered tokens that a window holds
 #include <limits.h>
 #include <stdlib.h>
 #include "common.h"
@@ -453,6 +454,43 @@ int cw_launch_align_path_score(const float* w, int B, int Ha, int rows_cap, int 
     if ((rows + APS_WAVES - 1) / APS_WAVES > 0x7fffffffLL) return CW_ERR_INVALID;
     hipLaunchKernelGGL(align_path_score_kernel, dim3((unsigned)((rows + APS_WAVES - 1) / APS_WAVES)), dim3(64 * APS_WAVES), 0, st,
                        w, B, Ha, rows_cap, S, row0, N, n_cols, first_col, collar, mass, spread);
+    return CW_OK;
+}
+
+// cw_align_cut_tokens: how much of the offered text was spoken inside the window.  One thread per row r: with lp / st the row's
+// n_tok + 1 scores from base[r] on,  S[n] = sum_{i<n} lp[i] + st[n]  is the log-probability that exactly the first n tokens are
+// the window's text (n tokens, then "the text stops").  cut = the allowed n (ok[n] != 0) of the largest S[n], the lowest on an
+// exact tie; a forced row takes n_tok whatever the mask says.  The prefix sum is float64, strictly ascending, one add per
+// term -- no product, so nothing contracts -- and cut_score is S[cut] rounded once to f32: the same bits on every run.
+__global__ __launch_bounds__(64) void align_cut_kernel(const float* __restrict__ logprob, const float* __restrict__ stop_logprob,
+                                                       const int* __restrict__ base, const int* __restrict__ n_tok,
+                                                       const unsigned char* __restrict__ cut_ok, int ok_stride,
+                                                       const unsigned char* __restrict__ force, int rows,
+                                                       int* __restrict__ cut, float* __restrict__ cut_score) {
+    const int r = blockIdx.x * 64 + threadIdx.x;
+    if (r >= rows) return;
+    const float* lp = logprob + base[r];
+    const float* st = stop_logprob + base[r];
+    const unsigned char* ok = cut_ok + (size_t)r * ok_stride;
+    const int N = n_tok[r];
+    const bool forced = force[r] != 0;
+    double acc = 0.0, best = 0.0;
+    int best_n = -1;
+    for (int n = 0; n <= N; ++n) {
+        const double s = acc + (double)st[n];
+        if (forced ? n == N : (ok[n] != 0 && (best_n < 0 || s > best))) { best = s; best_n = n; }
+        acc += (double)lp[n];                              // (the entry at N is the eos: read, never part of a candidate)
+    }
+    cut[r] = best_n;                                       // -1: no candidate (the caller refuses such a row before the launch)
+    cut_score[r] = best_n < 0 ? -INFINITY : (float)best;
+}
+
+int cw_launch_align_cut(const float* logprob, const float* stop_logprob, const int* base, const int* n_tok,
+                        const unsigned char* cut_ok, int ok_stride, const unsigned char* force, int rows, int* cut,
+                        float* cut_score, hipStream_t st) {
+    if (rows < 1 || ok_stride < 1) return CW_ERR_INVALID;
+    hipLaunchKernelGGL(align_cut_kernel, dim3((rows + 63) / 64), dim3(64), 0, st, logprob, stop_logprob, base, n_tok, cut_ok,
+                       ok_stride, force, rows, cut, cut_score);
     return CW_OK;
 }
 

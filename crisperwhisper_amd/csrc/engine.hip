@@ -251,6 +251,16 @@ struct cw_ctx {
     bool score_hook = false;
     float *sc_step_lp = nullptr, *sc_step_tl = nullptr;
     int* sc_step_ti = nullptr;
+    // cw_align_cut_tokens: the STOP form of the head (stop_logprob beside the scores; score_stop switches the loop's hook to it)
+    // and the cut kernel's arguments and results, [Bm] each, cut_ok [Bm][TGT] bytes
+    bool score_stop = false;
+    size_t sc_stop_rows = 0, sc_sparts = 0;
+    float* sc_stop = nullptr;
+    ScoreStopPart* sc_spart = nullptr;
+    float* sc_step_stop = nullptr;
+    int *cut_base = nullptr, *cut_ntok = nullptr, *cut_out = nullptr;
+    float* cut_score = nullptr;
+    unsigned char *cut_force = nullptr, *cut_ok = nullptr;
     int stage_kind[CW_MAX_DEC_STAGES] = {};
     int stage_launches[CW_MAX_DEC_STAGES] = {};   // kernel launches behind each stage (2 where gemv_prep_kernel precedes gemv_mt_kernel)
     float stage_ms[CW_N_STAGES] = {};
@@ -715,7 +725,8 @@ void cw_destroy(cw_ctx* c) {
     for (auto& o : c->out_stages) hipFree(o.stage);
     for (void* p : c->allocs) hipFree(p);
     for (void* p : {(void*)c->pf_x, c->pf_a, c->pf_q, c->pf_o, c->pf_h}) if (p) hipFree(p);
-    for (void* p : {(void*)c->sc_src, (void*)c->sc_tgt, (void*)c->sc_ti, c->sc_a, (void*)c->sc_part, (void*)c->sc_lp, (void*)c->sc_tl}) if (p) hipFree(p);
+    for (void* p : {(void*)c->sc_src, (void*)c->sc_tgt, (void*)c->sc_ti, c->sc_a, (void*)c->sc_part, (void*)c->sc_lp, (void*)c->sc_tl,
+                    (void*)c->sc_stop, (void*)c->sc_spart}) if (p) hipFree(p);
     if (c->h_nunf) hipHostFree(c->h_nunf);
     if (c->ev0) hipEventDestroy(c->ev0);
     if (c->ev1) hipEventDestroy(c->ev1);
@@ -1860,7 +1871,10 @@ static int decode_once(cw_ctx* c, int32_t nb, const int32_t* prompt, int32_t n_p
             // forward at position t-1, logits, fused processors + argmax -> ids[t], x for position t, pos := t
             c->hist_short = t <= 64;               // keys 0 .. t-1
             CWCHK(c, run_step(c, nb));
-            if (c->score_hook)    // cw_score_tokens' loop: log-softmax / target / arg-max of the raw logits that predict ids[t]
+            if (c->score_hook && c->score_stop)   // ... of cw_align_cut_tokens: the same three numbers and stop_logprob
+                CWCHK(c, KD(c, cw_launch_score_rows_stop, c->dlogits, c->Vpad, V, c->d_forced, TGT, t, nb, c->gen.eos_token_id, c->gen.no_timestamps_token_id + 1,
+                            c->sc_step_lp, c->sc_step_ti, c->sc_step_tl, c->sc_step_stop, c->st));
+            else if (c->score_hook)    // cw_score_tokens' loop: log-softmax / target / arg-max of the raw logits that predict ids[t]
                 CWCHK(c, KD(c, cw_launch_score_rows, c->dlogits, c->Vpad, V, c->d_forced, TGT, t, nb, c->sc_step_lp, c->sc_step_ti, c->sc_step_tl, c->st));
             if (c->logits_capture && step < c->logits_capture_steps)
                 HIPCHK(c, hipMemcpy2DAsync(c->logits_capture + (size_t)step * nb * V, (size_t)V * 4, c->dlogits, (size_t)c->Vpad * 4, (size_t)V * 4, nb, hipMemcpyDeviceToHost, c->st));
@@ -3137,6 +3151,61 @@ static int score_reserve(cw_ctx* c, size_t M, size_t parts) {
     return CW_OK;
 }
 
+// what cw_align_cut_tokens needs on top: stop_logprob [M] and the stop records of the head, the cut kernel's [Bm] arrays
+static int cut_reserve(cw_ctx* c, size_t M, size_t parts) {
+    if (M > c->sc_stop_rows) {
+        HIPCHK(c, hipStreamSynchronize(c->st));
+        if (c->sc_stop) { hipFree(c->sc_stop); c->sc_stop = nullptr; }
+        c->sc_stop_rows = 0;
+        hipError_t e = hipMalloc((void**)&c->sc_stop, M * 4);
+        if (e != hipSuccess) return fail(c, CW_ERR_NOMEM, "align_cut: hipMalloc(%zu) failed: %s", M * 4, hipGetErrorString(e));
+        c->sc_stop_rows = M;
+    }
+    if (parts > c->sc_sparts) {
+        HIPCHK(c, hipStreamSynchronize(c->st));
+        if (c->sc_spart) { hipFree(c->sc_spart); c->sc_spart = nullptr; }
+        c->sc_sparts = 0;
+        hipError_t e = hipMalloc((void**)&c->sc_spart, parts * sizeof(ScoreStopPart));
+        if (e != hipSuccess) return fail(c, CW_ERR_NOMEM, "align_cut: hipMalloc(%zu) failed: %s", parts * sizeof(ScoreStopPart), hipGetErrorString(e));
+        c->sc_sparts = parts;
+    }
+    if (!c->cut_ok) {
+        const size_t Bm = (size_t)c->Bm;
+        CWCHK(c, dmalloc(c, &c->cut_base, Bm * 4)); CWCHK(c, dmalloc(c, &c->cut_ntok, Bm * 4)); CWCHK(c, dmalloc(c, &c->cut_out, Bm * 4));
+        CWCHK(c, dmalloc(c, &c->cut_score, Bm * 4)); CWCHK(c, dmalloc(c, &c->cut_force, Bm));
+        CWCHK(c, dmalloc(c, &c->cut_ok, Bm * c->d.max_target_positions));
+    }
+    return CW_OK;
+}
+
+// cw_align_cut_tokens' extra arguments; null through score_rows: the plain scoring calls
+struct CutArgs {
+    const uint8_t* cut_ok;       // [rows][ids_stride]
+    const uint8_t* force_all;    // [rows]
+    int32_t* cut;                // [rows] out
+    float* cut_score;            // [rows] out
+    float* stop_logprob;         // [rows][ids_stride] out
+};
+
+// the cut kernel's arguments, uploaded before the forward: row r's scores start at base[r] in the arrays the head fills
+static int cut_upload(cw_ctx* c, int rows, int ids_stride, const int32_t* n_ids, int n_init, const CutArgs& ca,
+                      const std::vector<int>& base) {
+    const int TGT = c->d.max_target_positions;
+    std::vector<int> ntok(rows);
+    std::vector<uint8_t> ok((size_t)rows * TGT, 0), force(rows);
+    for (int r = 0; r < rows; ++r) {
+        ntok[r] = n_ids[r] - n_init - 1;
+        force[r] = ca.force_all[r] ? 1 : 0;
+        memcpy(ok.data() + (size_t)r * TGT, ca.cut_ok + (size_t)r * ids_stride, (size_t)ntok[r] + 1);
+    }
+    HIPCHK(c, hipMemcpyAsync(c->cut_base, base.data(), (size_t)rows * 4, hipMemcpyHostToDevice, c->st));
+    HIPCHK(c, hipMemcpyAsync(c->cut_ntok, ntok.data(), (size_t)rows * 4, hipMemcpyHostToDevice, c->st));
+    HIPCHK(c, hipMemcpyAsync(c->cut_force, force.data(), (size_t)rows, hipMemcpyHostToDevice, c->st));
+    HIPCHK(c, hipMemcpyAsync(c->cut_ok, ok.data(), ok.size(), hipMemcpyHostToDevice, c->st));
+    HIPCHK(c, hipStreamSynchronize(c->st));      // host vectors go out of scope
+    return CW_OK;
+}
+
 // The scoring head over the residual stream run_prefill (full) leaves in pf_x [rows][n_pos][D]: position p of a row predicts id
 // p + 1, and only positions n_init-1 .. n_ids[row]-2 are projected.  score_head_prepare uploads their list and targets (they
 // depend on the arguments alone, so before the forward), score_head_launch queues the kernels behind the forward,
@@ -3156,34 +3225,50 @@ static int score_head_prepare(cw_ctx* c, int rows, int n_pos, const int32_t* ids
     return CW_OK;
 }
 
-static int score_head_launch(cw_ctx* c, int M) {
+static int score_head_launch(cw_ctx* c, int M, int cut_rows = 0) {
     const int V = c->d.vocab_size, D = c->d.d_model;
     CWCHK(c, KD(c, cw_launch_score_ln, c->pf_x, c->sc_src, c->dec_ln_g, c->dec_ln_b, c->sc_a, M, D, c->st));
+    if (cut_rows > 0) {                          // cw_align_cut_tokens: the STOP head, then the cut on the arrays it leaves
+        CWCHK(c, KD(c, cw_launch_score_head_stop, c->sc_a, c->embed_pk, c->sc_tgt, c->sc_part, c->sc_spart, M, V, D, c->gen.eos_token_id,
+                    c->gen.no_timestamps_token_id + 1, c->sc_lp, c->sc_ti, c->sc_tl, c->sc_stop, c->st));
+        CWCHK(c, cw_launch_align_cut(c->sc_lp, c->sc_stop, c->cut_base, c->cut_ntok, c->cut_ok, c->d.max_target_positions, c->cut_force,
+                                     cut_rows, c->cut_out, c->cut_score, c->st));
+        return CW_OK;
+    }
     CWCHK(c, KD(c, cw_launch_score_head, c->sc_a, c->embed_pk, c->sc_tgt, c->sc_part, M, V, D, c->sc_lp, c->sc_ti, c->sc_tl, c->st));
     return CW_OK;
 }
 
 static int score_head_fetch(cw_ctx* c, int rows, int M, int ids_stride, const int32_t* n_ids, int n_init, float* token_logprob,
-                            int32_t* top_id, float* top_logprob) {
-    std::vector<float> lp(M), tl(M);
+                            int32_t* top_id, float* top_logprob, const CutArgs* ca = nullptr) {
+    std::vector<float> lp(M), tl(M), sl(ca ? M : 0);
     std::vector<int> ti(M);
     HIPCHK(c, hipStreamSynchronize(c->st));
     HIPCHK(c, hipMemcpy(lp.data(), c->sc_lp, (size_t)M * 4, hipMemcpyDeviceToHost));
     HIPCHK(c, hipMemcpy(ti.data(), c->sc_ti, (size_t)M * 4, hipMemcpyDeviceToHost));
     HIPCHK(c, hipMemcpy(tl.data(), c->sc_tl, (size_t)M * 4, hipMemcpyDeviceToHost));
+    if (ca) {
+        HIPCHK(c, hipMemcpy(sl.data(), c->sc_stop, (size_t)M * 4, hipMemcpyDeviceToHost));
+        HIPCHK(c, hipMemcpy(ca->cut, c->cut_out, (size_t)rows * 4, hipMemcpyDeviceToHost));
+        HIPCHK(c, hipMemcpy(ca->cut_score, c->cut_score, (size_t)rows * 4, hipMemcpyDeviceToHost));
+    }
     int m = 0;
     for (int r = 0; r < rows; ++r)
         for (int k = n_init; k < n_ids[r]; ++k, ++m) {
             token_logprob[(size_t)r * ids_stride + k] = lp[m];
             if (top_id) top_id[(size_t)r * ids_stride + k] = ti[m];
             if (top_logprob) top_logprob[(size_t)r * ids_stride + k] = tl[m];
+            if (ca) ca->stop_logprob[(size_t)r * ids_stride + k] = sl[m];
         }
     return CW_OK;
 }
 
-// num_frames / token_ts null: scores only (any rows_per_item); else rows_per_item == 1 and the timestamps of cw_align_tokens too
+// num_frames / token_ts null: scores only (any rows_per_item); else rows_per_item == 1 and the timestamps of cw_align_tokens too.
+// ca non-null (cw_align_cut_tokens, with token_ts): the STOP head and the cut kernel behind the same forward, and the timestamp
+// stage over row b's first n_init + cut[b] + 1 ids -- the forward is causal, so those rows are what the prefix alone would give.
 static int score_rows(cw_ctx* c, const char* who, int n_items, int rpi, const int32_t* num_frames, const int32_t* ids, int ids_stride,
-                      const int32_t* n_ids, int n_init, float* token_ts, float* token_logprob, int32_t* top_id, float* top_logprob) {
+                      const int32_t* n_ids, int n_init, float* token_ts, float* token_logprob, int32_t* top_id, float* top_logprob,
+                      const CutArgs* ca = nullptr) {
     const int TGT = c->d.max_target_positions;
     const bool align = token_ts != nullptr;
     if (align && c->d.n_align <= 0) return fail(c, CW_ERR_STATE, "%s: no alignment heads configured", who);
@@ -3195,6 +3280,12 @@ static int score_rows(cw_ctx* c, const char* who, int n_items, int rpi, const in
     const int rows = n_items * rpi;
     int n_max = 0;
     CWCHK(c, check_token_rows(c, who, rows, num_frames, ids, ids_stride, n_ids, n_init, &n_max));
+    if (ca)
+        for (int b = 0; b < rows; ++b) {
+            bool any = ca->force_all[b] != 0;
+            for (int n = 0; !any && n <= n_ids[b] - n_init - 1; ++n) any = ca->cut_ok[(size_t)b * ids_stride + n] != 0;
+            if (!any) return fail(c, CW_ERR_INVALID, "%s: row %d is not forced and its cut_ok allows no cut", who, b);
+        }
     PrefixScope scope{c, c->pf_prefix};
     c->pf_prefix = 0;
     const int Lmax = n_max - 1;
@@ -3210,16 +3301,22 @@ static int score_rows(cw_ctx* c, const char* who, int n_items, int rpi, const in
         HIPCHK(c, hipMemcpyAsync(c->d_ids, dev.data(), dev.size() * 4, hipMemcpyHostToDevice, c->st));
         int M = 0;
         CWCHK(c, score_head_prepare(c, rows, Lmax, ids, ids_stride, n_ids, n_init, &M));     // (synchronises the stream)
+        if (ca) {
+            CWCHK(c, cut_reserve(c, (size_t)M, (size_t)M * KD(c, cw_score_head_splits, M, c->d.vocab_size, nullptr)));
+            std::vector<int> first(rows, 0);     // the head's arrays hold row after row, n_ids - n_init entries each
+            for (int r = 1; r < rows; ++r) first[r] = first[r - 1] + n_ids[r - 1] - n_init;
+            CWCHK(c, cut_upload(c, rows, ids_stride, n_ids, n_init, *ca, first));
+        }
         StageTimer tm(c, CW_STAGE_DECODE);
         CWCHK(c, run_prefill(c, rows, Lmax + 1, rpi, align, true));
-        CWCHK(c, score_head_launch(c, M));
+        CWCHK(c, score_head_launch(c, M, ca ? rows : 0));
         KCHK(c);
         tm.stop();
         ++c->score_prefill_runs;
         c->last_L = align ? Lmax : 0;            // without align no alignment rows were recorded: nothing is retained
         c->last_nb = align ? rows : 0;
         c->align_unnormalized = align;
-        CWCHK(c, score_head_fetch(c, rows, M, ids_stride, n_ids, n_init, token_logprob, top_id, top_logprob));
+        CWCHK(c, score_head_fetch(c, rows, M, ids_stride, n_ids, n_init, token_logprob, top_id, top_logprob, ca));
     } else {
         // the per-position decoder step with every token forced; the item is encoded into each of its rows, and the raw logits
         // of every step are reduced on the device (score_rows_kernel) before the next step overwrites them
@@ -3230,18 +3327,36 @@ static int score_rows(cw_ctx* c, const char* who, int n_items, int rpi, const in
             const size_t n = (size_t)c->Bm * TGT * 4;
             CWCHK(c, dmalloc(c, &c->sc_step_lp, n)); CWCHK(c, dmalloc(c, &c->sc_step_tl, n)); CWCHK(c, dmalloc(c, &c->sc_step_ti, n));
         }
+        if (ca) {
+            if (!c->sc_step_stop) CWCHK(c, dmalloc(c, &c->sc_step_stop, (size_t)c->Bm * TGT * 4));
+            CWCHK(c, cut_reserve(c, 0, 0));
+            std::vector<int> first(rows);        // the loop's arrays are [rows][TGT], indexed by position
+            for (int r = 0; r < rows; ++r) first[r] = r * TGT + n_init;
+            CWCHK(c, cut_upload(c, rows, ids_stride, n_ids, n_init, *ca, first));
+        }
         std::vector<int> prompt((size_t)rows * n_init), forced((size_t)rows * TGT, -1), seq((size_t)rows * TGT), lens(rows);
         for (int b = 0; b < rows; ++b) {
             memcpy(prompt.data() + (size_t)b * n_init, ids + (size_t)b * ids_stride, (size_t)n_init * 4);
             for (int k = n_init; k < n_ids[b]; ++k) forced[(size_t)b * TGT + k] = ids[(size_t)b * ids_stride + k];
         }
-        struct HookScope { cw_ctx* c; ~HookScope() { c->score_hook = false; } } hook{c};
+        struct HookScope { cw_ctx* c; ~HookScope() { c->score_hook = false; c->score_stop = false; } } hook{c};
         c->score_hook = true;
+        c->score_stop = ca != nullptr;
         CWCHK(c, cw_decode(c, rows, prompt.data(), n_init, n_max, 0, forced.data(), seq.data(), lens.data(), nullptr));
         c->score_hook = false;
+        c->score_stop = false;
         if (c->last_L < Lmax) return fail(c, CW_ERR_STATE, "%s: the forced decode stopped at %d of %d positions", who, c->last_L, Lmax);
-        std::vector<float> lp((size_t)rows * TGT), tl((size_t)rows * TGT);
+        std::vector<float> lp((size_t)rows * TGT), tl((size_t)rows * TGT), sl(ca ? (size_t)rows * TGT : 0);
         std::vector<int> ti((size_t)rows * TGT);
+        if (ca) {                                // the cut over the loop's [rows][TGT] arrays; the copies below wait for it
+            CWCHK(c, cw_launch_align_cut(c->sc_step_lp, c->sc_step_stop, c->cut_base, c->cut_ntok, c->cut_ok, TGT, c->cut_force, rows,
+                                         c->cut_out, c->cut_score, c->st));
+            KCHK(c);
+            HIPCHK(c, hipStreamSynchronize(c->st));
+            HIPCHK(c, hipMemcpy(sl.data(), c->sc_step_stop, sl.size() * 4, hipMemcpyDeviceToHost));
+            HIPCHK(c, hipMemcpy(ca->cut, c->cut_out, (size_t)rows * 4, hipMemcpyDeviceToHost));
+            HIPCHK(c, hipMemcpy(ca->cut_score, c->cut_score, (size_t)rows * 4, hipMemcpyDeviceToHost));
+        }
         HIPCHK(c, hipMemcpy(lp.data(), c->sc_step_lp, lp.size() * 4, hipMemcpyDeviceToHost));
         HIPCHK(c, hipMemcpy(ti.data(), c->sc_step_ti, ti.size() * 4, hipMemcpyDeviceToHost));
         HIPCHK(c, hipMemcpy(tl.data(), c->sc_step_tl, tl.size() * 4, hipMemcpyDeviceToHost));
@@ -3250,7 +3365,16 @@ static int score_rows(cw_ctx* c, const char* who, int n_items, int rpi, const in
                 token_logprob[(size_t)r * ids_stride + k] = lp[(size_t)r * TGT + k];
                 if (top_id) top_id[(size_t)r * ids_stride + k] = ti[(size_t)r * TGT + k];
                 if (top_logprob) top_logprob[(size_t)r * ids_stride + k] = tl[(size_t)r * TGT + k];
+                if (ca) ca->stop_logprob[(size_t)r * ids_stride + k] = sl[(size_t)r * TGT + k];
             }
+    }
+    if (ca) {
+        std::vector<int32_t> kept(rows);         // init tokens + the kept text + the slot cw_align_tokens gives the eos
+        for (int b = 0; b < rows; ++b) {
+            if (ca->cut[b] < 0 || ca->cut[b] > n_ids[b] - n_init - 1) return fail(c, CW_ERR_STATE, "%s: row %d came back with cut %d", who, b, ca->cut[b]);
+            kept[b] = n_init + ca->cut[b] + 1;
+        }
+        return forced_rows_timestamps(c, rows, num_frames, ids_stride, kept.data(), n_init, token_ts);
     }
     if (align) return forced_rows_timestamps(c, rows, num_frames, ids_stride, n_ids, n_init, token_ts);
     return CW_OK;
@@ -3268,6 +3392,17 @@ int32_t cw_align_score_tokens(cw_ctx* c, int32_t nb, const int32_t* num_frames, 
     if (!token_ts) return fail(c, CW_ERR_INVALID, "align_score_tokens: null argument");
     return score_rows(c, "align_score_tokens", nb, 1, num_frames, ids, ids_stride, n_ids, n_init, token_ts, token_logprob, top_id,
                       top_logprob);
+}
+
+int32_t cw_align_cut_tokens(cw_ctx* c, int32_t nb, const int32_t* num_frames, const int32_t* ids, int32_t ids_stride,
+                            const int32_t* n_ids, int32_t n_init, const uint8_t* cut_ok, const uint8_t* force_all, int32_t* cut,
+                            float* cut_score, float* token_ts, float* token_logprob, float* stop_logprob, int32_t* top_id,
+                            float* top_logprob) {
+    if (!cut_ok || !force_all || !cut || !cut_score || !token_ts || !token_logprob || !stop_logprob)
+        return fail(c, CW_ERR_INVALID, "align_cut_tokens: null argument");
+    const CutArgs ca{cut_ok, force_all, cut, cut_score, stop_logprob};
+    return score_rows(c, "align_cut_tokens", nb, 1, num_frames, ids, ids_stride, n_ids, n_init, token_ts, token_logprob, top_id,
+                      top_logprob, &ca);
 }
 
 int32_t cw_align_matrix(cw_ctx* c, const float* attn, int32_t B, int32_t Ha, int32_t N, int32_t M, const int32_t* n_cols,
@@ -3644,8 +3779,10 @@ int32_t cw_test_prefill_gemm(cw_ctx* c, int32_t mode, int32_t M, int32_t N, int3
 // cw_test_score_head: the scoring head (score.hip) on its own.  x [M][D] f32 residual rows, ln_g / ln_b [D], embed [V][D] (rounded
 // to the engine's 16-bit type and packed fragment-major), targets [M] -> logprob / top_id / top_logprob [M].  16-bit engines;
 // D % 32 == 0.  Sizes are validated on the host before anything is allocated or launched.
-int32_t cw_test_score_head(cw_ctx* c, int32_t M, int32_t D, int32_t V, const float* x, const float* ln_g, const float* ln_b,
-                           const float* embed, const int32_t* targets, float* logprob, int32_t* top_id, float* top_logprob) {
+// stop_logprob non-null (cw_test_score_head_stop): the STOP form over S = {eos} + {n >= timestamp_begin} instead.
+static int test_score_head(cw_ctx* c, int32_t M, int32_t D, int32_t V, const float* x, const float* ln_g, const float* ln_b,
+                           const float* embed, const int32_t* targets, float* logprob, int32_t* top_id, float* top_logprob,
+                           int eos, int timestamp_begin, float* stop_logprob) {
     if (!c->bf16) return fail(c, CW_ERR_INVALID, "test_score_head: 16-bit engines only");
     if (M < 1 || M > (1 << 16) || D < 32 || D % 32 || D > 8192 || V < 1 || V > (1 << 20) || !x || !ln_g || !ln_b || !embed || !targets ||
         !logprob || !top_id || !top_logprob) return fail(c, CW_ERR_INVALID, "test_score_head: bad arguments");
@@ -3657,7 +3794,11 @@ int32_t cw_test_score_head(cw_ctx* c, int32_t M, int32_t D, int32_t V, const flo
     int *dt = nullptr, *dti = nullptr;
     void *dA = nullptr, *dW = nullptr, *dWp = nullptr;
     ScorePart* dP = nullptr;
+    ScoreStopPart* dS = nullptr;
+    float* dsl = nullptr;
     int r = CW_OK;
+    if (stop_logprob && (hipMalloc((void**)&dS, (size_t)M * ns * sizeof(ScoreStopPart)) != hipSuccess ||
+                         hipMalloc((void**)&dsl, (size_t)M * 4) != hipSuccess)) r = fail(c, CW_ERR_NOMEM, "test_score_head: hipMalloc failed");
     if (hipMalloc((void**)&dx, (size_t)M * D * 4) != hipSuccess || hipMalloc((void**)&dg, (size_t)D * 4) != hipSuccess ||
         hipMalloc((void**)&db, (size_t)D * 4) != hipSuccess || hipMalloc((void**)&dlp, (size_t)M * 4) != hipSuccess ||
         hipMalloc((void**)&dtl, (size_t)M * 4) != hipSuccess || hipMalloc((void**)&dt, (size_t)M * 4) != hipSuccess ||
@@ -3671,13 +3812,66 @@ int32_t cw_test_score_head(cw_ctx* c, int32_t M, int32_t D, int32_t V, const flo
     if (r == CW_OK) r = upload_T(c, dW, 0, embed, (size_t)V * D);
     if (r == CW_OK) r = KD(c, cw_launch_wfrag_pack, dW, V, D, dWp, c->st);
     if (r == CW_OK) r = KD(c, cw_launch_score_ln, dx, nullptr, dg, db, dA, M, D, c->st);
-    if (r == CW_OK) r = KD(c, cw_launch_score_head, dA, dWp, dt, dP, M, V, D, dlp, dti, dtl, c->st);
+    if (r == CW_OK) r = stop_logprob ? KD(c, cw_launch_score_head_stop, dA, dWp, dt, dP, dS, M, V, D, eos, timestamp_begin, dlp, dti, dtl, dsl, c->st)
+                                     : KD(c, cw_launch_score_head, dA, dWp, dt, dP, M, V, D, dlp, dti, dtl, c->st);
     if (r == CW_OK) { hipError_t er = hipStreamSynchronize(c->st); if (er != hipSuccess) r = fail(c, CW_ERR_HIP, "test_score_head: %s", hipGetErrorString(er)); }
+    if (r == CW_OK && stop_logprob && hipMemcpy(stop_logprob, dsl, (size_t)M * 4, hipMemcpyDeviceToHost) != hipSuccess) r = fail(c, CW_ERR_HIP, "test_score_head: copy");
     if (r == CW_OK && (hipMemcpy(logprob, dlp, (size_t)M * 4, hipMemcpyDeviceToHost) != hipSuccess ||
                        hipMemcpy(top_id, dti, (size_t)M * 4, hipMemcpyDeviceToHost) != hipSuccess ||
                        hipMemcpy(top_logprob, dtl, (size_t)M * 4, hipMemcpyDeviceToHost) != hipSuccess)) r = fail(c, CW_ERR_HIP, "test_score_head: copy");
     hipFree(dx); hipFree(dg); hipFree(db); hipFree(dlp); hipFree(dtl); hipFree(dt); hipFree(dti); hipFree(dA); hipFree(dW); hipFree(dWp); hipFree(dP);
+    if (dS) hipFree(dS);
+    if (dsl) hipFree(dsl);
     return r;
+}
+
+int32_t cw_test_score_head(cw_ctx* c, int32_t M, int32_t D, int32_t V, const float* x, const float* ln_g, const float* ln_b,
+                           const float* embed, const int32_t* targets, float* logprob, int32_t* top_id, float* top_logprob) {
+    return test_score_head(c, M, D, V, x, ln_g, ln_b, embed, targets, logprob, top_id, top_logprob, 0, 0, nullptr);
+}
+
+int32_t cw_test_score_head_stop(cw_ctx* c, int32_t M, int32_t D, int32_t V, const float* x, const float* ln_g, const float* ln_b,
+                                const float* embed, const int32_t* targets, int32_t eos, int32_t timestamp_begin, float* logprob,
+                                int32_t* top_id, float* top_logprob, float* stop_logprob) {
+    if (!stop_logprob || eos < 0 || eos >= V || timestamp_begin < 0 || timestamp_begin > V)
+        return fail(c, CW_ERR_INVALID, "test_score_head_stop: eos=%d inside 0 .. %d, timestamp_begin=%d inside 0 .. %d and stop_logprob are needed",
+                    eos, V - 1, timestamp_begin, V);
+    return test_score_head(c, M, D, V, x, ln_g, ln_b, embed, targets, logprob, top_id, top_logprob, eos, timestamp_begin, stop_logprob);
+}
+
+// cw_test_align_cut: the cut kernel of cw_align_cut_tokens, through its launcher, on caller-supplied scores.  Row r holds n_tok[r]
+// text tokens: logprob / stop_logprob / cut_ok [rows][stride] with entries 0 .. n_tok[r] used (stride > the largest n_tok).
+// A row that is neither forced nor allowed any cut is refused before the launch, as the call refuses it.
+int32_t cw_test_align_cut(cw_ctx* c, int32_t rows, int32_t stride, const int32_t* n_tok, const float* logprob, const float* stop_logprob,
+                          const uint8_t* cut_ok, const uint8_t* force_all, int32_t* cut, float* cut_score) {
+    if (rows < 1 || rows > (1 << 16) || stride < 1 || stride > (1 << 12) || !n_tok || !logprob || !stop_logprob || !cut_ok || !force_all ||
+        !cut || !cut_score) return fail(c, CW_ERR_INVALID, "test_align_cut: bad arguments");
+    std::vector<int> base(rows);
+    for (int r = 0; r < rows; ++r) {
+        if (n_tok[r] < 0 || n_tok[r] >= stride) return fail(c, CW_ERR_INVALID, "test_align_cut: n_tok[%d]=%d outside 0 .. %d", r, n_tok[r], stride - 1);
+        bool any = force_all[r] != 0;
+        for (int n = 0; !any && n <= n_tok[r]; ++n) any = cut_ok[(size_t)r * stride + n] != 0;
+        if (!any) return fail(c, CW_ERR_INVALID, "test_align_cut: row %d is not forced and its cut_ok allows no cut", r);
+        base[r] = r * stride;
+    }
+    const size_t n = (size_t)rows * stride;
+    DevBuf dlp, dsl, dok, dfo, dba, dnt, dcu, dsc;
+    if (dlp.alloc(n * 4) != hipSuccess || dsl.alloc(n * 4) != hipSuccess || dok.alloc(n) != hipSuccess || dfo.alloc(rows) != hipSuccess ||
+        dba.alloc((size_t)rows * 4) != hipSuccess || dnt.alloc((size_t)rows * 4) != hipSuccess || dcu.alloc((size_t)rows * 4) != hipSuccess ||
+        dsc.alloc((size_t)rows * 4) != hipSuccess) return fail(c, CW_ERR_NOMEM, "test_align_cut: hipMalloc failed");
+    HIPCHK(c, hipMemcpy(dlp.p, logprob, n * 4, hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemcpy(dsl.p, stop_logprob, n * 4, hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemcpy(dok.p, cut_ok, n, hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemcpy(dfo.p, force_all, rows, hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemcpy(dba.p, base.data(), (size_t)rows * 4, hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemcpy(dnt.p, n_tok, (size_t)rows * 4, hipMemcpyHostToDevice));
+    CWCHK(c, cw_launch_align_cut((const float*)dlp.p, (const float*)dsl.p, (const int*)dba.p, (const int*)dnt.p, (const unsigned char*)dok.p,
+                                 stride, (const unsigned char*)dfo.p, rows, (int*)dcu.p, (float*)dsc.p, c->st));
+    KCHK(c);
+    HIPCHK(c, hipStreamSynchronize(c->st));
+    HIPCHK(c, hipMemcpy(cut, dcu.p, (size_t)rows * 4, hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(cut_score, dsc.p, (size_t)rows * 4, hipMemcpyDeviceToHost));
+    return CW_OK;
 }
 
 // cw_time_score_head: the scoring head at the context's own geometry (d_model, vocabulary, its packed tied embedding) over M
@@ -3698,7 +3892,14 @@ int32_t cw_time_score_head(cw_ctx* c, int32_t M, int32_t unfused, int32_t iters,
     int *dt = nullptr, *dti = nullptr;
     void* dA = nullptr;
     ScorePart* dP = nullptr;
+    ScoreStopPart* dS = nullptr;
+    float* dsl = nullptr;
+    const bool stop = unfused == 2;              // the STOP form of the fused head, over this context's eos and timestamp ids
+    if (stop) unfused = 0;
+    if (stop && !c->gen_set) return fail(c, CW_ERR_STATE, "cw_set_generation not called");
     int r = CW_OK;
+    if (stop && (hipMalloc((void**)&dS, (size_t)M * ns * sizeof(ScoreStopPart)) != hipSuccess || hipMalloc((void**)&dsl, (size_t)M * 4) != hipSuccess))
+        r = fail(c, CW_ERR_NOMEM, "time_score_head: hipMalloc failed");
     if (hipMalloc((void**)&dx, x.size() * 4) != hipSuccess || hipMalloc((void**)&dlp, (size_t)M * 4) != hipSuccess ||
         hipMalloc((void**)&dtl, (size_t)M * 4) != hipSuccess || hipMalloc((void**)&dt, (size_t)M * 4) != hipSuccess ||
         hipMalloc((void**)&dti, (size_t)M * 4) != hipSuccess || hipMalloc(&dA, (size_t)M * D * 2) != hipSuccess ||
@@ -3709,6 +3910,9 @@ int32_t cw_time_score_head(cw_ctx* c, int32_t M, int32_t unfused, int32_t iters,
     for (int it = 0; it <= iters && r == CW_OK; ++it) {
         if (it == 1 && hipEventRecord(c->ev0, c->st) != hipSuccess) r = fail(c, CW_ERR_HIP, "time_score_head: event");
         if (r == CW_OK) r = KD(c, cw_launch_score_ln, dx, nullptr, c->dec_ln_g, c->dec_ln_b, dA, M, D, c->st);
+        if (r == CW_OK && stop) r = KD(c, cw_launch_score_head_stop, dA, c->embed_pk, dt, dP, dS, M, V, D, c->gen.eos_token_id,
+                                       c->gen.no_timestamps_token_id + 1, dlp, dti, dtl, dsl, c->st);
+        else
         if (r == CW_OK) r = unfused ? KD(c, cw_launch_score_head_unfused, dA, c->embed_pk, dt, dlog, c->Vpad, M, V, D, dlp, dti, dtl, c->st)
                                     : KD(c, cw_launch_score_head, dA, c->embed_pk, dt, dP, M, V, D, dlp, dti, dtl, c->st);
     }
@@ -3720,6 +3924,8 @@ int32_t cw_time_score_head(cw_ctx* c, int32_t M, int32_t unfused, int32_t iters,
     }
     hipStreamSynchronize(c->st);
     hipFree(dx); hipFree(dlp); hipFree(dtl); hipFree(dt); hipFree(dti); hipFree(dA); hipFree(dP); if (dlog) hipFree(dlog);
+    if (dS) hipFree(dS);
+    if (dsl) hipFree(dsl);
     return r;
 }
 

@@ -378,6 +378,10 @@ struct ScorePart {
     float tl;              // the target's logit if its column is the split's, else -inf
     float bv; int bi;      // best (logit, id), lowest id on an exact tie
 };
+// ... and, for the STOP form, of the split's columns in S = {eos} + {n >= timestamp_begin}: their own maximum and sum
+struct ScoreStopPart {
+    float mx, sum;
+};
 
 #define CW_DTYPE_KERNEL_DECLS \
     int cw_launch_gemm(bool bf16, int epi, const AParams& ap, const void* W, int M, int N, int K, const EpiParams& ep, hipStream_t st); \
@@ -440,6 +444,8 @@ struct ScorePart {
     int cw_launch_score_head(const void* A, const void* W, const int* target, ScorePart* part, int M, int V, int K, float* logprob, int* top_id, float* top_logprob, hipStream_t st); \
     int cw_launch_score_head_unfused(const void* A, const void* W, const int* target, float* logits, int ldv, int M, int V, int K, float* logprob, int* top_id, float* top_logprob, hipStream_t st); \
     int cw_launch_score_rows(const float* logits, int ldv, int V, const int* target, int t_stride, int t, int rows, float* logprob, int* top_id, float* top_logprob, hipStream_t st); \
+    int cw_launch_score_head_stop(const void* A, const void* W, const int* target, ScorePart* part, ScoreStopPart* spart, int M, int V, int K, int eos, int ts_begin, float* logprob, int* top_id, float* top_logprob, float* stop_logprob, hipStream_t st); \
+    int cw_launch_score_rows_stop(const float* logits, int ldv, int V, const int* target, int t_stride, int t, int rows, int eos, int ts_begin, float* logprob, int* top_id, float* top_logprob, float* stop_logprob, hipStream_t st); \
     int cw_launch_attn_encoder(bool bf16, const void* Q, const void* K, const void* V, void* out, int B, int H, int S, int S_pad, hipStream_t st); \
     int cw_launch_attn_decode(bool bf16, const DecAttnParams& p, hipStream_t st); \
     int cw_launch_attn_cross_split(bool bf16, const CrossSplitParams& p, hipStream_t st); \
@@ -475,6 +481,11 @@ int cw_launch_align_similarity(const float* w, int B, int Ha, int rows_cap, int 
 // alignment scores of the rows the DTW just walked (align.hip: align_path_score_kernel): mass / spread [B][N]
 int cw_launch_align_path_score(const float* w, int B, int Ha, int rows_cap, int S, int row0, int N, const int* n_cols,
                                const int* first_col, int collar, float* mass, float* spread, hipStream_t st);
+// the cut of cw_align_cut_tokens (align.hip: align_cut_kernel): row r's scores start at logprob / stop_logprob[base[r]] and hold
+// n_tok[r] + 1 entries; cut_ok [rows][ok_stride] bytes, force [rows] bytes -> cut [rows], cut_score [rows]
+int cw_launch_align_cut(const float* logprob, const float* stop_logprob, const int* base, const int* n_tok,
+                        const unsigned char* cut_ok, int ok_stride, const unsigned char* force, int rows, int* cut,
+                        float* cut_score, hipStream_t st);
 // skew: workspace of cw_dtw_skew_floats(B, N, S) floats (null: round-1 block kernel)
 size_t cw_dtw_skew_floats(int B, int N, int S);
 int cw_launch_dtw(const float* mat, int B, int N, int S, const int* n_cols, unsigned char* trace, int* first_col,

@@ -10,6 +10,10 @@
 //                          the best (logit, id) -- lowest id on an exact tie, as sample_kernel.  Columns >= V take no part.
 //   score_combine_kernel   merges the [M][n_split] partials: logprob = logit[target] - logsumexp, top_id, top_logprob
 //   score_rows_kernel      the same three numbers from a row of f32 logits the decode step left (the per-position fallback)
+// STOP forms (cw_align_cut_tokens): besides the above, stop_logprob = logsumexp(logit[n], n in S) - logsumexp(all logits) with
+// S = {eos} + {n >= timestamp_begin}: the log-probability that the text stops before this position.  S keeps its own running
+// (maximum, sum of exp) pair, never rescaled against the row's maximum: a stop set 100 nats under the row maximum would
+// underflow to log(0) there.  The pair travels in its own record array (ScoreStopPart); the plain forms write what they wrote.
 #include <hip/hip_runtime.h>
 #include "kernels.h"
 
@@ -43,11 +47,12 @@ __device__ static inline bool score_better(float v, int i, float bv, int bi) { r
 // its own columns, and the 16 lanes of a row are merged once at the end.
 // STORE (the unfused form, kept for the A/B of cw_time_score_head only): the same tile loop writes the f32 logits [M][ldv]
 // instead of keeping statistics; score_rows_kernel then makes one pass per row.
-template <bool STORE>
+template <bool STORE, bool STOP>
 __global__ __launch_bounds__(256) void score_head_kernel(const bf16_t* __restrict__ A, const bf16_t* __restrict__ W,
                                                          const int* __restrict__ target, ScorePart* __restrict__ part,
                                                          int M, int V, int K, int tiles_per_split, int n_split,
-                                                         float* __restrict__ logits, int ldv) {
+                                                         float* __restrict__ logits, int ldv,
+                                                         ScoreStopPart* __restrict__ spart, int eos, int ts_begin) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int l15 = lane & 15, g = lane >> 4;
     const int m0 = blockIdx.x * 128 + wave * 32;
@@ -59,15 +64,19 @@ __global__ __launch_bounds__(256) void score_head_kernel(const bf16_t* __restric
     const bf16x8_t zero = bf16x8_t{0, 0, 0, 0, 0, 0, 0, 0};
     float mx[8], sum[8], tl[8], bv[8];
     int bi[8], tg[8];
+    float smx[8], ssum[8];                                            // STOP only: the lane's columns that lie in S
 #pragma unroll
     for (int q = 0; q < 8; ++q) {
         const int m = m0 + (q >> 2) * 16 + g * 4 + (q & 3);
         mx[q] = -INFINITY; sum[q] = 0.f; tl[q] = -INFINITY; bv[q] = -INFINITY; bi[q] = 0x7fffffff;
         tg[q] = m < M ? target[m] : -1;
+        if (STOP) { smx[q] = -INFINITY; ssum[q] = 0.f; }
     }
     const bf16_t* a0 = A + (size_t)(m0 + l15) * K + g * 8;
     const bf16_t* a1 = a0 + (size_t)16 * K;
     for (int t0 = t_begin; t0 < t_end; t0 += 4) {
+        // STOP: does any of the four tiles' columns lie in S (the same answer in every lane: most tile groups skip the pair)
+        const bool stop_here = STOP && ((eos >= t0 * 16 && eos < (t0 + 4) * 16) || (t0 + 4) * 16 > ts_begin);
         f32x4_t acc[2][4];
 #pragma unroll
         for (int i = 0; i < 2; ++i)
@@ -124,6 +133,23 @@ __global__ __launch_bounds__(256) void score_head_kernel(const bf16_t* __restric
                 sum[q] = (mx[q] > -INFINITY ? sum[q] * expf(mx[q] - mnew) : 0.f) + add;
                 mx[q] = mnew;
             }
+            if (STOP && stop_here) {
+                float sv[4];
+                float snew = smx[q];
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    const int n = (t0 + j) * 16 + l15;
+                    sv[j] = (n == eos || n >= ts_begin) ? v[j] : -INFINITY;   // v is -inf already for columns >= V
+                    snew = fmaxf(snew, sv[j]);
+                }
+                if (snew > -INFINITY) {
+                    float add = 0.f;
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) add += sv[j] > -INFINITY ? expf(sv[j] - snew) : 0.f;
+                    ssum[q] = (smx[q] > -INFINITY ? ssum[q] * expf(smx[q] - snew) : 0.f) + add;
+                    smx[q] = snew;
+                }
+            }
         }
     }
     if (STORE) return;
@@ -141,20 +167,36 @@ __global__ __launch_bounds__(256) void score_head_kernel(const bf16_t* __restric
             mx[q] = mnew;
             tl[q] = fmaxf(tl[q], otl);                                        // at most one lane holds the target's column
             if (score_better(obv, obi, bv[q], bi[q])) { bv[q] = obv; bi[q] = obi; }
+            if (STOP) {
+                const float osmx = __shfl_xor(smx[q], off, 64), ossum = __shfl_xor(ssum[q], off, 64);
+                const float snew = fmaxf(smx[q], osmx);
+                if (snew > -INFINITY)
+                    ssum[q] = (smx[q] > -INFINITY ? ssum[q] * expf(smx[q] - snew) : 0.f) +
+                              (osmx > -INFINITY ? ossum * expf(osmx - snew) : 0.f);
+                smx[q] = snew;
+            }
         }
         const int m = m0 + (q >> 2) * 16 + g * 4 + (q & 3);
         if (l15 == 0 && m < M) {
             ScorePart p;
             p.mx = mx[q]; p.sum = sum[q]; p.tl = tl[q]; p.bv = bv[q]; p.bi = bi[q];
             part[(size_t)m * n_split + split] = p;
+            if (STOP) {
+                ScoreStopPart sp;
+                sp.mx = smx[q]; sp.sum = ssum[q];
+                spart[(size_t)m * n_split + split] = sp;
+            }
         }
     }
 }
 
-// one thread per row
+// one thread per row; STOP: stop_logprob[m] = logsumexp over S - logsumexp, -inf where no column of S exists
+template <bool STOP>
 __global__ __launch_bounds__(256) void score_combine_kernel(const ScorePart* __restrict__ part, int M, int n_split,
                                                             float* __restrict__ logprob, int* __restrict__ top_id,
-                                                            float* __restrict__ top_logprob) {
+                                                            float* __restrict__ top_logprob,
+                                                            const ScoreStopPart* __restrict__ spart,
+                                                            float* __restrict__ stop_logprob) {
     const int m = blockIdx.x * 256 + threadIdx.x;
     if (m >= M) return;
     const ScorePart* p = part + (size_t)m * n_split;
@@ -172,15 +214,26 @@ __global__ __launch_bounds__(256) void score_combine_kernel(const ScorePart* __r
     logprob[m] = tl - lse;
     top_id[m] = bi;
     top_logprob[m] = bv - lse;
+    if (STOP) {
+        const ScoreStopPart* sp = spart + (size_t)m * n_split;
+        float smx = -INFINITY;
+        for (int s = 0; s < n_split; ++s) smx = fmaxf(smx, sp[s].mx);
+        float ssum = 0.f;
+        for (int s = 0; s < n_split; ++s)
+            if (sp[s].mx > -INFINITY) ssum += sp[s].sum * expf(sp[s].mx - smx);
+        stop_logprob[m] = smx > -INFINITY ? (smx + logf(ssum)) - lse : -INFINITY;
+    }
 }
 
 // one block per row of f32 logits [rows][ldv]; target[row * t_stride + t] (negative: no target, the row's logprob is -inf);
-// results at out[row * t_stride + t]
+// results at out[row * t_stride + t].  STOP: stop_logprob likewise, from a second (maximum, sum) pass over the columns of S
+template <bool STOP>
 __global__ __launch_bounds__(256) void score_rows_kernel(const float* __restrict__ logits, int ldv, int V,
                                                          const int* __restrict__ target, int t_stride, int t,
                                                          float* __restrict__ logprob, int* __restrict__ top_id,
-                                                         float* __restrict__ top_logprob) {
-    __shared__ float s_v[4], s_s[4];
+                                                         float* __restrict__ top_logprob, int eos, int ts_begin,
+                                                         float* __restrict__ stop_logprob) {
+    __shared__ float s_v[4], s_s[4], s_sv[4], s_ss[4];
     __shared__ int s_i[4];
     const int row = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const float* lg = logits + (size_t)row * ldv;
@@ -202,7 +255,24 @@ __global__ __launch_bounds__(256) void score_rows_kernel(const float* __restrict
     for (int n = tid; n < V; n += 256) sum += expf(lg[n] - bv);
     for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o, 64);
     if (lane == 0) s_s[wave] = sum;
+    float smx = -INFINITY;
+    if (STOP) {
+        for (int n = tid; n < V; n += 256)
+            if (n == eos || n >= ts_begin) smx = fmaxf(smx, lg[n]);
+        for (int o = 32; o > 0; o >>= 1) smx = fmaxf(smx, __shfl_xor(smx, o, 64));
+        if (lane == 0) s_sv[wave] = smx;
+    }
     __syncthreads();
+    if (STOP) {
+        smx = fmaxf(fmaxf(s_sv[0], s_sv[1]), fmaxf(s_sv[2], s_sv[3]));
+        float ssum = 0.f;
+        if (smx > -INFINITY)
+            for (int n = tid; n < V; n += 256)
+                if (n == eos || n >= ts_begin) ssum += expf(lg[n] - smx);
+        for (int o = 32; o > 0; o >>= 1) ssum += __shfl_xor(ssum, o, 64);
+        if (lane == 0) s_ss[wave] = ssum;
+        __syncthreads();
+    }
     if (tid == 0) {
         const float lse = bv + logf((s_s[0] + s_s[1]) + (s_s[2] + s_s[3]));
         const size_t o = (size_t)row * t_stride + t;
@@ -210,6 +280,8 @@ __global__ __launch_bounds__(256) void score_rows_kernel(const float* __restrict
         logprob[o] = (tg >= 0 && tg < V) ? lg[tg] - lse : -INFINITY;
         top_id[o] = bi;
         top_logprob[o] = bv - lse;
+        if (STOP)
+            stop_logprob[o] = smx > -INFINITY ? (smx + logf((s_ss[0] + s_ss[1]) + (s_ss[2] + s_ss[3]))) - lse : -INFINITY;
     }
 }
 
@@ -235,9 +307,24 @@ int cw_launch_score_head(const void* A, const void* W, const int* target, ScoreP
     if (M < 1 || V < 1 || K < 32 || K % 32) return CW_ERR_INVALID;
     int tps = 0;
     const int ns = cw_score_head_splits(M, V, &tps);
-    hipLaunchKernelGGL(score_head_kernel<false>, dim3((M + 127) / 128, ns), dim3(256), 0, st, (const bf16_t*)A, (const bf16_t*)W,
-                       target, part, M, V, K, tps, ns, (float*)nullptr, 0);
-    hipLaunchKernelGGL(score_combine_kernel, dim3((M + 255) / 256), dim3(256), 0, st, part, M, ns, logprob, top_id, top_logprob);
+    hipLaunchKernelGGL((score_head_kernel<false, false>), dim3((M + 127) / 128, ns), dim3(256), 0, st, (const bf16_t*)A,
+                       (const bf16_t*)W, target, part, M, V, K, tps, ns, (float*)nullptr, 0, (ScoreStopPart*)nullptr, 0, 0);
+    hipLaunchKernelGGL(score_combine_kernel<false>, dim3((M + 255) / 256), dim3(256), 0, st, part, M, ns, logprob, top_id,
+                       top_logprob, (const ScoreStopPart*)nullptr, (float*)nullptr);
+    return CW_OK;
+}
+
+// cw_launch_score_head plus stop_logprob [M] over S = {eos} + {n >= ts_begin}; spart: as many records as part
+int cw_launch_score_head_stop(const void* A, const void* W, const int* target, ScorePart* part, ScoreStopPart* spart, int M, int V,
+                              int K, int eos, int ts_begin, float* logprob, int* top_id, float* top_logprob, float* stop_logprob,
+                              hipStream_t st) {
+    if (M < 1 || V < 1 || K < 32 || K % 32 || eos < 0 || ts_begin < 0) return CW_ERR_INVALID;
+    int tps = 0;
+    const int ns = cw_score_head_splits(M, V, &tps);
+    hipLaunchKernelGGL((score_head_kernel<false, true>), dim3((M + 127) / 128, ns), dim3(256), 0, st, (const bf16_t*)A,
+                       (const bf16_t*)W, target, part, M, V, K, tps, ns, (float*)nullptr, 0, spart, eos, ts_begin);
+    hipLaunchKernelGGL(score_combine_kernel<true>, dim3((M + 255) / 256), dim3(256), 0, st, part, M, ns, logprob, top_id,
+                       top_logprob, (const ScoreStopPart*)spart, stop_logprob);
     return CW_OK;
 }
 
@@ -247,18 +334,26 @@ int cw_launch_score_head_unfused(const void* A, const void* W, const int* target
     if (M < 1 || V < 1 || ldv < V || K < 32 || K % 32) return CW_ERR_INVALID;
     int tps = 0;
     const int ns = cw_score_head_splits(M, V, &tps);
-    hipLaunchKernelGGL(score_head_kernel<true>, dim3((M + 127) / 128, ns), dim3(256), 0, st, (const bf16_t*)A, (const bf16_t*)W,
-                       target, (ScorePart*)nullptr, M, V, K, tps, ns, logits, ldv);
-    hipLaunchKernelGGL(score_rows_kernel, dim3(M), dim3(256), 0, st, (const float*)logits, ldv, V, target, 1, 0, logprob, top_id,
-                       top_logprob);
+    hipLaunchKernelGGL((score_head_kernel<true, false>), dim3((M + 127) / 128, ns), dim3(256), 0, st, (const bf16_t*)A,
+                       (const bf16_t*)W, target, (ScorePart*)nullptr, M, V, K, tps, ns, logits, ldv, (ScoreStopPart*)nullptr, 0, 0);
+    hipLaunchKernelGGL(score_rows_kernel<false>, dim3(M), dim3(256), 0, st, (const float*)logits, ldv, V, target, 1, 0, logprob,
+                       top_id, top_logprob, 0, 0, (float*)nullptr);
     return CW_OK;
 }
 
 int cw_launch_score_rows(const float* logits, int ldv, int V, const int* target, int t_stride, int t, int rows, float* logprob,
                          int* top_id, float* top_logprob, hipStream_t st) {
     if (rows < 1 || V < 1 || ldv < V || t < 0 || t >= t_stride) return CW_ERR_INVALID;
-    hipLaunchKernelGGL(score_rows_kernel, dim3(rows), dim3(256), 0, st, logits, ldv, V, target, t_stride, t, logprob, top_id,
-                       top_logprob);
+    hipLaunchKernelGGL(score_rows_kernel<false>, dim3(rows), dim3(256), 0, st, logits, ldv, V, target, t_stride, t, logprob,
+                       top_id, top_logprob, 0, 0, (float*)nullptr);
+    return CW_OK;
+}
+
+int cw_launch_score_rows_stop(const float* logits, int ldv, int V, const int* target, int t_stride, int t, int rows, int eos,
+                              int ts_begin, float* logprob, int* top_id, float* top_logprob, float* stop_logprob, hipStream_t st) {
+    if (rows < 1 || V < 1 || ldv < V || t < 0 || t >= t_stride || eos < 0 || ts_begin < 0) return CW_ERR_INVALID;
+    hipLaunchKernelGGL(score_rows_kernel<true>, dim3(rows), dim3(256), 0, st, logits, ldv, V, target, t_stride, t, logprob,
+                       top_id, top_logprob, eos, ts_begin, stop_logprob);
     return CW_OK;
 }
 

@@ -617,6 +617,87 @@ class Engine:
         return ([ts[b, :n[b]].copy() for b in range(nb)], [lp[b, k:n[b]].copy() for b in range(nb)],
                 [ti[b, k:n[b]].astype(np.int64) for b in range(nb)], [tl[b, k:n[b]].copy() for b in range(nb)])
 
+    def align_cut_tokens(self, num_frames, ids, n_init: int, cut_ok, force_all):
+        """cw_align_cut_tokens: how much of each offered transcript was spoken inside its window, and the alignment of that part,
+        in the one forward of ``align_score_tokens``.  ``ids`` as ``align_tokens`` takes them (row b offers N_b = len(ids[b]) -
+        n_init - 1 text tokens); ``cut_ok[b]``: N_b + 1 flags, entry n allowing "keep the first n tokens"; ``force_all[b]``: keep
+        all N_b whatever the flags say.  Returns (cut [nb] int64, cut_score [nb] float32, timestamps: per row n_init + cut[b] + 1
+        entries, what ``align_tokens`` gives for the kept prefix followed by eos, logprob / stop_logprob / top_id / top_logprob: per
+        row len(ids[b]) - n_init entries as ``score_tokens`` returns them).  stop_logprob[k] is the log-probability that the
+        text stops before position k (eos or any timestamp token); cut maximises sum(logprob[:n]) + stop_logprob[n] over the
+        allowed n, the lowest n on an exact tie."""
+        nb = len(ids)
+        n, stride, table = self._token_table(ids)
+        if len(cut_ok) != nb or len(force_all) != nb:
+            raise ValueError(f"cut_ok / force_all hold {len(cut_ok)} / {len(force_all)} rows for {nb} rows of ids")
+        k = int(n_init)
+        ok = np.zeros((nb, stride), dtype=np.uint8)
+        for b in range(nb):
+            m = np.asarray(cut_ok[b]).astype(bool)
+            if m.shape != (max(0, int(n[b]) - k),):
+                raise ValueError(f"cut_ok[{b}] holds {m.shape} flags for {int(n[b]) - k - 1} text tokens (one per count 0 .. N)")
+            ok[b, :len(m)] = m
+        force = np.ascontiguousarray(np.asarray(force_all).astype(bool), dtype=np.uint8)
+        nf = _i32(num_frames)
+        cut = np.zeros(nb, dtype=np.int32)
+        score = np.zeros(nb, dtype=np.float32)
+        ts = np.zeros((nb, stride), dtype=np.float32)
+        lp = np.zeros((nb, stride), dtype=np.float32)
+        sl = np.zeros((nb, stride), dtype=np.float32)
+        ti = np.zeros((nb, stride), dtype=np.int32)
+        tl = np.zeros((nb, stride), dtype=np.float32)
+        self._chk(self.lib.cw_align_cut_tokens(self.ctx, nb, _ptr(nf), _ptr(table), stride, _ptr(n), k, _ptr(ok), _ptr(force),
+                                               _ptr(cut), _ptr(score), _ptr(ts), _ptr(lp), _ptr(sl), _ptr(ti), _ptr(tl)))
+        return (cut.astype(np.int64), score, [ts[b, :k + cut[b] + 1].copy() for b in range(nb)],
+                [lp[b, k:n[b]].copy() for b in range(nb)], [sl[b, k:n[b]].copy() for b in range(nb)],
+                [ti[b, k:n[b]].astype(np.int64) for b in range(nb)], [tl[b, k:n[b]].copy() for b in range(nb)])
+
+    def test_score_head_stop(self, x, ln_g, ln_b, embed, targets, eos: int, timestamp_begin: int):
+        """cw_test_score_head_stop: ``test_score_head`` through the STOP form of the head -> (logprob, top_id, top_logprob,
+        stop_logprob) [M], stop_logprob over S = {eos} + {n >= timestamp_begin}."""
+        x = np.ascontiguousarray(x, np.float32)
+        embed = np.ascontiguousarray(embed, np.float32)
+        g = np.ascontiguousarray(ln_g, np.float32)
+        b = np.ascontiguousarray(ln_b, np.float32)
+        t = _i32(targets)
+        M, D = x.shape
+        V = embed.shape[0]
+        if embed.shape[1] != D or g.shape != (D,) or b.shape != (D,) or t.shape != (M,):
+            raise ValueError("test_score_head_stop: shapes do not agree")
+        lp = np.zeros(M, np.float32)
+        ti = np.zeros(M, np.int32)
+        tl = np.zeros(M, np.float32)
+        sl = np.zeros(M, np.float32)
+        self._chk(self.lib.cw_test_score_head_stop(self.ctx, M, D, V, _ptr(x), _ptr(g), _ptr(b), _ptr(embed), _ptr(t), int(eos),
+                                                   int(timestamp_begin), _ptr(lp), _ptr(ti), _ptr(tl), _ptr(sl)))
+        return lp, ti, tl, sl
+
+    def test_align_cut(self, logprob, stop_logprob, cut_ok, force_all):
+        """cw_test_align_cut: the cut kernel on caller-supplied scores.  Per row r ``logprob[r]`` / ``stop_logprob[r]`` /
+        ``cut_ok[r]`` hold N_r + 1 entries (N_r text tokens; the last logprob is the eos's); ``force_all`` [rows] ->
+        (cut [rows] int64, cut_score [rows] float32)."""
+        rows = len(logprob)
+        if not (len(stop_logprob) == len(cut_ok) == len(force_all) == rows):
+            raise ValueError("test_align_cut: row counts do not agree")
+        n_tok = _i32([len(r) - 1 for r in logprob])
+        stride = max(1, int(n_tok.max()) + 1 if rows else 1)
+        lp = np.zeros((rows, stride), np.float32)
+        sl = np.zeros((rows, stride), np.float32)
+        ok = np.zeros((rows, stride), np.uint8)
+        for r in range(rows):
+            m = int(n_tok[r]) + 1
+            if m < 1 or len(stop_logprob[r]) != m or len(cut_ok[r]) != m:
+                raise ValueError(f"test_align_cut: row {r} needs the same non-zero number of logprob / stop_logprob / cut_ok entries")
+            lp[r, :m] = logprob[r]
+            sl[r, :m] = stop_logprob[r]
+            ok[r, :m] = np.asarray(cut_ok[r]).astype(bool)
+        force = np.ascontiguousarray(np.asarray(force_all).astype(bool), dtype=np.uint8)
+        cut = np.zeros(rows, np.int32)
+        score = np.zeros(rows, np.float32)
+        self._chk(self.lib.cw_test_align_cut(self.ctx, rows, stride, _ptr(n_tok), _ptr(lp), _ptr(sl), _ptr(ok), _ptr(force),
+                                             _ptr(cut), _ptr(score)))
+        return cut.astype(np.int64), score
+
     def score_prefill_runs(self) -> int:
         """cw_score_prefill_runs: scoring calls of this engine whose forward ran as the batched prefill."""
         return int(self.lib.cw_score_prefill_runs(self.ctx))
@@ -643,11 +724,11 @@ class Engine:
                                               _ptr(ti), _ptr(tl)))
         return lp, ti, tl
 
-    def time_score_head(self, M: int, unfused: bool = False, iters: int = 10) -> float:
+    def time_score_head(self, M: int, unfused: bool = False, iters: int = 10, stop: bool = False) -> float:
         """cw_time_score_head: ms per run of the scoring head over M rows at this engine's geometry (fused, or the unfused form
-        that stores f32 logits and reduces them row by row)."""
+        that stores f32 logits and reduces them row by row; ``stop``: the fused STOP form of ``align_cut_tokens``)."""
         ms = C.c_float(0.0)
-        self._chk(self.lib.cw_time_score_head(self.ctx, int(M), 1 if unfused else 0, int(iters), C.byref(ms)))
+        self._chk(self.lib.cw_time_score_head(self.ctx, int(M), 2 if stop else (1 if unfused else 0), int(iters), C.byref(ms)))
         return float(ms.value)
 
     # ------------------------------------------------------------------ beam search (device half; host half: generation.beam_search)

@@ -1056,6 +1056,175 @@ def align(engine: Engine, n_items: int, num_frames, transcripts, *, language: Op
     return out
 
 
+def check_text_ids(spec, ids) -> np.ndarray:
+    """A transcript for ``align_long``: ``check_transcript_ids`` without timestamp tokens.  The cut of a window is scored by the
+    probability that the text stops, i.e. of eos or any timestamp token; a timestamp inside the transcript would make that
+    event ambiguous, so every id >= eos raises."""
+    a = check_transcript_ids(spec, ids)
+    bad = a[a >= spec.eos_token_id]
+    if bad.size:
+        raise ValueError(f"token id {int(bad[0])} is a timestamp token; align_long takes text tokens only (ids below "
+                         f"{spec.eos_token_id}): where the text stops inside a window is scored by eos and the timestamp tokens")
+    return a
+
+
+def align_long(engine: Engine, pcms, transcripts, collate_words, *, language: Optional[str] = None, task: Optional[str] = None,
+               return_scores: bool = False, return_alignment_scores: bool = False,
+               alignment_collar_frames: Optional[int] = None, max_window_tokens: Optional[int] = None,
+               stats: Optional[dict] = None, item_ids=None, sampling_rate: int = 16000):
+    """Forced alignment of known transcripts to recordings of any length: the walk behind ``CrisperWhisperPipeline.align_long``.
+
+    ``pcms``: at most ``engine.max_batch`` mono float32 recordings at ``sampling_rate``; ``transcripts``: one per recording, text
+    token ids only (``check_text_ids``).  ``collate_words(tokens, token_timestamps) -> (text, words, groups)`` is the word
+    collator (``collate.decode_asr(..., return_timestamps="word", return_token_groups=True)`` bound to a vocabulary).
+
+    Per recording, with pos = 0 (tokens consumed), seek = 0 (samples) and W = the token indices at which the collator starts a
+    word (one collation of the whole transcript): the window is pcm[seek : seek + 30 s], the last one iff it reaches the end
+    of the recording.  It is offered T[pos : pos + L], L the largest count <= min(N - pos, cap) that ends on a word boundary
+    (pos + L in W or == N; cap = ``max_window_tokens`` or max_target_positions - n_init - 1; a single word longer than cap
+    raises).  One ``engine.align_cut_tokens`` call tells how many of them, cut, were spoken inside the window -- cuts are allowed
+    at word boundaries, at 0 and at N; the last window is forced to take all L -- and gives the timestamps of those cut tokens
+    and, from the same forward, their log-probabilities.  The kept tokens are collated on their own, seek / sampling_rate is
+    added to every timestamp (rounded to 0.01 s as the collator rounds), pos += cut, and seek moves to the end of the last
+    kept word floored to whole 20 ms frames, or by 30 s when cut == 0 (nothing of the text is in this window: silence,
+    music); on the last window seek stays and pos grows by L > 0.  Recordings run in lockstep, one batched engine call per
+    round, each at its own (seek, pos); finished ones drop out.  ``language=None`` detects once per recording, on its first
+    window.
+
+    What is not claimed: cut is the maximum-a-posteriori prefix under the model (``Engine.align_cut_tokens``).  How well that
+    places the cut with a trained checkpoint is unmeasured.
+
+    Returns per recording {"text", "chunks": [{"text", "timestamp"}]}; ``return_scores``: "logprob" per chunk and "logprob" /
+    "avg_logprob" over the kept tokens and the eos (scored once, where the last token is consumed);
+    ``return_alignment_scores``: "alignment_score" / "alignment_spread" per chunk.  ``stats["align_long"]`` gains one record
+    per (recording, window): {"item", "seek_s", "offered", "cut", "cut_score", "forced"}."""
+    spec = engine.spec
+    n_rec = len(pcms)
+    want_as = bool(return_alignment_scores)
+    collar = check_alignment_collar(spec, alignment_collar_frames)
+    if want_as and not hasattr(engine, "set_alignment_scores"):
+        raise ValueError("this engine does not implement alignment scores (cw_set_alignment_scores)")
+    if len(transcripts) != n_rec:
+        raise ValueError(f"{len(transcripts)} transcripts for {n_rec} recordings")
+    if n_rec > engine.max_batch:
+        raise ValueError(f"{n_rec} recordings exceed the engine's {engine.max_batch} rows")
+    texts = [check_text_ids(spec, t) for t in transcripts]
+    toks, detect = resolve_prompt(spec, language, task)
+    if detect and not spec.lang_to_id:
+        raise ValueError("Cannot detect language for an English-only checkpoint: the generation config has no `lang_to_id`.")
+    n_init = len(toks)
+    cap = spec.max_target_positions - n_init - 1
+    if max_window_tokens is not None:
+        if isinstance(max_window_tokens, (bool, np.bool_)) or not isinstance(max_window_tokens, (int, np.integer)) or \
+                not 1 <= int(max_window_tokens) <= cap:
+            raise ValueError(f"max_window_tokens must be an integer in 1 .. {cap} (max_target_positions - init tokens - eos), "
+                             f"got {max_window_tokens!r}")
+        cap = int(max_window_tokens)
+    ids_of = list(range(n_rec)) if item_ids is None else list(item_ids)
+    win = N.N_SAMPLES
+    frame = win // N_FRAMES                                   # samples per 10 ms mel frame; a 20 ms token frame is two
+    trace = stats.setdefault("align_long", []) if stats is not None else None
+
+    class Rec:
+        pass
+    recs = []
+    for b in range(n_rec):
+        r = Rec()
+        r.pcm, r.T, r.n, r.pos, r.seek, r.init, r.rounds = pcms[b], texts[b], len(texts[b]), 0, 0, None, 0
+        r.chunks, r.lp, r.text, r.bounds = [], [], "", []
+        if r.n:
+            r.text, _, groups = collate_words(r.T, np.zeros(r.n, np.float32))
+            starts = {int(min(g)) for g in groups if len(g)}
+            r.bounds = sorted(starts | {r.n})                # where a cut may fall: word starts and the end
+            first = min(b_ for b_ in r.bounds if b_ > 0)
+            if first > cap:
+                raise ValueError(f"transcript {b}: its first word holds {first} tokens, above the {cap} a window is offered")
+            for lo, hi in zip(r.bounds, r.bounds[1:]):
+                if hi - lo > cap:
+                    raise ValueError(f"transcript {b}: the word at token {lo} holds {hi - lo} tokens, above the {cap} a window "
+                                     "is offered")
+            # every recording ends: a round consumes a token or moves seek by 30 s
+            r.max_rounds = r.n + -(-len(r.pcm) // win) + 1
+        recs.append(r)
+    if any(r.n for r in recs):                               # (an empty transcript does not touch the engine)
+        set_alignment_scores(engine, want_as, collar)
+    first_round = True
+    while True:
+        active = [b for b in range(n_rec) if recs[b].pos < recs[b].n]
+        if not active:
+            break
+        _, nf = engine.mel([recs[b].pcm[recs[b].seek:recs[b].seek + win] for b in active])
+        nf = np.asarray(nf, dtype=np.int64)
+        if first_round:
+            if detect:
+                engine.encode(list(range(len(active))), np.zeros(len(active), np.int64), np.full(len(active), N_FRAMES, np.int64))
+                for b, l in zip(active, detect_language(engine, len(active))):
+                    recs[b].init = init_tokens(spec, language, task, lang_id=l)
+            else:
+                for b in active:
+                    recs[b].init = init_tokens(spec, language, task)
+            first_round = False
+        rows, masks, forced, offered = [], [], [], []
+        for b in active:
+            r = recs[b]
+            last = r.seek + win >= len(r.pcm)
+            L = max(x for x in r.bounds if r.pos < x <= r.pos + min(r.n - r.pos, cap)) - r.pos
+            ok = np.zeros(L + 1, bool)
+            ok[0] = True
+            for x in r.bounds:
+                if r.pos <= x <= r.pos + L:
+                    ok[x - r.pos] = True
+            rows.append(np.concatenate([np.asarray(r.init, np.int64), r.T[r.pos:r.pos + L], [spec.eos_token_id]]))
+            masks.append(ok); forced.append(last); offered.append(L)
+        cut, cut_score, ts, lp, _, _, _ = engine.align_cut_tokens(nf, rows, n_init, masks, forced)
+        if want_as:
+            mass, spread = engine.alignment_scores(len(active), max(n_init + int(c) for c in cut))
+        for k, b in enumerate(active):
+            r = recs[b]
+            c, L = int(cut[k]), offered[k]
+            if not (0 <= c <= L and masks[k][c] and (not forced[k] or c == L)):
+                raise RuntimeError(f"align_cut_tokens returned cut {c} for {L} offered tokens (forced: {forced[k]})")
+            if trace is not None:
+                trace.append({"item": ids_of[b], "seek_s": r.seek / sampling_rate, "offered": L, "cut": c,
+                              "cut_score": float(cut_score[k]), "forced": bool(forced[k])})
+            seek_before, pos_before = r.seek, r.pos
+            if c > 0:
+                kept_lp = np.asarray(lp[k][:c], np.float64)
+                _, words, groups = collate_words(r.T[r.pos:r.pos + c], np.asarray(ts[k][n_init:n_init + c], np.float32))
+                end = max((w["timestamp"][1] for w in words if w["timestamp"][1] is not None), default=0.0)
+                if return_scores:
+                    words = [{"text": w["text"], "timestamp": w["timestamp"], "logprob": float(np.sum(kept_lp[g]))}
+                             for w, g in zip(words, groups)]
+                if want_as:
+                    from .pipeline import add_alignment_scores
+                    add_alignment_scores(words, groups, [mass[k, n_init:n_init + c]], [spread[k, n_init:n_init + c]])
+                off = r.seek / sampling_rate
+                for w in words:
+                    w["timestamp"] = tuple(None if t is None else round(t + off, 2) for t in w["timestamp"])
+                r.chunks.extend(words)
+                r.lp.append(kept_lp)
+                r.pos += c
+                if r.pos == r.n:
+                    r.lp.append(np.asarray(lp[k][c:c + 1], np.float64))      # c == L here: the eos after the whole transcript
+                if not forced[k]:
+                    r.seek += (int(round(end * 100)) // 2) * 2 * frame         # whole 20 ms frames, floored
+            elif not forced[k]:
+                r.seek += win
+            r.rounds += 1
+            assert r.pos > pos_before or r.seek >= seek_before + win, "align_long: a round neither consumed a token nor moved on"
+            assert r.rounds <= r.max_rounds, "align_long: more rounds than tokens and windows"
+    out = []
+    for r in recs:
+        res = {"text": r.text, "chunks": r.chunks}
+        if return_scores:
+            allp = np.concatenate(r.lp) if r.lp else np.zeros(0, np.float64)
+            total = float(allp.sum())
+            res["logprob"] = total
+            res["avg_logprob"] = total / (r.n + 1)
+        out.append(res)
+    return out
+
+
 ALIGN_HEADS_ROW_BYTES = 1500 * 4          # one recorded attention row (f32 over the encoder frames)
 
 

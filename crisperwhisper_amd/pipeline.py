@@ -842,7 +842,9 @@ class CrisperWhisperPipeline:
             pcm = self._load(x)
             if len(pcm) > N_SAMPLES:
                 raise ValueError(f"input {k} is {len(pcm) / self.sampling_rate:.2f} s long: {who} takes at most 30 s "
-                                 f"({N_SAMPLES} samples) per input; long-form {'scoring' if who == 'score' else 'alignment'} is not implemented")
+                                 f"({N_SAMPLES} samples) per input; "
+                                 + ("long-form scoring is not implemented" if who == "score" else
+                                    "long-form alignment is not implemented here: align_long walks a transcript over longer audio"))
             pcms.append(pcm)
         return pcms
 
@@ -984,6 +986,51 @@ class CrisperWhisperPipeline:
                                                           time_precision=0.02, return_timestamps="word",
                                                           **({"return_token_groups": True} if akw else {}))
                 results.append({"text": text, "chunks": with_alignment(out, k, words, groups[0] if akw else None)})
+        return results[0] if single else results
+
+    def align_long(self, inputs, transcripts, language: Optional[str] = None, task: Optional[str] = None,
+                   return_scores: bool = False, return_alignment_scores: bool = False,
+                   alignment_collar_frames: Optional[int] = None, max_window_tokens: Optional[int] = None):
+        """``align`` for audio of any length: walks a known transcript over the recording in 30 s windows.  ``inputs`` one
+        input or a list, as ``align`` takes them but of any length; ``transcripts`` one per input, a ``str`` or text token ids
+        (no timestamp tokens).  Every window is offered the transcript from the first token not yet placed, up to
+        ``max_window_tokens`` (None: what fits the decoder, max_target_positions - init tokens - eos) and ending on a word
+        boundary; one teacher-forced HIP forward per window tells how much of it was spoken inside the window (the cut: the
+        most probable prefix under the model, scored by the probability that eos or a timestamp token follows it), aligns
+        that part and scores it, and the next window starts where the last placed word ends -- or 30 s later where the window
+        held none of the text.  The last window takes whatever is left.  A list of inputs runs in lockstep, one batched
+        forward per round over up to the pipeline's decoder rows.  ``language=None`` detects once per input, on its first
+        window.  Returns what ``align`` returns, with the same options; for audio of at most 30 s it is ``align``'s result.
+        ``stats["align_long"]`` lists per (input, window) {"item", "seek_s", "offered", "cut", "cut_score", "forced"}.
+
+        Not claimed: that the cut is right.  It is the maximum-a-posteriori prefix under the model; how well that places
+        the cut with a trained checkpoint is unmeasured."""
+        collar = getattr(self, "alignment_collar_frames", None) if alignment_collar_frames is None else alignment_collar_frames
+        if collar is not None:
+            collar = generation.check_alignment_collar(None, collar)
+        single = not isinstance(inputs, (list, tuple))
+        if single:
+            inputs, transcripts = [inputs], [transcripts]
+        elif not isinstance(transcripts, (list, tuple)) or len(transcripts) != len(inputs):
+            raise ValueError(f"{len(inputs)} inputs need a list of {len(inputs)} transcripts, got "
+                             f"{len(transcripts) if isinstance(transcripts, (list, tuple)) else type(transcripts).__name__}")
+        ids = [generation.check_text_ids(self.bundle.spec, self._transcript_ids(t)) for t in transcripts]
+        generation.resolve_prompt(self.bundle.spec, language, task)        # refuses a bad language / task before any audio work
+        pcms = [self._load(x) for x in inputs]
+        eng = self.engine
+        per = max(1, eng.max_batch)
+
+        def collate_words(tokens, token_ts):
+            return collate.decode_asr(self.vocab, [{"tokens": tokens, "token_timestamps": token_ts}], time_precision=0.02,
+                                      return_timestamps="word", return_token_groups=True)
+        self.stats["align_long"] = []
+        results = []
+        for b0 in range(0, len(pcms), per):
+            idx = list(range(b0, min(len(pcms), b0 + per)))
+            results.extend(generation.align_long(
+                eng, [pcms[i] for i in idx], [ids[i] for i in idx], collate_words, language=language, task=task,
+                return_scores=return_scores, return_alignment_scores=return_alignment_scores, alignment_collar_frames=collar,
+                max_window_tokens=max_window_tokens, stats=self.stats, item_ids=idx, sampling_rate=self.sampling_rate))
         return results[0] if single else results
 
     # -- per-head forced alignment, alignment-head selection -----------------------------------------

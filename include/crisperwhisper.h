@@ -444,6 +444,26 @@ int32_t cw_score_tokens(cw_ctx* ctx, int32_t n_items, int32_t rows_per_item, con
 int32_t cw_align_score_tokens(cw_ctx* ctx, int32_t nb, const int32_t* num_frames, const int32_t* ids, int32_t ids_stride,
                               const int32_t* n_ids, int32_t n_init, float* token_ts, float* token_logprob, int32_t* top_id,
                               float* top_logprob);
+/* cw_align_cut_tokens: how much of an offered transcript was spoken inside the window, and the alignment of that part, in the
+ * one forward of cw_align_score_tokens (same inputs, checks, encoder pass and forward path).  Row b offers N_b = n_ids[b] -
+ * n_init - 1 text tokens.  Beside token_logprob the head reduces, at every scored position k = n_init .. n_ids[b]-1,
+ *   stop_logprob[b][k] = logsumexp(logit[n], n in S) - logsumexp(all logits),  S = {eos} + {n >= timestamp_begin}:
+ * the log-probability that the text stops before position k (after the last word a window holds, Whisper predicts the end of
+ * text or a closing timestamp).  On the device, S_b[n] = sum_{i<n} token_logprob[b][n_init + i] + stop_logprob[b][n_init + n]
+ * (float64, ascending) is the log-probability that exactly the first n tokens are the window's text; cut[b] = the n in
+ * 0 .. N_b with cut_ok[b][n] != 0 of the largest S_b[n], the lowest on an exact tie, or N_b whatever the mask says where
+ * force_all[b] != 0; cut_score[b] = that S_b[n] rounded once to f32.  cut_ok [nb][ids_stride] bytes indexed by n = tokens kept,
+ * force_all [nb] bytes.  The timestamp stage then runs with row b shortened to n_init + cut[b] + 1 ids: token_ts[b] holds
+ * entries 0 .. n_init + cut[b], exactly what cw_align_tokens writes for ids[b][0 .. n_init + cut[b] - 1] followed by eos (the
+ * forward is causal, so a prefix's alignment rows do not depend on what follows; the z-score over tokens is taken over the
+ * prefix).  token_logprob, top_id and top_logprob are bit-identical to cw_align_score_tokens', written with stop_logprob for
+ * every k; alignment scores (cw_set_alignment_scores) cover the shortened rows.  CW_ERR_INVALID, before anything is launched:
+ * what cw_align_score_tokens refuses, a null cut_ok / force_all / cut / cut_score / token_ts / token_logprob / stop_logprob, a
+ * row with neither force_all nor a non-zero cut_ok[b][0 .. N_b]; CW_ERR_STATE without alignment heads.                      */
+int32_t cw_align_cut_tokens(cw_ctx* ctx, int32_t nb, const int32_t* num_frames, const int32_t* ids, int32_t ids_stride,
+                            const int32_t* n_ids, int32_t n_init, const uint8_t* cut_ok, const uint8_t* force_all, int32_t* cut,
+                            float* cut_score, float* token_ts, float* token_logprob, float* stop_logprob, int32_t* top_id,
+                            float* top_logprob);
 /* cw_score_prefill_runs: how many scoring calls of this context ran their forward as the batched prefill.                  */
 int32_t cw_score_prefill_runs(cw_ctx* ctx);
 
@@ -561,8 +581,20 @@ int32_t cw_test_attention(cw_ctx* ctx, int32_t B, int32_t H, int32_t S, const fl
  * type), targets [M] in 0 .. V-1 -> logprob / top_id / top_logprob [M].  16-bit engines; D % 32 == 0.                      */
 int32_t cw_test_score_head(cw_ctx* ctx, int32_t M, int32_t D, int32_t V, const float* x, const float* ln_g, const float* ln_b,
                            const float* embed, const int32_t* targets, float* logprob, int32_t* top_id, float* top_logprob);
+/* ... and its STOP form (cw_align_cut_tokens): also stop_logprob [M] over S = {eos} + {n >= timestamp_begin}, eos in 0 .. V-1,
+ * timestamp_begin in 0 .. V (V: S = {eos}).  logprob / top_id / top_logprob are bit-identical to cw_test_score_head's.       */
+int32_t cw_test_score_head_stop(cw_ctx* ctx, int32_t M, int32_t D, int32_t V, const float* x, const float* ln_g, const float* ln_b,
+                                const float* embed, const int32_t* targets, int32_t eos, int32_t timestamp_begin, float* logprob,
+                                int32_t* top_id, float* top_logprob, float* stop_logprob);
+/* The cut kernel of cw_align_cut_tokens on caller-supplied scores: logprob / stop_logprob / cut_ok [rows][stride], entries
+ * 0 .. n_tok[r] of row r used (n_tok[r] < stride), force_all [rows] -> cut / cut_score [rows].  Any engine.  CW_ERR_INVALID for
+ * a row that is neither forced nor allowed any cut.                                                                         */
+int32_t cw_test_align_cut(cw_ctx* ctx, int32_t rows, int32_t stride, const int32_t* n_tok, const float* logprob,
+                          const float* stop_logprob, const uint8_t* cut_ok, const uint8_t* force_all, int32_t* cut,
+                          float* cut_score);
 /* Times the scoring head at the context's geometry over M pseudo-random rows: unfused = 0 the fused kernels, 1 the same GEMM
- * writing f32 logits [M][V] plus a row-wise log-softmax pass.  avg_ms per repetition (HIP events, one warm-up).           */
+ * writing f32 logits [M][V] plus a row-wise log-softmax pass, 2 the fused STOP form.  avg_ms per repetition (HIP events, one
+ * warm-up).                                                                                                                */
 int32_t cw_time_score_head(cw_ctx* ctx, int32_t M, int32_t unfused, int32_t iters, float* avg_ms);
 /* Decoder prompt prefill kernels (16-bit engines) against a host reference: cw_test_prefill_gemm runs the prefill GEMM over
  * fragment-major packed W with epilogue mode 0 = 16-bit store, 2 = f32 residual add (out: residual in, result out), 3 = erf GELU
