@@ -20,9 +20,12 @@ typedef __attribute__((ext_vector_type(4))) float f32x4_t;   // one MFMA 16x16 C
 
 #define CW_WAVE 64
 
-// Streams that one block reads once per launch (decode weights, K/V caches): non-temporal loads -- `global_load ... nt` --
-// land ~18 % sooner than default-policy loads on this chip (MI355X_MICROARCH.md price list, row nt-weights) and do not
-// displace the activations that every block re-reads from L2.  -DCW_NO_NT restores the default policy (A/B builds).
+// Streams that exactly one block of a launch reads, once per token step: non-temporal loads (`global_load ... nt`).  Used by the
+// cross- and self-attention K/V streams, the logits projection and -- on fragment-major weights, where one wave instruction covers
+// eight whole cache lines -- the weight streams of the <= 16-row decode GEMVs (gemv2_bf16_kernel / gemv_stack_kernel / qkv_self_kernel
+// <.., WNT>; a run-time choice per launch, CW_NO_WNT).  Not used where a tile is re-read from L2 by design
+// (row groups, 17..64 rows), on row-major weights, on operands every block re-reads (activation rows, bias, partial planes) or on
+// granule hand-offs.  -DCW_NO_NT restores the default policy everywhere (A/B builds).
 #ifdef CW_NO_NT
 #define CW_STREAM_LD(p) (*(p))
 #else

@@ -109,7 +109,9 @@ int cw_launch_fold_rowvec(const float* A, const float* s, float scale, const flo
 // UNI (round 6): every segment streams NT tiles per block from fragment-major weights -- the shape of every launch of the default
 // engine.  The weight requests then sit under no branch (`t < snt` and `wpk` are run-time values otherwise: hipcc wraps each tile's
 // loads in a block-uniform branch and must answer the first wait behind them with vmcnt(0)).  Same arithmetic.
-template <int RPW, int NSLOT, int PER_LANE, int NT, bool UNI = false>
+// WNT (with UNI): the weight stream with non-temporal loads -- launches of one row group (gridDim.y == 1), where every tile is read by
+// exactly one block; the 16-row groups of 17..64 rows re-read the tiles from L2 (below) and keep the default policy.
+template <int RPW, int NSLOT, int PER_LANE, int NT, bool UNI = false, bool WNT = false>
 __global__ __launch_bounds__(256) void gemv_stack_kernel(StackParams p) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_s[];
     // 17..64 rows (round 5): blockIdx.y = group of 16 rows; a group is a 16-row launch of its own over the same weights (its
@@ -193,7 +195,7 @@ __global__ __launch_bounds__(256) void gemv_stack_kernel(StackParams p) {
                                         : (const u32x4_t*)(wrow + step * 128);
                 const int sj = wpk ? 64 : 4;
 #pragma unroll
-                for (int j = 0; j < 4; ++j) wq[t][s][j] = wp[j * sj];
+                for (int j = 0; j < 4; ++j) wq[t][s][j] = WNT ? CW_STREAM_LD(wp + j * sj) : wp[j * sj];
             }
         } else {
 #pragma unroll
@@ -325,7 +327,8 @@ static int launch_stack_nt(StackParams& p, hipStream_t st) {
     else {
         bool uni = p.wpk != 0;
         for (int s = 0; s < p.nseg; ++s) uni = uni && p.seg[s].nt == NT;
-        if (uni) hipLaunchKernelGGL((gemv_stack_kernel<RPW, 3, 5, NT, true>), grid, dim3(256), lds, st, p);
+        if (uni && p.wnt && grid.y == 1) hipLaunchKernelGGL((gemv_stack_kernel<RPW, 3, 5, NT, true, true>), grid, dim3(256), lds, st, p);
+        else if (uni) hipLaunchKernelGGL((gemv_stack_kernel<RPW, 3, 5, NT, true>), grid, dim3(256), lds, st, p);
         else hipLaunchKernelGGL((gemv_stack_kernel<RPW, 3, 5, NT>), grid, dim3(256), lds, st, p);
     }
     return CW_OK;

@@ -513,7 +513,8 @@ __global__ __launch_bounds__(DL_THREADS) void dec_layer_a_kernel(DecLayerParams 
 #define QS_GROUPS (QS_THREADS / 8)
 #define QS_PRE 2
 
-template <int NSLOT, int PER_LANE>
+// WNT: the tiles' weight stream with non-temporal loads (tile t has one reading block: block t).  The granule loads and stores keep their policy.
+template <int NSLOT, int PER_LANE, bool WNT>
 __global__ __launch_bounds__(QS_THREADS) void qkv_self_kernel(QkvSelfParams p) {
     extern __shared__ __attribute__((aligned(16))) unsigned char qsm[];
     const int K = p.D, Mb = p.Mb, H = p.H, N = 3 * K, cap = p.cap;
@@ -567,7 +568,7 @@ __global__ __launch_bounds__(QS_THREADS) void qkv_self_kernel(QkvSelfParams p) {
             step = step < steps ? step : steps - 1;
             const dl_u32x4_t* wp = (const dl_u32x4_t*)(W + ((((size_t)(ncl >> 4) * (K >> 5)) + step * 4) * 64 + g * 16 + (ncl & 15)) * 8);
 #pragma unroll
-            for (int j = 0; j < 4; ++j) wq[s][j] = wp[j * 64];
+            for (int j = 0; j < 4; ++j) wq[s][j] = WNT ? CW_STREAM_LD(wp + j * 64) : wp[j * 64];
         }
     }
     __builtin_amdgcn_sched_barrier(0);
@@ -853,16 +854,18 @@ int cw_launch_qkv_self(const QkvSelfParams& p, hipStream_t st) {
     const size_t lds = (size_t)16 * (D + 8) * 2 + (size_t)(4 * 4 * 64 + 64) * 4 + 2 * 64 * 2 +
                        ((size_t)((p.cap + 63) & ~63) + QS_GROUPS * 64 + 64) * 4;
     const dim3 grid(3 * (D / 16));
-#define QS_LAUNCH(NS, PL)                                                                                                   \
+#define QS_LAUNCH_P(NS, PL, NTL)                                                                                            \
     do {                                                                                                                     \
         static std::once_flag attr;                                                                                          \
-        std::call_once(attr, [] { (void)hipFuncSetAttribute((const void*)qkv_self_kernel<NS, PL>, hipFuncAttributeMaxDynamicSharedMemorySize, 100 * 1024); }); \
-        hipLaunchKernelGGL((qkv_self_kernel<NS, PL>), grid, dim3(QS_THREADS), lds, st, p);                                   \
+        std::call_once(attr, [] { (void)hipFuncSetAttribute((const void*)qkv_self_kernel<NS, PL, NTL>, hipFuncAttributeMaxDynamicSharedMemorySize, 100 * 1024); }); \
+        hipLaunchKernelGGL((qkv_self_kernel<NS, PL, NTL>), grid, dim3(QS_THREADS), lds, st, p);                              \
     } while (0)
+#define QS_LAUNCH(NS, PL) do { if (p.wnt) QS_LAUNCH_P(NS, PL, true); else QS_LAUNCH_P(NS, PL, false); } while (0)
     if (D <= 256) QS_LAUNCH(1, 1);
     else if (D <= 768) QS_LAUNCH(2, 3);
     else QS_LAUNCH(3, 5);
 #undef QS_LAUNCH
+#undef QS_LAUNCH_P
     return CW_OK;
 }
 

@@ -120,6 +120,8 @@ struct cw_ctx {
     bool weights_ok = false;        // every tensor of the geometry has been loaded (checked once, see cw_check_weights)
     bool wpacked = false;           // the decoder's GEMV matrices are in fragment-major order (gemm.hip: wfrag_pack_kernel)
     bool wpack_enabled = true;      // CW_NO_WPACK=1: keep them row-major (A/B)
+    bool wnt = true;                // the <= 16-row decode launches stream packed weights that one block reads with non-temporal loads;
+                                    // CW_NO_WNT=1 / option "no_wnt": the default-policy instantiations (A/B)
     void* embed_pk = nullptr;       // fragment-major copy of the tied embedding for the logits GEMV (the row-major one serves the token lookup)
 
     // weights
@@ -479,6 +481,7 @@ static int create_impl(cw_ctx* c) {
     c->dtw_block = sw.dtw_block;
     c->fuse_mlp = sw.fuse_mlp;
     c->wpack_enabled = !sw.no_wpack;
+    c->wnt = !sw.no_wnt;
     c->mlp_pair = sw.mlp_pair;
     c->mlp_pair_fence = sw.mlp_pair_fence;
     c->declayer = sw.declayer;
@@ -1160,7 +1163,7 @@ static int gemv_ln(cw_ctx* c, int epi, const float* x, int Mb, int K, const void
                    const float* b, const EpiParams& ep) {
     // (17..64 rows over row-major weights -- CW_NO_WPACK=1, or a geometry pack_decoder_weights does not take: no scratch, i.e. groups of
     // 16 rows on the <= 16-row kernels; gemv_mt_kernel reads fragment-major weights only)
-    if (c->bf16 || !g) return KD(c, cw_launch_gemv, c->bf16, epi, x, Mb, K, W, N, g, b, ep, c->st, nullptr, (Mb <= 16 || c->wpacked) ? c->d_xfrag : nullptr, c->bf16 && c->wpacked);
+    if (c->bf16 || !g) return KD(c, cw_launch_gemv, c->bf16, epi, x, Mb, K, W, N, g, b, ep, c->st, nullptr, (Mb <= 16 || c->wpacked) ? c->d_xfrag : nullptr, c->bf16 && c->wpacked, c->wnt);
     int r = KD(c, cw_launch_layernorm_f32, x, g, b, c->dxn, Mb, K, c->st);   // f32 parity mode: unfused LN
     if (r != CW_OK) return r;
     return KD(c, cw_launch_gemv, false, epi, c->dxn, Mb, K, W, N, nullptr, nullptr, ep, c->st);
@@ -1320,7 +1323,7 @@ static int layer_self_attention(cw_ctx* c, const StepPlan& P, int l, int nb, con
     }
     QkvSelfParams qp = zeroed<QkvSelfParams>();
     qp.x = x; qp.W = L.wqkv; qp.bias = L.bqkv; qp.sk = L.sk; qp.sv = L.sv; qp.cap = TGT; qp.pos = c->d_pos; qp.out = c->dattn;
-    qp.gq = c->d_gq2; qp.gkv = c->d_gkv; qp.epoch = c->d_epoch; qp.layer = l; qp.err = c->d_err; qp.Mb = nb; qp.D = D; qp.H = H; qp.fail_pos = c->fail_pos;
+    qp.gq = c->d_gq2; qp.gkv = c->d_gkv; qp.epoch = c->d_epoch; qp.layer = l; qp.err = c->d_err; qp.Mb = nb; qp.D = D; qp.H = H; qp.fail_pos = c->fail_pos; qp.wnt = c->wnt ? 1 : 0;
     const int dbg = cw_sw::cw_switches().qkv_self_dbg;   // 1: tiles fused, attention by attn_decode_kernel behind it (bisecting aid)
     if (dbg) { qp.q_plain = c->dq; qp.no_attn = 1; }
     STG(DST_QKV_SELF, KD(c, cw_launch_qkv_self, qp, c->st));
@@ -1331,7 +1334,7 @@ static int layer_self_attention(cw_ctx* c, const StepPlan& P, int l, int nb, con
 static StackParams stack_params(cw_ctx* c, LayerW& L, int nb, const float* xin, float* xalt) {
     const int D = c->d.d_model, TD = D / 16;
     StackParams sp = zeroed<StackParams>();
-    sp.W = L.ws3; sp.wpk = c->wpacked ? 1 : 0; sp.K = D; sp.Mb = nb; sp.nseg = 3;
+    sp.W = L.ws3; sp.wpk = c->wpacked ? 1 : 0; sp.wnt = c->wnt ? 1 : 0; sp.K = D; sp.Mb = nb; sp.nseg = 3;
     sp.seg[0].x = xin;      sp.seg[0].bias = L.qa_bias; sp.seg[0].out = c->d_qa; sp.seg[0].tile0 = 0;      sp.seg[0].n_tiles = TD; sp.seg[0].epi = 0;
     sp.seg[0].wsum = c->stack_center ? L.q_wsum : nullptr;   // x is rounded as x - mean(x): the operand the cross-attention LayerNorm is sensitive to
     sp.seg[1].x = c->dattn; sp.seg[1].bias = nullptr;   sp.seg[1].out = c->d_qb; sp.seg[1].tile0 = TD;     sp.seg[1].n_tiles = TD; sp.seg[1].epi = 0;
@@ -3664,6 +3667,11 @@ int32_t cw_set_option(cw_ctx* c, const char* name, int32_t value) {
         drop_step_graphs(c);   // kernel arguments are baked into the graphs
         return CW_OK;
     }
+    if (!strcmp(name, "no_wnt")) {    // != 0: default-policy weight loads in the <= 16-row decode GEMVs (CW_NO_WNT; A/B, differential tests)
+        c->wnt = value == 0;
+        drop_step_graphs(c);   // graphs hold the kernel choice
+        return CW_OK;
+    }
     if (!strcmp(name, "rows_ln")) {   // 17..64-row decode: 0 = preparation launch in front of every GEMV (A/B, differential tests)
         c->rows_ln_enabled = value != 0;
         drop_step_graphs(c);   // graphs hold the kernel choice
@@ -3687,9 +3695,11 @@ int32_t cw_has_experiments(void) {
 #endif
 }
 
+static int g_test_no_wnt = 0;      // cw_test_gemv_epi / cw_test_gemv_stack with default-policy weight loads (option "no_wnt"; a context's own: cw_set_option)
 static int g_test_cross_fp8 = 0;   // cw_test_cross_attention through the e4m3 cache (option "cross_test_fp8")
 static int g_test_attn_poison_qpad = 0;   // cw_test_attention: Q rows S .. S_pad-1 hold NaN instead of zeros (option "attn_poison_qpad")
 int32_t cw_test_set_option(const char* name, int32_t value) {
+    if (!strcmp(name, "no_wnt")) { g_test_no_wnt = value; return CW_OK; }
     if (!strcmp(name, "cross_test_fp8")) { g_test_cross_fp8 = value; return CW_OK; }
     if (!strcmp(name, "attn_poison_qpad")) { g_test_attn_poison_qpad = value; return CW_OK; }
     if (!strcmp(name, "gemm256_min_tiles")) { cw_bf16::cw_gemm_set_256_min_tiles(value); cw_f16::cw_gemm_set_256_min_tiles(value); return CW_OK; }
@@ -4611,7 +4621,7 @@ int32_t cw_test_gemv_stack(cw_ctx* c, const cw_test_gemv_stack_args* a) {
     };
     StackParams sp;
     memset(&sp, 0, sizeof(sp));
-    sp.W = a->wpk ? dWp : dW; sp.wpk = a->wpk ? 1 : 0; sp.K = K; sp.Mb = Mb; sp.nseg = nseg;
+    sp.W = a->wpk ? dWp : dW; sp.wpk = a->wpk ? 1 : 0; sp.wnt = (c->wnt && !g_test_no_wnt) ? 1 : 0; sp.K = K; sp.Mb = Mb; sp.nseg = nseg;
     float *dout[3] = {}, *dout2[3] = {}, *dps[3] = {}, *dzero = nullptr;
     int tile0 = 0;
     for (int s = 0; s < nseg; ++s) {
@@ -4818,7 +4828,7 @@ int32_t cw_test_gemv_epi(cw_ctx* c, const cw_test_gemv_epi_args* a) {
         const float* xin = comb ? dpo : a->frag_in ? nullptr : a->x16 ? (const float*)dx16 : dx;
         const bool wpacked = c->bf16 && a->wpk;
         r = KD(c, cw_launch_gemv, c->bf16, epi, xin, Mb, K, Wd, N, dg, dbeta, ep, c->st, comb ? &cb : nullptr,
-               (Mb <= 16 || wpacked) ? dscr : nullptr, wpacked);
+               (Mb <= 16 || wpacked) ? dscr : nullptr, wpacked, c->wnt && !g_test_no_wnt);
     } else if (op == 1) {
         CWCHK(c, getg(&dout, (size_t)Mpad * K * 2, "out"));
         CWCHK(c, frag_up(dout, a->out, Mb, K, Mpad, FILL));

@@ -1165,7 +1165,8 @@ extern "C" int cw_debug_phases(unsigned long long* out) {
 #endif
 
 template <int EPI, int RPW, bool ATOMIC, bool COMBINE, int NSLOT, int PER_LANE, int NT = 1 /* 16-column tiles per block */,
-          bool X16 = false /* activation rows arrive in the engine's 16-bit type (no LayerNorm, no combine) */>
+          bool X16 = false /* activation rows arrive in the engine's 16-bit type (no LayerNorm, no combine) */,
+          bool WNT = false /* weight stream with non-temporal loads: launches where every weight tile has ONE reading block (see the loads) */>
 __global__ __launch_bounds__(256) void gemv2_bf16_kernel(const float* __restrict__ x, int Mb, int K, int Kb,
                                                          const bf16_t* __restrict__ W, int N,
                                                          const float* __restrict__ ln_g,
@@ -1290,7 +1291,12 @@ __global__ __launch_bounds__(256) void gemv2_bf16_kernel(const float* __restrict
                                     : (const u32x4_t*)(wrow + step * 128);
             const int sj = wpk ? 64 : 4;
 #pragma unroll
-            for (int j = 0; j < 4; ++j) wq[t][s][j] = wp[j * sj];   // (non-temporal loads measured slower here: decode 436 vs 418 ms / step)
+            // WNT: the launcher sets it for fragment-major weights read by one block per tile (every line is then touched exactly once
+            // per token step).  Measured with every weight stream of the <= 16-row layer non-temporal at once, against the parent
+            // commit: DESIGN.md 6g', profiles/wnt_bench_ab.txt.  Row groups (gridDim.z, m_base) re-read a tile from L2 by design and
+            // row-major weights touch every line twice -- the layout on which non-temporal loads measured slower in round 2 (436 vs
+            // 418 ms / step): both stay default-policy
+            for (int j = 0; j < 4; ++j) wq[t][s][j] = WNT ? CW_STREAM_LD(wp + j * sj) : wp[j * sj];
         }
     }
 
@@ -2004,10 +2010,22 @@ int cw_gemv_kc(int Mb, int K) {
     return 128;
 }
 
+// wnt: the launches below stream their weights with non-temporal loads (cw_launch_gemv sets it only for fragment-major weights and one
+// group of <= 16 rows: every tile is then read by exactly one block of the launch).  The combining out-projection (row groups re-read a
+// tile from L2) and the three-tile fallback of the logits keep the default policy.
+#define CW_GEMV2_LAUNCH(GRID, LDS, ...)                                                                                               \
+    do {                                                                                                                               \
+        if (wnt)                                                                                                                       \
+            hipLaunchKernelGGL((gemv2_bf16_kernel<__VA_ARGS__, true>), GRID, dim3(256), LDS, st, x, Mb, K, Kb, (const bf16_t*)W, N,    \
+                               ln_g, ln_b, ep, cb, m_base, wpk);                                                                       \
+        else                                                                                                                           \
+            hipLaunchKernelGGL((gemv2_bf16_kernel<__VA_ARGS__, false>), GRID, dim3(256), LDS, st, x, Mb, K, Kb, (const bf16_t*)W, N,   \
+                               ln_g, ln_b, ep, cb, m_base, wpk);                                                                       \
+    } while (0)
 template <int EPI, int RPW, int NSLOT, int PER_LANE>
 static void launch_gemv2_shape(dim3 grid, size_t lds, int ksplit, const float* x, int Mb, int K, int Kb, const void* W,
                                int N, const float* ln_g, const float* ln_b, const EpiParams& ep, hipStream_t st,
-                               const CombineParams& cb, int m_base, int wpk) {
+                               const CombineParams& cb, int m_base, int wpk, bool wnt) {
     if (EPI == EPI_RESID_F32 && cb.part_ml) {
         if (ksplit > 1)
             hipLaunchKernelGGL((gemv2_bf16_kernel<EPI_RESID_F32, RPW, true, true, NSLOT, PER_LANE>), grid, dim3(256), lds, st,
@@ -2018,18 +2036,10 @@ static void launch_gemv2_shape(dim3 grid, size_t lds, int ksplit, const float* x
     } else if (EPI == EPI_RESID_F32 && ksplit > 1) {
         if (N % 32 == 0 && (int)(grid.x * grid.y) > 256 && (int)(grid.x * grid.y) / 2 >= 128) {   // fc2: (80, 4) -> (40, 4)
             dim3 g2(grid.x / 2, grid.y);
-            if (ep.x16)
-                hipLaunchKernelGGL((gemv2_bf16_kernel<EPI_RESID_F32, RPW, true, false, NSLOT, PER_LANE, 2, true>), g2, dim3(256),
-                                   lds + 4 * 4 * 64 * 4, st, x, Mb, K, Kb, (const bf16_t*)W, N, ln_g, ln_b, ep, cb, m_base, wpk);
-            else
-            hipLaunchKernelGGL((gemv2_bf16_kernel<EPI_RESID_F32, RPW, true, false, NSLOT, PER_LANE, 2>), g2, dim3(256),
-                               lds + 4 * 4 * 64 * 4, st, x, Mb, K, Kb, (const bf16_t*)W, N, ln_g, ln_b, ep, cb, m_base, wpk);
-        } else if (ep.x16)
-            hipLaunchKernelGGL((gemv2_bf16_kernel<EPI_RESID_F32, RPW, true, false, NSLOT, PER_LANE, 1, true>), grid, dim3(256), lds, st, x,
-                               Mb, K, Kb, (const bf16_t*)W, N, ln_g, ln_b, ep, cb, m_base, wpk);
-        else
-        hipLaunchKernelGGL((gemv2_bf16_kernel<EPI_RESID_F32, RPW, true, false, NSLOT, PER_LANE>), grid, dim3(256), lds, st, x,
-                           Mb, K, Kb, (const bf16_t*)W, N, ln_g, ln_b, ep, cb, m_base, wpk);
+            if (ep.x16) CW_GEMV2_LAUNCH(g2, lds + 4 * 4 * 64 * 4, EPI_RESID_F32, RPW, true, false, NSLOT, PER_LANE, 2, true);
+            else CW_GEMV2_LAUNCH(g2, lds + 4 * 4 * 64 * 4, EPI_RESID_F32, RPW, true, false, NSLOT, PER_LANE, 2, false);
+        } else if (ep.x16) CW_GEMV2_LAUNCH(grid, lds, EPI_RESID_F32, RPW, true, false, NSLOT, PER_LANE, 1, true);
+        else CW_GEMV2_LAUNCH(grid, lds, EPI_RESID_F32, RPW, true, false, NSLOT, PER_LANE, 1, false);
     } else {
         // wide LayerNorm GEMVs (fc1: 320 16-column tiles on 256 CUs put two blocks on 64 CUs, whose 2 x 120 KB of loads are
         // the kernel's critical path): two column tiles per block share the activation rows and the LayerNorm work,
@@ -2052,17 +2062,15 @@ static void launch_gemv2_shape(dim3 grid, size_t lds, int ksplit, const float* x
                                x, Mb, K, Kb, (const bf16_t*)W, N, ln_g, ln_b, ep, cb, m_base, wpk);
         } else if (ln_g && ksplit == 1 && grid.x > 256 && grid.x / 2 >= 128) {
             dim3 g2((grid.x + 1) / 2, 1);
-            hipLaunchKernelGGL((gemv2_bf16_kernel<EPI, RPW, false, false, NSLOT, PER_LANE, 2>), g2, dim3(256), lds + 4 * 4 * 64 * 4, st,
-                               x, Mb, K, Kb, (const bf16_t*)W, N, ln_g, ln_b, ep, cb, m_base, wpk);
-        } else
-        hipLaunchKernelGGL((gemv2_bf16_kernel<EPI, RPW, false, false, NSLOT, PER_LANE>), grid, dim3(256), lds, st, x, Mb, K,
-                           Kb, (const bf16_t*)W, N, ln_g, ln_b, ep, cb, m_base, wpk);
+            CW_GEMV2_LAUNCH(g2, lds + 4 * 4 * 64 * 4, EPI, RPW, false, false, NSLOT, PER_LANE, 2, false);
+        } else CW_GEMV2_LAUNCH(grid, lds, EPI, RPW, false, false, NSLOT, PER_LANE, 1, false);
     }
 }
+#undef CW_GEMV2_LAUNCH
 
 template <int EPI, int RPW>
 static void launch_gemv2(const float* x, int Mb, int K, const void* W, int N, const float* ln_g, const float* ln_b,
-                         const EpiParams& ep, hipStream_t st, const CombineParams* comb, int m_base, int wpk) {
+                         const EpiParams& ep, hipStream_t st, const CombineParams* comb, int m_base, int wpk, bool wnt) {
     CombineParams cb{nullptr, 0, 0};
     if (comb) cb = *comb;
     // K split: only for the in-place residual epilogue (f32 atomics into the residual stream), sized so that
@@ -2121,9 +2129,9 @@ static void launch_gemv2(const float* x, int Mb, int K, const void* W, int N, co
         }
     }
     dim3 grid((N + 15) / 16, ksplit);
-    if (Kb <= 256) launch_gemv2_shape<EPI, RPW, 1, 1>(grid, lds, ksplit, x, Mb, K, Kb, W, N, ln_g, ln_b, ep, st, cb, m_base, wpk);
-    else if (Kb <= 768) launch_gemv2_shape<EPI, RPW, 2, 3>(grid, lds, ksplit, x, Mb, K, Kb, W, N, ln_g, ln_b, ep, st, cb, m_base, wpk);
-    else launch_gemv2_shape<EPI, RPW, 3, 5>(grid, lds, ksplit, x, Mb, K, Kb, W, N, ln_g, ln_b, ep, st, cb, m_base, wpk);
+    if (Kb <= 256) launch_gemv2_shape<EPI, RPW, 1, 1>(grid, lds, ksplit, x, Mb, K, Kb, W, N, ln_g, ln_b, ep, st, cb, m_base, wpk, wnt);
+    else if (Kb <= 768) launch_gemv2_shape<EPI, RPW, 2, 3>(grid, lds, ksplit, x, Mb, K, Kb, W, N, ln_g, ln_b, ep, st, cb, m_base, wpk, wnt);
+    else launch_gemv2_shape<EPI, RPW, 3, 5>(grid, lds, ksplit, x, Mb, K, Kb, W, N, ln_g, ln_b, ep, st, cb, m_base, wpk, wnt);
 }
 
 static bool gemv2_ok(int epi, int Mb, int K, const float* ln_g, const EpiParams& ep) {
@@ -2234,7 +2242,7 @@ static int launch_gemv_large(const float* x, int Mb, int K, const void* W, int N
 template <int EPI>
 static int launch_gemv_epi(bool bf16, const float* x, int Mb, int K, const void* W, int N, const float* ln_g,
                            const float* ln_b, const EpiParams& ep, hipStream_t st, const CombineParams* comb,
-                           void* scratch, int wpk) {
+                           void* scratch, int wpk, bool wnt) {
     // (row-major weights: gemv_mt_kernel reads fragment-major ones only -- the groups of 16 rows below)
     if (bf16 && Mb > 16 && scratch && wpk) return launch_gemv_large<EPI>(x, Mb, K, W, N, ln_g, ln_b, ep, st, comb, scratch, wpk);
     if (bf16 && Mb > 16 && !x) return CW_ERR_INVALID;          // fragment-major activations have no other consumer
@@ -2245,8 +2253,8 @@ static int launch_gemv_epi(bool bf16, const float* x, int Mb, int K, const void*
             // L2 / Infinity Cache (the layer's weights were just streamed by the first group)
             for (int m_base = 0; m_base < Mb; m_base += 16) {
                 const int rows = Mb - m_base < 16 ? Mb - m_base : 16;
-                if (rows <= 8) launch_gemv2<EPI, 2>(x, rows, K, W, N, ln_g, ln_b, ep, st, comb, m_base, wpk);
-                else launch_gemv2<EPI, 4>(x, rows, K, W, N, ln_g, ln_b, ep, st, comb, m_base, wpk);
+                if (rows <= 8) launch_gemv2<EPI, 2>(x, rows, K, W, N, ln_g, ln_b, ep, st, comb, m_base, wpk, wnt);
+                else launch_gemv2<EPI, 4>(x, rows, K, W, N, ln_g, ln_b, ep, st, comb, m_base, wpk, wnt);
             }
             return CW_OK;
         }
@@ -2311,23 +2319,26 @@ int cw_launch_rows_combine(const float* part_o, int Mb, int K, const CombinePara
 }
 
 int cw_launch_gemv(bool bf16, int epi, const float* x, int Mb, int K, const void* W, int N, const float* ln_g,
-                   const float* ln_b, const EpiParams& ep, hipStream_t st, const CombineParams* comb, void* scratch, bool wpacked) {
+                   const float* ln_b, const EpiParams& ep, hipStream_t st, const CombineParams* comb, void* scratch, bool wpacked, bool wnt) {
     const int wpk = wpacked ? 1 : 0;
+    // wnt: non-temporal weight stream, for launches in which one block reads each weight tile: fragment-major weights and a single group
+    // of <= 16 rows (further groups re-read the tiles from L2 by design; so do the 17..64-row kernels' row tiles)
+    wnt = wnt && bf16 && wpacked && Mb <= 16;
     // 16-bit activation rows: only the K-split residual GEMV of <= 16 rows takes them (fc2 behind an EPI_GELU fc1)
     if (ep.x16 && !(bf16 && epi == EPI_RESID_F32 && !ln_g && !comb && Mb <= 16 && K > 1280 && ep.outf == ep.resid)) return CW_ERR_INVALID;
     if (Mb <= 0 || Mb > GV_MAXM || K % 128 != 0) return CW_ERR_INVALID;
     if (!x && !(bf16 && Mb > 16 && scratch)) return CW_ERR_INVALID;
     switch (epi) {
-        case EPI_GELU_F32: return launch_gemv_epi<EPI_GELU_F32>(bf16, x, Mb, K, W, N, ln_g, ln_b, ep, st, comb, scratch, wpk);
+        case EPI_GELU_F32: return launch_gemv_epi<EPI_GELU_F32>(bf16, x, Mb, K, W, N, ln_g, ln_b, ep, st, comb, scratch, wpk, wnt);
         case EPI_GELU:                                           // 16-bit row-major output [Mb][ldo] for a consumer launched with ep.x16
             if (!bf16 || Mb > 16) return CW_ERR_INVALID;
-            return launch_gemv_epi<EPI_GELU>(bf16, x, Mb, K, W, N, ln_g, ln_b, ep, st, comb, scratch, wpk);
+            return launch_gemv_epi<EPI_GELU>(bf16, x, Mb, K, W, N, ln_g, ln_b, ep, st, comb, scratch, wpk, wnt);
         case EPI_GELU_FRAG:
             if (!(bf16 && Mb > 16 && scratch)) return CW_ERR_INVALID;
             return launch_gemv_large<EPI_GELU_FRAG>(x, Mb, K, W, N, ln_g, ln_b, ep, st, comb, scratch, wpk);
-        case EPI_RESID_F32: return launch_gemv_epi<EPI_RESID_F32>(bf16, x, Mb, K, W, N, ln_g, ln_b, ep, st, comb, scratch, wpk);
-        case EPI_STORE_F32: return launch_gemv_epi<EPI_STORE_F32>(bf16, x, Mb, K, W, N, ln_g, ln_b, ep, st, comb, scratch, wpk);
-        case EPI_QKV_CACHE: return launch_gemv_epi<EPI_QKV_CACHE>(bf16, x, Mb, K, W, N, ln_g, ln_b, ep, st, comb, scratch, wpk);
+        case EPI_RESID_F32: return launch_gemv_epi<EPI_RESID_F32>(bf16, x, Mb, K, W, N, ln_g, ln_b, ep, st, comb, scratch, wpk, wnt);
+        case EPI_STORE_F32: return launch_gemv_epi<EPI_STORE_F32>(bf16, x, Mb, K, W, N, ln_g, ln_b, ep, st, comb, scratch, wpk, wnt);
+        case EPI_QKV_CACHE: return launch_gemv_epi<EPI_QKV_CACHE>(bf16, x, Mb, K, W, N, ln_g, ln_b, ep, st, comb, scratch, wpk, wnt);
         default: return CW_ERR_INVALID;
     }
 }

@@ -185,6 +185,7 @@ struct StackParams {
     StackSeg seg[3];
     float* zero;           // optional: the launch also clears zero_n4 float4 (a buffer a LATER launch accumulates into)
     int zero_n4;
+    int wnt;               // != 0: non-temporal weight stream where every tile has one reading block (fragment-major, one group of <= 16 rows)
 };
 // decfuse.hip: fc2 that finishes fc1 on load, mid = gelu(rstd (u - mean w1sum) + b1), (mean, rstd) = LayerNorm statistics of
 // the residual rows `xstat` (an untouched copy: the launch's own atomics are already modifying the stream x)
@@ -316,6 +317,7 @@ struct QkvSelfParams {
     int* err;                  // 0, or 1 + the decoder position of the first forward in which a wait gave up
     int Mb, D, H;
     int fail_pos;              // test hook: the item of layer 0 gives up at this position (-1: never)
+    int wnt;                   // the tiles' weight stream with non-temporal loads (each tile has one reading block)
 };
 
 // declayer.hip: LayerNorm + fc1 + GELU and fc2 + residual of rows <= 8 in ONE launch (fc1 blocks publish a flag each, fc2 blocks
@@ -400,7 +402,7 @@ struct ScoreStopPart {
     int cw_launch_quant_rows_fp8(const void* x, int rows, int K, void* out8, float* scale, hipStream_t st); \
     int cw_launch_gemm_fp8(int epi, const void* A8, int lda, const void* W8, int M, int N, int K, const float* sa, const float* sw, const EpiParams& ep, hipStream_t st); \
     int cw_launch_fold_layernorm(const float* Wf, int N, int K, const float* g, const float* beta, float scale, void* w_out, float* bias, hipStream_t st); \
-    int cw_launch_gemv(bool bf16, int epi, const float* x, int Mb, int K, const void* W, int N, const float* ln_g, const float* ln_b, const EpiParams& ep, hipStream_t st, const CombineParams* comb = nullptr, void* scratch = nullptr, bool wpacked = false); \
+    int cw_launch_gemv(bool bf16, int epi, const float* x, int Mb, int K, const void* W, int N, const float* ln_g, const float* ln_b, const EpiParams& ep, hipStream_t st, const CombineParams* comb = nullptr, void* scratch = nullptr, bool wpacked = false, bool wnt = false); \
     int cw_gemv_own_nt(int N); \
     int cw_launch_gemv_own(const void* xf, int Mb, int K, const void* W, int N, const EpiParams& ep, const float* cvec, void* xf_out, float* stats_out, hipStream_t st, bool wpacked); \
     int cw_launch_gemv_lna(const void* xf, int Mb, int K, const void* W, int N, const EpiParams& ep, const float* stats_in, int n_stats, const float* wsum, hipStream_t st, bool wpacked); \

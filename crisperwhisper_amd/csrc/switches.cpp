@@ -19,6 +19,7 @@ Switches read_switches() {
     s.dtw_block = flag("CW_DTW_BLOCK");
     s.fuse_mlp = flag("CW_FUSE_MLP");
     s.no_wpack = flag("CW_NO_WPACK");
+    s.no_wnt = flag("CW_NO_WNT");
     s.mlp_pair = flag("CW_MLP_PAIR");
     s.mlp_pair_fence = flag("CW_MLP_PAIR_FENCE");
     s.declayer = flag("CW_DECLAYER");
