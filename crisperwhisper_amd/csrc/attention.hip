@@ -871,8 +871,17 @@ __device__ inline float row_ror8_add(float v) { return v + dpp_mov<0x128, 0xf>(0
 // see the FUSED block below (every wave-level 16 B-per-lane load costs 16 clocks of the CU's address unit whatever it fetches:
 // all eight waves fetching the residual row and 8 columns of each constant measured +3 us per launch; wave 0 alone + a block
 // barrier +1.3 us).
+// Kernel arguments (DESIGN.md 6g''): eight plain values of 14 dwords lead -- the file's -amdgpu-kernarg-preload-count places them in
+// user SGPRs at dispatch -- and they are all the query-operand and K/V requests need, so the 64 KB stream of a block waits for no
+// scalar load of the (cold) kernarg lines; `p` arrives under the stream.  A by-value struct is never preloaded and ends the
+// preloaded run: keep the order and the 14 dwords (tests/test_kernarg_preload.py reads the descriptor).  cross_lead() fills them:
+//   Kp, Vp = p.K, p.V;  qa = p.qa (FUSED) or p.q;  pstats, qw, qbias = p.pstats, p.qw, p.qbias (FUSED; else unused)
+//   dims   = p.H | p.n_keys << 12 | (FUSED ? p.n_pstats : p.kv_div) << 24;   qb_off = p.qb - p.qa in floats (FUSED)
 template <typename T, int NQ, bool FUSED>
-__global__ __launch_bounds__(CROSS_THREADS) void attn_cross_split_kernel(CrossSplitParams p) {
+__global__ __launch_bounds__(CROSS_THREADS) void attn_cross_split_kernel(const void* __restrict__ Kp, const void* __restrict__ Vp,
+                                                                         const float* __restrict__ pstats, const float* __restrict__ qa,
+                                                                         const float* __restrict__ qw, const float* __restrict__ qbias,
+                                                                         unsigned dims, unsigned qb_off, CrossSplitParams p) {
     __shared__ float s_max[8 * NQ];
     __shared__ float red[8 * NQ * 64];
     __shared__ float red_l[8 * NQ];
@@ -883,13 +892,15 @@ __global__ __launch_bounds__(CROSS_THREADS) void attn_cross_split_kernel(CrossSp
     // kv_div times (26 us per layer at 8 items x 5 beams against 12.5 us at 8 rows), and a serial loop over the queries
     // inside one block was slower still (32 us: 3 barriers + reductions per query).
     const int h = blockIdx.x, b0 = blockIdx.y * NQ, sp = blockIdx.z;
-    const int bk = p.kv_div > 1 ? b0 / p.kv_div : b0;
-    const int per = (p.n_keys + ATT_NS - 1) / ATT_NS;
-    const int k_lo = sp * per, k_hi = min(p.n_keys, k_lo + per), nk = k_hi - k_lo;
+    const int H = (int)(dims & 0xfffu), n_keys = (int)((dims >> 12) & 0xfffu);
+    const int n_pstats = (int)(dims >> 24), kv_div = FUSED ? 1 : (int)(dims >> 24);   // the fused stage is launched at kv_div <= 1 only
+    const int bk = kv_div > 1 ? b0 / kv_div : b0;
+    const int per = (n_keys + ATT_NS - 1) / ATT_NS;
+    const int k_lo = sp * per, k_hi = min(n_keys, k_lo + per), nk = k_hi - k_lo;
     const int tid = threadIdx.x, lane = tid & 63, sub = tid & 7, grp = tid >> 3;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const T* Kh = (const T*)p.K + (((size_t)bk * p.H + h) * p.n_keys + k_lo) * 64 + sub * 8;
-    const T* Vh = (const T*)p.V + (((size_t)bk * p.H + h) * p.n_keys + k_lo) * 64 + sub * 8;
+    const T* Kh = (const T*)Kp + (((size_t)bk * H + h) * n_keys + k_lo) * 64 + sub * 8;
+    const T* Vh = (const T*)Vp + (((size_t)bk * H + h) * n_keys + k_lo) * 64 + sub * 8;
     constexpr int G = CROSS_THREADS / 8;                       // 64 key groups
 
     // FUSED: every wave finishes the query itself -- lane c takes column c of the head: two 8-byte loads of the per-block
@@ -900,13 +911,13 @@ __global__ __launch_bounds__(CROSS_THREADS) void attn_cross_split_kernel(CrossSp
     float2 pt0 = make_float2(0.f, 0.f), pt1 = pt0;
     float qa1 = 0.f, qb1 = 0.f, qw1 = 0.f, qc1 = 0.f;
     if (FUSED) {                                                // loads only: using a value in here makes hipcc wait before the K/V loads go out
-        const int Dm = p.H * 64;
-        const float* ps = p.pstats + (size_t)(b0 >> 4) * p.n_pstats * 32;   // one [tiles][16][2] plane per group of 16 rows (gemv_stack_kernel)
-        pt0 = *(const float2*)(ps + ((size_t)min(lane, p.n_pstats - 1) * 16 + (b0 & 15)) * 2);
-        pt1 = *(const float2*)(ps + ((size_t)min(lane + 64, p.n_pstats - 1) * 16 + (b0 & 15)) * 2);
+        const int Dm = H * 64;
+        const float* ps = pstats + (size_t)(b0 >> 4) * n_pstats * 32;   // one [tiles][16][2] plane per group of 16 rows (gemv_stack_kernel)
+        pt0 = *(const float2*)(ps + ((size_t)min(lane, n_pstats - 1) * 16 + (b0 & 15)) * 2);
+        pt1 = *(const float2*)(ps + ((size_t)min(lane + 64, n_pstats - 1) * 16 + (b0 & 15)) * 2);
         const size_t col = (size_t)h * 64 + lane;
-        qa1 = p.qa[(size_t)b0 * Dm + col]; qb1 = p.qb[(size_t)b0 * Dm + col];
-        qw1 = p.qw[col]; qc1 = p.qbias[col];
+        qa1 = qa[(size_t)b0 * Dm + col]; qb1 = (qa + qb_off)[(size_t)b0 * Dm + col];
+        qw1 = qw[col]; qc1 = qbias[col];
     }
     Raw8<T> kr[4], vr[4];
 #pragma unroll
@@ -923,9 +934,9 @@ __global__ __launch_bounds__(CROSS_THREADS) void attn_cross_split_kernel(CrossSp
     for (int q = 0; q < NQ; ++q) apos[q] = (slot >= 0) ? p.pos[b0 + q] : 0;
     float qv[NQ][8];
     if (FUSED) {
-        const float inv_d = 1.0f / (float)(p.H * 64);
-        const float ps1 = (lane < p.n_pstats ? pt0.x : 0.f) + (lane + 64 < p.n_pstats ? pt1.x : 0.f);
-        const float ps2 = (lane < p.n_pstats ? pt0.y : 0.f) + (lane + 64 < p.n_pstats ? pt1.y : 0.f);
+        const float inv_d = 1.0f / (float)(H * 64);
+        const float ps1 = (lane < n_pstats ? pt0.x : 0.f) + (lane + 64 < n_pstats ? pt1.x : 0.f);
+        const float ps2 = (lane < n_pstats ? pt0.y : 0.f) + (lane + 64 < n_pstats ? pt1.y : 0.f);
         const float mean = wave_sum(ps1) * inv_d;
         const float var = fmaxf(wave_sum(ps2) * inv_d - mean * mean, 0.f);
         const float rstd = 1.0f / sqrtf(var + 1e-5f);
@@ -938,7 +949,7 @@ __global__ __launch_bounds__(CROSS_THREADS) void attn_cross_split_kernel(CrossSp
         for (int e = 0; e < 8; ++e) qv[0][e] = sq[sub * 8 + e];
     } else {
 #pragma unroll
-        for (int q = 0; q < NQ; ++q) Row8<float>::ld(p.q + (size_t)(b0 + q) * p.H * 64 + h * 64 + sub * 8, qv[q]);
+        for (int q = 0; q < NQ; ++q) Row8<float>::ld(qa + (size_t)(b0 + q) * H * 64 + h * 64 + sub * 8, qv[q]);
     }
     float d[NQ][4], mx[NQ];
 #pragma unroll
@@ -991,7 +1002,7 @@ __global__ __launch_bounds__(CROSS_THREADS) void attn_cross_split_kernel(CrossSp
                 lsum[q] += pk;
                 if (slot >= 0) {                               // un-normalised; align_normalize_kernel finishes the row
                     const size_t rowi = ((size_t)(b0 + q) * p.n_align + slot) * p.align_rows + apos[q];
-                    p.align_out[rowi * p.n_keys + k_lo + k] = pk;
+                    p.align_out[rowi * n_keys + k_lo + k] = pk;
                 }
             }
             if (k < nk) {
@@ -1018,14 +1029,14 @@ __global__ __launch_bounds__(CROSS_THREADS) void attn_cross_split_kernel(CrossSp
         float r = 0.f;
 #pragma unroll
         for (int w = 0; w < 8; ++w) r += red[(w * NQ + q) * 64 + c];
-        p.part_o[((size_t)sp * p.B + b0 + q) * p.H * 64 + h * 64 + c] = r;
+        p.part_o[((size_t)sp * p.B + b0 + q) * H * 64 + h * 64 + c] = r;
     }
     if (tid >= 64 * NQ && tid < 64 * NQ + NQ) {
         const int q = tid - 64 * NQ;
         float l = 0.f;
 #pragma unroll
         for (int w = 0; w < 8; ++w) l += red_l[w * NQ + q];
-        float* ml = p.part_ml + (((size_t)(b0 + q) * p.H + h) * ATT_NS + sp) * 2;
+        float* ml = p.part_ml + (((size_t)(b0 + q) * H + h) * ATT_NS + sp) * 2;
         ml[0] = mx[q]; ml[1] = l;
         if (slot >= 0) {
             const size_t rowi = ((size_t)(b0 + q) * p.n_align + slot) * p.align_rows + apos[q];
@@ -1411,11 +1422,16 @@ __global__ __launch_bounds__(CROSS_THREADS) void attn_cross_mfma_kernel(CrossSpl
     }
 }
 
+// the leading (preloaded) arguments of attn_cross_split_kernel from the one struct the callers fill
+#define CW_CROSS_LEAD(p, FUSED)                                                                                                  \
+    (p).K, (p).V, (p).pstats, (FUSED) ? (p).qa : (p).q, (p).qw, (p).qbias,                                                       \
+        (unsigned)(p).H | (unsigned)(p).n_keys << 12 | (unsigned)((FUSED) ? (p).n_pstats : ((p).kv_div > 1 ? (p).kv_div : 1)) << 24, \
+        (unsigned)((FUSED) ? (p).qb - (p).qa : 0), (p)
 template <int NQ>
 static void launch_cross_split(bool bf16, const CrossSplitParams& p, hipStream_t st) {
     dim3 grid(p.H, p.B / NQ, ATT_NS);
-    if (bf16) hipLaunchKernelGGL((attn_cross_split_kernel<bf16_t, NQ, false>), grid, dim3(CROSS_THREADS), 0, st, p);
-    else hipLaunchKernelGGL((attn_cross_split_kernel<float, NQ, false>), grid, dim3(CROSS_THREADS), 0, st, p);
+    if (bf16) hipLaunchKernelGGL((attn_cross_split_kernel<bf16_t, NQ, false>), grid, dim3(CROSS_THREADS), 0, st, CW_CROSS_LEAD(p, false));
+    else hipLaunchKernelGGL((attn_cross_split_kernel<float, NQ, false>), grid, dim3(CROSS_THREADS), 0, st, CW_CROSS_LEAD(p, false));
 }
 
 static int g_cross_valu = 0;
@@ -1426,6 +1442,7 @@ int cw_launch_attn_cross_split(bool bf16, const CrossSplitParams& p, hipStream_t
     if ((p.n_keys + ATT_NS - 1) / ATT_NS > 4 * (CROSS_THREADS / 8) || CROSS_THREADS != 512) return CW_ERR_INVALID;
     // every key split must own at least one key (the kernels clamp their loads to the split's last key)
     if (p.n_keys < 1 || (ATT_NS - 1) * ((p.n_keys + ATT_NS - 1) / ATT_NS) >= p.n_keys) return CW_ERR_INVALID;
+    if (p.H < 1 || p.H > 0xfff || p.n_keys > 0xfff || p.kv_div > 0xff) return CW_ERR_INVALID;   // packed into one kernel argument (CW_CROSS_LEAD)
 #ifndef CW_EXPERIMENTS
     if (p.a_frag || p.a_out) return CW_ERR_INVALID;   // the full-key kernel is an A/B build (-DCW_EXPERIMENTS)
 #else
@@ -1453,6 +1470,8 @@ int cw_launch_attn_cross_split(bool bf16, const CrossSplitParams& p, hipStream_t
         }
 #endif
         if (!p.pstats || p.n_pstats < 1 || p.n_pstats > 128 || p.B > 64) return CW_ERR_INVALID;
+        // the kernel takes qb as a 32-bit offset from qa (its preloaded arguments are full): the two planes share an allocation
+        if (p.qb <= p.qa || p.qb - p.qa > 0x7fffffffll) return CW_ERR_INVALID;
         // A/B (CW_CROSS_LDS_PAD=bytes): unused dynamic LDS that limits how many blocks share a CU (the 960 blocks of a B = 8 launch
         // are all resident at once: their tails -- softmax, V pass, reductions -- then run together after the last byte landed)
         const int lds_pad = cw_sw::cw_switches().cross_lds_pad;
@@ -1460,7 +1479,7 @@ int cw_launch_attn_cross_split(bool bf16, const CrossSplitParams& p, hipStream_t
             static std::once_flag attr;
             std::call_once(attr, [] { (void)hipFuncSetAttribute((const void*)attn_cross_split_kernel<bf16_t, 1, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024); });
         }
-        hipLaunchKernelGGL((attn_cross_split_kernel<bf16_t, 1, true>), dim3(p.H, p.B, ATT_NS), dim3(CROSS_THREADS), (size_t)lds_pad, st, p);
+        hipLaunchKernelGGL((attn_cross_split_kernel<bf16_t, 1, true>), dim3(p.H, p.B, ATT_NS), dim3(CROSS_THREADS), (size_t)lds_pad, st, CW_CROSS_LEAD(p, true));
         return CW_OK;
     }
     const bool per_row = cw_sw::cw_switches().cross_per_row || g_cross_per_row;   // A/B: one block per row even under beam search

@@ -104,20 +104,25 @@ int cw_launch_fold_rowvec(const float* A, const float* s, float scale, const flo
 // Structure and MFMA fragment conventions are those of gemv2_bf16_kernel (gemm.hip): unconditional clamped loads, a row of
 // activations lives in one wave, weights go straight from HBM into B fragments, cross-wave reduction through LDS.
 // ---------------------------------------------------------------------------------------------------
-#define SEG_PICK(field) (si == 0 ? p.seg[0].field : (si == 1 ? p.seg[1].field : p.seg[2].field))
 
 // UNI (round 6): every segment streams NT tiles per block from fragment-major weights -- the shape of every launch of the default
 // engine.  The weight requests then sit under no branch (`t < snt` and `wpk` are run-time values otherwise: hipcc wraps each tile's
 // loads in a block-uniform branch and must answer the first wait behind them with vmcnt(0)).  Same arithmetic.
 // WNT (with UNI): the weight stream with non-temporal loads -- launches of one row group (gridDim.y == 1), where every tile is read by
 // exactly one block; the 16-row groups of 17..64 rows re-read the tiles from L2 (below) and keep the default policy.
+// Kernel arguments (DESIGN.md 6g''): five plain values of 7 dwords lead -- preloaded into user SGPRs at dispatch by the file's
+// -amdgpu-kernarg-preload-count -- and they decide the block's segment: W, the buffer to clear, dims = p.K | p.Mb << 16 | p.nseg << 24 |
+// (p.wpk != 0) << 26, blocks12 = seg[1].block0 | seg[2].block0 << 16.  The segment's fields then come as ONE batch of scalar loads at
+// a block-uniform offset into `p` (two kernarg lines, one wait) instead of a first round for the block starts and a second for the
+// picked segment; twelve pointers of three segments do not fit the 14 preloadable dwords, so the requests of this kernel still
+// wait for that one round.  A by-value struct is never preloaded and ends the preloaded run: keep the order.
 template <int RPW, int NSLOT, int PER_LANE, int NT, bool UNI = false, bool WNT = false>
-__global__ __launch_bounds__(256) void gemv_stack_kernel(StackParams p) {
+__global__ __launch_bounds__(256) void gemv_stack_kernel(const void* __restrict__ Wp, float* zero, int zero_n4, unsigned dims, unsigned blocks12, StackParams p) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_s[];
     // 17..64 rows (round 5): blockIdx.y = group of 16 rows; a group is a 16-row launch of its own over the same weights (its
     // blocks follow the first group's on the same XCD: 240 % 8 == 0, so the tile's weights come out of that L2 from the second
     // group on), per-row arithmetic unchanged -- rows m0 .. m0 + 15 of every operand, pstats one plane per group
-    const int K = p.K, m0 = blockIdx.y * 16, Mb = min(16, p.Mb - m0);
+    const int K = (int)(dims & 0xffffu), nseg = (int)((dims >> 24) & 3u), m0 = blockIdx.y * 16, Mb = min(16, (int)((dims >> 16) & 0xffu) - m0);
     const int xs_stride = K + 8;
     bf16_t* xs = (bf16_t*)smem_s;                               // [16][K+8]
     float* red = (float*)(smem_s + (size_t)16 * xs_stride * 2);  // [4 waves][NT][4][64]
@@ -126,20 +131,21 @@ __global__ __launch_bounds__(256) void gemv_stack_kernel(StackParams p) {
     const int l15 = lane & 15, g = lane >> 4;
     const int bid = blockIdx.x;
     int si = 0;                                                  // block-uniform segment
-    if (p.nseg > 1 && bid >= p.seg[1].block0) si = 1;
-    if (p.nseg > 2 && bid >= p.seg[2].block0) si = 2;
-    const float* __restrict__ x = SEG_PICK(x) + (size_t)m0 * K;
-    const float* __restrict__ bias = SEG_PICK(bias);
-    const int tile0 = SEG_PICK(tile0), n_tiles = SEG_PICK(n_tiles), block0 = SEG_PICK(block0), snt = SEG_PICK(nt);
+    if (nseg > 1 && bid >= (int)(blocks12 & 0xffffu)) si = 1;
+    if (nseg > 2 && bid >= (int)(blocks12 >> 16)) si = 2;
+    const StackSeg& sg = p.seg[si];                              // ONE batch of scalar loads at a block-uniform offset
+    const float* __restrict__ x = sg.x + (size_t)m0 * K;
+    const float* __restrict__ bias = sg.bias;
+    const int tile0 = sg.tile0, n_tiles = sg.n_tiles, block0 = sg.block0, snt = sg.nt;
     const int steps = K >> 7, nvec = K >> 2;
     const int tl0 = (bid - block0) * snt;                        // first tile of this block inside the segment
-    const bf16_t* __restrict__ W = (const bf16_t*)p.W;
+    const bf16_t* __restrict__ W = (const bf16_t*)Wp;
 
-    if (p.zero && blockIdx.y == 0) {                             // clear a buffer that a later launch accumulates into
+    if (zero && blockIdx.y == 0) {                               // clear a buffer that a later launch accumulates into
         const int zi = bid * 256 + tid;
-        if (zi < p.zero_n4) ((float4*)p.zero)[zi] = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (zi < zero_n4) ((float4*)zero)[zi] = make_float4(0.f, 0.f, 0.f, 0.f);
     }
-    const float* __restrict__ wsum = SEG_PICK(wsum);
+    const float* __restrict__ wsum = sg.wsum;
     float* smean = red + 4 * NT * 4 * 64;                       // [16] row means (segments with wsum)
     int nloc[NT];                                                // this lane's output column inside the segment (or -1)
     float bias_v[NT], wsum_v[NT];
@@ -157,7 +163,7 @@ __global__ __launch_bounds__(256) void gemv_stack_kernel(StackParams p) {
     // segments read an element of their own input instead: a load under a branch would make every later counted wait conservative)
     float resid_pre[NT];
     {
-        const float* rsd = SEG_PICK(resid);
+        const float* rsd = sg.resid;
         const int ldo_ = n_tiles * 16, mr = min(g * 4 + (tid >> 6), Mb - 1);
 #pragma unroll
         for (int t = 0; t < NT; ++t) {
@@ -190,7 +196,7 @@ __global__ __launch_bounds__(256) void gemv_stack_kernel(StackParams p) {
             for (int s = 0; s < NSLOT; ++s) {
                 int step = wave + 4 * s;
                 step = step < steps ? step : steps - 1;
-                const bool wpk = UNI || p.wpk;
+                const bool wpk = UNI || ((dims >> 26) & 1u);
                 const u32x4_t* wp = wpk ? (const u32x4_t*)(W + ((((size_t)(tile0 + tl) * (K >> 5)) + step * 4) * 64 + lane) * 8)
                                         : (const u32x4_t*)(wrow + step * 128);
                 const int sj = wpk ? 64 : 4;
@@ -267,14 +273,14 @@ __global__ __launch_bounds__(256) void gemv_stack_kernel(StackParams p) {
 #pragma unroll
         for (int r = 0; r < 4; ++r) red[((wave * NT + t) * 4 + r) * 64 + lane] = acc[t][r];
     __syncthreads();
-    const int epi = SEG_PICK(epi);
+    const int epi = sg.epi;
     const int ldo = n_tiles * 16;
-    float* __restrict__ out = SEG_PICK(out) + (size_t)m0 * ldo;
-    float* __restrict__ out2 = SEG_PICK(out2);
+    float* __restrict__ out = sg.out + (size_t)m0 * ldo;
+    float* __restrict__ out2 = sg.out2;
     if (out2) out2 += (size_t)m0 * ldo;
-    const float* __restrict__ resid = SEG_PICK(resid);
+    const float* __restrict__ resid = sg.resid;
     if (resid) resid += (size_t)m0 * ldo;
-    float* __restrict__ pstats = SEG_PICK(pstats);
+    float* __restrict__ pstats = sg.pstats;
     if (pstats) pstats += (size_t)blockIdx.y * ((n_tiles + snt - 1) / snt) * 32;   // [group][blocks of the segment][16][2]
     float ps1 = 0.f, ps2 = 0.f;                                 // this lane's share of (sum, sum of squares) of row g*4 + wave
 #pragma unroll
@@ -322,15 +328,20 @@ static int launch_stack_nt(StackParams& p, hipStream_t st) {
     if (p.zero && (long long)blocks * 256 < p.zero_n4) return CW_ERR_INVALID;
     const size_t lds = (size_t)16 * (p.K + 8) * 2 + (size_t)4 * NT * 4 * 64 * 4 + 16 * 4;
     const dim3 grid(blocks, (p.Mb + 15) / 16);                  // y: groups of 16 rows
-    if (p.K <= 256) hipLaunchKernelGGL((gemv_stack_kernel<RPW, 1, 1, NT>), grid, dim3(256), lds, st, p);
-    else if (p.K <= 768) hipLaunchKernelGGL((gemv_stack_kernel<RPW, 2, 3, NT>), grid, dim3(256), lds, st, p);
+    if (p.K > 0xffff || p.Mb > 0xff || blocks > 0xffff) return CW_ERR_INVALID;   // packed into gemv_stack_kernel's leading arguments
+#define CW_STACK_LEAD(p)                                                                                                     \
+    (p).W, (p).zero, (p).zero_n4, (unsigned)(p).K | (unsigned)(p).Mb << 16 | (unsigned)(p).nseg << 24 | ((p).wpk ? 1u << 26 : 0u), \
+        (unsigned)((p).nseg > 1 ? (p).seg[1].block0 : 0) | (unsigned)((p).nseg > 2 ? (p).seg[2].block0 : 0) << 16, (p)
+    if (p.K <= 256) hipLaunchKernelGGL((gemv_stack_kernel<RPW, 1, 1, NT>), grid, dim3(256), lds, st, CW_STACK_LEAD(p));
+    else if (p.K <= 768) hipLaunchKernelGGL((gemv_stack_kernel<RPW, 2, 3, NT>), grid, dim3(256), lds, st, CW_STACK_LEAD(p));
     else {
         bool uni = p.wpk != 0;
         for (int s = 0; s < p.nseg; ++s) uni = uni && p.seg[s].nt == NT;
-        if (uni && p.wnt && grid.y == 1) hipLaunchKernelGGL((gemv_stack_kernel<RPW, 3, 5, NT, true, true>), grid, dim3(256), lds, st, p);
-        else if (uni) hipLaunchKernelGGL((gemv_stack_kernel<RPW, 3, 5, NT, true>), grid, dim3(256), lds, st, p);
-        else hipLaunchKernelGGL((gemv_stack_kernel<RPW, 3, 5, NT>), grid, dim3(256), lds, st, p);
+        if (uni && p.wnt && grid.y == 1) hipLaunchKernelGGL((gemv_stack_kernel<RPW, 3, 5, NT, true, true>), grid, dim3(256), lds, st, CW_STACK_LEAD(p));
+        else if (uni) hipLaunchKernelGGL((gemv_stack_kernel<RPW, 3, 5, NT, true>), grid, dim3(256), lds, st, CW_STACK_LEAD(p));
+        else hipLaunchKernelGGL((gemv_stack_kernel<RPW, 3, 5, NT>), grid, dim3(256), lds, st, CW_STACK_LEAD(p));
     }
+#undef CW_STACK_LEAD
     return CW_OK;
 }
 

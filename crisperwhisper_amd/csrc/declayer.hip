@@ -514,10 +514,16 @@ __global__ __launch_bounds__(DL_THREADS) void dec_layer_a_kernel(DecLayerParams 
 #define QS_PRE 2
 
 // WNT: the tiles' weight stream with non-temporal loads (tile t has one reading block: block t).  The granule loads and stores keep their policy.
+// Kernel arguments (DESIGN.md 6g''): eight plain values of 14 dwords lead -- preloaded into user SGPRs at dispatch by the file's
+// -amdgpu-kernarg-preload-count -- and every request of the entry (cache row, bias, rows, weights, history) is addressed from them alone;
+// `p` (a by-value struct is never preloaded, and ends the preloaded run) arrives under those requests.  cw_launch_qkv_self fills both
+// from the one struct:  x, Wp, bias, sk, sv, pos = the fields of `p`;  dims = p.Mb | p.H << 8 | p.D << 16;  cap = p.cap
 template <int NSLOT, int PER_LANE, bool WNT>
-__global__ __launch_bounds__(QS_THREADS) void qkv_self_kernel(QkvSelfParams p) {
+__global__ __launch_bounds__(QS_THREADS) void qkv_self_kernel(const float* __restrict__ x, const void* __restrict__ Wp,
+                                                              const float* __restrict__ bias, void* sk, void* sv,
+                                                              const int* __restrict__ pos, unsigned dims, int cap, QkvSelfParams p) {
     extern __shared__ __attribute__((aligned(16))) unsigned char qsm[];
-    const int K = p.D, Mb = p.Mb, H = p.H, N = 3 * K, cap = p.cap;
+    const int Mb = (int)(dims & 0xffu), H = (int)((dims >> 8) & 0xffu), K = (int)(dims >> 16), N = 3 * K;
     const int xs_stride = K + 8;
     bf16_t* xs = (bf16_t*)qsm;                                       // [16][K+8]
     float* red = (float*)(qsm + (size_t)16 * xs_stride * 2);         // [4 waves][4][64]
@@ -529,7 +535,6 @@ __global__ __launch_bounds__(QS_THREADS) void qkv_self_kernel(QkvSelfParams p) {
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);       // 0..7
     const int l15 = lane & 15, g = lane >> 4;
     const int bid = blockIdx.x;
-    const unsigned tag = (p.epoch[0] << 6) | (unsigned)p.layer;
     const int n0 = bid * 16;
     const int steps = K >> 7, nvec = K >> 2;
     const int nn = n0 + l15, ncl = nn < N ? nn : N - 1;
@@ -540,16 +545,16 @@ __global__ __launch_bounds__(QS_THREADS) void qkv_self_kernel(QkvSelfParams p) {
     const bool has_item = bid < n_items;
     const int ih = has_item ? bid % H : 0, ib = has_item ? bid / H : 0;
     const int sub = tid & 7, grp = tid >> 3;
-    const bf16_t* Kh = (const bf16_t*)p.sk + ((size_t)ib * H + ih) * cap * 64;
-    const bf16_t* Vh = (const bf16_t*)p.sv + ((size_t)ib * H + ih) * cap * 64;
+    const bf16_t* Kh = (const bf16_t*)sk + ((size_t)ib * H + ih) * cap * 64;
+    const bf16_t* Vh = (const bf16_t*)sv + ((size_t)ib * H + ih) * cap * 64;
 
     float bias_v = 0.f;
     int pos_m = 0;                                                   // cache row of tile row m = g * 4 + wave (waves 0..3): FIRST in the queue --
     float4 xv[2][PER_LANE];                                          // vmcnt retires in order, and behind the history rows its wait would be vmcnt(0)
     dl_u32x4_t wq[NSLOT][4];
     if (wave < 4) {
-        pos_m = p.pos[min(g * 4 + wave, Mb - 1)];
-        bias_v = p.bias ? p.bias[ncl] : 0.f;
+        pos_m = pos[min(g * 4 + wave, Mb - 1)];
+        bias_v = bias ? bias[ncl] : 0.f;
 #pragma unroll
         for (int i = 0; i < 2; ++i) {
             int row = wave + 4 * i;
@@ -558,10 +563,10 @@ __global__ __launch_bounds__(QS_THREADS) void qkv_self_kernel(QkvSelfParams p) {
             for (int c = 0; c < PER_LANE; ++c) {
                 int v4 = lane + 64 * c;
                 v4 = v4 < nvec ? v4 : nvec - 1;
-                xv[i][c] = *(const float4*)(p.x + (size_t)row * K + v4 * 4);
+                xv[i][c] = *(const float4*)(x + (size_t)row * K + v4 * 4);
             }
         }
-        const bf16_t* __restrict__ W = (const bf16_t*)p.W;
+        const bf16_t* __restrict__ W = (const bf16_t*)Wp;
 #pragma unroll
         for (int s = 0; s < NSLOT; ++s) {
             int step = wave + 4 * s;
@@ -577,12 +582,13 @@ __global__ __launch_bounds__(QS_THREADS) void qkv_self_kernel(QkvSelfParams p) {
     for (int u = 0; u < QS_PRE; ++u) kpre[u].ld(Kh + (size_t)min(grp + u * QS_GROUPS, cap - 1) * 64 + sub * 8);
 #pragma unroll
     for (int u = 0; u < QS_PRE; ++u) vpre[u].ld(Vh + (size_t)min(grp + u * QS_GROUPS, cap - 1) * 64 + sub * 8);
-    const int n_keys = p.pos[ib] + 1;
+    const int n_keys = pos[ib] + 1;
     // (the position the give-up word needs, requested here with everything else: at its use it is a scalar round trip in front of wave
     // 4's first poll.  The epilogue's cache row pos_m is requested at the head of the queue above: left at its use it was a dependent
     // load + `s_waitcnt vmcnt(0)` in front of the granule stores, the hand-off every attention item waits for)
-    const int pos0 = p.pos[0];
+    const int pos0 = pos[0];
     __builtin_amdgcn_sched_barrier(0);
+    const unsigned tag = (p.epoch[0] << 6) | (unsigned)p.layer;       // from `p`: behind every request of the entry
     asm volatile("" : "+v"(pos_m));                                  // (pins the first use behind the fence: hipcc otherwise sign-extends it -- and waits for it -- in front of the history requests)
 
     // ---- tile: LayerNorm (gamma / beta folded into W / bias), rows -> 16 bit -> LDS, MFMA, cross-wave sum
@@ -650,7 +656,7 @@ __global__ __launch_bounds__(QS_THREADS) void qkv_self_kernel(QkvSelfParams p) {
                 if (p.q_plain) p.q_plain[(size_t)m * K + rc] = v;
             } else {
                 const int hh = rc >> 6, dd = rc & 63;
-                bf16_t* base = (bf16_t*)(which == 1 ? p.sk : p.sv);
+                bf16_t* base = (bf16_t*)(which == 1 ? sk : sv);
                 if (!(l15 & 1)) dl_gran_st(p.gkv + ((size_t)(which - 1) * 16 + m) * (K >> 1) + (rc >> 1), tag, h16 | (other << 16));   // the hand-off first
                 base[(((size_t)m * H + hh) * cap + pos_m) * 64 + dd] = (bf16_t)h16;
             }
@@ -858,7 +864,8 @@ int cw_launch_qkv_self(const QkvSelfParams& p, hipStream_t st) {
     do {                                                                                                                     \
         static std::once_flag attr;                                                                                          \
         std::call_once(attr, [] { (void)hipFuncSetAttribute((const void*)qkv_self_kernel<NS, PL, NTL>, hipFuncAttributeMaxDynamicSharedMemorySize, 100 * 1024); }); \
-        hipLaunchKernelGGL((qkv_self_kernel<NS, PL, NTL>), grid, dim3(QS_THREADS), lds, st, p);                              \
+        hipLaunchKernelGGL((qkv_self_kernel<NS, PL, NTL>), grid, dim3(QS_THREADS), lds, st, p.x, p.W, p.bias, p.sk, p.sv, p.pos, \
+                           (unsigned)p.Mb | (unsigned)p.H << 8 | (unsigned)D << 16, p.cap, p);                                \
     } while (0)
 #define QS_LAUNCH(NS, PL) do { if (p.wnt) QS_LAUNCH_P(NS, PL, true); else QS_LAUNCH_P(NS, PL, false); } while (0)
     if (D <= 256) QS_LAUNCH(1, 1);

@@ -273,26 +273,33 @@ __device__ inline float seq_bias_of(const int* __restrict__ tab, int tok, const 
         if (seq_bias_applies(tab, e, ids, t)) sum = __fadd_rn(sum, __int_as_float(tab[SB_VAL + e]));
     return sum;
 }
+// Kernel arguments of the two sampler launches (DESIGN.md 6g''): the pointers and integers their entry chains of dependent scalar loads
+// start from lead as plain values (14 dwords each, preloaded into user SGPRs at dispatch by the file's -amdgpu-kernarg-preload-count);
+// `p` (a by-value struct is never preloaded, and ends the preloaded run) is fetched under them.  launch_sample_t fills both from
+// the one struct.  SAMPLE_THREADS: the block of sample_kernel, a constant instead of a hidden-argument load.
+#define SAMPLE_THREADS 256
 template <bool TOPK, bool BIAS>
-__global__ __launch_bounds__(256) void sample_partial_kernel(SampleParams p, SamplePart* __restrict__ part) {
+__global__ __launch_bounds__(256) void sample_partial_kernel(const float* __restrict__ logits, const int* ids_all, const int* cfg, const int* pos,
+                                                             const int* last_ts_tok, const unsigned char* __restrict__ mask, int ldv, int ids_stride,
+                                                             SampleParams p, SamplePart* __restrict__ part) {
     __shared__ float s_f[64];
     __shared__ int s_i[64];
     const int b = blockIdx.x, sl = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const float* lg = p.logits + (size_t)b * p.ldv;
-    const int* ids = p.ids + (size_t)b * p.ids_stride;
-    const int n_prompt = p.cfg[0], min_new_tokens = p.cfg[1];
-    const int t = p.pos[b] + 1, tb = p.timestamp_begin;
+    const float* lg = logits + (size_t)b * ldv;
+    const int* ids = ids_all + (size_t)b * ids_stride;
+    const int n_prompt = cfg[0], min_new_tokens = cfg[1];
+    const int t = pos[b] + 1, tb = p.timestamp_begin;
     const int n_gen = t - n_prompt;
     const bool last_ts = n_gen >= 1 && ids[t - 1] >= tb;
     const bool penult_ts = n_gen < 2 || ids[t - 2] >= tb;
-    const int last_tok = p.last_ts_tok[b];
+    const int last_tok = last_ts_tok[b];
     const int ts_floor = (last_tok >= 0) ? ((last_ts && !penult_ts) ? last_tok : last_tok + 1) : tb;
     const bool at_begin = (n_gen == 0);
     const int ts_cap = (at_begin && p.max_initial_timestamp_index >= 0) ? tb + p.max_initial_timestamp_index : 0x7fffffff;
-    const int per4 = ((p.ldv >> 2) + SAMPLE_NS - 1) / SAMPLE_NS;           // float4 groups per slice
-    const int lo4 = sl * per4, hi4 = min(p.ldv >> 2, lo4 + per4);
+    const int per4 = ((ldv >> 2) + SAMPLE_NS - 1) / SAMPLE_NS;           // float4 groups per slice
+    const int lo4 = sl * per4, hi4 = min(ldv >> 2, lo4 + per4);
     const float4* lg4 = (const float4*)lg;
-    const uchar4* mk4 = (const uchar4*)p.mask;
+    const uchar4* mk4 = (const uchar4*)mask;
     ArgPair bt = {-INFINITY, 0x7fffffff}, bs = {-INFINITY, 0x7fffffff};
     ArgPair pt = {-INFINITY, 0x7fffffff}, ps = {-INFINITY, 0x7fffffff};    // sampling: the same over the perturbed scores
     const float temp = p.samp ? __uint_as_float(p.samp[0]) : 0.f;          // block-uniform; 0 = greedy
@@ -466,32 +473,33 @@ __global__ __launch_bounds__(256) void sample_partial_kernel(SampleParams p, Sam
 }
 
 template <typename T, bool TOPK, bool BIAS>
-__global__ __launch_bounds__(1024) void sample_kernel(SampleParams p) {
+__global__ __launch_bounds__(1024) void sample_kernel(int* ids_all, const int* cfg, int* pos, int* finished, int* last_ts_tok,
+                                                       const void* partials, int ids_stride, int timestamp_begin, SampleParams p) {
     __shared__ float s_f[64];
     __shared__ int s_i[64];
     __shared__ int s_tok;
-    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, nw = blockDim.x >> 6;
+    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, nw = SAMPLE_THREADS >> 6;
     const float* lg = p.logits + (size_t)b * p.ldv;
-    int* ids = p.ids + (size_t)b * p.ids_stride;
-    const int n_prompt = p.cfg[0], min_new_tokens = p.cfg[1], max_length = p.cfg[2], use_forced = p.cfg[3];
-    const int t = p.pos[b] + 1, tb = p.timestamp_begin;
+    int* ids = ids_all + (size_t)b * ids_stride;
+    const int n_prompt = cfg[0], min_new_tokens = cfg[1], max_length = cfg[2], use_forced = cfg[3];
+    const int t = pos[b] + 1, tb = timestamp_begin;
     const int n_gen = t - n_prompt;
 
-    const int fin_in = p.finished[b];                  // 2: a row the caller masked out (cw_decode_rows): its ids stay as they are
+    const int fin_in = finished[b];                  // 2: a row the caller masked out (cw_decode_rows): its ids stay as they are
     const bool was_finished = fin_in != 0;
-    int forced = (p.forced && use_forced) ? p.forced[(size_t)b * p.ids_stride + t] : -1;
+    int forced = (p.forced && use_forced) ? p.forced[(size_t)b * ids_stride + t] : -1;
 
     // timestamp grammar state from the generated suffix
     const bool last_ts = n_gen >= 1 && ids[t - 1] >= tb;
     const bool penult_ts = n_gen < 2 || ids[t - 2] >= tb;
-    const int last_tok = p.last_ts_tok[b];
+    const int last_tok = last_ts_tok[b];
     const int ts_floor = (last_tok >= 0) ? ((last_ts && !penult_ts) ? last_tok : last_tok + 1) : tb;
     const bool at_begin = (n_gen == 0);
     const int ts_cap = (at_begin && p.max_initial_timestamp_index >= 0) ? tb + p.max_initial_timestamp_index
                                                                          : 0x7fffffff;
     // stage 2: merge the SAMPLE_NS slice records of this row (sample_partial_kernel)
     ArgPair bt = {-INFINITY, 0x7fffffff}, bs = {-INFINITY, 0x7fffffff};
-    const SamplePart* pr = (const SamplePart*)p.partials + (size_t)b * SAMPLE_NS;
+    const SamplePart* pr = (const SamplePart*)partials + (size_t)b * SAMPLE_NS;
     for (int i = 0; i < SAMPLE_NS; ++i) {
         bt = arg_better(bt, ArgPair{pr[i].bt_v, pr[i].bt_i});
         bs = arg_better(bs, ArgPair{pr[i].bs_v, pr[i].bs_i});
@@ -527,7 +535,7 @@ __global__ __launch_bounds__(1024) void sample_kernel(SampleParams p) {
                 prev = c;
             }
             if (lane < k) {
-                const size_t o = ((size_t)b * p.ids_stride + t) * CW_TOP_LOGPROBS_MAX + lane;
+                const size_t o = ((size_t)b * ids_stride + t) * CW_TOP_LOGPROBS_MAX + lane;
                 const bool ok = mine.v > -INFINITY;                           // fewer than lane + 1 candidates in the row
                 p.top_id[o] = ok ? mine.i : -1;
                 p.top_lp[o] = ok ? mine.v - norm : NAN;
@@ -552,7 +560,7 @@ __global__ __launch_bounds__(1024) void sample_kernel(SampleParams p) {
         // no finite candidate at all (every token masked, or NaN logits): torch.argmax of an all -inf row is index 0;
         // never hand an out-of-range id to the next step's embedding gather
         if (!(M > -INFINITY) || choice < 0 || choice >= p.V) choice = 0;
-        if (p.argmax_trace) p.argmax_trace[(size_t)b * p.ids_stride + t] = choice;
+        if (p.argmax_trace) p.argmax_trace[(size_t)b * ids_stride + t] = choice;
         int tok = (forced >= 0) ? forced : choice;
         if (p.lp_sum && !was_finished && n_gen >= 0) {
             // log_softmax of the PROCESSED scores at the chosen token (generation_whisper.py:1967-1971): suppressed tokens
@@ -575,16 +583,16 @@ __global__ __launch_bounds__(1024) void sample_kernel(SampleParams p) {
             for (int i = 0; i < SAMPLE_NS; ++i) Mr = fmaxf(Mr, pr[i].pad[1]);
             for (int i = 0; i < SAMPLE_NS; ++i)
                 if (pr[i].pad[1] > -INFINITY) Sr += pr[i].pad[2] * expf(pr[i].pad[1] - Mr);
-            p.tok_lp[(size_t)b * p.ids_stride + t] = lg[tok] - (Mr + logf(Sr));
+            p.tok_lp[(size_t)b * ids_stride + t] = lg[tok] - (Mr + logf(Sr));
         }
         if (was_finished) tok = p.pad;                                  // utils.py:2928-2929
         if (fin_in != 2) ids[t] = tok;
-        if (tok >= tb && n_gen >= 0) p.last_ts_tok[b] = tok;
+        if (tok >= tb && n_gen >= 0) last_ts_tok[b] = tok;
         int fin = was_finished ? fin_in : ((n_gen >= 0 && tok == p.eos) || (t + 1 >= max_length));
-        p.finished[b] = fin;
+        finished[b] = fin;
         if (!fin) atomicAdd(p.n_unfinished, 1);
         s_tok = tok;
-        p.pos[b] = t;                                                   // next decoder input position
+        pos[b] = t;                                                   // next decoder input position
     }
     __syncthreads();
     // embedding for the next decoder step: token at sequence index t is fed at position t
@@ -592,7 +600,7 @@ __global__ __launch_bounds__(1024) void sample_kernel(SampleParams p) {
     if (p.x_out && t < max_length) {
         const T* e = (const T*)p.embed + (size_t)tok * p.d;
         const float* pe = p.pos_embed + (size_t)t * p.d;
-        for (int k = tid; k < p.d; k += blockDim.x) {
+        for (int k = tid; k < p.d; k += SAMPLE_THREADS) {
             const float v = Act<T>::ld(e + k) + pe[k];
             p.x_out[(size_t)b * p.d + k] = sizeof(T) == 2 ? resid_grid(v) : v;
         }
@@ -944,11 +952,14 @@ int cw_launch_align_gather(const float* align, const int* row_of_pos, int n_item
 
 template <bool TOPK, bool BIAS>
 static void launch_sample_t(const SampleParams& p, hipStream_t st) {
-    hipLaunchKernelGGL((sample_partial_kernel<TOPK, BIAS>), dim3(p.B, SAMPLE_NS), dim3(256), 0, st, p, (SamplePart*)p.partials);
+    hipLaunchKernelGGL((sample_partial_kernel<TOPK, BIAS>), dim3(p.B, SAMPLE_NS), dim3(256), 0, st, p.logits, (const int*)p.ids, p.cfg,
+                       (const int*)p.pos, (const int*)p.last_ts_tok, p.mask, p.ldv, p.ids_stride, p, (SamplePart*)p.partials);
     if (p.embed_bf16)
-        hipLaunchKernelGGL((sample_kernel<bf16_t, TOPK, BIAS>), dim3(p.B), dim3(256), 0, st, p);
+        hipLaunchKernelGGL((sample_kernel<bf16_t, TOPK, BIAS>), dim3(p.B), dim3(SAMPLE_THREADS), 0, st, p.ids, p.cfg, p.pos, p.finished,
+                           p.last_ts_tok, p.partials, p.ids_stride, p.timestamp_begin, p);
     else
-        hipLaunchKernelGGL((sample_kernel<float, TOPK, BIAS>), dim3(p.B), dim3(256), 0, st, p);
+        hipLaunchKernelGGL((sample_kernel<float, TOPK, BIAS>), dim3(p.B), dim3(SAMPLE_THREADS), 0, st, p.ids, p.cfg, p.pos, p.finished,
+                           p.last_ts_tok, p.partials, p.ids_stride, p.timestamp_begin, p);
 }
 int cw_launch_sample(const SampleParams& p, hipStream_t st) {
     static_assert(SAMPLE_NS == 16 && SB_OFF > SB_SLICE + SAMPLE_NS, "the sequence_bias table holds one range per sampler slice");

@@ -628,7 +628,7 @@ static int create_impl(cw_ctx* c) {
     CWCHK(c, dmalloc(c, &c->dq, (size_t)Bm * D * 4)); CWCHK(c, dmalloc(c, &c->dattn, (size_t)Bm * D * 4));
     CWCHK(c, dmalloc(c, &c->dmid, (size_t)Bm * F * 4));
     CWCHK(c, dmalloc(c, &c->dx1, (size_t)Bm * D * 4)); CWCHK(c, dmalloc(c, &c->dx2c, (size_t)Bm * D * 4));
-    CWCHK(c, dmalloc(c, &c->d_qa, (size_t)Bm * D * 4)); CWCHK(c, dmalloc(c, &c->d_qb, (size_t)Bm * D * 4));
+    CWCHK(c, dmalloc(c, &c->d_qa, (size_t)2 * Bm * D * 4)); c->d_qb = c->d_qa + (size_t)Bm * D;   // one allocation: the cross-attention kernel takes qb as a 32-bit offset from qa
     CWCHK(c, dmalloc(c, &c->d_u1, (size_t)Bm * F * 4)); CWCHK(c, dmalloc(c, &c->d_pstats, (size_t)128 * 64 * 2 * 4));   // [group of 16 rows 4][tile <= 128][16][2]
     CWCHK(c, dmalloc(c, &c->d_rstats, (size_t)((D > F ? D : F) / 16 + 1) * 64 * 2 * 4));
     CWCHK(c, dmalloc(c, &c->d_bar, 64 * 4));
@@ -4451,7 +4451,7 @@ int32_t cw_test_cross_attention_fused(cw_ctx* c, int32_t B, int32_t H, int32_t S
     void *dk = nullptr, *dv = nullptr, *dk8 = nullptr, *dv8 = nullptr;
     int *dslot = nullptr, *dpos = nullptr;
     DevScope mem;
-    HIPCHK(c, mem.get(&dqa, (size_t)B * D * 4)); HIPCHK(c, mem.get(&dqb, (size_t)B * D * 4));
+    HIPCHK(c, mem.get(&dqa, (size_t)2 * B * D * 4)); dqb = dqa + (size_t)B * D;   // one allocation, as the engine's: the kernel takes qb as an offset from qa
     HIPCHK(c, mem.get(&dqw, (size_t)D * 4)); HIPCHK(c, mem.get(&dqc, (size_t)D * 4));
     HIPCHK(c, mem.get(&dps, (nps + 128 * 32) * 4));   // 128 further plane slots of NaN: what a read beyond n_pstats in the last group meets
     HIPCHK(c, hipMemset(dps + nps, 0xFF, (size_t)128 * 32 * 4));

@@ -1167,14 +1167,24 @@ extern "C" int cw_debug_phases(unsigned long long* out) {
 template <int EPI, int RPW, bool ATOMIC, bool COMBINE, int NSLOT, int PER_LANE, int NT = 1 /* 16-column tiles per block */,
           bool X16 = false /* activation rows arrive in the engine's 16-bit type (no LayerNorm, no combine) */,
           bool WNT = false /* weight stream with non-temporal loads: launches where every weight tile has ONE reading block (see the loads) */>
-__global__ __launch_bounds__(256) void gemv2_bf16_kernel(const float* __restrict__ x, int Mb, int K, int Kb,
-                                                         const bf16_t* __restrict__ W, int N,
+// Kernel arguments (DESIGN.md 6g''): the first ten are plain values of 14 dwords, which the file's -amdgpu-kernarg-preload-count places
+// in user SGPRs at dispatch -- everything the bias, activation and weight requests need, so none of them waits for a scalar load of
+// the (cold) kernarg lines; the structs behind them arrive under those requests.  A by-value struct is never preloaded and ends the
+// preloaded run: keep the order, and keep the leading arguments at <= 14 dwords (tests/test_kernarg_preload.py reads the descriptor).
+//   bias  = ep.bias;  aux = ep.row_pos (EPI_QKV_CACHE) or cb.part_ml (COMBINE);  cb_H, cb_plane = cb.H, cb.plane
+//   rows  = Mb | m_base << 8 | gridDim.z << 16 | wpk << 24 | (ln_g != null) << 25 | (ln_b != null) << 26   (gemv2_rows)
+__global__ __launch_bounds__(256) void gemv2_bf16_kernel(const float* __restrict__ x, const bf16_t* __restrict__ W,
+                                                         const float* __restrict__ bias, const void* __restrict__ aux,
+                                                         int K, int Kb, int N, unsigned rows, int cb_H, int cb_plane,
                                                          const float* __restrict__ ln_g,
                                                          const float* __restrict__ ln_b, EpiParams ep,
-                                                         CombineParams cb, int m_base, int wpk) {
+                                                         CombineParams cb) {
+    static_assert(!(COMBINE && EPI == EPI_QKV_CACHE), "aux is either the cache rows or the attention partials' (m, l)");
     extern __shared__ __attribute__((aligned(16))) unsigned char smem2[];
-    if (gridDim.z > 1) {   // row groups inside one launch (the combining out-projection): block z takes rows z * rpb .. of the launch's Mb
-        const int rpb = (Mb + (int)gridDim.z - 1) / (int)gridDim.z;
+    int Mb = (int)(rows & 0xffu), m_base = (int)((rows >> 8) & 0xffu);
+    const int grid_z = (int)((rows >> 16) & 0xffu), wpk = (int)((rows >> 24) & 1u);
+    if (grid_z > 1) {   // row groups inside one launch (the combining out-projection): block z takes rows z * rpb .. of the launch's Mb
+        const int rpb = (Mb + grid_z - 1) / grid_z;
         const int mb0 = (int)blockIdx.z * rpb;
         m_base += mb0;
         Mb = min(rpb, Mb - mb0);
@@ -1195,16 +1205,16 @@ __global__ __launch_bounds__(256) void gemv2_bf16_kernel(const float* __restrict
 #pragma unroll
     for (int t = 0; t < NT; ++t) { nn[t] = n0 + t * 16 + l15; ncl[t] = nn[t] < N ? nn[t] : N - 1; }
     const int nvec = Kb >> 2;                                 // float4 per row slice
-    const bool has_ln = ln_g != nullptr;
-    const bool ln_affine = ln_b != nullptr;                   // false: gamma / beta were folded into W / bias at load time
+    const bool has_ln = (rows >> 25) & 1u;
+    const bool ln_affine = (rows >> 26) & 1u;                 // false: gamma / beta were folded into W / bias at load time
 
     PH(0);                                                    // kernel entry
     float bias_v[NT];
 #pragma unroll
-    for (int t = 0; t < NT; ++t) bias_v[t] = ep.bias ? ep.bias[ncl[t]] : 0.f;
+    for (int t = 0; t < NT; ++t) bias_v[t] = bias ? bias[ncl[t]] : 0.f;
     // EPI_QKV_CACHE: the cache row of the batch row this thread stores (m = g * 4 + wave), requested at the head of the queue
     int rpos_pre = 0;
-    if (EPI == EPI_QKV_CACHE) rpos_pre = ep.row_pos[m_base + min(g * 4 + wave, Mb - 1)];
+    if (EPI == EPI_QKV_CACHE) rpos_pre = ((const int*)aux)[m_base + min(g * 4 + wave, Mb - 1)];
 
     // activation rows -> registers
     constexpr int PER8 = (PER_LANE + 1) / 2;                  // X16: 8 elements per 16-byte load
@@ -1239,14 +1249,14 @@ __global__ __launch_bounds__(256) void gemv2_bf16_kernel(const float* __restrict
                 xv[i][c] = *(const float4*)(x + off);
             } else {   // x = sum_s w_s o_s over the ATT_NS attention partials of head (k / 64)
                 const int head = (kbase + v4 * 4) >> 6;
-                const float* ml = cb.part_ml + ((size_t)(m_base + row) * cb.H + head) * ATT_NS * 2;
+                const float* ml = (const float*)aux + ((size_t)(m_base + row) * cb_H + head) * ATT_NS * 2;
                 float m[ATT_NS], l[ATT_NS];
                 float4 o[ATT_NS];
 #pragma unroll
                 for (int sI = 0; sI < ATT_NS; ++sI) {
                     const float2 t = *(const float2*)(ml + 2 * sI);
                     m[sI] = t.x; l[sI] = t.y;
-                    o[sI] = *(const float4*)(x + (size_t)sI * cb.plane + off);
+                    o[sI] = *(const float4*)(x + (size_t)sI * cb_plane + off);
                 }
                 float M = m[0];
 #pragma unroll
@@ -1421,9 +1431,12 @@ __global__ __launch_bounds__(256) void gemv2_bf16_kernel(const float* __restrict
 // 0..3): bit-identical logits.
 // ---------------------------------------------------------------------------------------------------
 template <int RPW, int NSLOT, int PER_LANE>
-__global__ __launch_bounds__(256) void gemv_loop_kernel(const float* __restrict__ x, int Mb, int K, const bf16_t* __restrict__ W, int N,
+// Arguments: the pointers and integers of the first requests and of the tile walk lead (14 dwords, preloaded into user SGPRs:
+// see gemv2_bf16_kernel); grid_x = gridDim.x, which would otherwise be a load of a hidden argument
+__global__ __launch_bounds__(256) void gemv_loop_kernel(const float* __restrict__ x, const bf16_t* __restrict__ W,
                                                         const float* __restrict__ ln_g, const float* __restrict__ ln_b,
-                                                        const float* __restrict__ bias, float* __restrict__ out, int ldo) {
+                                                        const float* __restrict__ bias, int Mb, int K, int N, int grid_x,
+                                                        float* __restrict__ out, int ldo) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem3[];
     const int xs_stride = K + 8;
     bf16_t* xs = (bf16_t*)smem3;                               // [16][K+8]
@@ -1506,8 +1519,8 @@ __global__ __launch_bounds__(256) void gemv_loop_kernel(const float* __restrict_
     }
     __syncthreads();
     int buf = 0;
-    for (; tile < ntiles; tile += gridDim.x) {
-        const int nxt = tile + gridDim.x;
+    for (; tile < ntiles; tile += grid_x) {
+        const int nxt = tile + grid_x;
         if (nxt < ntiles) load_tile(nxt, wn);                   // the next tile's stream runs under this tile's MFMAs and exchange
         f32x4_t acc = (f32x4_t){0.f, 0.f, 0.f, 0.f};
 #pragma unroll
@@ -2013,14 +2026,19 @@ int cw_gemv_kc(int Mb, int K) {
 // wnt: the launches below stream their weights with non-temporal loads (cw_launch_gemv sets it only for fragment-major weights and one
 // group of <= 16 rows: every tile is then read by exactly one block of the launch).  The combining out-projection (row groups re-read a
 // tile from L2) and the three-tile fallback of the logits keep the default policy.
+// gemv2_bf16_kernel's argument list from the launchers' locals: the 14 preloaded dwords first (see the kernel), one source for both copies
+static inline unsigned gemv2_rows(int Mb, int m_base, unsigned grid_z, int wpk, const float* ln_g, const float* ln_b) {
+    return (unsigned)Mb | (unsigned)m_base << 8 | grid_z << 16 | (wpk ? 1u << 24 : 0u) | (ln_g ? 1u << 25 : 0u) | (ln_b ? 1u << 26 : 0u);
+}
+#define CW_GEMV2_ARGS(GRID, KB)                                                                                                        \
+    x, (const bf16_t*)W, ep.bias, (EPI == EPI_QKV_CACHE ? (const void*)ep.row_pos : (const void*)cb.part_ml), K, KB, N,                \
+        gemv2_rows(Mb, m_base, dim3(GRID).z, wpk, ln_g, ln_b), cb.H, cb.plane, ln_g, ln_b, ep, cb
 #define CW_GEMV2_LAUNCH(GRID, LDS, ...)                                                                                               \
     do {                                                                                                                               \
         if (wnt)                                                                                                                       \
-            hipLaunchKernelGGL((gemv2_bf16_kernel<__VA_ARGS__, true>), GRID, dim3(256), LDS, st, x, Mb, K, Kb, (const bf16_t*)W, N,    \
-                               ln_g, ln_b, ep, cb, m_base, wpk);                                                                       \
+            hipLaunchKernelGGL((gemv2_bf16_kernel<__VA_ARGS__, true>), GRID, dim3(256), LDS, st, CW_GEMV2_ARGS(GRID, Kb));             \
         else                                                                                                                           \
-            hipLaunchKernelGGL((gemv2_bf16_kernel<__VA_ARGS__, false>), GRID, dim3(256), LDS, st, x, Mb, K, Kb, (const bf16_t*)W, N,   \
-                               ln_g, ln_b, ep, cb, m_base, wpk);                                                                       \
+            hipLaunchKernelGGL((gemv2_bf16_kernel<__VA_ARGS__, false>), GRID, dim3(256), LDS, st, CW_GEMV2_ARGS(GRID, Kb));            \
     } while (0)
 template <int EPI, int RPW, int NSLOT, int PER_LANE>
 static void launch_gemv2_shape(dim3 grid, size_t lds, int ksplit, const float* x, int Mb, int K, int Kb, const void* W,
@@ -2029,10 +2047,10 @@ static void launch_gemv2_shape(dim3 grid, size_t lds, int ksplit, const float* x
     if (EPI == EPI_RESID_F32 && cb.part_ml) {
         if (ksplit > 1)
             hipLaunchKernelGGL((gemv2_bf16_kernel<EPI_RESID_F32, RPW, true, true, NSLOT, PER_LANE>), grid, dim3(256), lds, st,
-                               x, Mb, K, Kb, (const bf16_t*)W, N, ln_g, ln_b, ep, cb, m_base, wpk);
+                               CW_GEMV2_ARGS(grid, Kb));
         else
             hipLaunchKernelGGL((gemv2_bf16_kernel<EPI_RESID_F32, RPW, false, true, NSLOT, PER_LANE>), grid, dim3(256), lds, st,
-                               x, Mb, K, Kb, (const bf16_t*)W, N, ln_g, ln_b, ep, cb, m_base, wpk);
+                               CW_GEMV2_ARGS(grid, Kb));
     } else if (EPI == EPI_RESID_F32 && ksplit > 1) {
         if (N % 32 == 0 && (int)(grid.x * grid.y) > 256 && (int)(grid.x * grid.y) / 2 >= 128) {   // fc2: (80, 4) -> (40, 4)
             dim3 g2(grid.x / 2, grid.y);
@@ -2054,12 +2072,12 @@ static void launch_gemv2_shape(dim3 grid, size_t lds, int ksplit, const float* x
             const int cap = cw_sw::cw_switches().gemv_loop_cap;   // blocks in the grid per round of tiles (2 per CU measured best: 24.8 us; 3 per CU 25.9)
             const int tiles = (int)grid.x, rounds = (tiles + cap - 1) / cap, gsz = (tiles + rounds - 1) / rounds;
             const size_t lds3 = (size_t)16 * (K + 8) * 2 + 2 * 4 * 4 * 64 * 4;
-            hipLaunchKernelGGL((gemv_loop_kernel<RPW, NSLOT, PER_LANE>), dim3(gsz), dim3(256), lds3, st, x, Mb, K, (const bf16_t*)W, N, ln_g, ln_b,
-                               ep.bias, ep.outf, ep.ldo);
+            hipLaunchKernelGGL((gemv_loop_kernel<RPW, NSLOT, PER_LANE>), dim3(gsz), dim3(256), lds3, st, x, (const bf16_t*)W, ln_g, ln_b, ep.bias,
+                               Mb, K, N, gsz, ep.outf, ep.ldo);
         } else if (ln_g && ksplit == 1 && grid.x >= 1024) {
             dim3 g3((grid.x + 2) / 3, 1);
             hipLaunchKernelGGL((gemv2_bf16_kernel<EPI, RPW, false, false, NSLOT, PER_LANE, 3>), g3, dim3(256), lds + 2 * 4 * 4 * 64 * 4, st,
-                               x, Mb, K, Kb, (const bf16_t*)W, N, ln_g, ln_b, ep, cb, m_base, wpk);
+                               CW_GEMV2_ARGS(g3, Kb));
         } else if (ln_g && ksplit == 1 && grid.x > 256 && grid.x / 2 >= 128) {
             dim3 g2((grid.x + 1) / 2, 1);
             CW_GEMV2_LAUNCH(g2, lds + 4 * 4 * 64 * 4, EPI, RPW, false, false, NSLOT, PER_LANE, 2, false);
@@ -2098,7 +2116,7 @@ static void launch_gemv2(const float* x, int Mb, int K, const void* W, int N, co
         const int ks = K / 256;
         const size_t lds2 = (size_t)16 * (256 + 8) * 2 + 2 * 4 * 4 * 64 * 4;
         hipLaunchKernelGGL((gemv2_bf16_kernel<EPI_RESID_F32, RPW, true, true, 1, 1, 2>), dim3(N / 32, ks), dim3(256), lds2, st,
-                           x, Mb, K, 256, (const bf16_t*)W, N, ln_g, ln_b, ep, cb, m_base, wpk);
+                               CW_GEMV2_ARGS(dim3(N / 32, ks), 256));
         return;
     }
     const int Kb = K / ksplit;
@@ -2118,13 +2136,13 @@ static void launch_gemv2(const float* x, int Mb, int K, const void* W, int N, co
         // (320 blocks: 64 CUs would take two); CW_COMB_G4=1 keeps the four groups (A/B)
         if (RPW == 4 && Mb > 12 && (Mb + G - 1) / G <= 8 && !cw_sw::cw_switches().comb_g4) {
             hipLaunchKernelGGL((gemv2_bf16_kernel<EPI_RESID_F32, 2, true, true, 2, 3, 2>), dim3(N / 32, ksplit, G), dim3(256), lds + 4 * 4 * 64 * 4, st,
-                               x, Mb, K, Kb, (const bf16_t*)W, N, ln_g, ln_b, ep, cb, m_base, wpk);
+                               CW_GEMV2_ARGS(dim3(N / 32, ksplit, G), Kb));
             return;
         }
         while (G > 1 && (Mb + G - 1) / G > 4) ++G;             // one row per wave (RPW = 1): at most four rows per group
         if ((Mb + G - 1) / G <= 4) {
             hipLaunchKernelGGL((gemv2_bf16_kernel<EPI_RESID_F32, 1, true, true, 2, 3, 2>), dim3(N / 32, ksplit, G), dim3(256), lds + 4 * 4 * 64 * 4, st,
-                               x, Mb, K, Kb, (const bf16_t*)W, N, ln_g, ln_b, ep, cb, m_base, wpk);
+                               CW_GEMV2_ARGS(dim3(N / 32, ksplit, G), Kb));
             return;
         }
     }
@@ -2133,6 +2151,7 @@ static void launch_gemv2(const float* x, int Mb, int K, const void* W, int N, co
     else if (Kb <= 768) launch_gemv2_shape<EPI, RPW, 2, 3>(grid, lds, ksplit, x, Mb, K, Kb, W, N, ln_g, ln_b, ep, st, cb, m_base, wpk, wnt);
     else launch_gemv2_shape<EPI, RPW, 3, 5>(grid, lds, ksplit, x, Mb, K, Kb, W, N, ln_g, ln_b, ep, st, cb, m_base, wpk, wnt);
 }
+#undef CW_GEMV2_ARGS
 
 static bool gemv2_ok(int epi, int Mb, int K, const float* ln_g, const EpiParams& ep) {
     if (Mb > GV_MAXM || K % 128 != 0) return false;

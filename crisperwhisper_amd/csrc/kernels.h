@@ -141,7 +141,7 @@ struct CrossSplitParams {
     const float* pstats;   // [n_pstats][16][2] per-block (sum, sum of squares) of those rows, left by the producing GEMV
     int n_pstats;
     const float* qa;       // [B][H*64] W'q x + W'q bo
-    const float* qb;       // [B][H*64] (W'q Wo) a
+    const float* qb;       // [B][H*64] (W'q Wo) a; in qa's allocation, 0 < qb - qa < 2^31 floats (attn_cross_split_kernel gets it as an offset)
     const float* qw;       // [H*64]    W'q 1
     const float* qbias;    // [H*64]    b'q
     float* a_out;          // [B][H*64] non-null: one block per (row, head) over all keys writes the finished output (no splits)
