@@ -141,6 +141,12 @@ _SIGS = {
     "cw_test_score_head_stop": (_I, [_P, _I, _I, _I, _P, _P, _P, _P, _P, _I, _I, _P, _P, _P, _P]),
     "cw_test_align_cut": (_I, [_P, _I, _I, _P, _P, _P, _P, _P, _P, _P]),
     "cw_score_prefill_runs": (_I, [_P]),
+    "cw_set_score_top_logprobs": (_I, [_P, _I]),
+    "cw_get_score_top_logprobs": (_I, [_P, _P, _P, _I, _I]),
+    "cw_test_score_head_top": (_I, [_P, _I, _I, _I, _P, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _P]),
+    "cw_test_score_head_stop_top": (_I, [_P, _I, _I, _I, _P, _P, _P, _P, _P, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P]),
+    "cw_test_score_rows_top": (_I, [_P, _I, _I, _I, _P, _P, _I, _I, _I, _P, _P, _P, _P, _P, _P]),
+    "cw_time_score_head_top": (_I, [_P, _I, _I, _I, _I, _P]),
     "cw_align_matrix": (_I, [_P, _P, _I, _I, _I, _I, _P, _I, _P]),
     "cw_dtw": (_I, [_P, _P, _I, _I, _P, _P, _P]),
     "cw_adjust_pauses": (_I, [_P, _P, _P, _I, C.c_double]),

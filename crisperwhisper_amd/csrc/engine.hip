@@ -9,6 +9,7 @@
 #include <set>
 #include <string>
 #include <vector>
+#include <limits>
 #include <functional>
 #include <algorithm>
 
@@ -263,6 +264,17 @@ struct cw_ctx {
     int *cut_base = nullptr, *cut_ntok = nullptr, *cut_out = nullptr;
     float* cut_score = nullptr;
     unsigned char *cut_force = nullptr, *cut_ok = nullptr;
+    // cw_set_score_top_logprobs: the TOPK forms of the head and of the loop's row kernel.  sc_tpart: the head's per-split lists,
+    // sc_alt_*: [M][CW_TOP_LOGPROBS_MAX] of the head, sc_step_alt_*: [Bm][TGT][CW_TOP_LOGPROBS_MAX] of the loop; all allocated on
+    // first use.  sc_top_ids / sc_top_lps: the last scoring call's alternatives [sc_top_rows][sc_top_stride][CW_TOP_LOGPROBS_MAX]
+    int sc_top_k = 0;
+    size_t sc_tparts = 0, sc_alt_rows = 0;
+    ScoreTopPart* sc_tpart = nullptr;
+    int *sc_alt_id = nullptr, *sc_step_alt_id = nullptr;
+    float *sc_alt_lp = nullptr, *sc_step_alt_lp = nullptr;
+    std::vector<int32_t> sc_top_ids;
+    std::vector<float> sc_top_lps;
+    int sc_top_rows = 0, sc_top_stride = 0;
     int stage_kind[CW_MAX_DEC_STAGES] = {};
     int stage_launches[CW_MAX_DEC_STAGES] = {};   // kernel launches behind each stage (2 where gemv_prep_kernel precedes gemv_mt_kernel)
     float stage_ms[CW_N_STAGES] = {};
@@ -729,7 +741,7 @@ void cw_destroy(cw_ctx* c) {
     for (void* p : c->allocs) hipFree(p);
     for (void* p : {(void*)c->pf_x, c->pf_a, c->pf_q, c->pf_o, c->pf_h}) if (p) hipFree(p);
     for (void* p : {(void*)c->sc_src, (void*)c->sc_tgt, (void*)c->sc_ti, c->sc_a, (void*)c->sc_part, (void*)c->sc_lp, (void*)c->sc_tl,
-                    (void*)c->sc_stop, (void*)c->sc_spart}) if (p) hipFree(p);
+                    (void*)c->sc_stop, (void*)c->sc_spart, (void*)c->sc_tpart, (void*)c->sc_alt_id, (void*)c->sc_alt_lp}) if (p) hipFree(p);
     if (c->h_nunf) hipHostFree(c->h_nunf);
     if (c->ev0) hipEventDestroy(c->ev0);
     if (c->ev1) hipEventDestroy(c->ev1);
@@ -1874,6 +1886,15 @@ static int decode_once(cw_ctx* c, int32_t nb, const int32_t* prompt, int32_t n_p
             // forward at position t-1, logits, fused processors + argmax -> ids[t], x for position t, pos := t
             c->hist_short = t <= 64;               // keys 0 .. t-1
             CWCHK(c, run_step(c, nb));
+            if (c->score_hook && c->sc_top_k > 0) {   // ... with cw_set_score_top_logprobs: the TOPK forms of the two below
+                if (c->score_stop)
+                    CWCHK(c, KD(c, cw_launch_score_rows_stop_top, c->dlogits, c->Vpad, V, c->d_forced, TGT, t, nb, c->gen.eos_token_id,
+                                c->gen.no_timestamps_token_id + 1, c->sc_top_k, c->sc_step_lp, c->sc_step_ti, c->sc_step_tl, c->sc_step_stop,
+                                c->sc_step_alt_id, c->sc_step_alt_lp, c->st));
+                else
+                    CWCHK(c, KD(c, cw_launch_score_rows_top, c->dlogits, c->Vpad, V, c->d_forced, TGT, t, nb, c->sc_top_k, c->sc_step_lp,
+                                c->sc_step_ti, c->sc_step_tl, c->sc_step_alt_id, c->sc_step_alt_lp, c->st));
+            } else
             if (c->score_hook && c->score_stop)   // ... of cw_align_cut_tokens: the same three numbers and stop_logprob
                 CWCHK(c, KD(c, cw_launch_score_rows_stop, c->dlogits, c->Vpad, V, c->d_forced, TGT, t, nb, c->gen.eos_token_id, c->gen.no_timestamps_token_id + 1,
                             c->sc_step_lp, c->sc_step_ti, c->sc_step_tl, c->sc_step_stop, c->st));
@@ -3181,6 +3202,38 @@ static int cut_reserve(cw_ctx* c, size_t M, size_t parts) {
     return CW_OK;
 }
 
+// what cw_set_score_top_logprobs needs on top: the head's per-split lists and its [M][CW_TOP_LOGPROBS_MAX] results
+static int top_reserve(cw_ctx* c, size_t M, size_t parts) {
+    if (M > c->sc_alt_rows) {
+        HIPCHK(c, hipStreamSynchronize(c->st));
+        for (void** p : {(void**)&c->sc_alt_id, (void**)&c->sc_alt_lp})
+            if (*p) { hipFree(*p); *p = nullptr; }
+        c->sc_alt_rows = 0;
+        for (void** p : {(void**)&c->sc_alt_id, (void**)&c->sc_alt_lp}) {
+            hipError_t e = hipMalloc(p, M * CW_TOP_LOGPROBS_MAX * 4);
+            if (e != hipSuccess) return fail(c, CW_ERR_NOMEM, "score: hipMalloc(%zu) failed: %s", M * CW_TOP_LOGPROBS_MAX * 4, hipGetErrorString(e));
+        }
+        c->sc_alt_rows = M;
+    }
+    if (parts > c->sc_tparts) {
+        HIPCHK(c, hipStreamSynchronize(c->st));
+        if (c->sc_tpart) { hipFree(c->sc_tpart); c->sc_tpart = nullptr; }
+        c->sc_tparts = 0;
+        const size_t bytes = parts * CW_TOP_LOGPROBS_MAX * sizeof(ScoreTopPart);
+        hipError_t e = hipMalloc((void**)&c->sc_tpart, bytes);
+        if (e != hipSuccess) return fail(c, CW_ERR_NOMEM, "score: hipMalloc(%zu) failed: %s", bytes, hipGetErrorString(e));
+        c->sc_tparts = parts;
+    }
+    return CW_OK;
+}
+
+// the host copy cw_get_score_top_logprobs answers from: [rows][ids_stride][CW_TOP_LOGPROBS_MAX], -1 / NaN until a position is filled
+static void top_results_begin(cw_ctx* c, int rows, int ids_stride) {
+    const size_t n = (size_t)rows * ids_stride * CW_TOP_LOGPROBS_MAX;
+    c->sc_top_ids.assign(n, -1);
+    c->sc_top_lps.assign(n, std::numeric_limits<float>::quiet_NaN());
+}
+
 // cw_align_cut_tokens' extra arguments; null through score_rows: the plain scoring calls
 struct CutArgs {
     const uint8_t* cut_ok;       // [rows][ids_stride]
@@ -3232,10 +3285,20 @@ static int score_head_launch(cw_ctx* c, int M, int cut_rows = 0) {
     const int V = c->d.vocab_size, D = c->d.d_model;
     CWCHK(c, KD(c, cw_launch_score_ln, c->pf_x, c->sc_src, c->dec_ln_g, c->dec_ln_b, c->sc_a, M, D, c->st));
     if (cut_rows > 0) {                          // cw_align_cut_tokens: the STOP head, then the cut on the arrays it leaves
+        if (c->sc_top_k > 0)
+            CWCHK(c, KD(c, cw_launch_score_head_stop_top, c->sc_a, c->embed_pk, c->sc_tgt, c->sc_part, c->sc_spart, c->sc_tpart, M, V, D,
+                        c->gen.eos_token_id, c->gen.no_timestamps_token_id + 1, c->sc_top_k, c->sc_lp, c->sc_ti, c->sc_tl, c->sc_stop,
+                        c->sc_alt_id, c->sc_alt_lp, c->st));
+        else
         CWCHK(c, KD(c, cw_launch_score_head_stop, c->sc_a, c->embed_pk, c->sc_tgt, c->sc_part, c->sc_spart, M, V, D, c->gen.eos_token_id,
                     c->gen.no_timestamps_token_id + 1, c->sc_lp, c->sc_ti, c->sc_tl, c->sc_stop, c->st));
         CWCHK(c, cw_launch_align_cut(c->sc_lp, c->sc_stop, c->cut_base, c->cut_ntok, c->cut_ok, c->d.max_target_positions, c->cut_force,
                                      cut_rows, c->cut_out, c->cut_score, c->st));
+        return CW_OK;
+    }
+    if (c->sc_top_k > 0) {
+        CWCHK(c, KD(c, cw_launch_score_head_top, c->sc_a, c->embed_pk, c->sc_tgt, c->sc_part, c->sc_tpart, M, V, D, c->sc_top_k, c->sc_lp,
+                    c->sc_ti, c->sc_tl, c->sc_alt_id, c->sc_alt_lp, c->st));
         return CW_OK;
     }
     CWCHK(c, KD(c, cw_launch_score_head, c->sc_a, c->embed_pk, c->sc_tgt, c->sc_part, M, V, D, c->sc_lp, c->sc_ti, c->sc_tl, c->st));
@@ -3263,6 +3326,20 @@ static int score_head_fetch(cw_ctx* c, int rows, int M, int ids_stride, const in
             if (top_logprob) top_logprob[(size_t)r * ids_stride + k] = tl[m];
             if (ca) ca->stop_logprob[(size_t)r * ids_stride + k] = sl[m];
         }
+    if (c->sc_top_k > 0) {                       // the alternatives stay with the context (cw_get_score_top_logprobs)
+        const size_t W = CW_TOP_LOGPROBS_MAX;
+        std::vector<int> ai((size_t)M * W);
+        std::vector<float> al((size_t)M * W);
+        HIPCHK(c, hipMemcpy(ai.data(), c->sc_alt_id, ai.size() * 4, hipMemcpyDeviceToHost));
+        HIPCHK(c, hipMemcpy(al.data(), c->sc_alt_lp, al.size() * 4, hipMemcpyDeviceToHost));
+        top_results_begin(c, rows, ids_stride);
+        m = 0;
+        for (int r = 0; r < rows; ++r)
+            for (int k = n_init; k < n_ids[r]; ++k, ++m) {
+                memcpy(&c->sc_top_ids[((size_t)r * ids_stride + k) * W], &ai[(size_t)m * W], W * 4);
+                memcpy(&c->sc_top_lps[((size_t)r * ids_stride + k) * W], &al[(size_t)m * W], W * 4);
+            }
+    }
     return CW_OK;
 }
 
@@ -3292,6 +3369,7 @@ static int score_rows(cw_ctx* c, const char* who, int n_items, int rpi, const in
     PrefixScope scope{c, c->pf_prefix};
     c->pf_prefix = 0;
     const int Lmax = n_max - 1;
+    c->sc_top_rows = 0;                          // cw_get_score_top_logprobs answers for a call that came to its end only
     if (c->score_prefill && prefill_capable(c)) {
         // one encoder pass per item; decoder row r reads the cross K/V cache of item r / rows_per_item
         std::vector<int> all(n_items), zeros(n_items, 0), full(n_items, CW_N_FRAMES);
@@ -3304,6 +3382,7 @@ static int score_rows(cw_ctx* c, const char* who, int n_items, int rpi, const in
         HIPCHK(c, hipMemcpyAsync(c->d_ids, dev.data(), dev.size() * 4, hipMemcpyHostToDevice, c->st));
         int M = 0;
         CWCHK(c, score_head_prepare(c, rows, Lmax, ids, ids_stride, n_ids, n_init, &M));     // (synchronises the stream)
+        if (c->sc_top_k > 0) CWCHK(c, top_reserve(c, (size_t)M, (size_t)M * KD(c, cw_score_head_splits, M, c->d.vocab_size, nullptr)));
         if (ca) {
             CWCHK(c, cut_reserve(c, (size_t)M, (size_t)M * KD(c, cw_score_head_splits, M, c->d.vocab_size, nullptr)));
             std::vector<int> first(rows, 0);     // the head's arrays hold row after row, n_ids - n_init entries each
@@ -3329,6 +3408,10 @@ static int score_rows(cw_ctx* c, const char* who, int n_items, int rpi, const in
         if (!c->sc_step_lp) {
             const size_t n = (size_t)c->Bm * TGT * 4;
             CWCHK(c, dmalloc(c, &c->sc_step_lp, n)); CWCHK(c, dmalloc(c, &c->sc_step_tl, n)); CWCHK(c, dmalloc(c, &c->sc_step_ti, n));
+        }
+        if (c->sc_top_k > 0 && !c->sc_step_alt_id) {
+            const size_t n = (size_t)c->Bm * TGT * CW_TOP_LOGPROBS_MAX * 4;
+            CWCHK(c, dmalloc(c, &c->sc_step_alt_id, n)); CWCHK(c, dmalloc(c, &c->sc_step_alt_lp, n));
         }
         if (ca) {
             if (!c->sc_step_stop) CWCHK(c, dmalloc(c, &c->sc_step_stop, (size_t)c->Bm * TGT * 4));
@@ -3370,7 +3453,21 @@ static int score_rows(cw_ctx* c, const char* who, int n_items, int rpi, const in
                 if (top_logprob) top_logprob[(size_t)r * ids_stride + k] = tl[(size_t)r * TGT + k];
                 if (ca) ca->stop_logprob[(size_t)r * ids_stride + k] = sl[(size_t)r * TGT + k];
             }
+        if (c->sc_top_k > 0) {                   // the loop's [rows][TGT][CW_TOP_LOGPROBS_MAX], indexed by position
+            const size_t W = CW_TOP_LOGPROBS_MAX;
+            std::vector<int> ai((size_t)rows * TGT * W);
+            std::vector<float> al((size_t)rows * TGT * W);
+            HIPCHK(c, hipMemcpy(ai.data(), c->sc_step_alt_id, ai.size() * 4, hipMemcpyDeviceToHost));
+            HIPCHK(c, hipMemcpy(al.data(), c->sc_step_alt_lp, al.size() * 4, hipMemcpyDeviceToHost));
+            top_results_begin(c, rows, ids_stride);
+            for (int r = 0; r < rows; ++r)
+                for (int k = n_init; k < n_ids[r]; ++k) {
+                    memcpy(&c->sc_top_ids[((size_t)r * ids_stride + k) * W], &ai[((size_t)r * TGT + k) * W], W * 4);
+                    memcpy(&c->sc_top_lps[((size_t)r * ids_stride + k) * W], &al[((size_t)r * TGT + k) * W], W * 4);
+                }
+        }
     }
+    if (c->sc_top_k > 0) { c->sc_top_rows = rows; c->sc_top_stride = ids_stride; }
     if (ca) {
         std::vector<int32_t> kept(rows);         // init tokens + the kept text + the slot cw_align_tokens gives the eos
         for (int b = 0; b < rows; ++b) {
@@ -3406,6 +3503,29 @@ int32_t cw_align_cut_tokens(cw_ctx* c, int32_t nb, const int32_t* num_frames, co
     const CutArgs ca{cut_ok, force_all, cut, cut_score, stop_logprob};
     return score_rows(c, "align_cut_tokens", nb, 1, num_frames, ids, ids_stride, n_ids, n_init, token_ts, token_logprob, top_id,
                       top_logprob, &ca);
+}
+
+// ---- alternatives of the teacher-forced positions (include/crisperwhisper.h) ----------------------------------------------------
+int32_t cw_set_score_top_logprobs(cw_ctx* c, int32_t k) {
+    if (k < 0 || k > CW_TOP_LOGPROBS_MAX) return fail(c, CW_ERR_INVALID, "set_score_top_logprobs: k=%d outside 0 .. %d", k, CW_TOP_LOGPROBS_MAX);
+    c->sc_top_k = k;
+    c->sc_top_rows = 0;                          // what an earlier call stored was stored for its own k
+    if (k == 0) { c->sc_top_ids.clear(); c->sc_top_lps.clear(); }
+    return CW_OK;
+}
+
+int32_t cw_get_score_top_logprobs(cw_ctx* c, int32_t* ids_out, float* lp_out, int32_t rows, int32_t ids_stride) {
+    if (c->sc_top_k < 1) return fail(c, CW_ERR_STATE, "score top_logprobs is off (cw_set_score_top_logprobs)");
+    if (!ids_out || !lp_out || rows < 1 || ids_stride < 1) return fail(c, CW_ERR_INVALID, "get_score_top_logprobs: bad arguments");
+    if (rows > c->sc_top_rows || ids_stride != c->sc_top_stride)
+        return fail(c, CW_ERR_STATE, "get_score_top_logprobs: asked %d rows of stride %d, the last scoring call stored %d of stride %d", rows,
+                    ids_stride, c->sc_top_rows, c->sc_top_stride);
+    const size_t n = (size_t)rows * ids_stride, k = (size_t)c->sc_top_k;
+    for (size_t i = 0; i < n; ++i) {             // stored rows are CW_TOP_LOGPROBS_MAX wide, the caller's k
+        memcpy(ids_out + i * k, &c->sc_top_ids[i * CW_TOP_LOGPROBS_MAX], k * 4);
+        memcpy(lp_out + i * k, &c->sc_top_lps[i * CW_TOP_LOGPROBS_MAX], k * 4);
+    }
+    return CW_OK;
 }
 
 int32_t cw_align_matrix(cw_ctx* c, const float* attn, int32_t B, int32_t Ha, int32_t N, int32_t M, const int32_t* n_cols,
@@ -3792,8 +3912,11 @@ int32_t cw_test_prefill_gemm(cw_ctx* c, int32_t mode, int32_t M, int32_t N, int3
 // stop_logprob non-null (cw_test_score_head_stop): the STOP form over S = {eos} + {n >= timestamp_begin} instead.
 static int test_score_head(cw_ctx* c, int32_t M, int32_t D, int32_t V, const float* x, const float* ln_g, const float* ln_b,
                            const float* embed, const int32_t* targets, float* logprob, int32_t* top_id, float* top_logprob,
-                           int eos, int timestamp_begin, float* stop_logprob) {
+                           int eos, int timestamp_begin, float* stop_logprob, int k = 0, int32_t* alt_id = nullptr,
+                           float* alt_logprob = nullptr, float* logits_out = nullptr) {
     if (!c->bf16) return fail(c, CW_ERR_INVALID, "test_score_head: 16-bit engines only");
+    if (k < 0 || k > CW_TOP_LOGPROBS_MAX || (k > 0 && (!alt_id || !alt_logprob)) || (k == 0 && logits_out))
+        return fail(c, CW_ERR_INVALID, "test_score_head: k=%d outside 1 .. %d or a null alt_id / alt_logprob", k, CW_TOP_LOGPROBS_MAX);
     if (M < 1 || M > (1 << 16) || D < 32 || D % 32 || D > 8192 || V < 1 || V > (1 << 20) || !x || !ln_g || !ln_b || !embed || !targets ||
         !logprob || !top_id || !top_logprob) return fail(c, CW_ERR_INVALID, "test_score_head: bad arguments");
     for (int m = 0; m < M; ++m)
@@ -3807,6 +3930,14 @@ static int test_score_head(cw_ctx* c, int32_t M, int32_t D, int32_t V, const flo
     ScoreStopPart* dS = nullptr;
     float* dsl = nullptr;
     int r = CW_OK;
+    DevBuf dT, dai, dal, dlog;                   // TOPK form: the per-split lists, alt_id / alt_logprob [M][CW_TOP_LOGPROBS_MAX], f32 logits [M][V]
+    // ... each with 8 guard rows behind row M - 1, filled with 0x5a: a write there is CW_ERR_STATE
+    const size_t tp_row = (size_t)ns * CW_TOP_LOGPROBS_MAX * sizeof(ScoreTopPart), alt_row = (size_t)CW_TOP_LOGPROBS_MAX * 4;
+    if (k > 0 && (dT.alloc((size_t)(M + 8) * tp_row) != hipSuccess || dai.alloc((size_t)(M + 8) * alt_row) != hipSuccess ||
+                  dal.alloc((size_t)(M + 8) * alt_row) != hipSuccess || (logits_out && dlog.alloc((size_t)M * V * 4) != hipSuccess)))
+        r = fail(c, CW_ERR_NOMEM, "test_score_head: hipMalloc failed");
+    if (r == CW_OK && k > 0 && (hipMemset(dT.p, 0x5a, (size_t)(M + 8) * tp_row) != hipSuccess || hipMemset(dai.p, 0x5a, (size_t)(M + 8) * alt_row) != hipSuccess ||
+                                hipMemset(dal.p, 0x5a, (size_t)(M + 8) * alt_row) != hipSuccess)) r = fail(c, CW_ERR_HIP, "test_score_head: memset");
     if (stop_logprob && (hipMalloc((void**)&dS, (size_t)M * ns * sizeof(ScoreStopPart)) != hipSuccess ||
                          hipMalloc((void**)&dsl, (size_t)M * 4) != hipSuccess)) r = fail(c, CW_ERR_NOMEM, "test_score_head: hipMalloc failed");
     if (hipMalloc((void**)&dx, (size_t)M * D * 4) != hipSuccess || hipMalloc((void**)&dg, (size_t)D * 4) != hipSuccess ||
@@ -3822,9 +3953,30 @@ static int test_score_head(cw_ctx* c, int32_t M, int32_t D, int32_t V, const flo
     if (r == CW_OK) r = upload_T(c, dW, 0, embed, (size_t)V * D);
     if (r == CW_OK) r = KD(c, cw_launch_wfrag_pack, dW, V, D, dWp, c->st);
     if (r == CW_OK) r = KD(c, cw_launch_score_ln, dx, nullptr, dg, db, dA, M, D, c->st);
+    if (r == CW_OK && k > 0)
+        r = stop_logprob ? KD(c, cw_launch_score_head_stop_top, dA, dWp, dt, dP, dS, (ScoreTopPart*)dT.p, M, V, D, eos, timestamp_begin, k, dlp, dti,
+                              dtl, dsl, (int*)dai.p, (float*)dal.p, c->st)
+                         : KD(c, cw_launch_score_head_top, dA, dWp, dt, dP, (ScoreTopPart*)dT.p, M, V, D, k, dlp, dti, dtl, (int*)dai.p,
+                              (float*)dal.p, c->st);
+    else
     if (r == CW_OK) r = stop_logprob ? KD(c, cw_launch_score_head_stop, dA, dWp, dt, dP, dS, M, V, D, eos, timestamp_begin, dlp, dti, dtl, dsl, c->st)
                                      : KD(c, cw_launch_score_head, dA, dWp, dt, dP, M, V, D, dlp, dti, dtl, c->st);
+    if (r == CW_OK && logits_out) r = KD(c, cw_launch_score_head_store, dA, dWp, dt, (float*)dlog.p, V, M, V, D, c->st);
     if (r == CW_OK) { hipError_t er = hipStreamSynchronize(c->st); if (er != hipSuccess) r = fail(c, CW_ERR_HIP, "test_score_head: %s", hipGetErrorString(er)); }
+    if (r == CW_OK && k > 0) {
+        std::vector<unsigned char> gd(8 * tp_row), ga(8 * alt_row), gl(8 * alt_row);
+        if (hipMemcpy(gd.data(), (char*)dT.p + (size_t)M * tp_row, gd.size(), hipMemcpyDeviceToHost) != hipSuccess ||
+            hipMemcpy(ga.data(), (char*)dai.p + (size_t)M * alt_row, ga.size(), hipMemcpyDeviceToHost) != hipSuccess ||
+            hipMemcpy(gl.data(), (char*)dal.p + (size_t)M * alt_row, gl.size(), hipMemcpyDeviceToHost) != hipSuccess)
+            r = fail(c, CW_ERR_HIP, "test_score_head: copy");
+        for (const auto* gv : {&gd, &ga, &gl})
+            for (unsigned char b : *gv)
+                if (r == CW_OK && b != 0x5a) r = fail(c, CW_ERR_STATE, "test_score_head: a row behind M = %d was written", M);
+    }
+    if (r == CW_OK && k > 0 && (hipMemcpy(alt_id, dai.p, (size_t)M * alt_row, hipMemcpyDeviceToHost) != hipSuccess ||
+                                hipMemcpy(alt_logprob, dal.p, (size_t)M * CW_TOP_LOGPROBS_MAX * 4, hipMemcpyDeviceToHost) != hipSuccess ||
+                                (logits_out && hipMemcpy(logits_out, dlog.p, (size_t)M * V * 4, hipMemcpyDeviceToHost) != hipSuccess)))
+        r = fail(c, CW_ERR_HIP, "test_score_head: copy");
     if (r == CW_OK && stop_logprob && hipMemcpy(stop_logprob, dsl, (size_t)M * 4, hipMemcpyDeviceToHost) != hipSuccess) r = fail(c, CW_ERR_HIP, "test_score_head: copy");
     if (r == CW_OK && (hipMemcpy(logprob, dlp, (size_t)M * 4, hipMemcpyDeviceToHost) != hipSuccess ||
                        hipMemcpy(top_id, dti, (size_t)M * 4, hipMemcpyDeviceToHost) != hipSuccess ||
@@ -3847,6 +3999,63 @@ int32_t cw_test_score_head_stop(cw_ctx* c, int32_t M, int32_t D, int32_t V, cons
         return fail(c, CW_ERR_INVALID, "test_score_head_stop: eos=%d inside 0 .. %d, timestamp_begin=%d inside 0 .. %d and stop_logprob are needed",
                     eos, V - 1, timestamp_begin, V);
     return test_score_head(c, M, D, V, x, ln_g, ln_b, embed, targets, logprob, top_id, top_logprob, eos, timestamp_begin, stop_logprob);
+}
+
+// cw_test_score_head_top / _stop_top: the TOPK forms of the head.  alt_id / alt_logprob [M][CW_TOP_LOGPROBS_MAX]; logits_out
+// non-null: the same operands once more through the STORE form into [M][V] -- the same MFMA sequence, so the very accumulators
+// the fused form selected from.
+int32_t cw_test_score_head_top(cw_ctx* c, int32_t M, int32_t D, int32_t V, const float* x, const float* ln_g, const float* ln_b,
+                               const float* embed, const int32_t* targets, int32_t k, float* logprob, int32_t* top_id, float* top_logprob,
+                               int32_t* alt_id, float* alt_logprob, float* logits_out) {
+    if (k < 1) return fail(c, CW_ERR_INVALID, "test_score_head_top: k=%d outside 1 .. %d", k, CW_TOP_LOGPROBS_MAX);
+    return test_score_head(c, M, D, V, x, ln_g, ln_b, embed, targets, logprob, top_id, top_logprob, 0, 0, nullptr, k, alt_id, alt_logprob,
+                           logits_out);
+}
+
+int32_t cw_test_score_head_stop_top(cw_ctx* c, int32_t M, int32_t D, int32_t V, const float* x, const float* ln_g, const float* ln_b,
+                                    const float* embed, const int32_t* targets, int32_t eos, int32_t timestamp_begin, int32_t k,
+                                    float* logprob, int32_t* top_id, float* top_logprob, float* stop_logprob, int32_t* alt_id,
+                                    float* alt_logprob, float* logits_out) {
+    if (k < 1) return fail(c, CW_ERR_INVALID, "test_score_head_stop_top: k=%d outside 1 .. %d", k, CW_TOP_LOGPROBS_MAX);
+    if (!stop_logprob || eos < 0 || eos >= V || timestamp_begin < 0 || timestamp_begin > V)
+        return fail(c, CW_ERR_INVALID, "test_score_head_stop_top: eos=%d inside 0 .. %d, timestamp_begin=%d inside 0 .. %d and stop_logprob are needed",
+                    eos, V - 1, timestamp_begin, V);
+    return test_score_head(c, M, D, V, x, ln_g, ln_b, embed, targets, logprob, top_id, top_logprob, eos, timestamp_begin, stop_logprob, k,
+                           alt_id, alt_logprob, logits_out);
+}
+
+// cw_test_score_rows_top: the loop path's row kernel (TOPK form) on caller-supplied f32 logits [rows][ldv], any engine.  targets
+// [rows] (negative: none).  stop_logprob non-null: the STOP form over S = {eos} + {n >= timestamp_begin}.  Outputs [rows] and
+// alt_id / alt_logprob [rows][CW_TOP_LOGPROBS_MAX].
+int32_t cw_test_score_rows_top(cw_ctx* c, int32_t rows, int32_t V, int32_t ldv, const float* logits, const int32_t* targets, int32_t k,
+                               int32_t eos, int32_t timestamp_begin, float* logprob, int32_t* top_id, float* top_logprob,
+                               float* stop_logprob, int32_t* alt_id, float* alt_logprob) {
+    if (rows < 1 || rows > (1 << 16) || V < 1 || V > (1 << 20) || ldv < V || ldv > (1 << 21) || k < 1 || k > CW_TOP_LOGPROBS_MAX || !logits ||
+        !targets || !logprob || !top_id || !top_logprob || !alt_id || !alt_logprob || (stop_logprob && (eos < 0 || timestamp_begin < 0)))
+        return fail(c, CW_ERR_INVALID, "test_score_rows_top: bad arguments");
+    const size_t W = CW_TOP_LOGPROBS_MAX;
+    DevBuf dl, dt, dlp, dti, dtl, dsl, dai, dal;
+    if (dl.alloc((size_t)rows * ldv * 4) != hipSuccess || dt.alloc((size_t)rows * 4) != hipSuccess || dlp.alloc((size_t)rows * 4) != hipSuccess ||
+        dti.alloc((size_t)rows * 4) != hipSuccess || dtl.alloc((size_t)rows * 4) != hipSuccess || dsl.alloc((size_t)rows * 4) != hipSuccess ||
+        dai.alloc((size_t)rows * W * 4) != hipSuccess || dal.alloc((size_t)rows * W * 4) != hipSuccess)
+        return fail(c, CW_ERR_NOMEM, "test_score_rows_top: hipMalloc failed");
+    HIPCHK(c, hipMemcpy(dl.p, logits, (size_t)rows * ldv * 4, hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemcpy(dt.p, targets, (size_t)rows * 4, hipMemcpyHostToDevice));
+    if (stop_logprob)
+        CWCHK(c, KD(c, cw_launch_score_rows_stop_top, (const float*)dl.p, ldv, V, (const int*)dt.p, 1, 0, rows, eos, timestamp_begin, k,
+                    (float*)dlp.p, (int*)dti.p, (float*)dtl.p, (float*)dsl.p, (int*)dai.p, (float*)dal.p, c->st));
+    else
+        CWCHK(c, KD(c, cw_launch_score_rows_top, (const float*)dl.p, ldv, V, (const int*)dt.p, 1, 0, rows, k, (float*)dlp.p, (int*)dti.p,
+                    (float*)dtl.p, (int*)dai.p, (float*)dal.p, c->st));
+    KCHK(c);
+    HIPCHK(c, hipStreamSynchronize(c->st));
+    HIPCHK(c, hipMemcpy(logprob, dlp.p, (size_t)rows * 4, hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(top_id, dti.p, (size_t)rows * 4, hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(top_logprob, dtl.p, (size_t)rows * 4, hipMemcpyDeviceToHost));
+    if (stop_logprob) HIPCHK(c, hipMemcpy(stop_logprob, dsl.p, (size_t)rows * 4, hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(alt_id, dai.p, (size_t)rows * W * 4, hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(alt_logprob, dal.p, (size_t)rows * W * 4, hipMemcpyDeviceToHost));
+    return CW_OK;
 }
 
 // cw_test_align_cut: the cut kernel of cw_align_cut_tokens, through its launcher, on caller-supplied scores.  Row r holds n_tok[r]
@@ -3936,6 +4145,60 @@ int32_t cw_time_score_head(cw_ctx* c, int32_t M, int32_t unfused, int32_t iters,
     hipFree(dx); hipFree(dlp); hipFree(dtl); hipFree(dt); hipFree(dti); hipFree(dA); hipFree(dP); if (dlog) hipFree(dlog);
     if (dS) hipFree(dS);
     if (dsl) hipFree(dsl);
+    return r;
+}
+
+// cw_time_score_head_top: cw_time_score_head's fused forms (stop = 0 / 1) with k alternatives per row; k = 0: the plain forms,
+// timed by this same loop
+int32_t cw_time_score_head_top(cw_ctx* c, int32_t M, int32_t k, int32_t stop, int32_t iters, float* avg_ms) {
+    if (!c->bf16 || !c->embed_pk) return fail(c, CW_ERR_INVALID, "time_score_head_top: 16-bit engines with packed weights only");
+    if (M < 1 || M > (1 << 15) || k < 0 || k > CW_TOP_LOGPROBS_MAX || iters < 1 || !avg_ms)
+        return fail(c, CW_ERR_INVALID, "time_score_head_top: bad arguments");
+    if (stop && !c->gen_set) return fail(c, CW_ERR_STATE, "cw_set_generation not called");
+    CWCHK(c, cw_check_weights(c));
+    const int D = c->d.d_model, V = c->d.vocab_size;
+    const int ns = KD(c, cw_score_head_splits, M, V, nullptr);
+    std::vector<float> x((size_t)M * D);
+    std::vector<int> tg(M);
+    unsigned int lcg = 12345u;
+    for (auto& v : x) { lcg = lcg * 1664525u + 1013904223u; v = ((int)(lcg >> 8) % 4001 - 2000) * 1e-3f; }
+    for (int m = 0; m < M; ++m) { lcg = lcg * 1664525u + 1013904223u; tg[m] = (int)((lcg >> 8) % (unsigned)V); }
+    const size_t W = CW_TOP_LOGPROBS_MAX;
+    DevBuf dx, dlp, dtl, dt, dti, dA, dP, dS, dsl, dT, dai, dal;
+    if (dx.alloc(x.size() * 4) != hipSuccess || dlp.alloc((size_t)M * 4) != hipSuccess || dtl.alloc((size_t)M * 4) != hipSuccess ||
+        dt.alloc((size_t)M * 4) != hipSuccess || dti.alloc((size_t)M * 4) != hipSuccess || dA.alloc((size_t)M * D * 2) != hipSuccess ||
+        dP.alloc((size_t)M * ns * sizeof(ScorePart)) != hipSuccess || dS.alloc((size_t)M * ns * sizeof(ScoreStopPart)) != hipSuccess ||
+        dsl.alloc((size_t)M * 4) != hipSuccess || dT.alloc((size_t)M * ns * W * sizeof(ScoreTopPart)) != hipSuccess ||
+        dai.alloc((size_t)M * W * 4) != hipSuccess || dal.alloc((size_t)M * W * 4) != hipSuccess)
+        return fail(c, CW_ERR_NOMEM, "time_score_head_top: hipMalloc failed");
+    HIPCHK(c, hipMemcpy(dx.p, x.data(), x.size() * 4, hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemcpy(dt.p, tg.data(), (size_t)M * 4, hipMemcpyHostToDevice));
+    const int eos = c->gen.eos_token_id, tsb = c->gen.no_timestamps_token_id + 1;
+    int r = CW_OK;
+    for (int it = 0; it <= iters && r == CW_OK; ++it) {
+        if (it == 1 && hipEventRecord(c->ev0, c->st) != hipSuccess) r = fail(c, CW_ERR_HIP, "time_score_head_top: event");
+        if (r == CW_OK) r = KD(c, cw_launch_score_ln, (const float*)dx.p, nullptr, c->dec_ln_g, c->dec_ln_b, dA.p, M, D, c->st);
+        if (r != CW_OK) break;
+        if (k > 0 && stop)
+            r = KD(c, cw_launch_score_head_stop_top, dA.p, c->embed_pk, (const int*)dt.p, (ScorePart*)dP.p, (ScoreStopPart*)dS.p, (ScoreTopPart*)dT.p,
+                   M, V, D, eos, tsb, k, (float*)dlp.p, (int*)dti.p, (float*)dtl.p, (float*)dsl.p, (int*)dai.p, (float*)dal.p, c->st);
+        else if (k > 0)
+            r = KD(c, cw_launch_score_head_top, dA.p, c->embed_pk, (const int*)dt.p, (ScorePart*)dP.p, (ScoreTopPart*)dT.p, M, V, D, k,
+                   (float*)dlp.p, (int*)dti.p, (float*)dtl.p, (int*)dai.p, (float*)dal.p, c->st);
+        else if (stop)
+            r = KD(c, cw_launch_score_head_stop, dA.p, c->embed_pk, (const int*)dt.p, (ScorePart*)dP.p, (ScoreStopPart*)dS.p, M, V, D, eos, tsb,
+                   (float*)dlp.p, (int*)dti.p, (float*)dtl.p, (float*)dsl.p, c->st);
+        else
+            r = KD(c, cw_launch_score_head, dA.p, c->embed_pk, (const int*)dt.p, (ScorePart*)dP.p, M, V, D, (float*)dlp.p, (int*)dti.p,
+                   (float*)dtl.p, c->st);
+    }
+    if (r == CW_OK) {
+        float ms = 0.f;
+        if (hipEventRecord(c->ev1, c->st) != hipSuccess || hipEventSynchronize(c->ev1) != hipSuccess ||
+            hipEventElapsedTime(&ms, c->ev0, c->ev1) != hipSuccess) r = fail(c, CW_ERR_HIP, "time_score_head_top: event");
+        else *avg_ms = ms / (float)iters;
+    }
+    hipStreamSynchronize(c->st);
     return r;
 }
 

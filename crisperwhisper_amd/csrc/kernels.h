@@ -384,6 +384,10 @@ struct ScorePart {
 struct ScoreStopPart {
     float mx, sum;
 };
+// ... and, for the TOPK forms, one of the split's CW_TOP_LOGPROBS_MAX best (logit, id) pairs, best first; (-inf, INT_MAX): none
+struct ScoreTopPart {
+    float v; int i;
+};
 
 #define CW_DTYPE_KERNEL_DECLS \
     int cw_launch_gemm(bool bf16, int epi, const AParams& ap, const void* W, int M, int N, int K, const EpiParams& ep, hipStream_t st); \
@@ -448,6 +452,11 @@ struct ScoreStopPart {
     int cw_launch_score_rows(const float* logits, int ldv, int V, const int* target, int t_stride, int t, int rows, float* logprob, int* top_id, float* top_logprob, hipStream_t st); \
     int cw_launch_score_head_stop(const void* A, const void* W, const int* target, ScorePart* part, ScoreStopPart* spart, int M, int V, int K, int eos, int ts_begin, float* logprob, int* top_id, float* top_logprob, float* stop_logprob, hipStream_t st); \
     int cw_launch_score_rows_stop(const float* logits, int ldv, int V, const int* target, int t_stride, int t, int rows, int eos, int ts_begin, float* logprob, int* top_id, float* top_logprob, float* stop_logprob, hipStream_t st); \
+    int cw_launch_score_head_top(const void* A, const void* W, const int* target, ScorePart* part, ScoreTopPart* tpart, int M, int V, int K, int k, float* logprob, int* top_id, float* top_logprob, int* alt_id, float* alt_logprob, hipStream_t st); \
+    int cw_launch_score_head_stop_top(const void* A, const void* W, const int* target, ScorePart* part, ScoreStopPart* spart, ScoreTopPart* tpart, int M, int V, int K, int eos, int ts_begin, int k, float* logprob, int* top_id, float* top_logprob, float* stop_logprob, int* alt_id, float* alt_logprob, hipStream_t st); \
+    int cw_launch_score_head_store(const void* A, const void* W, const int* target, float* logits, int ldv, int M, int V, int K, hipStream_t st); \
+    int cw_launch_score_rows_top(const float* logits, int ldv, int V, const int* target, int t_stride, int t, int rows, int k, float* logprob, int* top_id, float* top_logprob, int* alt_id, float* alt_logprob, hipStream_t st); \
+    int cw_launch_score_rows_stop_top(const float* logits, int ldv, int V, const int* target, int t_stride, int t, int rows, int eos, int ts_begin, int k, float* logprob, int* top_id, float* top_logprob, float* stop_logprob, int* alt_id, float* alt_logprob, hipStream_t st); \
     int cw_launch_attn_encoder(bool bf16, const void* Q, const void* K, const void* V, void* out, int B, int H, int S, int S_pad, hipStream_t st); \
     int cw_launch_attn_decode(bool bf16, const DecAttnParams& p, hipStream_t st); \
     int cw_launch_attn_cross_split(bool bf16, const CrossSplitParams& p, hipStream_t st); \

@@ -14,6 +14,10 @@
 // S = {eos} + {n >= timestamp_begin}: the log-probability that the text stops before this position.  S keeps its own running
 // (maximum, sum of exp) pair, never rescaled against the row's maximum: a stop set 100 nats under the row maximum would
 // underflow to log(0) there.  The pair travels in its own record array (ScoreStopPart); the plain forms write what they wrote.
+// TOPK forms (cw_set_score_top_logprobs): besides the above, the k <= CW_TOP_LOGPROBS_MAX best (logit, id) pairs of every row --
+// value descending, id ascending on an exact tie, over the columns < V with a logit > -inf -- as alt_id and alt_logprob = logit -
+// logsumexp.  The head keeps a sorted list per row and split in LDS and writes it to its own record array (ScoreTopPart), the
+// combine kernel merges the splits' lists, the row kernel runs k selection rounds; the logits are still never stored.
 #include <hip/hip_runtime.h>
 #include "kernels.h"
 
@@ -47,12 +51,19 @@ __device__ static inline bool score_better(float v, int i, float bv, int bi) { r
 // its own columns, and the 16 lanes of a row are merged once at the end.
 // STORE (the unfused form, kept for the A/B of cw_time_score_head only): the same tile loop writes the f32 logits [M][ldv]
 // instead of keeping statistics; score_rows_kernel then makes one pass per row.
-template <bool STORE, bool STOP>
+// TOPK (cw_set_score_top_logprobs): besides the above, the split's topk best (logit, id) pairs of every row, in (value descending,
+// id ascending) order.  They live in LDS, one sorted list of CW_TOP_LOGPROBS_MAX pairs per row (32 accumulators a lane leave no
+// registers for 8 rows x 8 pairs); a wave's 32 rows are its own, so the lists need wave-level ordering only.  A lane keeps its
+// rows' topk-th pair in registers and offers a column only if it beats that pair in the full order -- after the first tile
+// groups almost none does.  Offers are served one lane at a time per 16-lane group (the four groups own different rows); the
+// serving lane tests against the list itself, so the result is the exact top of the split whatever the order of service.
+template <bool STORE, bool STOP, bool TOPK = false>
 __global__ __launch_bounds__(256) void score_head_kernel(const bf16_t* __restrict__ A, const bf16_t* __restrict__ W,
                                                          const int* __restrict__ target, ScorePart* __restrict__ part,
                                                          int M, int V, int K, int tiles_per_split, int n_split,
                                                          float* __restrict__ logits, int ldv,
-                                                         ScoreStopPart* __restrict__ spart, int eos, int ts_begin) {
+                                                         ScoreStopPart* __restrict__ spart, int eos, int ts_begin,
+                                                         ScoreTopPart* __restrict__ tpart, int topk) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int l15 = lane & 15, g = lane >> 4;
     const int m0 = blockIdx.x * 128 + wave * 32;
@@ -71,6 +82,22 @@ __global__ __launch_bounds__(256) void score_head_kernel(const bf16_t* __restric
         mx[q] = -INFINITY; sum[q] = 0.f; tl[q] = -INFINITY; bv[q] = -INFINITY; bi[q] = 0x7fffffff;
         tg[q] = m < M ? target[m] : -1;
         if (STOP) { smx[q] = -INFINITY; ssum[q] = 0.f; }
+    }
+    // TOPK: s_tv / s_ti [128 rows][CW_TOP_LOGPROBS_MAX], sorted best first, (-inf, INT_MAX) where empty; kv / ki: the topk-th pair
+    __shared__ float s_tv[TOPK ? 128 * CW_TOP_LOGPROBS_MAX : 1];
+    __shared__ int s_ti[TOPK ? 128 * CW_TOP_LOGPROBS_MAX : 1];
+    float kv[8];
+    int ki[8];
+    if (TOPK) {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            s_tv[wave * 32 * CW_TOP_LOGPROBS_MAX + e * 64 + lane] = -INFINITY;
+            s_ti[wave * 32 * CW_TOP_LOGPROBS_MAX + e * 64 + lane] = 0x7fffffff;
+        }
+#pragma unroll
+        for (int q = 0; q < 8; ++q) { kv[q] = -INFINITY; ki[q] = 0x7fffffff; }
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
     }
     const bf16_t* a0 = A + (size_t)(m0 + l15) * K + g * 8;
     const bf16_t* a1 = a0 + (size_t)16 * K;
@@ -133,6 +160,45 @@ __global__ __launch_bounds__(256) void score_head_kernel(const bf16_t* __restric
                 sum[q] = (mx[q] > -INFINITY ? sum[q] * expf(mx[q] - mnew) : 0.f) + add;
                 mx[q] = mnew;
             }
+            if (TOPK) {
+                const int lrow = (wave * 32 + i * 16 + g * 4 + r) * CW_TOP_LOGPROBS_MAX;
+                const int last = lrow + topk - 1;
+                const bool row_ok = m0 + i * 16 + g * 4 + r < M;
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    const int n = (t0 + j) * 16 + l15;
+                    // v is -inf already for a padding column, and a NaN passes no comparison.  The full order, not the value
+                    // alone: the 16 lanes of a row do not meet the ids of a tile group in ascending order.
+                    const bool offer = row_ok && v[j] > -INFINITY && score_better(v[j], n, kv[q], ki[q]);
+                    unsigned long long pend = __ballot(offer);
+                    if (pend == 0) continue;
+                    while (pend) {                                            // (the same in every lane)
+                        const unsigned grp = (unsigned)(pend >> (g * 16)) & 0xffffu;
+                        if (grp != 0 && l15 == __ffs(grp) - 1 && score_better(v[j], n, s_tv[last], s_ti[last])) {
+                            int p = topk - 1;                                 // the list's last pair leaves; shift until v fits
+                            while (p > 0) {
+                                const float pv = s_tv[lrow + p - 1];
+                                const int pi = s_ti[lrow + p - 1];
+                                if (!score_better(v[j], n, pv, pi)) break;
+                                s_tv[lrow + p] = pv; s_ti[lrow + p] = pi;
+                                --p;
+                            }
+                            s_tv[lrow + p] = v[j]; s_ti[lrow + p] = n;
+                        }
+                        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+                        __builtin_amdgcn_wave_barrier();
+                        unsigned long long rest = 0;                          // every group's lowest offer is served
+#pragma unroll
+                        for (int gg = 0; gg < 4; ++gg) {
+                            unsigned f = (unsigned)(pend >> (gg * 16)) & 0xffffu;
+                            f &= f - 1;
+                            rest |= (unsigned long long)f << (gg * 16);
+                        }
+                        pend = rest;
+                    }
+                    kv[q] = s_tv[last]; ki[q] = s_ti[last];
+                }
+            }
             if (STOP && stop_here) {
                 float sv[4];
                 float snew = smx[q];
@@ -187,18 +253,31 @@ __global__ __launch_bounds__(256) void score_head_kernel(const bf16_t* __restric
                 spart[(size_t)m * n_split + split] = sp;
             }
         }
+        if (TOPK && l15 < CW_TOP_LOGPROBS_MAX && m < M) {                     // the row's list, padded with the identity
+            const int e = (wave * 32 + (q >> 2) * 16 + g * 4 + (q & 3)) * CW_TOP_LOGPROBS_MAX + l15;
+            ScoreTopPart tp;
+            tp.v = s_tv[e]; tp.i = s_ti[e];
+            tpart[((size_t)m * n_split + split) * CW_TOP_LOGPROBS_MAX + l15] = tp;
+        }
     }
 }
 
 // one thread per row; STOP: stop_logprob[m] = logsumexp over S - logsumexp, -inf where no column of S exists
-template <bool STOP>
+// TOPK: one wave per row instead (every lane runs the same merge of the statistics, lane 0 writes them), then topk selection
+// rounds over the row's n_split x CW_TOP_LOGPROBS_MAX pairs: in each, the best pair behind the one the round before took --
+// pairs are distinct (one per column), so "behind" needs no marks.  alt_id / alt_logprob [M][CW_TOP_LOGPROBS_MAX]: z - lse with
+// the lse logprob is written with; -1 / NaN at the ranks no candidate fills and at ranks >= topk.
+template <bool STOP, bool TOPK = false>
 __global__ __launch_bounds__(256) void score_combine_kernel(const ScorePart* __restrict__ part, int M, int n_split,
                                                             float* __restrict__ logprob, int* __restrict__ top_id,
                                                             float* __restrict__ top_logprob,
                                                             const ScoreStopPart* __restrict__ spart,
-                                                            float* __restrict__ stop_logprob) {
-    const int m = blockIdx.x * 256 + threadIdx.x;
+                                                            float* __restrict__ stop_logprob,
+                                                            const ScoreTopPart* __restrict__ tpart, int topk,
+                                                            int* __restrict__ alt_id, float* __restrict__ alt_logprob) {
+    const int m = TOPK ? blockIdx.x * 4 + (threadIdx.x >> 6) : blockIdx.x * 256 + threadIdx.x;
     if (m >= M) return;
+    const bool writer = !TOPK || (threadIdx.x & 63) == 0;
     const ScorePart* p = part + (size_t)m * n_split;
     float mx = -INFINITY, tl = -INFINITY, bv = -INFINITY;
     int bi = 0x7fffffff;
@@ -211,9 +290,11 @@ __global__ __launch_bounds__(256) void score_combine_kernel(const ScorePart* __r
     for (int s = 0; s < n_split; ++s)
         if (p[s].mx > -INFINITY) sum += p[s].sum * expf(p[s].mx - mx);
     const float lse = mx + logf(sum);
-    logprob[m] = tl - lse;
-    top_id[m] = bi;
-    top_logprob[m] = bv - lse;
+    if (writer) {
+        logprob[m] = tl - lse;
+        top_id[m] = bi;
+        top_logprob[m] = bv - lse;
+    }
     if (STOP) {
         const ScoreStopPart* sp = spart + (size_t)m * n_split;
         float smx = -INFINITY;
@@ -221,20 +302,53 @@ __global__ __launch_bounds__(256) void score_combine_kernel(const ScorePart* __r
         float ssum = 0.f;
         for (int s = 0; s < n_split; ++s)
             if (sp[s].mx > -INFINITY) ssum += sp[s].sum * expf(sp[s].mx - smx);
-        stop_logprob[m] = smx > -INFINITY ? (smx + logf(ssum)) - lse : -INFINITY;
+        if (writer) stop_logprob[m] = smx > -INFINITY ? (smx + logf(ssum)) - lse : -INFINITY;
+    }
+    if (TOPK) {
+        const int lane = threadIdx.x & 63, n_pairs = n_split * CW_TOP_LOGPROBS_MAX;
+        const ScoreTopPart* tp = tpart + (size_t)m * n_pairs;
+        float pv = INFINITY;                                                  // the pair the round before took
+        int pi = -1;
+        for (int j = 0; j < CW_TOP_LOGPROBS_MAX; ++j) {
+            float cv = -INFINITY;
+            int ci = 0x7fffffff;
+            if (j < topk) {
+                for (int e = lane; e < n_pairs; e += 64) {
+                    const ScoreTopPart c = tp[e];
+                    if (c.v > -INFINITY && score_better(pv, pi, c.v, c.i) && score_better(c.v, c.i, cv, ci)) { cv = c.v; ci = c.i; }
+                }
+                for (int o = 32; o > 0; o >>= 1) {
+                    const float ov = __shfl_xor(cv, o, 64);
+                    const int oi = __shfl_xor(ci, o, 64);
+                    if (score_better(ov, oi, cv, ci)) { cv = ov; ci = oi; }
+                }
+            }
+            const bool any = cv > -INFINITY;
+            if (lane == 0) {
+                alt_id[(size_t)m * CW_TOP_LOGPROBS_MAX + j] = any ? ci : -1;
+                alt_logprob[(size_t)m * CW_TOP_LOGPROBS_MAX + j] = any ? cv - lse : __builtin_nanf("");
+            }
+            if (any) { pv = cv; pi = ci; } else { pv = -INFINITY; pi = -1; }     // no candidate left: none in later rounds either
+        }
     }
 }
 
 // one block per row of f32 logits [rows][ldv]; target[row * t_stride + t] (negative: no target, the row's logprob is -inf);
 // results at out[row * t_stride + t].  STOP: stop_logprob likewise, from a second (maximum, sum) pass over the columns of S
-template <bool STOP>
+// TOPK: topk block-wide selection rounds over the same row behind that, each taking the best (logit, id) behind the pair of the
+// round before; alt_id / alt_logprob [rows][t_stride][CW_TOP_LOGPROBS_MAX] = logit - lse with the lse above, -1 / NaN at the
+// ranks no candidate fills (a candidate is a column < V with a logit > -inf; a NaN is none) and at ranks >= topk
+template <bool STOP, bool TOPK = false>
 __global__ __launch_bounds__(256) void score_rows_kernel(const float* __restrict__ logits, int ldv, int V,
                                                          const int* __restrict__ target, int t_stride, int t,
                                                          float* __restrict__ logprob, int* __restrict__ top_id,
                                                          float* __restrict__ top_logprob, int eos, int ts_begin,
-                                                         float* __restrict__ stop_logprob) {
+                                                         float* __restrict__ stop_logprob, int topk,
+                                                         int* __restrict__ alt_id, float* __restrict__ alt_logprob) {
     __shared__ float s_v[4], s_s[4], s_sv[4], s_ss[4];
     __shared__ int s_i[4];
+    __shared__ float s_lse, s_cv[2][4];                                       // TOPK only: rounds alternate between two slots
+    __shared__ int s_ci[2][4];
     const int row = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const float* lg = logits + (size_t)row * ldv;
     float bv = -INFINITY;
@@ -282,6 +396,37 @@ __global__ __launch_bounds__(256) void score_rows_kernel(const float* __restrict
         top_logprob[o] = bv - lse;
         if (STOP)
             stop_logprob[o] = smx > -INFINITY ? (smx + logf((s_ss[0] + s_ss[1]) + (s_ss[2] + s_ss[3]))) - lse : -INFINITY;
+        if (TOPK) s_lse = lse;
+    }
+    if (TOPK) {
+        float pv = INFINITY;                                                  // the pair the round before took
+        int pi = -1;
+        const size_t o = ((size_t)row * t_stride + t) * CW_TOP_LOGPROBS_MAX;
+        for (int j = 0; j < topk; ++j) {
+            float cv = -INFINITY;
+            int ci = 0x7fffffff;
+            for (int n = tid; n < V; n += 256) {
+                const float x = lg[n];
+                if (x > -INFINITY && score_better(pv, pi, x, n) && score_better(x, n, cv, ci)) { cv = x; ci = n; }
+            }
+            for (int of = 32; of > 0; of >>= 1) {
+                const float ov = __shfl_xor(cv, of, 64);
+                const int oi = __shfl_xor(ci, of, 64);
+                if (score_better(ov, oi, cv, ci)) { cv = ov; ci = oi; }
+            }
+            if (lane == 0) { s_cv[j & 1][wave] = cv; s_ci[j & 1][wave] = ci; }
+            __syncthreads();                                                  // (the first one also publishes s_lse)
+            cv = s_cv[j & 1][0]; ci = s_ci[j & 1][0];
+            for (int w = 1; w < 4; ++w)
+                if (score_better(s_cv[j & 1][w], s_ci[j & 1][w], cv, ci)) { cv = s_cv[j & 1][w]; ci = s_ci[j & 1][w]; }
+            const bool any = cv > -INFINITY;
+            if (tid == 0) {
+                alt_id[o + j] = any ? ci : -1;
+                alt_logprob[o + j] = any ? cv - s_lse : __builtin_nanf("");
+            }
+            if (any) { pv = cv; pi = ci; } else { pv = -INFINITY; pi = -1; }
+        }
+        if (tid >= topk && tid < CW_TOP_LOGPROBS_MAX) { alt_id[o + tid] = -1; alt_logprob[o + tid] = __builtin_nanf(""); }
     }
 }
 
@@ -308,9 +453,9 @@ int cw_launch_score_head(const void* A, const void* W, const int* target, ScoreP
     int tps = 0;
     const int ns = cw_score_head_splits(M, V, &tps);
     hipLaunchKernelGGL((score_head_kernel<false, false>), dim3((M + 127) / 128, ns), dim3(256), 0, st, (const bf16_t*)A,
-                       (const bf16_t*)W, target, part, M, V, K, tps, ns, (float*)nullptr, 0, (ScoreStopPart*)nullptr, 0, 0);
+                       (const bf16_t*)W, target, part, M, V, K, tps, ns, (float*)nullptr, 0, (ScoreStopPart*)nullptr, 0, 0, (ScoreTopPart*)nullptr, 0);
     hipLaunchKernelGGL(score_combine_kernel<false>, dim3((M + 255) / 256), dim3(256), 0, st, part, M, ns, logprob, top_id,
-                       top_logprob, (const ScoreStopPart*)nullptr, (float*)nullptr);
+                       top_logprob, (const ScoreStopPart*)nullptr, (float*)nullptr, (const ScoreTopPart*)nullptr, 0, (int*)nullptr, (float*)nullptr);
     return CW_OK;
 }
 
@@ -322,9 +467,9 @@ int cw_launch_score_head_stop(const void* A, const void* W, const int* target, S
     int tps = 0;
     const int ns = cw_score_head_splits(M, V, &tps);
     hipLaunchKernelGGL((score_head_kernel<false, true>), dim3((M + 127) / 128, ns), dim3(256), 0, st, (const bf16_t*)A,
-                       (const bf16_t*)W, target, part, M, V, K, tps, ns, (float*)nullptr, 0, spart, eos, ts_begin);
+                       (const bf16_t*)W, target, part, M, V, K, tps, ns, (float*)nullptr, 0, spart, eos, ts_begin, (ScoreTopPart*)nullptr, 0);
     hipLaunchKernelGGL(score_combine_kernel<true>, dim3((M + 255) / 256), dim3(256), 0, st, part, M, ns, logprob, top_id,
-                       top_logprob, (const ScoreStopPart*)spart, stop_logprob);
+                       top_logprob, (const ScoreStopPart*)spart, stop_logprob, (const ScoreTopPart*)nullptr, 0, (int*)nullptr, (float*)nullptr);
     return CW_OK;
 }
 
@@ -335,9 +480,9 @@ int cw_launch_score_head_unfused(const void* A, const void* W, const int* target
     int tps = 0;
     const int ns = cw_score_head_splits(M, V, &tps);
     hipLaunchKernelGGL((score_head_kernel<true, false>), dim3((M + 127) / 128, ns), dim3(256), 0, st, (const bf16_t*)A,
-                       (const bf16_t*)W, target, (ScorePart*)nullptr, M, V, K, tps, ns, logits, ldv, (ScoreStopPart*)nullptr, 0, 0);
+                       (const bf16_t*)W, target, (ScorePart*)nullptr, M, V, K, tps, ns, logits, ldv, (ScoreStopPart*)nullptr, 0, 0, (ScoreTopPart*)nullptr, 0);
     hipLaunchKernelGGL(score_rows_kernel<false>, dim3(M), dim3(256), 0, st, (const float*)logits, ldv, V, target, 1, 0, logprob,
-                       top_id, top_logprob, 0, 0, (float*)nullptr);
+                       top_id, top_logprob, 0, 0, (float*)nullptr, 0, (int*)nullptr, (float*)nullptr);
     return CW_OK;
 }
 
@@ -345,7 +490,7 @@ int cw_launch_score_rows(const float* logits, int ldv, int V, const int* target,
                          int* top_id, float* top_logprob, hipStream_t st) {
     if (rows < 1 || V < 1 || ldv < V || t < 0 || t >= t_stride) return CW_ERR_INVALID;
     hipLaunchKernelGGL(score_rows_kernel<false>, dim3(rows), dim3(256), 0, st, logits, ldv, V, target, t_stride, t, logprob,
-                       top_id, top_logprob, 0, 0, (float*)nullptr);
+                       top_id, top_logprob, 0, 0, (float*)nullptr, 0, (int*)nullptr, (float*)nullptr);
     return CW_OK;
 }
 
@@ -353,7 +498,66 @@ int cw_launch_score_rows_stop(const float* logits, int ldv, int V, const int* ta
                               int ts_begin, float* logprob, int* top_id, float* top_logprob, float* stop_logprob, hipStream_t st) {
     if (rows < 1 || V < 1 || ldv < V || t < 0 || t >= t_stride || eos < 0 || ts_begin < 0) return CW_ERR_INVALID;
     hipLaunchKernelGGL(score_rows_kernel<true>, dim3(rows), dim3(256), 0, st, logits, ldv, V, target, t_stride, t, logprob,
-                       top_id, top_logprob, eos, ts_begin, stop_logprob);
+                       top_id, top_logprob, eos, ts_begin, stop_logprob, 0, (int*)nullptr, (float*)nullptr);
+    return CW_OK;
+}
+
+// ---- TOPK forms (cw_set_score_top_logprobs): k = 1 .. CW_TOP_LOGPROBS_MAX alternatives per row beside what the plain forms write.
+// tpart: cw_score_head_splits(M, V) x CW_TOP_LOGPROBS_MAX records per row; alt_id / alt_logprob [M][CW_TOP_LOGPROBS_MAX]
+int cw_launch_score_head_top(const void* A, const void* W, const int* target, ScorePart* part, ScoreTopPart* tpart, int M, int V, int K,
+                             int k, float* logprob, int* top_id, float* top_logprob, int* alt_id, float* alt_logprob, hipStream_t st) {
+    if (M < 1 || V < 1 || K < 32 || K % 32 || k < 1 || k > CW_TOP_LOGPROBS_MAX || !tpart || !alt_id || !alt_logprob) return CW_ERR_INVALID;
+    int tps = 0;
+    const int ns = cw_score_head_splits(M, V, &tps);
+    hipLaunchKernelGGL((score_head_kernel<false, false, true>), dim3((M + 127) / 128, ns), dim3(256), 0, st, (const bf16_t*)A,
+                       (const bf16_t*)W, target, part, M, V, K, tps, ns, (float*)nullptr, 0, (ScoreStopPart*)nullptr, 0, 0, tpart, k);
+    hipLaunchKernelGGL((score_combine_kernel<false, true>), dim3((M + 3) / 4), dim3(256), 0, st, part, M, ns, logprob, top_id,
+                       top_logprob, (const ScoreStopPart*)nullptr, (float*)nullptr, (const ScoreTopPart*)tpart, k, alt_id, alt_logprob);
+    return CW_OK;
+}
+
+int cw_launch_score_head_stop_top(const void* A, const void* W, const int* target, ScorePart* part, ScoreStopPart* spart,
+                                  ScoreTopPart* tpart, int M, int V, int K, int eos, int ts_begin, int k, float* logprob, int* top_id,
+                                  float* top_logprob, float* stop_logprob, int* alt_id, float* alt_logprob, hipStream_t st) {
+    if (M < 1 || V < 1 || K < 32 || K % 32 || eos < 0 || ts_begin < 0 || k < 1 || k > CW_TOP_LOGPROBS_MAX || !tpart || !alt_id ||
+        !alt_logprob) return CW_ERR_INVALID;
+    int tps = 0;
+    const int ns = cw_score_head_splits(M, V, &tps);
+    hipLaunchKernelGGL((score_head_kernel<false, true, true>), dim3((M + 127) / 128, ns), dim3(256), 0, st, (const bf16_t*)A,
+                       (const bf16_t*)W, target, part, M, V, K, tps, ns, (float*)nullptr, 0, spart, eos, ts_begin, tpart, k);
+    hipLaunchKernelGGL((score_combine_kernel<true, true>), dim3((M + 3) / 4), dim3(256), 0, st, part, M, ns, logprob, top_id,
+                       top_logprob, (const ScoreStopPart*)spart, stop_logprob, (const ScoreTopPart*)tpart, k, alt_id, alt_logprob);
+    return CW_OK;
+}
+
+// the GEMM of cw_launch_score_head_unfused alone: f32 logits [M][ldv] (the accumulators the fused forms reduce)
+int cw_launch_score_head_store(const void* A, const void* W, const int* target, float* logits, int ldv, int M, int V, int K, hipStream_t st) {
+    if (M < 1 || V < 1 || ldv < V || K < 32 || K % 32 || !logits) return CW_ERR_INVALID;
+    int tps = 0;
+    const int ns = cw_score_head_splits(M, V, &tps);
+    hipLaunchKernelGGL((score_head_kernel<true, false>), dim3((M + 127) / 128, ns), dim3(256), 0, st, (const bf16_t*)A,
+                       (const bf16_t*)W, target, (ScorePart*)nullptr, M, V, K, tps, ns, logits, ldv,
+                       (ScoreStopPart*)nullptr, 0, 0, (ScoreTopPart*)nullptr, 0);
+    return CW_OK;
+}
+
+// alt_id / alt_logprob [rows][t_stride][CW_TOP_LOGPROBS_MAX], written at [row][t]
+int cw_launch_score_rows_top(const float* logits, int ldv, int V, const int* target, int t_stride, int t, int rows, int k,
+                             float* logprob, int* top_id, float* top_logprob, int* alt_id, float* alt_logprob, hipStream_t st) {
+    if (rows < 1 || V < 1 || ldv < V || t < 0 || t >= t_stride || k < 1 || k > CW_TOP_LOGPROBS_MAX || !alt_id || !alt_logprob)
+        return CW_ERR_INVALID;
+    hipLaunchKernelGGL((score_rows_kernel<false, true>), dim3(rows), dim3(256), 0, st, logits, ldv, V, target, t_stride, t, logprob,
+                       top_id, top_logprob, 0, 0, (float*)nullptr, k, alt_id, alt_logprob);
+    return CW_OK;
+}
+
+int cw_launch_score_rows_stop_top(const float* logits, int ldv, int V, const int* target, int t_stride, int t, int rows, int eos,
+                                  int ts_begin, int k, float* logprob, int* top_id, float* top_logprob, float* stop_logprob,
+                                  int* alt_id, float* alt_logprob, hipStream_t st) {
+    if (rows < 1 || V < 1 || ldv < V || t < 0 || t >= t_stride || eos < 0 || ts_begin < 0 || k < 1 || k > CW_TOP_LOGPROBS_MAX ||
+        !alt_id || !alt_logprob) return CW_ERR_INVALID;
+    hipLaunchKernelGGL((score_rows_kernel<true, true>), dim3(rows), dim3(256), 0, st, logits, ldv, V, target, t_stride, t, logprob,
+                       top_id, top_logprob, eos, ts_begin, stop_logprob, k, alt_id, alt_logprob);
     return CW_OK;
 }
 

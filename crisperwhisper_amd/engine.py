@@ -582,11 +582,35 @@ class Engine:
             table[b, :len(r)] = r
         return n, stride, table
 
-    def score_tokens(self, rows, n_init: int, rows_per_item: int = 1):
+    def set_score_top_logprobs(self, k: int):
+        """cw_set_score_top_logprobs: the k best alternatives (0 = off, 1 .. 8) of every position the scoring calls score."""
+        self._chk(self.lib.cw_set_score_top_logprobs(self.ctx, int(k)))
+
+    def _with_score_top(self, k, call, nr, stride, n, n_init):
+        """Runs ``call`` (one of the scoring calls) with ``cw_set_score_top_logprobs(k)`` on around it -- off again afterwards,
+        also when the call raises -- and returns its alternatives per row: (ids int64 [n][k], logprobs float32 [n][k])."""
+        k = int(k)
+        if not 1 <= k <= 8:
+            raise ValueError(f"top_logprobs must be an integer in 0 .. 8, got {k!r}")
+        self.set_score_top_logprobs(k)
+        try:
+            call()
+            ai = np.zeros((nr, stride, k), dtype=np.int32)
+            al = np.zeros((nr, stride, k), dtype=np.float32)
+            self._chk(self.lib.cw_get_score_top_logprobs(self.ctx, _ptr(ai), _ptr(al), nr, stride))
+        finally:
+            self.set_score_top_logprobs(0)
+        i0 = int(n_init)
+        return ([ai[b, i0:n[b]].astype(np.int64) for b in range(nr)], [al[b, i0:n[b]].copy() for b in range(nr)])
+
+    def score_tokens(self, rows, n_init: int, rows_per_item: int = 1, top_logprobs: int = 0):
         """Teacher-forced log-probabilities (cw_score_tokens): ``rows[r]`` is a whole decoder input (``n_init`` init tokens,
         transcript, eos), scored against resident feature item r // rows_per_item.  Returns (logprob, top_id, top_logprob):
         per row one array over its text tokens and the eos (len(rows[r]) - n_init entries) -- log p(token | audio, tokens
-        before it) over the raw logits, and the arg-max id of the same distribution with its log-probability."""
+        before it) over the raw logits, and the arg-max id of the same distribution with its log-probability.
+        ``top_logprobs=k`` (1 .. 8): two more entries, per row the ids [n][k] and log-probabilities [n][k] of the k best
+        tokens of every scored position, best first, ties to the lower id, -1 / NaN past the candidates
+        (``cw_set_score_top_logprobs``)."""
         nr = len(rows)
         rpi = int(rows_per_item)
         if rpi >= 1 and nr % rpi:
@@ -595,15 +619,18 @@ class Engine:
         lp = np.zeros((nr, stride), dtype=np.float32)
         ti = np.zeros((nr, stride), dtype=np.int32)
         tl = np.zeros((nr, stride), dtype=np.float32)
-        self._chk(self.lib.cw_score_tokens(self.ctx, nr // rpi if rpi >= 1 else nr, rpi, _ptr(table), stride, _ptr(n), int(n_init),
-                                           _ptr(lp), _ptr(ti), _ptr(tl)))
+        def call():
+            self._chk(self.lib.cw_score_tokens(self.ctx, nr // rpi if rpi >= 1 else nr, rpi, _ptr(table), stride, _ptr(n), int(n_init),
+                                               _ptr(lp), _ptr(ti), _ptr(tl)))
+        alts = self._with_score_top(top_logprobs, call, nr, stride, n, n_init) if top_logprobs else call() or ()
         k = int(n_init)
         return ([lp[b, k:n[b]].copy() for b in range(nr)], [ti[b, k:n[b]].astype(np.int64) for b in range(nr)],
-                [tl[b, k:n[b]].copy() for b in range(nr)])
+                [tl[b, k:n[b]].copy() for b in range(nr)]) + tuple(alts)
 
-    def align_score_tokens(self, num_frames, ids, n_init: int):
+    def align_score_tokens(self, num_frames, ids, n_init: int, top_logprobs: int = 0):
         """cw_align_score_tokens: ``align_tokens`` and ``score_tokens`` (one row per item) of the same rows in one forward.
-        Returns (timestamps as align_tokens, logprob, top_id, top_logprob as score_tokens)."""
+        Returns (timestamps as align_tokens, logprob, top_id, top_logprob as score_tokens[, with ``top_logprobs=k`` its
+        alternative ids and log-probabilities])."""
         nb = len(ids)
         n, stride, table = self._token_table(ids)
         nf = _i32(num_frames)
@@ -611,13 +638,15 @@ class Engine:
         lp = np.zeros((nb, stride), dtype=np.float32)
         ti = np.zeros((nb, stride), dtype=np.int32)
         tl = np.zeros((nb, stride), dtype=np.float32)
-        self._chk(self.lib.cw_align_score_tokens(self.ctx, nb, _ptr(nf), _ptr(table), stride, _ptr(n), int(n_init), _ptr(ts),
-                                                 _ptr(lp), _ptr(ti), _ptr(tl)))
+        def call():
+            self._chk(self.lib.cw_align_score_tokens(self.ctx, nb, _ptr(nf), _ptr(table), stride, _ptr(n), int(n_init), _ptr(ts),
+                                                     _ptr(lp), _ptr(ti), _ptr(tl)))
+        alts = self._with_score_top(top_logprobs, call, nb, stride, n, n_init) if top_logprobs else call() or ()
         k = int(n_init)
         return ([ts[b, :n[b]].copy() for b in range(nb)], [lp[b, k:n[b]].copy() for b in range(nb)],
-                [ti[b, k:n[b]].astype(np.int64) for b in range(nb)], [tl[b, k:n[b]].copy() for b in range(nb)])
+                [ti[b, k:n[b]].astype(np.int64) for b in range(nb)], [tl[b, k:n[b]].copy() for b in range(nb)]) + tuple(alts)
 
-    def align_cut_tokens(self, num_frames, ids, n_init: int, cut_ok, force_all):
+    def align_cut_tokens(self, num_frames, ids, n_init: int, cut_ok, force_all, top_logprobs: int = 0):
         """cw_align_cut_tokens: how much of each offered transcript was spoken inside its window, and the alignment of that part,
         in the one forward of ``align_score_tokens``.  ``ids`` as ``align_tokens`` takes them (row b offers N_b = len(ids[b]) -
         n_init - 1 text tokens); ``cut_ok[b]``: N_b + 1 flags, entry n allowing "keep the first n tokens"; ``force_all[b]``: keep
@@ -625,7 +654,8 @@ class Engine:
         entries, what ``align_tokens`` gives for the kept prefix followed by eos, logprob / stop_logprob / top_id / top_logprob: per
         row len(ids[b]) - n_init entries as ``score_tokens`` returns them).  stop_logprob[k] is the log-probability that the
         text stops before position k (eos or any timestamp token); cut maximises sum(logprob[:n]) + stop_logprob[n] over the
-        allowed n, the lowest n on an exact tie."""
+        allowed n, the lowest n on an exact tie.  ``top_logprobs=k``: two more entries, the alternatives as ``score_tokens``
+        returns them (every offered position, not the kept prefix only)."""
         nb = len(ids)
         n, stride, table = self._token_table(ids)
         if len(cut_ok) != nb or len(force_all) != nb:
@@ -646,11 +676,13 @@ class Engine:
         sl = np.zeros((nb, stride), dtype=np.float32)
         ti = np.zeros((nb, stride), dtype=np.int32)
         tl = np.zeros((nb, stride), dtype=np.float32)
-        self._chk(self.lib.cw_align_cut_tokens(self.ctx, nb, _ptr(nf), _ptr(table), stride, _ptr(n), k, _ptr(ok), _ptr(force),
-                                               _ptr(cut), _ptr(score), _ptr(ts), _ptr(lp), _ptr(sl), _ptr(ti), _ptr(tl)))
+        def call():
+            self._chk(self.lib.cw_align_cut_tokens(self.ctx, nb, _ptr(nf), _ptr(table), stride, _ptr(n), k, _ptr(ok), _ptr(force),
+                                                   _ptr(cut), _ptr(score), _ptr(ts), _ptr(lp), _ptr(sl), _ptr(ti), _ptr(tl)))
+        alts = self._with_score_top(top_logprobs, call, nb, stride, n, k) if top_logprobs else call() or ()
         return (cut.astype(np.int64), score, [ts[b, :k + cut[b] + 1].copy() for b in range(nb)],
                 [lp[b, k:n[b]].copy() for b in range(nb)], [sl[b, k:n[b]].copy() for b in range(nb)],
-                [ti[b, k:n[b]].astype(np.int64) for b in range(nb)], [tl[b, k:n[b]].copy() for b in range(nb)])
+                [ti[b, k:n[b]].astype(np.int64) for b in range(nb)], [tl[b, k:n[b]].copy() for b in range(nb)]) + tuple(alts)
 
     def test_score_head_stop(self, x, ln_g, ln_b, embed, targets, eos: int, timestamp_begin: int):
         """cw_test_score_head_stop: ``test_score_head`` through the STOP form of the head -> (logprob, top_id, top_logprob,
@@ -723,6 +755,62 @@ class Engine:
         self._chk(self.lib.cw_test_score_head(self.ctx, M, D, V, _ptr(x), _ptr(g), _ptr(b), _ptr(embed), _ptr(t), _ptr(lp),
                                               _ptr(ti), _ptr(tl)))
         return lp, ti, tl
+
+    def test_score_head_top(self, x, ln_g, ln_b, embed, targets, k: int, want_logits: bool = False, stop=None):
+        """cw_test_score_head_top (``stop`` = (eos, timestamp_begin): cw_test_score_head_stop_top): the TOPK form of the head ->
+        dict with logprob / top_id / top_logprob [M], alt_id / alt_logprob [M][8] (ranks >= k: -1 / NaN)[, stop_logprob [M]][,
+        logits [M][V]: the same operands through the logits-storing form]."""
+        x = np.ascontiguousarray(x, np.float32)
+        embed = np.ascontiguousarray(embed, np.float32)
+        g = np.ascontiguousarray(ln_g, np.float32)
+        b = np.ascontiguousarray(ln_b, np.float32)
+        t = _i32(targets)
+        M, D = x.shape
+        V = embed.shape[0]
+        if embed.shape[1] != D or g.shape != (D,) or b.shape != (D,) or t.shape != (M,):
+            raise ValueError("test_score_head_top: shapes do not agree")
+        out = {"logprob": np.zeros(M, np.float32), "top_id": np.zeros(M, np.int32), "top_logprob": np.zeros(M, np.float32),
+               "alt_id": np.full((M, 8), -7, np.int32), "alt_logprob": np.full((M, 8), 7.0, np.float32)}
+        lg = np.full((M, V), 7.0, np.float32) if want_logits else None
+        if stop is None:
+            self._chk(self.lib.cw_test_score_head_top(self.ctx, M, D, V, _ptr(x), _ptr(g), _ptr(b), _ptr(embed), _ptr(t), int(k),
+                                                      _ptr(out["logprob"]), _ptr(out["top_id"]), _ptr(out["top_logprob"]),
+                                                      _ptr(out["alt_id"]), _ptr(out["alt_logprob"]), _ptr(lg) if want_logits else None))
+        else:
+            out["stop_logprob"] = np.zeros(M, np.float32)
+            self._chk(self.lib.cw_test_score_head_stop_top(self.ctx, M, D, V, _ptr(x), _ptr(g), _ptr(b), _ptr(embed), _ptr(t),
+                                                           int(stop[0]), int(stop[1]), int(k), _ptr(out["logprob"]),
+                                                           _ptr(out["top_id"]), _ptr(out["top_logprob"]), _ptr(out["stop_logprob"]),
+                                                           _ptr(out["alt_id"]), _ptr(out["alt_logprob"]),
+                                                           _ptr(lg) if want_logits else None))
+        if want_logits:
+            out["logits"] = lg
+        return out
+
+    def test_score_rows_top(self, logits, V: int, targets, k: int, stop=None):
+        """cw_test_score_rows_top: the loop path's row kernel (TOPK form) over f32 ``logits`` [rows][ldv], columns 0 .. V-1 ->
+        dict as ``test_score_head_top`` (``stop`` = (eos, timestamp_begin): the STOP form, with stop_logprob)."""
+        lg = np.ascontiguousarray(logits, np.float32)
+        rows, ldv = lg.shape
+        t = _i32(targets)
+        if t.shape != (rows,):
+            raise ValueError("test_score_rows_top: shapes do not agree")
+        out = {"logprob": np.zeros(rows, np.float32), "top_id": np.zeros(rows, np.int32), "top_logprob": np.zeros(rows, np.float32),
+               "alt_id": np.full((rows, 8), -7, np.int32), "alt_logprob": np.full((rows, 8), 7.0, np.float32)}
+        if stop is not None:
+            out["stop_logprob"] = np.zeros(rows, np.float32)
+        self._chk(self.lib.cw_test_score_rows_top(self.ctx, rows, int(V), ldv, _ptr(lg), _ptr(t), int(k),
+                                                  int(stop[0]) if stop is not None else 0, int(stop[1]) if stop is not None else 0,
+                                                  _ptr(out["logprob"]), _ptr(out["top_id"]), _ptr(out["top_logprob"]),
+                                                  _ptr(out["stop_logprob"]) if stop is not None else None, _ptr(out["alt_id"]),
+                                                  _ptr(out["alt_logprob"])))
+        return out
+
+    def time_score_head_top(self, M: int, k: int, stop: bool = False, iters: int = 10) -> float:
+        """cw_time_score_head_top: ms per run of the fused head (``stop``: its STOP form) with k alternatives per row (0: none)."""
+        ms = C.c_float(0.0)
+        self._chk(self.lib.cw_time_score_head_top(self.ctx, int(M), int(k), 1 if stop else 0, int(iters), C.byref(ms)))
+        return float(ms.value)
 
     def time_score_head(self, M: int, unfused: bool = False, iters: int = 10, stop: bool = False) -> float:
         """cw_time_score_head: ms per run of the scoring head over M rows at this engine's geometry (fused, or the unfused form

@@ -1005,7 +1005,7 @@ def check_transcript_ids(spec, ids) -> np.ndarray:
 
 def align(engine: Engine, n_items: int, num_frames, transcripts, *, language: Optional[str] = None,
           task: Optional[str] = None, return_scores: bool = False, return_alignment_scores: bool = False,
-          alignment_collar_frames: Optional[int] = None):
+          alignment_collar_frames: Optional[int] = None, top_logprobs: int = 0):
     """Forced alignment of known transcripts to the ``n_items`` 30 s feature windows resident in the engine.
 
     Row b is the decoder input <|startoftranscript|><|lang|><|task|> ++ transcripts[b] ++ eos, with the init tokens resolved by
@@ -1014,9 +1014,14 @@ def align(engine: Engine, n_items: int, num_frames, transcripts, *, language: Op
     transcripts), "token_timestamps": list of float32 arrays, one timestamp per transcript token} -- the fields the pipeline
     hands to ``collate.decode_asr``, as ``generate`` returns them for its own tokens.  ``return_scores=True`` runs the full
     scoring forward instead of the early-stopping one (cw_align_score_tokens: same timestamps) and adds "token_logprobs",
-    "top_ids", "top_logprobs": per transcript one entry per token plus one for the eos.  ``return_alignment_scores=True`` adds
-    "alignment_scores" and "alignment_spreads", one value per transcript token, as ``generate`` defines them."""
+    "top_ids", "top_logprobs": per transcript one entry per token plus one for the eos; with ``top_logprobs=k`` (1 .. 8) also
+    "alt_ids" / "alt_logprobs" [n][k], the k best tokens of each of those positions (``check_score_top_logprobs``).
+    ``return_alignment_scores=True`` adds "alignment_scores" and "alignment_spreads", one value per transcript token, as
+    ``generate`` defines them."""
     spec = engine.spec
+    want_top = check_score_top_logprobs(top_logprobs)
+    if want_top and not return_scores:
+        raise ValueError("top_logprobs lists the alternatives next to every token's log-probability: it needs return_scores=True")
     want_as = bool(return_alignment_scores)
     collar = check_alignment_collar(spec, alignment_collar_frames)
     if want_as and not hasattr(engine, "set_alignment_scores"):
@@ -1043,9 +1048,12 @@ def align(engine: Engine, n_items: int, num_frames, transcripts, *, language: Op
     rows = [np.concatenate([np.asarray(i, np.int64), t, [spec.eos_token_id]]) for i, t in zip(inits, texts)]
     set_alignment_scores(engine, want_as, collar)
     if return_scores:
-        ts, lp, ti, tl = engine.align_score_tokens(num_frames, rows, n_init)
+        # (the argument is passed only when set: an engine without it still serves the plain call)
+        ts, lp, ti, tl, *alts = engine.align_score_tokens(num_frames, rows, n_init, **({"top_logprobs": want_top} if want_top else {}))
         out = {"sequences": texts, "token_timestamps": [s[n_init:n_init + len(t)] for s, t in zip(ts, texts)],
                "token_logprobs": lp, "top_ids": ti, "top_logprobs": tl}
+        if want_top:
+            out["alt_ids"], out["alt_logprobs"] = alts
     else:
         ts = engine.align_tokens(num_frames, rows, n_init)
         out = {"sequences": texts, "token_timestamps": [s[n_init:n_init + len(t)] for s, t in zip(ts, texts)]}
@@ -1054,6 +1062,17 @@ def align(engine: Engine, n_items: int, num_frames, transcripts, *, language: Op
         out["alignment_scores"] = [mass[b, n_init:n_init + len(t)].copy() for b, t in enumerate(texts)]
         out["alignment_spreads"] = [spread[b, n_init:n_init + len(t)].copy() for b, t in enumerate(texts)]
     return out
+
+
+def check_score_top_logprobs(k) -> int:
+    """``top_logprobs`` of ``score`` / ``align`` / ``align_long``: None or an integer in 0 .. TOP_LOGPROBS_MAX -> int.  k > 0 asks
+    for the k best tokens of every teacher-forced position (``Engine.score_tokens``): value descending, the lower id on an exact
+    tie, over the raw logits with the normaliser of "token_logprobs"; -1 / NaN where fewer than k logits are finite."""
+    if k is None:
+        return 0
+    if isinstance(k, (bool, np.bool_)) or not isinstance(k, (int, np.integer)) or not 0 <= int(k) <= TOP_LOGPROBS_MAX:
+        raise ValueError(f"top_logprobs must be an integer in 0 .. {TOP_LOGPROBS_MAX}, got {k!r}")
+    return int(k)
 
 
 def check_text_ids(spec, ids) -> np.ndarray:
@@ -1071,7 +1090,7 @@ def check_text_ids(spec, ids) -> np.ndarray:
 def align_long(engine: Engine, pcms, transcripts, collate_words, *, language: Optional[str] = None, task: Optional[str] = None,
                return_scores: bool = False, return_alignment_scores: bool = False,
                alignment_collar_frames: Optional[int] = None, max_window_tokens: Optional[int] = None,
-               stats: Optional[dict] = None, item_ids=None, sampling_rate: int = 16000):
+               stats: Optional[dict] = None, item_ids=None, sampling_rate: int = 16000, top_logprobs: int = 0):
     """Forced alignment of known transcripts to recordings of any length: the walk behind ``CrisperWhisperPipeline.align_long``.
 
     ``pcms``: at most ``engine.max_batch`` mono float32 recordings at ``sampling_rate``; ``transcripts``: one per recording, text
@@ -1096,10 +1115,16 @@ def align_long(engine: Engine, pcms, transcripts, collate_words, *, language: Op
 
     Returns per recording {"text", "chunks": [{"text", "timestamp"}]}; ``return_scores``: "logprob" per chunk and "logprob" /
     "avg_logprob" over the kept tokens and the eos (scored once, where the last token is consumed);
-    ``return_alignment_scores``: "alignment_score" / "alignment_spread" per chunk.  ``stats["align_long"]`` gains one record
-    per (recording, window): {"item", "seek_s", "offered", "cut", "cut_score", "forced"}."""
+    ``return_alignment_scores``: "alignment_score" / "alignment_spread" per chunk.  ``top_logprobs=k`` (needs
+    ``return_scores``): every chunk gains "tokens", one {"id", "logprob", "alt_ids", "alt_logprobs"} per token of its group --
+    the k best tokens of that position, carried through the cut as the log-probabilities are: the kept prefix of a window
+    only.  ``stats["align_long"]`` gains one record per (recording, window): {"item", "seek_s", "offered", "cut", "cut_score",
+    "forced"}."""
     spec = engine.spec
     n_rec = len(pcms)
+    want_top = check_score_top_logprobs(top_logprobs)
+    if want_top and not return_scores:
+        raise ValueError("top_logprobs lists the alternatives next to every token's log-probability: it needs return_scores=True")
     want_as = bool(return_alignment_scores)
     collar = check_alignment_collar(spec, alignment_collar_frames)
     if want_as and not hasattr(engine, "set_alignment_scores"):
@@ -1176,7 +1201,8 @@ def align_long(engine: Engine, pcms, transcripts, collate_words, *, language: Op
                     ok[x - r.pos] = True
             rows.append(np.concatenate([np.asarray(r.init, np.int64), r.T[r.pos:r.pos + L], [spec.eos_token_id]]))
             masks.append(ok); forced.append(last); offered.append(L)
-        cut, cut_score, ts, lp, _, _, _ = engine.align_cut_tokens(nf, rows, n_init, masks, forced)
+        cut, cut_score, ts, lp, _, _, _, *alts = engine.align_cut_tokens(nf, rows, n_init, masks, forced,
+                                                                       **({"top_logprobs": want_top} if want_top else {}))
         if want_as:
             mass, spread = engine.alignment_scores(len(active), max(n_init + int(c) for c in cut))
         for k, b in enumerate(active):
@@ -1195,6 +1221,11 @@ def align_long(engine: Engine, pcms, transcripts, collate_words, *, language: Op
                 if return_scores:
                     words = [{"text": w["text"], "timestamp": w["timestamp"], "logprob": float(np.sum(kept_lp[g]))}
                              for w, g in zip(words, groups)]
+                if want_top:                                 # the kept prefix's rows only, as kept_lp
+                    a_id, a_lp = alts[0][k][:c], alts[1][k][:c]
+                    for w, g in zip(words, groups):
+                        w["tokens"] = [{"id": int(r.T[r.pos + j]), "logprob": float(lp[k][j]), "alt_ids": a_id[j].copy(),
+                                        "alt_logprobs": a_lp[j].copy()} for j in g]
                 if want_as:
                     from .pipeline import add_alignment_scores
                     add_alignment_scores(words, groups, [mass[k, n_init:n_init + c]], [spread[k, n_init:n_init + c]])
@@ -1374,7 +1405,7 @@ def plan_score_calls(n_candidates: Sequence[int], max_batch: int):
 
 
 def score(engine: Engine, n_items: int, candidates, *, language: Optional[str] = None, task: Optional[str] = None,
-          load_items: Optional[Callable[[List[int]], None]] = None):
+          load_items: Optional[Callable[[List[int]], None]] = None, top_logprobs: int = 0):
     """Teacher-forced log-probabilities of candidate transcripts of the ``n_items`` 30 s feature windows resident in the engine.
 
     ``candidates[b]`` is a list of K_b transcripts (token ids, ``check_transcript_ids``).  Row (b, k) is the decoder input
@@ -1384,8 +1415,11 @@ def score(engine: Engine, n_items: int, candidates, *, language: Optional[str] =
     ``load_items(items)`` is called before such a call (and once more with all items at the end) to make them so -- the
     pipeline passes a function that computes their features again; without it only plans whose every call covers the items
     0 .. n-1 in order run (all items with one candidate count, fitting one call).  Returns per item a list over its candidates of
-    {"ids", "token_logprobs", "top_ids", "top_logprobs"}: one entry per token plus one for the eos."""
+    {"ids", "token_logprobs", "top_ids", "top_logprobs"}: one entry per token plus one for the eos ("top_logprobs" is the
+    arg-max's log-probability).  The argument ``top_logprobs=k`` (1 .. 8, ``check_score_top_logprobs``) adds "alt_ids" /
+    "alt_logprobs" [n][k]: the k best tokens of each of those positions."""
     spec = engine.spec
+    want_top = check_score_top_logprobs(top_logprobs)
     if len(candidates) != n_items:
         raise ValueError(f"{len(candidates)} candidate lists for {n_items} items")
     if n_items > engine.max_batch:
@@ -1421,11 +1455,13 @@ def score(engine: Engine, n_items: int, candidates, *, language: Optional[str] =
             resident = list(items)
         rows = [np.concatenate([np.asarray(inits[b], np.int64), texts[b][c0 + j], [spec.eos_token_id]])
                 for b, c0 in members for j in range(rpi)]
-        lp, ti, tl = engine.score_tokens(rows, n_init, rows_per_item=rpi)
+        lp, ti, tl, *alts = engine.score_tokens(rows, n_init, rows_per_item=rpi, **({"top_logprobs": want_top} if want_top else {}))
         r = 0
         for b, c0 in members:
             for j in range(rpi):
                 out[b][c0 + j] = {"ids": texts[b][c0 + j], "token_logprobs": lp[r], "top_ids": ti[r], "top_logprobs": tl[r]}
+                if want_top:
+                    out[b][c0 + j]["alt_ids"], out[b][c0 + j]["alt_logprobs"] = alts[0][r], alts[1][r]
                 r += 1
     if resident != list(range(n_items)) and load_items is not None:
         load_items(list(range(n_items)))

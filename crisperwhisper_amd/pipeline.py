@@ -423,6 +423,14 @@ def _check_top_logprobs(k) -> int:
     return int(k)
 
 
+def token_alternatives(vocab, token_id, alt_ids, alt_logprobs):
+    """One teacher-forced position's alternatives (``score(top_logprobs=k)``): ("top_logprobs": [{"id", "text", "logprob"}, ...]
+    best first, entries with id -1 left out; "rank": the index of ``token_id`` in that list, None when it is not among them)."""
+    top = [{"id": int(v), "text": token_text(vocab, v), "logprob": float(x)} for v, x in zip(alt_ids, alt_logprobs) if v >= 0]
+    rank = next((j for j, t in enumerate(top) if t["id"] == int(token_id)), None)
+    return top, rank
+
+
 class CrisperWhisperPipeline:
     def __init__(self, model, tokenizer=None, feature_extractor=None, chunk_length_s=0, stride_length_s=None,
                  batch_size=1, return_timestamps=None, torch_dtype=None, dtype=None, device=None,
@@ -848,6 +856,24 @@ class CrisperWhisperPipeline:
             pcms.append(pcm)
         return pcms
 
+    @staticmethod
+    def _check_align_top(who, top_logprobs, return_scores):
+        """``top_logprobs`` of ``align`` / ``align_long``, checked before anything is loaded."""
+        top_k = _check_top_logprobs(top_logprobs)
+        if top_k and not return_scores:
+            raise ValueError(f"{who}: top_logprobs lists the alternatives next to every token's log-probability: it needs "
+                             "return_scores=True")
+        return top_k
+
+    def _alt_tokens(self, ids, token_logprobs, alt_ids, alt_logprobs, group):
+        """"tokens" of one chunk: the tokens of ``group`` with their log-probability, alternatives and rank."""
+        toks = []
+        for i in np.asarray(group, np.int64).reshape(-1):
+            top, rank = token_alternatives(self.vocab, ids[i], alt_ids[i], alt_logprobs[i])
+            toks.append({"id": int(ids[i]), "text": token_text(self.vocab, ids[i]),
+                         "logprob": float(np.float32(token_logprobs[i])), "top_logprobs": top, "rank": rank})
+        return toks
+
     def _scored_words(self, ids, token_logprobs, token_timestamps=None, return_groups=False):
         """Words of one transcript with the sum of their tokens' log-probabilities, grouped by the collator itself
         (``return_groups=True``: its token groups as a third value)."""
@@ -887,13 +913,17 @@ class CrisperWhisperPipeline:
             raise ValueError("a transcript mixes token ids with other elements: give either one sequence of ids or a list of candidates")
         return list(t), True
 
-    def score(self, inputs, transcripts, language: Optional[str] = None, task: Optional[str] = None, **kwargs):
+    def score(self, inputs, transcripts, language: Optional[str] = None, task: Optional[str] = None, top_logprobs=None, **kwargs):
         """How well known transcripts fit the audio: teacher-forced log-probabilities under the model.  ``inputs`` as
         ``align`` takes them (one, or a list; each at most 30 s); ``transcripts[b]`` one transcript (``str`` or token ids) or
         a list of candidates for input b, which share one encoder pass.  Per input one dict, or a list of dicts in the order
         of the candidates: {"text", "logprob": sum over the tokens and the eos, "avg_logprob": logprob / (n_tokens + 1),
         "tokens": [{"id", "logprob", "top_id", "top_logprob"}] (the eos last), "chunks": [{"text", "logprob"}]} -- a word's
-        logprob is the sum over the tokens the collator groups into it.  Raw logits: no suppress lists, no timestamp rules."""
+        logprob is the sum over the tokens the collator groups into it.  Raw logits: no suppress lists, no timestamp rules.
+        ``top_logprobs=k`` (0 .. 8; the constructor's ``top_logprobs`` concerns ``__call__`` only): every entry of "tokens"
+        gains "top_logprobs": [{"id", "text", "logprob"}, ...], the k most probable tokens of that position best first (ties
+        to the lower id), and "rank": the index of the token's own id in that list, None when it is not among the k."""
+        top_k = _check_top_logprobs(top_logprobs)
         language, task = self._forced_kwargs("score", language, task, kwargs)
         single = not isinstance(inputs, (list, tuple))
         if single:
@@ -916,7 +946,8 @@ class CrisperWhisperPipeline:
             idx = list(range(b0, min(len(pcms), b0 + per)))
             eng.mel([pcms[i] for i in idx])
             out = generation.score(eng, len(idx), [cands[i] for i in idx], language=language, task=task,
-                                   load_items=lambda items: eng.mel([pcms[idx[j]] for j in items]))
+                                   load_items=lambda items: eng.mel([pcms[idx[j]] for j in items]),
+                                   **({"top_logprobs": top_k} if top_k else {}))
             for k, i in enumerate(idx):
                 rs = []
                 for o in out[k]:
@@ -924,6 +955,9 @@ class CrisperWhisperPipeline:
                     text, chunks = self._scored_words(o["ids"], lp[:-1])
                     toks = [{"id": int(t), "logprob": float(a), "top_id": int(ti), "top_logprob": float(tl)}
                             for t, a, ti, tl in zip(list(o["ids"]) + [eos], lp, o["top_ids"], o["top_logprobs"])]
+                    if top_k:
+                        for t, ai, al in zip(toks, o["alt_ids"], o["alt_logprobs"]):
+                            t["top_logprobs"], t["rank"] = token_alternatives(self.vocab, t["id"], ai, al)
                     total = float(lp.sum())
                     rs.append({"text": text, "logprob": total, "avg_logprob": total / (len(o["ids"]) + 1), "tokens": toks,
                                "chunks": chunks})
@@ -932,7 +966,7 @@ class CrisperWhisperPipeline:
 
     def align(self, inputs, transcripts, language: Optional[str] = None, task: Optional[str] = None,
               return_scores: bool = False, return_alignment_scores: bool = False,
-              alignment_collar_frames: Optional[int] = None, **kwargs):
+              alignment_collar_frames: Optional[int] = None, top_logprobs=None, **kwargs):
         """Word timestamps for known transcripts: ``inputs`` in any form ``__call__`` takes (one, or a list), each at most
         30 s; ``transcripts`` one per input, a ``str`` (needs a transformers tokenizer) or token ids without special
         tokens.  ``language`` / ``task`` resolve like ``generate_kwargs`` in ``__call__`` (``language=None``: detected per
@@ -941,7 +975,10 @@ class CrisperWhisperPipeline:
         ``return_scores=True`` adds what ``score`` computes, from the same forward: "logprob" on every chunk, and "logprob" /
         "avg_logprob" of the whole transcript (eos included) at the top level.  ``return_alignment_scores=True`` adds
         "alignment_score" / "alignment_spread" to every chunk, as ``__call__`` defines them (``alignment_collar_frames`` likewise;
-        None: the pipeline's own setting)."""
+        None: the pipeline's own setting).  ``top_logprobs=k`` (0 .. 8, needs ``return_scores=True``): every chunk gains
+        "tokens": [{"id", "text", "logprob", "top_logprobs", "rank"}] over the collator's own token group, as ``score`` lists
+        them."""
+        top_k = self._check_align_top("align", top_logprobs, return_scores)
         language, task = self._forced_kwargs("align", language, task, kwargs)
         collar = getattr(self, "alignment_collar_frames", None) if alignment_collar_frames is None else alignment_collar_frames
         if collar is not None:
@@ -969,14 +1006,18 @@ class CrisperWhisperPipeline:
             _, nf = eng.mel([pcms[i] for i in idx])
             if return_scores:
                 out = generation.align(eng, len(idx), nf, [ids[i] for i in idx], language=language, task=task, return_scores=True,
-                                       **akw)
+                                       **akw, **({"top_logprobs": top_k} if top_k else {}))
                 for k in range(len(idx)):
                     lp = np.asarray(out["token_logprobs"][k], np.float64)
                     text, chunks, groups = self._scored_words(out["sequences"][k], lp[:-1], out["token_timestamps"][k],
                                                               return_groups=True)
                     total = float(lp.sum())
-                    results.append({"text": text, "chunks": with_alignment(out, k, [
-                        {"text": c["text"], "timestamp": c["timestamp"], "logprob": c["logprob"]} for c in chunks], groups),
+                    chunks = [{"text": c["text"], "timestamp": c["timestamp"], "logprob": c["logprob"]} for c in chunks]
+                    if top_k:
+                        for c, g in zip(chunks, groups):
+                            c["tokens"] = self._alt_tokens(out["sequences"][k], out["token_logprobs"][k], out["alt_ids"][k],
+                                                           out["alt_logprobs"][k], g)
+                    results.append({"text": text, "chunks": with_alignment(out, k, chunks, groups),
                                     "logprob": total, "avg_logprob": total / (len(out["sequences"][k]) + 1)})
                 continue
             out = generation.align(eng, len(idx), nf, [ids[i] for i in idx], language=language, task=task, **akw)
@@ -990,7 +1031,7 @@ class CrisperWhisperPipeline:
 
     def align_long(self, inputs, transcripts, language: Optional[str] = None, task: Optional[str] = None,
                    return_scores: bool = False, return_alignment_scores: bool = False,
-                   alignment_collar_frames: Optional[int] = None, max_window_tokens: Optional[int] = None):
+                   alignment_collar_frames: Optional[int] = None, max_window_tokens: Optional[int] = None, top_logprobs=None):
         """``align`` for audio of any length: walks a known transcript over the recording in 30 s windows.  ``inputs`` one
         input or a list, as ``align`` takes them but of any length; ``transcripts`` one per input, a ``str`` or text token ids
         (no timestamp tokens).  Every window is offered the transcript from the first token not yet placed, up to
@@ -1005,6 +1046,7 @@ class CrisperWhisperPipeline:
 
         Not claimed: that the cut is right.  It is the maximum-a-posteriori prefix under the model; how well that places
         the cut with a trained checkpoint is unmeasured."""
+        top_k = self._check_align_top("align_long", top_logprobs, return_scores)
         collar = getattr(self, "alignment_collar_frames", None) if alignment_collar_frames is None else alignment_collar_frames
         if collar is not None:
             collar = generation.check_alignment_collar(None, collar)
@@ -1030,7 +1072,14 @@ class CrisperWhisperPipeline:
             results.extend(generation.align_long(
                 eng, [pcms[i] for i in idx], [ids[i] for i in idx], collate_words, language=language, task=task,
                 return_scores=return_scores, return_alignment_scores=return_alignment_scores, alignment_collar_frames=collar,
-                max_window_tokens=max_window_tokens, stats=self.stats, item_ids=idx, sampling_rate=self.sampling_rate))
+                max_window_tokens=max_window_tokens, stats=self.stats, item_ids=idx, sampling_rate=self.sampling_rate,
+                **({"top_logprobs": top_k} if top_k else {})))
+        if top_k:                                            # the walk's raw rows -> what align(top_logprobs=k) lists
+            for res in results:
+                for c in res["chunks"]:
+                    raw = c["tokens"]
+                    c["tokens"] = self._alt_tokens([t["id"] for t in raw], [t["logprob"] for t in raw], [t["alt_ids"] for t in raw],
+                                                   [t["alt_logprobs"] for t in raw], range(len(raw)))
         return results[0] if single else results
 
     # -- per-head forced alignment, alignment-head selection -----------------------------------------

@@ -466,6 +466,20 @@ int32_t cw_align_cut_tokens(cw_ctx* ctx, int32_t nb, const int32_t* num_frames, 
                             float* top_logprob);
 /* cw_score_prefill_runs: how many scoring calls of this context ran their forward as the batched prefill.                  */
 int32_t cw_score_prefill_runs(cw_ctx* ctx);
+/* cw_set_score_top_logprobs: the k best alternatives of every teacher-forced position (0 = off, the default; 1 ..
+ * CW_TOP_LOGPROBS_MAX), selected on the device inside the scoring forward of cw_score_tokens / cw_align_score_tokens /
+ * cw_align_cut_tokens -- the [M][V] logits are still never stored.  With z[n], n < V, the f32 logits of a scored position as
+ * the head computes them and lse the normaliser token_logprob uses there: candidates are the columns with z[n] > -inf (no
+ * suppress lists, no timestamp rules, temperature 1; a NaN is none), ordered by value descending, id ascending on an exact
+ * tie; rank j holds that column's id and z - lse, ranks at or past the number of candidates -1 / NaN.  Rank 0 is top_id /
+ * top_logprob bit for bit, the target's entry (where it is among the k) token_logprob, and every other output of the call is
+ * what it is with k = 0.  Independent of cw_set_token_logprobs / cw_set_top_logprobs (the free-running decode), and the
+ * captured decode steps stay: the loop path reduces the step's logits behind the step.  CW_ERR_INVALID outside 0 .. 8.
+ * cw_get_score_top_logprobs: after one of the three calls, with that call's rows and ids_stride: ids_out / lp_out
+ * [rows][ids_stride][k], filled at indices n_init .. n_ids[r]-1 of row r, -1 / NaN elsewhere.  CW_ERR_STATE while off, for more
+ * rows than the last call scored, for another stride, or when no call has run since the switch was set.                     */
+int32_t cw_set_score_top_logprobs(cw_ctx* ctx, int32_t k);
+int32_t cw_get_score_top_logprobs(cw_ctx* ctx, int32_t* ids_out, float* lp_out, int32_t rows, int32_t ids_stride);
 
 /* ---- stand-alone differential-test entry points for the alignment kernels ---------------------------- */
 /* attn [B][Ha][N][M] -> mat [B][N][M] (z-score, median(width), head mean); n_cols[b] <= M columns used.  */
@@ -596,6 +610,25 @@ int32_t cw_test_align_cut(cw_ctx* ctx, int32_t rows, int32_t stride, const int32
  * writing f32 logits [M][V] plus a row-wise log-softmax pass, 2 the fused STOP form.  avg_ms per repetition (HIP events, one
  * warm-up).                                                                                                                */
 int32_t cw_time_score_head(cw_ctx* ctx, int32_t M, int32_t unfused, int32_t iters, float* avg_ms);
+/* The TOPK forms of the head (cw_set_score_top_logprobs), k = 1 .. CW_TOP_LOGPROBS_MAX: cw_test_score_head[_stop] plus alt_id /
+ * alt_logprob [M][CW_TOP_LOGPROBS_MAX] (ranks >= k hold -1 / NaN).  logits_out non-null: [M][V], the same operands through the
+ * head's logits-storing form -- the same MFMA sequence, so the very f32 numbers the fused form selected from.  The device
+ * arrays carry guard rows behind row M - 1: a write there is CW_ERR_STATE.                                                  */
+int32_t cw_test_score_head_top(cw_ctx* ctx, int32_t M, int32_t D, int32_t V, const float* x, const float* ln_g, const float* ln_b,
+                               const float* embed, const int32_t* targets, int32_t k, float* logprob, int32_t* top_id,
+                               float* top_logprob, int32_t* alt_id, float* alt_logprob, float* logits_out);
+int32_t cw_test_score_head_stop_top(cw_ctx* ctx, int32_t M, int32_t D, int32_t V, const float* x, const float* ln_g,
+                                    const float* ln_b, const float* embed, const int32_t* targets, int32_t eos,
+                                    int32_t timestamp_begin, int32_t k, float* logprob, int32_t* top_id, float* top_logprob,
+                                    float* stop_logprob, int32_t* alt_id, float* alt_logprob, float* logits_out);
+/* The loop path's row kernel in its TOPK form on caller-supplied f32 logits [rows][ldv] (ldv >= V), any engine: targets [rows]
+ * (negative: none) -> logprob / top_id / top_logprob [rows], alt_id / alt_logprob [rows][CW_TOP_LOGPROBS_MAX]; stop_logprob
+ * non-null: the STOP form over S = {eos} + {n >= timestamp_begin} as well.                                                  */
+int32_t cw_test_score_rows_top(cw_ctx* ctx, int32_t rows, int32_t V, int32_t ldv, const float* logits, const int32_t* targets,
+                               int32_t k, int32_t eos, int32_t timestamp_begin, float* logprob, int32_t* top_id,
+                               float* top_logprob, float* stop_logprob, int32_t* alt_id, float* alt_logprob);
+/* cw_time_score_head's fused forms (stop = 0 / 1) with k alternatives per row; k = 0 times the plain forms in the same loop.  */
+int32_t cw_time_score_head_top(cw_ctx* ctx, int32_t M, int32_t k, int32_t stop, int32_t iters, float* avg_ms);
 /* Decoder prompt prefill kernels (16-bit engines) against a host reference: cw_test_prefill_gemm runs the prefill GEMM over
  * fragment-major packed W with epilogue mode 0 = 16-bit store, 2 = f32 residual add (out: residual in, result out), 3 = erf GELU
  * (K % 32 == 0, N % 16 == 0); cw_test_prefill_attention the flash attention of the prefill (causal over n_keys >= n_q keys, or
