@@ -388,6 +388,19 @@ struct ScoreStopPart {
 struct ScoreTopPart {
     float v; int i;
 };
+// what cw_launch_score_rows writes for every row: logprob / top_id / top_logprob always, and the optional forms' outputs.
+// stop_logprob non-null: the STOP form, over S = {eos} + {n >= ts_begin}.  k != 0: the TOPK form, k = 1 .. CW_TOP_LOGPROBS_MAX
+// alternatives per row in alt_id / alt_logprob [..][CW_TOP_LOGPROBS_MAX]
+struct ScoreRowsOut {
+    float* logprob; int* top_id; float* top_logprob;
+    float* stop_logprob; int eos, ts_begin;
+    int k; int* alt_id; float* alt_logprob;
+};
+// ... and cw_launch_score_head, with its per-split records: cw_score_head_splits(M, V) per row in part and (STOP) spart, times
+// CW_TOP_LOGPROBS_MAX in (TOPK) tpart
+struct ScoreHeadOut : ScoreRowsOut {
+    ScorePart* part; ScoreStopPart* spart; ScoreTopPart* tpart;
+};
 
 #define CW_DTYPE_KERNEL_DECLS \
     int cw_launch_gemm(bool bf16, int epi, const AParams& ap, const void* W, int M, int N, int K, const EpiParams& ep, hipStream_t st); \
@@ -447,16 +460,10 @@ struct ScoreTopPart {
     int cw_launch_prefill_attn_align(const void* Q, const void* K, const void* V, void* out, int rows, int n_q, int H, int cap, int n_keys, int causal, int kv_div, const PrefillAlign& al, hipStream_t st); \
     int cw_launch_score_ln(const float* x, const int* src, const float* g, const float* b, void* out, int M, int D, hipStream_t st); \
     int cw_score_head_splits(int M, int V, int* tiles_per_split); \
-    int cw_launch_score_head(const void* A, const void* W, const int* target, ScorePart* part, int M, int V, int K, float* logprob, int* top_id, float* top_logprob, hipStream_t st); \
+    int cw_launch_score_head(const void* A, const void* W, const int* target, int M, int V, int K, const ScoreHeadOut& out, hipStream_t st); \
     int cw_launch_score_head_unfused(const void* A, const void* W, const int* target, float* logits, int ldv, int M, int V, int K, float* logprob, int* top_id, float* top_logprob, hipStream_t st); \
-    int cw_launch_score_rows(const float* logits, int ldv, int V, const int* target, int t_stride, int t, int rows, float* logprob, int* top_id, float* top_logprob, hipStream_t st); \
-    int cw_launch_score_head_stop(const void* A, const void* W, const int* target, ScorePart* part, ScoreStopPart* spart, int M, int V, int K, int eos, int ts_begin, float* logprob, int* top_id, float* top_logprob, float* stop_logprob, hipStream_t st); \
-    int cw_launch_score_rows_stop(const float* logits, int ldv, int V, const int* target, int t_stride, int t, int rows, int eos, int ts_begin, float* logprob, int* top_id, float* top_logprob, float* stop_logprob, hipStream_t st); \
-    int cw_launch_score_head_top(const void* A, const void* W, const int* target, ScorePart* part, ScoreTopPart* tpart, int M, int V, int K, int k, float* logprob, int* top_id, float* top_logprob, int* alt_id, float* alt_logprob, hipStream_t st); \
-    int cw_launch_score_head_stop_top(const void* A, const void* W, const int* target, ScorePart* part, ScoreStopPart* spart, ScoreTopPart* tpart, int M, int V, int K, int eos, int ts_begin, int k, float* logprob, int* top_id, float* top_logprob, float* stop_logprob, int* alt_id, float* alt_logprob, hipStream_t st); \
+    int cw_launch_score_rows(const float* logits, int ldv, int V, const int* target, int t_stride, int t, int rows, const ScoreRowsOut& out, hipStream_t st); \
     int cw_launch_score_head_store(const void* A, const void* W, const int* target, float* logits, int ldv, int M, int V, int K, hipStream_t st); \
-    int cw_launch_score_rows_top(const float* logits, int ldv, int V, const int* target, int t_stride, int t, int rows, int k, float* logprob, int* top_id, float* top_logprob, int* alt_id, float* alt_logprob, hipStream_t st); \
-    int cw_launch_score_rows_stop_top(const float* logits, int ldv, int V, const int* target, int t_stride, int t, int rows, int eos, int ts_begin, int k, float* logprob, int* top_id, float* top_logprob, float* stop_logprob, int* alt_id, float* alt_logprob, hipStream_t st); \
     int cw_launch_attn_encoder(bool bf16, const void* Q, const void* K, const void* V, void* out, int B, int H, int S, int S_pad, hipStream_t st); \
     int cw_launch_attn_decode(bool bf16, const DecAttnParams& p, hipStream_t st); \
     int cw_launch_attn_cross_split(bool bf16, const CrossSplitParams& p, hipStream_t st); \

@@ -446,32 +446,38 @@ int cw_score_head_splits(int M, int V, int* tiles_per_split) {
     return (NT + tps - 1) / tps;
 }
 
-// part: cw_score_head_splits(M, V) records per row
-int cw_launch_score_head(const void* A, const void* W, const int* target, ScorePart* part, int M, int V, int K, float* logprob,
-                         int* top_id, float* top_logprob, hipStream_t st) {
-    if (M < 1 || V < 1 || K < 32 || K % 32) return CW_ERR_INVALID;
+// One form of the fused head: the split kernel and its combine.  The arguments of a form that is off are null / 0.
+template <bool STOP, bool TOPK>
+static void score_head_form(const void* A, const void* W, const int* target, int M, int V, int K, const ScoreHeadOut& o, hipStream_t st) {
     int tps = 0;
     const int ns = cw_score_head_splits(M, V, &tps);
-    hipLaunchKernelGGL((score_head_kernel<false, false>), dim3((M + 127) / 128, ns), dim3(256), 0, st, (const bf16_t*)A,
-                       (const bf16_t*)W, target, part, M, V, K, tps, ns, (float*)nullptr, 0, (ScoreStopPart*)nullptr, 0, 0, (ScoreTopPart*)nullptr, 0);
-    hipLaunchKernelGGL(score_combine_kernel<false>, dim3((M + 255) / 256), dim3(256), 0, st, part, M, ns, logprob, top_id,
-                       top_logprob, (const ScoreStopPart*)nullptr, (float*)nullptr, (const ScoreTopPart*)nullptr, 0, (int*)nullptr, (float*)nullptr);
-    return CW_OK;
+    ScoreStopPart* const spart = STOP ? o.spart : nullptr;
+    ScoreTopPart* const tpart = TOPK ? o.tpart : nullptr;
+    hipLaunchKernelGGL((score_head_kernel<false, STOP, TOPK>), dim3((M + 127) / 128, ns), dim3(256), 0, st, (const bf16_t*)A,
+                       (const bf16_t*)W, target, o.part, M, V, K, tps, ns, (float*)nullptr, 0, spart, STOP ? o.eos : 0, STOP ? o.ts_begin : 0,
+                       tpart, TOPK ? o.k : 0);
+    hipLaunchKernelGGL((score_combine_kernel<STOP, TOPK>), dim3(TOPK ? (M + 3) / 4 : (M + 255) / 256), dim3(256), 0, st, o.part, M, ns,
+                       o.logprob, o.top_id, o.top_logprob, (const ScoreStopPart*)spart, STOP ? o.stop_logprob : nullptr,
+                       (const ScoreTopPart*)tpart, TOPK ? o.k : 0, TOPK ? o.alt_id : nullptr, TOPK ? o.alt_logprob : nullptr);
+}
+// ... and of the row kernel
+template <bool STOP, bool TOPK>
+static void score_rows_form(const float* logits, int ldv, int V, const int* target, int t_stride, int t, int rows, const ScoreRowsOut& o,
+                            hipStream_t st) {
+    hipLaunchKernelGGL((score_rows_kernel<STOP, TOPK>), dim3(rows), dim3(256), 0, st, logits, ldv, V, target, t_stride, t, o.logprob,
+                       o.top_id, o.top_logprob, STOP ? o.eos : 0, STOP ? o.ts_begin : 0, STOP ? o.stop_logprob : nullptr, TOPK ? o.k : 0,
+                       TOPK ? o.alt_id : nullptr, TOPK ? o.alt_logprob : nullptr);
 }
 
-// cw_launch_score_head plus stop_logprob [M] over S = {eos} + {n >= ts_begin}; spart: as many records as part
-int cw_launch_score_head_stop(const void* A, const void* W, const int* target, ScorePart* part, ScoreStopPart* spart, int M, int V,
-                              int K, int eos, int ts_begin, float* logprob, int* top_id, float* top_logprob, float* stop_logprob,
-                              hipStream_t st) {
-    if (M < 1 || V < 1 || K < 32 || K % 32 || eos < 0 || ts_begin < 0) return CW_ERR_INVALID;
-    int tps = 0;
-    const int ns = cw_score_head_splits(M, V, &tps);
-    hipLaunchKernelGGL((score_head_kernel<false, true>), dim3((M + 127) / 128, ns), dim3(256), 0, st, (const bf16_t*)A,
-                       (const bf16_t*)W, target, part, M, V, K, tps, ns, (float*)nullptr, 0, spart, eos, ts_begin, (ScoreTopPart*)nullptr, 0);
-    hipLaunchKernelGGL(score_combine_kernel<true>, dim3((M + 255) / 256), dim3(256), 0, st, part, M, ns, logprob, top_id,
-                       top_logprob, (const ScoreStopPart*)spart, stop_logprob, (const ScoreTopPart*)nullptr, 0, (int*)nullptr, (float*)nullptr);
-    return CW_OK;
-}
+// The code object holds the kernels in the order their instantiations are first asked for.  The forms are asked for here, around
+// the unfused launcher, in the order every build so far has held them, so that the device code of a change to the launchers
+// compares equal with its parent's.
+#define CW_SCORE_HEAD_FORM(STOP, TOPK) \
+    template void score_head_form<STOP, TOPK>(const void*, const void*, const int*, int, int, int, const ScoreHeadOut&, hipStream_t)
+#define CW_SCORE_ROWS_FORM(STOP, TOPK) \
+    template void score_rows_form<STOP, TOPK>(const float*, int, int, const int*, int, int, int, const ScoreRowsOut&, hipStream_t)
+CW_SCORE_HEAD_FORM(false, false);
+CW_SCORE_HEAD_FORM(true, false);
 
 // the unfused form of cw_launch_score_head: f32 logits [M][ldv] (ldv >= V) through the same GEMM, then a row-wise pass
 int cw_launch_score_head_unfused(const void* A, const void* W, const int* target, float* logits, int ldv, int M, int V, int K,
@@ -486,47 +492,22 @@ int cw_launch_score_head_unfused(const void* A, const void* W, const int* target
     return CW_OK;
 }
 
-int cw_launch_score_rows(const float* logits, int ldv, int V, const int* target, int t_stride, int t, int rows, float* logprob,
-                         int* top_id, float* top_logprob, hipStream_t st) {
-    if (rows < 1 || V < 1 || ldv < V || t < 0 || t >= t_stride) return CW_ERR_INVALID;
-    hipLaunchKernelGGL(score_rows_kernel<false>, dim3(rows), dim3(256), 0, st, logits, ldv, V, target, t_stride, t, logprob,
-                       top_id, top_logprob, 0, 0, (float*)nullptr, 0, (int*)nullptr, (float*)nullptr);
-    return CW_OK;
-}
+CW_SCORE_ROWS_FORM(false, false);
+CW_SCORE_ROWS_FORM(true, false);
+CW_SCORE_HEAD_FORM(false, true);
+CW_SCORE_HEAD_FORM(true, true);
+CW_SCORE_ROWS_FORM(false, true);
+CW_SCORE_ROWS_FORM(true, true);
+#undef CW_SCORE_HEAD_FORM
+#undef CW_SCORE_ROWS_FORM
 
-int cw_launch_score_rows_stop(const float* logits, int ldv, int V, const int* target, int t_stride, int t, int rows, int eos,
-                              int ts_begin, float* logprob, int* top_id, float* top_logprob, float* stop_logprob, hipStream_t st) {
-    if (rows < 1 || V < 1 || ldv < V || t < 0 || t >= t_stride || eos < 0 || ts_begin < 0) return CW_ERR_INVALID;
-    hipLaunchKernelGGL(score_rows_kernel<true>, dim3(rows), dim3(256), 0, st, logits, ldv, V, target, t_stride, t, logprob,
-                       top_id, top_logprob, eos, ts_begin, stop_logprob, 0, (int*)nullptr, (float*)nullptr);
-    return CW_OK;
-}
-
-// ---- TOPK forms (cw_set_score_top_logprobs): k = 1 .. CW_TOP_LOGPROBS_MAX alternatives per row beside what the plain forms write.
-// tpart: cw_score_head_splits(M, V) x CW_TOP_LOGPROBS_MAX records per row; alt_id / alt_logprob [M][CW_TOP_LOGPROBS_MAX]
-int cw_launch_score_head_top(const void* A, const void* W, const int* target, ScorePart* part, ScoreTopPart* tpart, int M, int V, int K,
-                             int k, float* logprob, int* top_id, float* top_logprob, int* alt_id, float* alt_logprob, hipStream_t st) {
-    if (M < 1 || V < 1 || K < 32 || K % 32 || k < 1 || k > CW_TOP_LOGPROBS_MAX || !tpart || !alt_id || !alt_logprob) return CW_ERR_INVALID;
-    int tps = 0;
-    const int ns = cw_score_head_splits(M, V, &tps);
-    hipLaunchKernelGGL((score_head_kernel<false, false, true>), dim3((M + 127) / 128, ns), dim3(256), 0, st, (const bf16_t*)A,
-                       (const bf16_t*)W, target, part, M, V, K, tps, ns, (float*)nullptr, 0, (ScoreStopPart*)nullptr, 0, 0, tpart, k);
-    hipLaunchKernelGGL((score_combine_kernel<false, true>), dim3((M + 3) / 4), dim3(256), 0, st, part, M, ns, logprob, top_id,
-                       top_logprob, (const ScoreStopPart*)nullptr, (float*)nullptr, (const ScoreTopPart*)tpart, k, alt_id, alt_logprob);
-    return CW_OK;
-}
-
-int cw_launch_score_head_stop_top(const void* A, const void* W, const int* target, ScorePart* part, ScoreStopPart* spart,
-                                  ScoreTopPart* tpart, int M, int V, int K, int eos, int ts_begin, int k, float* logprob, int* top_id,
-                                  float* top_logprob, float* stop_logprob, int* alt_id, float* alt_logprob, hipStream_t st) {
-    if (M < 1 || V < 1 || K < 32 || K % 32 || eos < 0 || ts_begin < 0 || k < 1 || k > CW_TOP_LOGPROBS_MAX || !tpart || !alt_id ||
-        !alt_logprob) return CW_ERR_INVALID;
-    int tps = 0;
-    const int ns = cw_score_head_splits(M, V, &tps);
-    hipLaunchKernelGGL((score_head_kernel<false, true, true>), dim3((M + 127) / 128, ns), dim3(256), 0, st, (const bf16_t*)A,
-                       (const bf16_t*)W, target, part, M, V, K, tps, ns, (float*)nullptr, 0, spart, eos, ts_begin, tpart, k);
-    hipLaunchKernelGGL((score_combine_kernel<true, true>), dim3((M + 3) / 4), dim3(256), 0, st, part, M, ns, logprob, top_id,
-                       top_logprob, (const ScoreStopPart*)spart, stop_logprob, (const ScoreTopPart*)tpart, k, alt_id, alt_logprob);
+// The fused head over M rows (kernels.h: ScoreHeadOut).  This and cw_launch_score_rows pick among the STOP / TOPK forms
+int cw_launch_score_head(const void* A, const void* W, const int* target, int M, int V, int K, const ScoreHeadOut& o, hipStream_t st) {
+    const bool stop = o.stop_logprob != nullptr, top = o.k != 0;
+    if (M < 1 || V < 1 || K < 32 || K % 32 || (stop && (o.eos < 0 || o.ts_begin < 0)) ||
+        (top && (o.k < 1 || o.k > CW_TOP_LOGPROBS_MAX || !o.tpart || !o.alt_id || !o.alt_logprob))) return CW_ERR_INVALID;
+    if (top) stop ? score_head_form<true, true>(A, W, target, M, V, K, o, st) : score_head_form<false, true>(A, W, target, M, V, K, o, st);
+    else stop ? score_head_form<true, false>(A, W, target, M, V, K, o, st) : score_head_form<false, false>(A, W, target, M, V, K, o, st);
     return CW_OK;
 }
 
@@ -541,23 +522,14 @@ int cw_launch_score_head_store(const void* A, const void* W, const int* target, 
     return CW_OK;
 }
 
-// alt_id / alt_logprob [rows][t_stride][CW_TOP_LOGPROBS_MAX], written at [row][t]
-int cw_launch_score_rows_top(const float* logits, int ldv, int V, const int* target, int t_stride, int t, int rows, int k,
-                             float* logprob, int* top_id, float* top_logprob, int* alt_id, float* alt_logprob, hipStream_t st) {
-    if (rows < 1 || V < 1 || ldv < V || t < 0 || t >= t_stride || k < 1 || k > CW_TOP_LOGPROBS_MAX || !alt_id || !alt_logprob)
-        return CW_ERR_INVALID;
-    hipLaunchKernelGGL((score_rows_kernel<false, true>), dim3(rows), dim3(256), 0, st, logits, ldv, V, target, t_stride, t, logprob,
-                       top_id, top_logprob, 0, 0, (float*)nullptr, k, alt_id, alt_logprob);
-    return CW_OK;
-}
-
-int cw_launch_score_rows_stop_top(const float* logits, int ldv, int V, const int* target, int t_stride, int t, int rows, int eos,
-                                  int ts_begin, int k, float* logprob, int* top_id, float* top_logprob, float* stop_logprob,
-                                  int* alt_id, float* alt_logprob, hipStream_t st) {
-    if (rows < 1 || V < 1 || ldv < V || t < 0 || t >= t_stride || eos < 0 || ts_begin < 0 || k < 1 || k > CW_TOP_LOGPROBS_MAX ||
-        !alt_id || !alt_logprob) return CW_ERR_INVALID;
-    hipLaunchKernelGGL((score_rows_kernel<true, true>), dim3(rows), dim3(256), 0, st, logits, ldv, V, target, t_stride, t, logprob,
-                       top_id, top_logprob, eos, ts_begin, stop_logprob, k, alt_id, alt_logprob);
+// The loop path's row kernel at column t of [rows][t_stride] outputs (alternatives: [rows][t_stride][CW_TOP_LOGPROBS_MAX])
+int cw_launch_score_rows(const float* logits, int ldv, int V, const int* target, int t_stride, int t, int rows, const ScoreRowsOut& o,
+                         hipStream_t st) {
+    const bool stop = o.stop_logprob != nullptr, top = o.k != 0;
+    if (rows < 1 || V < 1 || ldv < V || t < 0 || t >= t_stride || (stop && (o.eos < 0 || o.ts_begin < 0)) ||
+        (top && (o.k < 1 || o.k > CW_TOP_LOGPROBS_MAX || !o.alt_id || !o.alt_logprob))) return CW_ERR_INVALID;
+    if (top) stop ? score_rows_form<true, true>(logits, ldv, V, target, t_stride, t, rows, o, st) : score_rows_form<false, true>(logits, ldv, V, target, t_stride, t, rows, o, st);
+    else stop ? score_rows_form<true, false>(logits, ldv, V, target, t_stride, t, rows, o, st) : score_rows_form<false, false>(logits, ldv, V, target, t_stride, t, rows, o, st);
     return CW_OK;
 }
 
