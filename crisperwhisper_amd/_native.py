@@ -190,6 +190,7 @@ _SIGS = {
     "cw_time_score_head": (_I, [_P, _I, _I, _I, _P]),
     "cw_test_beam_topk": (_I, [_P, _I, _P, _P, _I, _I, _I, _I, _P, _P]),
     "cw_test_beam_x": (_I, [_P, _I, _P]),
+    "cw_test_decode_state": (_I, [_P, _I, _I, _I, _I, _P]),
     "cw_test_sample": (_I, [_P, _I, _P, _P, _I, _I, _I, _I, _P]),
     "cw_test_sample_seeded": (_I, [_P, _I, _P, _P, _I, _I, _I, _I, C.c_float, C.c_uint64, _P, _P]),
     "cw_test_sample_logprobs": (_I, [_P, _I, _P, _P, _I, _I, _I, _I, C.c_float, C.c_uint64, _P, _P, _P, _P]),

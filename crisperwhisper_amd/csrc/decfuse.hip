@@ -372,6 +372,132 @@ int cw_launch_gemv_stack(const StackParams& p_in, int nt, hipStream_t st) {
     return launch_stack_nt<2, 3>(p, st);
 }
 
+// ---------------------------------------------------------------------------------------------------
+// gemv_stack_a16_kernel: the stage's two `a` segments behind qkv_self_kernel<.., XQ> (declayer.hip), rows <= 8, one tile per block,
+// fragment-major weights (DESIGN.md 6g''').  That launch computes the x segment in blocks that finish early and leaves the self-attention
+// output in 16 bits -- the rounding the segments' first use of an f32 row was -- so a block here takes in 20 KB of rows instead of 40 and
+// the launch is 2 K/16 blocks instead of 3 K/16:
+//   block b <  K/16:  qb = (W'q_c Wo) a            tile K/16 + b of W
+//   block b >= K/16:  x1 = resid + grid(Wo a + bo)  tile K/16 + b of W, and the LayerNorm partial sums of its 16 columns
+// Same K steps per wave, MFMA order, cross-wave sum and epilogues as gemv_stack_kernel<2, NSLOT, 2 PL16 - 1, 1, true, WNT>: bit-identical.
+// Kernel arguments: everything a request of the entry is addressed from -- W, the rows, the residual rows, the bias, dims = K | Mb << 16
+// -- is 9 leading dwords, preloaded into user SGPRs; the three destinations follow in `p` and arrive under the requests.
+// ---------------------------------------------------------------------------------------------------
+template <int NSLOT, int PL16, bool WNT>
+__global__ __launch_bounds__(256) void gemv_stack_a16_kernel(const void* __restrict__ Wp, const void* a16, const float* resid, const float* bias, unsigned dims,
+                                                             StackA16Out p) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem_a[];
+    const int K = (int)(dims & 0xffffu), Mb = (int)(dims >> 16), TD = K >> 4;
+    const int xs_stride = K + 8;
+    bf16_t* xs = (bf16_t*)smem_a;                               // [16][K+8]
+    float* red = (float*)(smem_a + (size_t)16 * xs_stride * 2);  // [4 waves][4][64]
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int l15 = lane & 15, g = lane >> 4;
+    const int bid = blockIdx.x;
+    const bool seg_x1 = bid >= TD;                               // block-uniform
+    const int tl = seg_x1 ? bid - TD : bid;                      // tile inside the segment
+    const int steps = K >> 7, nv8 = K >> 3;
+    const int n = tl * 16 + l15;                                 // output column
+    // every load is unconditional: the qb segment has no bias and no residual, and reads the x1 segment's in their place
+    const float bias_ld = bias[n];
+    const float resid_pre = resid[(size_t)min(g * 4 + wave, Mb - 1) * K + n];
+    u32x4_t av[2][PL16];                                         // rows wave, wave + 4: 16 bytes per lane per load
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+        int row = wave + 4 * i;
+        row = row < Mb ? row : Mb - 1;
+#pragma unroll
+        for (int c = 0; c < PL16; ++c) {
+            int v8 = lane + 64 * c;
+            v8 = v8 < nv8 ? v8 : nv8 - 1;
+            av[i][c] = *(const u32x4_t*)((const bf16_t*)a16 + (size_t)row * K + v8 * 8);
+        }
+    }
+    __builtin_amdgcn_sched_barrier(0);                           // the rows are waited for first: their requests go first
+    u32x4_t wq[NSLOT][4];
+    const bf16_t* __restrict__ W = (const bf16_t*)Wp;
+#pragma unroll
+    for (int s = 0; s < NSLOT; ++s) {
+        int step = wave + 4 * s;
+        step = step < steps ? step : steps - 1;
+        const u32x4_t* wp = (const u32x4_t*)(W + ((((size_t)(TD + bid) * (K >> 5)) + step * 4) * 64 + lane) * 8);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) wq[s][j] = WNT ? CW_STREAM_LD(wp + j * 64) : wp[j * 64];
+    }
+    __builtin_amdgcn_sched_barrier(0);
+    // rows -> LDS as they are
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+        const int row = wave + 4 * i;
+#pragma unroll
+        for (int c = 0; c < PL16; ++c) {
+            int v8 = lane + 64 * c;                             // (unconditional like the load: a tail lane rewrites the last chunk with itself)
+            v8 = v8 < nv8 ? v8 : nv8 - 1;
+            *(u32x4_t*)(xs + (size_t)row * xs_stride + v8 * 8) = av[i][c];
+        }
+    }
+    float bias_v = bias_ld, resid_v = resid_pre;
+    asm volatile("" : "+v"(bias_v), "+v"(resid_v));          // their requests stay at the head of the queue: hipcc otherwise sinks them into the x1 epilogue
+    __syncthreads();
+    f32x4_t acc = (f32x4_t){0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int s = 0; s < NSLOT; ++s) {
+        // A tail wave (step >= steps) runs the slot on the clamped step it loaded and drops the result: under a branch hipcc sinks
+        // the slot's weight requests into it, behind the barrier (the K steps that count, and their order, are gemv_stack_kernel's)
+        const int step = wave + 4 * s, stepc = step < steps ? step : steps - 1;
+        const bf16_t* xr = xs + (size_t)l15 * xs_stride + stepc * 128 + g * 8;
+        f32x4_t nacc = acc;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            bf16x8_t a = *(const bf16x8_t*)(xr + j * 32);
+            nacc = mfma16x(a, __builtin_bit_cast(bf16x8_t, wq[s][j]), nacc);
+        }
+        acc = step < steps ? nacc : acc;
+    }
+#pragma unroll
+    for (int r = 0; r < 4; ++r) red[(wave * 4 + r) * 64 + lane] = acc[r];
+    __syncthreads();
+    const int r = tid >> 6;
+    const float v = red[(0 * 4 + r) * 64 + lane] + red[(1 * 4 + r) * 64 + lane] + red[(2 * 4 + r) * 64 + lane] + red[(3 * 4 + r) * 64 + lane];
+    const int m = g * 4 + r;
+    const size_t o = (size_t)m * K + n;
+    if (!seg_x1) {
+        if (m < Mb) p.qb[o] = v + 0.f + 0.f;                     // gemv_stack_kernel's epi 0 without bias and add-back (-0 leaves as +0 there too)
+        return;
+    }
+    float ps1 = 0.f, ps2 = 0.f;                                 // this lane's share of (sum, sum of squares) of row g*4 + wave
+    if (m < Mb) {
+        const float rv = resid_v + resid_grid(v + bias_v);
+        p.x1[o] = rv;
+        ps1 += rv; ps2 += rv * rv;
+    }
+#pragma unroll
+    for (int sft = 0; sft < 4; ++sft) {
+        ps1 += sft == 0 ? dpp_mov<0x111, 0xf>(0.f, ps1) : sft == 1 ? dpp_mov<0x112, 0xf>(0.f, ps1) : sft == 2 ? dpp_mov<0x114, 0xf>(0.f, ps1) : dpp_mov<0x118, 0xf>(0.f, ps1);
+        ps2 += sft == 0 ? dpp_mov<0x111, 0xf>(0.f, ps2) : sft == 1 ? dpp_mov<0x112, 0xf>(0.f, ps2) : sft == 2 ? dpp_mov<0x114, 0xf>(0.f, ps2) : dpp_mov<0x118, 0xf>(0.f, ps2);
+    }
+    if (l15 == 15) *(float2*)(p.pstats + ((size_t)tl * 16 + m) * 2) = make_float2(ps1, ps2);
+}
+
+int cw_launch_gemv_stack_a16(const StackA16Params& p, hipStream_t st) {
+    if (p.Mb < 1 || p.Mb > 8 || p.K % 128 || p.K < 128 || p.K > 1280 || !p.W || !p.a16 || !p.resid || !p.bias || !p.qb || !p.x1 || !p.pstats) return CW_ERR_INVALID;
+    const size_t lds = (size_t)16 * (p.K + 8) * 2 + (size_t)4 * 4 * 64 * 4;
+    const dim3 grid(2 * (p.K / 16));
+    const unsigned dims = (unsigned)p.K | (unsigned)p.Mb << 16;
+    const StackA16Out out{p.qb, p.x1, p.pstats};
+#define CW_A16_LAUNCH(NS, PL)                                                                                                        \
+    do {                                                                                                                              \
+        if (p.wnt) hipLaunchKernelGGL((gemv_stack_a16_kernel<NS, PL, true>), grid, dim3(256), lds, st, p.W, p.a16, p.resid, p.bias, dims, out);  \
+        else hipLaunchKernelGGL((gemv_stack_a16_kernel<NS, PL, false>), grid, dim3(256), lds, st, p.W, p.a16, p.resid, p.bias, dims, out);       \
+    } while (0)
+    if (p.K <= 256) CW_A16_LAUNCH(1, 1);
+    else if (p.K <= 768) CW_A16_LAUNCH(2, 2);
+    else CW_A16_LAUNCH(3, 3);
+#undef CW_A16_LAUNCH
+    return CW_OK;
+}
+
 // ===================================================================================================
 // Measured and rejected: kept as published A/Bs behind -DCW_EXPERIMENTS, not part of the default library.
 // ===================================================================================================

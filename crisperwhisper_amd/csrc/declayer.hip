@@ -491,6 +491,200 @@ __global__ __launch_bounds__(DL_THREADS) void dec_layer_a_kernel(DecLayerParams 
 #undef DL_KV_LOAD
 #endif  // CW_EXPERIMENTS (stage A)
 
+// A V-tile block of qkv_self_kernel<.., XQ> (blocks 2 D/16 .. 3 D/16 - 1: they never carry an attention item and finish long before the
+// item blocks, DESIGN.md 6g'''): its q/k/v tile exactly as in the kernel below, then tile (block - 2 D/16) of the cross-query x term
+//     qa = W'q_c x + W'q_c bo
+// from the rows of x the block already holds -- the x segment of gemv_stack_kernel<2, NSLOT, PER_LANE, 1> (decfuse.hip) operation for
+// operation: rows rounded as x - mean(x) where |mean| >= std, the same K steps per wave, MFMA order and cross-wave sum, mean * (W'q_c 1)
+// added back in f32.  A path of its own from the block's first instruction, so that every counted wait is exact: the extra tile's weights
+// are requested BEHIND the first tile's (whose data therefore return first) and are waited for only after the V granules are out.
+// The second 16-bit image of the rows takes the place of the first once every wave's MFMAs have read that one.
+template <int NSLOT, int PER_LANE, bool WNT>
+__device__ __forceinline__ void qs_vtile_xq_block(const float* __restrict__ x, const void* __restrict__ Wp, const float* __restrict__ bias,
+                                                  void* sv, const int* __restrict__ pos, int Mb, int H, int K, int cap,
+                                                  const QkvSelfParams& p, unsigned char* qsm) {
+    const int xs_stride = K + 8;
+    bf16_t* xs = (bf16_t*)qsm;                                       // [16][K+8]
+    float* red = (float*)(qsm + (size_t)16 * xs_stride * 2);         // [4 waves][4][64]
+    float* smean = red + 4 * 4 * 64;                                 // [16] (where an item block keeps its query)
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);       // 0..7 (waves 4..7 only keep the barriers' count)
+    const int l15 = lane & 15, g = lane >> 4;
+    const int bid = blockIdx.x;
+    const int steps = K >> 7, nvec = K >> 2;
+    const int nn = bid * 16 + l15;                                   // a V column: 2 K <= nn < 3 K
+    const int tx = bid - 2 * (K >> 4), nx = tx * 16 + l15;           // tile and column of qa
+    float bias_v = 0.f, xbias_v = 0.f, xwsum_v = 0.f;
+    int pos_m = 0;
+    float4 xv[2][PER_LANE];
+    dl_u32x4_t wq[NSLOT][4], wx[NSLOT][4];
+    if (wave < 4) {
+        pos_m = pos[min(g * 4 + wave, Mb - 1)];
+        bias_v = bias ? bias[nn] : 0.f;
+#pragma unroll
+        for (int i = 0; i < 2; ++i) {
+            int row = wave + 4 * i;
+            row = row < Mb ? row : Mb - 1;
+#pragma unroll
+            for (int c = 0; c < PER_LANE; ++c) {
+                int v4 = lane + 64 * c;
+                v4 = v4 < nvec ? v4 : nvec - 1;
+                xv[i][c] = *(const float4*)(x + (size_t)row * K + v4 * 4);
+            }
+        }
+        const bf16_t* __restrict__ W = (const bf16_t*)Wp;
+#pragma unroll
+        for (int s = 0; s < NSLOT; ++s) {
+            int step = wave + 4 * s;
+            step = step < steps ? step : steps - 1;
+            const dl_u32x4_t* wp = (const dl_u32x4_t*)(W + ((((size_t)bid * (K >> 5)) + step * 4) * 64 + lane) * 8);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) wq[s][j] = WNT ? CW_STREAM_LD(wp + j * 64) : wp[j * 64];
+        }
+        __builtin_amdgcn_sched_barrier(0);
+        // the extra tile's requests: their addresses come from `p`, which arrives under the requests above.  Unconditional (a row sum
+        // that is not wanted reads the bias instead: a load under a branch would make the counted waits conservative)
+        const bf16_t* __restrict__ WX = (const bf16_t*)p.xq_W;
+#pragma unroll
+        for (int s = 0; s < NSLOT; ++s) {
+            int step = wave + 4 * s;
+            step = step < steps ? step : steps - 1;
+            const dl_u32x4_t* wp = (const dl_u32x4_t*)(WX + ((((size_t)tx * (K >> 5)) + step * 4) * 64 + lane) * 8);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) wx[s][j] = WNT ? CW_STREAM_LD(wp + j * 64) : wp[j * 64];
+        }
+        xbias_v = p.xq_bias[nx];
+        xwsum_v = (p.xq_wsum ? p.xq_wsum : p.xq_bias)[nx];
+    }
+    __builtin_amdgcn_sched_barrier(0);
+    const unsigned tag = (p.epoch[0] << 6) | (unsigned)p.layer;
+    const bool center = p.xq_wsum != nullptr;                        // block-uniform; read here: `p` must not be waited for in front of the first request
+    asm volatile("" : "+v"(pos_m));
+
+    // ---- the V tile: LayerNorm, rows -> 16 bit -> LDS, MFMA, cross-wave sum, cache row and granules (qkv_self_kernel's own lines)
+    if (wave < 4) {
+#pragma unroll
+        for (int i = 0; i < 2; ++i) {
+            float sx = 0.f;
+#pragma unroll
+            for (int c = 0; c < PER_LANE; ++c) {
+                const float ok = (lane + 64 * c < nvec) ? 1.f : 0.f;
+                sx += ok * ((xv[i][c].x + xv[i][c].y) + (xv[i][c].z + xv[i][c].w));
+            }
+            const float mean = wave_sum(sx) / (float)K;
+            float q = 0.f;
+#pragma unroll
+            for (int c = 0; c < PER_LANE; ++c) {
+                const float ok = (lane + 64 * c < nvec) ? 1.f : 0.f;
+                const float a = xv[i][c].x - mean, b = xv[i][c].y - mean, cc = xv[i][c].z - mean, d = xv[i][c].w - mean;
+                q += ok * cw_sumsq4(a, b, cc, d);
+            }
+            const float rstd = 1.0f / sqrtf(wave_sum(q) / (float)K + 1e-5f);
+            const int row = wave + 4 * i;
+#pragma unroll
+            for (int c = 0; c < PER_LANE; ++c) {
+                int v4 = lane + 64 * c;
+                v4 = v4 < nvec ? v4 : nvec - 1;
+                ushort4 o;
+                o.x = f32_to_bf16((xv[i][c].x - mean) * rstd); o.y = f32_to_bf16((xv[i][c].y - mean) * rstd);
+                o.z = f32_to_bf16((xv[i][c].z - mean) * rstd); o.w = f32_to_bf16((xv[i][c].w - mean) * rstd);
+                *(ushort4*)(xs + (size_t)row * xs_stride + v4 * 4) = o;
+            }
+        }
+    }
+    dl_barrier();
+    if (wave < 4) {
+        f32x4_t acc = (f32x4_t){0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int s = 0; s < NSLOT; ++s) {
+            const int step = wave + 4 * s;
+            if (step < steps) {
+                const bf16_t* xr = xs + (size_t)l15 * xs_stride + step * 128 + g * 8;
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    const bf16x8_t a = *(const bf16x8_t*)(xr + j * 32);
+                    acc = cw_mfma_16x16x32(a, __builtin_bit_cast(bf16x8_t, wq[s][j]), acc);
+                }
+            }
+        }
+#pragma unroll
+        for (int r = 0; r < 4; ++r) red[(wave * 4 + r) * 64 + lane] = acc[r];
+    }
+    dl_barrier();                                                    // every wave's MFMAs have read the first image: xs is free
+    if (wave < 4) {
+        const int r = wave;
+        const float v = (red[(0 * 4 + r) * 64 + lane] + red[(1 * 4 + r) * 64 + lane] + red[(2 * 4 + r) * 64 + lane] + red[(3 * 4 + r) * 64 + lane]) + bias_v;
+        const int m = g * 4 + r;
+        const int rc = nn - 2 * K;
+        const unsigned h16 = f32_to_bf16(v);
+        const unsigned other = (unsigned)__shfl_xor((int)h16, 1, 64);          // the neighbouring column's 16 bits
+        if (m < Mb) {
+            const int hh = rc >> 6, dd = rc & 63;
+            if (!(l15 & 1)) dl_gran_st(p.gkv + ((size_t)16 + m) * (K >> 1) + (rc >> 1), tag, h16 | (other << 16));   // the hand-off first
+            ((bf16_t*)sv)[(((size_t)m * H + hh) * cap + pos_m) * 64 + dd] = (bf16_t)h16;
+        }
+        // ---- the second image: gemv_stack_kernel's rounding of its x segment
+        if (center) {
+#pragma unroll
+            for (int i = 0; i < 2; ++i) {
+                float sx = 0.f, sq = 0.f;
+#pragma unroll
+                for (int c = 0; c < PER_LANE; ++c)
+                    if (lane + 64 * c < nvec) {
+                        sx += (xv[i][c].x + xv[i][c].y) + (xv[i][c].z + xv[i][c].w);
+                        sq += cw_sumsq4(xv[i][c].x, xv[i][c].y, xv[i][c].z, xv[i][c].w);
+                    }
+                float mu = wave_sum(sx) / (float)K;
+                if (2.f * mu * mu < wave_sum(sq) / (float)K) mu = 0.f;    // |mean| < std  <=>  2 mean^2 < E[x^2]
+#pragma unroll
+                for (int c = 0; c < PER_LANE; ++c) { xv[i][c].x -= mu; xv[i][c].y -= mu; xv[i][c].z -= mu; xv[i][c].w -= mu; }
+                if (lane == 0) smean[wave + 4 * i] = mu;
+            }
+        }
+#pragma unroll
+        for (int i = 0; i < 2; ++i) {
+            const int row = wave + 4 * i;
+#pragma unroll
+            for (int c = 0; c < PER_LANE; ++c) {
+                int v4 = lane + 64 * c;
+                v4 = v4 < nvec ? v4 : nvec - 1;
+                const float4 v = xv[i][c];
+                ushort4 o;
+                o.x = f32_to_bf16(v.x); o.y = f32_to_bf16(v.y); o.z = f32_to_bf16(v.z); o.w = f32_to_bf16(v.w);
+                *(ushort4*)(xs + (size_t)row * xs_stride + v4 * 4) = o;
+            }
+        }
+    }
+    dl_barrier();                                                    // the second image is whole, and the first epilogue has read `red`
+    if (wave < 4) {
+        f32x4_t acc = (f32x4_t){0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int s = 0; s < NSLOT; ++s) {
+            const int step = wave + 4 * s;
+            if (step < steps) {
+                const bf16_t* xr = xs + (size_t)l15 * xs_stride + step * 128 + g * 8;
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    const bf16x8_t a = *(const bf16x8_t*)(xr + j * 32);
+                    acc = cw_mfma_16x16x32(a, __builtin_bit_cast(bf16x8_t, wx[s][j]), acc);
+                }
+            }
+        }
+#pragma unroll
+        for (int r = 0; r < 4; ++r) red[(wave * 4 + r) * 64 + lane] = acc[r];
+    }
+    dl_barrier();
+    if (wave < 4) {
+        const int r = wave;
+        const float v = red[(0 * 4 + r) * 64 + lane] + red[(1 * 4 + r) * 64 + lane] + red[(2 * 4 + r) * 64 + lane] + red[(3 * 4 + r) * 64 + lane];
+        const int m = g * 4 + r;
+        if (m < Mb) {
+            const float back = center ? smean[m] * xwsum_v : 0.f;
+            p.xq_out[(size_t)m * K + nx] = v + xbias_v + back;
+        }
+    }
+}
+
 // ---------------------------------------------------------------------------------------------------
 // q/k/v projection + self-attention in ONE launch (rows <= 8): grid = 3 D / 16 tiles, 512 threads.
 //   waves 0..3 of block t: the LayerNorm + GEMV tile t of gemv2_bf16_kernel<EPI_QKV_CACHE, 2, false, false, NSLOT, PER_LANE>
@@ -518,12 +712,17 @@ __global__ __launch_bounds__(DL_THREADS) void dec_layer_a_kernel(DecLayerParams 
 // -amdgpu-kernarg-preload-count -- and every request of the entry (cache row, bias, rows, weights, history) is addressed from them alone;
 // `p` (a by-value struct is never preloaded, and ends the preloaded run) arrives under those requests.  cw_launch_qkv_self fills both
 // from the one struct:  x, Wp, bias, sk, sv, pos = the fields of `p`;  dims = p.Mb | p.H << 8 | p.D << 16;  cap = p.cap
-template <int NSLOT, int PER_LANE, bool WNT>
+// XQ: the V-tile blocks also compute the cross-query x term and the item blocks also leave their output rows in 16 bits (p.xq_*, p.out16)
+template <int NSLOT, int PER_LANE, bool WNT, bool XQ>
 __global__ __launch_bounds__(QS_THREADS) void qkv_self_kernel(const float* __restrict__ x, const void* __restrict__ Wp,
                                                               const float* __restrict__ bias, void* sk, void* sv,
                                                               const int* __restrict__ pos, unsigned dims, int cap, QkvSelfParams p) {
     extern __shared__ __attribute__((aligned(16))) unsigned char qsm[];
     const int Mb = (int)(dims & 0xffu), H = (int)((dims >> 8) & 0xffu), K = (int)(dims >> 16), N = 3 * K;
+    if (XQ && (int)blockIdx.x >= 2 * (K >> 4)) {                      // block-uniform, decided from preloaded arguments
+        qs_vtile_xq_block<NSLOT, PER_LANE, WNT>(x, Wp, bias, sv, pos, Mb, H, K, cap, p, qsm);
+        return;
+    }
     const int xs_stride = K + 8;
     bf16_t* xs = (bf16_t*)qsm;                                       // [16][K+8]
     float* red = (float*)(qsm + (size_t)16 * xs_stride * 2);         // [4 waves][4][64]
@@ -756,6 +955,7 @@ __global__ __launch_bounds__(QS_THREADS) void qkv_self_kernel(const float* __res
             for (int w = 0; w < QS_THREADS / 64; ++w) { r += red8[w * 64 + tid]; l += red8[8 * 64 + w]; }
             r *= 1.0f / l;
             p.out[(size_t)ib * H * 64 + ih * 64 + tid] = r;
+            if (XQ) ((bf16_t*)p.out16)[(size_t)ib * H * 64 + ih * 64 + tid] = f32_to_bf16(r);   // the rounding gemv_stack_kernel applies to the f32 row
         }
         return;
     }
@@ -841,6 +1041,7 @@ __global__ __launch_bounds__(QS_THREADS) void qkv_self_kernel(const float* __res
         float r = 0.f;
         for (int gI = 0; gI < QS_GROUPS; ++gI) r += redd[gI * 64 + tid];
         p.out[(size_t)ib * H * 64 + ih * 64 + tid] = r;
+        if (XQ) ((bf16_t*)p.out16)[(size_t)ib * H * 64 + ih * 64 + tid] = f32_to_bf16(r);
     }
 }
 
@@ -857,17 +1058,22 @@ int cw_launch_qkv_self(const QkvSelfParams& p, hipStream_t st) {
     if (p.Mb < 1 || p.Mb > 8 || D % 128 || D > 1280 || p.H * 64 != D || p.cap < 1 || p.cap > 512) return CW_ERR_INVALID;
     if (p.Mb * p.H > 3 * (D / 16) || !p.gq || !p.gkv || !p.epoch || !p.err || !p.W || !p.x || !p.pos) return CW_ERR_INVALID;
     if (p.layer < 0 || p.layer >= 64) return CW_ERR_INVALID;          // the granule tag is (epoch << 6) | layer
+    if (p.xq_W && (!p.xq_out || !p.xq_bias || !p.out16 || p.no_attn || p.Mb * p.H > 2 * (D / 16))) return CW_ERR_INVALID;   // (the V-tile blocks carry no item)
     const size_t lds = (size_t)16 * (D + 8) * 2 + (size_t)(4 * 4 * 64 + 64) * 4 + 2 * 64 * 2 +
                        ((size_t)((p.cap + 63) & ~63) + QS_GROUPS * 64 + 64) * 4;
     const dim3 grid(3 * (D / 16));
-#define QS_LAUNCH_P(NS, PL, NTL)                                                                                            \
+#define QS_LAUNCH_P(NS, PL, NTL, XQ)                                                                                            \
     do {                                                                                                                     \
         static std::once_flag attr;                                                                                          \
-        std::call_once(attr, [] { (void)hipFuncSetAttribute((const void*)qkv_self_kernel<NS, PL, NTL>, hipFuncAttributeMaxDynamicSharedMemorySize, 100 * 1024); }); \
-        hipLaunchKernelGGL((qkv_self_kernel<NS, PL, NTL>), grid, dim3(QS_THREADS), lds, st, p.x, p.W, p.bias, p.sk, p.sv, p.pos, \
+        std::call_once(attr, [] { (void)hipFuncSetAttribute((const void*)qkv_self_kernel<NS, PL, NTL, XQ>, hipFuncAttributeMaxDynamicSharedMemorySize, 100 * 1024); }); \
+        hipLaunchKernelGGL((qkv_self_kernel<NS, PL, NTL, XQ>), grid, dim3(QS_THREADS), lds, st, p.x, p.W, p.bias, p.sk, p.sv, p.pos, \
                            (unsigned)p.Mb | (unsigned)p.H << 8 | (unsigned)D << 16, p.cap, p);                                \
     } while (0)
-#define QS_LAUNCH(NS, PL) do { if (p.wnt) QS_LAUNCH_P(NS, PL, true); else QS_LAUNCH_P(NS, PL, false); } while (0)
+#define QS_LAUNCH(NS, PL)                                                                                                   \
+    do {                                                                                                                     \
+        if (p.xq_W) { if (p.wnt) QS_LAUNCH_P(NS, PL, true, true); else QS_LAUNCH_P(NS, PL, false, true); }                   \
+        else { if (p.wnt) QS_LAUNCH_P(NS, PL, true, false); else QS_LAUNCH_P(NS, PL, false, false); }                        \
+    } while (0)
     if (D <= 256) QS_LAUNCH(1, 1);
     else if (D <= 768) QS_LAUNCH(2, 3);
     else QS_LAUNCH(3, 5);

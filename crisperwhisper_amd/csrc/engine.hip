@@ -170,6 +170,7 @@ static int create_impl(cw_ctx* c) {
     c->mlp_pair_fence = sw.mlp_pair_fence;
     c->declayer = sw.declayer;
     c->qkv_self = !sw.no_qkv_self;
+    c->xq_in_qkv = !sw.no_xq_in_qkv;
     c->mlp_chain = sw.mlp_chain;
     c->stack_nt3 = sw.stack_nt3;
     c->stack_nt5 = sw.stack_nt5;
@@ -320,6 +321,7 @@ static int create_impl(cw_ctx* c) {
         CWCHK(c, dmalloc(c, &c->d_gq, (size_t)2 * 16 * D * 8)); CWCHK(c, dmalloc(c, &c->d_gps, (size_t)(D / 16) * 16 * 2 * 8));
         CWCHK(c, dmalloc(c, &c->d_gq2, (size_t)16 * D * 8)); CWCHK(c, dmalloc(c, &c->d_gkv, (size_t)2 * 16 * (D / 2) * 8));
         CWCHK(c, dmalloc(c, &c->d_gflag, (size_t)512 * 8));
+        CWCHK(c, dmalloc(c, &c->d_attn16, (size_t)8 * D * 2));
         CWCHK(c, dmalloc(c, &c->d_epoch, 4));
         const unsigned int one = 1;
         HIPCHK(c, hipMemcpy(c->d_epoch, &one, 4, hipMemcpyHostToDevice));
@@ -861,7 +863,7 @@ int launch_logits(cw_ctx* c, int nb, const float* x) {   // final LN + tied proj
 // ---- the decode step: plan, layers, logits.  Which launches a decoder layer has is constant over the layers of one forward: plan_step settles it
 // once per (context, nb), every predicate in one place; decode_step, run_step (graph slot) and the stage bookkeeping of cw_time_decode_stage read it.
 struct StepPlan {
-    bool frag, fuse, own, qs, short_hist, mid16; int nt3;
+    bool frag, fuse, own, qs, xq, short_hist, mid16; int nt3;
 #ifdef CW_EXPERIMENTS
     bool fuse_mlp, mlp_pair, mlp_chain, dl, sk_ok, skinny, xfull, rows, pf; int lo_off;
 #else   // the measured-and-rejected variants are not in this build: create_impl and cw_set_option refuse their switches
@@ -902,6 +904,11 @@ static StepPlan plan_step(const cw_ctx* c, int nb) {
     // (its 3 D / 16 blocks wait for each other: only where the whole grid is resident at once on this part; layer < 64: granule tag)
     P.qs = c->qkv_self && c->bf16 && c->ln_folded && c->wpacked && nb <= 8 && c->beam_K == 0 && D <= 1280 && nb * H <= 3 * (D / 16) && TGT <= 512 &&
            c->d.dec_layers <= 64 && 3 * (D / 16) <= c->n_cu * KD(c, cw_qkv_self_blocks_per_cu, D, TGT);
+    // behind qkv_self and in front of the fused stage, one tile per block, packed weights: the x segment of the stage (qa = W'q_c x, which depends on
+    // nothing the self-attention produces) rides in the V-tile blocks of qkv_self_kernel, which finish early; the attention epilogue leaves the 16-bit
+    // rows the stage would round itself, and the stage is two segments over them (gemv_stack_a16_kernel).  Bit-identical (tests/test_xq_in_qkv.py).
+    // The hand-off fallback (c->qkv_self off), two-launch q/k/v, 9..64 rows, beam search, f32 and row-major weights keep the three segments.
+    P.xq = c->xq_in_qkv && P.qs && P.fuse && P.nt3 == 1 && cw_sw::cw_switches().qkv_self_dbg == 0 && !c->fuse_mlp && !c->declayer && !c->mlp_pair && !c->mlp_chain;
     P.short_hist = c->hist_short && c->short_hist_enabled && nb > 8;   // bytes matter from 9 rows up (<= 8: latency-bound, qkv_self)
     // <= 16 rows behind the fused stage: fc1 writes gelu(.) in the 16-bit type fc2 would round it to anyway (bit-identical): fc2's activation load halves
     P.mid16 = P.fuse && !P.frag && F > 1280 && c->mid16;
@@ -934,6 +941,7 @@ static StepPlan plan_step(const cw_ctx* c, int nb) {
 #endif
     return P;
 }
+bool step_plan_xq(const cw_ctx* c, int nb) { return plan_step(c, nb).xq; }   // cw_test_decode_state: which stack launch nb rows take
 // kernel launches behind a stage.  17..64 rows: a LayerNorm / combining GEMV is gemv_prep_kernel + gemv_mt_kernel
 static int stage_launches(const StepPlan& P, int kind) {
     const bool prepared = kind == DST_QKV || kind == DST_CROSS_Q || kind == DST_FC1 || kind == DST_CROSS_O, owned = P.own && (kind == DST_FC1 || kind == DST_CROSS_O);
@@ -1010,6 +1018,7 @@ static int layer_self_attention(cw_ctx* c, const StepPlan& P, int l, int nb, con
     qp.gq = c->d_gq2; qp.gkv = c->d_gkv; qp.epoch = c->d_epoch; qp.layer = l; qp.err = c->d_err; qp.Mb = nb; qp.D = D; qp.H = H; qp.fail_pos = c->fail_pos; qp.wnt = c->wnt ? 1 : 0;
     const int dbg = cw_sw::cw_switches().qkv_self_dbg;   // 1: tiles fused, attention by attn_decode_kernel behind it (bisecting aid)
     if (dbg) { qp.q_plain = c->dq; qp.no_attn = 1; }
+    if (P.xq) { qp.xq_W = L.ws3; qp.xq_bias = L.qa_bias; qp.xq_wsum = c->stack_center ? L.q_wsum : nullptr; qp.xq_out = c->d_qa; qp.out16 = c->d_attn16; }
     STG(DST_QKV_SELF, KD(c, cw_launch_qkv_self, qp, c->st));
     if (dbg) STG(DST_SELF_ATTN, self_attn(c, P, L, nb));
     return CW_OK;
@@ -1031,7 +1040,11 @@ static StackParams stack_params(cw_ctx* c, LayerW& L, int nb, const float* xin, 
 static int layer_fused(cw_ctx* c, const StepPlan& P, int l, int nb, float*& xin, float*& xalt) {
     const int D = c->d.d_model, H = c->d.n_heads, F = c->d.ffn_dim;
     LayerW& L = c->dec[l];
-    STG(DST_STACK, KD(c, cw_launch_gemv_stack, stack_params(c, L, nb, xin, xalt), P.nt3, c->st));
+    if (P.xq) {   // qa came out of qkv_self_kernel: qb = (W'q_c Wo) a, x1 = x + Wo a + bo over the 16-bit rows of a
+        StackA16Params sp = zeroed<StackA16Params>();
+        sp.W = L.ws3; sp.a16 = c->d_attn16; sp.resid = xin; sp.bias = L.bo; sp.qb = c->d_qb; sp.x1 = xalt; sp.pstats = c->d_pstats; sp.K = D; sp.Mb = nb; sp.wnt = c->wnt ? 1 : 0;
+        STG(DST_STACK, KD(c, cw_launch_gemv_stack_a16, sp, c->st));
+    } else STG(DST_STACK, KD(c, cw_launch_gemv_stack, stack_params(c, L, nb, xin, xalt), P.nt3, c->st));
     const CrossSplitParams p = cross_params(c, P, L, l, nb, nullptr);
     STG(DST_CROSS_ATTN, cross_attn(c, L, p));
     if (P.own) {
@@ -3323,6 +3336,11 @@ int32_t cw_set_option(cw_ctx* c, const char* name, int32_t value) {
     }
     if (!strcmp(name, "no_wnt")) {    // != 0: default-policy weight loads in the <= 16-row decode GEMVs (CW_NO_WNT; A/B, differential tests)
         c->wnt = value == 0;
+        drop_step_graphs(c);   // graphs hold the kernel choice
+        return CW_OK;
+    }
+    if (!strcmp(name, "no_xq_in_qkv")) {   // != 0: the fused stage keeps its x segment and f32 attention rows (CW_NO_XQ_IN_QKV; A/B, differential tests)
+        c->xq_in_qkv = value == 0;
         drop_step_graphs(c);   // graphs hold the kernel choice
         return CW_OK;
     }

@@ -1489,6 +1489,26 @@ int32_t cw_test_beam_x(cw_ctx* c, int32_t rows, float* x) {
     return CW_OK;
 }
 
+// What the last decoder forward left on the device (differential tests of the decode step's launch plans):
+//   what 0: the cross-query x term qa of the last layer that ran, [rows][d_model] f32 (fused layers only)
+//   what 1 / 2: rows 0 .. n_pos - 1 of the self-attention key / value cache of `layer`, [rows][heads][n_pos][64] in the engine's element type
+//   what 3: one int32, 1 when a forward of `rows` rows takes the x term in qkv_self_kernel and the two-segment stack launch (plan_step)
+int32_t cw_test_decode_state(cw_ctx* c, int32_t what, int32_t layer, int32_t rows, int32_t n_pos, void* out) {
+    const int D = c->d.d_model, H = c->d.n_heads, TGT = c->d.max_target_positions;
+    if (!out || rows < 1 || rows > c->Bm || what < 0 || what > 3) return fail(c, CW_ERR_INVALID, "test_decode_state: what=%d rows=%d", what, rows);
+    if (what == 3) { *(int32_t*)out = step_plan_xq(c, rows) ? 1 : 0; return CW_OK; }
+    HIPCHK(c, hipStreamSynchronize(c->st));
+    if (what == 0) {
+        HIPCHK(c, hipMemcpy(out, c->d_qa, (size_t)rows * D * 4, hipMemcpyDeviceToHost));
+        return CW_OK;
+    }
+    if (layer < 0 || layer >= c->d.dec_layers || n_pos < 1 || n_pos > TGT) return fail(c, CW_ERR_INVALID, "test_decode_state: layer=%d n_pos=%d", layer, n_pos);
+    const void* src = what == 1 ? c->dec[layer].sk : c->dec[layer].sv;
+    const size_t row_bytes = (size_t)64 * c->esz;
+    HIPCHK(c, hipMemcpy2D(out, (size_t)n_pos * row_bytes, src, (size_t)TGT * row_bytes, (size_t)n_pos * row_bytes, (size_t)rows * H, hipMemcpyDeviceToHost));
+    return CW_OK;
+}
+
 // One call of the fused logits-processor + argmax kernel (sample_kernel) on caller-supplied rows: logits [nb][V],
 // ids [nb][t] = prompt + generated so far (the kernel's grammar state is rebuilt from it), choice_out [nb] = the
 // token the kernel picks for index t.  Differential test against TF/generation/logits_process.py:203-260, 1816-2047.

@@ -110,6 +110,9 @@ struct cw_ctx {
                                     // measured SLOWER: 22-24 us against 18.4 for the two launches -- A/B and differential test only)
     bool qkv_self = true;           // q/k/v projection + self-attention in one launch (declayer.hip: qkv_self_kernel); CW_NO_QKV_SELF=1: two launches
     unsigned long long *d_gq = nullptr, *d_gps = nullptr, *d_gq2 = nullptr, *d_gkv = nullptr, *d_gflag = nullptr;
+    bool xq_in_qkv = true;          // behind qkv_self: its V-tile blocks also compute the cross-query x term W'q_c x, its attention epilogue leaves the 16-bit rows,
+                                    // and the fused stage is the two-segment gemv_stack_a16_kernel (DESIGN.md 6g'''); CW_NO_XQ_IN_QKV=1 / option "no_xq_in_qkv": three segments (A/B)
+    void* d_attn16 = nullptr;       // [8][D] self-attention output in the engine's 16-bit type (qkv_self_kernel<.., XQ> -> gemv_stack_a16_kernel)
     bool mlp_chain = false;         // CW_MLP_CHAIN=1: fc1 + fc2 in one launch (declayer.hip: mlp_chain_kernel; flags instead of a kernel boundary);
                                     // bit-identical, measured SLOWER: 13.1 us against 5.7 + 4.9 for the two launches (profiles/r05_mlp_chain_phases.txt)
     unsigned int* d_epoch = nullptr;
@@ -351,6 +354,7 @@ int gemv_resid(cw_ctx* c, bool frag, const float* a, void* xf, int nb, int K, co
 int cross_attn(cw_ctx* c, LayerW& L, CrossSplitParams p);
 DecLayerParams dec_layer_params(cw_ctx* c, int l, int nb, const float* xin, float* xalt);
 int decode_step(cw_ctx* c, int nb, bool want_logits);
+bool step_plan_xq(const cw_ctx* c, int nb);
 int launch_sample(cw_ctx* c, int nb);
 void drop_step_graphs(cw_ctx* c);
 int epoch_hygiene(cw_ctx* c, long long upcoming_forwards);

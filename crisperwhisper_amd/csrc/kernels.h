@@ -187,6 +187,21 @@ struct StackParams {
     int zero_n4;
     int wnt;               // != 0: non-temporal weight stream where every tile has one reading block (fragment-major, one group of <= 16 rows)
 };
+// decfuse.hip: the stage's two `a` segments alone, rows <= 8, one tile per block, fragment-major weights, over the 16-bit rows of the
+// self-attention output that qkv_self_kernel<.., XQ> leaves (the x segment rides in that launch):  blocks [0, K/16): qb = (W'q_c Wo) a
+// (tiles K/16 .. of W),  blocks [K/16, 2 K/16): x1 = resid + grid(Wo a + bias) (tiles 2 K/16 ..) and its per-tile LayerNorm partial sums
+struct StackA16Params {
+    const void* W;         // [3 K][K] 16-bit fragment-major [W'q_c ; W'q_c Wo ; Wo]
+    const void* a16;       // [Mb][K] 16-bit attention output
+    const float* resid;    // [Mb][K] residual rows entering the layer
+    const float* bias;     // [K] bo
+    float* qb;             // [Mb][K]
+    float* x1;             // [Mb][K]
+    float* pstats;         // [K/16][16][2]
+    int K, Mb;
+    int wnt;               // non-temporal weight stream
+};
+struct StackA16Out { float *qb, *x1, *pstats; };   // the kernel's trailing argument: what no request of its entry is addressed from
 // decfuse.hip: fc2 that finishes fc1 on load, mid = gelu(rstd (u - mean w1sum) + b1), (mean, rstd) = LayerNorm statistics of
 // the residual rows `xstat` (an untouched copy: the launch's own atomics are already modifying the stream x)
 struct Fc2xParams {
@@ -318,6 +333,13 @@ struct QkvSelfParams {
     int Mb, D, H;
     int fail_pos;              // test hook: the item of layer 0 gives up at this position (-1: never)
     int wnt;                   // the tiles' weight stream with non-temporal loads (each tile has one reading block)
+    // non-null: the blocks of the V tiles (2 D/16 .. 3 D/16 - 1, which never carry an attention item) also compute tile (block - 2 D/16) of
+    // qa = W'q_c x + qa_bias, gemv_stack_kernel's x segment operation for operation, from the rows of x they hold
+    const void* xq_W;          // [D][D] 16-bit fragment-major W'q_c (the head of the layer's stacked matrix)
+    const float* xq_bias;      // [D] W'q_c bo
+    const float* xq_wsum;      // [D] W'q_c 1: rows with |mean| >= std are rounded as x - mean(x); null: x is rounded as it is
+    float* xq_out;             // [Mb][D] qa
+    void* out16;               // with xq_W: [Mb][D] the attention output once more, in the engine's 16-bit type
 };
 
 // declayer.hip: LayerNorm + fc1 + GELU and fc2 + residual of rows <= 8 in ONE launch (fc1 blocks publish a flag each, fc2 blocks
@@ -428,6 +450,7 @@ struct ScoreHeadOut : ScoreRowsOut {
     int cw_launch_fold_product(const float* A, const float* s, float scale, const float* B, int N, int J, int K, void* C16, hipStream_t st); \
     int cw_launch_fold_rowvec(const float* A, const float* s, float scale, const float* v, const void* W16, int N, int J, float* c_out, float* w_out, hipStream_t st); \
     int cw_launch_gemv_stack(const StackParams& p, int nt, hipStream_t st); \
+    int cw_launch_gemv_stack_a16(const StackA16Params& p, hipStream_t st); \
     int cw_launch_dec_layer(const DecLayerParams& p, int n_cu, hipStream_t st); \
     bool cw_mlp_chain_ok(int Mb, int D, int F); \
     int cw_launch_mlp_chain(const MlpChainParams& p, hipStream_t st); \

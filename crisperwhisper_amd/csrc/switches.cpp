@@ -30,6 +30,7 @@ Switches read_switches() {
     s.no_fuse_beam = flag("CW_NO_FUSE_BEAM");
     s.no_own_cols = flag("CW_NO_OWN_COLS");
     s.no_short_hist = flag("CW_NO_SHORT_HIST");
+    s.no_xq_in_qkv = flag("CW_NO_XQ_IN_QKV");
     s.skinny = num("CW_SKINNY", 0);
     s.prefetch = num("CW_PREFETCH", 0);
     s.prefetch_wide = num("CW_PREFETCH_WIDE", 0);

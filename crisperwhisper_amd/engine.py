@@ -1201,6 +1201,20 @@ class Engine:
         self._chk(self.lib.cw_test_beam_x(self.ctx, int(rows), _ptr(x)))
         return x
 
+    def test_decode_state(self, what: str, rows: int, layer: int = 0, n_pos: int = 1) -> np.ndarray:
+        """What the last decoder forward left on the device (cw_test_decode_state): ``"qa"`` the cross-query x term of the last
+        layer, [rows][d_model] f32; ``"k"`` / ``"v"`` the first n_pos self-attention cache rows of a layer, raw element bits;
+        ``"xq_plan"``: [1] int32, whether ``rows`` rows take the x term in the q/k/v launch."""
+        code = {"qa": 0, "k": 1, "v": 2, "xq_plan": 3}[what]
+        if code == 3:
+            out = np.zeros(1, np.int32)
+        elif code == 0:
+            out = np.zeros((int(rows), self.spec.d_model), np.float32)
+        else:
+            out = np.zeros((int(rows), self.spec.n_heads, int(n_pos), 64), np.float32 if self.dtype == "f32" else np.uint16)
+        self._chk(self.lib.cw_test_decode_state(self.ctx, code, int(layer), int(rows), int(n_pos), _ptr(out)))
+        return out
+
     def test_sample(self, logits: np.ndarray, ids: np.ndarray, n_prompt: int, min_new_tokens: int = 0,
                     max_length: Optional[int] = None) -> np.ndarray:
         """One launch of the fused logits processors + greedy choice on caller rows (cw_test_sample)."""

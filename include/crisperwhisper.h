@@ -789,6 +789,11 @@ int32_t cw_test_beam_topk(cw_ctx* ctx, int32_t nb, const float* logits, const in
                           int32_t min_new_tokens, int32_t n_cand, float* cand_val, int32_t* cand_id);
 /* The decoder input rows of the next step as the device holds them, x [rows][d_model].  Read-only.                  */
 int32_t cw_test_beam_x(cw_ctx* ctx, int32_t rows, float* x);
+/* What the last decoder forward left on the device (differential tests of the decode step's launch plans).  what 0: the
+ * cross-query x term of the last layer that ran, out [rows][d_model] f32 (fused layers only); what 1 / 2: rows 0 .. n_pos - 1
+ * of the self-attention key / value cache of `layer`, out [rows][heads][n_pos][64] in the engine's element type; what 3: one
+ * int32, 1 when a forward of `rows` rows computes the x term in the q/k/v launch (the two-segment fused stage).            */
+int32_t cw_test_decode_state(cw_ctx* ctx, int32_t what, int32_t layer, int32_t rows, int32_t n_pos, void* out);
 /* One launch of the fused logits processors + greedy choice (MinNewTokensLength, SuppressTokensAtBegin, SuppressTokens,
  * WhisperTimeStamp: TF/generation/logits_process.py:203-260, 1816-2047; argmax TF/generation/utils.py:2925) on
  * caller-supplied rows: logits [nb][vocab], ids [nb][t] = prompt + tokens generated so far; choice_out [nb] = token for
