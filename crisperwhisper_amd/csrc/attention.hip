@@ -1434,10 +1434,6 @@ static void launch_cross_split(bool bf16, const CrossSplitParams& p, hipStream_t
     else hipLaunchKernelGGL((attn_cross_split_kernel<float, NQ, false>), grid, dim3(CROSS_THREADS), 0, st, CW_CROSS_LEAD(p, false));
 }
 
-static int g_cross_valu = 0;
-void cw_cross_set_valu(int on) { g_cross_valu = on; }
-static int g_cross_per_row = 0;   // test option "cross_per_row" (same meaning as CW_CROSS_PER_ROW=1, switchable inside a process)
-void cw_cross_set_per_row(int on) { g_cross_per_row = on; }
 int cw_launch_attn_cross_split(bool bf16, const CrossSplitParams& p, hipStream_t st) {
     if ((p.n_keys + ATT_NS - 1) / ATT_NS > 4 * (CROSS_THREADS / 8) || CROSS_THREADS != 512) return CW_ERR_INVALID;
     // every key split must own at least one key (the kernels clamp their loads to the split's last key)
@@ -1482,10 +1478,10 @@ int cw_launch_attn_cross_split(bool bf16, const CrossSplitParams& p, hipStream_t
         hipLaunchKernelGGL((attn_cross_split_kernel<bf16_t, 1, true>), dim3(p.H, p.B, ATT_NS), dim3(CROSS_THREADS), (size_t)lds_pad, st, CW_CROSS_LEAD(p, true));
         return CW_OK;
     }
-    const bool per_row = cw_sw::cw_switches().cross_per_row || g_cross_per_row;   // A/B: one block per row even under beam search
-    const int valu = cw_sw::cw_switches().cross_valu; // A/B: instruction-bound 8-lane-group kernel for 2..6 rows per K/V
+    const bool per_row = cw_sw::cw_switches().cross_per_row;   // A/B: one block per row even under beam search
+    const bool valu = cw_sw::cw_switches().cross_valu; // A/B: instruction-bound 8-lane-group kernel for 2..6 rows per K/V
     const bool no_tr = cw_sw::cw_switches().cross_no_tr; // A/B: 2-byte LDS reads instead of the transposing read
-    if (bf16 && p.kv_div > 1 && p.kv_div <= 16 && p.B % p.kv_div == 0 && !per_row && !(valu || g_cross_valu) &&
+    if (bf16 && p.kv_div > 1 && p.kv_div <= 16 && p.B % p.kv_div == 0 && !per_row && !valu &&
         (p.n_keys + ATT_NS - 1) / ATT_NS <= 256) {
         dim3 grid(p.H, p.B / p.kv_div, ATT_NS);
         if (no_tr) hipLaunchKernelGGL((attn_cross_mfma_kernel<false>), grid, dim3(CROSS_THREADS), 0, st, p, p.kv_div);
@@ -2157,7 +2153,7 @@ int cw_launch_attn_cross_split_fp8(const CrossSplitParams& p, hipStream_t st) {
     if (p.n_keys < 1 || (ATT_NS - 1) * ((p.n_keys + ATT_NS - 1) / ATT_NS) >= p.n_keys) return CW_ERR_INVALID;   // a split without a key
     if (cross8_mfma(p.n_keys)) {
         // rows that share one cache (beam search): one block per (item, head, split) takes all of them (A/B: CW_CROSS_PER_ROW=1)
-        if (!p.qa && p.kv_div > 1 && p.kv_div <= 8 && p.B % p.kv_div == 0 && !cw_sw::cw_switches().cross_per_row && !g_cross_per_row) {
+        if (!p.qa && p.kv_div > 1 && p.kv_div <= 8 && p.B % p.kv_div == 0 && !cw_sw::cw_switches().cross_per_row) {
             const dim3 grid(p.H, p.B / p.kv_div, ATT_NS);
             if (p.kv_div <= 4) hipLaunchKernelGGL((attn_cross_mfma8_rows_kernel<1>), grid, dim3(CROSS_THREADS), 0, st, p, p.kv_div);
             else hipLaunchKernelGGL((attn_cross_mfma8_rows_kernel<2>), grid, dim3(CROSS_THREADS), 0, st, p, p.kv_div);

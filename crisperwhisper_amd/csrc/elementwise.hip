@@ -880,14 +880,11 @@ __global__ __launch_bounds__(64) void beam_topk_merge_kernel(const float* __rest
     }
 }
 
-static int g_topk_1block = -1;   // 1: the single-block kernel (differential tests / A-B); -1: from the environment
-void cw_beam_topk_set_1block(int on) { g_topk_1block = on; }
 size_t cw_beam_topk_scratch_floats(int rows) { return (size_t)rows * BT_NS * BT_REC; }
 
 int cw_launch_beam_topk(const SampleParams& p, int n_cand, float* cand_val, int* cand_id, float* scratch, hipStream_t st) {
     if (n_cand < 1 || n_cand > 64) return CW_ERR_INVALID;
-    if (g_topk_1block < 0) g_topk_1block = cw_sw::cw_switches().beam_topk_1block;
-    const bool one_block = g_topk_1block != 0;
+    const bool one_block = cw_sw::cw_switches().beam_topk_1block;   // the single-block kernel (differential tests / A-B)
     if (scratch && !one_block && (p.V + BT_NS - 1) / BT_NS <= BT_PER_LANE * 256) {
         hipLaunchKernelGGL(beam_topk_partial_kernel, dim3(BT_NS, p.B), dim3(256), 0, st, p, n_cand, scratch);
         hipLaunchKernelGGL(beam_topk_merge_kernel, dim3(p.B), dim3(64), 0, st, (const float*)scratch, n_cand, cand_val, cand_id);

@@ -138,43 +138,12 @@ static int create_impl(cw_ctx* c) {
     if (d.dtype != CW_DTYPE_F32 && d.dtype != CW_DTYPE_BF16 && d.dtype != CW_DTYPE_F16) return fail(c, CW_ERR_INVALID, "unknown dtype %d", d.dtype);
     c->f16 = d.dtype == CW_DTYPE_F16;
     c->bf16 = d.dtype == CW_DTYPE_BF16 || c->f16;
-    const cw_sw::Switches sw = cw_sw::read_switches();   // the environment as it is now: a context's switches are fixed at creation
+    c->sw = cw_sw::read_switches();   // the environment as it is now: a context's switches are its own from here on
 #ifndef CW_EXPERIMENTS
-    {
-        const struct { const char* name; bool set; } rejected[] = {{"CW_ROWS_LN", sw.rows_ln}, {"CW_FUSE_MLP", sw.fuse_mlp}, {"CW_MLP_PAIR", sw.mlp_pair},
-                                                                   {"CW_SKINNY", sw.skinny != 0}, {"CW_PREFETCH", sw.prefetch != 0},
-                                                                   {"CW_DECLAYER", sw.declayer}, {"CW_MLP_CHAIN", sw.mlp_chain}};
-        for (const auto& r : rejected)
-            if (r.set)
-                return fail(c, CW_ERR_INVALID, "%s selects a measured-and-rejected kernel variant that is not in this build: make EXTRA=-DCW_EXPERIMENTS", r.name);
-    }
+    for (int i = 0; i < cw_sw::kNumRows; ++i)
+        if (cw_sw::kRows[i].rejected && cw_sw::kRows[i].get(c->sw) != 0)
+            return fail(c, CW_ERR_INVALID, "%s selects a measured-and-rejected kernel variant that is not in this build: make EXTRA=-DCW_EXPERIMENTS", cw_sw::kRows[i].env);
 #endif
-    c->use_graph = !sw.no_graph;
-    c->fuse_rows = !sw.no_fuse_rows;
-    c->fuse_rows8 = !sw.no_fuse_rows8;
-    c->fuse_beam = !sw.no_fuse_beam;
-    c->own_cols = !sw.no_own_cols;
-    c->short_hist_enabled = !sw.no_short_hist;
-    c->fold_enabled = !sw.no_ln_fold;
-    c->fuse6_enabled = !sw.no_fuse6;
-    c->rows_ln_enabled = sw.rows_ln;
-    c->rows_hilo = !sw.no_rows_hilo;
-    c->skinny_mode = sw.skinny;
-    c->stack_center = !sw.no_stack_center;
-    c->mid16 = !sw.no_mid16;
-    c->dtw_block = sw.dtw_block;
-    c->fuse_mlp = sw.fuse_mlp;
-    c->wpack_enabled = !sw.no_wpack;
-    c->wnt = !sw.no_wnt;
-    c->mlp_pair = sw.mlp_pair;
-    c->mlp_pair_fence = sw.mlp_pair_fence;
-    c->declayer = sw.declayer;
-    c->qkv_self = !sw.no_qkv_self;
-    c->xq_in_qkv = !sw.no_xq_in_qkv;
-    c->mlp_chain = sw.mlp_chain;
-    c->stack_nt3 = sw.stack_nt3;
-    c->stack_nt5 = sw.stack_nt5;
-    c->prefetch = sw.prefetch;   // experiments builds only (refused above otherwise)
     c->esz = c->bf16 ? 2 : 4;
     c->Bm = Bm;
     c->S_pad = 1536;
@@ -494,7 +463,7 @@ static int apply_folds(cw_ctx* c) {
     // six-launch layer: product matrices W'q_c Wo and W'1 Wo_c (f32 from the checkpoint values, one 16-bit rounding), the
     // constants W'q_c bo / W'1 bo_c and the row sums of the folded 16-bit weights (what the MFMAs actually multiply by)
     const int D = c->d.d_model, F = c->d.ffn_dim;
-    bool all = !c->folds.empty() && c->fuse6_enabled && F % D == 0 && D <= 1280 && D % 64 == 0 && F % 64 == 0 && c->d.n_heads <= 20;
+    bool all = !c->folds.empty() && !c->sw.no_fuse6 && F % D == 0 && D <= 1280 && D % 64 == 0 && F % 64 == 0 && c->d.n_heads <= 20;
     if (all) {
         for (int l = 0; l < c->d.dec_layers && all; ++l) {
             const cw_ctx::Fold *fq = nullptr, *f1 = nullptr;
@@ -537,7 +506,7 @@ static int apply_folds(cw_ctx* c) {
 // wfrag_pack_kernel) -- in place through one scratch buffer -- and the tied embedding gets a packed copy for the logits GEMV.
 // A tensor loaded afterwards would land row-major in a packed matrix: refused like a load after folding.
 static int pack_decoder_weights(cw_ctx* c) {
-    if (!c->bf16 || !c->wpack_enabled || c->wpacked) return CW_OK;
+    if (!c->bf16 || c->sw.no_wpack || c->wpacked) return CW_OK;
     const int D = c->d.d_model, F = c->d.ffn_dim, V = c->d.vocab_size;
     // packed weights are read by gemv2_bf16_kernel / gemv_mt_kernel / gemv_stack_kernel only (the first-generation GEMV reads
     // row-major): pack exactly when those kernels take every decoder shape -- K = d_model in one K slice (<= 1280), fc2's
@@ -619,14 +588,14 @@ static int load_tensor_impl(cw_ctx* c, const char* name, const float* data, cons
     const size_t DD = (size_t)D * D;
     if (c->wpacked && is_dec)
         return fail(c, CW_ERR_STATE, "decoder weights were already packed for the decode GEMVs: create a new context to load another checkpoint");
-    if (is_dec && c->bf16 && c->fold_enabled) {   // LayerNorm-fed decode projections: folded once all tensors are in
+    if (is_dec && c->bf16 && !c->sw.no_ln_fold) {   // LayerNorm-fed decode projections: folded once all tensors are in
         if (c->ln_folded) return fail(c, CW_ERR_STATE, "weights were already folded: create a new context to load another checkpoint");
         if (r == "self_attn.q_proj.weight") { CWCHK(c, expect(DD)); return stage_fold(c, li, 0, data, D, D, L.wqkv, 0, L.bqkv, 0, qs); }
         if (r == "self_attn.k_proj.weight") { CWCHK(c, expect(DD)); return stage_fold(c, li, 0, data, D, D, L.wqkv, DD, L.bqkv, (size_t)D, 1.f); }
         if (r == "self_attn.v_proj.weight") { CWCHK(c, expect(DD)); return stage_fold(c, li, 0, data, D, D, L.wqkv, 2 * DD, L.bqkv, 2 * (size_t)D, 1.f); }
         if (r == "encoder_attn.q_proj.weight") { CWCHK(c, expect(DD)); return stage_fold(c, li, 1, data, D, D, L.wq_c, 0, L.bq_c, 0, qs); }
         if (r == "fc1.weight") { CWCHK(c, expect((size_t)F * D)); return stage_fold(c, li, 2, data, F, D, L.w1, 0, L.b1, 0, 1.f); }
-        if (c->fuse6_enabled && (r == "self_attn.out_proj.weight" || r == "encoder_attn.out_proj.weight")) {   // f32 copy for the products
+        if (!c->sw.no_fuse6 && (r == "self_attn.out_proj.weight" || r == "encoder_attn.out_proj.weight")) {   // f32 copy for the products
             CWCHK(c, expect(DD));
             cw_ctx::OutStage o{nullptr, li, r[0] == 's' ? 0 : 1};
             HIPCHK(c, hipMalloc((void**)&o.stage, DD * 4));
@@ -849,7 +818,7 @@ int gemv_ln(cw_ctx* c, int epi, const float* x, int Mb, int K, const void* W, in
                    const float* b, const EpiParams& ep) {
     // (17..64 rows over row-major weights -- CW_NO_WPACK=1, or a geometry pack_decoder_weights does not take: no scratch, i.e. groups of
     // 16 rows on the <= 16-row kernels; gemv_mt_kernel reads fragment-major weights only)
-    if (c->bf16 || !g) return KD(c, cw_launch_gemv, c->bf16, epi, x, Mb, K, W, N, g, b, ep, c->st, nullptr, (Mb <= 16 || c->wpacked) ? c->d_xfrag : nullptr, c->bf16 && c->wpacked, c->wnt);
+    if (c->bf16 || !g) return KD(c, cw_launch_gemv, c->bf16, epi, x, Mb, K, W, N, g, b, ep, c->st, nullptr, (Mb <= 16 || c->wpacked) ? c->d_xfrag : nullptr, c->bf16 && c->wpacked, !c->sw.no_wnt);
     int r = KD(c, cw_launch_layernorm_f32, x, g, b, c->dxn, Mb, K, c->st);   // f32 parity mode: unfused LN
     if (r != CW_OK) return r;
     return KD(c, cw_launch_gemv, false, epi, c->dxn, Mb, K, W, N, nullptr, nullptr, ep, c->st);
@@ -886,58 +855,58 @@ static StepPlan plan_step(const cw_ctx* c, int nb) {
     // finish the query (attn_cross_mfma8_kernel<1, 2>; every wave doing it, as at <= 16 rows, measured flat).  CW_NO_FUSE_ROWS8=1: A/B
     // (the rejected 17..64-row A/B variants of -DCW_EXPERIMENTS builds -- rows path, skinny GEMMs, full-key cross-attention -- keep their
     // own twelve / nine launches: they read c->dx and d_xfrag, which the fused stage's alternating buffers would leave stale)
-    const bool ab17 = nb > 16 && (c->rows_ln_enabled || c->skinny_mode != 0);
-    P.fuse = c->bf16 && c->fuse6_ready && c->fuse6_enabled && c->ln_folded && !ab17 && (nb <= 16 || P.frag) && (nb <= 16 || (c->fuse_rows && nb <= 64 && (!c->kv8 || c->fuse_rows8))) &&
+    const bool ab17 = nb > 16 && (c->sw.rows_ln || c->sw.skinny != 0);
+    P.fuse = c->bf16 && c->fuse6_ready && !c->sw.no_fuse6 && c->ln_folded && !ab17 && (nb <= 16 || P.frag) && (nb <= 16 || (!c->sw.no_fuse_rows && nb <= 64 && (!c->kv8 || !c->sw.no_fuse_rows8))) &&
              // beam search (round 6): the hypotheses of an item share a cross-attention block that finishes their queries
              // (attn_cross_mfma_kernel<.., FUSED>, 16-bit cache); CW_NO_FUSE_BEAM=1: the twelve launches
-             (c->beam_K == 0 || (c->fuse_beam && !c->kv8 && c->beam_K <= 16 && !c->fuse_mlp)) &&
-             (!c->kv8 || (KD(c, cw_cross8_is_mfma, CW_N_CTX) && !c->fuse_mlp)) && !((c->fuse_mlp || c->mlp_pair) && nb > 8);
+             (c->beam_K == 0 || (!c->sw.no_fuse_beam && !c->kv8 && c->beam_K <= 16 && !c->sw.fuse_mlp)) &&
+             (!c->kv8 || (KD(c, cw_cross8_is_mfma, CW_N_CTX) && !c->sw.fuse_mlp)) && !((c->sw.fuse_mlp || c->sw.mlp_pair) && nb > 8);
     // 33..64 rows behind the fused stage (round 6): the cross-attention out-projection owns whole columns (no K split, no atomics) and
     // leaves fc1 its 16-bit rows and LayerNorm partial sums -- one preparation launch less per layer (gemm.hip: gemv_mt_kernel OWN / LNA)
-    P.own = c->own_cols && P.fuse && P.frag && nb > 32 && !c->fuse_mlp && !c->mlp_pair && c->rows_ln_ready && D % 32 == 0 && D / 16 <= 96 && D <= 1536 &&
+    P.own = !c->sw.no_own_cols && P.fuse && P.frag && nb > 32 && !c->sw.fuse_mlp && !c->sw.mlp_pair && c->rows_ln_ready && D % 32 == 0 && D / 16 <= 96 && D <= 1536 &&
             D % 128 == 0 && F % 32 == 0;
     // column tiles per X1 block (3 * TD blocks at 1: 240 at large-v3).  17..64 rows: two -- a block's 16 f32 rows are twice the bytes
     // of a weight tile, and a pair of tiles shares them (64 rows, 4 groups: 11.2 us at one tile, 10.5 at two, 15.5 at three)
-    P.nt3 = c->stack_nt3 > 0 ? c->stack_nt3 : (nb > 16 ? 2 : 1);
+    P.nt3 = c->sw.stack_nt3 > 0 ? c->sw.stack_nt3 : (nb > 16 ? 2 : 1);
     // rows <= 8, 16-bit engines: LN + q/k/v projection + self-attention as ONE launch (declayer.hip: qkv_self_kernel; the tiles
     // reach the attention blocks as granules, the history rows of the cache are requested at kernel entry); bit-identical
     // (its 3 D / 16 blocks wait for each other: only where the whole grid is resident at once on this part; layer < 64: granule tag)
-    P.qs = c->qkv_self && c->bf16 && c->ln_folded && c->wpacked && nb <= 8 && c->beam_K == 0 && D <= 1280 && nb * H <= 3 * (D / 16) && TGT <= 512 &&
+    P.qs = !c->sw.no_qkv_self && c->bf16 && c->ln_folded && c->wpacked && nb <= 8 && c->beam_K == 0 && D <= 1280 && nb * H <= 3 * (D / 16) && TGT <= 512 &&
            c->d.dec_layers <= 64 && 3 * (D / 16) <= c->n_cu * KD(c, cw_qkv_self_blocks_per_cu, D, TGT);
     // behind qkv_self and in front of the fused stage, one tile per block, packed weights: the x segment of the stage (qa = W'q_c x, which depends on
     // nothing the self-attention produces) rides in the V-tile blocks of qkv_self_kernel, which finish early; the attention epilogue leaves the 16-bit
     // rows the stage would round itself, and the stage is two segments over them (gemv_stack_a16_kernel).  Bit-identical (tests/test_xq_in_qkv.py).
-    // The hand-off fallback (c->qkv_self off), two-launch q/k/v, 9..64 rows, beam search, f32 and row-major weights keep the three segments.
-    P.xq = c->xq_in_qkv && P.qs && P.fuse && P.nt3 == 1 && cw_sw::cw_switches().qkv_self_dbg == 0 && !c->fuse_mlp && !c->declayer && !c->mlp_pair && !c->mlp_chain;
-    P.short_hist = c->hist_short && c->short_hist_enabled && nb > 8;   // bytes matter from 9 rows up (<= 8: latency-bound, qkv_self)
+    // The hand-off fallback (sw.no_qkv_self set), two-launch q/k/v, 9..64 rows, beam search, f32 and row-major weights keep the three segments.
+    P.xq = !c->sw.no_xq_in_qkv && P.qs && P.fuse && P.nt3 == 1 && cw_sw::cw_switches().qkv_self_dbg == 0 && !c->sw.fuse_mlp && !c->sw.declayer && !c->sw.mlp_pair && !c->sw.mlp_chain;
+    P.short_hist = c->hist_short && !c->sw.no_short_hist && nb > 8;   // bytes matter from 9 rows up (<= 8: latency-bound, qkv_self)
     // <= 16 rows behind the fused stage: fc1 writes gelu(.) in the 16-bit type fc2 would round it to anyway (bit-identical): fc2's activation load halves
-    P.mid16 = P.fuse && !P.frag && F > 1280 && c->mid16;
+    P.mid16 = P.fuse && !P.frag && F > 1280 && !c->sw.no_mid16;
 #ifdef CW_EXPERIMENTS
-    P.fuse_mlp = c->fuse_mlp;
-    P.mlp_pair = c->mlp_pair && F % D == 0 && D % 32 == 0 && F / 32 <= 256 && F / D <= 32;
-    P.mlp_chain = c->mlp_chain && c->wpacked && c->mid16 && nb <= 8 && KD(c, cw_mlp_chain_ok, nb, D, F);
+    P.fuse_mlp = c->sw.fuse_mlp;
+    P.mlp_pair = c->sw.mlp_pair && F % D == 0 && D % 32 == 0 && F / 32 <= 256 && F / D <= 32;
+    P.mlp_chain = c->sw.mlp_chain && c->wpacked && !c->sw.no_mid16 && nb <= 8 && KD(c, cw_mlp_chain_ok, nb, D, F);
     // rows <= 8: X1 and the cross-attention as ONE persistent launch (declayer.hip): the K/V rows are requested at kernel
     // entry and stream under the GEMV tile; qa / qb / the partial sums cross CUs as granules.  Bit-identical to the two launches.
-    P.dl = P.fuse && c->declayer && !c->kv8 && !c->fuse_mlp && P.nt3 == 1 && c->wpacked && nb <= 8 && 3 * (D / 16) <= c->n_cu &&
+    P.dl = P.fuse && c->sw.declayer && !c->kv8 && !c->sw.fuse_mlp && P.nt3 == 1 && c->wpacked && nb <= 8 && 3 * (D / 16) <= c->n_cu &&
            nb * H * ATT_NS <= 4 * c->n_cu && D / 16 <= 128 && KD(c, cw_dec_layer_lds, D) <= (size_t)160 * 1024;
     // 17..64 rows without preparation launches (decfuse.hip: gemv_rows_kernel): the residual GEMVs own whole columns and leave
     // the stream in f32, its 16-bit fragment-major copy in d_xfrag and LayerNorm partial sums in d_rstats; the LayerNorm
     // GEMVs read that copy and normalise their outputs.  d_xfrag2 carries attention outputs and the GELU'd MLP rows.
-    // 17..64 rows, DEFAULT (skinny_mode 0): the round-3 path -- gemv_prep_kernel (LayerNorm / combine -> fragment-major rows) +
+    // 17..64 rows, DEFAULT (sw.skinny 0): the round-3 path -- gemv_prep_kernel (LayerNorm / combine -> fragment-major rows) +
     // gemv_mt_kernel per projection.  A/B only (-DCW_EXPERIMENTS builds, CW_SKINNY=1|2; measured slower in the step,
     // profiles/r04_b64_skinny_planes_rejected_*): the LayerNorm projections as skinny-M GEMMs (skinny.hip): f32 rows -> K-split
     // partial planes, finished (statistics, bias, cache / GELU epilogue) by one light launch.  The residual projections stay on
     // the 16-column K-split GEMV either way: their cost is the f32 atomics (7 ps each), which a wider tile with more K slices multiplies.
     P.sk_ok = P.frag && c->wpacked && c->ln_folded && c->rows_ln_ready && c->d_planes;
-    P.skinny = P.sk_ok && c->skinny_mode >= 2;
+    P.skinny = P.sk_ok && c->sw.skinny >= 2;
     // greedy rows over the 16-bit cache: one cross-attention block per (row, head) over all keys writes the out-projection's
     // 16-bit rows itself (1280 blocks at 64 rows: the chip is full without key splits)
-    P.xfull = P.frag && c->skinny_mode >= 1 && c->beam_K == 0 && !c->kv8 && !c->rows_ln_enabled && H <= 20 && CW_N_CTX <= 24 * 64;
-    P.rows = !P.skinny && P.frag && c->rows_ln_ready && c->rows_ln_enabled && c->ln_folded && D <= 1280;
+    P.xfull = P.frag && c->sw.skinny >= 1 && c->beam_K == 0 && !c->kv8 && !c->sw.rows_ln && H <= 20 && CW_N_CTX <= 24 * 64;
+    P.rows = !P.skinny && P.frag && c->rows_ln_ready && c->sw.rows_ln && c->ln_folded && D <= 1280;
     // bf16 only: the 16-bit copy of the residual rows keeps 8 mantissa bits of values that are NOT normalised yet; carried as
     // hi + lo halves (two MFMAs per fragment) the LayerNorm GEMVs see 16 bits, more than the rounded LN(x) of the prepared path
-    P.lo_off = (c->rows_hilo && !c->f16) ? 64 * (D / 8) : 0;
-    P.pf = c->prefetch > 0 && c->bf16 && c->beam_K == 0 && !c->kv8;
+    P.lo_off = (!c->sw.no_rows_hilo && !c->f16) ? 64 * (D / 8) : 0;
+    P.pf = c->sw.prefetch > 0 && c->bf16 && c->beam_K == 0 && !c->kv8;
 #endif
     return P;
 }
@@ -1015,10 +984,10 @@ static int layer_self_attention(cw_ctx* c, const StepPlan& P, int l, int nb, con
     }
     QkvSelfParams qp = zeroed<QkvSelfParams>();
     qp.x = x; qp.W = L.wqkv; qp.bias = L.bqkv; qp.sk = L.sk; qp.sv = L.sv; qp.cap = TGT; qp.pos = c->d_pos; qp.out = c->dattn;
-    qp.gq = c->d_gq2; qp.gkv = c->d_gkv; qp.epoch = c->d_epoch; qp.layer = l; qp.err = c->d_err; qp.Mb = nb; qp.D = D; qp.H = H; qp.fail_pos = c->fail_pos; qp.wnt = c->wnt ? 1 : 0;
+    qp.gq = c->d_gq2; qp.gkv = c->d_gkv; qp.epoch = c->d_epoch; qp.layer = l; qp.err = c->d_err; qp.Mb = nb; qp.D = D; qp.H = H; qp.fail_pos = c->fail_pos; qp.wnt = !c->sw.no_wnt ? 1 : 0;
     const int dbg = cw_sw::cw_switches().qkv_self_dbg;   // 1: tiles fused, attention by attn_decode_kernel behind it (bisecting aid)
     if (dbg) { qp.q_plain = c->dq; qp.no_attn = 1; }
-    if (P.xq) { qp.xq_W = L.ws3; qp.xq_bias = L.qa_bias; qp.xq_wsum = c->stack_center ? L.q_wsum : nullptr; qp.xq_out = c->d_qa; qp.out16 = c->d_attn16; }
+    if (P.xq) { qp.xq_W = L.ws3; qp.xq_bias = L.qa_bias; qp.xq_wsum = !c->sw.no_stack_center ? L.q_wsum : nullptr; qp.xq_out = c->d_qa; qp.out16 = c->d_attn16; }
     STG(DST_QKV_SELF, KD(c, cw_launch_qkv_self, qp, c->st));
     if (dbg) STG(DST_SELF_ATTN, self_attn(c, P, L, nb));
     return CW_OK;
@@ -1027,9 +996,9 @@ static int layer_self_attention(cw_ctx* c, const StepPlan& P, int l, int nb, con
 static StackParams stack_params(cw_ctx* c, LayerW& L, int nb, const float* xin, float* xalt) {
     const int D = c->d.d_model, TD = D / 16;
     StackParams sp = zeroed<StackParams>();
-    sp.W = L.ws3; sp.wpk = c->wpacked ? 1 : 0; sp.wnt = c->wnt ? 1 : 0; sp.K = D; sp.Mb = nb; sp.nseg = 3;
+    sp.W = L.ws3; sp.wpk = c->wpacked ? 1 : 0; sp.wnt = !c->sw.no_wnt ? 1 : 0; sp.K = D; sp.Mb = nb; sp.nseg = 3;
     sp.seg[0].x = xin;      sp.seg[0].bias = L.qa_bias; sp.seg[0].out = c->d_qa; sp.seg[0].tile0 = 0;      sp.seg[0].n_tiles = TD; sp.seg[0].epi = 0;
-    sp.seg[0].wsum = c->stack_center ? L.q_wsum : nullptr;   // x is rounded as x - mean(x): the operand the cross-attention LayerNorm is sensitive to
+    sp.seg[0].wsum = !c->sw.no_stack_center ? L.q_wsum : nullptr;   // x is rounded as x - mean(x): the operand the cross-attention LayerNorm is sensitive to
     sp.seg[1].x = c->dattn; sp.seg[1].bias = nullptr;   sp.seg[1].out = c->d_qb; sp.seg[1].tile0 = TD;     sp.seg[1].n_tiles = TD; sp.seg[1].epi = 0;
     sp.seg[2].x = c->dattn; sp.seg[2].bias = L.bo;      sp.seg[2].out = xalt;    sp.seg[2].tile0 = 2 * TD; sp.seg[2].n_tiles = TD; sp.seg[2].epi = 1;
     sp.seg[2].resid = xin; sp.seg[2].pstats = c->d_pstats;   // LayerNorm partial sums of x1 for the cross-attention
@@ -1042,7 +1011,7 @@ static int layer_fused(cw_ctx* c, const StepPlan& P, int l, int nb, float*& xin,
     LayerW& L = c->dec[l];
     if (P.xq) {   // qa came out of qkv_self_kernel: qb = (W'q_c Wo) a, x1 = x + Wo a + bo over the 16-bit rows of a
         StackA16Params sp = zeroed<StackA16Params>();
-        sp.W = L.ws3; sp.a16 = c->d_attn16; sp.resid = xin; sp.bias = L.bo; sp.qb = c->d_qb; sp.x1 = xalt; sp.pstats = c->d_pstats; sp.K = D; sp.Mb = nb; sp.wnt = c->wnt ? 1 : 0;
+        sp.W = L.ws3; sp.a16 = c->d_attn16; sp.resid = xin; sp.bias = L.bo; sp.qb = c->d_qb; sp.x1 = xalt; sp.pstats = c->d_pstats; sp.K = D; sp.Mb = nb; sp.wnt = !c->sw.no_wnt ? 1 : 0;
         STG(DST_STACK, KD(c, cw_launch_gemv_stack_a16, sp, c->st));
     } else STG(DST_STACK, KD(c, cw_launch_gemv_stack, stack_params(c, L, nb, xin, xalt), P.nt3, c->st));
     const CrossSplitParams p = cross_params(c, P, L, l, nb, nullptr);
@@ -1088,7 +1057,7 @@ DecLayerParams dec_layer_params(cw_ctx* c, int l, int nb, const float* xin, floa
     const int D = c->d.d_model, H = c->d.n_heads, TGT = c->d.max_target_positions;
     LayerW& L = c->dec[l];
     DecLayerParams dp = zeroed<DecLayerParams>();
-    dp.Ws = L.ws3; dp.x = xin; dp.a = c->dattn; dp.qa_bias = L.qa_bias; dp.q_wsum = c->stack_center ? L.q_wsum : nullptr;
+    dp.Ws = L.ws3; dp.x = xin; dp.a = c->dattn; dp.qa_bias = L.qa_bias; dp.q_wsum = !c->sw.no_stack_center ? L.q_wsum : nullptr;
     dp.bo = L.bo; dp.x1 = xalt;
     dp.K = L.ck; dp.V = L.cv; dp.n_keys = CW_N_CTX; dp.part_o = c->d_part_o; dp.part_ml = c->d_part_ml;
     dp.align_out = c->d.n_align > 0 ? c->d_align : nullptr; dp.align_ml = c->d_align_ml;
@@ -1123,8 +1092,8 @@ static int launch_prefetch_layer(cw_ctx* c, const StepPlan& P, int l, int nb) {
     const int what = cw_sw::cw_switches().prefetch_what;   // 1 weights, 2 cross K/V, 3 both
     if (!(what & 1)) { int k = 0; for (int i = 0; i < r.count; ++i) if (r.p[i] == (const char*)L.ck || r.p[i] == (const char*)L.cv) { r.p[k] = r.p[i]; r.n[k] = r.n[i]; ++k; } r.count = k; }
     if (!(what & 2)) { int k = 0; for (int i = 0; i < r.count; ++i) if (r.p[i] != (const char*)L.ck && r.p[i] != (const char*)L.cv) { r.p[k] = r.p[i]; r.n[k] = r.n[i]; ++k; } r.count = k; }
-    if (wide) hipLaunchKernelGGL(prefetch_kernel<1>, dim3(c->prefetch), dim3(256), 0, c->st2, r, c->d_pf_sink);
-    else hipLaunchKernelGGL(prefetch_kernel<0>, dim3(c->prefetch), dim3(256), 0, c->st2, r, c->d_pf_sink);
+    if (wide) hipLaunchKernelGGL(prefetch_kernel<1>, dim3(c->sw.prefetch), dim3(256), 0, c->st2, r, c->d_pf_sink);
+    else hipLaunchKernelGGL(prefetch_kernel<0>, dim3(c->sw.prefetch), dim3(256), 0, c->st2, r, c->d_pf_sink);
     return CW_OK;
 }
 
@@ -1222,11 +1191,11 @@ static int layer_fused_ab(cw_ctx* c, const StepPlan& P, int l, int nb, float*& x
         StackParams sp = zeroed<StackParams>();
         sp.W = L.ws5; sp.wpk = c->wpacked ? 1 : 0; sp.K = D; sp.Mb = nb; sp.nseg = 3;
         sp.seg[0].x = xalt;     sp.seg[0].bias = L.u1_bias; sp.seg[0].out = c->d_u1; sp.seg[0].tile0 = 0;      sp.seg[0].n_tiles = TF; sp.seg[0].epi = 2;
-        sp.seg[0].wsum = c->stack_center ? L.u1_wsum : nullptr;
+        sp.seg[0].wsum = !c->sw.no_stack_center ? L.u1_wsum : nullptr;
         sp.seg[1].x = c->dattn; sp.seg[1].bias = nullptr;   sp.seg[1].out = c->d_u1; sp.seg[1].tile0 = TF;     sp.seg[1].n_tiles = TF; sp.seg[1].epi = 2;
         sp.seg[2].x = c->dattn; sp.seg[2].bias = L.bo_c;    sp.seg[2].out = xin;     sp.seg[2].tile0 = 2 * TF; sp.seg[2].n_tiles = TD; sp.seg[2].epi = 1;
         sp.seg[2].resid = xalt; sp.seg[2].out2 = c->dx2c;
-        STG(DST_STACK, KD(c, cw_launch_gemv_stack, sp, c->stack_nt5, c->st));
+        STG(DST_STACK, KD(c, cw_launch_gemv_stack, sp, c->sw.stack_nt5, c->st));
         // fc2: mid = gelu(rstd(x2) (u1 - mean(x2) W'1 1) + b'1) on load; x3 = x2 + W2 mid + b2 in place
         Fc2xParams fp{c->dx2c, c->d_u1, L.u1_wsum, L.b1, L.w2, L.b2, xin, nb, D, F, c->wpacked ? 1 : 0};
         STG(DST_FC2, KD(c, cw_launch_gemv_fc2x, fp, c->st));
@@ -1236,7 +1205,7 @@ static int layer_fused_ab(cw_ctx* c, const StepPlan& P, int l, int nb, float*& x
     STG(DST_CROSS_O, cross_out(c, P, L, nb, xalt));
     if (P.mlp_pair) {
         // LN + fc1 + GELU, group barrier, fc2 + residual in one launch (decfuse.hip: mlp_pair_kernel)
-        MlpPairParams mp{xalt, L.w1, L.b1, L.w2, L.b2, c->d_xfrag2, c->d_bar, c->d_err, nb, D, F, c->wpacked ? 1 : 0, c->mlp_pair_fence ? 1 : 0};
+        MlpPairParams mp{xalt, L.w1, L.b1, L.w2, L.b2, c->d_xfrag2, c->d_bar, c->d_err, nb, D, F, c->wpacked ? 1 : 0, c->sw.mlp_pair_fence ? 1 : 0};
         STG(DST_MLP_PAIR, KD(c, cw_launch_mlp_pair, mp, c->st));
     } else if (P.mlp_chain) {
         // LN + fc1 + GELU and fc2 + residual in ONE launch: fc2's blocks request their weights at kernel entry and wait for
@@ -1308,7 +1277,7 @@ int launch_sample(cw_ctx* c, int nb) {
 // decoder forward + logits + sampling for one position, captured once per batch size as a hipGraph
 // (~260 launches -> one replay; every per-step value lives in device memory: d_pos, d_cfg).
 static int run_step(cw_ctx* c, int nb) {
-    const bool graph_ok = c->use_graph && !c->logits_capture;
+    const bool graph_ok = !c->sw.no_graph && !c->logits_capture;
     if (!graph_ok) {
         CWCHK(c, decode_step(c, nb, true));
         return launch_sample(c, nb);
@@ -1339,7 +1308,7 @@ static int run_step(cw_ctx* c, int nb) {
 // kernels are bit-identical, so the caller sees the result it would have had, late.
 #define CW_HANDOFF_RETRY 0x7e57
 void drop_step_graphs(cw_ctx* c) { for (auto& ge : c->step_graph) if (ge) { hipGraphExecDestroy(ge); ge = nullptr; } }   // kernel arguments are baked into the graphs
-static bool handoffs_on(const cw_ctx* c) { return c->qkv_self || c->mlp_chain || c->declayer || c->mlp_pair; }
+static bool handoffs_on(const cw_ctx* c) { return !c->sw.no_qkv_self || c->sw.mlp_chain || c->sw.declayer || c->sw.mlp_pair; }
 static int handoff_gave_up(cw_ctx* c, bool* gave_up, int* word = nullptr) {
     int e = 0;
     HIPCHK(c, hipStreamSynchronize(c->st));
@@ -1351,7 +1320,8 @@ static int handoff_gave_up(cw_ctx* c, bool* gave_up, int* word = nullptr) {
 }
 static int handoffs_off(cw_ctx* c, const char* where) {
     if (!handoffs_on(c)) return fail(c, CW_ERR_HIP, "%s: an in-launch hand-off gave up although none is enabled", where);
-    c->qkv_self = c->mlp_chain = c->declayer = c->mlp_pair = false;
+    c->sw.no_qkv_self = true;
+    c->sw.mlp_chain = c->sw.declayer = c->sw.mlp_pair = false;
     drop_step_graphs(c);
     if (c->handoff_fallbacks++ == 0)
         fprintf(stderr, "crisperwhisper: %s: blocks of one launch waited for each other in vain (GPU shared with other work?); "
@@ -2251,7 +2221,7 @@ static int timestamp_first_cols(cw_ctx* c, const float* w, int nseq, int Ha, int
             c->skew_cap = want;
         }
     }
-    CWCHK(c, cw_launch_dtw(c->d_mat, nseq, N, S, c->d_ncols, c->d_trace, c->d_first_col, c->dtw_block ? c->d_path_text : nullptr, c->dtw_block ? c->d_path_time : nullptr, c->d_path_len, c->st, c->dtw_block ? nullptr : c->d_skew));
+    CWCHK(c, cw_launch_dtw(c->d_mat, nseq, N, S, c->d_ncols, c->d_trace, c->d_first_col, c->sw.dtw_block ? c->d_path_text : nullptr, c->sw.dtw_block ? c->d_path_time : nullptr, c->d_path_len, c->st, c->sw.dtw_block ? nullptr : c->d_skew));
     const bool scores = sc && c->as_on;
     if (scores)
         CWCHK(c, cw_launch_align_path_score(w, nseq, Ha, rows_cap, S, row0, N, c->d_ncols, c->d_first_col, c->as_collar, c->d_as_mass,
@@ -3105,7 +3075,7 @@ int32_t cw_dtw(cw_ctx* c, const float* mat, int32_t N, int32_t M, int32_t* text_
     HIPCHK(c, hipMemcpy(dn, &M, 4, hipMemcpyHostToDevice));
     float* dskew = nullptr;
     HIPCHK(c, hipMalloc((void**)&dskew, cw_dtw_skew_floats(1, N, M) * 4));
-    int r = cw_launch_dtw(dmat, 1, N, M, dn, dtr, dfc, dpt, dpj, dpl, c->st, c->dtw_block ? nullptr : dskew);
+    int r = cw_launch_dtw(dmat, 1, N, M, dn, dtr, dfc, dpt, dpj, dpl, c->st, c->sw.dtw_block ? nullptr : dskew);
     if (r == CW_OK) {
         std::vector<int> pt(N + M + 2), pj(N + M + 2);
         int n = 0;
@@ -3321,10 +3291,6 @@ int32_t cw_set_option(cw_ctx* c, const char* name, int32_t value) {
         c->nb_encoded = 0;                                   // windows must be re-encoded
         return CW_OK;
     }
-#ifndef CW_EXPERIMENTS
-    if ((!strcmp(name, "rows_ln") || !strcmp(name, "skinny")) && value != 0)
-        return fail(c, CW_ERR_INVALID, "option %s selects a measured-and-rejected kernel variant that is not in this build (make EXTRA=-DCW_EXPERIMENTS)", name);
-#endif
     if (!strcmp(name, "test_epoch_forwards")) {   // test hook: pretend this many decoder forwards have run since the granule epoch last started (epoch_hygiene)
         c->forwards_since_reset = (long long)value;
         return CW_OK;
@@ -3334,24 +3300,16 @@ int32_t cw_set_option(cw_ctx* c, const char* name, int32_t value) {
         drop_step_graphs(c);   // kernel arguments are baked into the graphs
         return CW_OK;
     }
-    if (!strcmp(name, "no_wnt")) {    // != 0: default-policy weight loads in the <= 16-row decode GEMVs (CW_NO_WNT; A/B, differential tests)
-        c->wnt = value == 0;
+    // the context's own switches under their names in switches.def (A/B, differential tests); a flag is set by value != 0
+    for (const char* sw_name : {"no_wnt", "no_xq_in_qkv", "rows_ln", "skinny"}) {
+        if (strcmp(name, sw_name)) continue;
+        const cw_sw::Row* r = cw_sw::find(name);
+#ifndef CW_EXPERIMENTS
+        if (r->rejected && value != 0)
+            return fail(c, CW_ERR_INVALID, "option %s selects a measured-and-rejected kernel variant that is not in this build (make EXTRA=-DCW_EXPERIMENTS)", name);
+#endif
+        r->set(c->sw, value);
         drop_step_graphs(c);   // graphs hold the kernel choice
-        return CW_OK;
-    }
-    if (!strcmp(name, "no_xq_in_qkv")) {   // != 0: the fused stage keeps its x segment and f32 attention rows (CW_NO_XQ_IN_QKV; A/B, differential tests)
-        c->xq_in_qkv = value == 0;
-        drop_step_graphs(c);   // graphs hold the kernel choice
-        return CW_OK;
-    }
-    if (!strcmp(name, "rows_ln")) {   // 17..64-row decode: 0 = preparation launch in front of every GEMV (A/B, differential tests)
-        c->rows_ln_enabled = value != 0;
-        drop_step_graphs(c);   // graphs hold the kernel choice
-        return CW_OK;
-    }
-    if (!strcmp(name, "skinny")) {    // 17..64-row decode: cw_ctx::skinny_mode (0 = round-3 path, for A/B and differential tests)
-        c->skinny_mode = value;
-        drop_step_graphs(c);
         return CW_OK;
     }
     return fail(c, CW_ERR_INVALID, "unknown option %s", name);

@@ -14,23 +14,13 @@ int32_t cw_test_set_option(const char* name, int32_t value) {
     if (!strcmp(name, "no_wnt")) { g_test_no_wnt = value; return CW_OK; }
     if (!strcmp(name, "cross_test_fp8")) { g_test_cross_fp8 = value; return CW_OK; }
     if (!strcmp(name, "attn_poison_qpad")) { g_test_attn_poison_qpad = value; return CW_OK; }
-    if (!strcmp(name, "gemm256_min_tiles")) { cw_bf16::cw_gemm_set_256_min_tiles(value); cw_f16::cw_gemm_set_256_min_tiles(value); return CW_OK; }
-    if (!strcmp(name, "beam_topk_1block")) { cw_bf16::cw_beam_topk_set_1block(value); cw_f16::cw_beam_topk_set_1block(value); return CW_OK; }
-    if (!strcmp(name, "gemm_pp")) { cw_bf16::cw_gemm_set_pp(value); cw_f16::cw_gemm_set_pp(value); return CW_OK; }
-    if (!strcmp(name, "gemm_8ph")) { cw_bf16::cw_gemm_set_8ph(value); cw_f16::cw_gemm_set_8ph(value); return CW_OK; }
     if (!strcmp(name, "gemm_gm")) {
 #ifndef CW_EXPERIMENTS
         return CW_ERR_INVALID;
 #endif
         cw_bf16::cw_gemm_set_gm(value); cw_f16::cw_gemm_set_gm(value); return CW_OK;
     }
-    if (!strcmp(name, "gemv_loop")) { cw_bf16::cw_gemv_set_loop(value); cw_f16::cw_gemv_set_loop(value); return CW_OK; }
-    if (!strcmp(name, "mt_variant")) { cw_bf16::cw_gemv_set_mt_variant(value); cw_f16::cw_gemv_set_mt_variant(value); return CW_OK; }
-    if (!strcmp(name, "comb_rowgroups")) { cw_bf16::cw_gemv_set_comb_rowgroups(value); cw_f16::cw_gemv_set_comb_rowgroups(value); return CW_OK; }
-    if (!strcmp(name, "gemm_w128")) { cw_bf16::cw_gemm_set_w128(value); cw_f16::cw_gemm_set_w128(value); return CW_OK; }
-    if (!strcmp(name, "cross_valu")) { cw_bf16::cw_cross_set_valu(value); cw_f16::cw_cross_set_valu(value); return CW_OK; }
-    if (!strcmp(name, "cross_per_row")) { cw_bf16::cw_cross_set_per_row(value); cw_f16::cw_cross_set_per_row(value); return CW_OK; }
-    return CW_ERR_INVALID;
+    return cw_sw::set_test_option(name, value) ? CW_OK : CW_ERR_INVALID;   // the launcher switches: the process table
 }
 
 int32_t cw_test_gemm(cw_ctx* c, int32_t M, int32_t N, int32_t K, const float* A, const float* W, const float* bias,
@@ -1053,7 +1043,7 @@ int32_t cw_test_gemv_stack(cw_ctx* c, const cw_test_gemv_stack_args* a) {
     };
     StackParams sp;
     memset(&sp, 0, sizeof(sp));
-    sp.W = a->wpk ? dWp : dW; sp.wpk = a->wpk ? 1 : 0; sp.wnt = (c->wnt && !g_test_no_wnt) ? 1 : 0; sp.K = K; sp.Mb = Mb; sp.nseg = nseg;
+    sp.W = a->wpk ? dWp : dW; sp.wpk = a->wpk ? 1 : 0; sp.wnt = (!c->sw.no_wnt && !g_test_no_wnt) ? 1 : 0; sp.K = K; sp.Mb = Mb; sp.nseg = nseg;
     float *dout[3] = {}, *dout2[3] = {}, *dps[3] = {}, *dzero = nullptr;
     int tile0 = 0;
     for (int s = 0; s < nseg; ++s) {
@@ -1260,7 +1250,7 @@ int32_t cw_test_gemv_epi(cw_ctx* c, const cw_test_gemv_epi_args* a) {
         const float* xin = comb ? dpo : a->frag_in ? nullptr : a->x16 ? (const float*)dx16 : dx;
         const bool wpacked = c->bf16 && a->wpk;
         r = KD(c, cw_launch_gemv, c->bf16, epi, xin, Mb, K, Wd, N, dg, dbeta, ep, c->st, comb ? &cb : nullptr,
-               (Mb <= 16 || wpacked) ? dscr : nullptr, wpacked, c->wnt && !g_test_no_wnt);
+               (Mb <= 16 || wpacked) ? dscr : nullptr, wpacked, !c->sw.no_wnt && !g_test_no_wnt);
     } else if (op == 1) {
         CWCHK(c, getg(&dout, (size_t)Mpad * K * 2, "out"));
         CWCHK(c, frag_up(dout, a->out, Mb, K, Mpad, FILL));
@@ -1814,7 +1804,7 @@ int32_t cw_time_kernel(cw_ctx* c, int32_t which, int32_t nb, int32_t iters, floa
                 if (c->bf16) {
                     CrossSplitParams p{c->dq, L.ck, L.cv, CW_N_CTX, c->d_part_o, c->d_part_ml, nullptr, c->d_align_ml, nullptr,
                                        c->d_pos, 0, 0, nb, H};
-                    if (c->fuse6_ready && c->fuse6_enabled && c->ln_folded && nb <= 16 && (!c->kv8 || KD(c, cw_cross8_is_mfma, CW_N_CTX))) {
+                    if (c->fuse6_ready && !c->sw.no_fuse6 && c->ln_folded && nb <= 16 && (!c->kv8 || KD(c, cw_cross8_is_mfma, CW_N_CTX))) {
                         p.kv_div = 1; p.qa = c->d_qa; p.qb = c->d_qb; p.qw = L.q_wsum; p.qbias = L.bq_c;
                         p.pstats = c->d_pstats; p.n_pstats = D / 16;
                     }

@@ -68,8 +68,9 @@ struct cw_ctx {
     hipStream_t st = nullptr;
     hipStream_t st2 = nullptr;          // side stream of the decode step: run-ahead prefetch of the next layer's streams (CW_PREFETCH)
     hipEvent_t ev_pf[2] = {nullptr, nullptr};
-    int prefetch = 0;                   // 0 off; n > 0: blocks of the prefetch launch
     unsigned int* d_pf_sink = nullptr;
+    cw_sw::Switches sw{};               // this context's A/B switches (switches.def): the environment when it was created, then its own to edit
+                                        // (cw_set_option "no_wnt" / "no_xq_in_qkv" / "rows_ln" / "skinny"; handoffs_off)
     std::vector<void*> allocs;
     char err[512] = "";
     bool err_set = false;      // a specific message is pending (set by fail(), cleared by cw_last_error)
@@ -82,50 +83,30 @@ struct cw_ctx {
     std::vector<OutStage> out_stages;
     bool fuse6_ready = false;       // product matrices of the fused decoder stages are in place
     bool rows_ln_ready = false;     // row sums of the LayerNorm-folded q/k/v, cross-q and fc1 weights are in place (gemv_rows_kernel)
-    bool rows_ln_enabled = false;   // CW_ROWS_LN=1 (A/B, measured slower): 17..64 rows without the preparation launch in front of every GEMV
-    bool rows_hilo = true;          // CW_NO_ROWS_HILO=1: single 16-bit copy of the residual rows (A/B)
-    bool mid16 = true;              // fc1 hands gelu(.) to fc2 in 16 bits (CW_NO_MID16=1: f32; A/B)
-    bool dtw_block = false;         // CW_DTW_BLOCK=1: round-1 block-per-sequence DTW (A/B)
-    bool stack_center = true;       // fused out-projection / cross-query stage rounds x - mean(x) (CW_NO_STACK_CENTER=1: x itself, round-3 behaviour; A/B)
-    int skinny_mode = 0;            // 17..64 rows (skinny.hip / attention.hip: attn_cross_full_kernel); option "skinny" / CW_SKINNY=n:
-                                    //   0 (default) round-3 path; 1 greedy rows: cross-attention query as a K-split skinny GEMM whose
-                                    //   planes the one-block-per-(row, head) cross-attention finishes, which also writes the
-                                    //   out-projection's rows (no LayerNorm preparation, no finish, no combine launch); 2 = 1 + q/k/v and
-                                    //   fc1 through planes + finish launch.  Both measured slower in the step (profiles/r04_b64_*_rejected_*): A/B only
+    // sw.skinny, 17..64 rows (skinny.hip / attention.hip: attn_cross_full_kernel): 0 (default) round-3 path; 1 greedy rows:
+    // cross-attention query as a K-split skinny GEMM whose planes the one-block-per-(row, head) cross-attention finishes, which also
+    // writes the out-projection's rows (no LayerNorm preparation, no finish, no combine launch); 2 = 1 + q/k/v and fc1 through
+    // planes + finish launch.  Both measured slower in the step (profiles/r04_b64_*_rejected_*): A/B only
     float* d_planes = nullptr;      // [S][rows][N] K-split partial products of the LayerNorm projections (skinny.hip)
     size_t planes_cap = 0;          // floats
     float* d_sk_stats = nullptr;    // [16][64][2] slice statistics of the rows (skinny.hip)
     float* d_rstats = nullptr;      // [max(D, F) / 16][64][2] per-block LayerNorm partial sums of the 17..64-row producers
-    bool fuse6_enabled = true;      // CW_NO_FUSE6=1: eight launches per layer (A/B)
-    bool fuse_mlp = false;          // CW_FUSE_MLP=1: also fuse cross out-projection + fc1 (six launches; measured slower, A/B)
-    bool mlp_pair_fence = false;    // CW_MLP_PAIR_FENCE=1: round-3 hand-over (agent-scope acquire fence behind the group barrier)
-    bool mlp_pair = false;          // CW_MLP_PAIR=1: fc1 + fc2 in one launch with an in-kernel group barrier (A/B: 23 us against 12.8 for two launches)
     unsigned int* d_bar = nullptr; int* d_err = nullptr;   // group barriers of mlp_pair_kernel; "a block gave up waiting" flag
     int handoff_fallbacks = 0;      // times this context left the in-launch hand-offs for the launch-per-stage path because a wait gave up
     int handoff_resumes = 0;        // ... of which the decode call resumed at the failed position instead of starting over
     long long forwards_since_reset = 0;   // upper bound of the decoder forwards since the granule epoch last started at 1 (epoch_hygiene)
     int fail_pos = -1;              // test hook (option "handoff_fail_pos"): qkv_self_kernel gives up at this decoder position
-    // persistent decoder-layer kernel (declayer.hip), rows <= 8: granule buffers, the epoch counter their tags carry, CU count
-    bool declayer = false;          // CW_DECLAYER=1: stage A of declayer.hip (fused stage + cross-attention in one persistent launch; bit-identical,
-                                    // measured SLOWER: 22-24 us against 18.4 for the two launches -- A/B and differential test only)
-    bool qkv_self = true;           // q/k/v projection + self-attention in one launch (declayer.hip: qkv_self_kernel); CW_NO_QKV_SELF=1: two launches
+    // persistent decoder-layer kernels (declayer.hip), rows <= 8: granule buffers, the epoch counter their tags carry, CU count.
+    // Behind qkv_self_kernel (unless sw.no_xq_in_qkv) its V-tile blocks also compute the cross-query x term W'q_c x, its attention
+    // epilogue leaves the 16-bit rows, and the fused stage is the two-segment gemv_stack_a16_kernel (DESIGN.md 6g''')
     unsigned long long *d_gq = nullptr, *d_gps = nullptr, *d_gq2 = nullptr, *d_gkv = nullptr, *d_gflag = nullptr;
-    bool xq_in_qkv = true;          // behind qkv_self: its V-tile blocks also compute the cross-query x term W'q_c x, its attention epilogue leaves the 16-bit rows,
-                                    // and the fused stage is the two-segment gemv_stack_a16_kernel (DESIGN.md 6g'''); CW_NO_XQ_IN_QKV=1 / option "no_xq_in_qkv": three segments (A/B)
     void* d_attn16 = nullptr;       // [8][D] self-attention output in the engine's 16-bit type (qkv_self_kernel<.., XQ> -> gemv_stack_a16_kernel)
-    bool mlp_chain = false;         // CW_MLP_CHAIN=1: fc1 + fc2 in one launch (declayer.hip: mlp_chain_kernel; flags instead of a kernel boundary);
-                                    // bit-identical, measured SLOWER: 13.1 us against 5.7 + 4.9 for the two launches (profiles/r05_mlp_chain_phases.txt)
     unsigned int* d_epoch = nullptr;
     int n_cu = 0;
-    int stack_nt3 = 0, stack_nt5 = 0;   // column tiles per block of the two stacked GEMVs (0 = launcher's choice; CW_STACK_NT3/5)
     bool ln_folded = false;         // decoder LN-GEMVs run plain normalisation (affine part is inside W / bias)
-    bool fold_enabled = true;       // CW_NO_LN_FOLD=1: keep gamma / beta in the kernels
     std::set<std::string> loaded;   // HF tensor names received through cw_load_tensor
     bool weights_ok = false;        // every tensor of the geometry has been loaded (checked once, see cw_check_weights)
     bool wpacked = false;           // the decoder's GEMV matrices are in fragment-major order (gemm.hip: wfrag_pack_kernel)
-    bool wpack_enabled = true;      // CW_NO_WPACK=1: keep them row-major (A/B)
-    bool wnt = true;                // the <= 16-row decode launches stream packed weights that one block reads with non-temporal loads;
-                                    // CW_NO_WNT=1 / option "no_wnt": the default-policy instantiations (A/B)
     void* embed_pk = nullptr;       // fragment-major copy of the tied embedding for the logits GEMV (the row-major one serves the token lookup)
 
     // weights
@@ -152,7 +133,6 @@ struct cw_ctx {
     float *dx = nullptr, *dxn = nullptr, *dq = nullptr, *dattn = nullptr, *dmid = nullptr, *dlogits = nullptr;
     float *dx1 = nullptr, *dx2c = nullptr, *d_qa = nullptr, *d_qb = nullptr, *d_u1 = nullptr, *d_pstats = nullptr;   // fused decoder stages (decfuse.hip)
     float *d_cvec = nullptr, *d_ostats = nullptr;             // 33..64 rows: row centres and per-(column pair, row) LayerNorm partial sums of the column-owning out-projection
-    bool own_cols = true;                                     // CW_NO_OWN_COLS=1: K-split out-projection + LayerNorm preparation launch (A/B)
     void *d_xfrag = nullptr, *d_xfrag2 = nullptr;             // bf16 [64][5120] fragment-major activations of the 17..64-row GEMV path
     int *d_ids = nullptr, *d_forced = nullptr, *d_argmax = nullptr, *d_last_ts = nullptr, *d_finished = nullptr,
         *d_nunf = nullptr, *d_align_slot = nullptr;
@@ -185,11 +165,6 @@ struct cw_ctx {
     int *d_pos = nullptr, *d_cfg = nullptr;   // per-row decoder input position; [n_prompt, min_new, max_length, use_forced]
     hipGraphExec_t step_graph[130] = {};      // captured decode step (layers + logits + sampling) per batch size; + 65: the short-history form (hist_short)
     bool hist_short = false;                  // every row attends over <= 64 self-attention keys in the forward being launched (host knows the position)
-    bool short_hist_enabled = true;           // CW_NO_SHORT_HIST=1: always request 128 history rows (A/B)
-    bool use_graph = true;
-    bool fuse_rows = true;                    // fused out-projection / cross-query stage at 17..64 greedy rows (CW_NO_FUSE_ROWS=1: off)
-    bool fuse_beam = true;                    // ... and under beam search over the 16-bit cache (round 6; CW_NO_FUSE_BEAM=1: the twelve launches)
-    bool fuse_rows8 = true;                   // ... over the e4m3 cache too (CW_NO_FUSE_ROWS8=1: that mode keeps its twelve launches)
     cw_gen_cfg gen{};
     bool gen_set = false;
     bool kv8 = false;                    // cross-attention reads the fp8 cache (cw_set_option "cross_kv_fp8")

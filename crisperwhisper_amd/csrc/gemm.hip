@@ -1885,14 +1885,6 @@ __global__ __launch_bounds__(256) void gemv_f32_kernel(const float* __restrict__
 // Host launchers
 // ---------------------------------------------------------------------------------------------------
 static const bf16_t* g_zero_page = nullptr;   // 256 B of zeros: DMA source for padded rows
-static bool g_use_glds = true;
-static bool g_use_256 = true;   // CW_NO_GEMM256=1: keep the 128x128 tiles everywhere
-static int g_256_min_tiles = 200;
-static int g_use_pp = -1;   // ping-pong schedule for the plain-A 256-tile shapes; -1: from the environment (CW_NO_GEMM_PP)
-void cw_gemm_set_256_min_tiles(int n) { g_256_min_tiles = n; }
-static int g_use_8ph = -1;  // quarter-tile (8-phase) schedule instead of ping-pong; -1: from the environment (CW_NO_GEMM_8PH)
-void cw_gemm_set_pp(int on) { g_use_pp = on; }
-void cw_gemm_set_8ph(int on) { g_use_8ph = on; }
 void cw_gemm_set_gm(int gm) {   // experiments builds: tile order of the 8-phase kernel (see the kernel)
 #ifdef CW_EXPERIMENTS
     if (gm == 0) gm = 8;
@@ -1901,12 +1893,6 @@ void cw_gemm_set_gm(int gm) {   // experiments builds: tile order of the 8-phase
     (void)gm;
 #endif
 }
-static int g_gemv_loop = -1;  // persistent column loop for very wide LayerNorm GEMVs (logits); -1: from the environment (CW_NO_GEMV_LOOP)
-void cw_gemv_set_loop(int on) { g_gemv_loop = on; }
-static int g_comb_rowgroups = -1;  // combining out-projection of <= 8 rows as (N / 32, ksplit, row groups); -1: from the environment (CW_COMB_NO_ROWGROUPS)
-void cw_gemv_set_comb_rowgroups(int on) { g_comb_rowgroups = on; }
-static int g_use_w128 = -1;  // four waves of 128 x 128 (round 4, measured slower: -DCW_EXPERIMENTS builds only); -1: from the environment (CW_GEMM_W128=1)
-void cw_gemm_set_w128(int on) { g_use_w128 = on; }
 
 template <int EPI>
 static void launch_gemm_epi(bool bf16, const AParams& ap, const void* W, int M, int N, int K, const EpiParams& ep,
@@ -1917,22 +1903,22 @@ static void launch_gemm_epi(bool bf16, const AParams& ap, const void* W, int M, 
         std::call_once(once, [] {
             void* z = nullptr;
             if (hipMalloc(&z, 256) == hipSuccess) { hipMemset(z, 0, 256); g_zero_page = (const bf16_t*)z; }
-            if (cw_sw::cw_switches().no_glds) g_use_glds = false;
-            if (cw_sw::cw_switches().no_gemm256) g_use_256 = false;
         });
         // large shapes: 256x256 tiles once they fill most of the chip (>= 200 tiles); small M keeps the 128 tiles
         const int tm2 = (M + BM2 - 1) / BM2, tn2 = (N + BN2 - 1) / BN2;
-        if (g_use_pp < 0) g_use_pp = !cw_sw::cw_switches().no_gemm_pp;
-        const bool use_pp = g_use_pp != 0;
-        if (g_use_8ph < 0) g_use_8ph = !cw_sw::cw_switches().no_gemm_8ph;
+        const cw_sw::Switches& sw = cw_sw::cw_switches();
+        const bool use_glds = !sw.no_glds && g_zero_page;
+        const bool use_256 = use_glds && !sw.no_gemm256 && tm2 * tn2 >= sw.gemm256_min_tiles;
+        const bool plain_a = ap.amode == 0 && N % BN2 == 0;
+        const bool use_pp = !sw.no_gemm_pp, use_8ph = !sw.no_gemm_8ph;
 #ifdef CW_EXPERIMENTS
-        if (g_use_w128 < 0) g_use_w128 = cw_sw::cw_switches().gemm_w128;
+        const bool use_w128 = sw.gemm_w128;
 #else
-        g_use_w128 = 0;
+        const bool use_w128 = false;
 #endif
-        if (g_use_glds && g_zero_page && g_use_256 && g_use_w128 && tm2 * tn2 >= g_256_min_tiles && ap.amode == 0 && N % BN2 == 0) {
+        if (use_256 && use_w128 && plain_a) {
             cw_launch_gemm_w128(EPI, (const bf16_t*)ap.A, ap.lda, (const bf16_t*)W, M, N, K, ep, tm2, tn2, st);
-        } else if (g_use_glds && g_zero_page && g_use_256 && use_pp && g_use_8ph && tm2 * tn2 >= g_256_min_tiles && ap.amode == 0 && N % BN2 == 0) {
+        } else if (use_256 && use_pp && use_8ph && plain_a) {
             static std::once_flag attr_8;
             std::call_once(attr_8, [] {
                 hipFuncSetAttribute((const void*)gemm_bf16_8ph_kernel<EPI>, hipFuncAttributeMaxDynamicSharedMemorySize, 131072);
@@ -1940,7 +1926,7 @@ static void launch_gemm_epi(bool bf16, const AParams& ap, const void* W, int M, 
             hipLaunchKernelGGL((gemm_bf16_8ph_kernel<EPI>), dim3(tm2 * tn2), dim3(512), 131072, st, (const bf16_t*)ap.A, ap.lda,
                                (const bf16_t*)W, M, N, K, ep, tn2);
 #ifdef CW_EXPERIMENTS
-        } else if (g_use_glds && g_zero_page && g_use_256 && use_pp && tm2 * tn2 >= g_256_min_tiles && ap.amode == 0 && N % BN2 == 0) {
+        } else if (use_256 && use_pp && plain_a) {
             static std::once_flag attr_pp;
             std::call_once(attr_pp, [] {
                 hipFuncSetAttribute((const void*)gemm_bf16_pp_kernel<EPI>, hipFuncAttributeMaxDynamicSharedMemorySize, 131072);
@@ -1948,14 +1934,14 @@ static void launch_gemm_epi(bool bf16, const AParams& ap, const void* W, int M, 
             hipLaunchKernelGGL((gemm_bf16_pp_kernel<EPI>), dim3(tm2 * tn2), dim3(512), 131072, st, (const bf16_t*)ap.A, ap.lda,
                                (const bf16_t*)W, M, N, K, ep, tn2, g_zero_page);
 #endif
-        } else if (g_use_glds && g_zero_page && g_use_256 && tm2 * tn2 >= g_256_min_tiles) {
+        } else if (use_256) {
             static std::once_flag attr_once;     // one per EPI instantiation (function-local static in a template)
             std::call_once(attr_once, [] {
                 hipFuncSetAttribute((const void*)gemm_bf16_256_kernel<EPI>, hipFuncAttributeMaxDynamicSharedMemorySize, 131072);
             });
             hipLaunchKernelGGL((gemm_bf16_256_kernel<EPI>), dim3(tm2 * tn2), dim3(512), 131072, st, ap, (const bf16_t*)W, M,
                                N, K, ep, tn2, g_zero_page);
-        } else if (g_use_glds && g_zero_page)
+        } else if (use_glds)
             hipLaunchKernelGGL((gemm_bf16_glds_kernel<EPI>), dim3(tm * tn), dim3(256), 65536, st, ap, (const bf16_t*)W, M,
                                N, K, ep, tn, g_zero_page);
         else
@@ -2065,8 +2051,7 @@ static void launch_gemv2_shape(dim3 grid, size_t lds, int ksplit, const float* x
         // (column indices are clamped and stores masked per column, so N need not be a multiple of the block's columns.)  Very wide
         // outputs (the 51866-column logits: 3242 tiles, 12.7 per CU) take three tiles per block: every tile re-reads the 40 KB of
         // activation rows, which at one tile per block is half of all the bytes a CU takes in
-        if (g_gemv_loop < 0) g_gemv_loop = !cw_sw::cw_switches().no_gemv_loop;   // A/B: 0 = three tiles per block instead of the persistent column loop
-        const bool no_loop = g_gemv_loop == 0;
+        const bool no_loop = cw_sw::cw_switches().no_gemv_loop;   // A/B: three tiles per block instead of the persistent column loop
         if (EPI == EPI_STORE_F32 && ln_g && ksplit == 1 && grid.x >= 1024 && wpk && Kb == K && K % 128 == 0 && K <= 1280 && !cb.part_ml && !no_loop && m_base == 0) {
             // the logits projection: persistent column loop, grid resident at once (3 blocks per CU), tiles spread evenly
             const int cap = cw_sw::cw_switches().gemv_loop_cap;   // blocks in the grid per round of tiles (2 per CU measured best: 24.8 us; 3 per CU 25.9)
@@ -2129,7 +2114,7 @@ static void launch_gemv2(const float* x, int Mb, int K, const void* W, int N, co
     // 9..16 rows (round 6; RPW = 4 callers): the same -- 16 rows x 640 x 4 B x 6 = 246 KB of partials per 16-column block on 160 CUs
     // became grid (40, 2, 4) = 320 blocks of 61 + 41 KB: 8.18 us per launch at 16 rows before (the reference's batch_size)
     if (EPI == EPI_RESID_F32 && cb.part_ml && ksplit > 1 && (RPW == 2 || RPW == 4) && Mb > 1 && N % 32 == 0 && Kb > 256 && Kb <= 768 &&
-        (g_comb_rowgroups < 0 ? !cw_sw::cw_switches().comb_no_rowgroups : g_comb_rowgroups != 0)) {
+        !cw_sw::cw_switches().comb_no_rowgroups) {
         int G = 256 / ((N / 32) * ksplit);
         G = G < 1 ? 1 : (G > Mb ? Mb : G);
         // 13..16 rows: three groups of <= 6 rows, two rows per wave (240 blocks, one per CU) rather than four groups of four
@@ -2172,8 +2157,6 @@ static int cw_gemv_mt_pick(int N, int K, int ksplit) {
     if (N % 32 == 0 && (N / 32) * ksplit * 2 >= 160) return 2;
     return 1;
 }
-static int g_mt_variant = -2;   // -2: from the environment (CW_MT_VARIANT); -1: heuristic; 0: one tile per block; 1: two row groups; 2: two row groups x two column tiles
-void cw_gemv_set_mt_variant(int v) { g_mt_variant = v; }
 
 template <int EPI, int MT>
 static void launch_gemv_mt(const bf16_t* xf, int Mb, int K, const void* W, int N, const EpiParams& ep, bool allow_split,
@@ -2191,8 +2174,7 @@ static void launch_gemv_mt(const bf16_t* xf, int Mb, int K, const void* W, int N
     const int steps = Kb / 128;
     // 33..64 rows: row groups / column-tile pairs (see the kernel).  Chosen per shape from the launch table of
     // profiles/r05_b64_mt_variants.txt; CW_MT_VARIANT=0|1|2 forces one for A/B.
-    if (g_mt_variant == -2) g_mt_variant = cw_sw::cw_switches().mt_variant;
-    int variant = g_mt_variant;
+    int variant = cw_sw::cw_switches().mt_variant;
     if (variant < 0) variant = cw_gemv_mt_pick(N, K, ksplit);
     if (MT >= 3 && prea && variant >= 1 && (variant == 1 || N % 32 == 0)) {
         constexpr int MH = 2;                                  // row tiles per group: 33..64 rows in two groups

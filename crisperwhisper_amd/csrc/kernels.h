@@ -426,17 +426,8 @@ struct ScoreHeadOut : ScoreRowsOut {
 
 #define CW_DTYPE_KERNEL_DECLS \
     int cw_launch_gemm(bool bf16, int epi, const AParams& ap, const void* W, int M, int N, int K, const EpiParams& ep, hipStream_t st); \
-    void cw_gemm_set_256_min_tiles(int n); \
-    void cw_gemm_set_pp(int on); \
-    void cw_gemm_set_8ph(int on); \
     void cw_gemm_set_gm(int gm); \
-    void cw_gemm_set_w128(int on); \
-    void cw_gemv_set_comb_rowgroups(int on); \
-    void cw_gemv_set_mt_variant(int v); \
-    void cw_gemv_set_loop(int on); \
     int cw_launch_gemm_w128(int epi, const bf16_t* A, int lda, const bf16_t* W, int M, int N, int K, const EpiParams& ep, int tm2, int tn2, hipStream_t st); \
-    void cw_cross_set_valu(int on); \
-    void cw_cross_set_per_row(int on); \
     int cw_launch_layernorm_fp8(const float* x, const float* g, const float* b, void* out8, float* scale, int rows, int d, hipStream_t st); \
     int cw_launch_quant_rows_fp8(const void* x, int rows, int K, void* out8, float* scale, hipStream_t st); \
     int cw_launch_gemm_fp8(int epi, const void* A8, int lda, const void* W8, int M, int N, int K, const float* sa, const float* sw, const EpiParams& ep, hipStream_t st); \
@@ -471,7 +462,6 @@ struct ScoreHeadOut : ScoreRowsOut {
     int cw_launch_sample(const SampleParams& p, hipStream_t st); \
     int cw_launch_beam_topk(const SampleParams& p, int n_cand, float* cand_val, int* cand_id, float* scratch, hipStream_t st); \
     size_t cw_beam_topk_scratch_floats(int rows); \
-    void cw_beam_topk_set_1block(int on); \
     int cw_launch_beam_advance(const BeamAdvanceParams& p, hipStream_t st); \
     int cw_launch_align_gather(const float* align, const int* row_of_pos, int n_items, int n_align, int align_rows, int L, int n_keys, float* out, hipStream_t st); \
     int cw_launch_set_pos(int* pos, int value, int B, hipStream_t st, unsigned int* epoch = nullptr); \
