@@ -109,6 +109,9 @@ _SIGS = {
     "cw_set_top_logprobs": (_I, [_P, _I]),
     "cw_get_top_logprobs": (_I, [_P, _P, _P, _I]),
     "cw_get_transcribe_top_logprobs": (_I, [_P, _P, _P, _I, _I]),
+    "cw_set_token_entropy": (_I, [_P, _I]),
+    "cw_get_token_entropy": (_I, [_P, _P, _I]),
+    "cw_get_transcribe_token_entropy": (_I, [_P, _P, _I, _I]),
     "cw_set_sequence_bias": (_I, [_P, _I, _P, _P, _P]),
     "cw_get_logits": (_I, [_P, _P, _I]),
     "cw_set_logits_capture": (_I, [_P, _P, _I]),
@@ -143,6 +146,11 @@ _SIGS = {
     "cw_score_prefill_runs": (_I, [_P]),
     "cw_set_score_top_logprobs": (_I, [_P, _I]),
     "cw_get_score_top_logprobs": (_I, [_P, _P, _P, _I, _I]),
+    "cw_set_score_entropy": (_I, [_P, _I]),
+    "cw_get_score_entropy": (_I, [_P, _P, _I, _I]),
+    "cw_test_score_head_entropy": (_I, [_P, _I, _I, _I, _P, _P, _P, _P, _P, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "cw_test_score_rows_entropy": (_I, [_P, _I, _I, _I, _P, _P, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P]),
+    "cw_time_score_head_entropy": (_I, [_P, _I, _I, _I, _I, _P]),
     "cw_test_score_head_top": (_I, [_P, _I, _I, _I, _P, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _P]),
     "cw_test_score_head_stop_top": (_I, [_P, _I, _I, _I, _P, _P, _P, _P, _P, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P]),
     "cw_test_score_rows_top": (_I, [_P, _I, _I, _I, _P, _P, _I, _I, _I, _P, _P, _P, _P, _P, _P]),
@@ -195,6 +203,7 @@ _SIGS = {
     "cw_test_sample_seeded": (_I, [_P, _I, _P, _P, _I, _I, _I, _I, C.c_float, C.c_uint64, _P, _P]),
     "cw_test_sample_logprobs": (_I, [_P, _I, _P, _P, _I, _I, _I, _I, C.c_float, C.c_uint64, _P, _P, _P, _P]),
     "cw_test_sample_top_logprobs": (_I, [_P, _I, _P, _P, _I, _I, _I, _I, C.c_float, C.c_uint64, _P, _P, _I, _P, _P, _P, _P]),
+    "cw_test_sample_entropy": (_I, [_P, _I, _P, _P, _I, _I, _I, _I, C.c_float, C.c_uint64, _P, _P, _I, _P, _P, _P, _P, _P]),
     "cw_test_sample_biased": (_I, [_P, _I, _P, _P, _I, _I, _I, _I, C.c_float, C.c_uint64, _P, _P, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P]),
     "cw_stage_times": (_I, [_P, _P, _P, _I]),
     "cw_time_kernel": (_I, [_P, _I, _I, _I, _P, _P]),

@@ -277,8 +277,19 @@ __device__ inline float seq_bias_of(const int* __restrict__ tab, int tok, const 
 // start from lead as plain values (14 dwords each, preloaded into user SGPRs at dispatch by the file's -amdgpu-kernarg-preload-count);
 // `p` (a by-value struct is never preloaded, and ends the preloaded run) is fetched under them.  launch_sample_t fills both from
 // the one struct.  SAMPLE_THREADS: the block of sample_kernel, a constant instead of a hidden-argument load.
+//
+// ENT (block-uniform, a template parameter for the same reason; needs p.tok_lp): token entropy (include/crisperwhisper.h,
+// cw_set_token_entropy).  Next to the online pair (rm, rs) a thread keeps rz = sum exp(x - rm) (x - rm); wherever a partial
+// (m_i, S_i, Zc_i) moves to a new centre M it becomes (M, S_i e^(m_i - M), (Zc_i + S_i (m_i - M)) e^(m_i - M)) -- inside the
+// thread, between the block's threads, and between the 16 slices in stage 2, which stores H = log S - Zc / S.  A -inf logit adds
+// nothing (its term is the limit 0, not 0 * -inf); a NaN or +inf one makes the row's value NaN, also where the thread has not met
+// a finite logit yet and the sums above skip it: rq, the plain sum of the thread's logits scaled by 2^-8 (no overflow from finite
+// logits), is NaN exactly when one of them is NaN or both infinities occur.
 #define SAMPLE_THREADS 256
-template <bool TOPK, bool BIAS>
+__device__ inline float ent_recentre(float z, float s, float d) {           // (Zc + S d) e^d, d = old centre - new centre <= 0
+    return (z + s * d) * expf(d);
+}
+template <bool TOPK, bool BIAS, bool ENT>
 __global__ __launch_bounds__(256) void sample_partial_kernel(const float* __restrict__ logits, const int* ids_all, const int* cfg, const int* pos,
                                                              const int* last_ts_tok, const unsigned char* __restrict__ mask, int ldv, int ids_stride,
                                                              SampleParams p, SamplePart* __restrict__ part) {
@@ -309,6 +320,7 @@ __global__ __launch_bounds__(256) void sample_partial_kernel(const float* __rest
     float sv[4][4]; int nmine = 0;                                         // this thread's allowed timestamp scores
     float tv[4][4];                                                        // ... and allowed text scores (p.lp_sum only)
     float rm = -INFINITY, rs = 0.f;                                        // p.tok_lp: online raw max / sum exp(x - rm), v < V
+    [[maybe_unused]] float rz = 0.f, rq = 0.f;                             // ENT: sum exp(x - rm) (x - rm) beside rs; NaN detector
     float rv[4][4];                                                        // TOPK: this thread's raw candidates (-inf: none)
     if (TOPK) {
 #pragma unroll
@@ -352,7 +364,11 @@ __global__ __launch_bounds__(256) void sample_partial_kernel(const float* __rest
         }
         const unsigned char ms[4] = {mk.x, mk.y, mk.z, mk.w};
         unsigned rnd[4] = {0u, 0u, 0u, 0u};
-        if (sampling) philox4x32_10((unsigned)i4, (unsigned)t, stream_lo, stream_hi, seed_lo, seed_hi, rnd);
+        unsigned key_lo = seed_lo, key_hi = seed_hi;
+        // ENT: the ten round keys are derived again in every iteration instead of living in twenty scalar registers across the loop,
+        // which the extra sums would push into spills
+        if constexpr (ENT) asm volatile("" : "+s"(key_lo), "+s"(key_hi));
+        if (sampling) philox4x32_10((unsigned)i4, (unsigned)t, stream_lo, stream_hi, key_lo, key_hi, rnd);
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             const int v = i4 * 4 + j;
@@ -378,10 +394,29 @@ __global__ __launch_bounds__(256) void sample_partial_kernel(const float* __rest
             float gm = -INFINITY;
 #pragma unroll
             for (int j = 0; j < 4; ++j) if (i4 * 4 + j < p.V) gm = fmaxf(gm, xs[j]);
-            if (gm > rm) { rs *= expf(rm - gm); rm = gm; }      // rs == 0 while rm == -inf
-            if (rm > -INFINITY) {
+            if constexpr (ENT) {
 #pragma unroll
-                for (int j = 0; j < 4; ++j) if (i4 * 4 + j < p.V) rs += expf(xs[j] - rm);
+                for (int j = 0; j < 4; ++j) rq += i4 * 4 + j < p.V ? xs[j] * 0x1p-8f : 0.f;
+                if (gm > rm) {                                  // rz == 0 while rm == -inf, as rs
+                    const float d = rm - gm, e = expf(d);
+                    rz = rm > -INFINITY ? (rz + rs * d) * e : 0.f;
+                    rs *= e; rm = gm;
+                }
+                if (rm > -INFINITY) {
+#pragma unroll
+                    for (int j = 0; j < 4; ++j)
+                        if (i4 * 4 + j < p.V) {
+                            const float d = xs[j] - rm, e = expf(d);
+                            rs += e;
+                            rz += e * fmaxf(d, -3.402823466e38f);       // d == -inf: 0 * -3.402823466e38f, not 0 * -inf; a NaN d is in rs already
+                        }
+                }
+            } else {
+                if (gm > rm) { rs *= expf(rm - gm); rm = gm; }  // rs == 0 while rm == -inf
+                if (rm > -INFINITY) {
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) if (i4 * 4 + j < p.V) rs += expf(xs[j] - rm);
+                }
             }
         }
         nmine = it + 1;
@@ -419,6 +454,13 @@ __global__ __launch_bounds__(256) void sample_partial_kernel(const float* __rest
         raw_m = block_max(rm, s_f);
         __syncthreads();
         raw_s = block_sum(rm > -INFINITY ? rs * expf(rm - raw_m) : 0.f, s_f);
+    }
+    if constexpr (ENT) {                                        // the slice's Zc about raw_m: the threads' in the order of raw_s
+        float z = rm > -INFINITY ? ent_recentre(rz, rs, rm - raw_m) : 0.f;
+        z = rq != rq ? NAN : z;
+        __syncthreads();
+        z = block_sum(z, s_f);
+        if (tid == 0) p.ent_part[(size_t)b * SAMPLE_NS + sl] = z;
     }
     if (TOPK) {
         // p.top_k rounds of "best candidate strictly after the previous winner"; the waves' winners alternate between two
@@ -472,7 +514,7 @@ __global__ __launch_bounds__(256) void sample_partial_kernel(const float* __rest
     }
 }
 
-template <typename T, bool TOPK, bool BIAS>
+template <typename T, bool TOPK, bool BIAS, bool ENT>
 __global__ __launch_bounds__(1024) void sample_kernel(int* ids_all, const int* cfg, int* pos, int* finished, int* last_ts_tok,
                                                        const void* partials, int ids_stride, int timestamp_begin, SampleParams p) {
     __shared__ float s_f[64];
@@ -584,6 +626,17 @@ __global__ __launch_bounds__(1024) void sample_kernel(int* ids_all, const int* c
             for (int i = 0; i < SAMPLE_NS; ++i)
                 if (pr[i].pad[1] > -INFINITY) Sr += pr[i].pad[2] * expf(pr[i].pad[1] - Mr);
             p.tok_lp[(size_t)b * ids_stride + t] = lg[tok] - (Mr + logf(Sr));
+            if constexpr (ENT) {
+                // entropy of the same distribution: the slices' Zc moved to the row maximum in slice order.  An empty slice holds
+                // 0, or NaN where it met a NaN; no finite logit at all is log 0 - 0 / 0 = NaN.  Rounding can leave a one-point
+                // distribution a hair below 0: the value is clamped there (a NaN stays).
+                const float* zp = p.ent_part + (size_t)b * SAMPLE_NS;
+                float Zr = 0.f;
+                for (int i = 0; i < SAMPLE_NS; ++i)
+                    Zr += pr[i].pad[1] > -INFINITY ? ent_recentre(zp[i], pr[i].pad[2], pr[i].pad[1] - Mr) : zp[i];
+                const float H = logf(Sr) - Zr / Sr;
+                p.tok_ent[(size_t)b * ids_stride + t] = H < 0.f ? 0.f : H;
+            }
         }
         if (was_finished) tok = p.pad;                                  // utils.py:2928-2929
         if (fin_in != 2) ids[t] = tok;
@@ -947,27 +1000,32 @@ int cw_launch_align_gather(const float* align, const int* row_of_pos, int n_item
     return CW_OK;
 }
 
-template <bool TOPK, bool BIAS>
+template <bool TOPK, bool BIAS, bool ENT>
 static void launch_sample_t(const SampleParams& p, hipStream_t st) {
-    hipLaunchKernelGGL((sample_partial_kernel<TOPK, BIAS>), dim3(p.B, SAMPLE_NS), dim3(256), 0, st, p.logits, (const int*)p.ids, p.cfg,
+    hipLaunchKernelGGL((sample_partial_kernel<TOPK, BIAS, ENT>), dim3(p.B, SAMPLE_NS), dim3(256), 0, st, p.logits, (const int*)p.ids, p.cfg,
                        (const int*)p.pos, (const int*)p.last_ts_tok, p.mask, p.ldv, p.ids_stride, p, (SamplePart*)p.partials);
     if (p.embed_bf16)
-        hipLaunchKernelGGL((sample_kernel<bf16_t, TOPK, BIAS>), dim3(p.B), dim3(SAMPLE_THREADS), 0, st, p.ids, p.cfg, p.pos, p.finished,
+        hipLaunchKernelGGL((sample_kernel<bf16_t, TOPK, BIAS, ENT>), dim3(p.B), dim3(SAMPLE_THREADS), 0, st, p.ids, p.cfg, p.pos, p.finished,
                            p.last_ts_tok, p.partials, p.ids_stride, p.timestamp_begin, p);
     else
-        hipLaunchKernelGGL((sample_kernel<float, TOPK, BIAS>), dim3(p.B), dim3(SAMPLE_THREADS), 0, st, p.ids, p.cfg, p.pos, p.finished,
+        hipLaunchKernelGGL((sample_kernel<float, TOPK, BIAS, ENT>), dim3(p.B), dim3(SAMPLE_THREADS), 0, st, p.ids, p.cfg, p.pos, p.finished,
                            p.last_ts_tok, p.partials, p.ids_stride, p.timestamp_begin, p);
+}
+template <bool TOPK, bool BIAS>
+static void launch_sample_e(const SampleParams& p, hipStream_t st) {           // token entropy: the instantiations that also keep Zc
+    if (p.tok_ent) launch_sample_t<TOPK, BIAS, true>(p, st); else launch_sample_t<TOPK, BIAS, false>(p, st);
 }
 int cw_launch_sample(const SampleParams& p, hipStream_t st) {
     static_assert(SAMPLE_NS == 16 && SB_OFF > SB_SLICE + SAMPLE_NS, "the sequence_bias table holds one range per sampler slice");
     if (!p.partials || (p.ldv >> 2) > SAMPLE_NS * 1024 || (p.ldv & 3)) return CW_ERR_INVALID;
+    if (p.tok_ent && (!p.ent_part || !p.tok_lp)) return CW_ERR_INVALID;
     const bool bias = p.seq_bias != nullptr;                    // sequence_bias: the instantiations that also add the table
     if (p.top_k != 0) {                                         // top_logprobs: the instantiations that also select
         if (p.top_k < 0 || p.top_k > CW_TOP_LOGPROBS_MAX || !p.top_part || !p.top_id || !p.top_lp || !p.tok_lp) return CW_ERR_INVALID;
-        if (bias) launch_sample_t<true, true>(p, st); else launch_sample_t<true, false>(p, st);
+        if (bias) launch_sample_e<true, true>(p, st); else launch_sample_e<true, false>(p, st);
         return CW_OK;
     }
-    if (bias) launch_sample_t<false, true>(p, st); else launch_sample_t<false, false>(p, st);
+    if (bias) launch_sample_e<false, true>(p, st); else launch_sample_e<false, false>(p, st);
     return CW_OK;
 }
 

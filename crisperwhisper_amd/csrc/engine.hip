@@ -384,7 +384,8 @@ void cw_destroy(cw_ctx* c) {
     for (void* p : c->allocs) hipFree(p);
     for (void* p : {(void*)c->pf_x, c->pf_a, c->pf_q, c->pf_o, c->pf_h}) if (p) hipFree(p);
     for (void* p : {(void*)c->sc_src, (void*)c->sc_tgt, (void*)c->sc_ti, c->sc_a, (void*)c->sc_part, (void*)c->sc_lp, (void*)c->sc_tl,
-                    (void*)c->sc_stop, (void*)c->sc_spart, (void*)c->sc_tpart, (void*)c->sc_alt_id, (void*)c->sc_alt_lp}) if (p) hipFree(p);
+                    (void*)c->sc_stop, (void*)c->sc_spart, (void*)c->sc_tpart, (void*)c->sc_alt_id, (void*)c->sc_alt_lp,
+                    (void*)c->sc_epart, (void*)c->sc_ent}) if (p) hipFree(p);
     if (c->h_nunf) hipHostFree(c->h_nunf);
     if (c->ev0) hipEventDestroy(c->ev0);
     if (c->ev1) hipEventDestroy(c->ev1);
@@ -1268,6 +1269,7 @@ int launch_sample(cw_ctx* c, int nb) {
     if (c->score_tokens) { sp.lp_sum = c->d_lp_sum; sp.lp_cnt = c->d_lp_cnt; }
     if (c->tok_lp_on) sp.tok_lp = c->d_tok_lp;
     if (c->tok_lp_on && c->top_k > 0) { sp.top_k = c->top_k; sp.top_part = c->d_top_part; sp.top_id = c->d_top_id; sp.top_lp = c->d_top_lp; }
+    if (c->tok_lp_on && c->tok_ent_on) { sp.tok_ent = c->d_tok_ent; sp.ent_part = c->d_ent_part; }
     if (c->sb_n > 0) sp.seq_bias = c->d_seq_bias;
     sp.epoch = c->d_epoch;
     sp.samp = c->d_samp; sp.pert = c->d_sample_pert;
@@ -1386,13 +1388,14 @@ static int prefill_reserve(cw_ctx* c, size_t M) {
 }
 
 // What the scoring kernels write, from the context (kernels.h: ScoreHeadOut): the loop's [Bm][TGT] arrays (step) or the head's [M]
-// arrays; stop: the STOP form (cw_align_cut_tokens); the TOPK form with cw_set_score_top_logprobs
+// arrays; stop: the STOP form (cw_align_cut_tokens); the TOPK form with cw_set_score_top_logprobs, the ENT form with cw_set_score_entropy
 static ScoreHeadOut score_out(cw_ctx* c, bool stop, bool step) {
     ScoreHeadOut o{};
     o.logprob = step ? c->sc_step_lp : c->sc_lp; o.top_id = step ? c->sc_step_ti : c->sc_ti; o.top_logprob = step ? c->sc_step_tl : c->sc_tl;
     if (stop) { o.stop_logprob = step ? c->sc_step_stop : c->sc_stop; o.eos = c->gen.eos_token_id; o.ts_begin = c->gen.no_timestamps_token_id + 1; }
     o.k = c->sc_top_k; o.alt_id = step ? c->sc_step_alt_id : c->sc_alt_id; o.alt_logprob = step ? c->sc_step_alt_lp : c->sc_alt_lp;
     o.part = c->sc_part; o.spart = c->sc_spart; o.tpart = c->sc_tpart;
+    if (c->sc_ent_on) { o.entropy = step ? c->sc_step_ent : c->sc_ent; o.epart = c->sc_epart; }
     return o;
 }
 
@@ -1507,6 +1510,7 @@ static int decode_once(cw_ctx* c, int32_t nb, const int32_t* prompt, int32_t n_p
         HIPCHK(c, hipMemsetAsync(c->d_lp_sum, 0, nb * 4, c->st));
         HIPCHK(c, hipMemsetAsync(c->d_lp_cnt, 0, nb * 4, c->st));
         if (c->tok_lp_on) HIPCHK(c, hipMemsetAsync(c->d_tok_lp, 0xff, (size_t)nb * TGT * 4, c->st));   // all-ones = NaN
+        if (c->tok_ent_on) HIPCHK(c, hipMemsetAsync(c->d_tok_ent, 0xff, (size_t)nb * TGT * 4, c->st));
         if (c->top_k > 0) {                                                                             // ... and id -1
             HIPCHK(c, hipMemsetAsync(c->d_top_id, 0xff, (size_t)nb * TGT * CW_TOP_LOGPROBS_MAX * 4, c->st));
             HIPCHK(c, hipMemsetAsync(c->d_top_lp, 0xff, (size_t)nb * TGT * CW_TOP_LOGPROBS_MAX * 4, c->st));
@@ -1518,6 +1522,7 @@ static int decode_once(cw_ctx* c, int32_t nb, const int32_t* prompt, int32_t n_p
                 HIPCHK(c, hipMemsetAsync(c->d_lp_sum + b, 0, 4, c->st));
                 HIPCHK(c, hipMemsetAsync(c->d_lp_cnt + b, 0, 4, c->st));
                 if (c->tok_lp_on) HIPCHK(c, hipMemsetAsync(c->d_tok_lp + (size_t)b * TGT, 0xff, (size_t)TGT * 4, c->st));
+                if (c->tok_ent_on) HIPCHK(c, hipMemsetAsync(c->d_tok_ent + (size_t)b * TGT, 0xff, (size_t)TGT * 4, c->st));
                 if (c->top_k > 0) {
                     const size_t row = (size_t)TGT * CW_TOP_LOGPROBS_MAX;
                     HIPCHK(c, hipMemsetAsync(c->d_top_id + (size_t)b * row, 0xff, row * 4, c->st));
@@ -1647,6 +1652,7 @@ int32_t cw_set_thresholds(cw_ctx* c, float logprob_threshold, float no_speech_th
 int32_t cw_set_token_logprobs(cw_ctx* c, int32_t on) {
     const bool want = on != 0;
     if (!want && c->top_k > 0) CWCHK(c, cw_set_top_logprobs(c, 0));   // the alternatives share this switch's normaliser
+    if (!want && c->tok_ent_on) CWCHK(c, cw_set_token_entropy(c, 0)); // ... and so does the entropy
     const size_t n = (size_t)c->Bm * c->d.max_target_positions;
     if (want && !c->d_tok_lp) {
         CWCHK(c, dmalloc(c, &c->d_tok_lp, n * 4, false));
@@ -1675,6 +1681,41 @@ int32_t cw_get_transcribe_token_logprobs(cw_ctx* c, float* out, int32_t B, int32
         const int n = (int)c->tr_lp[i].size();
         if (n > cap) return fail(c, CW_ERR_INVALID, "item %d holds %d tokens, capacity %d", i, n, cap);
         memcpy(out + (size_t)i * cap, c->tr_lp[i].data(), (size_t)n * 4);
+        for (int k = n; k < cap; ++k) out[(size_t)i * cap + k] = NAN;
+    }
+    return CW_OK;
+}
+
+// ---- token entropy: predictive entropy of every step's raw distribution (include/crisperwhisper.h) -------------------------
+int32_t cw_set_token_entropy(cw_ctx* c, int32_t on) {
+    const bool want = on != 0;
+    if (want && !c->tok_lp_on) return fail(c, CW_ERR_STATE, "token entropy needs token log-probabilities (cw_set_token_logprobs)");
+    const size_t n = (size_t)c->Bm * c->d.max_target_positions;
+    if (want && !c->d_ent_part) CWCHK(c, dmalloc(c, &c->d_ent_part, (size_t)c->Bm * 16 * 4));
+    if (want && !c->d_tok_ent) CWCHK(c, dmalloc(c, &c->d_tok_ent, n * 4, false));
+    if (want != c->tok_ent_on) {
+        HIPCHK(c, hipStreamSynchronize(c->st));
+        if (want) HIPCHK(c, hipMemset(c->d_tok_ent, 0xff, n * 4));   // nothing decoded under this switch yet
+        c->tok_ent_on = want;
+        c->tr_ent.clear();
+        drop_step_graphs(c);
+    }
+    return CW_OK;
+}
+int32_t cw_get_token_entropy(cw_ctx* c, float* out, int32_t nb) {
+    if (!c->tok_ent_on) return fail(c, CW_ERR_STATE, "token entropy is off (cw_set_token_entropy)");
+    if (!out || nb < 1 || nb > c->Bm) return fail(c, CW_ERR_INVALID, "get_token_entropy: nb=%d outside 1 .. %d", nb, c->Bm);
+    HIPCHK(c, hipStreamSynchronize(c->st));
+    HIPCHK(c, hipMemcpy(out, c->d_tok_ent, (size_t)nb * c->d.max_target_positions * 4, hipMemcpyDeviceToHost));
+    return CW_OK;
+}
+int32_t cw_get_transcribe_token_entropy(cw_ctx* c, float* out, int32_t B, int32_t cap) {
+    if (!c->tok_ent_on) return fail(c, CW_ERR_STATE, "token entropy is off (cw_set_token_entropy)");
+    if (!out || B < 1 || (size_t)B != c->tr_ent.size()) return fail(c, CW_ERR_STATE, "get_transcribe_token_entropy: B=%d but the last cw_transcribe had %d items", B, (int)c->tr_ent.size());
+    for (int i = 0; i < B; ++i) {
+        const int n = (int)c->tr_ent[i].size();
+        if (n > cap) return fail(c, CW_ERR_INVALID, "item %d holds %d tokens, capacity %d", i, n, cap);
+        memcpy(out + (size_t)i * cap, c->tr_ent[i].data(), (size_t)n * 4);
         for (int k = n; k < cap; ++k) out[(size_t)i * cap + k] = NAN;
     }
     return CW_OK;
@@ -2354,9 +2395,10 @@ int32_t cw_transcribe_prompted(cw_ctx* c, int32_t B, const int32_t* num_frames, 
     if (max_length <= n_prompt) return fail(c, CW_ERR_INVALID, "max_length %d leaves no room after %d decoder input tokens", max_length, n_prompt);
     std::vector<long> seek(B, 0);
     std::vector<std::vector<int>> out_tok(B);
-    std::vector<std::vector<float>> out_ts(B), out_lp(B), out_tl(B), out_am(B), out_as(B);
+    std::vector<std::vector<float>> out_ts(B), out_lp(B), out_tl(B), out_am(B), out_as(B), out_en(B);
     std::vector<std::vector<int>> out_ti(B);
     c->tr_lp.clear();
+    c->tr_ent.clear();
     c->tr_top_id.clear(); c->tr_top_lp.clear();
     c->tr_as_mass.clear(); c->tr_as_spread.clear();
     const int top_k = c->tok_lp_on ? c->top_k : 0;
@@ -2383,6 +2425,8 @@ int32_t cw_transcribe_prompted(cw_ctx* c, int32_t B, const int32_t* num_frames, 
         if (thr) CWCHK(c, cw_get_avg_logprobs(c, alp.data(), nb));
         std::vector<float> tlp;
         if (c->tok_lp_on) { tlp.resize((size_t)nb * TGT); CWCHK(c, cw_get_token_logprobs(c, tlp.data(), nb)); }
+        std::vector<float> ten;
+        if (c->tok_ent_on) { ten.resize((size_t)nb * TGT); CWCHK(c, cw_get_token_entropy(c, ten.data(), nb)); }
         std::vector<int> tti; std::vector<float> ttl;
         if (top_k > 0) {
             tti.resize((size_t)nb * TGT * top_k); ttl.resize(tti.size());
@@ -2421,6 +2465,7 @@ int32_t cw_transcribe_prompted(cw_ctx* c, int32_t B, const int32_t* num_frames, 
                 out_tok[i].push_back(s[k]);
                 out_ts[i].push_back(ts[(size_t)r * (L + 1) + n_prompt + k] + off32);
                 if (c->tok_lp_on) out_lp[i].push_back(tlp[(size_t)r * TGT + n_prompt + k]);
+                if (c->tok_ent_on) out_en[i].push_back(ten[(size_t)r * TGT + n_prompt + k]);
                 if (c->as_on) {                                                        // (rows of the cw_token_timestamps above)
                     out_am[i].push_back(c->as_mass[r][n_prompt + k]);
                     out_as[i].push_back(c->as_spread[r][n_prompt + k]);
@@ -2442,6 +2487,7 @@ int32_t cw_transcribe_prompted(cw_ctx* c, int32_t B, const int32_t* num_frames, 
         memcpy(token_ts + (size_t)i * cap, out_ts[i].data(), (size_t)n * 4);
     }
     if (c->tok_lp_on) c->tr_lp = std::move(out_lp);
+    if (c->tok_ent_on) c->tr_ent = std::move(out_en);
     if (top_k > 0) { c->tr_top_id = std::move(out_ti); c->tr_top_lp = std::move(out_tl); }
     if (c->as_on) { c->tr_as_mass = std::move(out_am); c->tr_as_spread = std::move(out_as); }
     if (n_passes) *n_passes = passes;
@@ -2758,6 +2804,12 @@ static int top_reserve(cw_ctx* c, size_t M, size_t parts) {
     return regrow(c, "score", c->sc_tparts, parts, {{(void**)&c->sc_tpart, parts * CW_TOP_LOGPROBS_MAX * sizeof(ScoreTopPart)}});
 }
 
+// what cw_set_score_entropy needs on top: the head's per-split centred sums and its [M] results
+static int ent_reserve(cw_ctx* c, size_t M, size_t parts) {
+    CWCHK(c, regrow(c, "score", c->sc_ent_rows, M, {{(void**)&c->sc_ent, M * 4}}));
+    return regrow(c, "score", c->sc_eparts, parts, {{(void**)&c->sc_epart, parts * 4}});
+}
+
 // the host copy cw_get_score_top_logprobs answers from: [rows][ids_stride][CW_TOP_LOGPROBS_MAX], -1 / NaN until a position is filled
 static void top_results_begin(cw_ctx* c, int rows, int ids_stride) {
     const size_t n = (size_t)rows * ids_stride * CW_TOP_LOGPROBS_MAX;
@@ -2857,6 +2909,14 @@ static int score_head_fetch(cw_ctx* c, int rows, int M, int ids_stride, const in
                 memcpy(&c->sc_top_lps[((size_t)r * ids_stride + k) * W], &al[(size_t)m * W], W * 4);
             }
     }
+    if (c->sc_ent_on) {                          // the entropies stay with the context too (cw_get_score_entropy)
+        std::vector<float> en((size_t)M);
+        HIPCHK(c, hipMemcpy(en.data(), c->sc_ent, en.size() * 4, hipMemcpyDeviceToHost));
+        c->sc_ents.assign((size_t)rows * ids_stride, std::numeric_limits<float>::quiet_NaN());
+        m = 0;
+        for (int r = 0; r < rows; ++r)
+            for (int k = n_init; k < n_ids[r]; ++k, ++m) c->sc_ents[(size_t)r * ids_stride + k] = en[m];
+    }
     return CW_OK;
 }
 
@@ -2887,6 +2947,7 @@ static int score_rows(cw_ctx* c, const char* who, int n_items, int rpi, const in
     c->pf_prefix = 0;
     const int Lmax = n_max - 1;
     c->sc_top_rows = 0;                          // cw_get_score_top_logprobs answers for a call that came to its end only
+    c->sc_ent_nrows = 0;                         // ... and so does cw_get_score_entropy
     if (c->score_prefill && prefill_capable(c)) {
         // one encoder pass per item; decoder row r reads the cross K/V cache of item r / rows_per_item
         std::vector<int> all(n_items), zeros(n_items, 0), full(n_items, CW_N_FRAMES);
@@ -2900,6 +2961,7 @@ static int score_rows(cw_ctx* c, const char* who, int n_items, int rpi, const in
         int M = 0;
         CWCHK(c, score_head_prepare(c, rows, Lmax, ids, ids_stride, n_ids, n_init, &M));     // (synchronises the stream)
         if (c->sc_top_k > 0) CWCHK(c, top_reserve(c, (size_t)M, (size_t)M * KD(c, cw_score_head_splits, M, c->d.vocab_size, nullptr)));
+        if (c->sc_ent_on) CWCHK(c, ent_reserve(c, (size_t)M, (size_t)M * KD(c, cw_score_head_splits, M, c->d.vocab_size, nullptr)));
         if (ca) {
             CWCHK(c, cut_reserve(c, (size_t)M, (size_t)M * KD(c, cw_score_head_splits, M, c->d.vocab_size, nullptr)));
             std::vector<int> first(rows, 0);     // the head's arrays hold row after row, n_ids - n_init entries each
@@ -2930,6 +2992,7 @@ static int score_rows(cw_ctx* c, const char* who, int n_items, int rpi, const in
             const size_t n = (size_t)c->Bm * TGT * CW_TOP_LOGPROBS_MAX * 4;
             CWCHK(c, dmalloc(c, &c->sc_step_alt_id, n)); CWCHK(c, dmalloc(c, &c->sc_step_alt_lp, n));
         }
+        if (c->sc_ent_on && !c->sc_step_ent) CWCHK(c, dmalloc(c, &c->sc_step_ent, (size_t)c->Bm * TGT * 4));
         if (ca) {
             if (!c->sc_step_stop) CWCHK(c, dmalloc(c, &c->sc_step_stop, (size_t)c->Bm * TGT * 4));
             CWCHK(c, cut_reserve(c, 0, 0));
@@ -2983,8 +3046,16 @@ static int score_rows(cw_ctx* c, const char* who, int n_items, int rpi, const in
                     memcpy(&c->sc_top_lps[((size_t)r * ids_stride + k) * W], &al[((size_t)r * TGT + k) * W], W * 4);
                 }
         }
+        if (c->sc_ent_on) {                      // the loop's [rows][TGT], indexed by position
+            std::vector<float> en((size_t)rows * TGT);
+            HIPCHK(c, hipMemcpy(en.data(), c->sc_step_ent, en.size() * 4, hipMemcpyDeviceToHost));
+            c->sc_ents.assign((size_t)rows * ids_stride, std::numeric_limits<float>::quiet_NaN());
+            for (int r = 0; r < rows; ++r)
+                for (int k = n_init; k < n_ids[r]; ++k) c->sc_ents[(size_t)r * ids_stride + k] = en[(size_t)r * TGT + k];
+        }
     }
     if (c->sc_top_k > 0) { c->sc_top_rows = rows; c->sc_top_stride = ids_stride; }
+    if (c->sc_ent_on) { c->sc_ent_nrows = rows; c->sc_ent_stride = ids_stride; }
     if (ca) {
         std::vector<int32_t> kept(rows);         // init tokens + the kept text + the slot cw_align_tokens gives the eos
         for (int b = 0; b < rows; ++b) {
@@ -3042,6 +3113,24 @@ int32_t cw_get_score_top_logprobs(cw_ctx* c, int32_t* ids_out, float* lp_out, in
         memcpy(ids_out + i * k, &c->sc_top_ids[i * CW_TOP_LOGPROBS_MAX], k * 4);
         memcpy(lp_out + i * k, &c->sc_top_lps[i * CW_TOP_LOGPROBS_MAX], k * 4);
     }
+    return CW_OK;
+}
+
+// ---- entropy of the teacher-forced positions (include/crisperwhisper.h) ----------------------------------------------------------
+int32_t cw_set_score_entropy(cw_ctx* c, int32_t on) {
+    c->sc_ent_on = on != 0;
+    c->sc_ent_nrows = 0;                         // what an earlier call stored is not handed out under a new setting
+    if (!c->sc_ent_on) c->sc_ents.clear();
+    return CW_OK;
+}
+
+int32_t cw_get_score_entropy(cw_ctx* c, float* out, int32_t rows, int32_t ids_stride) {
+    if (!c->sc_ent_on) return fail(c, CW_ERR_STATE, "score entropy is off (cw_set_score_entropy)");
+    if (!out || rows < 1 || ids_stride < 1) return fail(c, CW_ERR_INVALID, "get_score_entropy: bad arguments");
+    if (rows > c->sc_ent_nrows || ids_stride != c->sc_ent_stride)
+        return fail(c, CW_ERR_STATE, "get_score_entropy: asked %d rows of stride %d, the last scoring call stored %d of stride %d", rows,
+                    ids_stride, c->sc_ent_nrows, c->sc_ent_stride);
+    memcpy(out, c->sc_ents.data(), (size_t)rows * ids_stride * 4);
     return CW_OK;
 }
 

@@ -95,9 +95,9 @@ int32_t cw_test_prefill_gemm(cw_ctx* c, int32_t mode, int32_t M, int32_t N, int3
 static int test_score_head(cw_ctx* c, int32_t M, int32_t D, int32_t V, const float* x, const float* ln_g, const float* ln_b,
                            const float* embed, const int32_t* targets, float* logprob, int32_t* top_id, float* top_logprob,
                            int eos, int timestamp_begin, float* stop_logprob, int k = 0, int32_t* alt_id = nullptr,
-                           float* alt_logprob = nullptr, float* logits_out = nullptr) {
+                           float* alt_logprob = nullptr, float* logits_out = nullptr, float* entropy = nullptr) {
     if (!c->bf16) return fail(c, CW_ERR_INVALID, "test_score_head: 16-bit engines only");
-    if (k < 0 || k > CW_TOP_LOGPROBS_MAX || (k > 0 && (!alt_id || !alt_logprob)) || (k == 0 && logits_out))
+    if (k < 0 || k > CW_TOP_LOGPROBS_MAX || (k > 0 && (!alt_id || !alt_logprob)) || (k == 0 && !entropy && logits_out))
         return fail(c, CW_ERR_INVALID, "test_score_head: k=%d outside 1 .. %d or a null alt_id / alt_logprob", k, CW_TOP_LOGPROBS_MAX);
     if (M < 1 || M > (1 << 16) || D < 32 || D % 32 || D > 8192 || V < 1 || V > (1 << 20) || !x || !ln_g || !ln_b || !embed || !targets ||
         !logprob || !top_id || !top_logprob) return fail(c, CW_ERR_INVALID, "test_score_head: bad arguments");
@@ -118,8 +118,10 @@ static int test_score_head(cw_ctx* c, int32_t M, int32_t D, int32_t V, const flo
     const size_t tp_row = (size_t)ns * CW_TOP_LOGPROBS_MAX * sizeof(ScoreTopPart), alt_row = (size_t)CW_TOP_LOGPROBS_MAX * 4;
     if (k > 0) {
         get(&o.tpart, (size_t)(M + 8) * tp_row); get(&o.alt_id, (size_t)(M + 8) * alt_row); get(&o.alt_logprob, (size_t)(M + 8) * alt_row);
-        if (logits_out) get(&dlog, (size_t)M * V * 4);
     }
+    if (logits_out) get(&dlog, (size_t)M * V * 4);
+    // ENT form: the per-split centred sums and entropy [M], with 8 guard rows each as above
+    if (entropy) { get(&o.epart, (size_t)(M + 8) * ns * 4); get(&o.entropy, (size_t)(M + 8) * 4); }
     if (stop_logprob) { get(&o.spart, (size_t)M * ns * sizeof(ScoreStopPart)); get(&o.stop_logprob, (size_t)M * 4); }
     get(&dx, (size_t)M * D * 4); get(&dg, (size_t)D * 4); get(&db, (size_t)D * 4); get(&o.logprob, (size_t)M * 4);
     get(&o.top_logprob, (size_t)M * 4); get(&dt, (size_t)M * 4); get(&o.top_id, (size_t)M * 4); get(&dA, (size_t)M * D * e);
@@ -127,6 +129,8 @@ static int test_score_head(cw_ctx* c, int32_t M, int32_t D, int32_t V, const flo
     if (!ok) return fail(c, CW_ERR_NOMEM, "test_score_head: hipMalloc failed");
     if (k > 0 && (hipMemset(o.tpart, 0x5a, (size_t)(M + 8) * tp_row) != hipSuccess || hipMemset(o.alt_id, 0x5a, (size_t)(M + 8) * alt_row) != hipSuccess ||
                   hipMemset(o.alt_logprob, 0x5a, (size_t)(M + 8) * alt_row) != hipSuccess)) return fail(c, CW_ERR_HIP, "test_score_head: memset");
+    if (entropy && (hipMemset(o.epart, 0x5a, (size_t)(M + 8) * ns * 4) != hipSuccess || hipMemset(o.entropy, 0x5a, (size_t)(M + 8) * 4) != hipSuccess))
+        return fail(c, CW_ERR_HIP, "test_score_head: memset");
     if (hipMemcpy(dx, x, (size_t)M * D * 4, hipMemcpyHostToDevice) != hipSuccess ||
         hipMemcpy(dg, ln_g, (size_t)D * 4, hipMemcpyHostToDevice) != hipSuccess ||
         hipMemcpy(db, ln_b, (size_t)D * 4, hipMemcpyHostToDevice) != hipSuccess ||
@@ -148,9 +152,20 @@ static int test_score_head(cw_ctx* c, int32_t M, int32_t D, int32_t V, const flo
             for (unsigned char b : *gv)
                 if (b != 0x5a) return fail(c, CW_ERR_STATE, "test_score_head: a row behind M = %d was written", M);
         if (hipMemcpy(alt_id, o.alt_id, (size_t)M * alt_row, hipMemcpyDeviceToHost) != hipSuccess ||
-            hipMemcpy(alt_logprob, o.alt_logprob, (size_t)M * alt_row, hipMemcpyDeviceToHost) != hipSuccess ||
-            (logits_out && hipMemcpy(logits_out, dlog, (size_t)M * V * 4, hipMemcpyDeviceToHost) != hipSuccess))
+            hipMemcpy(alt_logprob, o.alt_logprob, (size_t)M * alt_row, hipMemcpyDeviceToHost) != hipSuccess)
             return fail(c, CW_ERR_HIP, "test_score_head: copy");
+    }
+    if (logits_out && hipMemcpy(logits_out, dlog, (size_t)M * V * 4, hipMemcpyDeviceToHost) != hipSuccess)
+        return fail(c, CW_ERR_HIP, "test_score_head: copy");
+    if (entropy) {
+        std::vector<unsigned char> gp((size_t)8 * ns * 4), ge(8 * 4);
+        if (hipMemcpy(gp.data(), (char*)o.epart + (size_t)M * ns * 4, gp.size(), hipMemcpyDeviceToHost) != hipSuccess ||
+            hipMemcpy(ge.data(), (char*)o.entropy + (size_t)M * 4, ge.size(), hipMemcpyDeviceToHost) != hipSuccess ||
+            hipMemcpy(entropy, o.entropy, (size_t)M * 4, hipMemcpyDeviceToHost) != hipSuccess)
+            return fail(c, CW_ERR_HIP, "test_score_head: copy");
+        for (const auto* gv : {&gp, &ge})
+            for (unsigned char b : *gv)
+                if (b != 0x5a) return fail(c, CW_ERR_STATE, "test_score_head: an entropy row behind M = %d was written", M);
     }
     if ((stop_logprob && hipMemcpy(stop_logprob, o.stop_logprob, (size_t)M * 4, hipMemcpyDeviceToHost) != hipSuccess) ||
         hipMemcpy(logprob, o.logprob, (size_t)M * 4, hipMemcpyDeviceToHost) != hipSuccess ||
@@ -196,15 +211,51 @@ int32_t cw_test_score_head_stop_top(cw_ctx* c, int32_t M, int32_t D, int32_t V, 
                            alt_id, alt_logprob, logits_out);
 }
 
+// cw_test_score_head_entropy: the ENT forms of the head, alone (stop_logprob NULL, k = 0) or joined with STOP (stop_logprob non-null)
+// and / or TOPK (k > 0; alt_id / alt_logprob as above).  entropy [M]; logits_out as above.
+int32_t cw_test_score_head_entropy(cw_ctx* c, int32_t M, int32_t D, int32_t V, const float* x, const float* ln_g, const float* ln_b,
+                                   const float* embed, const int32_t* targets, int32_t eos, int32_t timestamp_begin, int32_t k,
+                                   float* logprob, int32_t* top_id, float* top_logprob, float* stop_logprob, int32_t* alt_id,
+                                   float* alt_logprob, float* entropy, float* logits_out) {
+    if (!entropy) return fail(c, CW_ERR_INVALID, "test_score_head_entropy: null entropy");
+    if (stop_logprob && (eos < 0 || eos >= V || timestamp_begin < 0 || timestamp_begin > V))
+        return fail(c, CW_ERR_INVALID, "test_score_head_entropy: eos=%d inside 0 .. %d and timestamp_begin=%d inside 0 .. %d are needed", eos,
+                    V - 1, timestamp_begin, V);
+    return test_score_head(c, M, D, V, x, ln_g, ln_b, embed, targets, logprob, top_id, top_logprob, stop_logprob ? eos : 0,
+                           stop_logprob ? timestamp_begin : 0, stop_logprob, k, alt_id, alt_logprob, logits_out, entropy);
+}
+
+// the loop path's row kernel on caller-supplied f32 logits [rows][ldv], any engine: k = 0 without the TOPK form, entropy non-null with
+// the ENT form
+static int test_score_rows(cw_ctx* c, const char* who, int32_t rows, int32_t V, int32_t ldv, const float* logits, const int32_t* targets,
+                           int32_t k, int32_t eos, int32_t timestamp_begin, float* logprob, int32_t* top_id, float* top_logprob,
+                           float* stop_logprob, int32_t* alt_id, float* alt_logprob, float* entropy);
+
 // cw_test_score_rows_top: the loop path's row kernel (TOPK form) on caller-supplied f32 logits [rows][ldv], any engine.  targets
 // [rows] (negative: none).  stop_logprob non-null: the STOP form over S = {eos} + {n >= timestamp_begin}.  Outputs [rows] and
 // alt_id / alt_logprob [rows][CW_TOP_LOGPROBS_MAX].
 int32_t cw_test_score_rows_top(cw_ctx* c, int32_t rows, int32_t V, int32_t ldv, const float* logits, const int32_t* targets, int32_t k,
                                int32_t eos, int32_t timestamp_begin, float* logprob, int32_t* top_id, float* top_logprob,
                                float* stop_logprob, int32_t* alt_id, float* alt_logprob) {
-    if (rows < 1 || rows > (1 << 16) || V < 1 || V > (1 << 20) || ldv < V || ldv > (1 << 21) || k < 1 || k > CW_TOP_LOGPROBS_MAX || !logits ||
-        !targets || !logprob || !top_id || !top_logprob || !alt_id || !alt_logprob || (stop_logprob && (eos < 0 || timestamp_begin < 0)))
-        return fail(c, CW_ERR_INVALID, "test_score_rows_top: bad arguments");
+    if (k < 1) return fail(c, CW_ERR_INVALID, "test_score_rows_top: bad arguments");
+    return test_score_rows(c, "test_score_rows_top", rows, V, ldv, logits, targets, k, eos, timestamp_begin, logprob, top_id, top_logprob,
+                           stop_logprob, alt_id, alt_logprob, nullptr);
+}
+// cw_test_score_rows_entropy: the same with the ENT form on: entropy [rows]; k = 0 .. CW_TOP_LOGPROBS_MAX (0: no alternatives, alt_id /
+// alt_logprob may be NULL), stop_logprob as above.
+int32_t cw_test_score_rows_entropy(cw_ctx* c, int32_t rows, int32_t V, int32_t ldv, const float* logits, const int32_t* targets, int32_t k,
+                                   int32_t eos, int32_t timestamp_begin, float* logprob, int32_t* top_id, float* top_logprob,
+                                   float* stop_logprob, int32_t* alt_id, float* alt_logprob, float* entropy) {
+    if (!entropy) return fail(c, CW_ERR_INVALID, "test_score_rows_entropy: null entropy");
+    return test_score_rows(c, "test_score_rows_entropy", rows, V, ldv, logits, targets, k, eos, timestamp_begin, logprob, top_id, top_logprob,
+                           stop_logprob, alt_id, alt_logprob, entropy);
+}
+static int test_score_rows(cw_ctx* c, const char* who, int32_t rows, int32_t V, int32_t ldv, const float* logits, const int32_t* targets,
+                           int32_t k, int32_t eos, int32_t timestamp_begin, float* logprob, int32_t* top_id, float* top_logprob,
+                           float* stop_logprob, int32_t* alt_id, float* alt_logprob, float* entropy) {
+    if (rows < 1 || rows > (1 << 16) || V < 1 || V > (1 << 20) || ldv < V || ldv > (1 << 21) || k < 0 || k > CW_TOP_LOGPROBS_MAX || !logits ||
+        !targets || !logprob || !top_id || !top_logprob || (k > 0 && (!alt_id || !alt_logprob)) || (stop_logprob && (eos < 0 || timestamp_begin < 0)))
+        return fail(c, CW_ERR_INVALID, "%s: bad arguments", who);
     const size_t W = CW_TOP_LOGPROBS_MAX;
     float* dl = nullptr;
     int* dt = nullptr;
@@ -214,8 +265,9 @@ int32_t cw_test_score_rows_top(cw_ctx* c, int32_t rows, int32_t V, int32_t ldv, 
     if (mem.get(&dl, (size_t)rows * ldv * 4) != hipSuccess || mem.get(&dt, (size_t)rows * 4) != hipSuccess || mem.get(&o.logprob, (size_t)rows * 4) != hipSuccess ||
         mem.get(&o.top_id, (size_t)rows * 4) != hipSuccess || mem.get(&o.top_logprob, (size_t)rows * 4) != hipSuccess ||
         (stop_logprob && mem.get(&o.stop_logprob, (size_t)rows * 4) != hipSuccess) ||
-        mem.get(&o.alt_id, (size_t)rows * W * 4) != hipSuccess || mem.get(&o.alt_logprob, (size_t)rows * W * 4) != hipSuccess)
-        return fail(c, CW_ERR_NOMEM, "test_score_rows_top: hipMalloc failed");
+        (entropy && mem.get(&o.entropy, (size_t)rows * 4) != hipSuccess) ||
+        (k > 0 && (mem.get(&o.alt_id, (size_t)rows * W * 4) != hipSuccess || mem.get(&o.alt_logprob, (size_t)rows * W * 4) != hipSuccess)))
+        return fail(c, CW_ERR_NOMEM, "%s: hipMalloc failed", who);
     HIPCHK(c, hipMemcpy(dl, logits, (size_t)rows * ldv * 4, hipMemcpyHostToDevice));
     HIPCHK(c, hipMemcpy(dt, targets, (size_t)rows * 4, hipMemcpyHostToDevice));
     CWCHK(c, KD(c, cw_launch_score_rows, dl, ldv, V, dt, 1, 0, rows, o, c->st));
@@ -225,8 +277,11 @@ int32_t cw_test_score_rows_top(cw_ctx* c, int32_t rows, int32_t V, int32_t ldv, 
     HIPCHK(c, hipMemcpy(top_id, o.top_id, (size_t)rows * 4, hipMemcpyDeviceToHost));
     HIPCHK(c, hipMemcpy(top_logprob, o.top_logprob, (size_t)rows * 4, hipMemcpyDeviceToHost));
     if (stop_logprob) HIPCHK(c, hipMemcpy(stop_logprob, o.stop_logprob, (size_t)rows * 4, hipMemcpyDeviceToHost));
-    HIPCHK(c, hipMemcpy(alt_id, o.alt_id, (size_t)rows * W * 4, hipMemcpyDeviceToHost));
-    HIPCHK(c, hipMemcpy(alt_logprob, o.alt_logprob, (size_t)rows * W * 4, hipMemcpyDeviceToHost));
+    if (entropy) HIPCHK(c, hipMemcpy(entropy, o.entropy, (size_t)rows * 4, hipMemcpyDeviceToHost));
+    if (k > 0) {
+        HIPCHK(c, hipMemcpy(alt_id, o.alt_id, (size_t)rows * W * 4, hipMemcpyDeviceToHost));
+        HIPCHK(c, hipMemcpy(alt_logprob, o.alt_logprob, (size_t)rows * W * 4, hipMemcpyDeviceToHost));
+    }
     return CW_OK;
 }
 
@@ -317,10 +372,18 @@ int32_t cw_time_score_head(cw_ctx* c, int32_t M, int32_t unfused, int32_t iters,
 
 // cw_time_score_head_top: cw_time_score_head's fused forms (stop = 0 / 1) with k alternatives per row; k = 0: the plain forms,
 // timed by this same loop
+static int time_score_head_forms(cw_ctx* c, const char* who, int32_t M, int32_t k, int32_t stop, bool ent, int32_t iters, float* avg_ms);
 int32_t cw_time_score_head_top(cw_ctx* c, int32_t M, int32_t k, int32_t stop, int32_t iters, float* avg_ms) {
-    if (!c->bf16 || !c->embed_pk) return fail(c, CW_ERR_INVALID, "time_score_head_top: 16-bit engines with packed weights only");
+    return time_score_head_forms(c, "time_score_head_top", M, k, stop, false, iters, avg_ms);
+}
+// cw_time_score_head_entropy: the same loop with the ENT form on (entropy [M] and its per-split record array beside the rest)
+int32_t cw_time_score_head_entropy(cw_ctx* c, int32_t M, int32_t k, int32_t stop, int32_t iters, float* avg_ms) {
+    return time_score_head_forms(c, "time_score_head_entropy", M, k, stop, true, iters, avg_ms);
+}
+static int time_score_head_forms(cw_ctx* c, const char* who, int32_t M, int32_t k, int32_t stop, bool ent, int32_t iters, float* avg_ms) {
+    if (!c->bf16 || !c->embed_pk) return fail(c, CW_ERR_INVALID, "%s: 16-bit engines with packed weights only", who);
     if (M < 1 || M > (1 << 15) || k < 0 || k > CW_TOP_LOGPROBS_MAX || iters < 1 || !avg_ms)
-        return fail(c, CW_ERR_INVALID, "time_score_head_top: bad arguments");
+        return fail(c, CW_ERR_INVALID, "%s: bad arguments", who);
     if (stop && !c->gen_set) return fail(c, CW_ERR_STATE, "cw_set_generation not called");
     CWCHK(c, cw_check_weights(c));
     const int D = c->d.d_model, V = c->d.vocab_size;
@@ -341,20 +404,21 @@ int32_t cw_time_score_head_top(cw_ctx* c, int32_t M, int32_t k, int32_t stop, in
         mem.get(&dt, (size_t)M * 4) != hipSuccess || mem.get(&o.top_id, (size_t)M * 4) != hipSuccess || mem.get(&dA, (size_t)M * D * 2) != hipSuccess ||
         mem.get(&o.part, (size_t)M * ns * sizeof(ScorePart)) != hipSuccess || mem.get(&o.spart, (size_t)M * ns * sizeof(ScoreStopPart)) != hipSuccess ||
         (stop && mem.get(&o.stop_logprob, (size_t)M * 4) != hipSuccess) || mem.get(&o.tpart, (size_t)M * ns * W * sizeof(ScoreTopPart)) != hipSuccess ||
-        mem.get(&o.alt_id, (size_t)M * W * 4) != hipSuccess || mem.get(&o.alt_logprob, (size_t)M * W * 4) != hipSuccess)
-        return fail(c, CW_ERR_NOMEM, "time_score_head_top: hipMalloc failed");
+        mem.get(&o.alt_id, (size_t)M * W * 4) != hipSuccess || mem.get(&o.alt_logprob, (size_t)M * W * 4) != hipSuccess ||
+        (ent && (mem.get(&o.epart, (size_t)M * ns * 4) != hipSuccess || mem.get(&o.entropy, (size_t)M * 4) != hipSuccess)))
+        return fail(c, CW_ERR_NOMEM, "%s: hipMalloc failed", who);
     HIPCHK(c, hipMemcpy(dx, x.data(), x.size() * 4, hipMemcpyHostToDevice));
     HIPCHK(c, hipMemcpy(dt, tg.data(), (size_t)M * 4, hipMemcpyHostToDevice));
     int r = CW_OK;
     for (int it = 0; it <= iters && r == CW_OK; ++it) {
-        if (it == 1 && hipEventRecord(c->ev0, c->st) != hipSuccess) r = fail(c, CW_ERR_HIP, "time_score_head_top: event");
+        if (it == 1 && hipEventRecord(c->ev0, c->st) != hipSuccess) r = fail(c, CW_ERR_HIP, "%s: event", who);
         if (r == CW_OK) r = KD(c, cw_launch_score_ln, dx, nullptr, c->dec_ln_g, c->dec_ln_b, dA, M, D, c->st);
         if (r == CW_OK) r = KD(c, cw_launch_score_head, dA, c->embed_pk, dt, M, V, D, o, c->st);
     }
     if (r == CW_OK) {
         float ms = 0.f;
         if (hipEventRecord(c->ev1, c->st) != hipSuccess || hipEventSynchronize(c->ev1) != hipSuccess ||
-            hipEventElapsedTime(&ms, c->ev0, c->ev1) != hipSuccess) r = fail(c, CW_ERR_HIP, "time_score_head_top: event");
+            hipEventElapsedTime(&ms, c->ev0, c->ev1) != hipSuccess) r = fail(c, CW_ERR_HIP, "%s: event", who);
         else *avg_ms = ms / (float)iters;
     }
     hipStreamSynchronize(c->st);
@@ -1504,7 +1568,7 @@ int32_t cw_test_decode_state(cw_ctx* c, int32_t what, int32_t layer, int32_t row
 // token the kernel picks for index t.  Differential test against TF/generation/logits_process.py:203-260, 1816-2047.
 static int test_sample(cw_ctx* c, int32_t nb, const float* logits, const int32_t* ids, int32_t t, int32_t n_prompt,
                        int32_t min_new_tokens, int32_t max_length, int32_t* choice_out, const int32_t* forced_tok = nullptr,
-                       float* lp_out = nullptr, int32_t* top_id_out = nullptr, float* top_lp_out = nullptr);
+                       float* lp_out = nullptr, int32_t* top_id_out = nullptr, float* top_lp_out = nullptr, float* ent_out = nullptr);
 int32_t cw_test_sample(cw_ctx* c, int32_t nb, const float* logits, const int32_t* ids, int32_t t, int32_t n_prompt,
                        int32_t min_new_tokens, int32_t max_length, int32_t* choice_out) {
     return test_sample(c, nb, logits, ids, t, n_prompt, min_new_tokens, max_length, choice_out);
@@ -1579,6 +1643,40 @@ int32_t cw_test_sample_top_logprobs(cw_ctx* c, int32_t nb, const float* logits, 
     if (!was_on) CWCHK(c, cw_set_token_logprobs(c, 0));
     return r;
 }
+// ... and with the token entropy on for this call (cw_set_token_entropy): ent_out [nb] = what the kernels stored at [b][t].  k = 0 ..
+// CW_TOP_LOGPROBS_MAX: the alternatives ride along (top_id_out / top_lp_out [nb][k], NULL when k = 0), so that every instantiation
+// the entropy joins can be driven.  The pad columns of the logits hold +75 during the call.  The context's settings are restored.
+int32_t cw_test_sample_entropy(cw_ctx* c, int32_t nb, const float* logits, const int32_t* ids, int32_t t, int32_t n_prompt,
+                               int32_t min_new_tokens, int32_t max_length, float temperature, uint64_t seed,
+                               const uint64_t* row_streams, const int32_t* forced_tok, int32_t k, int32_t* choice_out,
+                               float* lp_out, float* ent_out, int32_t* top_id_out, float* top_lp_out) {
+    if (!logits || !ids || !choice_out || !lp_out || !ent_out) return fail(c, CW_ERR_INVALID, "test_sample_entropy: null argument");
+    if (k < 0 || k > CW_TOP_LOGPROBS_MAX || (k > 0 && (!top_id_out || !top_lp_out)))
+        return fail(c, CW_ERR_INVALID, "test_sample_entropy: k=%d outside 0 .. %d, or no room for the alternatives", k, CW_TOP_LOGPROBS_MAX);
+    if (nb < 1 || nb > c->Bm || nb > 64) return fail(c, CW_ERR_INVALID, "test_sample_entropy: nb=%d outside 1 .. %d", nb, c->Bm < 64 ? c->Bm : 64);
+    if (max_length <= n_prompt || max_length > c->d.max_target_positions || min_new_tokens < 0)
+        return fail(c, CW_ERR_INVALID, "test_sample_entropy: max_length=%d / min_new_tokens=%d out of range", max_length, min_new_tokens);
+    if (temperature > 0.f && !row_streams) return fail(c, CW_ERR_INVALID, "test_sample_entropy: a positive temperature needs row_streams");
+    if (forced_tok)
+        for (int b = 0; b < nb; ++b)
+            if (forced_tok[b] >= c->d.vocab_size) return fail(c, CW_ERR_INVALID, "test_sample_entropy: forced token %d out of range", forced_tok[b]);
+    const bool was_on = c->tok_lp_on, was_ent = c->tok_ent_on;
+    const int was_k = c->top_k;
+    CWCHK(c, cw_set_token_logprobs(c, 1));
+    CWCHK(c, cw_set_top_logprobs(c, k));
+    CWCHK(c, cw_set_token_entropy(c, 1));
+    const std::vector<unsigned int> keep = c->samp_host;
+    CWCHK(c, write_sampling(c, temperature, seed, row_streams, nb, "test_sample_entropy"));
+    const int r = test_sample(c, nb, logits, ids, t, n_prompt, min_new_tokens, max_length, choice_out, forced_tok, lp_out,
+                              k > 0 ? top_id_out : nullptr, k > 0 ? top_lp_out : nullptr, ent_out);
+    HIPCHK(c, hipStreamSynchronize(c->st));
+    HIPCHK(c, hipMemcpy(c->d_samp, keep.data(), keep.size() * 4, hipMemcpyHostToDevice));
+    c->samp_host = keep;
+    CWCHK(c, cw_set_token_entropy(c, was_ent ? 1 : 0));
+    CWCHK(c, cw_set_top_logprobs(c, was_on ? was_k : 0));
+    if (!was_on) CWCHK(c, cw_set_token_logprobs(c, 0));
+    return r;
+}
 // ... and with a sequence_bias table for this call only; proc_lp_out [nb] = what the step added to the processed-score sum.
 int32_t cw_test_sample_biased(cw_ctx* c, int32_t nb, const float* logits, const int32_t* ids, int32_t t, int32_t n_prompt,
                               int32_t min_new_tokens, int32_t max_length, float temperature, uint64_t seed,
@@ -1610,7 +1708,7 @@ int32_t cw_test_sample_biased(cw_ctx* c, int32_t nb, const float* logits, const 
 }
 static int test_sample(cw_ctx* c, int32_t nb, const float* logits, const int32_t* ids, int32_t t, int32_t n_prompt,
                        int32_t min_new_tokens, int32_t max_length, int32_t* choice_out, const int32_t* forced_tok, float* lp_out,
-                       int32_t* top_id_out, float* top_lp_out) {
+                       int32_t* top_id_out, float* top_lp_out, float* ent_out) {
     const int V = c->d.vocab_size, TGT = c->d.max_target_positions;
     if (!c->gen_set) return fail(c, CW_ERR_STATE, "cw_set_generation not called");
     if (nb < 1 || nb > c->Bm || t < n_prompt || t < 1 || t >= TGT || n_prompt < 1) return fail(c, CW_ERR_INVALID, "test_sample: bad args");
@@ -1634,6 +1732,7 @@ static int test_sample(cw_ctx* c, int32_t nb, const float* logits, const int32_t
         HIPCHK(c, hipMemcpy(c->d_forced, fr.data(), fr.size() * 4, hipMemcpyHostToDevice));
     }
     if (lp_out) HIPCHK(c, hipMemset(c->d_tok_lp, 0xff, (size_t)nb * TGT * 4));
+    if (ent_out) HIPCHK(c, hipMemset(c->d_tok_ent, 0xff, (size_t)nb * TGT * 4));
     if (top_id_out) {
         HIPCHK(c, hipMemset(c->d_top_id, 0xff, (size_t)nb * TGT * CW_TOP_LOGPROBS_MAX * 4));
         HIPCHK(c, hipMemset(c->d_top_lp, 0xff, (size_t)nb * TGT * CW_TOP_LOGPROBS_MAX * 4));
@@ -1642,13 +1741,14 @@ static int test_sample(cw_ctx* c, int32_t nb, const float* logits, const int32_t
     HIPCHK(c, hipMemcpy(c->d_cfg, cfg, sizeof(cfg), hipMemcpyHostToDevice));
     HIPCHK(c, hipMemcpy2D(c->dlogits, (size_t)c->Vpad * 4, logits, (size_t)V * 4, (size_t)V * 4, nb, hipMemcpyHostToDevice));
     const int n_padcol = c->Vpad - V;
-    if (top_id_out && n_padcol > 0) {                 // the pad columns hold +75 for this call: they must never count
+    const bool hot_pad = (top_id_out || ent_out) && n_padcol > 0;
+    if (hot_pad) {                                    // the pad columns hold +75 for this call: they must never count
         const std::vector<float> hot((size_t)nb * n_padcol, 75.0f);
         HIPCHK(c, hipMemcpy2D(c->dlogits + V, (size_t)c->Vpad * 4, hot.data(), (size_t)n_padcol * 4, (size_t)n_padcol * 4, nb, hipMemcpyHostToDevice));
     }
     CWCHK(c, launch_sample(c, nb));
     HIPCHK(c, hipStreamSynchronize(c->st));
-    if (top_id_out && n_padcol > 0) HIPCHK(c, hipMemset2D(c->dlogits + V, (size_t)c->Vpad * 4, 0, (size_t)n_padcol * 4, nb));
+    if (hot_pad) HIPCHK(c, hipMemset2D(c->dlogits + V, (size_t)c->Vpad * 4, 0, (size_t)n_padcol * 4, nb));
     std::vector<int> am((size_t)nb * TGT);
     HIPCHK(c, hipMemcpy(am.data(), c->d_argmax, am.size() * 4, hipMemcpyDeviceToHost));
     for (int b = 0; b < nb; ++b) choice_out[b] = am[(size_t)b * TGT + t];
@@ -1656,6 +1756,11 @@ static int test_sample(cw_ctx* c, int32_t nb, const float* logits, const int32_t
         std::vector<float> lp((size_t)nb * TGT);
         HIPCHK(c, hipMemcpy(lp.data(), c->d_tok_lp, lp.size() * 4, hipMemcpyDeviceToHost));
         for (int b = 0; b < nb; ++b) lp_out[b] = lp[(size_t)b * TGT + t];
+    }
+    if (ent_out) {
+        std::vector<float> en((size_t)nb * TGT);
+        HIPCHK(c, hipMemcpy(en.data(), c->d_tok_ent, en.size() * 4, hipMemcpyDeviceToHost));
+        for (int b = 0; b < nb; ++b) ent_out[b] = en[(size_t)b * TGT + t];
     }
     if (top_id_out) {
         const int k = c->top_k;

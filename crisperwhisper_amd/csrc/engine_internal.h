@@ -148,6 +148,11 @@ struct cw_ctx {
     void* d_top_part = nullptr;                               // [Bm][16][CW_TOP_LOGPROBS_MAX] (value, id) pairs of the sampler's stage 1
     std::vector<std::vector<int>> tr_top_id;                  // ... of the last cw_transcribe: top_k entries per token of every item
     std::vector<std::vector<float>> tr_top_lp;
+    // predictive entropy of every step's raw distribution (cw_set_token_entropy; needs tok_lp_on)
+    bool tok_ent_on = false;
+    float* d_tok_ent = nullptr;                               // [Bm][max_target], NaN where d_tok_lp is
+    float* d_ent_part = nullptr;                              // [Bm][16] centred sums of the sampler's stage 1
+    std::vector<std::vector<float>> tr_ent;                   // ... of the last cw_transcribe, per item, aligned with its tokens
     // sequence_bias (cw_set_sequence_bias): the device table in the layout of kernels.h, its host copy and entry count (0: off)
     int* d_seq_bias = nullptr;
     std::vector<int> sb_host;
@@ -253,6 +258,14 @@ struct cw_ctx {
     std::vector<int32_t> sc_top_ids;
     std::vector<float> sc_top_lps;
     int sc_top_rows = 0, sc_top_stride = 0;
+    // cw_set_score_entropy: the ENT forms of the head and of the loop's row kernel.  sc_epart: the head's per-split centred sums,
+    // sc_ent: [M] of the head, sc_step_ent: [Bm][TGT] of the loop; all allocated on first use.  sc_ents: the last scoring call's
+    // entropies [sc_ent_nrows][sc_ent_stride], NaN where nothing was scored
+    bool sc_ent_on = false;
+    size_t sc_eparts = 0, sc_ent_rows = 0;
+    float *sc_epart = nullptr, *sc_ent = nullptr, *sc_step_ent = nullptr;
+    std::vector<float> sc_ents;
+    int sc_ent_nrows = 0, sc_ent_stride = 0;
     int stage_kind[CW_MAX_DEC_STAGES] = {};
     int stage_launches[CW_MAX_DEC_STAGES] = {};   // kernel launches behind each stage (2 where gemv_prep_kernel precedes gemv_mt_kernel)
     float stage_ms[CW_N_STAGES] = {};

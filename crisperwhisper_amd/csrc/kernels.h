@@ -61,6 +61,11 @@ struct SampleParams {
     // optional (null: off): sequence_bias, the table of include/crisperwhisper.h: cw_set_sequence_bias in the layout below.  The
     // kernels add the row's float32 bias to every logit they consume; tok_lp / top_lp stay raw.
     const int* seq_bias;       // [SB_WORDS]
+    // optional (null: off; needs tok_lp): predictive entropy of the raw distribution, H = log S - Zc / S in nats with
+    // S = sum exp(x - m), Zc = sum exp(x - m) (x - m) over v < V, x > -inf, stored at [b][t] where tok_lp is stored
+    // (include/crisperwhisper.h: cw_set_token_entropy)
+    float* tok_ent;            // [B][ids_stride]
+    float* ent_part;           // [B][SAMPLE_NS] Zc of every slice, centred on the slice maximum, written by stage 1
 };
 // Device table of cw_set_sequence_bias (32-bit words).  The host orders the entries by their LAST token (stable: for one last token
 // the length-1 entry first, then the longer ones in the caller's order -- the summation order of SequenceBiasLogitsProcessor), so
@@ -412,16 +417,20 @@ struct ScoreTopPart {
 };
 // what cw_launch_score_rows writes for every row: logprob / top_id / top_logprob always, and the optional forms' outputs.
 // stop_logprob non-null: the STOP form, over S = {eos} + {n >= ts_begin}.  k != 0: the TOPK form, k = 1 .. CW_TOP_LOGPROBS_MAX
-// alternatives per row in alt_id / alt_logprob [..][CW_TOP_LOGPROBS_MAX]
+// alternatives per row in alt_id / alt_logprob [..][CW_TOP_LOGPROBS_MAX].  entropy non-null: the ENT form, the predictive entropy of
+// the row's distribution (cw_set_score_entropy), indexed as logprob
 struct ScoreRowsOut {
     float* logprob; int* top_id; float* top_logprob;
     float* stop_logprob; int eos, ts_begin;
     int k; int* alt_id; float* alt_logprob;
+    float* entropy;
 };
 // ... and cw_launch_score_head, with its per-split records: cw_score_head_splits(M, V) per row in part and (STOP) spart, times
-// CW_TOP_LOGPROBS_MAX in (TOPK) tpart
+// CW_TOP_LOGPROBS_MAX in (TOPK) tpart; (ENT) epart: per row and split one float, sum exp(logit - mx) (logit - mx) over the split's
+// columns about the mx of its ScorePart (NaN: the split met a NaN logit)
 struct ScoreHeadOut : ScoreRowsOut {
     ScorePart* part; ScoreStopPart* spart; ScoreTopPart* tpart;
+    float* epart;
 };
 
 #define CW_DTYPE_KERNEL_DECLS \

@@ -18,6 +18,11 @@
 // value descending, id ascending on an exact tie, over the columns < V with a logit > -inf -- as alt_id and alt_logprob = logit -
 // logsumexp.  The head keeps a sorted list per row and split in LDS and writes it to its own record array (ScoreTopPart), the
 // combine kernel merges the splits' lists, the row kernel runs k selection rounds; the logits are still never stored.
+// ENT forms (cw_set_score_entropy): besides the above, entropy = log S - Zc / S with S = sum exp(logit - mx), Zc = sum exp(logit - mx)
+// (logit - mx) over the columns < V with a logit > -inf.  Wherever a (mx, S, Zc) partial moves to a new centre M it becomes
+// (M, S e^(mx - M), (Zc + S (mx - M)) e^(mx - M)): in a lane when its maximum moves, between the 16 lanes of a row, between the
+// splits.  Zc travels in its own record array (one float per row and split); the other forms write what they wrote.  A NaN logit,
+// which the (maximum, sum) pair steps over, makes the row's entropy NaN.
 #include <hip/hip_runtime.h>
 #include "kernels.h"
 
@@ -43,6 +48,11 @@ __global__ __launch_bounds__(256) void score_ln_kernel(const float* __restrict__
 }
 
 __device__ static inline bool score_better(float v, int i, float bv, int bi) { return v > bv || (v == bv && i < bi); }
+__device__ static inline float score_recentre(float z, float s, float d) { return (z + s * d) * expf(d); }   // d = old centre - new <= 0
+__device__ static inline float score_entropy(float S, float Zc) {            // rounding may leave a one-point row a hair below 0
+    const float H = logf(S) - Zc / S;
+    return H < 0.f ? 0.f : H;                                                 // (a NaN stays)
+}
 
 // grid (m-tiles of 128 rows, n_split); 4 waves, wave w owns rows m0 + 32 w .. + 31 and walks the split's 16-column tiles four at
 // a time (2 x 4 MFMA tiles, 8 accumulators).  The four waves read the same W fragments (one fetch, three cache hits), so one
@@ -57,13 +67,15 @@ __device__ static inline bool score_better(float v, int i, float bv, int bi) { r
 // rows' topk-th pair in registers and offers a column only if it beats that pair in the full order -- after the first tile
 // groups almost none does.  Offers are served one lane at a time per 16-lane group (the four groups own different rows); the
 // serving lane tests against the list itself, so the result is the exact top of the split whatever the order of service.
-template <bool STORE, bool STOP, bool TOPK = false>
+// ENT (cw_set_score_entropy): a lane also keeps zc = sum exp(v - mx) (v - mx) for its 8 rows, and one bit per row for a NaN it saw.
+template <bool STORE, bool STOP, bool TOPK = false, bool ENT = false>
 __global__ __launch_bounds__(256) void score_head_kernel(const bf16_t* __restrict__ A, const bf16_t* __restrict__ W,
                                                          const int* __restrict__ target, ScorePart* __restrict__ part,
                                                          int M, int V, int K, int tiles_per_split, int n_split,
                                                          float* __restrict__ logits, int ldv,
                                                          ScoreStopPart* __restrict__ spart, int eos, int ts_begin,
-                                                         ScoreTopPart* __restrict__ tpart, int topk) {
+                                                         ScoreTopPart* __restrict__ tpart, int topk,
+                                                         float* __restrict__ epart) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int l15 = lane & 15, g = lane >> 4;
     const int m0 = blockIdx.x * 128 + wave * 32;
@@ -76,12 +88,15 @@ __global__ __launch_bounds__(256) void score_head_kernel(const bf16_t* __restric
     float mx[8], sum[8], tl[8], bv[8];
     int bi[8], tg[8];
     float smx[8], ssum[8];                                            // STOP only: the lane's columns that lie in S
+    float zc[8];                                                      // ENT only
+    unsigned nanrow = 0;                                              // ENT only: bit q = row q met a NaN logit
 #pragma unroll
     for (int q = 0; q < 8; ++q) {
         const int m = m0 + (q >> 2) * 16 + g * 4 + (q & 3);
         mx[q] = -INFINITY; sum[q] = 0.f; tl[q] = -INFINITY; bv[q] = -INFINITY; bi[q] = 0x7fffffff;
         tg[q] = m < M ? target[m] : -1;
         if (STOP) { smx[q] = -INFINITY; ssum[q] = 0.f; }
+        if (ENT) zc[q] = 0.f;
     }
     // TOPK: s_tv / s_ti [128 rows][CW_TOP_LOGPROBS_MAX], sorted best first, (-inf, INT_MAX) where empty; kv / ki: the topk-th pair
     __shared__ float s_tv[TOPK ? 128 * CW_TOP_LOGPROBS_MAX : 1];
@@ -153,7 +168,23 @@ __global__ __launch_bounds__(256) void score_head_kernel(const bf16_t* __restric
                 if (ok && n == tg[q]) tl[q] = v[j];
                 if (ok && v[j] > bv[q]) { bv[q] = v[j]; bi[q] = n; }          // columns ascend within a lane: strict > keeps the lowest id
             }
-            if (mnew > -INFINITY) {
+            if constexpr (ENT) {
+#pragma unroll
+                for (int j = 0; j < 4; ++j) nanrow |= (v[j] != v[j]) ? 1u << q : 0u;
+                if (mnew > -INFINITY) {
+                    float add = 0.f, addz = 0.f;
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) {
+                        const float d = v[j] - mnew, e = v[j] > -INFINITY ? expf(d) : 0.f;
+                        add += e;
+                        addz += v[j] > -INFINITY ? e * d : 0.f;
+                    }
+                    const float d0 = mx[q] - mnew, e0 = expf(d0);
+                    zc[q] = (mx[q] > -INFINITY ? (zc[q] + sum[q] * d0) * e0 : 0.f) + addz;
+                    sum[q] = (mx[q] > -INFINITY ? sum[q] * e0 : 0.f) + add;
+                    mx[q] = mnew;
+                }
+            } else if (mnew > -INFINITY) {
                 float add = 0.f;
 #pragma unroll
                 for (int j = 0; j < 4; ++j) add += v[j] > -INFINITY ? expf(v[j] - mnew) : 0.f;
@@ -228,6 +259,12 @@ __global__ __launch_bounds__(256) void score_head_kernel(const bf16_t* __restric
             const float obv = __shfl_xor(bv[q], off, 64);
             const int obi = __shfl_xor(bi[q], off, 64);
             const float mnew = fmaxf(mx[q], omx);
+            if constexpr (ENT) {                                              // before sum and mx move
+                const float ozc = __shfl_xor(zc[q], off, 64);
+                if (mnew > -INFINITY)
+                    zc[q] = (mx[q] > -INFINITY ? score_recentre(zc[q], sum[q], mx[q] - mnew) : 0.f) +
+                            (omx > -INFINITY ? score_recentre(ozc, osum, omx - mnew) : 0.f);
+            }
             if (mnew > -INFINITY)
                 sum[q] = (mx[q] > -INFINITY ? sum[q] * expf(mx[q] - mnew) : 0.f) + (omx > -INFINITY ? osum * expf(omx - mnew) : 0.f);
             mx[q] = mnew;
@@ -243,6 +280,12 @@ __global__ __launch_bounds__(256) void score_head_kernel(const bf16_t* __restric
             }
         }
         const int m = m0 + (q >> 2) * 16 + g * 4 + (q & 3);
+        if constexpr (ENT) {
+            bool bad = (nanrow >> q) & 1u;
+#pragma unroll
+            for (int off = 1; off < 16; off <<= 1) bad |= __shfl_xor((int)bad, off, 64) != 0;
+            if (l15 == 0 && m < M) epart[(size_t)m * n_split + split] = bad ? __builtin_nanf("") : zc[q];
+        }
         if (l15 == 0 && m < M) {
             ScorePart p;
             p.mx = mx[q]; p.sum = sum[q]; p.tl = tl[q]; p.bv = bv[q]; p.bi = bi[q];
@@ -267,14 +310,16 @@ __global__ __launch_bounds__(256) void score_head_kernel(const bf16_t* __restric
 // rounds over the row's n_split x CW_TOP_LOGPROBS_MAX pairs: in each, the best pair behind the one the round before took --
 // pairs are distinct (one per column), so "behind" needs no marks.  alt_id / alt_logprob [M][CW_TOP_LOGPROBS_MAX]: z - lse with
 // the lse logprob is written with; -1 / NaN at the ranks no candidate fills and at ranks >= topk.
-template <bool STOP, bool TOPK = false>
+// ENT: entropy[m] from the splits' (mx, sum, Zc) moved to the row maximum in split order
+template <bool STOP, bool TOPK = false, bool ENT = false>
 __global__ __launch_bounds__(256) void score_combine_kernel(const ScorePart* __restrict__ part, int M, int n_split,
                                                             float* __restrict__ logprob, int* __restrict__ top_id,
                                                             float* __restrict__ top_logprob,
                                                             const ScoreStopPart* __restrict__ spart,
                                                             float* __restrict__ stop_logprob,
                                                             const ScoreTopPart* __restrict__ tpart, int topk,
-                                                            int* __restrict__ alt_id, float* __restrict__ alt_logprob) {
+                                                            int* __restrict__ alt_id, float* __restrict__ alt_logprob,
+                                                            const float* __restrict__ epart, float* __restrict__ entropy) {
     const int m = TOPK ? blockIdx.x * 4 + (threadIdx.x >> 6) : blockIdx.x * 256 + threadIdx.x;
     if (m >= M) return;
     const bool writer = !TOPK || (threadIdx.x & 63) == 0;
@@ -294,6 +339,12 @@ __global__ __launch_bounds__(256) void score_combine_kernel(const ScorePart* __r
         logprob[m] = tl - lse;
         top_id[m] = bi;
         top_logprob[m] = bv - lse;
+    }
+    if constexpr (ENT) {
+        const float* ep = epart + (size_t)m * n_split;
+        float z = 0.f;
+        for (int s = 0; s < n_split; ++s) z += p[s].mx > -INFINITY ? score_recentre(ep[s], p[s].sum, p[s].mx - mx) : ep[s];
+        if (writer) entropy[m] = score_entropy(sum, z);
     }
     if (STOP) {
         const ScoreStopPart* sp = spart + (size_t)m * n_split;
@@ -338,14 +389,16 @@ __global__ __launch_bounds__(256) void score_combine_kernel(const ScorePart* __r
 // TOPK: topk block-wide selection rounds over the same row behind that, each taking the best (logit, id) behind the pair of the
 // round before; alt_id / alt_logprob [rows][t_stride][CW_TOP_LOGPROBS_MAX] = logit - lse with the lse above, -1 / NaN at the
 // ranks no candidate fills (a candidate is a column < V with a logit > -inf; a NaN is none) and at ranks >= topk
-template <bool STOP, bool TOPK = false>
+// ENT: entropy likewise, from sum exp(x - max) (x - max) beside the sum above (a -inf column adds nothing, a NaN makes it NaN)
+template <bool STOP, bool TOPK = false, bool ENT = false>
 __global__ __launch_bounds__(256) void score_rows_kernel(const float* __restrict__ logits, int ldv, int V,
                                                          const int* __restrict__ target, int t_stride, int t,
                                                          float* __restrict__ logprob, int* __restrict__ top_id,
                                                          float* __restrict__ top_logprob, int eos, int ts_begin,
                                                          float* __restrict__ stop_logprob, int topk,
-                                                         int* __restrict__ alt_id, float* __restrict__ alt_logprob) {
-    __shared__ float s_v[4], s_s[4], s_sv[4], s_ss[4];
+                                                         int* __restrict__ alt_id, float* __restrict__ alt_logprob,
+                                                         float* __restrict__ entropy) {
+    __shared__ float s_v[4], s_s[4], s_sv[4], s_ss[4], s_z[4];
     __shared__ int s_i[4];
     __shared__ float s_lse, s_cv[2][4];                                       // TOPK only: rounds alternate between two slots
     __shared__ int s_ci[2][4];
@@ -366,7 +419,18 @@ __global__ __launch_bounds__(256) void score_rows_kernel(const float* __restrict
     for (int w = 1; w < 4; ++w)
         if (score_better(s_v[w], s_i[w], bv, bi)) { bv = s_v[w]; bi = s_i[w]; }
     float sum = 0.f;
-    for (int n = tid; n < V; n += 256) sum += expf(lg[n] - bv);
+    if constexpr (ENT) {
+        float z = 0.f;
+        for (int n = tid; n < V; n += 256) {
+            const float d = lg[n] - bv, e = expf(d);
+            sum += e;
+            z += d > -INFINITY ? e * d : 0.f;                                 // (a NaN d is in sum already)
+        }
+        for (int o = 32; o > 0; o >>= 1) z += __shfl_xor(z, o, 64);
+        if (lane == 0) s_z[wave] = z;
+    } else {
+        for (int n = tid; n < V; n += 256) sum += expf(lg[n] - bv);
+    }
     for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o, 64);
     if (lane == 0) s_s[wave] = sum;
     float smx = -INFINITY;
@@ -397,6 +461,7 @@ __global__ __launch_bounds__(256) void score_rows_kernel(const float* __restrict
         if (STOP)
             stop_logprob[o] = smx > -INFINITY ? (smx + logf((s_ss[0] + s_ss[1]) + (s_ss[2] + s_ss[3]))) - lse : -INFINITY;
         if (TOPK) s_lse = lse;
+        if constexpr (ENT) entropy[o] = score_entropy((s_s[0] + s_s[1]) + (s_s[2] + s_s[3]), (s_z[0] + s_z[1]) + (s_z[2] + s_z[3]));
     }
     if (TOPK) {
         float pv = INFINITY;                                                  // the pair the round before took
@@ -447,35 +512,37 @@ int cw_score_head_splits(int M, int V, int* tiles_per_split) {
 }
 
 // One form of the fused head: the split kernel and its combine.  The arguments of a form that is off are null / 0.
-template <bool STOP, bool TOPK>
+template <bool STOP, bool TOPK, bool ENT = false>
 static void score_head_form(const void* A, const void* W, const int* target, int M, int V, int K, const ScoreHeadOut& o, hipStream_t st) {
     int tps = 0;
     const int ns = cw_score_head_splits(M, V, &tps);
     ScoreStopPart* const spart = STOP ? o.spart : nullptr;
     ScoreTopPart* const tpart = TOPK ? o.tpart : nullptr;
-    hipLaunchKernelGGL((score_head_kernel<false, STOP, TOPK>), dim3((M + 127) / 128, ns), dim3(256), 0, st, (const bf16_t*)A,
+    float* const epart = ENT ? o.epart : nullptr;
+    hipLaunchKernelGGL((score_head_kernel<false, STOP, TOPK, ENT>), dim3((M + 127) / 128, ns), dim3(256), 0, st, (const bf16_t*)A,
                        (const bf16_t*)W, target, o.part, M, V, K, tps, ns, (float*)nullptr, 0, spart, STOP ? o.eos : 0, STOP ? o.ts_begin : 0,
-                       tpart, TOPK ? o.k : 0);
-    hipLaunchKernelGGL((score_combine_kernel<STOP, TOPK>), dim3(TOPK ? (M + 3) / 4 : (M + 255) / 256), dim3(256), 0, st, o.part, M, ns,
+                       tpart, TOPK ? o.k : 0, epart);
+    hipLaunchKernelGGL((score_combine_kernel<STOP, TOPK, ENT>), dim3(TOPK ? (M + 3) / 4 : (M + 255) / 256), dim3(256), 0, st, o.part, M, ns,
                        o.logprob, o.top_id, o.top_logprob, (const ScoreStopPart*)spart, STOP ? o.stop_logprob : nullptr,
-                       (const ScoreTopPart*)tpart, TOPK ? o.k : 0, TOPK ? o.alt_id : nullptr, TOPK ? o.alt_logprob : nullptr);
+                       (const ScoreTopPart*)tpart, TOPK ? o.k : 0, TOPK ? o.alt_id : nullptr, TOPK ? o.alt_logprob : nullptr,
+                       (const float*)epart, ENT ? o.entropy : nullptr);
 }
 // ... and of the row kernel
-template <bool STOP, bool TOPK>
+template <bool STOP, bool TOPK, bool ENT = false>
 static void score_rows_form(const float* logits, int ldv, int V, const int* target, int t_stride, int t, int rows, const ScoreRowsOut& o,
                             hipStream_t st) {
-    hipLaunchKernelGGL((score_rows_kernel<STOP, TOPK>), dim3(rows), dim3(256), 0, st, logits, ldv, V, target, t_stride, t, o.logprob,
+    hipLaunchKernelGGL((score_rows_kernel<STOP, TOPK, ENT>), dim3(rows), dim3(256), 0, st, logits, ldv, V, target, t_stride, t, o.logprob,
                        o.top_id, o.top_logprob, STOP ? o.eos : 0, STOP ? o.ts_begin : 0, STOP ? o.stop_logprob : nullptr, TOPK ? o.k : 0,
-                       TOPK ? o.alt_id : nullptr, TOPK ? o.alt_logprob : nullptr);
+                       TOPK ? o.alt_id : nullptr, TOPK ? o.alt_logprob : nullptr, ENT ? o.entropy : nullptr);
 }
 
 // The code object holds the kernels in the order their instantiations are first asked for.  The forms are asked for here, around
 // the unfused launcher, in the order every build so far has held them, so that the device code of a change to the launchers
-// compares equal with its parent's.
-#define CW_SCORE_HEAD_FORM(STOP, TOPK) \
-    template void score_head_form<STOP, TOPK>(const void*, const void*, const int*, int, int, int, const ScoreHeadOut&, hipStream_t)
-#define CW_SCORE_ROWS_FORM(STOP, TOPK) \
-    template void score_rows_form<STOP, TOPK>(const float*, int, int, const int*, int, int, int, const ScoreRowsOut&, hipStream_t)
+// compares equal with its parent's.  The ENT forms come last.
+#define CW_SCORE_HEAD_FORM(...) \
+    template void score_head_form<__VA_ARGS__>(const void*, const void*, const int*, int, int, int, const ScoreHeadOut&, hipStream_t)
+#define CW_SCORE_ROWS_FORM(...) \
+    template void score_rows_form<__VA_ARGS__>(const float*, int, int, const int*, int, int, int, const ScoreRowsOut&, hipStream_t)
 CW_SCORE_HEAD_FORM(false, false);
 CW_SCORE_HEAD_FORM(true, false);
 
@@ -486,9 +553,10 @@ int cw_launch_score_head_unfused(const void* A, const void* W, const int* target
     int tps = 0;
     const int ns = cw_score_head_splits(M, V, &tps);
     hipLaunchKernelGGL((score_head_kernel<true, false>), dim3((M + 127) / 128, ns), dim3(256), 0, st, (const bf16_t*)A,
-                       (const bf16_t*)W, target, (ScorePart*)nullptr, M, V, K, tps, ns, logits, ldv, (ScoreStopPart*)nullptr, 0, 0, (ScoreTopPart*)nullptr, 0);
+                       (const bf16_t*)W, target, (ScorePart*)nullptr, M, V, K, tps, ns, logits, ldv, (ScoreStopPart*)nullptr, 0, 0, (ScoreTopPart*)nullptr, 0,
+                       (float*)nullptr);
     hipLaunchKernelGGL(score_rows_kernel<false>, dim3(M), dim3(256), 0, st, (const float*)logits, ldv, V, target, 1, 0, logprob,
-                       top_id, top_logprob, 0, 0, (float*)nullptr, 0, (int*)nullptr, (float*)nullptr);
+                       top_id, top_logprob, 0, 0, (float*)nullptr, 0, (int*)nullptr, (float*)nullptr, (float*)nullptr);
     return CW_OK;
 }
 
@@ -498,16 +566,29 @@ CW_SCORE_HEAD_FORM(false, true);
 CW_SCORE_HEAD_FORM(true, true);
 CW_SCORE_ROWS_FORM(false, true);
 CW_SCORE_ROWS_FORM(true, true);
+CW_SCORE_HEAD_FORM(false, false, true);
+CW_SCORE_HEAD_FORM(true, false, true);
+CW_SCORE_HEAD_FORM(false, true, true);
+CW_SCORE_HEAD_FORM(true, true, true);
+CW_SCORE_ROWS_FORM(false, false, true);
+CW_SCORE_ROWS_FORM(true, false, true);
+CW_SCORE_ROWS_FORM(false, true, true);
+CW_SCORE_ROWS_FORM(true, true, true);
 #undef CW_SCORE_HEAD_FORM
 #undef CW_SCORE_ROWS_FORM
 
-// The fused head over M rows (kernels.h: ScoreHeadOut).  This and cw_launch_score_rows pick among the STOP / TOPK forms
+// The fused head over M rows (kernels.h: ScoreHeadOut).  This and cw_launch_score_rows pick among the STOP / TOPK / ENT forms
+template <bool ENT>
+static void score_head_pick(bool stop, bool top, const void* A, const void* W, const int* target, int M, int V, int K, const ScoreHeadOut& o, hipStream_t st) {
+    if (top) stop ? score_head_form<true, true, ENT>(A, W, target, M, V, K, o, st) : score_head_form<false, true, ENT>(A, W, target, M, V, K, o, st);
+    else stop ? score_head_form<true, false, ENT>(A, W, target, M, V, K, o, st) : score_head_form<false, false, ENT>(A, W, target, M, V, K, o, st);
+}
 int cw_launch_score_head(const void* A, const void* W, const int* target, int M, int V, int K, const ScoreHeadOut& o, hipStream_t st) {
-    const bool stop = o.stop_logprob != nullptr, top = o.k != 0;
-    if (M < 1 || V < 1 || K < 32 || K % 32 || (stop && (o.eos < 0 || o.ts_begin < 0)) ||
+    const bool stop = o.stop_logprob != nullptr, top = o.k != 0, ent = o.entropy != nullptr;
+    if (M < 1 || V < 1 || K < 32 || K % 32 || (stop && (o.eos < 0 || o.ts_begin < 0)) || (ent && !o.epart) ||
         (top && (o.k < 1 || o.k > CW_TOP_LOGPROBS_MAX || !o.tpart || !o.alt_id || !o.alt_logprob))) return CW_ERR_INVALID;
-    if (top) stop ? score_head_form<true, true>(A, W, target, M, V, K, o, st) : score_head_form<false, true>(A, W, target, M, V, K, o, st);
-    else stop ? score_head_form<true, false>(A, W, target, M, V, K, o, st) : score_head_form<false, false>(A, W, target, M, V, K, o, st);
+    if (ent) score_head_pick<true>(stop, top, A, W, target, M, V, K, o, st);
+    else score_head_pick<false>(stop, top, A, W, target, M, V, K, o, st);
     return CW_OK;
 }
 
@@ -518,18 +599,24 @@ int cw_launch_score_head_store(const void* A, const void* W, const int* target, 
     const int ns = cw_score_head_splits(M, V, &tps);
     hipLaunchKernelGGL((score_head_kernel<true, false>), dim3((M + 127) / 128, ns), dim3(256), 0, st, (const bf16_t*)A,
                        (const bf16_t*)W, target, (ScorePart*)nullptr, M, V, K, tps, ns, logits, ldv,
-                       (ScoreStopPart*)nullptr, 0, 0, (ScoreTopPart*)nullptr, 0);
+                       (ScoreStopPart*)nullptr, 0, 0, (ScoreTopPart*)nullptr, 0, (float*)nullptr);
     return CW_OK;
 }
 
 // The loop path's row kernel at column t of [rows][t_stride] outputs (alternatives: [rows][t_stride][CW_TOP_LOGPROBS_MAX])
+template <bool ENT>
+static void score_rows_pick(bool stop, bool top, const float* logits, int ldv, int V, const int* target, int t_stride, int t, int rows,
+                            const ScoreRowsOut& o, hipStream_t st) {
+    if (top) stop ? score_rows_form<true, true, ENT>(logits, ldv, V, target, t_stride, t, rows, o, st) : score_rows_form<false, true, ENT>(logits, ldv, V, target, t_stride, t, rows, o, st);
+    else stop ? score_rows_form<true, false, ENT>(logits, ldv, V, target, t_stride, t, rows, o, st) : score_rows_form<false, false, ENT>(logits, ldv, V, target, t_stride, t, rows, o, st);
+}
 int cw_launch_score_rows(const float* logits, int ldv, int V, const int* target, int t_stride, int t, int rows, const ScoreRowsOut& o,
                          hipStream_t st) {
-    const bool stop = o.stop_logprob != nullptr, top = o.k != 0;
+    const bool stop = o.stop_logprob != nullptr, top = o.k != 0, ent = o.entropy != nullptr;
     if (rows < 1 || V < 1 || ldv < V || t < 0 || t >= t_stride || (stop && (o.eos < 0 || o.ts_begin < 0)) ||
         (top && (o.k < 1 || o.k > CW_TOP_LOGPROBS_MAX || !o.alt_id || !o.alt_logprob))) return CW_ERR_INVALID;
-    if (top) stop ? score_rows_form<true, true>(logits, ldv, V, target, t_stride, t, rows, o, st) : score_rows_form<false, true>(logits, ldv, V, target, t_stride, t, rows, o, st);
-    else stop ? score_rows_form<true, false>(logits, ldv, V, target, t_stride, t, rows, o, st) : score_rows_form<false, false>(logits, ldv, V, target, t_stride, t, rows, o, st);
+    if (ent) score_rows_pick<true>(stop, top, logits, ldv, V, target, t_stride, t, rows, o, st);
+    else score_rows_pick<false>(stop, top, logits, ldv, V, target, t_stride, t, rows, o, st);
     return CW_OK;
 }
 

@@ -106,6 +106,29 @@ def split_alignment(rec: np.ndarray):
     return rec[:o], rec[o:o + nt].view(np.float32).copy(), rec[o + REC_TOKENS:o + REC_TOKENS + nt].view(np.float32).copy()
 
 
+REC_ENTROPY_WORDS = REC_TOKENS               # token entropies behind a record of any width (and behind its alignment tail): one f32 per token
+
+
+def append_entropy(rec: np.ndarray, entropy) -> np.ndarray:
+    """``rec`` (a ``pack_record`` of any width, with or without ``append_alignment``'s tail) followed by the chunk's per-token
+    entropies.  ``rec`` itself is unchanged; both ends of the gather know from the call's arguments that the tail is there."""
+    nt = int(rec[1])
+    entropy = np.asarray(entropy, dtype=np.float32)
+    if entropy.shape != (nt,):
+        raise ValueError(f"token entropies of shape {entropy.shape} for {nt} tokens")
+    tail = np.zeros(REC_ENTROPY_WORDS, dtype=np.int32)
+    tail[:nt] = entropy.view(np.int32)
+    return np.concatenate([rec, tail])
+
+
+def split_entropy(rec: np.ndarray):
+    """(the record ``append_entropy`` was given, entropy [n_tok] f32)."""
+    if len(rec) < REC_WORDS + REC_ENTROPY_WORDS:
+        raise ValueError(f"a record of {len(rec)} words carries no token entropies")
+    nt, o = int(rec[1]), len(rec) - REC_ENTROPY_WORDS
+    return rec[:o], rec[o:o + nt].view(np.float32).copy()
+
+
 WORD_MAX = 448
 WORD_TEXT_BYTES = 4096
 WORD_REC = 3 + 4 * WORD_MAX + WORD_TEXT_BYTES // 4   # chunk_idx, n_words, n_text_bytes, (start,end) f64 bits, utf-8 text

@@ -340,6 +340,28 @@ class Engine:
         self._chk(self.lib.cw_set_top_logprobs(self.ctx, int(k)))
         self._top_k = int(k)
 
+    def set_token_entropy(self, on: bool):
+        """Predictive entropy (nats) of the raw next-token distribution of every decode step, next to the token log-probabilities
+        (``cw_set_token_entropy``); off by default, needs ``set_token_logprobs(True)``.  Greedy and sampled decoding only."""
+        self._chk(self.lib.cw_set_token_entropy(self.ctx, 1 if on else 0))
+
+    def token_entropy(self, nb: int) -> np.ndarray:
+        """[nb, max_target_positions] float32 aligned with the last ``decode``'s sequences: ``log S - Zc / S`` over the raw logits
+        of the step that wrote each token, whichever token that was; NaN wherever ``token_logprobs`` holds NaN, and at a step
+        whose logits hold a NaN or +inf (``cw_get_token_entropy``)."""
+        out = np.empty((nb, self.spec.max_target_positions), np.float32)
+        self._chk(self.lib.cw_get_token_entropy(self.ctx, _ptr(out), nb))
+        return out
+
+    def transcribe_token_entropy(self, lens) -> List[np.ndarray]:
+        """The values of the last ``transcribe``, one float32 array per item aligned with its tokens (``lens`` = their
+        counts; ``cw_get_transcribe_token_entropy``)."""
+        nb = len(lens)
+        cap = max(1, max((int(n) for n in lens), default=1))
+        out = np.empty((nb, cap), np.float32)
+        self._chk(self.lib.cw_get_transcribe_token_entropy(self.ctx, _ptr(out), nb, cap))
+        return [out[i, :int(n)].copy() for i, n in enumerate(lens)]
+
     def set_sequence_bias(self, table):
         """Phrase boosting in the sampler kernels (``cw_set_sequence_bias``): ``table`` is a sequence of ``(token ids, bias)``
         pairs -- at most 256 distinct sequences of 1 .. 16 ids, finite biases -- with the semantics of transformers'
@@ -603,14 +625,42 @@ class Engine:
         i0 = int(n_init)
         return ([ai[b, i0:n[b]].astype(np.int64) for b in range(nr)], [al[b, i0:n[b]].copy() for b in range(nr)])
 
-    def score_tokens(self, rows, n_init: int, rows_per_item: int = 1, top_logprobs: int = 0):
+    def set_score_entropy(self, on: bool):
+        """cw_set_score_entropy: the predictive entropy (nats) of every position the scoring calls score; off by default."""
+        self._chk(self.lib.cw_set_score_entropy(self.ctx, 1 if on else 0))
+
+    def score_entropy(self, nr: int, stride: int) -> np.ndarray:
+        """cw_get_score_entropy: [nr, stride] float32 of the last scoring call (its rows and ids stride), NaN where nothing was
+        scored."""
+        out = np.zeros((int(nr), int(stride)), dtype=np.float32)
+        self._chk(self.lib.cw_get_score_entropy(self.ctx, _ptr(out), int(nr), int(stride)))
+        return out
+
+    def _with_score_extras(self, top_logprobs, entropy, call, nr, stride, n, n_init):
+        """Runs ``call`` (one of the scoring calls) under ``top_logprobs`` (``_with_score_top``) and / or with
+        ``cw_set_score_entropy`` on around it -- off again afterwards, also when the call raises.  Returns the extra entries of
+        the call's result: the alternatives (ids, logprobs) when ``top_logprobs``, then the entropies per row (float32 [n]) when
+        ``entropy``."""
+        if not entropy:
+            return self._with_score_top(top_logprobs, call, nr, stride, n, n_init) if top_logprobs else call() or ()
+        self.set_score_entropy(True)
+        try:
+            alts = self._with_score_top(top_logprobs, call, nr, stride, n, n_init) if top_logprobs else call() or ()
+            en = self.score_entropy(nr, stride)
+        finally:
+            self.set_score_entropy(False)
+        i0 = int(n_init)
+        return tuple(alts) + ([en[b, i0:n[b]].copy() for b in range(nr)],)
+
+    def score_tokens(self, rows, n_init: int, rows_per_item: int = 1, top_logprobs: int = 0, entropy: bool = False):
         """Teacher-forced log-probabilities (cw_score_tokens): ``rows[r]`` is a whole decoder input (``n_init`` init tokens,
         transcript, eos), scored against resident feature item r // rows_per_item.  Returns (logprob, top_id, top_logprob):
         per row one array over its text tokens and the eos (len(rows[r]) - n_init entries) -- log p(token | audio, tokens
         before it) over the raw logits, and the arg-max id of the same distribution with its log-probability.
         ``top_logprobs=k`` (1 .. 8): two more entries, per row the ids [n][k] and log-probabilities [n][k] of the k best
         tokens of every scored position, best first, ties to the lower id, -1 / NaN past the candidates
-        (``cw_set_score_top_logprobs``)."""
+        (``cw_set_score_top_logprobs``).  ``entropy=True``: one more entry behind those, per row the predictive entropy (nats,
+        float32) of every scored position's distribution (``cw_set_score_entropy``)."""
         nr = len(rows)
         rpi = int(rows_per_item)
         if rpi >= 1 and nr % rpi:
@@ -622,15 +672,15 @@ class Engine:
         def call():
             self._chk(self.lib.cw_score_tokens(self.ctx, nr // rpi if rpi >= 1 else nr, rpi, _ptr(table), stride, _ptr(n), int(n_init),
                                                _ptr(lp), _ptr(ti), _ptr(tl)))
-        alts = self._with_score_top(top_logprobs, call, nr, stride, n, n_init) if top_logprobs else call() or ()
+        alts = self._with_score_extras(top_logprobs, entropy, call, nr, stride, n, n_init)
         k = int(n_init)
         return ([lp[b, k:n[b]].copy() for b in range(nr)], [ti[b, k:n[b]].astype(np.int64) for b in range(nr)],
                 [tl[b, k:n[b]].copy() for b in range(nr)]) + tuple(alts)
 
-    def align_score_tokens(self, num_frames, ids, n_init: int, top_logprobs: int = 0):
+    def align_score_tokens(self, num_frames, ids, n_init: int, top_logprobs: int = 0, entropy: bool = False):
         """cw_align_score_tokens: ``align_tokens`` and ``score_tokens`` (one row per item) of the same rows in one forward.
         Returns (timestamps as align_tokens, logprob, top_id, top_logprob as score_tokens[, with ``top_logprobs=k`` its
-        alternative ids and log-probabilities])."""
+        alternative ids and log-probabilities][, with ``entropy=True`` the positions' entropies])."""
         nb = len(ids)
         n, stride, table = self._token_table(ids)
         nf = _i32(num_frames)
@@ -641,12 +691,12 @@ class Engine:
         def call():
             self._chk(self.lib.cw_align_score_tokens(self.ctx, nb, _ptr(nf), _ptr(table), stride, _ptr(n), int(n_init), _ptr(ts),
                                                      _ptr(lp), _ptr(ti), _ptr(tl)))
-        alts = self._with_score_top(top_logprobs, call, nb, stride, n, n_init) if top_logprobs else call() or ()
+        alts = self._with_score_extras(top_logprobs, entropy, call, nb, stride, n, n_init)
         k = int(n_init)
         return ([ts[b, :n[b]].copy() for b in range(nb)], [lp[b, k:n[b]].copy() for b in range(nb)],
                 [ti[b, k:n[b]].astype(np.int64) for b in range(nb)], [tl[b, k:n[b]].copy() for b in range(nb)]) + tuple(alts)
 
-    def align_cut_tokens(self, num_frames, ids, n_init: int, cut_ok, force_all, top_logprobs: int = 0):
+    def align_cut_tokens(self, num_frames, ids, n_init: int, cut_ok, force_all, top_logprobs: int = 0, entropy: bool = False):
         """cw_align_cut_tokens: how much of each offered transcript was spoken inside its window, and the alignment of that part,
         in the one forward of ``align_score_tokens``.  ``ids`` as ``align_tokens`` takes them (row b offers N_b = len(ids[b]) -
         n_init - 1 text tokens); ``cut_ok[b]``: N_b + 1 flags, entry n allowing "keep the first n tokens"; ``force_all[b]``: keep
@@ -655,7 +705,8 @@ class Engine:
         row len(ids[b]) - n_init entries as ``score_tokens`` returns them).  stop_logprob[k] is the log-probability that the
         text stops before position k (eos or any timestamp token); cut maximises sum(logprob[:n]) + stop_logprob[n] over the
         allowed n, the lowest n on an exact tie.  ``top_logprobs=k``: two more entries, the alternatives as ``score_tokens``
-        returns them (every offered position, not the kept prefix only)."""
+        returns them (every offered position, not the kept prefix only).  ``entropy=True``: one more entry behind those, the
+        positions' entropies as ``score_tokens`` returns them."""
         nb = len(ids)
         n, stride, table = self._token_table(ids)
         if len(cut_ok) != nb or len(force_all) != nb:
@@ -679,7 +730,7 @@ class Engine:
         def call():
             self._chk(self.lib.cw_align_cut_tokens(self.ctx, nb, _ptr(nf), _ptr(table), stride, _ptr(n), k, _ptr(ok), _ptr(force),
                                                    _ptr(cut), _ptr(score), _ptr(ts), _ptr(lp), _ptr(sl), _ptr(ti), _ptr(tl)))
-        alts = self._with_score_top(top_logprobs, call, nb, stride, n, k) if top_logprobs else call() or ()
+        alts = self._with_score_extras(top_logprobs, entropy, call, nb, stride, n, k)
         return (cut.astype(np.int64), score, [ts[b, :k + cut[b] + 1].copy() for b in range(nb)],
                 [lp[b, k:n[b]].copy() for b in range(nb)], [sl[b, k:n[b]].copy() for b in range(nb)],
                 [ti[b, k:n[b]].astype(np.int64) for b in range(nb)], [tl[b, k:n[b]].copy() for b in range(nb)]) + tuple(alts)
@@ -805,6 +856,59 @@ class Engine:
                                                   _ptr(out["stop_logprob"]) if stop is not None else None, _ptr(out["alt_id"]),
                                                   _ptr(out["alt_logprob"])))
         return out
+
+    def test_score_head_entropy(self, x, ln_g, ln_b, embed, targets, k: int = 0, want_logits: bool = False, stop=None):
+        """cw_test_score_head_entropy: the ENT form of the head, alone or joined with TOPK (``k`` > 0) and / or STOP (``stop`` =
+        (eos, timestamp_begin)) -> dict as ``test_score_head_top`` plus entropy [M] (alt_id / alt_logprob only with ``k`` > 0)."""
+        x = np.ascontiguousarray(x, np.float32)
+        embed = np.ascontiguousarray(embed, np.float32)
+        g = np.ascontiguousarray(ln_g, np.float32)
+        b = np.ascontiguousarray(ln_b, np.float32)
+        t = _i32(targets)
+        M, D = x.shape
+        V = embed.shape[0]
+        if embed.shape[1] != D or g.shape != (D,) or b.shape != (D,) or t.shape != (M,):
+            raise ValueError("test_score_head_entropy: shapes do not agree")
+        out = {"logprob": np.zeros(M, np.float32), "top_id": np.zeros(M, np.int32), "top_logprob": np.zeros(M, np.float32),
+               "entropy": np.full(M, 7.0, np.float32)}
+        if int(k) > 0:
+            out["alt_id"], out["alt_logprob"] = np.full((M, 8), -7, np.int32), np.full((M, 8), 7.0, np.float32)
+        if stop is not None:
+            out["stop_logprob"] = np.zeros(M, np.float32)
+        lg = np.full((M, V), 7.0, np.float32) if want_logits else None
+        self._chk(self.lib.cw_test_score_head_entropy(
+            self.ctx, M, D, V, _ptr(x), _ptr(g), _ptr(b), _ptr(embed), _ptr(t), int(stop[0]) if stop is not None else 0,
+            int(stop[1]) if stop is not None else 0, int(k), _ptr(out["logprob"]), _ptr(out["top_id"]), _ptr(out["top_logprob"]),
+            _ptr(out.get("stop_logprob")), _ptr(out.get("alt_id")), _ptr(out.get("alt_logprob")), _ptr(out["entropy"]), _ptr(lg)))
+        if want_logits:
+            out["logits"] = lg
+        return out
+
+    def test_score_rows_entropy(self, logits, V: int, targets, k: int = 0, stop=None):
+        """cw_test_score_rows_entropy: the loop path's row kernel (ENT form, with TOPK when ``k`` > 0 and STOP when ``stop``) over
+        f32 ``logits`` [rows][ldv], columns 0 .. V-1 -> dict as ``test_score_rows_top`` plus entropy [rows]."""
+        lg = np.ascontiguousarray(logits, np.float32)
+        rows, ldv = lg.shape
+        t = _i32(targets)
+        if t.shape != (rows,):
+            raise ValueError("test_score_rows_entropy: shapes do not agree")
+        out = {"logprob": np.zeros(rows, np.float32), "top_id": np.zeros(rows, np.int32), "top_logprob": np.zeros(rows, np.float32),
+               "entropy": np.full(rows, 7.0, np.float32)}
+        if int(k) > 0:
+            out["alt_id"], out["alt_logprob"] = np.full((rows, 8), -7, np.int32), np.full((rows, 8), 7.0, np.float32)
+        if stop is not None:
+            out["stop_logprob"] = np.zeros(rows, np.float32)
+        self._chk(self.lib.cw_test_score_rows_entropy(
+            self.ctx, rows, int(V), ldv, _ptr(lg), _ptr(t), int(k), int(stop[0]) if stop is not None else 0,
+            int(stop[1]) if stop is not None else 0, _ptr(out["logprob"]), _ptr(out["top_id"]), _ptr(out["top_logprob"]),
+            _ptr(out.get("stop_logprob")), _ptr(out.get("alt_id")), _ptr(out.get("alt_logprob")), _ptr(out["entropy"])))
+        return out
+
+    def time_score_head_entropy(self, M: int, k: int = 0, stop: bool = False, iters: int = 10) -> float:
+        """cw_time_score_head_entropy: ``time_score_head_top`` with the ENT form on."""
+        ms = C.c_float(0.0)
+        self._chk(self.lib.cw_time_score_head_entropy(self.ctx, int(M), int(k), 1 if stop else 0, int(iters), C.byref(ms)))
+        return float(ms.value)
 
     def time_score_head_top(self, M: int, k: int, stop: bool = False, iters: int = 10) -> float:
         """cw_time_score_head_top: ms per run of the fused head (``stop``: its STOP form) with k alternatives per row (0: none)."""
@@ -1292,6 +1396,35 @@ class Engine:
                                                        int(seed) & (2 ** 64 - 1), _ptr(rs), _ptr(fr), int(k), _ptr(out), _ptr(lp),
                                                        _ptr(top_id), _ptr(top_lp)))
         return out, lp, top_id, top_lp
+
+    def test_sample_entropy(self, logits: np.ndarray, ids: np.ndarray, n_prompt: int, k: int = 0, temperature: float = 0.0,
+                            seed: int = 0, row_streams=None, forced=None, min_new_tokens: int = 0,
+                            max_length: Optional[int] = None):
+        """``test_sample_logprobs`` with ``set_token_entropy(True)`` on for the call (cw_test_sample_entropy): returns (choice
+        [nb], logprob [nb], entropy [nb]) of index t, and with ``k`` > 0 also (top ids [nb][k], top logprobs [nb][k])."""
+        lg = np.ascontiguousarray(logits, np.float32)
+        ids = _i32(ids)
+        nb, t = ids.shape
+        if lg.shape != (nb, self.spec.vocab_size):
+            raise ValueError(f"logits must be [{nb}][{self.spec.vocab_size}], got {lg.shape}")
+        if not 0 <= int(k) <= 8:
+            raise ValueError(f"k must be in 0 .. 8, got {k}")
+        rs = None if row_streams is None else np.ascontiguousarray(row_streams, dtype=np.uint64)
+        if rs is not None and rs.shape != (nb,):
+            raise ValueError(f"row_streams must hold one id per row ({nb}), got shape {rs.shape}")
+        fr = None if forced is None else _i32(forced)
+        if fr is not None and fr.shape != (nb,):
+            raise ValueError(f"forced must hold one token per row ({nb}), got shape {fr.shape}")
+        out = np.zeros(nb, np.int32)
+        lp = np.zeros(nb, np.float32)
+        ent = np.zeros(nb, np.float32)
+        top_id = np.zeros((nb, max(1, int(k))), np.int32)
+        top_lp = np.zeros((nb, max(1, int(k))), np.float32)
+        self._chk(self.lib.cw_test_sample_entropy(self.ctx, nb, _ptr(lg), _ptr(ids), t, int(n_prompt), int(min_new_tokens),
+                                                  int(max_length or self.spec.max_target_positions), float(temperature),
+                                                  int(seed) & (2 ** 64 - 1), _ptr(rs), _ptr(fr), int(k), _ptr(out), _ptr(lp),
+                                                  _ptr(ent), _ptr(top_id), _ptr(top_lp)))
+        return (out, lp, ent, top_id, top_lp) if int(k) > 0 else (out, lp, ent)
 
     def test_sample_biased(self, logits: np.ndarray, ids: np.ndarray, n_prompt: int, k: int, table=None, temperature: float = 0.0,
                            seed: int = 0, row_streams=None, forced=None, min_new_tokens: int = 0,

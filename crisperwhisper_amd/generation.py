@@ -39,6 +39,7 @@ class Segment:
     top_logprobs: Optional[np.ndarray] = None     # float32 [n_tok][k]: their log-probabilities (-1 / NaN: fewer than k candidates)
     alignment_scores: Optional[np.ndarray] = None   # float32, one per token: attention mass on the DTW path (generate(return_alignment_scores=True))
     alignment_spreads: Optional[np.ndarray] = None  # float32, one per token: spread of the attention in seconds
+    token_entropy: Optional[np.ndarray] = None      # float32, one per token: entropy of its step's raw distribution (generate(return_token_entropy=True))
 
 
 def detect_language(engine: Engine, n_items: int) -> np.ndarray:
@@ -231,11 +232,15 @@ def prompted_max_length(spec, n_input: int, max_new_tokens: Optional[int]) -> in
 
 
 def split_segments(seq: np.ndarray, token_ts: np.ndarray, time_offset: float, timestamp_begin: int,
-                   seek_num_frames: int, idx_offset: int, token_lp: Optional[np.ndarray] = None, token_top=None, token_align=None):
+                   seek_num_frames: int, idx_offset: int, token_lp: Optional[np.ndarray] = None, token_top=None, token_align=None,
+                   token_ent: Optional[np.ndarray] = None):
     """Slice one decoded window at paired timestamp tokens; returns (segments, frames to advance).  ``token_lp`` (per-token
     log-probabilities of the row, indexed like ``token_ts``), ``token_top`` (the row's (ids [T][k], log-probabilities [T][k])
-    alternatives, indexed alike) and ``token_align`` (the row's (mass, spread) alignment scores, indexed alike) are cut by the
-    same index ranges."""
+    alternatives, indexed alike), ``token_align`` (the row's (mass, spread) alignment scores, indexed alike) and ``token_ent`` (the
+    row's token entropies, indexed alike) are cut by the same index ranges."""
+    def en(a, b):
+        return None if token_ent is None else np.asarray(token_ent[a:b], dtype=np.float32).copy()
+
     def al(a, b):
         if token_align is None:
             return None, None
@@ -265,7 +270,8 @@ def split_segments(seq: np.ndarray, token_ts: np.ndarray, time_offset: float, ti
         for cut in cuts:
             out.append(Segment(seq[prev:cut], (token_ts[idx_offset + prev: idx_offset + cut] + off32).astype(np.float32),
                                (idx_offset + prev, idx_offset + cut), lp(idx_offset + prev, idx_offset + cut),
-                               *top(idx_offset + prev, idx_offset + cut), *al(idx_offset + prev, idx_offset + cut)))
+                               *top(idx_offset + prev, idx_offset + cut), *al(idx_offset + prev, idx_offset + cut),
+                               en(idx_offset + prev, idx_offset + cut)))
             prev = cut
         if single_ending:
             advance = seek_num_frames
@@ -274,7 +280,8 @@ def split_segments(seq: np.ndarray, token_ts: np.ndarray, time_offset: float, ti
     else:
         out.append(Segment(seq, (token_ts[idx_offset: idx_offset + len(seq)] + off32).astype(np.float32),
                            (idx_offset, idx_offset + len(seq)), lp(idx_offset, idx_offset + len(seq)),
-                           *top(idx_offset, idx_offset + len(seq)), *al(idx_offset, idx_offset + len(seq))))
+                           *top(idx_offset, idx_offset + len(seq)), *al(idx_offset, idx_offset + len(seq)),
+                           en(idx_offset, idx_offset + len(seq))))
         advance = seek_num_frames
     return out, advance
 
@@ -579,7 +586,8 @@ def generate(engine: Engine, n_items: int, num_frames, *, language: Optional[str
              logprob_threshold: Optional[float] = None, no_speech_threshold: Optional[float] = None, prompt_ids=None,
              temperature=None, compression_ratio_threshold: Optional[float] = None, sampling_seed: int = 0, item_ids=None,
              return_token_logprobs: bool = False, top_logprobs: int = 0, sequence_bias=None,
-             return_alignment_scores: bool = False, alignment_collar_frames: Optional[int] = None, language_candidates=None):
+             return_alignment_scores: bool = False, alignment_collar_frames: Optional[int] = None, language_candidates=None,
+             return_token_entropy: bool = False):
     """Transcribe the ``n_items`` 30 s feature windows resident in the engine (items 0..n-1).
 
     Returns {"sequences": [B, Lmax] int64 (pad-right), "token_timestamps": list of float32 arrays,
@@ -623,6 +631,11 @@ def generate(engine: Engine, n_items: int, num_frames, *, language: Optional[str
     rule, no temperature, so the written token need not be among them; where it is, its value equals ``token_logprobs`` bit for
     bit.  A rank beyond the number of finite logits holds -1 / NaN.
 
+    ``return_token_entropy=True`` (needs ``return_token_logprobs=True`` and ``num_beams=1``) adds "token_entropy": one float32
+    array per item aligned with ``token_timestamps``, the predictive entropy in nats of the raw distribution of each token's step
+    (``cw_set_token_entropy``): no suppress lists, no timestamp rule, no temperature, no ``sequence_bias``, and independent of the
+    token that was written.  Under temperature fallback the values are those of the pass that was kept.
+
     ``sequence_bias`` (transformers' list or dict form, ``check_sequence_bias``; needs ``num_beams=1``): phrase boosting with the
     semantics of SequenceBiasLogitsProcessor, applied inside the sampler kernels (``cw_set_sequence_bias``) in front of every other
     logits processor, in every window and every fallback re-decode.  The prompt tokens take part in the prefix match.  The raw
@@ -652,7 +665,8 @@ def generate(engine: Engine, n_items: int, num_frames, *, language: Optional[str
                          temperature=temperature, compression_ratio_threshold=compression_ratio_threshold,
                          sampling_seed=sampling_seed, item_ids=item_ids, return_token_logprobs=return_token_logprobs,
                          top_logprobs=top_logprobs, return_alignment_scores=return_alignment_scores,
-                         alignment_collar_frames=alignment_collar_frames, language_candidates=language_candidates)
+                         alignment_collar_frames=alignment_collar_frames, language_candidates=language_candidates,
+                         return_token_entropy=return_token_entropy)
     finally:
         if table is not None:
             engine.set_sequence_bias(None)
@@ -661,7 +675,7 @@ def generate(engine: Engine, n_items: int, num_frames, *, language: Optional[str
 def _generate(engine: Engine, n_items: int, num_frames, *, language, task, max_new_tokens, min_new_tokens, num_beams, stats, native,
               logprob_threshold, no_speech_threshold, prompt_ids, temperature, compression_ratio_threshold, sampling_seed, item_ids,
               return_token_logprobs, top_logprobs, return_alignment_scores=False, alignment_collar_frames=None,
-              language_candidates=None):
+              language_candidates=None, return_token_entropy=False):
     """``generate`` proper: everything but the sequence_bias table, which ``generate`` sets around this call."""
     spec = engine.spec
     cand_ids = check_language_candidates(spec, language_candidates)
@@ -687,6 +701,15 @@ def _generate(engine: Engine, n_items: int, num_frames, *, language, task, max_n
                              "every step): pass num_beams=1")
         if not hasattr(engine, "set_top_logprobs"):
             raise ValueError("this engine does not implement top_logprobs (cw_set_top_logprobs)")
+    want_ent = bool(return_token_entropy)
+    if want_ent:
+        if not want_lp:
+            raise ValueError("return_token_entropy needs return_token_logprobs=True (the entropy shares its running sums)")
+        if num_beams is not None and int(num_beams) > 1:
+            raise ValueError("return_token_entropy is implemented for greedy and sampled decoding only (beam search re-parents its "
+                             "rows every step): pass num_beams=1")
+        if not hasattr(engine, "set_token_entropy"):
+            raise ValueError("this engine does not implement token entropy (cw_set_token_entropy)")
     if no_speech_threshold is not None and logprob_threshold is None:
         raise ValueError("no_speech_threshold needs logprob_threshold as well (generation_whisper.py:1275-1285 compares both)")
     # every argument is checked before any engine state changes (a refused call must not leave its thresholds behind)
@@ -722,7 +745,7 @@ def _generate(engine: Engine, n_items: int, num_frames, *, language, task, max_n
         if len(ids_) != n_items:
             raise ValueError(f"{len(ids_)} item_ids for {n_items} items")
         fb = {"temps": temps, "seed": int(sampling_seed), "item_ids": ids_, "cr_thr": compression_ratio_threshold,
-              "token_logprobs": want_lp, "top_logprobs": want_top, "alignment_scores": want_as}
+              "token_logprobs": want_lp, "top_logprobs": want_top, "alignment_scores": want_as, "token_entropy": want_ent}
         native = False                                  # the fallback loop runs here, like beam search
     if hasattr(engine, "set_thresholds"):
         engine.set_thresholds(logprob_threshold, no_speech_threshold)
@@ -732,6 +755,8 @@ def _generate(engine: Engine, n_items: int, num_frames, *, language, task, max_n
         engine.set_token_logprobs(want_lp)
     if hasattr(engine, "set_top_logprobs"):
         engine.set_top_logprobs(want_top)
+    if hasattr(engine, "set_token_entropy"):
+        engine.set_token_entropy(want_ent)
     set_alignment_scores(engine, want_as, collar)
     num_frames = np.asarray(num_frames, dtype=np.int64)
     if native is None:
@@ -771,6 +796,8 @@ def _generate(engine: Engine, n_items: int, num_frames, *, language, task, max_n
             out["top_ids"], out["top_logprobs"] = engine.transcribe_top_logprobs([len(s) for s in toks])
         if want_as:
             out["alignment_scores"], out["alignment_spreads"] = engine.transcribe_alignment_scores([len(s) for s in toks])
+        if want_ent:
+            out["token_entropy"] = engine.transcribe_token_entropy([len(s) for s in toks])
         return out
     pre_encoded = False
     _, detect = resolve_prompt(spec, language, task)
@@ -801,7 +828,7 @@ def _generate(engine: Engine, n_items: int, num_frames, *, language, task, max_n
     try:
         _seek_loop(engine, spec, n_items, num_frames, init, n_prompt, max_new_tokens, min_new_tokens, num_beams, prefix,
                    prompted_len if prefix is not None else None, skip_on, logprob_threshold, no_speech_threshold, pre_encoded,
-                   seek, max_frames, segments, tb, stats, fb, want_lp, want_top, want_as)
+                   seek, max_frames, segments, tb, stats, fb, want_lp, want_top, want_as, want_ent)
     finally:
         if prefix is not None and set_prefix is not None:
             set_prefix(0)
@@ -826,12 +853,15 @@ def _generate(engine: Engine, n_items: int, num_frames, *, language, task, max_n
                                    for segs in segments]
         out["alignment_spreads"] = [np.concatenate([s.alignment_spreads for s in segs]) if segs else np.zeros(0, np.float32)
                                     for segs in segments]
+    if want_ent:
+        out["token_entropy"] = [np.concatenate([s.token_entropy for s in segs]) if segs else np.zeros(0, np.float32)
+                                for segs in segments]
     return out
 
 
 def _seek_loop(engine, spec, n_items, num_frames, init, n_prompt, max_new_tokens, min_new_tokens, num_beams, prefix, prompted_len,
                skip_on, logprob_threshold, no_speech_threshold, pre_encoded, seek, max_frames, segments, tb, stats, fb=None, want_lp=False,
-               want_top=0, want_as=False):
+               want_top=0, want_as=False, want_ent=False):
     """The seek loop of the host path of ``generate`` (fills ``segments`` in place).  ``fb``: temperature fallback settings."""
     n_calls = 0
     while True:
@@ -856,11 +886,12 @@ def _seek_loop(engine, spec, n_items, num_frames, init, n_prompt, max_new_tokens
                 lp_row = kept[row][3] if want_lp else None
                 top_row = kept[row][4:6] if want_top else None
                 as_row = kept[row][-2:] if want_as else None
+                ent_row = kept[row][4 + (2 if want_top else 0)] if want_ent else None
                 if skip:
                     seek[i] += seek_num[i]                        # should_skip (:879-881)
                     continue
                 segs, advance = split_segments(s, ts_row, float(seek[i]) * TIME_PRECISION / INPUT_STRIDE, tb,
-                                               int(seek_num[i]), n_prompt, lp_row, top_row, as_row)
+                                               int(seek_num[i]), n_prompt, lp_row, top_row, as_row, ent_row)
                 seek[i] += advance
                 segments[i].extend(segs)
             continue
@@ -882,6 +913,8 @@ def _seek_loop(engine, spec, n_items, num_frames, init, n_prompt, max_new_tokens
                 tok_lp = engine.token_logprobs(len(active))
             if want_top:
                 tok_top = engine.top_logprobs(len(active))
+            if want_ent:
+                tok_ent = engine.token_entropy(len(active))
         token_ts = engine.token_timestamps(len(active), L, n_prompt, (num_frames - seek)[active])
         if want_as:
             tok_as = engine.alignment_scores(len(active), L)
@@ -902,7 +935,8 @@ def _seek_loop(engine, spec, n_items, num_frames, init, n_prompt, max_new_tokens
             segs, advance = split_segments(s, token_ts[row], float(seek[i]) * TIME_PRECISION / INPUT_STRIDE, tb,
                                            int(seek_num[i]), n_prompt, tok_lp[row] if want_lp else None,
                                            (tok_top[0][row], tok_top[1][row]) if want_top else None,
-                                           (tok_as[0][row], tok_as[1][row]) if want_as else None)
+                                           (tok_as[0][row], tok_as[1][row]) if want_as else None,
+                                           tok_ent[row] if want_ent else None)
             seek[i] += advance
             segments[i].extend(segs)
     if stats is not None:
@@ -919,7 +953,8 @@ def _decode_with_fallback(engine, spec, fb, active, init_rows, n_prompt, max_len
     rows).  Decisions are indexed by the original row throughout -- transformers indexes ``needs_fallback[i]`` /
     ``should_skip[i]`` by the row of the shrunken sub-batch (:1074 against :1088) and reads them back by the original one.
     Returns per row (tokens without eos, token timestamps of the whole row, skip[, token log-probabilities of the whole row when
-    ``fb["token_logprobs"]`` is set[, alternative ids and log-probabilities of the whole row when ``fb["top_logprobs"]`` is]][,
+    ``fb["token_logprobs"]`` is set[, alternative ids and log-probabilities of the whole row when ``fb["top_logprobs"]`` is][, the
+    token entropies of the whole row when ``fb["token_entropy"]`` is]][,
     last of all, the row's alignment scores and spreads when ``fb["alignment_scores"]`` is set])."""
     nb = len(active)
     temps = fb["temps"]
@@ -943,6 +978,7 @@ def _decode_with_fallback(engine, spec, fb, active, init_rows, n_prompt, max_len
             tok_as = engine.alignment_scores(nb, total - 1) if fb.get("alignment_scores") else None
             tok_lp = engine.token_logprobs(nb) if fb.get("token_logprobs") else None   # a masked row keeps its settled values
             tok_top = engine.top_logprobs(nb) if tok_lp is not None and fb.get("top_logprobs") else None   # ... and entries
+            tok_ent = engine.token_entropy(nb) if tok_lp is not None and fb.get("token_entropy") else None
             again = []
             for r in pending:
                 s = seqs[r, n_prompt:total].astype(np.int64)
@@ -969,6 +1005,8 @@ def _decode_with_fallback(engine, spec, fb, active, init_rows, n_prompt, max_len
                     kept[r] += (np.array(tok_lp[r], copy=True),)
                 if tok_top is not None:
                     kept[r] += (np.array(tok_top[0][r], copy=True), np.array(tok_top[1][r], copy=True))
+                if tok_ent is not None:
+                    kept[r] += (np.array(tok_ent[r], copy=True),)
                 if tok_as is not None:
                     kept[r] += (np.array(tok_as[0][r], copy=True), np.array(tok_as[1][r], copy=True))
                 if needs and not last:
@@ -1005,7 +1043,7 @@ def check_transcript_ids(spec, ids) -> np.ndarray:
 
 def align(engine: Engine, n_items: int, num_frames, transcripts, *, language: Optional[str] = None,
           task: Optional[str] = None, return_scores: bool = False, return_alignment_scores: bool = False,
-          alignment_collar_frames: Optional[int] = None, top_logprobs: int = 0):
+          alignment_collar_frames: Optional[int] = None, top_logprobs: int = 0, return_entropy: bool = False):
     """Forced alignment of known transcripts to the ``n_items`` 30 s feature windows resident in the engine.
 
     Row b is the decoder input <|startoftranscript|><|lang|><|task|> ++ transcripts[b] ++ eos, with the init tokens resolved by
@@ -1017,11 +1055,13 @@ def align(engine: Engine, n_items: int, num_frames, transcripts, *, language: Op
     "top_ids", "top_logprobs": per transcript one entry per token plus one for the eos; with ``top_logprobs=k`` (1 .. 8) also
     "alt_ids" / "alt_logprobs" [n][k], the k best tokens of each of those positions (``check_score_top_logprobs``).
     ``return_alignment_scores=True`` adds "alignment_scores" and "alignment_spreads", one value per transcript token, as
-    ``generate`` defines them."""
+    ``generate`` defines them.  ``return_entropy=True`` (needs ``return_scores=True``) adds "token_entropy": per transcript the
+    predictive entropy (nats, float32) of every scored position, indexed as "token_logprobs" (``cw_set_score_entropy``)."""
     spec = engine.spec
     want_top = check_score_top_logprobs(top_logprobs)
     if want_top and not return_scores:
         raise ValueError("top_logprobs lists the alternatives next to every token's log-probability: it needs return_scores=True")
+    want_ent = check_score_entropy(return_entropy, return_scores)
     want_as = bool(return_alignment_scores)
     collar = check_alignment_collar(spec, alignment_collar_frames)
     if want_as and not hasattr(engine, "set_alignment_scores"):
@@ -1049,11 +1089,14 @@ def align(engine: Engine, n_items: int, num_frames, transcripts, *, language: Op
     set_alignment_scores(engine, want_as, collar)
     if return_scores:
         # (the argument is passed only when set: an engine without it still serves the plain call)
-        ts, lp, ti, tl, *alts = engine.align_score_tokens(num_frames, rows, n_init, **({"top_logprobs": want_top} if want_top else {}))
+        ts, lp, ti, tl, *alts = engine.align_score_tokens(num_frames, rows, n_init, **({"top_logprobs": want_top} if want_top else {}),
+                                                          **({"entropy": True} if want_ent else {}))
         out = {"sequences": texts, "token_timestamps": [s[n_init:n_init + len(t)] for s, t in zip(ts, texts)],
                "token_logprobs": lp, "top_ids": ti, "top_logprobs": tl}
         if want_top:
-            out["alt_ids"], out["alt_logprobs"] = alts
+            out["alt_ids"], out["alt_logprobs"] = alts[:2]
+        if want_ent:
+            out["token_entropy"] = alts[-1]
     else:
         ts = engine.align_tokens(num_frames, rows, n_init)
         out = {"sequences": texts, "token_timestamps": [s[n_init:n_init + len(t)] for s, t in zip(ts, texts)]}
@@ -1062,6 +1105,14 @@ def align(engine: Engine, n_items: int, num_frames, transcripts, *, language: Op
         out["alignment_scores"] = [mass[b, n_init:n_init + len(t)].copy() for b, t in enumerate(texts)]
         out["alignment_spreads"] = [spread[b, n_init:n_init + len(t)].copy() for b, t in enumerate(texts)]
     return out
+
+
+def check_score_entropy(return_entropy, return_scores=True) -> bool:
+    """``return_entropy`` of ``score`` / ``align`` / ``align_long``: the predictive entropy of every teacher-forced position beside
+    its log-probability, so it needs the scoring forward."""
+    if return_entropy and not return_scores:
+        raise ValueError("return_entropy gives the entropy of every position next to its log-probability: it needs return_scores=True")
+    return bool(return_entropy)
 
 
 def check_score_top_logprobs(k) -> int:
@@ -1090,7 +1141,8 @@ def check_text_ids(spec, ids) -> np.ndarray:
 def align_long(engine: Engine, pcms, transcripts, collate_words, *, language: Optional[str] = None, task: Optional[str] = None,
                return_scores: bool = False, return_alignment_scores: bool = False,
                alignment_collar_frames: Optional[int] = None, max_window_tokens: Optional[int] = None,
-               stats: Optional[dict] = None, item_ids=None, sampling_rate: int = 16000, top_logprobs: int = 0):
+               stats: Optional[dict] = None, item_ids=None, sampling_rate: int = 16000, top_logprobs: int = 0,
+               return_entropy: bool = False):
     """Forced alignment of known transcripts to recordings of any length: the walk behind ``CrisperWhisperPipeline.align_long``.
 
     ``pcms``: at most ``engine.max_batch`` mono float32 recordings at ``sampling_rate``; ``transcripts``: one per recording, text
@@ -1118,13 +1170,16 @@ def align_long(engine: Engine, pcms, transcripts, collate_words, *, language: Op
     ``return_alignment_scores``: "alignment_score" / "alignment_spread" per chunk.  ``top_logprobs=k`` (needs
     ``return_scores``): every chunk gains "tokens", one {"id", "logprob", "alt_ids", "alt_logprobs"} per token of its group --
     the k best tokens of that position, carried through the cut as the log-probabilities are: the kept prefix of a window
-    only.  ``stats["align_long"]`` gains one record per (recording, window): {"item", "seek_s", "offered", "cut", "cut_score",
+    only.  ``return_entropy=True`` (needs ``return_scores``): every chunk gains "entropy" / "entropy_max" (float64 mean and maximum
+    over its group of the positions' predictive entropies, ``pipeline.add_token_entropy``), every entry of "tokens" its own
+    "entropy", and the result "avg_entropy" over the kept tokens and the eos.  ``stats["align_long"]`` gains one record per (recording, window): {"item", "seek_s", "offered", "cut", "cut_score",
     "forced"}."""
     spec = engine.spec
     n_rec = len(pcms)
     want_top = check_score_top_logprobs(top_logprobs)
     if want_top and not return_scores:
         raise ValueError("top_logprobs lists the alternatives next to every token's log-probability: it needs return_scores=True")
+    want_ent = check_score_entropy(return_entropy, return_scores)
     want_as = bool(return_alignment_scores)
     collar = check_alignment_collar(spec, alignment_collar_frames)
     if want_as and not hasattr(engine, "set_alignment_scores"):
@@ -1156,7 +1211,7 @@ def align_long(engine: Engine, pcms, transcripts, collate_words, *, language: Op
     for b in range(n_rec):
         r = Rec()
         r.pcm, r.T, r.n, r.pos, r.seek, r.init, r.rounds = pcms[b], texts[b], len(texts[b]), 0, 0, None, 0
-        r.chunks, r.lp, r.text, r.bounds = [], [], "", []
+        r.chunks, r.lp, r.text, r.bounds, r.en = [], [], "", [], []
         if r.n:
             r.text, _, groups = collate_words(r.T, np.zeros(r.n, np.float32))
             starts = {int(min(g)) for g in groups if len(g)}
@@ -1202,7 +1257,8 @@ def align_long(engine: Engine, pcms, transcripts, collate_words, *, language: Op
             rows.append(np.concatenate([np.asarray(r.init, np.int64), r.T[r.pos:r.pos + L], [spec.eos_token_id]]))
             masks.append(ok); forced.append(last); offered.append(L)
         cut, cut_score, ts, lp, _, _, _, *alts = engine.align_cut_tokens(nf, rows, n_init, masks, forced,
-                                                                       **({"top_logprobs": want_top} if want_top else {}))
+                                                                       **({"top_logprobs": want_top} if want_top else {}),
+                                                                       **({"entropy": True} if want_ent else {}))
         if want_as:
             mass, spread = engine.alignment_scores(len(active), max(n_init + int(c) for c in cut))
         for k, b in enumerate(active):
@@ -1226,6 +1282,10 @@ def align_long(engine: Engine, pcms, transcripts, collate_words, *, language: Op
                     for w, g in zip(words, groups):
                         w["tokens"] = [{"id": int(r.T[r.pos + j]), "logprob": float(lp[k][j]), "alt_ids": a_id[j].copy(),
                                         "alt_logprobs": a_lp[j].copy()} for j in g]
+                if want_ent:                                 # ... and so do the entropies
+                    from .pipeline import add_token_entropy
+                    add_token_entropy(words, groups, [alts[-1][k][:c]])
+                    r.en.append(np.asarray(alts[-1][k][:c], np.float64))
                 if want_as:
                     from .pipeline import add_alignment_scores
                     add_alignment_scores(words, groups, [mass[k, n_init:n_init + c]], [spread[k, n_init:n_init + c]])
@@ -1237,6 +1297,8 @@ def align_long(engine: Engine, pcms, transcripts, collate_words, *, language: Op
                 r.pos += c
                 if r.pos == r.n:
                     r.lp.append(np.asarray(lp[k][c:c + 1], np.float64))      # c == L here: the eos after the whole transcript
+                    if want_ent:
+                        r.en.append(np.asarray(alts[-1][k][c:c + 1], np.float64))
                 if not forced[k]:
                     r.seek += (int(round(end * 100)) // 2) * 2 * frame         # whole 20 ms frames, floored
             elif not forced[k]:
@@ -1252,6 +1314,9 @@ def align_long(engine: Engine, pcms, transcripts, collate_words, *, language: Op
             total = float(allp.sum())
             res["logprob"] = total
             res["avg_logprob"] = total / (r.n + 1)
+            if want_ent:
+                alle = np.concatenate(r.en) if r.en else np.zeros(0, np.float64)
+                res["avg_entropy"] = float(alle.mean()) if len(alle) else float("nan")
         out.append(res)
     return out
 
@@ -1405,7 +1470,7 @@ def plan_score_calls(n_candidates: Sequence[int], max_batch: int):
 
 
 def score(engine: Engine, n_items: int, candidates, *, language: Optional[str] = None, task: Optional[str] = None,
-          load_items: Optional[Callable[[List[int]], None]] = None, top_logprobs: int = 0):
+          load_items: Optional[Callable[[List[int]], None]] = None, top_logprobs: int = 0, return_entropy: bool = False):
     """Teacher-forced log-probabilities of candidate transcripts of the ``n_items`` 30 s feature windows resident in the engine.
 
     ``candidates[b]`` is a list of K_b transcripts (token ids, ``check_transcript_ids``).  Row (b, k) is the decoder input
@@ -1417,9 +1482,11 @@ def score(engine: Engine, n_items: int, candidates, *, language: Optional[str] =
     0 .. n-1 in order run (all items with one candidate count, fitting one call).  Returns per item a list over its candidates of
     {"ids", "token_logprobs", "top_ids", "top_logprobs"}: one entry per token plus one for the eos ("top_logprobs" is the
     arg-max's log-probability).  The argument ``top_logprobs=k`` (1 .. 8, ``check_score_top_logprobs``) adds "alt_ids" /
-    "alt_logprobs" [n][k]: the k best tokens of each of those positions."""
+    "alt_logprobs" [n][k]: the k best tokens of each of those positions.  ``return_entropy=True`` adds "token_entropy": the predictive
+    entropy (nats, float32) of each of those positions (``cw_set_score_entropy``)."""
     spec = engine.spec
     want_top = check_score_top_logprobs(top_logprobs)
+    want_ent = bool(return_entropy)
     if len(candidates) != n_items:
         raise ValueError(f"{len(candidates)} candidate lists for {n_items} items")
     if n_items > engine.max_batch:
@@ -1455,13 +1522,16 @@ def score(engine: Engine, n_items: int, candidates, *, language: Optional[str] =
             resident = list(items)
         rows = [np.concatenate([np.asarray(inits[b], np.int64), texts[b][c0 + j], [spec.eos_token_id]])
                 for b, c0 in members for j in range(rpi)]
-        lp, ti, tl, *alts = engine.score_tokens(rows, n_init, rows_per_item=rpi, **({"top_logprobs": want_top} if want_top else {}))
+        lp, ti, tl, *alts = engine.score_tokens(rows, n_init, rows_per_item=rpi, **({"top_logprobs": want_top} if want_top else {}),
+                                                **({"entropy": True} if want_ent else {}))
         r = 0
         for b, c0 in members:
             for j in range(rpi):
                 out[b][c0 + j] = {"ids": texts[b][c0 + j], "token_logprobs": lp[r], "top_ids": ti[r], "top_logprobs": tl[r]}
                 if want_top:
                     out[b][c0 + j]["alt_ids"], out[b][c0 + j]["alt_logprobs"] = alts[0][r], alts[1][r]
+                if want_ent:
+                    out[b][c0 + j]["token_entropy"] = alts[-1][r]
                 r += 1
     if resident != list(range(n_items)) and load_items is not None:
         load_items(list(range(n_items)))

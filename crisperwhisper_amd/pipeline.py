@@ -415,6 +415,24 @@ def scored_words(vocab, outputs, token_logprobs, warn=None, token_top=None, retu
     return text, words
 
 
+def add_token_entropy(words, groups, token_entropy):
+    """Puts "entropy" and "entropy_max" on every word: the float64 mean and the maximum of ``token_entropy`` (one array per
+    window, one value per token: the predictive entropy in nats of the raw distribution of the step that wrote the token) over
+    the collator's own token group of the word, so a token the seam merge drops counts in no word.  NaN if any member is NaN, or
+    the group is empty.  Where a word carries "tokens" (``top_logprobs``), each entry gains its own "entropy"."""
+    flat = np.concatenate([np.asarray(a, np.float64) for a in token_entropy]) if len(token_entropy) else np.zeros(0, np.float64)
+    for w, g in zip(words, groups):
+        g = np.asarray(g, np.int64).reshape(-1)
+        h = flat[g]
+        bad = (not g.size) or bool(np.isnan(h).any())
+        w["entropy"] = float("nan") if bad else float(np.mean(h))
+        w["entropy_max"] = float("nan") if bad else float(np.max(h))
+        if "tokens" in w and len(w["tokens"]) == g.size:
+            for t, x in zip(w["tokens"], h):
+                t["entropy"] = float(x)
+    return words
+
+
 def _check_top_logprobs(k) -> int:
     if k is None:
         return 0
@@ -438,8 +456,16 @@ class CrisperWhisperPipeline:
                  encoder_gemm_dtype: Optional[str] = None,
                  engines: Optional[List[Engine]] = None, num_beams: Optional[int] = None,
                  sampling_seed: Optional[int] = None, return_scores: bool = False, top_logprobs: int = 0,
-                 return_alignment_scores: bool = False, alignment_collar_frames: Optional[int] = None, **kwargs):
-        """``return_alignment_scores`` (here or per call, default False; needs ``return_timestamps="word"``): every word chunk
+                 return_alignment_scores: bool = False, alignment_collar_frames: Optional[int] = None,
+                 return_entropy: bool = False, **kwargs):
+        """``return_entropy`` (here or per call, default False; needs ``return_scores=True``, ``return_timestamps="word"`` and
+        ``num_beams=1``): every word chunk gains "entropy", the float64 mean over its tokens of the predictive entropy (nats) of
+        the raw next-token distribution at the decode step that chose each token, and "entropy_max", the largest of them
+        (``add_token_entropy``); with ``top_logprobs`` every entry of "tokens" gains its own "entropy".  A word written at
+        log-probability -0.7 with entropy 0.7 was a choice between two tokens; the same -0.7 with entropy 5 is a model that is
+        lost.  Everything else in the result is unchanged.
+
+        ``return_alignment_scores`` (here or per call, default False; needs ``return_timestamps="word"``): every word chunk
         gains "alignment_score", the share of the alignment heads' attention that lies inside the frames the DTW path gave the
         word's tokens (1: every head looks exactly there; near 0: the path had to invent the boundary), and "alignment_spread",
         the standard deviation of that attention over the frames in seconds -- float64 means over the collator's own token groups,
@@ -488,6 +514,7 @@ class CrisperWhisperPipeline:
         self.return_timestamps = return_timestamps
         self.return_scores = bool(return_scores)
         self.top_logprobs = _check_top_logprobs(top_logprobs)
+        self.return_entropy = bool(return_entropy)
         self.return_alignment_scores = bool(return_alignment_scores)
         if alignment_collar_frames is not None:
             generation.check_alignment_collar(self.bundle.spec, alignment_collar_frames)
@@ -553,7 +580,8 @@ class CrisperWhisperPipeline:
 
     def _run_one(self, inputs, return_timestamps=None, generate_kwargs=None, chunk_length_s=None,
                  stride_length_s=None, return_language=None, sampling_seed=None, return_scores=None, top_logprobs=None,
-                 return_alignment_scores=None, alignment_collar_frames=None, language_candidates=None, **unused):
+                 return_alignment_scores=None, alignment_collar_frames=None, language_candidates=None, return_entropy=None,
+                 **unused):
         """``return_language=True``: every chunk gains "language", the full lowercase name of the language its window was
         decoded with (``LANGUAGES[code]``, as transformers gives it; None when the decoder prompt carries no language), in word
         and in segment mode and in every decoding mode.  Each window's language token -- forced or detected -- is put in front
@@ -581,6 +609,10 @@ class CrisperWhisperPipeline:
         if top_k and not scores:
             raise ValueError("top_logprobs lists the alternatives next to every token's log-probability: it needs "
                              'return_scores=True and return_timestamps="word"')
+        ent_on = getattr(self, "return_entropy", False) if return_entropy is None else bool(return_entropy)
+        if ent_on and not (scores and rt == "word"):
+            raise ValueError("return_entropy gives every word the entropy of its tokens' decode steps next to their "
+                             'log-probability: it needs return_scores=True and return_timestamps="word"')
         if not (rt == "word" or rt is True):
             raise ValueError("crisperwhisper_amd implements the timestamped paths: pass return_timestamps='word' "
                              "(CrisperWhisper's purpose, REF/transcribe.py:28) or True (segment-level chunks, the "
@@ -601,6 +633,9 @@ class CrisperWhisperPipeline:
             raise ValueError("only the default length_penalty=1.0 / early_stopping=False beam search is implemented")
         if top_k and num_beams > 1:
             raise ValueError(f"top_logprobs is implemented for greedy and sampled decoding only, this call decodes with "
+                             f"{num_beams} beams: pass generate_kwargs={{'num_beams': 1}}")
+        if ent_on and num_beams > 1:
+            raise ValueError(f"return_entropy is implemented for greedy and sampled decoding only, this call decodes with "
                              f"{num_beams} beams: pass generate_kwargs={{'num_beams': 1}}")
         import time as _time
         t_ph = [_time.perf_counter()]                       # phase clock of this call: load | local batches | gather | collation
@@ -642,7 +677,7 @@ class CrisperWhisperPipeline:
                 no_speech_threshold=gk.get("no_speech_threshold"), prompt_ids=gk.get("prompt_ids"),
                 temperature=gk.get("temperature"), compression_ratio_threshold=gk.get("compression_ratio_threshold"),
                 sampling_seed=seed or 0, item_ids=idxs, **({"return_token_logprobs": True} if scores else {}),
-                **({"top_logprobs": top_k} if top_k else {}),
+                **({"top_logprobs": top_k} if top_k else {}), **({"return_token_entropy": True} if ent_on else {}),
                 **({"return_alignment_scores": True, "alignment_collar_frames": collar} if align_on else {}),
                 **({"sequence_bias": gk["sequence_bias"]} if gk.get("sequence_bias") is not None else {}),
                 **({"language_candidates": language_candidates} if language_candidates is not None else {}))
@@ -656,6 +691,7 @@ class CrisperWhisperPipeline:
                 r_lp = out["token_logprobs"][k] if scores else None
                 r_top = (out["top_ids"][k], out["top_logprobs"][k]) if top_k else None
                 r_as = (out["alignment_scores"][k], out["alignment_spreads"][k]) if align_on else None
+                r_en = out["token_entropy"][k] if ent_on else None
                 if want_lang and int(out["languages"][k]) >= 0:
                     # the window's language token leads its tokens (TF/pipelines/automatic_speech_recognition.py:640-650); it
                     # belongs to no word, so the placeholder in front of every per-token array belongs to no group
@@ -669,9 +705,13 @@ class CrisperWhisperPipeline:
                                  np.concatenate([np.full((1, top_k), np.nan, np.float32), np.asarray(r_top[1], np.float32).reshape(-1, top_k)]))
                     if align_on:
                         r_as = (np.concatenate([nan1, np.asarray(r_as[0], np.float32)]), np.concatenate([nan1, np.asarray(r_as[1], np.float32)]))
+                    if ent_on:
+                        r_en = np.concatenate([nan1, np.asarray(r_en, np.float32)])
                 rs.append(dist.pack_record(i, r_tok, r_ts, stride, r_lp, r_top))
                 if align_on:                               # the alignment scores travel behind the record, whatever its width
                     rs[-1] = dist.append_alignment(rs[-1], r_as[0], r_as[1])
+                if ent_on:                                 # ... and the token entropies behind that
+                    rs[-1] = dist.append_entropy(rs[-1], r_en)
             return rs, st.get("generate_calls", 0)
 
         per = self.batch_size
@@ -701,13 +741,18 @@ class CrisperWhisperPipeline:
         width = dist.rec_words_top(top_k) if top_k else (dist.REC_WORDS_SCORED if scores else dist.REC_WORDS)
         if align_on:
             width += dist.REC_ALIGN_WORDS
+        if ent_on:
+            width += dist.REC_ENTROPY_WORDS
         recs = np.stack(recs) if recs else np.zeros((0, width), np.int32)
         max_per_rank = max(h - l for l, h in dist.shard_bounds(len(windows), self.shard.world))
         t_ph.append(_time.perf_counter())
         allr = self.shard.all_gather_records(recs, max_per_rank)
         t_ph.append(_time.perf_counter())
-        outputs, token_lp, token_top, token_mass, token_spread = [], [], [], [], []
+        outputs, token_lp, token_top, token_mass, token_spread, token_ent = [], [], [], [], [], []
         for r in allr:
+            if ent_on:
+                r, ent = dist.split_entropy(r)
+                token_ent.append(ent)
             if align_on:
                 r, mass, spread = dist.split_alignment(r)
                 token_mass.append(mass)
@@ -733,6 +778,8 @@ class CrisperWhisperPipeline:
                                              return_timestamps="word" if rt == "word" else True, return_language=want_lang)
         if align_on:
             add_alignment_scores(words, groups, token_mass, token_spread)
+        if ent_on:
+            add_token_entropy(words, groups, token_ent)
         t_ph.append(_time.perf_counter())
         # where the wall time of the last call went on this rank (bench.py's long-form leg prints it: the scaling model of
         # DESIGN.md section 5 needs the rank-local part, which shrinks with the rank count, apart from the rest, which does not)
@@ -913,7 +960,8 @@ class CrisperWhisperPipeline:
             raise ValueError("a transcript mixes token ids with other elements: give either one sequence of ids or a list of candidates")
         return list(t), True
 
-    def score(self, inputs, transcripts, language: Optional[str] = None, task: Optional[str] = None, top_logprobs=None, **kwargs):
+    def score(self, inputs, transcripts, language: Optional[str] = None, task: Optional[str] = None, top_logprobs=None,
+              return_entropy: bool = False, **kwargs):
         """How well known transcripts fit the audio: teacher-forced log-probabilities under the model.  ``inputs`` as
         ``align`` takes them (one, or a list; each at most 30 s); ``transcripts[b]`` one transcript (``str`` or token ids) or
         a list of candidates for input b, which share one encoder pass.  Per input one dict, or a list of dicts in the order
@@ -922,8 +970,12 @@ class CrisperWhisperPipeline:
         logprob is the sum over the tokens the collator groups into it.  Raw logits: no suppress lists, no timestamp rules.
         ``top_logprobs=k`` (0 .. 8; the constructor's ``top_logprobs`` concerns ``__call__`` only): every entry of "tokens"
         gains "top_logprobs": [{"id", "text", "logprob"}, ...], the k most probable tokens of that position best first (ties
-        to the lower id), and "rank": the index of the token's own id in that list, None when it is not among the k."""
+        to the lower id), and "rank": the index of the token's own id in that list, None when it is not among the k.
+        ``return_entropy=True``: every entry of "tokens" gains "entropy", the predictive entropy (nats) of that position's whole
+        distribution; every chunk "entropy" / "entropy_max", the float64 mean and the maximum over its tokens; the result
+        "avg_entropy", the mean over the tokens and the eos (``cw_set_score_entropy``; the definition of ``__call__``'s)."""
         top_k = _check_top_logprobs(top_logprobs)
+        want_ent = bool(return_entropy)
         language, task = self._forced_kwargs("score", language, task, kwargs)
         single = not isinstance(inputs, (list, tuple))
         if single:
@@ -947,12 +999,12 @@ class CrisperWhisperPipeline:
             eng.mel([pcms[i] for i in idx])
             out = generation.score(eng, len(idx), [cands[i] for i in idx], language=language, task=task,
                                    load_items=lambda items: eng.mel([pcms[idx[j]] for j in items]),
-                                   **({"top_logprobs": top_k} if top_k else {}))
+                                   **({"top_logprobs": top_k} if top_k else {}), **({"return_entropy": True} if want_ent else {}))
             for k, i in enumerate(idx):
                 rs = []
                 for o in out[k]:
                     lp = np.asarray(o["token_logprobs"], np.float64)
-                    text, chunks = self._scored_words(o["ids"], lp[:-1])
+                    text, chunks, groups = self._scored_words(o["ids"], lp[:-1], return_groups=True)
                     toks = [{"id": int(t), "logprob": float(a), "top_id": int(ti), "top_logprob": float(tl)}
                             for t, a, ti, tl in zip(list(o["ids"]) + [eos], lp, o["top_ids"], o["top_logprobs"])]
                     if top_k:
@@ -961,12 +1013,18 @@ class CrisperWhisperPipeline:
                     total = float(lp.sum())
                     rs.append({"text": text, "logprob": total, "avg_logprob": total / (len(o["ids"]) + 1), "tokens": toks,
                                "chunks": chunks})
+                    if want_ent:
+                        en = np.asarray(o["token_entropy"], np.float64)
+                        for t, x in zip(toks, en):
+                            t["entropy"] = float(x)
+                        add_token_entropy(chunks, groups, [en[:-1]])
+                        rs[-1]["avg_entropy"] = float(en.mean())
                 results.append(rs if listed[i] else rs[0])
         return results[0] if single else results
 
     def align(self, inputs, transcripts, language: Optional[str] = None, task: Optional[str] = None,
               return_scores: bool = False, return_alignment_scores: bool = False,
-              alignment_collar_frames: Optional[int] = None, top_logprobs=None, **kwargs):
+              alignment_collar_frames: Optional[int] = None, top_logprobs=None, return_entropy: bool = False, **kwargs):
         """Word timestamps for known transcripts: ``inputs`` in any form ``__call__`` takes (one, or a list), each at most
         30 s; ``transcripts`` one per input, a ``str`` (needs a transformers tokenizer) or token ids without special
         tokens.  ``language`` / ``task`` resolve like ``generate_kwargs`` in ``__call__`` (``language=None``: detected per
@@ -977,8 +1035,10 @@ class CrisperWhisperPipeline:
         "alignment_score" / "alignment_spread" to every chunk, as ``__call__`` defines them (``alignment_collar_frames`` likewise;
         None: the pipeline's own setting).  ``top_logprobs=k`` (0 .. 8, needs ``return_scores=True``): every chunk gains
         "tokens": [{"id", "text", "logprob", "top_logprobs", "rank"}] over the collator's own token group, as ``score`` lists
-        them."""
+        them.  ``return_entropy=True`` (needs ``return_scores=True``): every chunk gains "entropy" / "entropy_max", every entry of
+        "tokens" its own "entropy", and the result "avg_entropy", as ``score`` defines them."""
         top_k = self._check_align_top("align", top_logprobs, return_scores)
+        want_ent = generation.check_score_entropy(return_entropy, return_scores)
         language, task = self._forced_kwargs("align", language, task, kwargs)
         collar = getattr(self, "alignment_collar_frames", None) if alignment_collar_frames is None else alignment_collar_frames
         if collar is not None:
@@ -1006,7 +1066,8 @@ class CrisperWhisperPipeline:
             _, nf = eng.mel([pcms[i] for i in idx])
             if return_scores:
                 out = generation.align(eng, len(idx), nf, [ids[i] for i in idx], language=language, task=task, return_scores=True,
-                                       **akw, **({"top_logprobs": top_k} if top_k else {}))
+                                       **akw, **({"top_logprobs": top_k} if top_k else {}),
+                                       **({"return_entropy": True} if want_ent else {}))
                 for k in range(len(idx)):
                     lp = np.asarray(out["token_logprobs"][k], np.float64)
                     text, chunks, groups = self._scored_words(out["sequences"][k], lp[:-1], out["token_timestamps"][k],
@@ -1019,6 +1080,10 @@ class CrisperWhisperPipeline:
                                                            out["alt_logprobs"][k], g)
                     results.append({"text": text, "chunks": with_alignment(out, k, chunks, groups),
                                     "logprob": total, "avg_logprob": total / (len(out["sequences"][k]) + 1)})
+                    if want_ent:
+                        en = np.asarray(out["token_entropy"][k], np.float64)
+                        add_token_entropy(chunks, groups, [en[:-1]])
+                        results[-1]["avg_entropy"] = float(en.mean())
                 continue
             out = generation.align(eng, len(idx), nf, [ids[i] for i in idx], language=language, task=task, **akw)
             for k in range(len(idx)):
@@ -1031,7 +1096,8 @@ class CrisperWhisperPipeline:
 
     def align_long(self, inputs, transcripts, language: Optional[str] = None, task: Optional[str] = None,
                    return_scores: bool = False, return_alignment_scores: bool = False,
-                   alignment_collar_frames: Optional[int] = None, max_window_tokens: Optional[int] = None, top_logprobs=None):
+                   alignment_collar_frames: Optional[int] = None, max_window_tokens: Optional[int] = None, top_logprobs=None,
+                   return_entropy: bool = False):
         """``align`` for audio of any length: walks a known transcript over the recording in 30 s windows.  ``inputs`` one
         input or a list, as ``align`` takes them but of any length; ``transcripts`` one per input, a ``str`` or text token ids
         (no timestamp tokens).  Every window is offered the transcript from the first token not yet placed, up to
@@ -1047,6 +1113,7 @@ class CrisperWhisperPipeline:
         Not claimed: that the cut is right.  It is the maximum-a-posteriori prefix under the model; how well that places
         the cut with a trained checkpoint is unmeasured."""
         top_k = self._check_align_top("align_long", top_logprobs, return_scores)
+        want_ent = generation.check_score_entropy(return_entropy, return_scores)
         collar = getattr(self, "alignment_collar_frames", None) if alignment_collar_frames is None else alignment_collar_frames
         if collar is not None:
             collar = generation.check_alignment_collar(None, collar)
@@ -1073,13 +1140,16 @@ class CrisperWhisperPipeline:
                 eng, [pcms[i] for i in idx], [ids[i] for i in idx], collate_words, language=language, task=task,
                 return_scores=return_scores, return_alignment_scores=return_alignment_scores, alignment_collar_frames=collar,
                 max_window_tokens=max_window_tokens, stats=self.stats, item_ids=idx, sampling_rate=self.sampling_rate,
-                **({"top_logprobs": top_k} if top_k else {})))
+                **({"top_logprobs": top_k} if top_k else {}), **({"return_entropy": True} if want_ent else {})))
         if top_k:                                            # the walk's raw rows -> what align(top_logprobs=k) lists
             for res in results:
                 for c in res["chunks"]:
                     raw = c["tokens"]
                     c["tokens"] = self._alt_tokens([t["id"] for t in raw], [t["logprob"] for t in raw], [t["alt_ids"] for t in raw],
                                                    [t["alt_logprobs"] for t in raw], range(len(raw)))
+                    for t, r_ in zip(c["tokens"], raw):
+                        if "entropy" in r_:
+                            t["entropy"] = r_["entropy"]
         return results[0] if single else results
 
     # -- per-head forced alignment, alignment-head selection -----------------------------------------

@@ -218,6 +218,31 @@ int32_t cw_get_transcribe_token_logprobs(cw_ctx* ctx, float* out /* [B][cap] */,
 int32_t cw_set_top_logprobs(cw_ctx* ctx, int32_t k);
 int32_t cw_get_top_logprobs(cw_ctx* ctx, int32_t* ids_out, float* lp_out /* [nb][max_target_positions][k] */, int32_t nb);
 int32_t cw_get_transcribe_top_logprobs(cw_ctx* ctx, int32_t* ids_out, float* lp_out /* [B][cap][k] */, int32_t B, int32_t cap);
+/* Token entropy: how flat the whole next-token distribution was at the step that wrote a token.  With the switch on (default
+ * off) the sampler kernels also store, for every row and sequence position t they write, the predictive entropy in nats
+ *     F = { v < vocab_size : logits[v] > -inf },  m = max_F logits,
+ *     S = sum_F exp(logits[v] - m),  Zc = sum_F exp(logits[v] - m) (logits[v] - m),
+ *     entropy[t] = log S - Zc / S                                  0 <= entropy[t] <= log |F|
+ * on the RAW f32 logits of the step, the distribution of logprob[t] above: no suppress lists, no timestamp rule, no temperature,
+ * no Gumbel noise, no sequence_bias; masked tokens count, pad columns never do.  It does not depend on which token was written
+ * (arg-max, sampled or forced), so free-running and teacher-forced numbers are comparable.  NaN where F is empty or a logit
+ * v < vocab_size is NaN or +inf.  A value that f32 rounding leaves below 0 (a one-point distribution) is stored as 0.  No launch, no forward and no stored logits are added: stage 1 of the sampler keeps Zc beside the
+ * (max, sum exp) pair it keeps for logprob[t]; partials (m_i, S_i, Zc_i) move to a common centre M as
+ *     S = sum S_i e^(m_i - M),  Zc = sum (Zc_i + S_i (m_i - M)) e^(m_i - M)
+ * in a fixed order (thread, block, the 16 slices), without atomics: a row's value is bit-identical from run to run and whatever
+ * else is in the batch.
+ * cw_set_token_entropy: CW_ERR_STATE while cw_set_token_logprobs is off (switching that off switches this off too).  Allocates
+ * [max_batch][max_target_positions] f32 and the slice partials on first use; drops the captured decode steps when the value
+ * changes.  Greedy / sampled decoding only: beam search does not carry it.
+ * cw_get_token_entropy: [nb][max_target_positions], aligned with `sequences`: NaN at every position where cw_get_token_logprobs
+ * holds NaN (prompt positions, behind a row's end, rows never decoded; both are stored by one branch), and besides only at a step
+ * whose logits hold a NaN or +inf -- there the log-probability may still be finite, because its log-sum-exp steps over a NaN that
+ * a thread meets before any finite logit, while the entropy is NaN for every such row.  A row masked by cw_decode_rows keeps its
+ * values.  cw_get_transcribe_token_entropy: those of the last cw_transcribe /
+ * cw_transcribe_prompted, carried through segment slicing as the token log-probabilities are (NaN behind lens[i]).          */
+int32_t cw_set_token_entropy(cw_ctx* ctx, int32_t on);
+int32_t cw_get_token_entropy(cw_ctx* ctx, float* out /* [nb][max_target_positions] */, int32_t nb);
+int32_t cw_get_transcribe_token_entropy(cw_ctx* ctx, float* out /* [B][cap] */, int32_t B, int32_t cap);
 /* sequence_bias: steer the free-running decode towards (or away from) known token sequences -- the contract of transformers'
  * SequenceBiasLogitsProcessor.  The table is a set of n_seq distinct token sequences (`tokens` = their concatenation, lengths[i]
  * tokens each, 1 .. CW_SEQUENCE_BIAS_MAX_LEN) with one finite bias each.  At the step that writes sequence index t (ids[0 .. t-1]
@@ -480,6 +505,18 @@ int32_t cw_score_prefill_runs(cw_ctx* ctx);
  * rows than the last call scored, for another stride, or when no call has run since the switch was set.                     */
 int32_t cw_set_score_top_logprobs(cw_ctx* ctx, int32_t k);
 int32_t cw_get_score_top_logprobs(cw_ctx* ctx, int32_t* ids_out, float* lp_out, int32_t rows, int32_t ids_stride);
+/* cw_set_score_entropy: the predictive entropy (nats) of every teacher-forced position (default off), computed on the device
+ * inside the scoring forward of cw_score_tokens / cw_align_score_tokens / cw_align_cut_tokens -- the [M][V] logits are still
+ * never stored.  The definition is that of cw_set_token_entropy over z[n], n < V, the f32 logits of a scored position as the head
+ * computes them: entropy = log S - Zc / S over the columns with z[n] > -inf; NaN where a z[n] is NaN or +inf.  The fused head keeps
+ * Zc beside its (maximum, sum) pair per lane, merges the 16 lanes of a row, then the vocabulary splits in split order; the loop
+ * path's row kernel takes it from the step's logits.  It can be combined with cw_set_score_top_logprobs and with the stop form of
+ * cw_align_cut_tokens; every other output of the call is what it is with the switch off.
+ * cw_get_score_entropy: after one of the three calls, with that call's rows and ids_stride: out [rows][ids_stride], filled at
+ * indices n_init .. n_ids[r]-1 of row r, NaN elsewhere (indexing as cw_get_score_top_logprobs).  CW_ERR_STATE while off, for more
+ * rows than the last call scored, for another stride, or when no call has run since the switch was set.                     */
+int32_t cw_set_score_entropy(cw_ctx* ctx, int32_t on);
+int32_t cw_get_score_entropy(cw_ctx* ctx, float* out, int32_t rows, int32_t ids_stride);
 
 /* ---- stand-alone differential-test entry points for the alignment kernels ---------------------------- */
 /* attn [B][Ha][N][M] -> mat [B][N][M] (z-score, median(width), head mean); n_cols[b] <= M columns used.  */
@@ -629,6 +666,18 @@ int32_t cw_test_score_rows_top(cw_ctx* ctx, int32_t rows, int32_t V, int32_t ldv
                                float* top_logprob, float* stop_logprob, int32_t* alt_id, float* alt_logprob);
 /* cw_time_score_head's fused forms (stop = 0 / 1) with k alternatives per row; k = 0 times the plain forms in the same loop.  */
 int32_t cw_time_score_head_top(cw_ctx* ctx, int32_t M, int32_t k, int32_t stop, int32_t iters, float* avg_ms);
+/* The ENT forms (cw_set_score_entropy).  cw_test_score_head_entropy: the head with entropy [M] beside its outputs; stop_logprob
+ * non-null joins the STOP form (eos / timestamp_begin as cw_test_score_head_stop), k > 0 the TOPK form (alt_id / alt_logprob as
+ * cw_test_score_head_top; NULL with k = 0); logits_out and the guard rows as there.  cw_test_score_rows_entropy: the row kernel
+ * likewise, k = 0 .. CW_TOP_LOGPROBS_MAX.  cw_time_score_head_entropy: cw_time_score_head_top's loop with the ENT form on.   */
+int32_t cw_test_score_head_entropy(cw_ctx* ctx, int32_t M, int32_t D, int32_t V, const float* x, const float* ln_g, const float* ln_b,
+                                   const float* embed, const int32_t* targets, int32_t eos, int32_t timestamp_begin, int32_t k,
+                                   float* logprob, int32_t* top_id, float* top_logprob, float* stop_logprob, int32_t* alt_id,
+                                   float* alt_logprob, float* entropy, float* logits_out);
+int32_t cw_test_score_rows_entropy(cw_ctx* ctx, int32_t rows, int32_t V, int32_t ldv, const float* logits, const int32_t* targets,
+                                   int32_t k, int32_t eos, int32_t timestamp_begin, float* logprob, int32_t* top_id,
+                                   float* top_logprob, float* stop_logprob, int32_t* alt_id, float* alt_logprob, float* entropy);
+int32_t cw_time_score_head_entropy(cw_ctx* ctx, int32_t M, int32_t k, int32_t stop, int32_t iters, float* avg_ms);
 /* Decoder prompt prefill kernels (16-bit engines) against a host reference: cw_test_prefill_gemm runs the prefill GEMM over
  * fragment-major packed W with epilogue mode 0 = 16-bit store, 2 = f32 residual add (out: residual in, result out), 3 = erf GELU
  * (K % 32 == 0, N % 16 == 0); cw_test_prefill_attention the flash attention of the prefill (causal over n_keys >= n_q keys, or
@@ -820,6 +869,14 @@ int32_t cw_test_sample_top_logprobs(cw_ctx* ctx, int32_t nb, const float* logits
                                     int32_t min_new_tokens, int32_t max_length, float temperature, uint64_t seed,
                                     const uint64_t* row_streams, const int32_t* forced_tok, int32_t k, int32_t* choice_out,
                                     float* lp_out, int32_t* top_id_out, float* top_lp_out);
+/* cw_test_sample_logprobs with cw_set_token_entropy on for this call as well: ent_out [nb] = the entropy stored for sequence
+ * index t.  k = 0 .. CW_TOP_LOGPROBS_MAX: with k > 0 the alternatives ride along as in cw_test_sample_top_logprobs (top_id_out /
+ * top_lp_out [nb][k]; NULL is accepted for k = 0).  The pad columns of the logits rows hold +75 during the call.  The context's
+ * own settings are restored afterwards.                                                                                       */
+int32_t cw_test_sample_entropy(cw_ctx* ctx, int32_t nb, const float* logits, const int32_t* ids, int32_t t, int32_t n_prompt,
+                               int32_t min_new_tokens, int32_t max_length, float temperature, uint64_t seed,
+                               const uint64_t* row_streams, const int32_t* forced_tok, int32_t k, int32_t* choice_out,
+                               float* lp_out, float* ent_out, int32_t* top_id_out, float* top_lp_out);
 /* ... and with a cw_set_sequence_bias table for this call only (n_seq == 0: none), the context's own table put back
  * afterwards.  proc_lp_out [nb] = the processed-score log-probability term of the token written at t, i.e. what the step adds to
  * the sum behind cw_get_avg_logprobs (0 where it adds nothing).                                                              */

@@ -11,6 +11,8 @@ geometry: large-v3 shape, aligned synthetic weights, --rows x 30 s clips residen
                     of every row and stores log_softmax(raw)[token]): step_*_logprobs_ms, off and on in the same build
   --top-logprobs K [K ...]  (with --token-logprobs) ... and once more per K with cw_set_top_logprobs(K) on top (the sampler also
                     selects the K best raw logits of every row): step_*_top<K>_ms, all in the same build and process
+  --token-entropy   (with --token-logprobs) ... and once more with cw_set_token_entropy on top (the sampler also keeps the centred
+                    sum of every row and stores its predictive entropy): step_*_entropy_ms, same build and process
   --sequence-bias N [N ...]  ... and once more per N with a cw_set_sequence_bias table of N entries (half single tokens, half
                     two-token sequences) whose last tokens are spread over the 16 vocabulary slices of the sampler, and once with
                     all N in one slice: step_*_bias<N>_ms / step_*_bias<N>_one_slice_ms, against the table-free figure of the same
@@ -37,6 +39,7 @@ def main():
     ap.add_argument("--token-logprobs", action="store_true"); ap.add_argument("--no-fallback-round", action="store_true")
     ap.add_argument("--top-logprobs", type=int, nargs="+", default=[], metavar="K")
     ap.add_argument("--sequence-bias", type=int, nargs="+", default=[], metavar="N")
+    ap.add_argument("--token-entropy", action="store_true")
     a = ap.parse_args()
     if a.top_logprobs and not a.token_logprobs:
         ap.error("--top-logprobs needs --token-logprobs (cw_set_top_logprobs shares its normaliser)")
@@ -55,11 +58,15 @@ def main():
 
     def steps():
         eng.decode(prompt, 3 + T, min_new_tokens=T)
-    variants = [("", False, 0)] + ([("_logprobs", True, 0)] if a.token_logprobs else []) + [(f"_top{k}", True, k) for k in a.top_logprobs]
-    for tag, on, k in variants:
+    if a.token_entropy and not a.token_logprobs:
+        ap.error("--token-entropy needs --token-logprobs (cw_set_token_entropy shares its running sums)")
+    variants = [("", False, 0, False)] + ([("_logprobs", True, 0, False)] if a.token_logprobs else []) + \
+               [(f"_top{k}", True, k, False) for k in a.top_logprobs] + ([("_entropy", True, 0, True)] if a.token_entropy else [])
+    for tag, on, k, ent in variants:
         eng.set_token_logprobs(on)
         if on:
             eng.set_top_logprobs(k)
+            eng.set_token_entropy(ent)
         for name, temp in (("greedy", 0.0), ("sampling", a.temperature)):
             eng.set_sampling(temp, 1, streams)
             ms, split = timed(eng, steps, a.reps)

@@ -31,6 +31,7 @@ def main():
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--only-forward", action="store_true", help="one prefill score call only (for a kernel trace)")
     ap.add_argument("--top-logprobs", type=int, default=0, help="alternatives per scored position (0 .. 8)")
+    ap.add_argument("--entropy", action="store_true", help="also time the head's ENT form (cw_time_score_head_entropy) against the plain one")
     a = ap.parse_args()
     g, v = syn.large_v3_geometry()
     spec = syn.model_spec(g, v, n_align=15)
@@ -85,6 +86,10 @@ def main():
     if top:                                  # the TOPK forms of the head against k = 0, timed by the same loop in this process
         out["head_top_ms"] = {str(M): {form: {str(k): round(eng.time_score_head_top(M, k, stop, 10), 3) for k in (0, 1, 8)}
                                        for form, stop in (("plain", False), ("stop", True))} for M in (1032, 5160)}
+    if a.entropy:                            # [without, with] the ENT form, timed by the same loop in this process
+        out["head_entropy_ms"] = {str(M): {form: {f"k{k}": [round(eng.time_score_head_top(M, k, stop, 10), 3),
+                                                            round(eng.time_score_head_entropy(M, k, stop, 10), 3)] for k in (0, 8)}
+                                           for form, stop in (("plain", False), ("stop", True))} for M in (1024, 5120)}
     print(json.dumps(out))
     eng.close()
 
