@@ -180,6 +180,7 @@ _SIGS = {
     "cw_test_gemm_fp8": (_I, [_P, _I, _I, _I, _P, _P, _P, _I, _P]),
     "cw_test_gemm_epi": (_I, [_P, C.POINTER(GemmEpiArgs)]),
     "cw_test_rownorm": (_I, [_P, _I, _I, _I, _P, _P, _P, _P, _P, _P]),
+    "cw_test_mel_stages": (_I, [_P, _I, _P, _P, _P]),
     "cw_test_gemv": (_I, [_P, _I, _I, _I, _P, _P, _P, _P, _P, _I, _P]),
     "cw_has_experiments": (_I, []),
     "cw_test_skinny": (_I, [_P, _I, _I, _I, _I, _P, _P, _P, _I, _I, _P, _P]),

@@ -120,7 +120,10 @@ static int create_impl(cw_ctx* c) {
     const cw_model_desc& d = c->d;
     const int D = d.d_model, H = d.n_heads, F = d.ffn_dim, V = d.vocab_size, Bm = d.max_batch;
     if (D != H * 64) return fail(c, CW_ERR_INVALID, "head_dim must be 64 (d_model=%d heads=%d)", D, H);
-    if (D % 128 || F % 128 || d.n_mels % 64) return fail(c, CW_ERR_INVALID, "d_model/ffn must be multiples of 128, n_mels of 64");
+    if (D % 128 || F % 128) return fail(c, CW_ERR_INVALID, "d_model/ffn must be multiples of 128");
+    // the mel stage runs at any filter count its launcher takes (80 mels: the checkpoints before large-v3); the encoder's conv1 is an
+    // implicit GEMM over n_mels-wide rows and needs a multiple of 64: its weight is refused when it is loaded, and so is cw_encode
+    if (d.n_mels < 1 || d.n_mels > 256) return fail(c, CW_ERR_INVALID, "n_mels=%d outside 1 .. 256", d.n_mels);
     if (Bm < 1 || Bm > 64) return fail(c, CW_ERR_INVALID, "max_batch must be in 1..64");
     if (d.max_target_positions > 512) return fail(c, CW_ERR_INVALID, "max_target_positions > 512 unsupported");
     HIPCHK(c, hipSetDevice(c->device));
@@ -556,6 +559,7 @@ static int load_tensor_impl(cw_ctx* c, const char* name, const float* data, cons
     if (s == "model.encoder.conv1.weight" || s == "model.encoder.conv2.weight") {
         const bool first = s == "model.encoder.conv1.weight";
         const int C = first ? NM : D;
+        if (C % 64) return fail(c, CW_ERR_INVALID, "tensor %s: the encoder needs n_mels to be a multiple of 64 (n_mels=%d runs the mel stage only)", name, NM);
         CWCHK(c, expect((size_t)D * C * 3));
         std::vector<float> re((size_t)D * 3 * C);  // [O][C][3] -> [O][3][C]
         for (int o = 0; o < D; ++o)
@@ -727,6 +731,7 @@ static int enc8_quantise(cw_ctx* c);
 int32_t cw_encode(cw_ctx* c, int32_t nb, const int32_t* item, const int32_t* seek, const int32_t* n_frames) {
     const int D = c->d.d_model, H = c->d.n_heads, F = c->d.ffn_dim, NM = c->d.n_mels, S = CW_N_CTX;
     if (nb < 1 || nb > c->Bm) return fail(c, CW_ERR_INVALID, "nb=%d out of range", nb);
+    if (NM % 64) return fail(c, CW_ERR_INVALID, "encode: the encoder needs n_mels to be a multiple of 64 (n_mels=%d runs the mel stage only)", NM);
     std::vector<int> off(nb), val(nb);
     for (int i = 0; i < nb; ++i) {
         if (item[i] < 0 || item[i] >= c->Bm || seek[i] < 0 || n_frames[i] < 0 || seek[i] + n_frames[i] > CW_N_FRAMES)

@@ -23,6 +23,25 @@ int32_t cw_test_set_option(const char* name, int32_t value) {
     return cw_sw::set_test_option(name, value) ? CW_OK : CW_ERR_INVALID;   // the launcher switches: the process table
 }
 
+// cw_test_mel_stages: what the last cw_mel / cw_mel_resident left in d_logspec, d_gmax and d_feats_tm for items 0 .. B-1 (copies
+// only).  The clip maximum is decoded here exactly as mel.hip: ordered_to_float decodes it.
+int32_t cw_test_mel_stages(cw_ctx* c, int32_t B, float* logspec, float* gmax, float* feats_tm) {
+    if (B < 1 || B > c->Bm) return fail(c, CW_ERR_INVALID, "test_mel_stages: B=%d out of range (max_batch %d)", B, c->Bm);
+    const size_t n = (size_t)B * CW_N_FRAMES * c->d.n_mels;
+    HIPCHK(c, hipStreamSynchronize(c->st));
+    if (logspec) HIPCHK(c, hipMemcpy(logspec, c->d_logspec, n * 4, hipMemcpyDeviceToHost));
+    if (gmax) {
+        std::vector<unsigned int> u(B);
+        HIPCHK(c, hipMemcpy(u.data(), c->d_gmax, (size_t)B * 4, hipMemcpyDeviceToHost));
+        for (int b = 0; b < B; ++b) {
+            const unsigned int bits = (u[b] & 0x80000000u) ? (u[b] & 0x7fffffffu) : ~u[b];
+            memcpy(gmax + b, &bits, 4);
+        }
+    }
+    if (feats_tm) CWCHK(c, download_T(c, c->d_feats_tm, 0, feats_tm, n));
+    return CW_OK;
+}
+
 int32_t cw_test_gemm(cw_ctx* c, int32_t M, int32_t N, int32_t K, const float* A, const float* W, const float* bias,
                      int32_t gelu, float* out) {
     void *dA = nullptr, *dW = nullptr, *dO = nullptr; float* dB = nullptr;

@@ -30,6 +30,10 @@ __device__ inline float ordered_to_float(unsigned int u) {
     return __uint_as_float((u & 0x80000000u) ? (u & 0x7fffffffu) : ~u);
 }
 
+// log10(max(x, 1e-10)) in f32.  At the clamp the value is the constant -10: the correctly rounded log10 of the f32 nearest to 1e-10
+// (torch's CPU log10 returns it, so silence is -10 and its features -1.5 in the reference); the device log10f returns the f32 below.
+__device__ inline float log10_clamped(float x) { return x > 1e-10f ? log10f(x) : -10.0f; }
+
 __global__ __launch_bounds__(256) void mel_kernel(MelTables tb, const float* __restrict__ pcm, int n_mels,
                                                   float* __restrict__ logspec_tm, unsigned int* __restrict__ gmax) {
     // Real 400-point DFT with both symmetries folded in (4x fewer FMAs than the direct form):
@@ -128,7 +132,7 @@ __global__ __launch_bounds__(256) void mel_kernel(MelTables tb, const float* __r
         for (int f = 0; f < MEL_FR; ++f) {
             const int frame = f0 + f;
             if (frame < N_FRAMES) {
-                const float lv = log10f(fmaxf((float)acc[f], 1e-10f));
+                const float lv = log10_clamped((float)acc[f]);
                 logspec_tm[((size_t)b * N_FRAMES + frame) * n_mels + tid] = lv;
                 lmax = fmaxf(lmax, lv);
             }
@@ -313,7 +317,7 @@ __global__ __launch_bounds__(256) void mel_mfma_kernel(MelTables tb, const float
         for (int f = 0; f < 16; ++f) {
             const int frame = f0 + fh * 16 + f;
             if (frame < N_FRAMES) {
-                const float lv = log10f(fmaxf((float)macc[f], 1e-10f));
+                const float lv = log10_clamped((float)macc[f]);
                 logspec_tm[((size_t)b * N_FRAMES + frame) * n_mels + m] = lv;
                 lmax = fmaxf(lmax, lv);
             }

@@ -53,7 +53,8 @@ bool set_test_option(const char* option, int value) {
         {"gemv_loop", "no_gemv_loop", true, INT_MIN, -1},    {"comb_rowgroups", "comb_no_rowgroups", true, INT_MIN, -1},
         {"gemm_w128", "gemm_w128", false, INT_MIN, -1},      {"beam_topk_1block", "beam_topk_1block", false, INT_MIN, -1},
         {"mt_variant", "mt_variant", false, -2, -2},         {"gemm256_min_tiles", "gemm256_min_tiles", false, 1, 0},
-        {"cross_valu", "cross_valu", false, 0, 0},           {"cross_per_row", "cross_per_row", false, 0, 0}};
+        {"cross_valu", "cross_valu", false, 0, 0},           {"cross_per_row", "cross_per_row", false, 0, 0},
+        {"mel_valu", "mel_valu", false, INT_MIN, -1}};
     for (const auto& o : opts) {
         if (strcmp(option, o.option)) continue;
         const Row* r = find(o.field);

@@ -1048,6 +1048,17 @@ class Engine:
         self._chk(self.lib.cw_test_rownorm(self.ctx, int(mode), rows, d, _ptr(x), _ptr(g), _ptr(b), _ptr(out), _ptr(out8), _ptr(scale)))
         return out if mode == 0 else (out8, scale)
 
+    def test_mel_stages(self, B: int):
+        """The mel stage's buffers after mel / mel_resident over B items (cw_test_mel_stages; copies only): logspec [B][3000]
+        [n_mels] (log10 before the clip floor), gmax [B] (the decoded clip maximum) and feats_tm [B][3000][n_mels] (the time-major
+        features conv1 reads, engine type -> float32)."""
+        B = int(B)
+        raw = np.empty((B, N.N_FRAMES, self.spec.n_mels), np.float32)
+        gmax = np.empty(B, np.float32)
+        tm = np.empty((B, N.N_FRAMES, self.spec.n_mels), np.float32)
+        self._chk(self.lib.cw_test_mel_stages(self.ctx, B, _ptr(raw), _ptr(gmax), _ptr(tm)))
+        return raw, gmax, tm
+
     def test_gemv(self, x, W, bias=None, ln=None, gelu=False):
         x = np.ascontiguousarray(x, np.float32); W = np.ascontiguousarray(W, np.float32)
         b = None if bias is None else np.ascontiguousarray(bias, np.float32)

@@ -609,6 +609,11 @@ int32_t cw_test_gemm_epi(cw_ctx* ctx, const cw_test_gemm_epi_args* args);
  * 2 belong to the 16-bit engines.  The outputs are in / out like those of cw_test_gemm_epi.                                    */
 int32_t cw_test_rownorm(cw_ctx* ctx, int32_t mode, int32_t rows, int32_t d, const float* x, const float* gamma, const float* beta,
                         float* out, uint8_t* out8, float* scale);
+/* The mel stage's own buffers as cw_mel / cw_mel_resident left them for items 0 .. B-1 (csrc/mel.hip).  Copies only: nothing is
+ * launched and nothing is written on the device.  logspec [B][3000][n_mels] f32: log10(max(mel, 1e-10)) before the clip floor;
+ * gmax [B]: the clip maximum, decoded from the ordered-uint form the atomicMax runs on; feats_tm [B][3000][n_mels]: the time-major
+ * features conv1 reads, converted from the engine's activation type to f32.  Any of the three may be NULL.                       */
+int32_t cw_test_mel_stages(cw_ctx* ctx, int32_t B, float* logspec, float* gmax, float* feats_tm);
 int32_t cw_test_gemv(cw_ctx* ctx, int32_t Mb, int32_t N, int32_t K, const float* x, const float* W,
                      const float* bias, const float* ln_g, const float* ln_b, int32_t gelu, float* out);
 /* One skinny-M decoder projection (17..64 rows; csrc/skinny.hip) on caller-supplied rows, 16-bit engines.  mode 0: LayerNorm

@@ -57,6 +57,17 @@ def test_environment_parses_as_before(driver, name):
     assert not diff and len(got) == len(case["want"]), diff
 
 
+@pytest.mark.parametrize("env,back", [({}, 0), ({"CW_MEL_VALU": "1"}, 1)])
+def test_mel_valu_option_edits_its_field_alone_and_returns_to_the_environment(driver, env, back):
+    """the option added after the fixture was recorded (tests/test_gpu_mel.py selects mel_kernel with it): 1 / 0 set the field, a
+    negative value copies it back from the environment, nothing else moves"""
+    blocks = driver(env, "mel_valu=1", "mel_valu=0", "mel_valu=-1")
+    assert [h for h, _ in blocks[1:]] == ["mel_valu=1 ok", "mel_valu=0 ok", "mel_valu=-1 ok"]
+    assert [g["mel_valu"] for _, g in blocks] == [back, 1, 0, back]
+    for _, g in blocks[1:]:
+        assert dict(g, mel_valu=back) == blocks[0][1]
+
+
 @pytest.mark.parametrize("i", range(len(GOLDEN["options"])))
 def test_options_edit_the_process_table(driver, i):
     case = GOLDEN["options"][i]
